@@ -1,21 +1,24 @@
 #!/usr/bin/env python3
 """bench.py -- particle-steps/sec of the SPH step on MI355X (see BASELINE.json / DESIGN.md section 5).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--runup R] [--workload C3|C2|C1|C4|C5] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--runup R] [--workload C3|C2|C1|C4|C5] [--full [--no-cpu] [--no-pmc]]
+                    [--dump-outputs DIR]
 
 N = 1: the whole-domain context runs BASELINE config 3 (dam-break, 16,777,216 particles, 512^3 grid, dt 5e-7)
 with the state resident in HBM.  The timed state is a FLOWING dam: the same initial lattice is first stepped R
 times on the device (state preparation, not timed; at dt = 5e-7 nothing crosses a cell face for the first ~1000
 steps), so that in the timed window every phase of the reference's step does work -- cell hash, sort, cell table,
 density, force, collision, integrate (SPH/particleSystem.cpp:773-795).  Then W warm-up steps and K timed steps
-between two device syncs.  `value` is that figure; `value_at_rest` (fresh lattice) and `value_full_sort` (the same
-flowing state with the radix sort forced every step) are reported next to it.
+between two device syncs.  `value` is that figure.  A plain run stops there: it prints the result line and, with
+`--dump-outputs DIR`, writes the state the last timed step left (see dump_outputs).  `--full` adds everything else:
+`value_at_rest` (fresh lattice), `value_full_sort` (the same flowing state with the radix sort forced every step), the
+per-phase times, the roofline block and the CPU baseline.
 N > 1 (launched by torch.distributed.run, one rank per GPU): z-slabs, see gpufluidsimulator_amd/slab.py.  The default is
 STRONG scaling of the same config 3 (BASELINE.json's metric: "dam-break 16M particles, 1/2/4/8 MI355X"); `--scaling weak`
 gives every GPU its own 16.7 M particles, `--workload C4` is BASELINE config 4.  `--gpus N --one-gpu --transport local`
 rehearses the N-rank step as N threads on one GPU.
 
-One JSON line on stdout (rank 0).  `roofline` prices the dominant kernel (the fused force+collision+integrate
+One JSON line on stdout (rank 0).  With --full, `roofline` prices the dominant kernel (the fused force+collision+integrate
 traversal) by its ALGORITHMIC bytes over its mean device time measured with HIP events on the library's stream
 during the flowing steps; `cpu_baseline` times the reference's own OpenMP code (oracle/_ref, kind "reference") and
 the C restatement (kind "port") on the host cores, on a bounded sample (a 64^3-particle dam break).
@@ -279,6 +282,23 @@ def _phases(ctx, dt, steps):
     return {k: v / max(nst, 1) for k, v in ph.items()}
 
 
+DUMP_SAMPLE = 1 << 20          # particles written by --dump-outputs: 8 float32 each, 32 MiB in all
+DUMP_SEED = 20240607
+
+
+def dump_outputs(ctx, n, out_dir):
+    """What a caller of the timed path receives after its last step: the state by creation index (position, velocity,
+    density, pressure).  More than DUMP_SAMPLE particles: a fixed, seeded sample of them (the same rows on every run),
+    in creation-index order."""
+    st = ctx.download(want=("pos", "vel", "density", "pressure"))
+    if n > DUMP_SAMPLE:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+        st = {k: v[rows] for k, v in st.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in st.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
+
+
 def run_single(args):
     cfg = ic.CONFIGS[args.workload]
     n = cfg["lattice"][0] * cfg["lattice"][1] * cfg["lattice"][2]
@@ -320,6 +340,11 @@ def run_single(args):
                    "skips": s1["skips"] - s0["skips"],
                    "movers_per_step": (s1["movers_total"] - s0["movers_total"]) / max(args.steps, 1),
                    "last_movers": s1["last_movers"]}
+    if args.dump_outputs:
+        dump_outputs(ctx, n, args.dump_outputs)
+    if not args.full:                       # a plain run: the headline only
+        ctx.close()
+        return res
     # per-phase device times (HIP events on the library's stream) from a second, instrumented pass over the same regime
     res["phases_ms"] = _phases(ctx, dt, args.steps)
     st = ctx.download(want=("density", "vel") if args.no_cpu else ("density", "vel", "pos"))
@@ -355,70 +380,10 @@ def run_single(args):
     return res
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)       # SURVEY.md 8(d): >= 20 warm-up, >= 100 timed steps
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--runup", type=int, default=None,
-                    help="steps of state preparation before the warm-up (default: 6000 for C3 -- a flowing dam)")
-    ap.add_argument("--workload", default="C3", choices=sorted(ic.CONFIGS))
-    ap.add_argument("--scaling", default="strong", choices=["weak", "strong"],
-                    help="--gpus N > 1: strong (default) = the SAME particles on every N -- BASELINE's metric is 'dam-break 16M "
-                         "particles, 1/2/4/8 MI355X', i.e. --workload C3 (--workload C4 = config 4, 67,108,864 particles); "
-                         "weak = 16.7 M particles PER GPU")
-    ap.add_argument("--transport", default="rccl", choices=["rccl", "host", "local"],
-                    help="--gpus N > 1: rccl = the library's own RCCL communicator (one rank per GPU); host = host-staged "
-                         "messages (processes over gloo, or threads); local = device-to-device copies between the streams of "
-                         "one process (--one-gpu without a launcher)")
-    ap.add_argument("--lattice", default=None, help="slab path: nx,ny,nz instead of the workload's lattice (e.g. one rank's "
-                                                    "eighth of C3: --force-slab --lattice 256,256,32)")
-    ap.add_argument("--rebalance-every", type=int, default=500, help="slab path: re-balancing check every so many run-up steps")
-    ap.add_argument("--precision", default="f32", choices=["f32", "mixed"],
-                    help="mixed = BASELINE config 5's arithmetic (fp32 state, packed-fp16 pair arithmetic and per-row sums in "
-                         "the density pass): a separate dtype line, never the fp32 headline")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc passes that measure roofline.traffic for this run")
-    ap.add_argument("--pmc-child", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("--pmc-slab", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("--pmc-device", type=int, default=0, help=argparse.SUPPRESS)
-    ap.add_argument("--cpu-budget", type=float, default=24.0, help="seconds of host time for the cpu_baseline probe (four legs)")
-    ap.add_argument("--protocol", type=int, default=3, choices=[1, 3],
-                    help="slab path: 3 = MIGRANTS / HALO A / HALO B per step; 1 = the one-message step (two ghost layers, ghost "
-                         "densities recomputed locally: sph_slab_set_protocol)")
-    ap.add_argument("--force-slab", action="store_true", help="run the z-slab path even with one rank (testing)")
-    ap.add_argument("--periodic-z", action="store_true",
-                    help="with --force-slab: ONE slab between its own periodic images (loop transport) -- a middle rank's whole step, "
-                         "halo work included, on one GPU; default lattice 256,256,32 (an eighth of C3)")
-    ap.add_argument("--early-force", default="auto", choices=["auto", "on", "off"],
-                    help="slab path (--gpus N, --periodic-z): sph_slab_set_early_force; auto = the rule a real run applies to its pings (on unless a group takes < 12 us and a halo-A message < 45 us)")
-    ap.add_argument("--link-gbs", type=float, default=153.0, help="--periodic-z: bandwidth a message is held back for (0: no hold)")
-    ap.add_argument("--link-latency-us", type=float, default=10.0, help="--periodic-z: latency a message is held back for")
-    ap.add_argument("--one-gpu", action="store_true",
-                    help="rehearsal of the multi-rank path on a one-GPU box: every rank uses device 0.  Without a launcher the "
-                         "N ranks are N THREADS of this process (--transport local or host; a GPU box admits at most 6 "
-                         "processes on its card); under torch.distributed.run they are processes (--transport host)")
-    args = ap.parse_args()
-    if args.pmc_child:
-        return pmc_child(args)
-    rank, world, local = _dist_env()
-    if args.gpus > 1 and world == 1 and "RANK" not in os.environ and not args.one_gpu:
-        # called without a launcher: start one rank per GPU as child processes (nothing has touched the GPU yet)
-        import subprocess
-        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-               "--master-addr", "127.0.0.1", "--master-port", os.environ.get("MASTER_PORT", "29533"),
-               os.path.abspath(__file__)] + sys.argv[1:]
-        sys.exit(subprocess.call(cmd))
-    if args.gpus > 1 or world > 1 or args.force_slab:
-        from gpufluidsimulator_amd import slab
-        return slab.bench_main(args)
-    strict_flow = args.runup is None                       # the default configuration must be a flowing state
-    if args.runup is None:
-        args.runup = DEFAULT_RUNUP[args.workload]
-
-    r = run_single(args)
+def full_fields(args, r, value):
+    """`--full`: the per-phase times, the roofline block, the full-sort and at-rest figures and the CPU baseline of a
+    single-GPU run (run_single measured them after the timed steps)."""
     n, cfg, phases_ms = r["n"], r["cfg"], r["phases_ms"]
-    value = n * args.steps / r["wall"]
     t_force, t_dens, t_sort = phases_ms["force"] * 1e-3, phases_ms["dens"] * 1e-3, phases_ms["sort"] * 1e-3
     achieved = BYTES_PER_PARTICLE["force_fused"] * n / t_force / 1e9
     # HBM traffic of the dominant kernel: PMC counters cannot be read from inside this process; the figure is the one
@@ -461,24 +426,7 @@ def main():
                                 "this command; a constant of an earlier run, not of this process")}
         except Exception:
             issue = None
-    # a flowing state: no sort of the timed window was skipped, particles changed cell in it, and over the last 1000
-    # run-up steps at least 1e-3 N of them did so per step (the dam falls as a lattice, so cell changes come in bursts:
-    # a 20-step window can sit between two of them)
-    flow_ok = (r["sort"]["skips"] == 0 and r["sort"]["movers_per_step"] >= 1e-4 * n
-               and r["runup_tail"]["movers_per_step"] >= 1e-3 * n)
     out = {
-        "metric": "particle-steps/sec", "value": value, "unit": "particle-steps/s", "n_gpus": 1,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": r["wall"] / args.steps * 1e3,
-        # the N = 1 point of the strong-scaling series BASELINE's metric names (the same 16.7 M particles on 1/2/4/8 GPUs)
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-        "dtype": "f32" if args.precision == "f32" else "f32 state + packed-f16 density pairs (config 5's arithmetic: an option, slower than fp32 on gfx950)", "data": "synthetic",
-        "config": {"workload": f"dam-break {args.workload}: {cfg['lattice'][0]}x{cfg['lattice'][1]}x{cfg['lattice'][2]} "
-                               f"= {n} particles, grid {cfg['grid'][0]}^3, box {cfg['box'][0]}, dt 5e-7, jittered lattice"
-                               f"{' (BASELINE config 4 on one GPU: the N = 1 point of --scaling strong)' if args.workload == 'C4' else ''}, "
-                               f"FLOWING: timed after {args.runup} run-up steps on the device (+{args.warmup} warm-up)",
-                   "particles": n, "grid": list(cfg["grid"]), "parallelism": "1 GPU, whole domain",
-                   "state": "flow", "runup_steps": args.runup, "runup_seconds": r["runup_s"],
-                   "runup_last_1000_steps": r["runup_tail"]},
         # `achieved` / `peak` / `frac` are the contract's HBM figure (algorithmic bytes over the launch time); `bound` names
         # what the evidence says binds the kernel: fp32 VALU instruction issue (`issue`, `valu`), not bandwidth
         "roofline": {"bound": "valu-issue", "kernel": "k_force<force+collision+integrate>", "achieved": achieved,
@@ -499,11 +447,7 @@ def main():
                      "sort_phase": {"achieved": BYTES_PER_PARTICLE["sort_merge"] * n / max(t_sort, 1e-9) / 1e9,
                                     "unit": "GB/s", "avg_ms": phases_ms["sort"],
                                     "frac": BYTES_PER_PARTICLE["sort_merge"] * n / max(t_sort, 1e-9) / 1e9 / HBM_PEAK_GBS}},
-        # the sustained figure of the regime: the last 1000 run-up steps between two device syncs (cell changes come
-        # in bursts -- whole lattice layers cross a face together -- and a 100-step window can sit in a lull)
-        "value_sustained": (n * r["runup_tail"]["steps"] / r["runup_tail"]["wall_s"]) if r["runup_tail"]["wall_s"] else None,
-        "ms_per_step_sustained": r["runup_tail"]["ms_per_step"],
-        "phases_ms": phases_ms, "sort": r["sort"], "flowing": flow_ok, "finite": r["finite"], "vmax": r["vmax"],
+        "phases_ms": phases_ms, "finite": r["finite"], "vmax": r["vmax"],
         "value_full_sort": n * args.steps / r["wall_full_sort"],
         "ms_per_step_full_sort": r["wall_full_sort"] / args.steps * 1e3, "phases_ms_full_sort": r["phases_ms_full_sort"],
         "value_at_rest": n * args.steps / r["wall_rest"], "ms_per_step_at_rest": r["wall_rest"] / args.steps * 1e3,
@@ -517,6 +461,109 @@ def main():
         cb = cpu_baseline(budget_s=args.cpu_budget, headline=(cfg, pos_f, vel_f, label))
         out["cpu_baseline"] = cb
         out["gpu_over_cpu"] = value / cb["value"]
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=100)       # SURVEY.md 8(d): >= 20 warm-up, >= 100 timed steps
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--runup", type=int, default=None,
+                    help="steps of state preparation before the warm-up (default: 6000 for C3 -- a flowing dam)")
+    ap.add_argument("--workload", default="C3", choices=sorted(ic.CONFIGS))
+    ap.add_argument("--scaling", default="strong", choices=["weak", "strong"],
+                    help="--gpus N > 1: strong (default) = the SAME particles on every N -- BASELINE's metric is 'dam-break 16M "
+                         "particles, 1/2/4/8 MI355X', i.e. --workload C3 (--workload C4 = config 4, 67,108,864 particles); "
+                         "weak = 16.7 M particles PER GPU")
+    ap.add_argument("--transport", default="rccl", choices=["rccl", "host", "local"],
+                    help="--gpus N > 1: rccl = the library's own RCCL communicator (one rank per GPU); host = host-staged "
+                         "messages (processes over gloo, or threads); local = device-to-device copies between the streams of "
+                         "one process (--one-gpu without a launcher)")
+    ap.add_argument("--lattice", default=None, help="slab path: nx,ny,nz instead of the workload's lattice (e.g. one rank's "
+                                                    "eighth of C3: --force-slab --lattice 256,256,32)")
+    ap.add_argument("--rebalance-every", type=int, default=500, help="slab path: re-balancing check every so many run-up steps")
+    ap.add_argument("--precision", default="f32", choices=["f32", "mixed"],
+                    help="mixed = BASELINE config 5's arithmetic (fp32 state, packed-fp16 pair arithmetic and per-row sums in "
+                         "the density pass): a separate dtype line, never the fp32 headline")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: also measure what the headline does not need -- per-phase times and the roofline block, the "
+                         "same state with the full radix sort, the dam at rest, the rocprofv3 --pmc passes and the CPU baseline "
+                         "(a plain run sets up, warms up, times the K steps and prints the result line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="N = 1: write the state the last timed step left (pos, vel, density, pressure by creation index; a "
+                         f"fixed seeded sample of {DUMP_SAMPLE} particles when there are more) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-pmc", action="store_true",
+                    help="with --full: skip the rocprofv3 --pmc passes that measure roofline.traffic for this run")
+    ap.add_argument("--pmc-child", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--pmc-slab", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--pmc-device", type=int, default=0, help=argparse.SUPPRESS)
+    ap.add_argument("--cpu-budget", type=float, default=24.0, help="seconds of host time for the cpu_baseline probe (four legs)")
+    ap.add_argument("--protocol", type=int, default=3, choices=[1, 3],
+                    help="slab path: 3 = MIGRANTS / HALO A / HALO B per step; 1 = the one-message step (two ghost layers, ghost "
+                         "densities recomputed locally: sph_slab_set_protocol)")
+    ap.add_argument("--force-slab", action="store_true", help="run the z-slab path even with one rank (testing)")
+    ap.add_argument("--periodic-z", action="store_true",
+                    help="with --force-slab: ONE slab between its own periodic images (loop transport) -- a middle rank's whole step, "
+                         "halo work included, on one GPU; default lattice 256,256,32 (an eighth of C3)")
+    ap.add_argument("--early-force", default="auto", choices=["auto", "on", "off"],
+                    help="slab path (--gpus N, --periodic-z): sph_slab_set_early_force; auto = the rule a real run applies to its pings (on unless a group takes < 12 us and a halo-A message < 45 us)")
+    ap.add_argument("--link-gbs", type=float, default=153.0, help="--periodic-z: bandwidth a message is held back for (0: no hold)")
+    ap.add_argument("--link-latency-us", type=float, default=10.0, help="--periodic-z: latency a message is held back for")
+    ap.add_argument("--one-gpu", action="store_true",
+                    help="rehearsal of the multi-rank path on a one-GPU box: every rank uses device 0.  Without a launcher the "
+                         "N ranks are N THREADS of this process (--transport local or host; a GPU box admits at most 6 "
+                         "processes on its card); under torch.distributed.run they are processes (--transport host)")
+    args = ap.parse_args()
+    if args.pmc_child:
+        return pmc_child(args)
+    rank, world, local = _dist_env()
+    if args.gpus > 1 and world == 1 and "RANK" not in os.environ and not args.one_gpu:
+        # called without a launcher: start one rank per GPU as child processes (nothing has touched the GPU yet)
+        import subprocess
+        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
+               "--master-addr", "127.0.0.1", "--master-port", os.environ.get("MASTER_PORT", "29533"),
+               os.path.abspath(__file__)] + sys.argv[1:]
+        sys.exit(subprocess.call(cmd))
+    if args.gpus > 1 or world > 1 or args.force_slab:
+        if args.dump_outputs:
+            sys.exit("bench: --dump-outputs is an option of the single-GPU path (--gpus 1)")
+        from gpufluidsimulator_amd import slab
+        return slab.bench_main(args)
+    strict_flow = args.runup is None                       # the default configuration must be a flowing state
+    if args.runup is None:
+        args.runup = DEFAULT_RUNUP[args.workload]
+
+    r = run_single(args)
+    n, cfg = r["n"], r["cfg"]
+    value = n * args.steps / r["wall"]
+    # a flowing state: no sort of the timed window was skipped, particles changed cell in it, and over the last 1000
+    # run-up steps at least 1e-3 N of them did so per step (the dam falls as a lattice, so cell changes come in bursts:
+    # a 20-step window can sit between two of them)
+    flow_ok = (r["sort"]["skips"] == 0 and r["sort"]["movers_per_step"] >= 1e-4 * n
+               and r["runup_tail"]["movers_per_step"] >= 1e-3 * n)
+    out = {
+        "metric": "particle-steps/sec", "value": value, "unit": "particle-steps/s", "n_gpus": 1,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": r["wall"] / args.steps * 1e3,
+        # the N = 1 point of the strong-scaling series BASELINE's metric names (the same 16.7 M particles on 1/2/4/8 GPUs)
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+        "dtype": "f32" if args.precision == "f32" else "f32 state + packed-f16 density pairs (config 5's arithmetic: an option, slower than fp32 on gfx950)", "data": "synthetic",
+        "config": {"workload": f"dam-break {args.workload}: {cfg['lattice'][0]}x{cfg['lattice'][1]}x{cfg['lattice'][2]} "
+                               f"= {n} particles, grid {cfg['grid'][0]}^3, box {cfg['box'][0]}, dt 5e-7, jittered lattice"
+                               f"{' (BASELINE config 4 on one GPU: the N = 1 point of --scaling strong)' if args.workload == 'C4' else ''}, "
+                               f"FLOWING: timed after {args.runup} run-up steps on the device (+{args.warmup} warm-up)",
+                   "particles": n, "grid": list(cfg["grid"]), "parallelism": "1 GPU, whole domain",
+                   "state": "flow", "runup_steps": args.runup, "runup_seconds": r["runup_s"],
+                   "runup_last_1000_steps": r["runup_tail"]},
+        # the sustained figure of the regime: the last 1000 run-up steps between two device syncs (cell changes come
+        # in bursts -- whole lattice layers cross a face together -- and a 100-step window can sit in a lull)
+        "value_sustained": (n * r["runup_tail"]["steps"] / r["runup_tail"]["wall_s"]) if r["runup_tail"]["wall_s"] else None,
+        "ms_per_step_sustained": r["runup_tail"]["ms_per_step"],
+        "sort": r["sort"], "flowing": flow_ok,
+    }
+    if args.full:
+        out.update(full_fields(args, r, value))
     print(json.dumps(out), flush=True)
     if strict_flow and not flow_ok:
         sys.exit("bench: the timed window was not a flowing state (sort skipped or too few particles changed cell)")

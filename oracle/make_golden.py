@@ -12,6 +12,8 @@ have built oracle/_ref); the fixtures are what travels.
 """
 from __future__ import annotations
 
+import glob
+import io
 import os
 import sys
 
@@ -25,11 +27,49 @@ from oracle import refio  # noqa: E402
 OUT = os.path.join(ROOT, "tests", "golden")
 
 
+PART_BYTES = 960 * 1024         # a committed file stays under 1 MiB: larger fixtures go into <name>.partNN.npz files
+
+
+def _packed(a):
+    buf = io.BytesIO()
+    np.savez_compressed(buf, a=a)
+    return buf.getbuffer().nbytes
+
+
 def _save(name, **arrs):
+    """<name>.npz, or -- when that would exceed PART_BYTES -- <name>.part00.npz, .part01.npz, ... holding the arrays in
+    turn; an array too big for one part is cut into row blocks saved as <key>@0, <key>@1, ... (tests/conftest.py's
+    load_golden puts them back together)."""
     os.makedirs(OUT, exist_ok=True)
+    for old in glob.glob(os.path.join(OUT, name + ".part*.npz")) + glob.glob(os.path.join(OUT, name + ".npz")):
+        os.remove(old)
     path = os.path.join(OUT, name + ".npz")
     np.savez_compressed(path, **arrs)
-    print(f"{name}: {os.path.getsize(path) / 1024:.0f} KiB")
+    if os.path.getsize(path) <= PART_BYTES:
+        print(f"{name}: {os.path.getsize(path) / 1024:.0f} KiB")
+        return
+    os.remove(path)
+    pieces = []
+    for k, a in arrs.items():
+        a = np.asarray(a)
+        size = _packed(a)
+        if size <= PART_BYTES * 3 // 4 or a.ndim == 0:
+            pieces.append((k, a, size))
+            continue
+        blocks = -(-size // (PART_BYTES // 2))
+        for i, b in enumerate(np.array_split(a, blocks)):
+            pieces.append((f"{k}@{i}", b, _packed(b)))
+    parts, cur, used = [], {}, 0
+    for k, a, size in pieces:
+        if cur and used + size > PART_BYTES * 3 // 4:
+            parts.append(cur); cur, used = {}, 0
+        cur[k] = a; used += size
+    parts.append(cur)
+    for i, part in enumerate(parts):
+        pp = os.path.join(OUT, f"{name}.part{i:02d}.npz")
+        np.savez_compressed(pp, **part)
+        assert os.path.getsize(pp) <= PART_BYTES, pp
+    print(f"{name}: {len(parts)} parts")
 
 
 def _phase_arrays(recs, steps):
@@ -185,8 +225,31 @@ def gen_c2_flow():
           dt=np.float32(ic.DEFAULT_DT), runup=np.uint32(runup), lock_steps=np.uint32(lock), moved=np.uint32(moved), **arrs)
 
 
+# the cases of tests/test_oracle_vs_ref.py: (n_side, box, grid, jitter), three steps each with the reference's tie order
+VS_REF_CASES = ((8, 2.0, 32, True), (12, 4.0, 64, False), (20, 4.0, 64, True))
+
+
+def gen_vs_ref():
+    """What tests/test_oracle_vs_ref.py checks the oracle against: the reference's sorted order and state after each of
+    three steps from fresh lattices, and its state after five steps of a 10^3 lattice run with one and with four threads."""
+    arrs = {}
+    for n_side, box, grid, jitter in VS_REF_CASES:
+        tag = f"n{n_side}"
+        pos, vel = ic.dam_break_lattice((n_side,) * 3, (box,) * 3, jitter=jitter)
+        recs, _ = refio.run_ref(pos, vel, box, grid, ic.DEFAULT_DT, 3, phases=True)
+        arrs[f"{tag}_pos"], arrs[f"{tag}_vel"] = pos, vel
+        for s in (1, 2, 3):
+            arrs[f"{tag}_s{s}_order"] = recs[("order", s)]
+            arrs[f"{tag}_s{s}_state"] = recs[("state", s)]
+    pos, vel = ic.dam_break_lattice((10,) * 3, (2.0,) * 3, jitter=True)
+    for threads in (1, 4):
+        recs, _ = refio.run_ref(pos, vel, 2.0, 32, ic.DEFAULT_DT, 5, threads=threads)
+        arrs[f"threads{threads}_s5_state"] = recs[("state", 5)]
+    _save("oracle_vs_ref", **arrs)
+
+
 GENS = {"c1_flow": gen_c1_flow, "d24_flow": gen_d24_flow, "c1": gen_c1, "random": gen_random, "c2": gen_c2, "morton": gen_morton,
-        "c2_flow": gen_c2_flow}   # c2_flow: ~40-60 min of reference CPU time
+        "c2_flow": gen_c2_flow, "vs_ref": gen_vs_ref}   # c2_flow: ~40-60 min of reference CPU time
 
 if __name__ == "__main__":
     if not refio.available():

@@ -12,7 +12,7 @@ KRE='k_force|k_density|k_mm_move|k_cells_build|k_os_pass'
 pass() {   # name, counters...
   local name=$1; shift
   rocprofv3 --pmc "$@" --kernel-include-regex "$KRE" --output-format csv -d $OUT/$name -o p -- \
-      python bench.py --runup $RUNUP --steps $STEPS --warmup $WARM --no-cpu --no-pmc > $OUT/$name.log 2>&1
+      python bench.py --runup $RUNUP --steps $STEPS --warmup $WARM --full --no-cpu --no-pmc > $OUT/$name.log 2>&1
   echo "pass $name done: $(grep -c . $OUT/$name/*counter_collection.csv 2>/dev/null || echo 0) rows"
 }
 pass fetch FETCH_SIZE

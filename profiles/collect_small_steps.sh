@@ -10,7 +10,7 @@ set -e
 TAG=${1:-r06}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/prof_small; rm -rf $OUT; mkdir -p $OUT
-rocprofv3 --kernel-trace --output-format csv -d $OUT -o c2 -- python bench.py --workload C2 --steps 200 --warmup 20 --no-cpu --no-pmc > $OUT/c2.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT -o c2 -- python bench.py --workload C2 --steps 200 --warmup 20 --full --no-cpu --no-pmc > $OUT/c2.log 2>&1
 grep '^{"metric"' $OUT/c2.log > gpurun_out/${TAG}_c2_bench_under_rocprof.json
 python profiles/step_trace_summary.py $OUT/c2_kernel_trace.csv k_force 6020 200 gpurun_out/${TAG}_c2_flow_kernel_stats.csv > /dev/null
 rm -f $OUT/c2_kernel_trace.csv

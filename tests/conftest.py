@@ -1,4 +1,5 @@
 """pytest configuration: markers, paths, shared fixtures."""
+import glob
 import os
 import sys
 
@@ -20,7 +21,25 @@ def pytest_configure(config):
 
 
 def load_golden(name):
-    return np.load(os.path.join(GOLDEN, name + ".npz"))
+    """tests/golden/<name>.npz, or the parts a large fixture is stored in (<name>.partNN.npz, arrays cut into row
+    blocks <key>@0, <key>@1, ...: oracle/make_golden.py keeps every file under 1 MiB)."""
+    path = os.path.join(GOLDEN, name + ".npz")
+    if os.path.exists(path):
+        return np.load(path)
+    parts = sorted(glob.glob(os.path.join(GOLDEN, glob.escape(name) + ".part*.npz")))
+    assert parts, f"no fixture {name} in tests/golden"
+    out, blocks = {}, {}
+    for p in parts:
+        with np.load(p) as z:
+            for k in z.files:
+                if "@" in k:
+                    key, i = k.rsplit("@", 1)
+                    blocks.setdefault(key, {})[int(i)] = z[k]
+                else:
+                    out[k] = z[k]
+    for key, b in blocks.items():
+        out[key] = np.concatenate([b[i] for i in range(len(b))])
+    return out
 
 
 @pytest.fixture(scope="session")
