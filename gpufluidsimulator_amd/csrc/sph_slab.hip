@@ -35,7 +35,7 @@
 // size fixed in advance by a rule on the previous step's counts -- in the place of MIGRANTS; no HALO A (the receiver merges its own
 // leavers into its copy of the neighbour's layers: k_slab_unpack_ghosts_merge) and no HALO B (the density launch over "everything
 // that is not deep" also covers the inner ghost layers: same candidates, same order, the neighbour's bits).  DESIGN.md section 6
-// has both side by side and the measured table; `p1` marks that protocol's branches in slab_step_body.
+// has both side by side and the measured table; `p1` marks that protocol's branches in the step's phases (step_pre_wait ...).
 //
 // Equal keys at a cut keep the order of the whole-domain stable sort (what came up from below in front of the residents
 // of its cell, what came down from above behind them): an N-slab run has the bits of the one-context run.
@@ -255,7 +255,7 @@ __global__ __launch_bounds__(256) void k_slab_bounds_pack(const uint32_t* __rest
     }
 }
 
-// The early force launch (slab_step_body) ran before the owned range had its final start, so it left the next step's cell
+// The early force launch (step_pre_wait) ran before the owned range had its final start, so it left the next step's cell
 // keys in a scratch array by ABSOLUTE slot and marked no movers.  This pass, over whole 64-slot chunks of the final owned
 // range, puts the keys where the sort reads them and writes the chunks' mover bits (as the fused epilogue of k_force does).
 __global__ __launch_bounds__(256) void k_slab_early_finish(const uint32_t* __restrict__ key_abs, const uint32_t* __restrict__ keyS,
@@ -861,6 +861,16 @@ int loop_exchange(void* self, int tag, const void* send_lo, size_t send_lo_bytes
 }
 }  // namespace
 
+// One message group as the transport sees it: what goes to and comes from each neighbour (index 0: the lower, 1: the upper).
+// Built by the msg_* functions below, from which the step and its failure path (slab_fail) both take their groups.
+struct Msg {
+    int tag = 0;
+    const void* send[2] = {nullptr, nullptr};
+    size_t send_bytes[2] = {0, 0};
+    void* recv[2] = {nullptr, nullptr};
+    size_t recv_bytes[2] = {0, 0};
+};
+
 struct sph_slab {
     sph_ctx* c = nullptr;
     int rank = 0, world = 1;
@@ -880,7 +890,6 @@ struct sph_slab {
     bool hops_by_value = false;
     hipStream_t early = nullptr;         // the early force launch's own stream (behind the deep density by event): its tail then runs
     hipEvent_t ev_early_go = nullptr, ev_early_done = nullptr;   // beside the interior launch instead of in front of it
-    bool early_own_stream = true;        // SPH_SLAB_EARLY_STREAM=0: on the main stream (A/B)
     uint32_t gcap = 0, mcap = 0;         // halo / migrant capacity per side, in records
     uint32_t* d_lb = nullptr;            // DL_* words: layer bounds, deep-interior range, far counts, block counters (device)
     volatile uint32_t* h_lb = nullptr;   // HL_* words (pinned, mapped): what the step's one wait reads
@@ -921,7 +930,6 @@ struct sph_slab {
     int failed = 0;
     char fail_msg[512] = {0};
     bool transport_dead = false;
-    // what the step in flight has exchanged so far and what it still owes its neighbours (slab_fail)
     // ---- where a step's time goes (sph_slab_timing_get).  Host side, always on (three clock reads per step): the one
     //      wait, the host time in front of it (hash / sort / bounds / migrant exchange queued) and the whole call.
     //      Device side, only while sph_slab_timing_enable(1): an event pair around every transport call on the comm
@@ -934,16 +942,14 @@ struct sph_slab {
     struct Pending { int tag; hipEvent_t a, b; };
     std::vector<Pending> pending;
     std::vector<hipEvent_t> ev_free;
+    // The groups of the step in flight, in the order it posts them, and the next step's first group.  FIRST (MIGRANTS or ONE)
+    // is known before the step sends anything; the others are recorded from the headers, in numbers both ends of a link see.
+    enum { G_FIRST, G_REST, G_HALO_A, G_HALO_B, G_NEXT, G_COUNT };
     struct Progress {
-        bool mig_posted = false;                     // this step's first exchange (MIGRANTS, or ONE) has been handed to the transport
-        bool one = false;                            // the one-message protocol: that exchange carries one_s / one_r records behind the header
-        uint32_t one_s[2] = {0, 0}, one_r[2] = {0, 0};
-        bool next_known = false;                     // this step's headers are in: the NEXT step's one-message sizes follow from them
-        uint32_t next_s[2] = {0, 0}, next_r[2] = {0, 0};
-        bool headers = false, rest = false, halo_a = false, halo_b = false;
+        Msg group[G_COUNT];
+        bool posted[G_COUNT] = {};                   // handed to the transport (or nothing owed: an empty rest, no halos under ONE)
+        bool headers = false;                        // this step's headers are in: REST ... NEXT are recorded
         bool peer_dead[2] = {false, false};          // that neighbour's header said "abort": nothing more to or from it
-        uint32_t rest_s[2] = {0, 0}, rest_r[2] = {0, 0};   // records of the second migrant message (send, receive) per side
-        uint32_t h[2] = {0, 0}, g[2] = {0, 0};       // boundary-layer records I send / ghost records I receive per side
     } pg;
 };
 
@@ -973,35 +979,14 @@ void slab_free(sph_slab* s) {
     delete s;
 }
 
-// hand the four buffers to the transport.  Device transports get device pointers and the comm stream; host-staged
-// ones get pinned host copies (the comm stream is drained first: a test transport, not the product path).
 hipEvent_t slab_timing_event(sph_slab* s) {
     hipEvent_t e = nullptr;
     if (!s->ev_free.empty()) { e = s->ev_free.back(); s->ev_free.pop_back(); return e; }
     return hipEventCreate(&e) == hipSuccess ? e : nullptr;
 }
 
-int slab_exchange_raw(sph_slab* s, int tag, const void* send_lo, size_t send_lo_bytes, void* recv_lo, size_t recv_lo_bytes,
-                      const void* send_hi, size_t send_hi_bytes, void* recv_hi, size_t recv_hi_bytes);
-
-// the transport call of one message group; with sph_slab_timing_enable an event pair brackets it on the comm stream: the
-// time between the two is the group as the DEVICE sees it -- waiting for the neighbour's half included, which is the point
-int slab_exchange(sph_slab* s, int tag, const void* send_lo, size_t send_lo_bytes, void* recv_lo, size_t recv_lo_bytes,
-                  const void* send_hi, size_t send_hi_bytes, void* recv_hi, size_t recv_hi_bytes) {
-    hipEvent_t a = nullptr, b = nullptr;
-    if (s->time_groups && tag >= 1 && tag <= 9 && tag != SPH_TAG_RECUT_COUNTS && tag != SPH_TAG_RECUT) {
-        a = slab_timing_event(s); b = slab_timing_event(s);
-        if (a && b) SPH_HIP(hipEventRecord(a, s->comm));
-    }
-    const int rc = slab_exchange_raw(s, tag, send_lo, send_lo_bytes, recv_lo, recv_lo_bytes, send_hi, send_hi_bytes, recv_hi,
-                                     recv_hi_bytes);
-    if (a && b) {
-        if (rc == SPH_OK && hipEventRecord(b, s->comm) == hipSuccess) s->pending.push_back({tag, a, b});
-        else { s->ev_free.push_back(a); s->ev_free.push_back(b); }
-    }
-    return rc;
-}
-
+// hand the four buffers to the transport.  Device transports get device pointers and the comm stream; host-staged
+// ones get pinned host copies (the comm stream is drained first: a test transport, not the product path).
 int slab_exchange_raw(sph_slab* s, int tag, const void* send_lo, size_t send_lo_bytes, void* recv_lo, size_t recv_lo_bytes,
                       const void* send_hi, size_t send_hi_bytes, void* recv_hi, size_t recv_hi_bytes) {
     if (!s->has_lo || s->pg.peer_dead[0]) send_lo_bytes = recv_lo_bytes = 0;
@@ -1025,6 +1010,58 @@ int slab_exchange_raw(sph_slab* s, int tag, const void* send_lo, size_t send_lo_
     if (recv_lo_bytes) SPH_HIP(hipMemcpyAsync(recv_lo, s->stage_recv[0], recv_lo_bytes, hipMemcpyHostToDevice, s->comm));
     if (recv_hi_bytes) SPH_HIP(hipMemcpyAsync(recv_hi, s->stage_recv[1], recv_hi_bytes, hipMemcpyHostToDevice, s->comm));
     return SPH_OK;
+}
+
+// the transport call of one message group; with sph_slab_timing_enable an event pair brackets it on the comm stream: the
+// time between the two is the group as the DEVICE sees it -- waiting for the neighbour's half included, which is the point
+int slab_exchange(sph_slab* s, const Msg& m) {
+    hipEvent_t a = nullptr, b = nullptr;
+    if (s->time_groups && m.tag >= 1 && m.tag <= 9 && m.tag != SPH_TAG_RECUT_COUNTS && m.tag != SPH_TAG_RECUT) {
+        a = slab_timing_event(s); b = slab_timing_event(s);
+        if (a && b) SPH_HIP(hipEventRecord(a, s->comm));
+    }
+    const int rc = slab_exchange_raw(s, m.tag, m.send[0], m.send_bytes[0], m.recv[0], m.recv_bytes[0], m.send[1], m.send_bytes[1],
+                                     m.recv[1], m.recv_bytes[1]);
+    if (a && b) {
+        if (rc == SPH_OK && hipEventRecord(b, s->comm) == hipSuccess) s->pending.push_back({m.tag, a, b});
+        else { s->ev_free.push_back(a); s->ev_free.push_back(b); }
+    }
+    return rc;
+}
+
+// ---- the message groups.  A particle record is a position and a velocity; record 0 of a migrant buffer is the header.
+constexpr size_t REC = 2 * sizeof(float4);
+
+// records of a one-message group per side, from what the same link carried in the previous step: a margin of 1/16 + 1024
+// records, whole 64-record chunks (slab.py mirrors it: SlabSimulation.one_message_rows)
+uint32_t one_cap(uint32_t prev) { return (prev + prev / 16u + 1024u + 63u) & ~63u; }
+
+// a first group: the header and S_s / S_r records behind it per side (ONE: one_cap records; the re-cut's counts: none)
+Msg msg_first(const sph_slab* s, int tag, const uint32_t S_s[2], const uint32_t S_r[2]) {
+    return {tag, {s->mig_send[0], s->mig_send[1]}, {(1 + (size_t)S_s[0]) * REC, (1 + (size_t)S_s[1]) * REC},
+            {s->mig_recv[0], s->mig_recv[1]}, {(1 + (size_t)S_r[0]) * REC, (1 + (size_t)S_r[1]) * REC}};
+}
+// MIGRANTS: the header and the first MIG_INLINE leavers, a fixed size (the three-group step's first group)
+Msg msg_migrants(const sph_slab* s) {
+    const uint32_t inl = min(MIG_INLINE, s->mcap), S[2] = {inl, inl};
+    return msg_first(s, SPH_TAG_MIGRANTS, S, S);
+}
+// what did not fit a first group (MIGRANTS_REST, ONE_REST): n_s / n_r records right behind it in the same buffers
+Msg msg_rest(const Msg& first, const uint32_t n_s[2], const uint32_t n_r[2]) {
+    const char* const send[2] = {(const char*)first.send[0], (const char*)first.send[1]};
+    char* const recv[2] = {(char*)first.recv[0], (char*)first.recv[1]};
+    return {first.tag == SPH_TAG_ONE ? SPH_TAG_ONE_REST : SPH_TAG_MIGRANTS_REST,
+            {send[0] + first.send_bytes[0], send[1] + first.send_bytes[1]}, {n_s[0] * REC, n_s[1] * REC},
+            {recv[0] + first.recv_bytes[0], recv[1] + first.recv_bytes[1]}, {n_r[0] * REC, n_r[1] * REC}};
+}
+// h records out of each side's halo send buffer, g into its receive buffer (HALO A: boundary layer -> ghosts; the re-cut)
+Msg msg_halo(const sph_slab* s, int tag, const uint32_t h[2], const uint32_t g[2]) {
+    return {tag, {s->halo_send[0], s->halo_send[1]}, {h[0] * REC, h[1] * REC}, {s->halo_recv[0], s->halo_recv[1]}, {g[0] * REC, g[1] * REC}};
+}
+// HALO B: the (density, pressure) of the same h / g particles
+Msg msg_dens(const sph_slab* s, const uint32_t h[2], const uint32_t g[2]) {
+    return {SPH_TAG_HALO_B, {s->dens_send[0], s->dens_send[1]}, {h[0] * sizeof(float2), h[1] * sizeof(float2)},
+            {s->dens_recv[0], s->dens_recv[1]}, {g[0] * sizeof(float2), g[1] * sizeof(float2)}};
 }
 
 // comm stream continues after everything queued on main so far / main after comm
@@ -1064,7 +1101,7 @@ int after_comm(sph_slab* s) {
 // launchers use the context's stream: this runs them on the comm stream instead
 struct OnComm {
     sph_ctx* c; hipStream_t saved;
-    OnComm(sph_slab* s) : c(s->c), saved(s->c->stream) { c->stream = s->comm; }
+    OnComm(sph_slab* s, bool on = true) : c(s->c), saved(s->c->stream) { if (on) c->stream = s->comm; }
     ~OnComm() { c->stream = saved; }
 };
 
@@ -1117,27 +1154,58 @@ int slab_timing_collect(sph_slab* s) {
     return SPH_OK;
 }
 
-int slab_step_body(sph_slab* s, float dt) {
+// The step's state from phase to phase (slab_step_body).  Counts per side: _lo towards rank - 1, _hi towards rank + 1.
+struct Step {
+    float dt = 0.f;
+    std::chrono::steady_clock::time_point t_begin, t_waited;
+    bool p1 = false;                                 // the one-message step (see step_pre_wait)
+    uint32_t S_s[2] = {0, 0}, S_r[2] = {0, 0};       // ... its records behind the header per side (send, receive)
+    uint32_t layer = 0, n0 = 0, off0 = 0, G = 0;     // cells per layer; the owned range right after the sort; ghost layers per side
+    bool deep_valid = false;                         // the deep interior's density launched before the wait still holds
+    bool early_launched = false, early_pending = false;   // the early force launch: queued / the main stream has not joined it yet
+    uint32_t early_done_v = 0, early_grid_slots = 0;      // (the sequence number of that join: hop_mark) ; its grid
+    // ---- from the headers (step_headers)
+    uint32_t lb0 = 0, lb1 = 0, lb2 = 0, lb3 = 0, deep_lo = 0, deep_hi = 0, near_lo = 0, near_hi = 0, early_lo = 0, early_hi = 0;
+    uint32_t m_lo = 0, m_hi = 0, far_lo = 0, far_hi = 0;          // my leavers, and the far ones among them
+    uint32_t in_lo = 0, in_hi = 0, far_in_lo = 0, far_in_hi = 0;  // the arrivals, and the far ones among them
+    uint32_t own_lo = 0, own_hi = 0;                              // my boundary layers (the arrivals included: step_settle)
+    uint32_t peer_own_lo = 0, peer_own_hi = 0, n2p_lo = 0, n2p_hi = 0;   // the neighbours' boundary and second layers
+    uint32_t tot_s[2] = {0, 0}, tot_r[2] = {0, 0};                // records either end of a link packed: the next ONE step's sizes
+    bool early_halo = false;                         // no arrivals: the halo work goes to the comm stream at once
+    // ---- the ghosts and the slot ranges of the passes (step_ghosts)
+    uint32_t n = 0, g_lo = 0, g_hi = 0, h_lo = 0, h_hi = 0, a = 0, b = 0;
+    bool need_deep_event = false;
+    uint32_t deep_v = 0;
+};
+
+// whoever re-sorts or re-writes the ping-pong arrays on the main stream must come behind the early launch
+int join_early(sph_slab* s, Step& st) {
+    if (!st.early_pending) return SPH_OK;
+    const int rc = hop_wait(s, HOP_EARLY_MAIN, s->c->stream, s->ev_early_done, st.early_done_v);
+    if (rc == SPH_OK) st.early_pending = false;
+    return rc;
+}
+
+// ---- before the wait: sort, bounds and leavers, the deep density, the early force launch, the first group ----------------
+int step_pre_wait(sph_slab* s, Step& st) {
     sph_ctx* c = s->c;
     int rc;
-    const auto t_begin = std::chrono::steady_clock::now();
-    s->pg = sph_slab::Progress();
-    const size_t rec = 2 * sizeof(float4);
-    // The ONE-MESSAGE step (sph_slab_set_protocol(s, 1); two ghost layers): header, leavers and the residents of the two layers
-    // next to each cut travel in ONE message per neighbour, before the host knows any count -- so its size is fixed by a rule on
-    // the counts both ends saw in the PREVIOUS step's headers (a margin of 1/16 + 1024 records; what does not fit follows in an
-    // exact second message after the wait: the first step of a burst).  The first step after a create / re-cut has no such
-    // counts and runs the three-group protocol.
-    const bool p1 = s->protocol == 1 && s->one_ready && s->world > 1;
-    auto one_cap = [](uint32_t prev) { return (prev + prev / 16u + 1024u + 63u) & ~63u; };
-    const uint32_t S_s[2] = {p1 && s->has_lo ? one_cap(s->one_prev_s[0]) : 0u, p1 && s->has_hi ? one_cap(s->one_prev_s[1]) : 0u};
-    const uint32_t S_r[2] = {p1 && s->has_lo ? one_cap(s->one_prev_r[0]) : 0u, p1 && s->has_hi ? one_cap(s->one_prev_r[1]) : 0u};
-    if (p1) {
-        SPH_REQUIRE(S_s[0] <= s->msg_cap && S_s[1] <= s->msg_cap && S_r[0] <= s->msg_cap && S_r[1] <= s->msg_cap, SPH_E_CAPACITY,
-                    "rank %d: the one-message step would carry %u/%u (send) %u/%u (receive) records; the buffers hold %u", s->rank, S_s[0], S_s[1],
-                    S_r[0], S_r[1], s->msg_cap);
-        s->pg.one = true;
-        for (int k = 0; k < 2; k++) { s->pg.one_s[k] = S_s[k]; s->pg.one_r[k] = S_r[k]; }
+    // The ONE-MESSAGE step (sph_slab::protocol): its size is fixed before the host knows any count, by one_cap on the counts
+    // both ends saw in the PREVIOUS step's headers (what does not fit follows in an exact second message after the wait: the
+    // first step of a burst).  The first step after a create / re-cut has no such counts and runs the three-group protocol.
+    st.p1 = s->protocol == 1 && s->one_ready && s->world > 1;
+    for (int k = 0; k < 2; k++) {
+        const bool has = k == 0 ? s->has_lo : s->has_hi;
+        st.S_s[k] = st.p1 && has ? one_cap(s->one_prev_s[k]) : 0u;
+        st.S_r[k] = st.p1 && has ? one_cap(s->one_prev_r[k]) : 0u;
+    }
+    s->pg.group[sph_slab::G_FIRST] = msg_migrants(s);
+    if (st.p1) {
+        // (checked before FIRST becomes the ONE group: a rank that fails here sends its abort header at the MIGRANTS size)
+        SPH_REQUIRE(st.S_s[0] <= s->msg_cap && st.S_s[1] <= s->msg_cap && st.S_r[0] <= s->msg_cap && st.S_r[1] <= s->msg_cap,
+                    SPH_E_CAPACITY, "rank %d: the one-message step would carry %u/%u (send) %u/%u (receive) records; the buffers hold %u",
+                    s->rank, st.S_s[0], st.S_s[1], st.S_r[0], st.S_r[1], s->msg_cap);
+        s->pg.group[sph_slab::G_FIRST] = msg_first(s, SPH_TAG_ONE, st.S_s, st.S_r);
     }
     rc = slab_check_device_flags(s); if (rc) return rc;
     // ---- hash + sort the owned particles (leavers end up at the two ends of the owned range) -----------------------
@@ -1150,202 +1218,195 @@ int slab_step_body(sph_slab* s, float dt) {
     rc = step_sort(c);
     c->owned_cells_in_bounds = false;
     if (rc) return rc;
-    const uint32_t layer = c->grid.g[0] * c->grid.g[1];
-    const uint32_t n0 = c->n, off0 = c->own_off;
+    st.layer = c->grid.g[0] * c->grid.g[1];
+    st.n0 = c->n; st.off0 = c->own_off;
     // ---- layer bounds, leavers and headers in ONE kernel; the comm stream ships the fixed-size part ------------------
     s->seq++;
-    // a few blocks: every block finds the bounds for itself, the leavers (few, at most mcap) are packed in a grid-stride loop;
-    // behind them the blocks that build the cell table of the owned slots when the sort left it pending (not on a skipped sort)
     // a few blocks (many when they also copy two layers): every block finds the bounds for itself, the leavers and residents are packed in
     // grid-stride loops; behind them the blocks that build the cell table of the owned slots when the sort left it pending (not on a skipped sort)
-    const uint32_t pack_blocks = p1 ? 128u : min(ceil_div(s->mcap, 256u), 16u), build_blocks = c->owned_cells_pending ? cells_build_blocks(n0) : 0u;
+    const uint32_t pack_blocks = st.p1 ? 128u : min(ceil_div(s->mcap, 256u), 16u), build_blocks = c->owned_cells_pending ? cells_build_blocks(st.n0) : 0u;
     c->owned_cells_pending = false;
-    hipLaunchKernelGGL(k_slab_bounds_pack, dim3(pack_blocks + build_blocks), dim3(256), 0, c->stream, c->keyS + off0, c->posi + off0,
-                       c->velr + off0, n0, off0, layer, s->mcap, c->grid, s->early_cap, s->d_lb, s->mig_send[0], s->mig_send[1], pack_blocks,
-                       c->keyS, c->cells, c->mm_count_host_dev + 1, c->ghost_layers, p1 ? 1u : 0u, s->gcap);
+    hipLaunchKernelGGL(k_slab_bounds_pack, dim3(pack_blocks + build_blocks), dim3(256), 0, c->stream, c->keyS + st.off0, c->posi + st.off0,
+                       c->velr + st.off0, st.n0, st.off0, st.layer, s->mcap, c->grid, s->early_cap, s->d_lb, s->mig_send[0], s->mig_send[1],
+                       pack_blocks, c->keyS, c->cells, c->mm_count_host_dev + 1, c->ghost_layers, st.p1 ? 1u : 0u, s->gcap);
     SPH_HIP(hipGetLastError());
     rc = after_main(s); if (rc) return rc;
     // ---- the density of the deep interior goes into the main stream's queue BEFORE the host waits: its slot range
     //      comes from device memory (k_slab_bounds_pack wrote it).  Layers >= 4 from either cut see neither ghosts nor
     //      arrivals (those land in the boundary layers), and no slot of them moves before the force pass.
-    const uint32_t G = c->ghost_layers;           // ghost layers per side: the owned layers are the local layers [G, zl - G)
-    bool deep_valid = c->grid.zl >= 2u * G + 7u;
-    if (deep_valid) {
+    st.G = c->ghost_layers;                       // ghost layers per side: the owned layers are the local layers [G, zl - G)
+    st.deep_valid = c->grid.zl >= 2u * st.G + 7u;
+    if (st.deep_valid) {
         PhaseTimer t(c, SPH_PH_DENS);
-        rc = launch_density_dev_range(c, s->d_lb + DL_DEEP, n0);
+        rc = launch_density_dev_range(c, s->d_lb + DL_DEEP, st.n0);
         if (rc) return rc;
     }
-    // ---- and behind it the fused force pass of the innermost layers (local layers [6, zl-6): every density they read is
-    //      the deep launch's), also from a range in device memory.  More work that needs nothing from a link: the main
-    //      stream stays busy while the migrant message, the host's wake-up and halo A are on their way.  The owned range
-    //      does not have its final start yet (leavers go, arrivals may be merged in front), so the launch leaves its keys by
-    //      ABSOLUTE slot in the sort's scratch keys and marks no movers; k_slab_early_finish does both once the start is
-    //      known.  A step whose arrivals take the pass over all particles throws the result away (every slot moves).
-    bool early_launched = false;
+    // ---- and behind it, on the early stream, the fused force pass of the innermost layers (local layers [6, zl-6): every
+    //      density they read is the deep launch's), also from a range in device memory.  More work that needs nothing from a
+    //      link: the device stays busy while the migrant message, the host's wake-up and halo A are on their way; its tail runs
+    //      beside the interior launch instead of in front of it.  The owned range does not have its final start yet (leavers
+    //      go, arrivals may be merged in front), so the launch leaves its keys by ABSOLUTE slot in the sort's scratch keys and
+    //      marks no movers; k_slab_early_finish does both once the start is known.  A step whose arrivals take the pass over
+    //      all particles throws the result away (every slot moves).
     // the grid: the range's size is on the device; the host sizes the launch from the LAST step's range plus a margin (a range
     // changes by a few slots a step) -- whatever a too small grid leaves out is computed by the interior launch below
-    const uint32_t early_grid_slots = s->early_span_known ? min(n0, ((s->early_span + s->early_span / 64u + 1023u) & ~255u)) : n0;
-    bool early_pending = false;          // the launch runs on its own stream: the main stream has not waited for it yet
-    uint32_t early_done_v = 0u;          // (the sequence number of that edge: hop_mark)
+    st.early_grid_slots = s->early_span_known ? min(st.n0, ((s->early_span + s->early_span / 64u + 1023u) & ~255u)) : st.n0;
     // "the last step's range was EMPTY" (layer 5 not inside the deep range, a sparse slab) is not "unknown": no launch then --
     // a full-size grid of blocks that leave at once, two events and a stream hop bought nothing, every step.  The bounds
     // kernel reports the range whether or not a launch used it, so the launch comes back one step after the range does.
     const bool early_empty = s->early_span_known && s->early_span == 0u;
-    if (deep_valid && s->early_force && s->world > 1 && c->grid.zl >= 2u * G + 11u && !early_empty) {          // (no neighbour, no latency to fill)
-        if (s->early_own_stream && s->early) {
-            uint32_t go;                                                    // behind the deep density
-            rc = hop_mark(s, HOP_MAIN_EARLY, c->stream, s->ev_early_go, &go); if (rc) return rc;
-            rc = hop_wait(s, HOP_MAIN_EARLY, s->early, s->ev_early_go, go); if (rc) return rc;
-            hipStream_t saved = c->stream;
-            c->stream = s->early;
-            { PhaseTimer t(c, SPH_PH_FORCE); rc = launch_force_dev_range(c, s->d_lb + DL_EARLY, early_grid_slots, dt); }
-            c->stream = saved;
-            if (rc) return rc;
-            rc = hop_mark(s, HOP_EARLY_MAIN, s->early, s->ev_early_done, &early_done_v); if (rc) return rc;
-            early_pending = true;
-        } else {
-            PhaseTimer t(c, SPH_PH_FORCE);
-            rc = launch_force_dev_range(c, s->d_lb + DL_EARLY, early_grid_slots, dt);
-            if (rc) return rc;
-        }
-        early_launched = true;
+    if (st.deep_valid && s->early_force && s->world > 1 && c->grid.zl >= 2u * st.G + 11u && !early_empty) {   // (no neighbour, no latency to fill)
+        uint32_t go;                                                    // behind the deep density
+        rc = hop_mark(s, HOP_MAIN_EARLY, c->stream, s->ev_early_go, &go); if (rc) return rc;
+        rc = hop_wait(s, HOP_MAIN_EARLY, s->early, s->ev_early_go, go); if (rc) return rc;
+        hipStream_t saved = c->stream;
+        c->stream = s->early;
+        { PhaseTimer t(c, SPH_PH_FORCE); rc = launch_force_dev_range(c, s->d_lb + DL_EARLY, st.early_grid_slots, st.dt); }
+        c->stream = saved;
+        if (rc) return rc;
+        rc = hop_mark(s, HOP_EARLY_MAIN, s->early, s->ev_early_done, &st.early_done_v); if (rc) return rc;
+        st.early_pending = true;
+        st.early_launched = true;
         s->early_launches++;
     }
-    // whoever re-sorts or re-writes the ping-pong arrays on the main stream must come behind the early launch
-    auto join_early = [&]() -> int {
-        if (early_pending) { const int rj = hop_wait(s, HOP_EARLY_MAIN, c->stream, s->ev_early_done, early_done_v); if (rj) return rj; early_pending = false; }
-        return SPH_OK;
-    };
-    struct JoinOnExit {                  // (an error return leaves the step half done: the next sort must still come behind the launch)
-        sph_slab* s; bool* pending; uint32_t* value;
-        ~JoinOnExit() { if (*pending) (void)hop_wait(s, HOP_EARLY_MAIN, s->c->stream, s->ev_early_done, *value); }
-    } join_on_exit{s, &early_pending, &early_done_v};
-    const uint32_t inl = min(MIG_INLINE, s->mcap);
-    const size_t mig_bytes = (size_t)(1 + inl) * rec;
-    s->pg.mig_posted = true;                                    // (also when the call fails: the transport is dead then)
-    if (p1) rc = slab_exchange(s, SPH_TAG_ONE, s->mig_send[0], (1 + (size_t)S_s[0]) * rec, s->mig_recv[0], (1 + (size_t)S_r[0]) * rec,
-                               s->mig_send[1], (1 + (size_t)S_s[1]) * rec, s->mig_recv[1], (1 + (size_t)S_r[1]) * rec);
-    else rc = slab_exchange(s, SPH_TAG_MIGRANTS, s->mig_send[0], mig_bytes, s->mig_recv[0], mig_bytes, s->mig_send[1], mig_bytes,
-                            s->mig_recv[1], mig_bytes);
-    if (rc) return rc;
+    s->pg.posted[sph_slab::G_FIRST] = true;                    // (also when the call fails: the transport is dead then)
+    rc = slab_exchange(s, s->pg.group[sph_slab::G_FIRST]); if (rc) return rc;
     hipLaunchKernelGGL(k_slab_post_headers, dim3(1), dim3(64), 0, s->comm, s->d_lb, s->has_lo ? s->mig_recv[0] : (float4*)nullptr,
                        s->has_hi ? s->mig_recv[1] : (float4*)nullptr, s->h_lb_dev, s->seq);
     SPH_HIP(hipGetLastError());
-    // ---- the one host wait of the step ---------------------------------------------------------------------------
-    s->t_pre.add(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_begin).count());
+    return SPH_OK;
+}
+
+// What this step still owes its neighbours -- the rest message, halo A, halo B -- and the next step's first group, in numbers
+// BOTH ends of a link see (mine in my header, the neighbour's in its header), clamped to the buffers: if this rank fails from
+// here on it still sends and takes exactly these (slab_fail), so that no neighbour is left waiting for a message.  The step
+// posts these same groups; the sizes it derives from its own counts for its kernels equal them once its checks have passed.
+void record_owed(sph_slab* s, const Step& st) {
+    sph_slab::Progress& g = s->pg;
+    auto umin = [](uint32_t x, uint32_t y) { return x < y ? x : y; };
+    const uint32_t inl0 = umin(MIG_INLINE, s->mcap);
+    const uint32_t mm[2] = {umin(st.m_lo, s->mcap), umin(st.m_hi, s->mcap)}, ii[2] = {umin(st.in_lo, s->mcap), umin(st.in_hi, s->mcap)};
+    const uint32_t own[2] = {st.own_lo, st.own_hi}, peer[2] = {st.peer_own_lo, st.peer_own_hi},
+                   fo[2] = {umin(st.far_lo, st.m_lo), umin(st.far_hi, st.m_hi)}, fi[2] = {umin(st.far_in_lo, st.in_lo), umin(st.far_in_hi, st.in_hi)},
+                   mraw[2] = {st.m_lo, st.m_hi}, iraw[2] = {st.in_lo, st.in_hi};
+    const bool any_rest = st.m_lo > inl0 || st.m_hi > inl0 || st.in_lo > inl0 || st.in_hi > inl0;
+    uint32_t rest_s[2], rest_r[2], h[2] = {0, 0}, gh[2] = {0, 0}, next_s[2], next_r[2];
+    for (int k = 0; k < 2; k++) {
+        const bool has = k == 0 ? s->has_lo : s->has_hi;
+        if (st.p1) {                  // all that can still be owed is the part of the one message that did not fit its fixed size
+            rest_s[k] = st.tot_s[k] > st.S_s[k] ? umin(st.tot_s[k], s->msg_cap) - st.S_s[k] : 0u;
+            rest_r[k] = st.tot_r[k] > st.S_r[k] ? umin(st.tot_r[k], s->msg_cap) - st.S_r[k] : 0u;
+        } else {
+            rest_s[k] = any_rest && mm[k] > inl0 ? mm[k] - inl0 : 0u;
+            rest_r[k] = any_rest && ii[k] > inl0 ? ii[k] - inl0 : 0u;
+            h[k] = has ? umin(own[k] + iraw[k] - fi[k], s->gcap) : 0u;
+            gh[k] = has ? umin(peer[k] + mraw[k] - fo[k], s->gcap) : 0u;
+        }
+        next_s[k] = one_cap(st.tot_s[k]); next_r[k] = one_cap(st.tot_r[k]);
+    }
+    g.group[sph_slab::G_REST] = msg_rest(g.group[sph_slab::G_FIRST], rest_s, rest_r);
+    g.posted[sph_slab::G_REST] = (rest_s[0] | rest_s[1] | rest_r[0] | rest_r[1]) == 0u;      // (nothing owed)
+    g.group[sph_slab::G_HALO_A] = msg_halo(s, SPH_TAG_HALO_A, h, gh);
+    g.group[sph_slab::G_HALO_B] = msg_dens(s, h, gh);
+    g.posted[sph_slab::G_HALO_A] = g.posted[sph_slab::G_HALO_B] = st.p1;    // (no such messages in this protocol)
+    // (the neighbours, for whom this step goes through, take their next step under the slab's protocol: a one-message step is
+    // sized from THIS step's headers, which both ends have)
+    if (s->protocol == 1 && next_s[0] <= s->msg_cap && next_s[1] <= s->msg_cap && next_r[0] <= s->msg_cap && next_r[1] <= s->msg_cap) {
+        const uint32_t ns[2] = {s->has_lo ? next_s[0] : 0u, s->has_hi ? next_s[1] : 0u};
+        const uint32_t nr[2] = {s->has_lo ? next_r[0] : 0u, s->has_hi ? next_r[1] : 0u};
+        g.group[sph_slab::G_NEXT] = msg_first(s, SPH_TAG_ONE, ns, nr);
+    } else {
+        g.group[sph_slab::G_NEXT] = msg_migrants(s);
+    }
+}
+
+// ---- the one host wait of the step; the headers' counts, their checks, the groups still owed; the rest message -----------
+int step_headers(sph_slab* s, Step& st) {
+    sph_ctx* c = s->c;
+    int rc;
+    s->t_pre.add(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - st.t_begin).count());
     rc = slab_wait_headers(s); if (rc) return rc;
-    const auto t_waited = std::chrono::steady_clock::now();
+    st.t_waited = std::chrono::steady_clock::now();
     s->pg.headers = true;
-    const uint32_t lb0 = s->h_lb[HL_LB], lb1 = s->h_lb[HL_LB + 1], lb2 = s->h_lb[HL_LB + 2], lb3 = s->h_lb[HL_LB + 3];
-    const uint32_t deep_lo = s->h_lb[HL_DEEP], deep_hi = s->h_lb[HL_DEEP + 1];
-    const uint32_t near_lo = s->h_lb[HL_NEAR], near_hi = s->h_lb[HL_NEAR + 1];     // first slot of layer 3 / of layer zl-3
-    const uint32_t early_lo = s->h_lb[HL_EARLY];                                       // what the early force launch covered:
-    const uint32_t early_hi = min(s->h_lb[HL_EARLY + 1], early_lo + early_grid_slots);      // its range, as far as its grid reached
-    s->early_span = s->h_lb[HL_EARLY + 1] - early_lo;
+    st.lb0 = s->h_lb[HL_LB]; st.lb1 = s->h_lb[HL_LB + 1]; st.lb2 = s->h_lb[HL_LB + 2]; st.lb3 = s->h_lb[HL_LB + 3];
+    st.deep_lo = s->h_lb[HL_DEEP]; st.deep_hi = s->h_lb[HL_DEEP + 1];
+    st.near_lo = s->h_lb[HL_NEAR]; st.near_hi = s->h_lb[HL_NEAR + 1];                  // first slot of layer 3 / of layer zl-3
+    st.early_lo = s->h_lb[HL_EARLY];                                                    // what the early force launch covered:
+    st.early_hi = min(s->h_lb[HL_EARLY + 1], st.early_lo + st.early_grid_slots);        // its range, as far as its grid reached
+    s->early_span = s->h_lb[HL_EARLY + 1] - st.early_lo;
     s->early_span_known = true;
-    const uint32_t far_lo = s->has_lo ? s->h_lb[HL_FAR] : 0u, far_hi = s->has_hi ? s->h_lb[HL_FAR + 1] : 0u;
-    const uint32_t m_lo = lb0, m_hi = n0 - lb3;
-    uint32_t own_lo = lb1 - lb0, own_hi = lb3 - lb2;
-    const uint32_t in_lo = s->has_lo ? s->h_lb[HL_HDR_LO] : 0u, peer_own_lo = s->has_lo ? s->h_lb[HL_HDR_LO + 1] : 0u;
-    const uint32_t in_hi = s->has_hi ? s->h_lb[HL_HDR_HI] : 0u, peer_own_hi = s->has_hi ? s->h_lb[HL_HDR_HI + 1] : 0u;
-    const uint32_t far_in_lo = s->has_lo ? s->h_lb[HL_HDR_LO + 2] : 0u, far_in_hi = s->has_hi ? s->h_lb[HL_HDR_HI + 2] : 0u;
+    st.far_lo = s->has_lo ? s->h_lb[HL_FAR] : 0u; st.far_hi = s->has_hi ? s->h_lb[HL_FAR + 1] : 0u;
+    st.m_lo = st.lb0; st.m_hi = st.n0 - st.lb3;
+    st.own_lo = st.lb1 - st.lb0; st.own_hi = st.lb3 - st.lb2;
+    st.in_lo = s->has_lo ? s->h_lb[HL_HDR_LO] : 0u; st.peer_own_lo = s->has_lo ? s->h_lb[HL_HDR_LO + 1] : 0u;
+    st.in_hi = s->has_hi ? s->h_lb[HL_HDR_HI] : 0u; st.peer_own_hi = s->has_hi ? s->h_lb[HL_HDR_HI + 1] : 0u;
+    st.far_in_lo = s->has_lo ? s->h_lb[HL_HDR_LO + 2] : 0u; st.far_in_hi = s->has_hi ? s->h_lb[HL_HDR_HI + 2] : 0u;
     // the SECOND layers next to the cuts (the one-message step's ghosts-of-ghosts; every header carries the counts, so that the
     // step after a three-group step can size its message): mine from the bounds, the neighbours' from their headers
     // (the same expressions as the kernel's header words: k_slab_bounds_pack)
-    const uint32_t n2_lo = s->has_lo ? max(near_lo - off0, lb1) - lb1 : 0u;
-    const uint32_t n2_hi = s->has_hi ? lb2 - min(near_hi - off0, lb2) : 0u;
-    const uint32_t n2p_lo = s->has_lo ? s->h_lb[HL_HDR2_LO] : 0u, n2p_hi = s->has_hi ? s->h_lb[HL_HDR2_HI] : 0u;
+    const uint32_t n2_lo = s->has_lo ? max(st.near_lo - st.off0, st.lb1) - st.lb1 : 0u;
+    const uint32_t n2_hi = s->has_hi ? st.lb2 - min(st.near_hi - st.off0, st.lb2) : 0u;
+    st.n2p_lo = s->has_lo ? s->h_lb[HL_HDR2_LO] : 0u; st.n2p_hi = s->has_hi ? s->h_lb[HL_HDR2_HI] : 0u;
     const uint32_t vfar_mine = s->h_lb[HL_VFAR], vfar_peer = (s->has_lo ? s->h_lb[HL_HDR2_LO + 1] : 0u) + (s->has_hi ? s->h_lb[HL_HDR2_HI + 1] : 0u);
     // records either end of a link packed this step: what the NEXT one-message step is sized from
-    const uint32_t tot_s[2] = {s->has_lo ? m_lo + own_lo + n2_lo : 0u, s->has_hi ? m_hi + own_hi + n2_hi : 0u};
-    const uint32_t tot_r[2] = {s->has_lo ? in_lo + peer_own_lo + n2p_lo : 0u, s->has_hi ? in_hi + peer_own_hi + n2p_hi : 0u};
-    {   // What this step still owes its neighbours -- the second migrant message, halo A, halo B -- in numbers BOTH ends of
-        // a link see (mine in my header, the neighbour's in its header), clamped to the buffers: if this rank fails from
-        // here on it still sends and takes exactly these (slab_fail), so that no neighbour is left waiting for a message.
-        sph_slab::Progress& g = s->pg;
-        auto umin = [](uint32_t x, uint32_t y) { return x < y ? x : y; };
-        g.peer_dead[0] = s->has_lo && s->h_lb[HL_HDR_LO + 3] != 0u;
-        g.peer_dead[1] = s->has_hi && s->h_lb[HL_HDR_HI + 3] != 0u;
-        const uint32_t inl0 = umin(MIG_INLINE, s->mcap);
-        const uint32_t mm[2] = {umin(m_lo, s->mcap), umin(m_hi, s->mcap)}, ii[2] = {umin(in_lo, s->mcap), umin(in_hi, s->mcap)};
-        const uint32_t own[2] = {own_lo, own_hi}, peer[2] = {peer_own_lo, peer_own_hi}, fo[2] = {umin(far_lo, m_lo), umin(far_hi, m_hi)},
-                       fi[2] = {umin(far_in_lo, in_lo), umin(far_in_hi, in_hi)}, mraw[2] = {m_lo, m_hi}, iraw[2] = {in_lo, in_hi};
-        const bool any_rest = m_lo > inl0 || m_hi > inl0 || in_lo > inl0 || in_hi > inl0;
-        for (int k = 0; k < 2; k++) {
-            const bool has = k == 0 ? s->has_lo : s->has_hi;
-            if (p1) {                     // all that can still be owed is the part of the one message that did not fit its fixed size
-                g.rest_s[k] = tot_s[k] > S_s[k] ? umin(tot_s[k], s->msg_cap) - S_s[k] : 0u;
-                g.rest_r[k] = tot_r[k] > S_r[k] ? umin(tot_r[k], s->msg_cap) - S_r[k] : 0u;
-                continue;
-            }
-            g.rest_s[k] = any_rest && mm[k] > inl0 ? mm[k] - inl0 : 0u;
-            g.rest_r[k] = any_rest && ii[k] > inl0 ? ii[k] - inl0 : 0u;
-            g.h[k] = has ? umin(own[k] + iraw[k] - fi[k], s->gcap) : 0u;
-            g.g[k] = has ? umin(peer[k] + mraw[k] - fo[k], s->gcap) : 0u;
-        }
-        if (p1) g.halo_a = g.halo_b = true;       // (no such messages in this protocol)
-        g.next_known = true;
-        for (int k = 0; k < 2; k++) { g.next_s[k] = one_cap(tot_s[k]); g.next_r[k] = one_cap(tot_r[k]); }
-        SPH_REQUIRE(!g.peer_dead[0] && !g.peer_dead[1], SPH_E_PEER, "rank %d: its %s neighbour reported a failure and stopped (step %llu)",
-                    s->rank, g.peer_dead[0] ? (g.peer_dead[1] ? "lower and upper" : "lower") : "upper", (unsigned long long)s->steps);
-    }
+    st.tot_s[0] = s->has_lo ? st.m_lo + st.own_lo + n2_lo : 0u; st.tot_s[1] = s->has_hi ? st.m_hi + st.own_hi + n2_hi : 0u;
+    st.tot_r[0] = s->has_lo ? st.in_lo + st.peer_own_lo + st.n2p_lo : 0u; st.tot_r[1] = s->has_hi ? st.in_hi + st.peer_own_hi + st.n2p_hi : 0u;
+    bool* dead = s->pg.peer_dead;                   // that neighbour's header said "abort"
+    dead[0] = s->has_lo && s->h_lb[HL_HDR_LO + 3] != 0u;
+    dead[1] = s->has_hi && s->h_lb[HL_HDR_HI + 3] != 0u;
+    record_owed(s, st);
+    SPH_REQUIRE(!dead[0] && !dead[1], SPH_E_PEER, "rank %d: its %s neighbour reported a failure and stopped (step %llu)",
+                s->rank, dead[0] ? (dead[1] ? "lower and upper" : "lower") : "upper", (unsigned long long)s->steps);
+    const uint32_t m_lo = st.m_lo, m_hi = st.m_hi, in_lo = st.in_lo, in_hi = st.in_hi;
     SPH_REQUIRE(s->has_lo || m_lo == 0, SPH_E_STATE, "rank %d: %u particles below the lowest slab", s->rank, m_lo);
     SPH_REQUIRE(s->has_hi || m_hi == 0, SPH_E_STATE, "rank %d: %u particles above the highest slab", s->rank, m_hi);
     // both ends of a link see the same numbers (mine in my header, the neighbour's in its header): they fail together
     SPH_REQUIRE(m_lo <= s->mcap && m_hi <= s->mcap && in_lo <= s->mcap && in_hi <= s->mcap, SPH_E_CAPACITY,
                 "rank %d: a burst of %u/%u leaving, %u/%u arriving particles exceeds the migrant capacity %u", s->rank, m_lo, m_hi,
                 in_lo, in_hi, s->mcap);
-    SPH_REQUIRE(far_in_lo <= in_lo && far_in_hi <= in_hi && far_lo <= m_lo && far_hi <= m_hi, SPH_E_STATE,
+    SPH_REQUIRE(st.far_in_lo <= in_lo && st.far_in_hi <= in_hi && st.far_lo <= m_lo && st.far_hi <= m_hi, SPH_E_STATE,
                 "rank %d: inconsistent migrant headers", s->rank);
     // capacity for what arrives, checked BEFORE anything is dropped or merged: on this error the owned range is still the
     // sorted range of this step
-    SPH_REQUIRE(n0 - m_lo - m_hi + in_lo + in_hi <= c->cap && (uint64_t)off0 + n0 - m_hi + in_lo + in_hi <= c->tot, SPH_E_CAPACITY,
-                "rank %d: %u + %u arriving particles exceed the capacity %u", s->rank, n0 - m_lo - m_hi, in_lo + in_hi, c->cap);
-    if (p1) {
+    SPH_REQUIRE(st.n0 - m_lo - m_hi + in_lo + in_hi <= c->cap && (uint64_t)st.off0 + st.n0 - m_hi + in_lo + in_hi <= c->tot, SPH_E_CAPACITY,
+                "rank %d: %u + %u arriving particles exceed the capacity %u", s->rank, st.n0 - m_lo - m_hi, in_lo + in_hi, c->cap);
+    if (st.p1) {
         SPH_REQUIRE(vfar_mine == 0u && vfar_peer == 0u, SPH_E_STATE,
                     "rank %d: %u leaving / %u arriving particles crossed more than TWO cell layers in one step: the one-message step keeps two "
                     "ghost layers (the three-group protocol takes such particles as long as they land in an interior layer)", s->rank,
                     vfar_mine, vfar_peer);
-        SPH_REQUIRE(tot_s[0] <= s->msg_cap && tot_s[1] <= s->msg_cap && tot_r[0] <= s->msg_cap && tot_r[1] <= s->msg_cap &&
-                        peer_own_lo + n2p_lo <= s->gcap && peer_own_hi + n2p_hi <= s->gcap, SPH_E_CAPACITY,
+        SPH_REQUIRE(st.tot_s[0] <= s->msg_cap && st.tot_s[1] <= s->msg_cap && st.tot_r[0] <= s->msg_cap && st.tot_r[1] <= s->msg_cap &&
+                        st.peer_own_lo + st.n2p_lo <= s->gcap && st.peer_own_hi + st.n2p_hi <= s->gcap, SPH_E_CAPACITY,
                     "rank %d: two layers of %u+%u / %u+%u residents (+ %u / %u leavers) exceed the message buffers (%u records) or the ghost "
-                    "capacity %u", s->rank, peer_own_lo, n2p_lo, peer_own_hi, n2p_hi, in_lo, in_hi, s->msg_cap, s->gcap);
-        // what did not fit the size fixed in advance (a burst: many more leavers than in the step before), exact
-        const sph_slab::Progress& g = s->pg;
-        if (g.rest_s[0] | g.rest_s[1] | g.rest_r[0] | g.rest_r[1]) {
-            rc = slab_exchange(s, SPH_TAG_ONE_REST, s->mig_send[0] + 2 * (1 + (size_t)S_s[0]), g.rest_s[0] * rec, s->mig_recv[0] + 2 * (1 + (size_t)S_r[0]),
-                               g.rest_r[0] * rec, s->mig_send[1] + 2 * (1 + (size_t)S_s[1]), g.rest_s[1] * rec,
-                               s->mig_recv[1] + 2 * (1 + (size_t)S_r[1]), g.rest_r[1] * rec);
-            if (rc) return rc;
-            s->one_rest_msgs++;
-        }
-        s->one_steps++;
-    } else
-    // ---- more leavers than ride in the fixed-size message: the rest, exact size (both ends know both counts) ----------
-    if (m_lo > inl || m_hi > inl || in_lo > inl || in_hi > inl) {
-        const size_t s_lo = m_lo > inl ? (size_t)(m_lo - inl) * rec : 0, s_hi = m_hi > inl ? (size_t)(m_hi - inl) * rec : 0;
-        const size_t r_lo = in_lo > inl ? (size_t)(in_lo - inl) * rec : 0, r_hi = in_hi > inl ? (size_t)(in_hi - inl) * rec : 0;
-        rc = slab_exchange(s, SPH_TAG_MIGRANTS_REST, s->mig_send[0] + 2 * (1 + inl), s_lo, s->mig_recv[0] + 2 * (1 + inl), r_lo,
-                           s->mig_send[1] + 2 * (1 + inl), s_hi, s->mig_recv[1] + 2 * (1 + inl), r_hi);
-        if (rc) return rc;
-        s->rest_msgs++;
+                    "capacity %u", s->rank, st.peer_own_lo, st.n2p_lo, st.peer_own_hi, st.n2p_hi, in_lo, in_hi, s->msg_cap, s->gcap);
     }
-    s->pg.rest = true;
+    // ---- what did not fit the first group, exact size (both ends know both counts): more leavers than ride in MIGRANTS, or
+    //      in the one-message step more records than its size fixed in advance (a burst: many more leavers than the step before)
+    if (!s->pg.posted[sph_slab::G_REST]) {
+        rc = slab_exchange(s, s->pg.group[sph_slab::G_REST]); if (rc) return rc;
+        s->pg.posted[sph_slab::G_REST] = true;
+        if (st.p1) s->one_rest_msgs++; else s->rest_msgs++;
+    }
+    if (st.p1) s->one_steps++;
+    return SPH_OK;
+}
+
+// ---- the leavers go, the arrivals become owned particles: inserted in place, or appended and merged, or a full re-sort ----
+int step_settle(sph_slab* s, Step& st) {
+    sph_ctx* c = s->c;
+    int rc;
+    const uint32_t G = st.G, m_lo = st.m_lo, m_hi = st.m_hi, in_lo = st.in_lo, in_hi = st.in_hi;
     // A step without arrivals (the usual one) hands the rest of the halo work to the COMM stream at once: the main
     // stream is busy with the deep density, and pack -> HALO A -> ghost unpack need nothing from it (the slices they
     // read have been final since the sort).  The ghosts are then in place when the deep density ends, and everything
     // that is left of the density pass is ONE launch.
-    const bool early_halo = deep_valid && in_lo == 0 && in_hi == 0;
+    st.early_halo = st.deep_valid && in_lo == 0 && in_hi == 0;
     // ---- drop the leavers (their cells hold nothing else until the ghosts arrive; the clearing must precede the
     //      ghost cells, so it runs on the stream that builds those) ---------------------------------------------------
     if (m_lo || m_hi) {
         if (c->cells_valid && c->cells_lo == c->own_off && c->cells_hi == c->own_off + c->n) {
-            if (early_halo) {
-                OnComm on(s);
-                rc = launch_cells_clear_2ranges(c, c->own_off, c->own_off + m_lo, c->own_off + c->n - m_hi, c->own_off + c->n);
-            } else {
-                rc = launch_cells_clear_2ranges(c, c->own_off, c->own_off + m_lo, c->own_off + c->n - m_hi, c->own_off + c->n);
-            }
+            OnComm on(s, st.early_halo);
+            rc = launch_cells_clear_2ranges(c, c->own_off, c->own_off + m_lo, c->own_off + c->n - m_hi, c->own_off + c->n);
             if (rc) return rc;
             c->cells_lo += m_lo;
             c->cells_hi -= m_hi;
@@ -1356,112 +1417,120 @@ int slab_step_body(sph_slab* s, float dt) {
     }
     // ---- arrivals become owned particles.  They land in the boundary layer next to the cut they crossed -- except the
     //      `far` ones the sender counted, which land deeper -- so the boundary counts are known without counting again ---
-    if (in_lo || in_hi) {
-        SPH_REQUIRE(c->n + in_lo + in_hi <= c->cap && c->own_off + c->n + in_lo + in_hi <= c->tot, SPH_E_CAPACITY,
-                    "rank %d: %u + %u arriving particles exceed the capacity %u", s->rank, c->n, in_lo + in_hi, c->cap);
-        rc = after_comm(s); if (rc) return rc;                  // the received records are in mig_recv
-        const bool merge = c->sort_merge && c->order_valid && c->cells_valid && c->cells_lo == c->own_off &&
-                           c->cells_hi == c->own_off + c->n;
-        const bool in_place = merge && far_in_lo == 0 && far_in_hi == 0 && in_lo <= SLAB_INSERT_MAX &&
-                              in_hi <= SLAB_INSERT_MAX && in_lo <= c->own_off && own_lo + own_hi <= c->n;
-        if (in_place) {
-            // only the two boundary layers are touched (see k_slab_insert): their cells leave the table, the merged
-            // layers come back from the scratch arrays, their cells are built again
-            for (int side = 0; side < 2; side++) {
-                const uint32_t k = side == 0 ? in_lo : in_hi;
-                if (!k) continue;
-                const uint32_t nl = side == 0 ? own_lo : own_hi;
-                const uint32_t l0 = side == 0 ? c->own_off : c->own_off + c->n - own_hi;
-                const uint32_t d0 = side == 0 ? l0 - k : l0;
-                rc = launch_cells_clear_range(c, l0, l0 + nl); if (rc) return rc;
-                hipLaunchKernelGGL(k_slab_insert, dim3(ceil_div(nl + k, 256u)), dim3(256), 0, c->stream, c->posi, c->velr, c->keyS, l0,
-                                   nl, s->mig_recv[side] + 2, k, c->grid, c->posi2, c->velr2, c->keyS2, d0,
-                                   side == 0 ? G : c->grid.zl - G - 1u, side == 0, s->h_lb_dev + HL_ERR);
-                hipLaunchKernelGGL(k_slab_copy_back, dim3(ceil_div(nl + k, 256u)), dim3(256), 0, c->stream, c->posi2, c->velr2, c->keyS2,
-                                   c->posi, c->velr, c->keyS, d0, nl + k);
-                SPH_HIP(hipGetLastError());
-                if (side == 0) c->own_off = d0;
-                c->n += k;
-                c->cells_lo = c->own_off; c->cells_hi = c->own_off + c->n;
-                rc = launch_cells_build_range(c, d0, d0 + nl + k); if (rc) return rc;
-            }
-            own_lo += in_lo;
-            own_hi += in_hi;
-            s->inserts++;
-            s->resorts++;
-        } else {
-            // behind the sorted owned range, with their cell keys: the merge path takes them in as movers without an old
-            // slot (one pass over the particles; a full radix sort when the merge path is switched off).  Every slot
-            // moves: the density of the deep interior is computed again with the rest.
-            // Equal keys must come out in the whole-domain order (see k_slab_insert): what came up from below in front
-            // of the residents of its cell, what came down from above behind them.  The merge takes that as a rule on
-            // the appended slots (launch_merge_arrivals: the first in_lo of them are `front` movers); the full radix
-            // sort is stable, so there the lower neighbour's particles are put physically IN FRONT of the owned range.
-            deep_valid = false;
-            rc = join_early(); if (rc) return rc;     // every slot moves, through the arrays the early launch writes
-            uint32_t appended = 0;
-            const bool front_slots = !merge && in_lo <= c->own_off;
-            for (int side = 0; side < 2; side++) {
-                const uint32_t cnt = side == 0 ? in_lo : in_hi;
-                if (!cnt) continue;
-                if (side == 0 && front_slots) {
-                    hipLaunchKernelGGL(k_slab_unpack, dim3(ceil_div(cnt, 256u)), dim3(256), 0, c->stream, s->mig_recv[0] + 2, cnt,
-                                       c->posi + c->own_off - cnt, c->velr + c->own_off - cnt, (uint32_t*)nullptr, c->grid, G,
-                                       s->h_lb_dev + HL_ERR);
-                    continue;
-                }
-                const uint32_t at = c->own_off + c->n + appended;
-                hipLaunchKernelGGL(k_slab_unpack, dim3(ceil_div(cnt, 256u)), dim3(256), 0, c->stream, s->mig_recv[side] + 2, cnt,
-                                   c->posi + at, c->velr + at, merge ? c->k0 + c->n + appended : (uint32_t*)nullptr, c->grid, G,
-                                   s->h_lb_dev + HL_ERR);
-                appended += cnt;
-            }
+    if (!(in_lo || in_hi)) return SPH_OK;
+    SPH_REQUIRE(c->n + in_lo + in_hi <= c->cap && c->own_off + c->n + in_lo + in_hi <= c->tot, SPH_E_CAPACITY,
+                "rank %d: %u + %u arriving particles exceed the capacity %u", s->rank, c->n, in_lo + in_hi, c->cap);
+    rc = after_comm(s); if (rc) return rc;                      // the received records are in mig_recv
+    const bool merge = c->sort_merge && c->order_valid && c->cells_valid && c->cells_lo == c->own_off &&
+                       c->cells_hi == c->own_off + c->n;
+    const bool in_place = merge && st.far_in_lo == 0 && st.far_in_hi == 0 && in_lo <= SLAB_INSERT_MAX &&
+                          in_hi <= SLAB_INSERT_MAX && in_lo <= c->own_off && st.own_lo + st.own_hi <= c->n;
+    if (in_place) {
+        // only the two boundary layers are touched (see k_slab_insert): their cells leave the table, the merged
+        // layers come back from the scratch arrays, their cells are built again
+        for (int side = 0; side < 2; side++) {
+            const uint32_t k = side == 0 ? in_lo : in_hi;
+            if (!k) continue;
+            const uint32_t nl = side == 0 ? st.own_lo : st.own_hi;
+            const uint32_t l0 = side == 0 ? c->own_off : c->own_off + c->n - st.own_hi;
+            const uint32_t d0 = side == 0 ? l0 - k : l0;
+            rc = launch_cells_clear_range(c, l0, l0 + nl); if (rc) return rc;
+            hipLaunchKernelGGL(k_slab_insert, dim3(ceil_div(nl + k, 256u)), dim3(256), 0, c->stream, c->posi, c->velr, c->keyS, l0,
+                               nl, s->mig_recv[side] + 2, k, c->grid, c->posi2, c->velr2, c->keyS2, d0,
+                               side == 0 ? G : c->grid.zl - G - 1u, side == 0, s->h_lb_dev + HL_ERR);
+            hipLaunchKernelGGL(k_slab_copy_back, dim3(ceil_div(nl + k, 256u)), dim3(256), 0, c->stream, c->posi2, c->velr2, c->keyS2,
+                               c->posi, c->velr, c->keyS, d0, nl + k);
             SPH_HIP(hipGetLastError());
-            if (merge) {
-                rc = launch_merge_arrivals(c, appended, in_lo); if (rc) return rc;   // the first in_lo came up from below
-            } else {
-                if (front_slots) { c->own_off -= in_lo; c->n += in_lo; }
-                c->n += appended;
-                c->keys_fresh = false;
-                c->order_valid = false;
-                c->stage = sph_ctx::ST_LOADED;
-                rc = step_hash(c); if (rc) return rc;
-                rc = step_sort(c); if (rc) return rc;
-            }
-            own_lo += in_lo - far_in_lo;          // the far ones went past the boundary layer
-            own_hi += in_hi - far_in_hi;
-            s->resorts++;
-            if (far_in_lo || far_in_hi) {
-                // rare (a particle crossed more than one cell layer in a step): count the layers again.  The neighbours
-                // size their ghost messages from the headers, so what the count must confirm is that every far arrival
-                // stayed clear of the OTHER boundary layer and of the ghost layers.
-                s->far_steps++;
-                if (getenv("SPH_SLAB_DEBUG"))
-                    fprintf(stderr, "[slab %d] step %llu: far arrivals %u/%u of %u/%u; leavers %u/%u (far %u/%u); bounds %u %u %u %u of %u; "
-                            "peer boundary %u/%u\n", s->rank, (unsigned long long)s->steps, far_in_lo, far_in_hi, in_lo, in_hi, m_lo, m_hi,
-                            far_lo, far_hi, lb0, lb1, lb2, lb3, n0, peer_own_lo, peer_own_hi);
-                hipLaunchKernelGGL(k_slab_bounds, dim3(1), dim3(64), 0, c->stream, c->keyS + c->own_off, c->n, layer, c->grid.zl, G,
-                                   s->d_lb, s->h_lb_dev);
-                SPH_HIP(hipGetLastError());
-                SPH_HIP(hipStreamSynchronize(c->stream));
-                s->host_waits++;
-                rc = slab_check_device_flags(s); if (rc) return rc;
-                const uint32_t r0 = s->h_lb[0], r1 = s->h_lb[1], r2 = s->h_lb[2], r3 = s->h_lb[3];
-                SPH_REQUIRE(r0 == 0u && r3 == c->n && r1 - r0 == own_lo && r3 - r2 == own_hi, SPH_E_STATE,
-                            "rank %d: a particle that crossed several cell layers in one step landed in a boundary or ghost "
-                            "layer (boundary layers %u/%u, expected %u/%u): the time step is too large for this slab width",
-                            s->rank, r1 - r0, r3 - r2, own_lo, own_hi);
-            }
+            if (side == 0) c->own_off = d0;
+            c->n += k;
+            c->cells_lo = c->own_off; c->cells_hi = c->own_off + c->n;
+            rc = launch_cells_build_range(c, d0, d0 + nl + k); if (rc) return rc;
         }
+        st.own_lo += in_lo;
+        st.own_hi += in_hi;
+        s->inserts++;
+        s->resorts++;
+        return SPH_OK;
     }
-    const uint32_t n = c->n;
+    // behind the sorted owned range, with their cell keys: the merge path takes them in as movers without an old
+    // slot (one pass over the particles; a full radix sort when the merge path is switched off).  Every slot
+    // moves: the density of the deep interior is computed again with the rest.
+    // Equal keys must come out in the whole-domain order (see k_slab_insert): what came up from below in front
+    // of the residents of its cell, what came down from above behind them.  The merge takes that as a rule on
+    // the appended slots (launch_merge_arrivals: the first in_lo of them are `front` movers); the full radix
+    // sort is stable, so there the lower neighbour's particles are put physically IN FRONT of the owned range.
+    st.deep_valid = false;
+    rc = join_early(s, st); if (rc) return rc;         // every slot moves, through the arrays the early launch writes
+    uint32_t appended = 0;
+    const bool front_slots = !merge && in_lo <= c->own_off;
+    for (int side = 0; side < 2; side++) {
+        const uint32_t cnt = side == 0 ? in_lo : in_hi;
+        if (!cnt) continue;
+        if (side == 0 && front_slots) {
+            hipLaunchKernelGGL(k_slab_unpack, dim3(ceil_div(cnt, 256u)), dim3(256), 0, c->stream, s->mig_recv[0] + 2, cnt,
+                               c->posi + c->own_off - cnt, c->velr + c->own_off - cnt, (uint32_t*)nullptr, c->grid, G,
+                               s->h_lb_dev + HL_ERR);
+            continue;
+        }
+        const uint32_t at = c->own_off + c->n + appended;
+        hipLaunchKernelGGL(k_slab_unpack, dim3(ceil_div(cnt, 256u)), dim3(256), 0, c->stream, s->mig_recv[side] + 2, cnt,
+                           c->posi + at, c->velr + at, merge ? c->k0 + c->n + appended : (uint32_t*)nullptr, c->grid, G,
+                           s->h_lb_dev + HL_ERR);
+        appended += cnt;
+    }
+    SPH_HIP(hipGetLastError());
+    if (merge) {
+        rc = launch_merge_arrivals(c, appended, in_lo); if (rc) return rc;   // the first in_lo came up from below
+    } else {
+        if (front_slots) { c->own_off -= in_lo; c->n += in_lo; }
+        c->n += appended;
+        c->keys_fresh = false;
+        c->order_valid = false;
+        c->stage = sph_ctx::ST_LOADED;
+        rc = step_hash(c); if (rc) return rc;
+        rc = step_sort(c); if (rc) return rc;
+    }
+    st.own_lo += in_lo - st.far_in_lo;          // the far ones went past the boundary layer
+    st.own_hi += in_hi - st.far_in_hi;
+    s->resorts++;
+    if (st.far_in_lo || st.far_in_hi) {
+        // rare (a particle crossed more than one cell layer in a step): count the layers again.  The neighbours
+        // size their ghost messages from the headers, so what the count must confirm is that every far arrival
+        // stayed clear of the OTHER boundary layer and of the ghost layers.
+        s->far_steps++;
+        if (getenv("SPH_SLAB_DEBUG"))
+            fprintf(stderr, "[slab %d] step %llu: far arrivals %u/%u of %u/%u; leavers %u/%u (far %u/%u); bounds %u %u %u %u of %u; "
+                    "peer boundary %u/%u\n", s->rank, (unsigned long long)s->steps, st.far_in_lo, st.far_in_hi, in_lo, in_hi, m_lo, m_hi,
+                    st.far_lo, st.far_hi, st.lb0, st.lb1, st.lb2, st.lb3, st.n0, st.peer_own_lo, st.peer_own_hi);
+        hipLaunchKernelGGL(k_slab_bounds, dim3(1), dim3(64), 0, c->stream, c->keyS + c->own_off, c->n, st.layer, c->grid.zl, G,
+                           s->d_lb, s->h_lb_dev);
+        SPH_HIP(hipGetLastError());
+        SPH_HIP(hipStreamSynchronize(c->stream));
+        s->host_waits++;
+        rc = slab_check_device_flags(s); if (rc) return rc;
+        const uint32_t r0 = s->h_lb[0], r1 = s->h_lb[1], r2 = s->h_lb[2], r3 = s->h_lb[3];
+        SPH_REQUIRE(r0 == 0u && r3 == c->n && r1 - r0 == st.own_lo && r3 - r2 == st.own_hi, SPH_E_STATE,
+                    "rank %d: a particle that crossed several cell layers in one step landed in a boundary or ghost "
+                    "layer (boundary layers %u/%u, expected %u/%u): the time step is too large for this slab width",
+                    s->rank, r1 - r0, r3 - r2, st.own_lo, st.own_hi);
+    }
+    return SPH_OK;
+}
+
+// ---- the ghosts (halo A, or the one message's layers) and the density launches; the halo-B pack ----------------------------
+int step_ghosts(sph_slab* s, Step& st) {
+    sph_ctx* c = s->c;
+    int rc;
+    const bool p1 = st.p1, early_halo = st.early_halo;
+    const uint32_t n = st.n = c->n, m_lo = st.m_lo, m_hi = st.m_hi;
     // ghosts = what stayed in the neighbour's boundary layer + what I just sent INTO that layer; the one-message step keeps
     // the neighbour's second layer as well (g1: the inner ghost layer, whose densities this rank computes itself)
-    const uint32_t g1_lo = s->has_lo ? peer_own_lo + m_lo - far_lo : 0u, g1_hi = s->has_hi ? peer_own_hi + m_hi - far_hi : 0u;
-    const uint32_t g_lo = p1 && s->has_lo ? peer_own_lo + n2p_lo + m_lo : g1_lo;
-    const uint32_t g_hi = p1 && s->has_hi ? peer_own_hi + n2p_hi + m_hi : g1_hi;
-    const uint32_t h_lo = s->has_lo ? own_lo : 0u, h_hi = s->has_hi ? own_hi : 0u;
-    SPH_REQUIRE(own_lo <= n && own_hi <= n, SPH_E_STATE, "rank %d: inconsistent boundary counts", s->rank);
+    const uint32_t g1_lo = s->has_lo ? st.peer_own_lo + m_lo - st.far_lo : 0u, g1_hi = s->has_hi ? st.peer_own_hi + m_hi - st.far_hi : 0u;
+    const uint32_t g_lo = st.g_lo = p1 && s->has_lo ? st.peer_own_lo + st.n2p_lo + m_lo : g1_lo;
+    const uint32_t g_hi = st.g_hi = p1 && s->has_hi ? st.peer_own_hi + st.n2p_hi + m_hi : g1_hi;
+    const uint32_t h_lo = st.h_lo = s->has_lo ? st.own_lo : 0u, h_hi = st.h_hi = s->has_hi ? st.own_hi : 0u;
+    SPH_REQUIRE(st.own_lo <= n && st.own_hi <= n, SPH_E_STATE, "rank %d: inconsistent boundary counts", s->rank);
+    // (past this check the three-group step's h / g equal the HALO A / HALO B sizes record_owed clamped to gcap)
     SPH_REQUIRE(h_lo <= s->gcap && h_hi <= s->gcap && g_lo <= s->gcap && g_hi <= s->gcap && g_lo <= c->own_off &&
                     c->own_off + n + g_hi <= c->tot, SPH_E_CAPACITY,
                 "rank %d: a boundary layer of %u/%u (ghosts %u/%u) exceeds the ghost capacity %u", s->rank, h_lo, h_hi, g_lo, g_hi,
@@ -1470,6 +1539,7 @@ int slab_step_body(sph_slab* s, float dt) {
     // movers of the next sort per chunk)
     uint32_t a = c->own_off + ((h_lo + 63u) & ~63u), b = h_hi ? c->own_off + ((n - h_hi) & ~63u) : c->own_off + n;
     if (b < a || a > c->own_off + n) { a = c->own_off; b = c->own_off; }     // a thin slab: everything is "boundary"
+    st.a = a; st.b = b;
     // Early mode runs the boundary chunks' force launch on the comm stream with no event behind the deep density launch
     // -- allowed only while none of its targets can see a density that launch writes: [own_off, a) must end inside layer
     // 2 (it then reads layers <= 3; the deep interior starts at 4), [b, end) must start inside layer zl-3 (a side
@@ -1478,9 +1548,8 @@ int slab_step_body(sph_slab* s, float dt) {
     // (An unconditional record costs the device ~6 us of idle per step; a MISSING one cost 18 NaN particles in one of
     // three 2-rank rehearsals of round 3: the high-priority comm stream overtook a deep launch that queued behind
     // another rank's kernels.)
-    const bool need_deep_event = early_halo && !(a <= near_lo && b >= near_hi);
-    uint32_t deep_v = 0u;
-    if (need_deep_event) { rc = hop_mark(s, HOP_DEEP, c->stream, s->ev_deep, &deep_v); if (rc) return rc; }
+    st.need_deep_event = early_halo && !(a <= st.near_lo && b >= st.near_hi);
+    if (st.need_deep_event) { rc = hop_mark(s, HOP_DEEP, c->stream, s->ev_deep, &st.deep_v); if (rc) return rc; }
     // the slots the non-deep density launches cover: the owned range -- and, in the one-message step, the inner ghost layers
     // on either side (what HALO B carries in the three-group step), rounded down to a whole 64-slot chunk in front so that the
     // hole these launches leave for the deep range stays on the chunk boundaries the deep launch used; the few slots of the
@@ -1505,14 +1574,12 @@ int slab_step_body(sph_slab* s, float dt) {
         // the interior density runs while the halo travels: queued BEFORE the transfers are handed to the transport.
         // What the deep launch already did is left out.
         PhaseTimer t(c, SPH_PH_DENS);
-        rc = deep_valid ? launch_density_hole(c, a, b, deep_lo, deep_hi) : launch_density_range(c, a, b);
+        rc = st.deep_valid ? launch_density_hole(c, a, b, st.deep_lo, st.deep_hi) : launch_density_range(c, a, b);
         if (rc) return rc;
     }
     if (!p1) {
-        rc = slab_exchange(s, SPH_TAG_HALO_A, s->halo_send[0], h_lo * rec, s->halo_recv[0], g_lo * rec, s->halo_send[1], h_hi * rec,
-                           s->halo_recv[1], g_hi * rec);
-        if (rc) return rc;
-        s->pg.halo_a = true;
+        rc = slab_exchange(s, s->pg.group[sph_slab::G_HALO_A]); if (rc) return rc;
+        s->pg.posted[sph_slab::G_HALO_A] = true;
         // ghosts go directly in front of / behind the owned range, already in key order; their cells join the table of
         // the owned slots (comm stream, one kernel: none of it is touched by the interior passes)
         if (g_lo + g_hi)
@@ -1522,9 +1589,9 @@ int slab_step_body(sph_slab* s, float dt) {
         // The one-message step: the neighbours' two layers came with their headers and leavers (behind those, in the same
         // buffer); no message here.  A side this rank sent nobody to is unpacked as it is; else its own leavers -- still in the
         // send buffer -- are merged in where the neighbour will put them (k_slab_unpack_ghosts_merge), then the cells.
-        const float4* res_lo = s->mig_recv[0] + 2 * (1 + (size_t)in_lo);
-        const float4* res_hi = s->mig_recv[1] + 2 * (1 + (size_t)in_hi);
-        const uint32_t nr_lo = s->has_lo ? peer_own_lo + n2p_lo : 0u, nr_hi = s->has_hi ? peer_own_hi + n2p_hi : 0u;
+        const float4* res_lo = s->mig_recv[0] + 2 * (1 + (size_t)st.in_lo);
+        const float4* res_hi = s->mig_recv[1] + 2 * (1 + (size_t)st.in_hi);
+        const uint32_t nr_lo = s->has_lo ? st.peer_own_lo + st.n2p_lo : 0u, nr_hi = s->has_hi ? st.peer_own_hi + st.n2p_hi : 0u;
         if (m_lo + m_hi == 0u) {
             hipLaunchKernelGGL(k_slab_unpack_ghosts, dim3(ceil_div(g_lo + g_hi, 256u)), dim3(256), 0, s->comm, res_lo, g_lo, c->own_off - g_lo,
                                res_hi, g_hi, c->own_off + n, c->posi, c->velr, c->keyS, c->cells, c->grid);
@@ -1551,7 +1618,7 @@ int slab_step_body(sph_slab* s, float dt) {
         OnComm on(s);
         {
             PhaseTimer t(c, SPH_PH_DENS);
-            rc = launch_density_hole(c, dens_lo, dens_hi, deep_lo, deep_hi);
+            rc = launch_density_hole(c, dens_lo, dens_hi, st.deep_lo, st.deep_hi);
             if (rc) return rc;
         }
         if (!p1 && h_lo + h_hi)
@@ -1574,6 +1641,14 @@ int slab_step_body(sph_slab* s, float dt) {
         rc = after_main(s); if (rc) return rc;
     }
     c->have_dens = true;
+    return SPH_OK;
+}
+
+// ---- the forces: interior (leaving out what the early launch did), halo B, the boundary chunks; the step's counters -------
+int step_forces(sph_slab* s, Step& st) {
+    sph_ctx* c = s->c;
+    int rc;
+    const uint32_t n = st.n, g_lo = st.g_lo, g_hi = st.g_hi, a = st.a, b = st.b;
     // the interior forces run while halo B travels
     const bool mark = force_begin(c, true);
     {
@@ -1581,29 +1656,27 @@ int slab_step_body(sph_slab* s, float dt) {
         // what the early launch did is left out in whole 64-slot chunks of the FINAL owned range (the up to 63 slots at
         // either end of its range are simply computed again: same inputs, same bits)
         uint32_t h0 = 0, h1 = 0;
-        if (early_launched && deep_valid && early_hi > early_lo && early_lo >= c->own_off) {
-            h0 = c->own_off + ((early_lo - c->own_off + 63u) & ~63u);
-            h1 = c->own_off + ((early_hi - c->own_off) & ~63u);
+        if (st.early_launched && st.deep_valid && st.early_hi > st.early_lo && st.early_lo >= c->own_off) {
+            h0 = c->own_off + ((st.early_lo - c->own_off + 63u) & ~63u);
+            h1 = c->own_off + ((st.early_hi - c->own_off) & ~63u);
         }
         if (h1 > h0 && h0 >= a && h1 <= b) {
-            rc = launch_force_hole(c, a, b, h0, h1, true, true, true, dt, mark);                     // interior: queued before the transfer
+            rc = launch_force_hole(c, a, b, h0, h1, true, true, true, st.dt, mark);                  // interior: queued before the transfer
             if (rc) return rc;
-            rc = join_early(); if (rc) return rc;                   // (its tail has run beside the launch above)
+            rc = join_early(s, st); if (rc) return rc;              // (its tail has run beside the launch above)
             hipLaunchKernelGGL(k_slab_early_finish, dim3(ceil_div(h1 - h0, 256u)), dim3(256), 0, c->stream, c->keyS2, c->keyS, h0, h1,
                                c->own_off, c->k0, mark ? c->mm_mask : (uint64_t*)nullptr, c->mm_tile_cnt);
             SPH_HIP(hipGetLastError());
             s->early_used++;
         } else {
-            rc = join_early(); if (rc) return rc;                   // (both write the same slots of the ping-pong arrays: same values, but in order)
-            rc = launch_force_range(c, a, b, true, true, true, dt, mark);
+            rc = join_early(s, st); if (rc) return rc;              // (both write the same slots of the ping-pong arrays: same values, but in order)
+            rc = launch_force_range(c, a, b, true, true, true, st.dt, mark);
         }
     }
     if (rc) return rc;
-    if (!p1) {
-        rc = slab_exchange(s, SPH_TAG_HALO_B, s->dens_send[0], h_lo * sizeof(float2), s->dens_recv[0], g_lo * sizeof(float2),
-                           s->dens_send[1], h_hi * sizeof(float2), s->dens_recv[1], g_hi * sizeof(float2));
-        if (rc) return rc;
-        s->pg.halo_b = true;
+    if (!st.p1) {
+        rc = slab_exchange(s, s->pg.group[sph_slab::G_HALO_B]); if (rc) return rc;
+        s->pg.posted[sph_slab::G_HALO_B] = true;
         if (g_lo + g_hi)
             hipLaunchKernelGGL(k_slab_unpack_dp2, dim3(ceil_div(g_lo + g_hi, 256u)), dim3(256), 0, s->comm, s->dens_recv[0],
                                c->dp + c->own_off - g_lo, c->cw + c->own_off - g_lo, g_lo, s->dens_recv[1], c->dp + c->own_off + n,
@@ -1613,10 +1686,10 @@ int slab_step_body(sph_slab* s, float dt) {
     // the boundary layers' force pass: on the comm stream, behind the ghosts' (rho, p) -- beside the interior launch
     // (it reads what that one reads and writes other slots of the ping-pong arrays), not behind it
     {
-        if (need_deep_event) { rc = hop_wait(s, HOP_DEEP, s->comm, s->ev_deep, deep_v); if (rc) return rc; }  // (non-early: ev_main above covers the densities)
+        if (st.need_deep_event) { rc = hop_wait(s, HOP_DEEP, s->comm, s->ev_deep, st.deep_v); if (rc) return rc; }  // (non-early: ev_main above covers the densities)
         OnComm on(s);
         PhaseTimer t(c, SPH_PH_FORCE);
-        rc = launch_force_hole(c, c->own_off, c->own_off + n, a, b, true, true, true, dt, mark);
+        rc = launch_force_hole(c, c->own_off, c->own_off + n, a, b, true, true, true, st.dt, mark);
         if (rc) return rc;
     }
     rc = after_comm(s); if (rc) return rc;                      // the mover count (force_finish) needs both launches
@@ -1626,25 +1699,39 @@ int slab_step_body(sph_slab* s, float dt) {
     // k_slab_bounds_pack, i.e. behind everything queued above)
     s->steps++;
     // what either end of each link packed this step: the size rule of the next one-message step (both ends hold the same numbers)
-    for (int k = 0; k < 2; k++) { s->one_prev_s[k] = tot_s[k]; s->one_prev_r[k] = tot_r[k]; }
+    for (int k = 0; k < 2; k++) { s->one_prev_s[k] = st.tot_s[k]; s->one_prev_r[k] = st.tot_r[k]; }
     s->one_ready = true;
     if (c->timing) { c->timed_steps++; if (c->events.size() > 3 * 4096) timing_collect(c); }
     {
         const auto t_end = std::chrono::steady_clock::now();
-        s->t_post.add(std::chrono::duration<double, std::micro>(t_end - t_waited).count());
-        s->t_host.add(std::chrono::duration<double, std::micro>(t_end - t_begin).count());
+        s->t_post.add(std::chrono::duration<double, std::micro>(t_end - st.t_waited).count());
+        s->t_host.add(std::chrono::duration<double, std::micro>(t_end - st.t_begin).count());
     }
     if (s->pending.size() > 4096) { rc = slab_timing_collect(s); if (rc) return rc; }
     return SPH_OK;
 }
 
+int slab_step_body(sph_slab* s, float dt) {
+    Step st;
+    st.dt = dt;
+    st.t_begin = std::chrono::steady_clock::now();
+    s->pg = sph_slab::Progress();
+    int rc = step_pre_wait(s, st);
+    if (!rc) rc = step_headers(s, st);
+    if (!rc) rc = step_settle(s, st);
+    if (!rc) rc = step_ghosts(s, st);
+    if (!rc) rc = step_forces(s, st);
+    (void)join_early(s, st);             // (an error return leaves the step half done: the next sort must still come behind the early launch)
+    return rc;
+}
+
 // A rank that fails does not simply return: its neighbours have sized this step's messages from the headers and are
 // about to post them, and with RCCL a receive whose sender never sends stays on the comm stream for ever.  So the rank
-// (1) still exchanges what the step owes -- the numbers of Progress, contents irrelevant: the run is over --, (2) puts
-// "abort" into the header of its NEXT migrant message and exchanges that too, (3) is marked failed: every later call
+// (1) still exchanges what the step owes -- the groups Progress recorded, contents irrelevant: the run is over --, (2) puts
+// "abort" into the header of its NEXT first group and exchanges that too, (3) is marked failed: every later call
 // returns the first error.  A neighbour reads the abort word at its next wait, returns SPH_E_PEER and does the same
 // towards ITS other neighbour: the failure reaches rank r +- k after k steps, nobody waits for a timeout.  A step that
-// fails before its own migrant message was posted sends the abort header AS that message (same step).  If the
+// fails before its own first group was posted sends the abort header AS that group (same step).  If the
 // transport itself failed (or a wait timed out: the neighbour is gone) nothing more is exchanged and the transport is
 // aborted (RCCL: ncclCommAbort), so that destroy / sync do not block on a receive that will never complete.
 int slab_fail(sph_slab* s, int rc) {
@@ -1652,51 +1739,23 @@ int slab_fail(sph_slab* s, int rc) {
     s->failed = rc;
     snprintf(s->fail_msg, sizeof s->fail_msg, "%s", sph_last_error());
     sph_slab::Progress& g = s->pg;
-    const size_t rec = 2 * sizeof(float4);
-    const uint32_t inl = min(MIG_INLINE, s->mcap);
     int e = SPH_OK;
-    if (!s->transport_dead && !g.mig_posted && s->world > 1) {
-        // the step failed BEFORE its migrant message went out (a device-side flag of the last step, the sort, a launch):
-        // the neighbours are about to post theirs, so the abort header travels as THIS step's migrant message -- they
-        // read it at this step's wait and stop; nothing else is owed (no header of this rank promised anything)
-        g.mig_posted = true;
-        after_main(s);          // (a bounds kernel of this step may be queued on the main stream: it writes the same header words)
-        hipLaunchKernelGGL(k_slab_abort_headers, dim3(1), dim3(64), 0, s->comm, s->mig_send[0], s->mig_send[1]);
-        const size_t mig_bytes = (size_t)(1 + inl) * rec;
-        if (g.one)              // the neighbours have posted this step's ONE message at the sizes the rule gave all of us
-            e = slab_exchange(s, SPH_TAG_ONE, s->mig_send[0], (1 + (size_t)g.one_s[0]) * rec, s->mig_recv[0], (1 + (size_t)g.one_r[0]) * rec,
-                              s->mig_send[1], (1 + (size_t)g.one_s[1]) * rec, s->mig_recv[1], (1 + (size_t)g.one_r[1]) * rec);
-        else
-            e = slab_exchange(s, SPH_TAG_MIGRANTS, s->mig_send[0], mig_bytes, s->mig_recv[0], mig_bytes, s->mig_send[1], mig_bytes,
-                              s->mig_recv[1], mig_bytes);
-    } else if (!s->transport_dead && g.headers && s->world > 1) {
-        if (!g.rest && g.one && (g.rest_s[0] | g.rest_s[1] | g.rest_r[0] | g.rest_r[1]))
-            e = slab_exchange(s, SPH_TAG_ONE_REST, s->mig_send[0] + 2 * (1 + (size_t)g.one_s[0]), g.rest_s[0] * rec,
-                              s->mig_recv[0] + 2 * (1 + (size_t)g.one_r[0]), g.rest_r[0] * rec, s->mig_send[1] + 2 * (1 + (size_t)g.one_s[1]),
-                              g.rest_s[1] * rec, s->mig_recv[1] + 2 * (1 + (size_t)g.one_r[1]), g.rest_r[1] * rec);
-        else if (!g.rest && (g.rest_s[0] | g.rest_s[1] | g.rest_r[0] | g.rest_r[1]))
-            e = slab_exchange(s, SPH_TAG_MIGRANTS_REST, s->mig_send[0] + 2 * (1 + inl), g.rest_s[0] * rec, s->mig_recv[0] + 2 * (1 + inl),
-                              g.rest_r[0] * rec, s->mig_send[1] + 2 * (1 + inl), g.rest_s[1] * rec, s->mig_recv[1] + 2 * (1 + inl),
-                              g.rest_r[1] * rec);
-        if (!e && !g.halo_a)
-            e = slab_exchange(s, SPH_TAG_HALO_A, s->halo_send[0], g.h[0] * rec, s->halo_recv[0], g.g[0] * rec, s->halo_send[1],
-                              g.h[1] * rec, s->halo_recv[1], g.g[1] * rec);
-        if (!e && !g.halo_b)
-            e = slab_exchange(s, SPH_TAG_HALO_B, s->dens_send[0], g.h[0] * sizeof(float2), s->dens_recv[0], g.g[0] * sizeof(float2),
-                              s->dens_send[1], g.h[1] * sizeof(float2), s->dens_recv[1], g.g[1] * sizeof(float2));
-        if (!e) {                                               // the next step's header: "abort"
+    if (!s->transport_dead && s->world > 1) {
+        if (!g.posted[sph_slab::G_FIRST]) {
+            // the step failed BEFORE its first group went out (a device-side flag of the last step, the sort, a launch): the
+            // neighbours are about to post theirs, so the abort header travels as THIS step's first group -- they read it at
+            // this step's wait and stop; nothing else is owed (no header of this rank promised anything)
+            g.posted[sph_slab::G_FIRST] = true;
+            after_main(s);      // (a bounds kernel of this step may be queued on the main stream: it writes the same header words)
             hipLaunchKernelGGL(k_slab_abort_headers, dim3(1), dim3(64), 0, s->comm, s->mig_send[0], s->mig_send[1]);
-            const size_t mig_bytes = (size_t)(1 + inl) * rec;
-            // (the neighbours, for whom this step went through, take their next step under the slab's protocol: a one-message
-            // step is sized from THIS step's headers, which both ends have)
-            if (s->protocol == 1 && g.next_known && g.next_s[0] <= s->msg_cap && g.next_s[1] <= s->msg_cap && g.next_r[0] <= s->msg_cap &&
-                g.next_r[1] <= s->msg_cap)
-                e = slab_exchange(s, SPH_TAG_ONE, s->mig_send[0], (1 + (size_t)(s->has_lo ? g.next_s[0] : 0u)) * rec, s->mig_recv[0],
-                                  (1 + (size_t)(s->has_lo ? g.next_r[0] : 0u)) * rec, s->mig_send[1], (1 + (size_t)(s->has_hi ? g.next_s[1] : 0u)) * rec,
-                                  s->mig_recv[1], (1 + (size_t)(s->has_hi ? g.next_r[1] : 0u)) * rec);
-            else
-                e = slab_exchange(s, SPH_TAG_MIGRANTS, s->mig_send[0], mig_bytes, s->mig_recv[0], mig_bytes, s->mig_send[1], mig_bytes,
-                                  s->mig_recv[1], mig_bytes);
+            e = slab_exchange(s, g.group[sph_slab::G_FIRST]);
+        } else if (g.headers) {
+            for (int i = sph_slab::G_REST; i <= sph_slab::G_HALO_B && !e; i++)
+                if (!g.posted[i]) e = slab_exchange(s, g.group[i]);
+            if (!e) {                                           // the next step's header: "abort"
+                hipLaunchKernelGGL(k_slab_abort_headers, dim3(1), dim3(64), 0, s->comm, s->mig_send[0], s->mig_send[1]);
+                e = slab_exchange(s, g.group[sph_slab::G_NEXT]);
+            }
         }
     }
     if ((s->transport_dead || e) && s->tr.abort) { s->tr.abort(s->tr.self); s->transport_dead = true; }
@@ -1895,7 +1954,6 @@ int sph_slab_create(sph_slab** out, sph_ctx* ctx, int rank, int world, const sph
     s->has_lo = rank > 0; s->has_hi = rank + 1 < world;
     s->device = ctx->device;
     if (const char* e = getenv("SPH_SLAB_TIMEOUT_S")) { const double v = atof(e); if (v > 0.0) s->wait_timeout_s = v; }
-    if (const char* e = getenv("SPH_SLAB_EARLY_STREAM")) s->early_own_stream = atoi(e) != 0;
     if (const char* e = getenv("SPH_SLAB_EARLY_SPAN")) { const long v = atol(e); if (v > 0) s->early_cap = (uint32_t)v; }
     s->tr = *transport;
     s->host_staged = transport->host_buffers != 0;
@@ -2104,13 +2162,14 @@ int sph_slab_ping(sph_slab* s, size_t bytes, uint32_t reps, double out[3]) {
     const uint64_t exchanges0 = s->exchanges;
     const bool timed0 = s->time_groups;
     const sph_slab::Acc acc0 = s->t_group[4];
+    const Msg ping{SPH_TAG_PING, {s->halo_send[0], s->halo_send[1]}, {bytes, bytes}, {s->halo_recv[0], s->halo_recv[1]}, {bytes, bytes}};
     int rc = slab_timing_collect(s);
     s->t_group[4] = sph_slab::Acc();
     for (uint32_t rep = 0; rep <= reps && !rc; rep++) {
         s->time_groups = rep > 0;                             // round 0 is the connection set-up
         hipLaunchKernelGGL(k_slab_ping_fill, dim3(grid), dim3(256), 0, s->comm, s->has_lo ? (uint32_t*)s->halo_send[0] : nullptr,
                            s->has_hi ? (uint32_t*)s->halo_send[1] : nullptr, words, (uint32_t)s->rank, rep);
-        rc = slab_exchange(s, SPH_TAG_PING, s->halo_send[0], bytes, s->halo_recv[0], bytes, s->halo_send[1], bytes, s->halo_recv[1], bytes);
+        rc = slab_exchange(s, ping);
         if (rc) break;
         hipLaunchKernelGGL(k_slab_ping_check, dim3(grid), dim3(256), 0, s->comm, s->has_lo ? (const uint32_t*)s->halo_recv[0] : nullptr,
                            s->has_hi ? (const uint32_t*)s->halo_recv[1] : nullptr, words, (uint32_t)s->rank, rep, bad);
@@ -2179,7 +2238,6 @@ static int slab_wait_stream(sph_slab* s, hipStream_t st, const char* what) {
 static int slab_recut_body(sph_slab* s, uint32_t new_lo, uint32_t new_hi) {
     sph_ctx* c = s->c;
     int rc;
-    const size_t rec = 2 * sizeof(float4);
     SPH_HIP(hipStreamSynchronize(s->comm));
     rc = step_hash(c); if (rc) return rc;
     rc = step_sort(c); if (rc) return rc;                 // (a slab's sort also builds the table of its owned slots)
@@ -2205,7 +2263,8 @@ static int slab_recut_body(sph_slab* s, uint32_t new_lo, uint32_t new_hi) {
     hipLaunchKernelGGL(k_recut_counts_out, dim3(1), dim3(64), 0, c->stream, s->mig_send[0], s->mig_send[1], down, up);
     SPH_HIP(hipGetLastError());
     rc = after_main(s); if (rc) return rc;
-    rc = slab_exchange(s, SPH_TAG_RECUT_COUNTS, s->mig_send[0], rec, s->mig_recv[0], rec, s->mig_send[1], rec, s->mig_recv[1], rec);
+    const uint32_t none[2] = {0, 0};
+    rc = slab_exchange(s, msg_first(s, SPH_TAG_RECUT_COUNTS, none, none));
     if (rc) return rc;
     uint32_t in_lo = 0, in_hi = 0;
     if (s->has_lo) SPH_HIP(hipMemcpyAsync((void*)&s->h_lb[HL_RECUT + 2], s->mig_recv[0], sizeof(uint32_t), hipMemcpyDeviceToHost, s->comm));
@@ -2236,8 +2295,8 @@ static int slab_recut_body(sph_slab* s, uint32_t new_lo, uint32_t new_hi) {
                                s_lo, up0 + j * chunk, s_hi, s->halo_send[0], s->halo_send[1]);
         SPH_HIP(hipGetLastError());
         rc = after_main(s); if (rc) return rc;
-        rc = slab_exchange(s, SPH_TAG_RECUT, s->halo_send[0], s_lo * rec, s->halo_recv[0], r_lo * rec, s->halo_send[1], s_hi * rec,
-                           s->halo_recv[1], r_hi * rec);
+        const uint32_t sent[2] = {s_lo, s_hi}, taken[2] = {r_lo, r_hi};
+        rc = slab_exchange(s, msg_halo(s, SPH_TAG_RECUT, sent, taken));
         if (rc) return rc;
         if (r_lo + r_hi && !over)
             hipLaunchKernelGGL(k_recut_unpack, dim3(ceil_div(r_lo + r_hi, 256u)), dim3(256), 0, s->comm, s->halo_recv[0], r_lo,
