@@ -42,6 +42,14 @@ class Params(C.Structure):
                 ("particle_radius", C.c_float)]
 
 
+MAX_COLLIDERS = 8          # SPH_MAX_COLLIDERS
+
+
+class Collider(C.Structure):
+    """`sph_collider` of include/sph_hip.h: one solid sphere."""
+    _fields_ = [("center", C.c_float * 3), ("radius", C.c_float), ("velocity", C.c_float * 3), ("pad", C.c_float)]
+
+
 # name -> (restype, argtypes); also the list the symbol-export test walks
 _P = C.c_void_p
 _U32 = C.c_uint32
@@ -75,6 +83,8 @@ SIGNATURES = {
     "sph_snapshot_save": (C.c_int, [_P, C.c_char_p]),
     "sph_snapshot_load": (C.c_int, [_P, C.c_char_p]),
     "sph_snapshot_info": (C.c_int, [C.c_char_p, C.POINTER(_U32), C.POINTER(Params)]),
+    "sph_set_colliders": (C.c_int, [_P, _U32, C.POINTER(Collider)]),
+    "sph_get_colliders": (C.c_int, [_P, C.POINTER(_U32), C.POINTER(Collider)]),
     "sph_positions_dev": (C.c_int, [_P, C.POINTER(_P)]),
     "sph_download_positions4": (C.c_int, [_P, _P]),
     "sph_get_keys": (C.c_int, [_P, _P]),
@@ -345,6 +355,33 @@ class Context:
         n, p = _U32(0), Params()
         _check(load().sph_snapshot_info(os.fsencode(path), C.byref(n), C.byref(p)))
         return int(n.value), p
+
+    def set_colliders(self, centers, radii, velocities=None):
+        """Replace the context's solid spheres (include/sph_hip.h: sph_set_colliders): centers (n, 3), radii (n,), velocities
+        (n, 3) or None (at rest), in box coordinates; n = 0 clears them.  Every integrate pushes the particles out of them and
+        every step advances the centres by dt * velocity."""
+        centers = _f32(centers, 3)
+        n = centers.shape[0]
+        radii = np.ascontiguousarray(radii, dtype=np.float32).reshape(-1)
+        velocities = np.zeros((n, 3), np.float32) if velocities is None else _f32(velocities, 3)
+        if radii.shape[0] != n or velocities.shape[0] != n:
+            raise ValueError("centers, radii and velocities describe different numbers of spheres")
+        arr = (Collider * max(n, 1))()
+        for j in range(n):
+            arr[j].center[:] = [float(v) for v in centers[j]]
+            arr[j].radius = float(radii[j])
+            arr[j].velocity[:] = [float(v) for v in velocities[j]]
+        _check(self.L.sph_set_colliders(self.h, n, arr))
+
+    def colliders(self):
+        """The current spheres, centres advanced: {"centers": (n, 3), "radii": (n,), "velocities": (n, 3)} float32."""
+        arr = (Collider * MAX_COLLIDERS)()
+        n = _U32()
+        _check(self.L.sph_get_colliders(self.h, C.byref(n), arr))
+        rows = [arr[j] for j in range(n.value)]
+        return {"centers": np.array([list(r.center) for r in rows], np.float32).reshape(-1, 3),
+                "radii": np.array([r.radius for r in rows], np.float32),
+                "velocities": np.array([list(r.velocity) for r in rows], np.float32).reshape(-1, 3)}
 
     def positions4(self):
         out = np.empty((self.capacity, 4), dtype=np.float32)

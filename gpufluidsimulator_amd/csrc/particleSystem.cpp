@@ -89,7 +89,7 @@ ParticleSystem::ParticleSystem(uint numParticles, float3 boxDims, ParticleComput
 
 ParticleSystem::ParticleSystem(uint numParticles, float3 boxDims, ParticleComputeMode mode, uint3 gridDims)
     : m_bInitialized(false), m_numParticles(numParticles), m_boxDims(boxDims), m_solverIterations(1),
-      m_compute_mode(mode), m_ctx(nullptr), m_hostStale(false), m_log(nullptr), m_logLastMs(0), m_logGlobalMs(0), m_logFreqMs(2000.0), m_logStyle(0), m_logFrames(0) {
+      m_compute_mode(mode), m_ctx(nullptr), m_colliderOn(false), m_colliderVel{0.f, 0.f, 0.f}, m_hostStale(false), m_log(nullptr), m_logLastMs(0), m_logGlobalMs(0), m_logFreqMs(2000.0), m_logStyle(0), m_logFrames(0) {
     if (mode != CUDA_PARALLEL) {
         fprintf(stderr, "ParticleSystem: only the GPU compute mode exists in this build "
                         "(SEQUENTIAL / OMP_PARALLEL are the reference's CPU paths; there is no CPU fallback)\n");
@@ -157,10 +157,28 @@ void ParticleSystem::downloadAll() {
     m_hostStale = false;
 }
 
+void ParticleSystem::enableCollider(bool on) {
+    m_colliderOn = on;
+    if (!on) SPH_CHECK(sph_set_colliders(m_ctx, 0, nullptr));   // (on: update() sets the sphere before every run of steps)
+}
+
 // ---- stepping (particleSystem.cpp:719-817) ------------------------------------------------------------------
 void ParticleSystem::update(float deltaTime, float fps) {
     if (!m_bInitialized) { fprintf(stderr, "ParticleSystem::update before initialisation\n"); exit(EXIT_FAILURE); }
-    if (m_solverIterations > 0) SPH_CHECK(sph_step(m_ctx, deltaTime, (uint32_t)m_solverIterations));
+    if (m_solverIterations > 0) {
+        if (m_colliderOn) {
+            const sph_collider s = {{m_params.colliderPos.x, m_params.colliderPos.y, m_params.colliderPos.z}, m_params.colliderRadius,
+                                    {m_colliderVel.x, m_colliderVel.y, m_colliderVel.z}, 0.f};
+            SPH_CHECK(sph_set_colliders(m_ctx, 1, &s));
+        }
+        SPH_CHECK(sph_step(m_ctx, deltaTime, (uint32_t)m_solverIterations));
+        if (m_colliderOn) {                                  // the centre the steps advanced it to
+            uint32_t n = 0;
+            sph_collider s;
+            SPH_CHECK(sph_get_colliders(m_ctx, &n, &s));
+            m_params.colliderPos = make_float3(s.center[0], s.center[1], s.center[2]);
+        }
+    }
     m_hostStale = true;
     if (m_log) {
         // dumpBenchmark, particleSystem.cpp:697-716: at most one line every BENCHMARK_FREQ = 2000 ms

@@ -779,6 +779,34 @@ int sph_snapshot_load(sph_ctx* c, const char* path) {
     return sph_upload(c, n, pos.data(), vel.data(), idx.data());
 }
 
+int sph_set_colliders(sph_ctx* c, uint32_t n, const sph_collider* colliders) {
+    SPH_REQUIRE(c, SPH_E_INVALID, "null context");
+    SPH_REQUIRE(n <= SPH_MAX_COLLIDERS, SPH_E_INVALID, "%u colliders > SPH_MAX_COLLIDERS (%d)", n, SPH_MAX_COLLIDERS);
+    SPH_REQUIRE(n == 0 || colliders, SPH_E_INVALID, "null colliders");
+    for (uint32_t j = 0; j < n; j++) {
+        const sph_collider& s = colliders[j];
+        SPH_REQUIRE(std::isfinite(s.radius) && s.radius > 0.f, SPH_E_INVALID, "collider %u: radius %g is not a positive finite number", j,
+                    (double)s.radius);
+        for (int a = 0; a < 3; a++)
+            SPH_REQUIRE(std::isfinite(s.center[a]) && std::isfinite(s.velocity[a]), SPH_E_INVALID,
+                        "collider %u: centre or velocity is not finite", j);
+    }
+    for (uint32_t j = 0; j < n; j++) {
+        c->colliders[j] = colliders[j];
+        c->colliders[j].pad = 0.f;
+    }
+    c->n_colliders = n;
+    return SPH_OK;
+}
+
+int sph_get_colliders(const sph_ctx* c, uint32_t* n, sph_collider* out) {
+    SPH_REQUIRE(c && n, SPH_E_INVALID, "null argument");
+    *n = c->n_colliders;
+    if (out)
+        for (uint32_t j = 0; j < c->n_colliders; j++) out[j] = c->colliders[j];
+    return SPH_OK;
+}
+
 int sph_positions_dev(sph_ctx* c, void** out) {
     SPH_REQUIRE(c && out, SPH_E_INVALID, "null argument");
     SPH_REQUIRE(!c->slab, SPH_E_STATE, "slab contexts keep no by-index position buffer");

@@ -51,6 +51,14 @@ struct Phys {
     float box_min[3], box_max[3];
 };
 
+// The sphere colliders of a context (sph_set_colliders) as the collider instantiations of k_force / k_integrate take them: a
+// kernel argument by value -- a 256-byte table and its count -- so that they cost no dispatch and no copy of their own.
+struct Spheres {
+    float4 c[SPH_MAX_COLLIDERS];   // centre, R + wall_eps
+    float4 u[SPH_MAX_COLLIDERS];   // velocity, (R + wall_eps)^2
+    uint32_t n;
+};
+
 }  // namespace sph
 
 // The opaque context of include/sph_hip.h.
@@ -94,6 +102,11 @@ struct sph_ctx {
     float4* dvel = nullptr;   // delta_velocity xyz, collision count
     float4* pos_out = nullptr;// (x,y,z,1) by creation index: the gl_pos analogue
     uint32_t pos_out_cap = 0;
+
+    // sphere colliders (sph_set_colliders): every integrate pushes the particles out of them, the centres advance on the host
+    // once per step (sph_pairs.hip: push_out_of_spheres, advance_colliders); none by default
+    uint32_t n_colliders = 0;
+    sph_collider colliders[SPH_MAX_COLLIDERS] = {};
 
     // pair kernels: a (dz, dy) row whose staged hull would exceed this many slots is read straight from global memory
     // by every lane instead (sph_pairs.hip: traverse; sph_set_direct_hull)
@@ -243,7 +256,7 @@ int launch_force_hole(sph_ctx* c, uint32_t lo, uint32_t hi, uint32_t hole_lo, ui
                       bool integrate, float dt, bool mark);
 bool force_begin(sph_ctx* c, bool integrate);
 int launch_force_range(sph_ctx* c, uint32_t lo, uint32_t hi, bool force, bool collide, bool integrate, float dt, bool mark);
-void force_finish(sph_ctx* c, bool integrate, bool mark);
+void force_finish(sph_ctx* c, bool integrate, bool mark, float dt);   // also advances the colliders' centres by dt
 // phase bodies of sph_capi.hip (with their bookkeeping), for the slab driver
 int set_slab_range(sph_ctx* c, uint32_t z_lo, uint32_t z_hi);   // sph_capi.hip: a slab context takes over another layer range (its table must be clear)
 int step_hash(sph_ctx* c);

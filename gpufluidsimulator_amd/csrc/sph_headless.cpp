@@ -2,7 +2,9 @@
 // (SPH/particles.cpp:676-706: -n= -box= -i= -benchmark -device= -file=) and its runBenchmark()
 // output line (:176-192), on top of include/particleSystem.h.  No GLUT / OpenGL.
 //   sph_headless -benchmark -n=262144 -box=8 -i=100 [-device=0] [-grid=128] [-ic=grid|random] [-steps=1] [-dump=8]
-//                [-log=benchmark.txt [-logstyle=oscar|frames]] [-file=<snapshot>]
+//                [-log=benchmark.txt [-logstyle=oscar|frames]] [-file=<snapshot>] [-collider=x,y,z,r[,ux,uy,uz]]
+// -collider: the reference's collider sphere (centre, radius, and a velocity: default at rest), made to push the fluid
+// (ParticleSystem::enableCollider; one sphere, as the reference's UI has).
 // Several GPUs (no counterpart in the reference, which is a single-device program): -gpus=N cuts the dam into N
 // z-slabs and steps them with sph_slab_step through the C ABI --
 //   -gpus=N            N child PROCESSES, forked before anything touches a GPU, rank r on device r (+ -device=), messages
@@ -393,11 +395,29 @@ int main(int argc, char** argv) {
     if (flag(argc, argv, "help")) {
         printf("usage: sph_headless [-benchmark] [-n=<particles>] [-box=<edge>] [-i=<iterations>] [-device=<id>] [-grid=<cells per axis>] "
                "[-ic=grid|random] [-steps=<per update>] [-gpus=<N> [-onegpu] [-slab] [-lattice=nx,ny,nz] [-protocol=1|3]] "
-               "[-dump=<count>] [-log=<file> [-logfreq=<ms>] [-logstyle=oscar|frames]] [-sphere=<update>[,<radius>]] [-out=<file>] [-save=<file>] [-load=<file>] [-file=<file>]\n");
+               "[-dump=<count>] [-log=<file> [-logfreq=<ms>] [-logstyle=oscar|frames]] [-sphere=<update>[,<radius>]] "
+               "[-collider=<x>,<y>,<z>,<radius>[,<ux>,<uy>,<uz>]] [-out=<file>] [-save=<file>] [-load=<file>] [-file=<file>]\n"
+               "  -collider: a solid sphere the fluid flows around, moving at (ux, uy, uz) (default: at rest); one device only\n");
         return 0;
     }
     const int gpus = value(argc, argv, "gpus") ? atoi(value(argc, argv, "gpus")) : 1;
+    // -collider=x,y,z,r[,ux,uy,uz]
+    float col[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const char* colliderArg = value(argc, argv, "collider");
+    if (colliderArg) {
+        const int k = sscanf(colliderArg, "%f,%f,%f,%f,%f,%f,%f", &col[0], &col[1], &col[2], &col[3], &col[4], &col[5], &col[6]);
+        if ((k != 4 && k != 7) || !(col[3] > 0.f)) {
+            fprintf(stderr, "-collider=%s: expected x,y,z,r or x,y,z,r,ux,uy,uz with r > 0\n", colliderArg);
+            return EXIT_FAILURE;
+        }
+    }
     if (gpus > 1 || (gpus == 1 && flag(argc, argv, "slab"))) {     // (-gpus=1 -slab: the same machinery with one rank -- fork, RCCL communicator of one)
+        if (colliderArg) {
+            fprintf(stderr, "-collider is not supported with -gpus=%d%s: run it on one device, or set the sphere on every rank "
+                            "through the library (gpufluidsimulator_amd.slab.NativeSlabSimulation(colliders=...))\n",
+                    gpus, gpus == 1 ? " -slab" : "");
+            return EXIT_FAILURE;
+        }
         if (ic != ParticleSystem::CONFIG_GRID || load || value(argc, argv, "sphere") || value(argc, argv, "save") || value(argc, argv, "log") || dump) {
             fprintf(stderr, "-gpus=%d runs the dam-break lattice (-ic=grid) and takes -n -box -grid -i -steps -lattice -out -device -onegpu -nowarmup\n", gpus);
             return EXIT_FAILURE;
@@ -436,6 +456,12 @@ int main(int argc, char** argv) {
         numParticles = (uint)psystem->getNumParticles();  // the snapshot decides how many particles there are
     }
     psystem->setIterations(substeps);
+    if (colliderArg) {
+        psystem->setColliderPos(make_float3(col[0], col[1], col[2]));
+        psystem->setColliderRadius(col[3]);
+        psystem->setColliderVelocity(make_float3(col[4], col[5], col[6]));
+        psystem->enableCollider(true);
+    }
     if (const char* v = value(argc, argv, "log")) {
         const char* fq = value(argc, argv, "logfreq");
         // -logstyle=oscar: the line form of the reference's committed logs (benchmarks/oscar/, what its benchmark.py reads);

@@ -766,8 +766,54 @@ __device__ __forceinline__ void wall(float& x, float& v, float lo, float hi, flo
     if (x + eps > hi) { x = hi - eps; v *= damp; }
 }
 
+// ---- sphere colliders (sph_set_colliders, include/sph_hip.h) ------------------------------------------------------------
+// After the walls, sphere j = 0..n-1 in order: a particle inside R_j + eps goes onto that shell along the radial direction
+// ((0, 1, 0) at the centre); if it approaches the sphere, the normal part of its velocity RELATIVE to the sphere is scaled by
+// wall_damping, as the walls do; a particle that any sphere moved goes through the walls once more.  Unfused arithmetic in the
+// order of the header's pseudo-code (the tests' numpy model).  Like the near-wall test above, every lane makes one cheap test
+// per sphere and a wave with no lane inside any sphere -- nearly every wave -- skips the projection under one ballot.
+__device__ __forceinline__ void push_out_of_spheres(const Phys& ph, float4& pi, float4& vi, const Spheres& sp) {
+#pragma clang fp contract(off)
+    bool inside = false;
+    for (uint32_t j = 0; j < sp.n; j++) {
+        const float dx = pi.x - sp.c[j].x, dy = pi.y - sp.c[j].y, dz = pi.z - sp.c[j].z;
+        inside |= dx * dx + dy * dy + dz * dz < sp.u[j].w;
+    }
+    if (__ballot(inside) == 0ull) return;
+    bool hit = false;
+    for (uint32_t j = 0; j < sp.n; j++) {
+        const float dx = pi.x - sp.c[j].x, dy = pi.y - sp.c[j].y, dz = pi.z - sp.c[j].z;
+        const float r2 = dx * dx + dy * dy + dz * dz;
+        if (r2 < sp.u[j].w) {
+            float nx = 0.f, ny = 1.f, nz = 0.f;
+            if (r2 > 0.f) {
+                const float r = sqrtf(r2);
+                nx = dx / r; ny = dy / r; nz = dz / r;
+            }
+            const float rp = sp.c[j].w;
+            pi.x = sp.c[j].x + rp * nx;
+            pi.y = sp.c[j].y + rp * ny;
+            pi.z = sp.c[j].z + rp * nz;
+            const float wn = (vi.x - sp.u[j].x) * nx + (vi.y - sp.u[j].y) * ny + (vi.z - sp.u[j].z) * nz;
+            if (wn < 0.f) {
+                const float k = (ph.wall_damping - 1.f) * wn;
+                vi.x += k * nx; vi.y += k * ny; vi.z += k * nz;
+            }
+            hit = true;
+        }
+    }
+    if (hit) {
+        wall(pi.x, vi.x, ph.box_min[0], ph.box_max[0], ph.wall_eps, ph.wall_damping);
+        wall(pi.y, vi.y, ph.box_min[1], ph.box_max[1], ph.wall_eps, ph.wall_damping);
+        wall(pi.z, vi.z, ph.box_min[2], ph.box_max[2], ph.wall_eps, ph.wall_damping);
+    }
+}
+
+// `sp`: empty, or the sphere table (the collider instantiations of k_force / k_integrate, launched only while a context has
+// colliders); an empty pack compiles to exactly the code without them.
+template <class... Sph>
 __device__ __forceinline__ void integrate_one(const Phys& ph, float dt, float4& pi, float4& vi, float rho, float fx,
-                                              float fy, float fz, float dvx, float dvy, float dvz) {
+                                              float fy, float fz, float dvx, float dvy, float dvz, const Sph&... sp) {
     fy += ph.gravity_y * rho;
     // one v_rcp_f32 (1 ulp) and three multiplications instead of three IEEE divisions (~10 instructions each): the
     // acceleration moves by <= 1.5 ulp, five orders below the stated tolerance.  -DSPH_EXACT_DIV=1 builds the reference's
@@ -794,6 +840,7 @@ __device__ __forceinline__ void integrate_one(const Phys& ph, float dt, float4& 
         wall(pi.y, vi.y, ph.box_min[1], ph.box_max[1], ph.wall_eps, ph.wall_damping);
         wall(pi.z, vi.z, ph.box_min[2], ph.box_max[2], ph.wall_eps, ph.wall_damping);
     }
+    if constexpr (sizeof...(Sph) > 0) push_out_of_spheres(ph, pi, vi, sp...);
 }
 
 // ---- force / collision / integrate in ONE neighbour traversal ------------------------------------------
@@ -821,14 +868,15 @@ extern "C" void sph_debug_pair_stats(unsigned long long* out, int on) {     // r
 #else
 #define PAIR_STAT(k, v) do { } while (0)
 #endif
-template <bool FORCE, bool COLL, bool INTEG, int THREADS>
+// Sph: empty, or Spheres for the collider instantiation of the fused pass (one more argument: the sphere table, by value)
+template <bool FORCE, bool COLL, bool INTEG, int THREADS, class... Sph>
 __global__ __launch_bounds__(THREADS, SPH_FORCE_OCC) void k_force(
     const float4* __restrict__ posi, const float4* __restrict__ velr, const float2* __restrict__ dp,
     const float2* __restrict__ cw, const uint32_t* __restrict__ keyS, const uint2* __restrict__ cells, float4* __restrict__ fpress,
     float4* __restrict__ fvisc, float4* __restrict__ dvel, float4* __restrict__ posi_out,
     float4* __restrict__ velr_out, float4* __restrict__ pos_by_index, uint32_t* __restrict__ keys_out,
     uint64_t* __restrict__ mm_mask, uint32_t* __restrict__ mm_tile_cnt, Targets tg,
-    uint32_t slot0, float dt, GridDesc g, Phys ph) {
+    uint32_t slot0, float dt, GridDesc g, Phys ph, Sph... sp) {
     // One candidate = 4 float2 {x,y} {z,vx} {vy,vz} {cp,w} at a 40-byte stride (5 float2, the fifth is
     // padding): one address register serves all four ds_read_b64 through immediate offsets, and the
     // 8-entry (one cell) distance between the lane groups of a wave is 80 dwords = 16 banks, so the four
@@ -962,7 +1010,7 @@ __global__ __launch_bounds__(THREADS, SPH_FORCE_OCC) void k_force(
 #endif
             }
             if (INTEG) {
-                integrate_one(ph, dt, pi, vi, dpi.x, fpx + fvx, fpy + fvy, fpz + fvz, dvx, dvy, dvz);
+                integrate_one(ph, dt, pi, vi, dpi.x, fpx + fvx, fpy + fvy, fpz + fvz, dvx, dvy, dvz, sp...);
                 posi_out[i] = pi;
                 velr_out[i] = vi;
                 if (pos_by_index) pos_by_index[__float_as_uint(pi.w)] = make_float4(pi.x, pi.y, pi.z, 1.0f);
@@ -1126,6 +1174,40 @@ static Targets targets_with_hole(uint32_t lo, uint32_t hi, uint32_t hole_lo, uin
     return t;
 }
 
+// The sphere table of a context's colliders (kernel argument of the collider instantiations): R + eps and its square are
+// rounded once here, as the header's pseudo-code does on every particle.
+static Spheres sphere_table(const sph_ctx* c) {
+    Spheres t{};
+    const float eps = c->params.wall_eps;
+    for (uint32_t j = 0; j < c->n_colliders; j++) {
+        const sph_collider& s = c->colliders[j];
+        const float rp = s.radius + eps;
+        t.c[j] = make_float4(s.center[0], s.center[1], s.center[2], rp);
+        t.u[j] = make_float4(s.velocity[0], s.velocity[1], s.velocity[2], rp * rp);
+    }
+    t.n = c->n_colliders;
+    return t;
+}
+
+// one launch of k_force over `threads` slots; sp: empty, or the sphere table (the collider instantiation)
+template <bool F, bool C, bool I, class... Sph>
+static void force_kernel(sph_ctx* c, bool small, const Targets& tg, uint32_t threads, float dt, bool mark, Sph... sp) {
+#define SPH_LAUNCH_FORCE_T(T)                                                                                                   \
+    hipLaunchKernelGGL((k_force<F, C, I, T, Sph...>), dim3(ceil_div(threads, (uint32_t)T)), dim3(T), 0, c->stream, c->posi,       \
+                       c->velr, c->dp, c->cw, c->keyS, c->cells, c->fpress, c->fvisc, c->dvel, c->posi2, c->velr2,                \
+                       c->slab ? nullptr : c->pos_out, c->k0, mark ? c->mm_mask : nullptr, c->mm_tile_cnt, tg, c->own_off, dt, \
+                       c->grid, c->phys, sp...)
+    if (small) SPH_LAUNCH_FORCE_T(SMALL_THREADS_PAIR); else SPH_LAUNCH_FORCE_T(PAIR_THREADS);
+#undef SPH_LAUNCH_FORCE_T
+}
+
+// centres of the colliders after a step of dt (once per step: the fused pass's force_finish, launch_integrate)
+static void advance_colliders(sph_ctx* c, float dt) {
+#pragma clang fp contract(off)
+    for (uint32_t j = 0; j < c->n_colliders; j++)
+        for (int a = 0; a < 3; a++) c->colliders[j].center[a] = c->colliders[j].center[a] + dt * c->colliders[j].velocity[a];
+}
+
 // One launch of the pair kernel over the owned slots [lo, hi) minus the hole [hole_lo, hole_hi) (lo - own_off,
 // hole_lo - lo and the hole's length multiples of 64: a wave is one chunk of the mover marks).  The fused form
 // (integrate) writes the ping-pong arrays; force_finish() swaps them once every sub-range has been launched.
@@ -1142,21 +1224,15 @@ int launch_force_hole(sph_ctx* c, uint32_t lo, uint32_t hi, uint32_t hole_lo, ui
     SPH_REQUIRE(tg.gap_len == 0u || (((tg.gap_lo - lo) | tg.gap_len) & 63u) == 0u || tg.gap_lo + tg.gap_len == hi, SPH_E_INVALID,
                 "force hole is not made of whole 64-slot chunks");
     if (threads == 0) return SPH_OK;
-    dim3 grid(ceil_div(threads, bt)), block(bt);
-#define SPH_LAUNCH_FORCE_T(F, C, I, T)                                                                         \
-    hipLaunchKernelGGL((k_force<F, C, I, T>), grid, block, 0, c->stream, c->posi, c->velr, c->dp, c->cw, c->keyS, c->cells, \
-                       c->fpress, c->fvisc, c->dvel, c->posi2, c->velr2, c->slab ? nullptr : c->pos_out, c->k0,              \
-                       mark ? c->mm_mask : nullptr, c->mm_tile_cnt, tg, c->own_off, dt, c->grid, c->phys)
-#define SPH_LAUNCH_FORCE(F, C, I) do { if (small) SPH_LAUNCH_FORCE_T(F, C, I, SMALL_THREADS_PAIR); else SPH_LAUNCH_FORCE_T(F, C, I, PAIR_THREADS); } while (0)
-    if (force && collide && integrate) SPH_LAUNCH_FORCE(true, true, true);
-    else if (force && !collide && !integrate) SPH_LAUNCH_FORCE(true, false, false);
-    else if (!force && collide && !integrate) SPH_LAUNCH_FORCE(false, true, false);
+    if (force && collide && integrate) {
+        if (c->n_colliders) force_kernel<true, true, true>(c, small, tg, threads, dt, mark, sphere_table(c));
+        else force_kernel<true, true, true>(c, small, tg, threads, dt, mark);
+    } else if (force && !collide && !integrate) force_kernel<true, false, false>(c, small, tg, threads, dt, mark);
+    else if (!force && collide && !integrate) force_kernel<false, true, false>(c, small, tg, threads, dt, mark);
     else {
         set_error("launch_force: unsupported combination");
         return SPH_E_INVALID;
     }
-#undef SPH_LAUNCH_FORCE
-#undef SPH_LAUNCH_FORCE_T
     SPH_HIP(hipGetLastError());
     return SPH_OK;
 }
@@ -1168,11 +1244,17 @@ int launch_force_hole(sph_ctx* c, uint32_t lo, uint32_t hi, uint32_t hole_lo, ui
 int launch_force_dev_range(sph_ctx* c, const uint32_t* range_dev, uint32_t max_count, float dt) {
     if (max_count == 0) return SPH_OK;
     const Targets tg{0u, 0u, 0xFFFFFFFFu, 0u, range_dev, c->direct_hull, BlockOrder{0u, 0u, 0u, 0u, 0u}};
-#define SPH_LAUNCH_EARLY(T)                                                                                                         \
-    hipLaunchKernelGGL((k_force<true, true, true, T>), dim3(ceil_div(max_count, (uint32_t)T)), dim3(T), 0, c->stream, c->posi, c->velr,   \
-                       c->dp, c->cw, c->keyS, c->cells, c->fpress, c->fvisc, c->dvel, c->posi2, c->velr2, c->slab ? nullptr : c->pos_out, \
-                       c->keyS2, (uint64_t*)nullptr, c->mm_tile_cnt, tg, 0u, dt, c->grid, c->phys)
-    if (small_blocks(c)) SPH_LAUNCH_EARLY(SMALL_THREADS_PAIR); else SPH_LAUNCH_EARLY(PAIR_THREADS);
+#define SPH_LAUNCH_EARLY(T, ...)                                                                                                    \
+    hipLaunchKernelGGL((k_force<true, true, true, T __VA_OPT__(, ) __VA_ARGS__>), dim3(ceil_div(max_count, (uint32_t)T)), dim3(T), 0,   \
+                       c->stream, c->posi, c->velr, c->dp, c->cw, c->keyS, c->cells, c->fpress, c->fvisc, c->dvel, c->posi2, c->velr2,  \
+                       c->slab ? nullptr : c->pos_out, c->keyS2, (uint64_t*)nullptr, c->mm_tile_cnt, tg, 0u, dt, c->grid, c->phys      \
+                       __VA_OPT__(, sphere_table(c)))
+    // (the same centres as the step's other launches: force_finish advances them once all are queued)
+    if (c->n_colliders) {
+        if (small_blocks(c)) SPH_LAUNCH_EARLY(SMALL_THREADS_PAIR, Spheres); else SPH_LAUNCH_EARLY(PAIR_THREADS, Spheres);
+    } else {
+        if (small_blocks(c)) SPH_LAUNCH_EARLY(SMALL_THREADS_PAIR); else SPH_LAUNCH_EARLY(PAIR_THREADS);
+    }
 #undef SPH_LAUNCH_EARLY
     SPH_HIP(hipGetLastError());
     return SPH_OK;
@@ -1189,8 +1271,9 @@ bool force_begin(sph_ctx* c, bool integrate) {
     return integrate && c->sort_merge && c->order_valid;
 }
 
-void force_finish(sph_ctx* c, bool integrate, bool mark) {
+void force_finish(sph_ctx* c, bool integrate, bool mark, float dt) {
     if (!integrate) return;
+    advance_colliders(c, dt);
     float4* t;
     t = c->posi; c->posi = c->posi2; c->posi2 = t;
     t = c->velr; c->velr = c->velr2; c->velr2 = t;
@@ -1202,11 +1285,14 @@ void force_finish(sph_ctx* c, bool integrate, bool mark) {
 }
 
 int launch_force(sph_ctx* c, bool force, bool collide, bool integrate, float dt) {
-    if (c->n == 0) return SPH_OK;
+    if (c->n == 0) {
+        if (integrate) advance_colliders(c, dt);      // (a step without particles still moves the spheres)
+        return SPH_OK;
+    }
     const bool mark = force_begin(c, integrate);
     int rc = launch_force_range(c, c->own_off, c->own_off + c->n, force, collide, integrate, dt, mark);
     if (rc) return rc;
-    force_finish(c, integrate, mark);
+    force_finish(c, integrate, mark, dt);
     return SPH_OK;
 }
 
@@ -1248,26 +1334,37 @@ int launch_density_dev_range(sph_ctx* c, const uint32_t* range_dev, uint32_t max
 }
 
 // ---- stand-alone integrate for the phase API --------------------------------------------------------------
+// Sph: empty, or Spheres for the collider instantiation (as k_force)
+template <class... Sph>
 __global__ __launch_bounds__(256) void k_integrate(float4* __restrict__ posi, float4* __restrict__ velr,
                                                    const float2* __restrict__ dp, const float4* __restrict__ fpress,
                                                    const float4* __restrict__ fvisc, const float4* __restrict__ dvel,
                                                    float4* __restrict__ pos_by_index, uint32_t lo, uint32_t hi, float dt,
-                                                   Phys ph) {
+                                                   Phys ph, Sph... sp) {
     uint32_t i = lo + blockIdx.x * 256u + threadIdx.x;
     if (i >= hi) return;
     float4 pi = posi[i], vi = velr[i];
     const float4 fp = fpress[i], fv = fvisc[i], dv = dvel[i];
-    integrate_one(ph, dt, pi, vi, dp[i].x, fp.x + fv.x, fp.y + fv.y, fp.z + fv.z, dv.x, dv.y, dv.z);
+    integrate_one(ph, dt, pi, vi, dp[i].x, fp.x + fv.x, fp.y + fv.y, fp.z + fv.z, dv.x, dv.y, dv.z, sp...);
     posi[i] = pi;
     velr[i] = vi;
     if (pos_by_index) pos_by_index[__float_as_uint(pi.w)] = make_float4(pi.x, pi.y, pi.z, 1.0f);
 }
 
 int launch_integrate(sph_ctx* c, float dt) {
-    if (c->n == 0) return SPH_OK;
-    hipLaunchKernelGGL(k_integrate, dim3(ceil_div(c->n, 256)), dim3(256), 0, c->stream, c->posi, c->velr, c->dp,
-                       c->fpress, c->fvisc, c->dvel, c->slab ? nullptr : c->pos_out, c->own_off, c->own_off + c->n, dt, c->phys);
+    if (c->n == 0) {
+        advance_colliders(c, dt);
+        return SPH_OK;
+    }
+    float4* const pos_out = c->slab ? nullptr : c->pos_out;
+    if (c->n_colliders)
+        hipLaunchKernelGGL(k_integrate<Spheres>, dim3(ceil_div(c->n, 256)), dim3(256), 0, c->stream, c->posi, c->velr, c->dp,
+                           c->fpress, c->fvisc, c->dvel, pos_out, c->own_off, c->own_off + c->n, dt, c->phys, sphere_table(c));
+    else
+        hipLaunchKernelGGL(k_integrate<>, dim3(ceil_div(c->n, 256)), dim3(256), 0, c->stream, c->posi, c->velr, c->dp,
+                           c->fpress, c->fvisc, c->dvel, pos_out, c->own_off, c->own_off + c->n, dt, c->phys);
     SPH_HIP(hipGetLastError());
+    advance_colliders(c, dt);
     return SPH_OK;
 }
 

@@ -265,6 +265,8 @@ class HipEngine:
     def halo_unpack_density(self, lo, hi): self.ctx.halo_unpack_density(self.ptr(lo), self.ptr(hi))
 
     def force_collide_integrate(self, dt): self.ctx.force_collide_integrate(dt)
+    def set_colliders(self, centers, radii, velocities=None): self.ctx.set_colliders(centers, radii, velocities)
+    def colliders(self): return self.ctx.colliders()
 
     def sync(self): self.ctx.sync()
 
@@ -286,10 +288,14 @@ class HipEngine:
 class SlabSimulation:
     def __init__(self, comm, engine_factory, box, grid, lattice=None, jitter=True, jitter_dims=None,
                  capacity_factor=1.5, ghost_factor=3.0, particles=None, capacity_slack=4096, device_lattice=None, min_layers=None,
-                 python_protocol=3):
+                 python_protocol=3, colliders=None):
         """comm: TorchDistComm | LocalComm.  engine_factory(capacity, ghost_capacity, params, z_lo, z_hi)
         builds this rank's engine.  Either `lattice` (dam break generated slab by slab) or
-        `particles` = (pos, vel) of the WHOLE system (small tests)."""
+        `particles` = (pos, vel) of the WHOLE system (small tests).
+        colliders: None, or (centers, radii[, velocities]) -- solid spheres (capi.Context.set_colliders), the same on every
+        rank: positions are global, so every rank pushes the particles it owns out of every sphere (ghosts arrive already
+        pushed) and advances the centres once per step.  A sphere placed over fluid moves particles by up to its radius in
+        one step, and in a slab run such a particle must still land inside its neighbour's slab (include/sph_hip.h)."""
         self.comm = comm
         self.rank, self.world = comm.rank, comm.world
         try:                       # torch before libsph_hip.so (capi.load): one HIP runtime per process
@@ -377,11 +383,23 @@ class SlabSimulation:
             self.engine.upload(pos, vel, index)
         else:
             self.engine.reset_lattice((nx, ny, nz), jitter, jd, device_run[0], device_run[1])
+        if colliders is not None:
+            self.set_colliders(*colliders)
         self._alloc_buffers()
         self.lo_peer = self.rank - 1 if self.rank > 0 else None
         self.hi_peer = self.rank + 1 if self.rank + 1 < self.world else None
         self.stats = {"migrants": 0, "resorts": 0, "ghosts": 0}
         self._counts = None          # slab counts of the previous step, reusable while the sort finds nothing to do
+
+    def set_colliders(self, centers, radii, velocities=None):
+        """Replace the solid spheres of this rank's engine (call it on every rank with the same spheres)."""
+        if not hasattr(self.engine, "set_colliders"):
+            raise ValueError(f"{type(self.engine).__name__} has no sphere colliders")
+        self.engine.set_colliders(centers, radii, velocities)
+
+    def colliders(self):
+        """This rank's spheres, centres advanced (capi.Context.colliders)."""
+        return self.engine.colliders()
 
     def _alloc_buffers(self):
         e, g = self.engine, self.ghost_capacity
@@ -590,7 +608,8 @@ class SlabSimulation:
         parts = ([inbox[p].cpu().numpy() for p in sorted(inbox) if p < self.rank] + [rec[dest == self.rank]] +
                  [inbox[p].cpu().numpy() for p in sorted(inbox) if p > self.rank])
         rec = np.concatenate(parts) if parts else np.zeros((0, REC), np.float32)
-        # a fresh engine for the new layer range (cell table, key width and capacities depend on it)
+        # a fresh engine for the new layer range (cell table, key width and capacities depend on it); the spheres go along
+        spheres = e.colliders() if hasattr(e, "colliders") else None
         e.close()
         self.cuts = cuts
         self.z_lo, self.z_hi = cuts[self.rank], cuts[self.rank + 1]
@@ -600,6 +619,8 @@ class SlabSimulation:
         self._counts = None
         self._one_prev = None              # (new layers: the next step learns the one message's sizes again)
         self.engine.upload(rec[:, 0:3].copy(), rec[:, 4:7].copy(), np.ascontiguousarray(rec[:, 3]).view(np.uint32).copy())
+        if spheres is not None and spheres["radii"].size:
+            self.engine.set_colliders(spheres["centers"], spheres["radii"], spheres["velocities"])
         self._alloc_buffers()
         self.stats["rebalances"] = self.stats.get("rebalances", 0) + 1
         return True

@@ -34,8 +34,9 @@ static inline float3 make_float3(float x, float y, float z) { float3 v = {x, y, 
 #endif
 
 // SPH/particles_kernel.cuh:36-50, field for field, so that setSimParams() accepts the
-// reference's struct.  gravity / collider* are carried but, as in the reference, no kernel
-// reads them.
+// reference's struct.  gravity is carried but, as in the reference, no kernel reads it (SURVEY.md
+// A.1); colliderPos / colliderRadius describe the collider sphere, which pushes the fluid while
+// enableCollider(true) is set (off by default, as the reference's sphere is inert).
 struct SimParams {
     float3 colliderPos;
     float colliderRadius;
@@ -78,6 +79,9 @@ public:
 
     void setIterations(int i) { m_solverIterations = i; }
     void setGravity(float x) { m_params.gravity = make_float3(0.0f, x, 0.0f); }   // a physics no-op, as upstream
+    // The collider sphere (sph_set_colliders): inert until enableCollider(true).  While it is enabled, update() hands
+    // colliderPos / colliderRadius and the velocity to the context before its steps and reads the advanced centre back
+    // into colliderPos after them.
     void setColliderPos(float3 x) { m_params.colliderPos = x; }
     float3 getColliderPos() { return m_params.colliderPos; }
     float getColliderRadius() { return m_params.colliderRadius; }
@@ -86,6 +90,13 @@ public:
     float3 getBoxMax() { return m_params.boxMax; }
 
     void addSphere(int index, float* pos, float* vel, int r, float spacing);
+
+    // ---- additive: the collider sphere pushes the fluid (absent upstream, where it is drawn but inert) -----------------------
+    void enableCollider(bool on);
+    bool colliderEnabled() const { return m_colliderOn; }
+    void setColliderRadius(float r) { m_params.colliderRadius = r; }
+    void setColliderVelocity(float3 u) { m_colliderVel = u; }     // box units per unit time; kinematic (the fluid never pushes it)
+    float3 getColliderVelocity() const { return m_colliderVel; }
 
     // ---- additive (absent upstream; named by BASELINE.json's north star) ------------------------
     // 4 floats per particle, by creation index (the original NVIDIA sample's layout); the pointer
@@ -129,6 +140,8 @@ protected:
     uint m_solverIterations;
     ParticleComputeMode m_compute_mode;
     sph_ctx* m_ctx;
+    bool m_colliderOn;
+    float3 m_colliderVel;
     bool m_hostStale;
     std::string m_logPath;
     void* m_log;

@@ -29,6 +29,7 @@
  *                  sph_set_params sph_get_params sph_sync sph_num_particles sph_capacity sph_ghost_layers sph_set_precision
  *                  sph_get_precision | sph_upload sph_set_by_index sph_reset_lattice sph_download sph_download_owned
  *                  sph_positions_dev sph_download_positions4 sph_snapshot_save sph_snapshot_load sph_snapshot_info |
+ *                  sph_set_colliders sph_get_colliders |
  *                  sph_hash sph_sort sph_build_cells sph_density sph_force sph_collide sph_integrate sph_step sph_step_phased
  *                  sph_force_collide_integrate | sph_timing_enable sph_timing_get sph_timing_reset | the z-slab phase calls
  *                  (sph_migrants_* sph_slab_counts sph_halo_* sph_layer_histogram) | sph_rccl_unique_id
@@ -71,7 +72,8 @@ typedef struct sph_ctx sph_ctx;
 /* Replaces `struct SimParams` (SPH/particles_kernel.cuh:36-50) plus the physics macros of
  * particles_kernel.cuh:20-33, which the reference bakes in at compile time.  The reference
  * never reads SimParams.gravity / colliderPos / colliderRadius in any kernel (setGravity is a
- * physics no-op), so they are not part of the device parameters. */
+ * physics no-op), so they are not part of the device parameters; the collider
+ * sphere has an API of its own here, which makes it push the fluid (sph_set_colliders). */
 typedef struct sph_params {
     float box_min[3];        /* SimParams.boxMin                                   */
     float box_max[3];        /* SimParams.boxMax                                   */
@@ -192,6 +194,43 @@ int sph_download_owned(sph_ctx* c, float* pos_xyz, float* vel_xyz, uint32_t* ind
  * creation index, written by sph_integrate / sph_step.  Device pointer, n*16 bytes. */
 int sph_positions_dev(sph_ctx* c, void** out_dev);
 int sph_download_positions4(sph_ctx* c, float* pos_xyzw);
+
+/* ---- sphere colliders (the reference's SimParams.colliderPos / colliderRadius, which no kernel of the reference reads) ----
+ * A context holds 0 (the default) to SPH_MAX_COLLIDERS solid spheres, each with a centre c, a radius R > 0 and a velocity u,
+ * all in box coordinates.  The velocity is kinematic: the fluid never pushes a sphere.  On EVERY integrate the context
+ * performs (sph_step, sph_step_phased / sph_integrate, sph_force_collide_integrate, sph_slab_step), after the integration and
+ * the wall rule, each particle with position x and velocity v goes through the spheres in order j = 0..n-1:
+ *
+ *     d = x - c_j ; r2 = d.d ; Rp = R_j + wall_eps
+ *     if r2 < Rp*Rp:
+ *         nrm = r2 > 0 ? d / sqrt(r2) : (0, 1, 0)
+ *         x   = c_j + Rp * nrm
+ *         wn  = (v - u_j) . nrm
+ *         if wn < 0:  v += (wall_damping - 1) * wn * nrm
+ *
+ * (fp32, each operation rounded, sums left to right: the normal part of the velocity relative to the sphere is scaled by
+ * wall_damping, as the walls do).  A particle that any sphere moved goes through the wall rule once more, so it stays in the
+ * box; the next step's cell key is that of the final position.  Where spheres overlap, their ORDER decides the result: a
+ * later sphere may push a particle back into an earlier one.  After each step the centres advance on the host,
+ * c_j = c_j + dt * u_j in fp32 -- once per step, however many launches the step's force pass takes (a slab step: up to three).
+ * A sphere placed over fluid moves particles by up to R in one step; in a slab run such a particle must still land where the
+ * slab step accepts arrivals (sph_slab_step, sph_slab_set_protocol: within the neighbour's slab), so place spheres over fluid
+ * with R below a cell edge or move them in from outside the fluid.  In a slab run every rank holds the same spheres (positions
+ * are global) and applies all of them to the particles it owns; ghosts arrive already pushed.
+ * Snapshots do not carry colliders: sph_snapshot_load leaves the set as it is.  The reference seam (sph_compat_seam.h) has
+ * none.  With no collider set, the step launches exactly the kernels it launches without this feature. */
+#define SPH_MAX_COLLIDERS 8
+typedef struct sph_collider {
+    float center[3];
+    float radius;
+    float velocity[3];
+    float pad;          /* ignored */
+} sph_collider;
+/* Replace the set by n spheres (n = 0 clears it).  n > SPH_MAX_COLLIDERS, a radius that is not finite or not positive, or a
+ * centre or velocity that is not finite: SPH_E_INVALID, and the set is left unchanged. */
+int sph_set_colliders(sph_ctx* c, uint32_t n, const sph_collider* colliders);
+/* The current set with the ADVANCED centres: *n spheres into out (room for SPH_MAX_COLLIDERS; may be NULL if only *n is wanted). */
+int sph_get_colliders(const sph_ctx* c, uint32_t* n, sph_collider* out);
 
 /* State snapshot (checkpoint / resume; absent in the reference, whose device state is never
  * serialised -- SURVEY.md section 5).  The file holds the parameters and, IN SLOT ORDER, position,
