@@ -77,8 +77,12 @@ static int derive(sph_ctx* c, const sph_params* p, uint32_t z_lo, uint32_t z_hi,
     const float spiky = 45.f / (PI_F * powf(p->h, 6.f));
     ph.poly6_mass = p->mass * poly6;
     ph.spiky_half_mass = p->mass * spiky * 0.5f;
-    ph.visc_coef = (p->viscosity * p->mass) * spiky;
+    // k_force carries the pressure term relative to the viscous weight (cp_scale = spiky_half_mass / visc_coef): viscosity = 0
+    // would make that inf * 0 = NaN.  So a zero viscosity is folded as 1 and the viscous sum is switched off (visc_on).
+    const float visc = p->viscosity != 0.f ? p->viscosity : 1.f;
+    ph.visc_coef = (visc * p->mass) * spiky;
     ph.cp_scale = ph.spiky_half_mass / ph.visc_coef;
+    ph.visc_on = p->viscosity != 0.f ? 1.f : 0.f;
     ph.gravity_y = p->gravity_y;
     ph.wall_eps = p->wall_eps;
     ph.wall_damping = p->wall_damping;

@@ -49,6 +49,8 @@ struct Phys {
     float coll_dist2;      // (COLLISION_PARAM * 2 * radius)^2 (particleSystem.cu:61)
     float coll_mass;       // MASS * (1 + RESTITUTION)        (particleSystem.cu:62)
     float box_min[3], box_max[3];
+    float visc_on;         // 1, or 0 for viscosity = 0: visc_coef is then folded with viscosity 1 (cp_scale stays finite) and k_force
+                           // multiplies its viscous sum by this (by 1.0f: not a bit changes)
 };
 
 // The sphere colliders of a context (sph_set_colliders) as the collider instantiations of k_force / k_integrate take them: a

@@ -569,6 +569,9 @@ __device__ __forceinline__ PairWalk pair_walk(uint32_t slice_pairs, uint32_t l0,
 #ifndef SPH_MIXED_SPAN
 #define SPH_MIXED_SPAN 6.0f      // h: how far from the reference a target may lie for the plain packed walk
 #endif
+#ifndef SPH_MIXED_XSPAN
+#define SPH_MIXED_XSPAN 1000.0f  // h: how far from the reference in x (coarse parts exact in fp16 below 1024 h)
+#endif
 #ifndef SPH_MIXED_PASSES
 #define SPH_MIXED_PASSES 3       // reference points tried on a far-apart wave before the rest takes the fp32 walk
 #endif
@@ -581,10 +584,13 @@ __device__ __forceinline__ PairWalk pair_walk(uint32_t slice_pairs, uint32_t l0,
 // together 7.5 % of the waves of the flowing C3 dam are wider than 8 h in x), one across the end of a cell layer (the other
 // side in y; 130 waves), or one that holds the scattered particles of a nearly empty region.  Round 5 found densities 33 %
 // off on such waves (config 5 cut into slabs against one context: the cuts change which particles share a wave).  Now:
-//   x is carried as a coarse part (a multiple of h/2: exact in fp16 up to 1024 h) plus a fine part (|.| <= h/4):
-//     dx = (txh - xh) + (txl - xl), two more packed instructions per pair, right at any width;
+//   x is carried as a coarse part (a multiple of h/2) plus a fine part (|.| <= h/4): dx = (txh - xh) + (txl - xl), two
+//     more packed instructions per pair.  fp16 holds every multiple of h/2 only below 1024 h (above it, 1024.5 rounds to
+//     1024 and the gap to 1025 becomes a whole h), so a pass takes only lanes within MIXED_XSPAN = 1000 h of its reference
+//     in x: their candidates (within two cell edges) stay below 1024 h while the cells are not wider than 12 h.  In fluid
+//     longer than 1000 h a wave across an x-row's end takes a second pass;
 //   y and z by PASSES: the first lane not yet served gives the reference, the lanes within MIXED_SPAN h of it in y and z
-//     are served by this pass -- their row ranges staged and walked as ever, everybody else's ranges empty -- and the rest wait
+//     (and MIXED_XSPAN h in x) are served by this pass -- their row ranges staged and walked as ever, everybody else's ranges empty -- and the rest wait
 //     for the next (one pass for an ordinary wave, two for a wave across a layer's end); after MIXED_PASSES passes the lanes
 //     still waiting are scattered particles with short candidate lists: they gather their own candidates and sum in fp32
 //     (k_density's arithmetic), all in one last walk.
@@ -738,7 +744,8 @@ __global__ __launch_bounds__(PAIR_THREADS, SPH_DENSH_OCC) void k_density_h(const
                     ry = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, pi.y), lead)),
                     rz = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, pi.z), lead));
         const float far = fmaxf(fabsf(pi.y - ry), fabsf(pi.z - rz)) * inv_h;
-        const bool in = ((todo >> lane) & 1ull) != 0ull && far <= MIXED_SPAN;      // (the lead lane: far = 0)
+        const bool in = ((todo >> lane) & 1ull) != 0ull && far <= MIXED_SPAN &&          // (the lead lane: far = 0)
+                        fabsf(pi.x - rx) * inv_h <= SPH_MIXED_XSPAN;
         todo &= ~__ballot(in);
         serve(in, rx, ry, rz);
     }
@@ -996,7 +1003,9 @@ __global__ __launch_bounds__(THREADS, SPH_FORCE_OCC) void k_force(
             PAIR_STAT(9, sum);
         }
 #endif
-        if (FORCE) { fvx = fmaf(-vi.x, sw, fvx); fvy = fmaf(-vi.y, sw, fvy); fvz = fmaf(-vi.z, sw, fvz); }
+        if (FORCE) {         // (visc_on: 0 for viscosity = 0, derive(); times 1.0f changes no bit)
+            fvx = fmaf(-vi.x, sw, fvx) * ph.visc_on; fvy = fmaf(-vi.y, sw, fvy) * ph.visc_on; fvz = fmaf(-vi.z, sw, fvz) * ph.visc_on;
+        }
         bool moved = false;
         if (active) {
             float dvx = 0.f, dvy = 0.f, dvz = 0.f;

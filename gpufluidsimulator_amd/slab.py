@@ -288,14 +288,16 @@ class HipEngine:
 class SlabSimulation:
     def __init__(self, comm, engine_factory, box, grid, lattice=None, jitter=True, jitter_dims=None,
                  capacity_factor=1.5, ghost_factor=3.0, particles=None, capacity_slack=4096, device_lattice=None, min_layers=None,
-                 python_protocol=3, colliders=None):
+                 python_protocol=3, colliders=None, params=None):
         """comm: TorchDistComm | LocalComm.  engine_factory(capacity, ghost_capacity, params, z_lo, z_hi)
         builds this rank's engine.  Either `lattice` (dam break generated slab by slab) or
         `particles` = (pos, vel) of the WHOLE system (small tests).
         colliders: None, or (centers, radii[, velocities]) -- solid spheres (capi.Context.set_colliders), the same on every
         rank: positions are global, so every rank pushes the particles it owns out of every sphere (ghosts arrive already
         pushed) and advances the centres once per step.  A sphere placed over fluid moves particles by up to its radius in
-        one step, and in a slab run such a particle must still land inside its neighbour's slab (include/sph_hip.h)."""
+        one step, and in a slab run such a particle must still land inside its neighbour's slab (include/sph_hip.h).
+        params: None (the reference's constants for box and grid, sph_default_params), or a capi.Params of the same box and
+        grid with other physics parameters, the same on every rank."""
         self.comm = comm
         self.rank, self.world = comm.rank, comm.world
         try:                       # torch before libsph_hip.so (capi.load): one HIP runtime per process
@@ -304,7 +306,7 @@ class SlabSimulation:
             pass
         self.box = tuple(float(b) for b in box)
         self.grid = tuple(int(g) for g in grid)
-        self.params = capi.default_params(self.box, self.grid)
+        self.params = capi.default_params(self.box, self.grid) if params is None else params
         # which protocol THIS class's Python step speaks (NativeSlabSimulation's step is the library's: its own `protocol`)
         self.python_protocol = int(python_protocol)
         if self.python_protocol == 1:

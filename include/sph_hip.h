@@ -73,7 +73,16 @@ typedef struct sph_ctx sph_ctx;
  * particles_kernel.cuh:20-33, which the reference bakes in at compile time.  The reference
  * never reads SimParams.gravity / colliderPos / colliderRadius in any kernel (setGravity is a
  * physics no-op), so they are not part of the device parameters; the collider
- * sphere has an API of its own here, which makes it push the fluid (sph_set_colliders). */
+ * sphere has an API of its own here, which makes it push the fluid (sph_set_colliders).
+ * Legal values (sph_create / sph_set_params refuse a bad grid, box, h, mass or radius):
+ *   box_max > box_min on every axis, anywhere; grid 1..4096 per axis; h > 0, mass > 0, particle_radius > 0;
+ *   rest_density, gravity_y: any finite value;  gas_constant >= 0 (0: p = 0 everywhere);
+ *   viscosity >= 0 (0: no viscous force and the pressure force unchanged, as the reference's formulas give);
+ *   wall_eps >= 0, below half the box edge;  wall_damping: any finite factor (0 stops, -1 reflects);
+ *   restitution >= 0;  collision_param >= 0.
+ * The neighbour search is the reference's 27-cell stencil: with a cell edge below h, neighbours beyond it are missed, as
+ * in the reference.  The mixed-precision density pass (sph_set_precision) assumes cells at most 12 h wide.
+ * tests/test_gpu_physics_params.py holds the step to a float64 model of these formulas across these ranges. */
 typedef struct sph_params {
     float box_min[3];        /* SimParams.boxMin                                   */
     float box_max[3];        /* SimParams.boxMax                                   */
@@ -152,7 +161,7 @@ uint32_t sph_capacity(const sph_ctx* c);
  * stored and integrated in fp32; inside the DENSITY traversal the per-pair arithmetic and the per-row
  * accumulators are packed fp16 (two candidates per lane-instruction) on coordinates relative to a reference point
  * of the wave in units of h (x as a coarse + a fine half, one reference per group of lanes that lie within 6 h in
- * y and z: exact at any extent of the wave), with NORMALISED kernel sums (the reference's densities ~2e6 do not
+ * y and z and 1000 h in x: right at any extent of the wave while a cell is at most 12 h wide), with NORMALISED kernel sums (the reference's densities ~2e6 do not
  * fit fp16); row sums are added up in fp32 and scaled once.  The force and collision passes stay fp32 (decided on
  * a device measurement).  Looser tolerance: DESIGN.md section 4. */
 enum { SPH_PRECISION_F32 = 0, SPH_PRECISION_MIXED_F16 = 1 };
