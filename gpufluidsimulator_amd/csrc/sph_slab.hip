@@ -1835,7 +1835,8 @@ int sph_rccl_transport_selftest(sph_transport* t, size_t bytes) {
     if (!rc) {
         for (size_t i = 0; i < bytes; i++) { ha[i] = (char)(i * 7u + 1u); hb[i] = (char)(i * 13u + 5u); }
         if ((e = hipMemcpy(sa, ha.data(), bytes, hipMemcpyHostToDevice)) || (e = hipMemcpy(sb, hb.data(), bytes, hipMemcpyHostToDevice)) ||
-            (e = hipMemset(ra, 0, bytes)) || (e = hipMemset(rb, 0, bytes)))
+            (e = hipMemset(ra, 0, bytes)) || (e = hipMemset(rb, 0, bytes)) ||
+            (e = hipStreamSynchronize(nullptr)))      // hipMemset returns before the fill is done, and `st` does not wait for the null stream
             fail("fill", e);
     }
     if (!rc) {

@@ -81,7 +81,8 @@ typedef struct sph_ctx sph_ctx;
  *   wall_eps >= 0, below half the box edge;  wall_damping: any finite factor (0 stops, -1 reflects);
  *   restitution >= 0;  collision_param >= 0.
  * The neighbour search is the reference's 27-cell stencil: with a cell edge below h, neighbours beyond it are missed, as
- * in the reference.  The mixed-precision density pass (sph_set_precision) assumes cells at most 12 h wide.
+ * in the reference.  The mixed-precision density pass (sph_set_precision) assumes cells at most 12 h wide: up to that edge
+ * it keeps its tolerance (measured per cell width in DESIGN.md section 4; tests/test_gpu_mixed_walks.py runs 1.25, 4 and 12 h).
  * tests/test_gpu_physics_params.py holds the step to a float64 model of these formulas across these ranges. */
 typedef struct sph_params {
     float box_min[3];        /* SimParams.boxMin                                   */

@@ -83,7 +83,10 @@ def test_mixed_density_on_waves_whose_particles_are_far_apart():
     densities up to 33 % off (found by cutting config 5 into slabs: the cuts change which particles share a wave).  Now x
     travels as a coarse + a fine fp16 half (exact coarse differences), and a wave that is far apart in y or z is walked
     in passes, one reference point per group of lanes (the stragglers after three passes gather in fp32).  A long flat slab of fluid (100 x 3 x 5 lattice: every x-row is 31 h long and no row is a multiple of 64
-    particles) plus a sprinkle of isolated particles: every density within the mixed tolerance of the oracle."""
+    particles) plus a sprinkle of isolated particles: every density within the mixed tolerance of the oracle.
+    The spray particles have NO neighbours: their density is the self term, so this test reaches the fp32 gather after the
+    third pass but not its candidate loop.  tests/test_gpu_mixed_walks.py sends droplets with real neighbours through passes
+    2 and 3 and the gather, and holds every walk to the float64 model exactly on dyadic inputs."""
     from gpufluidsimulator_amd import ic
     box, grid = (8.0, 8.0, 8.0), (128, 128, 128)
     pos, vel = ic.dam_break_lattice((100, 3, 5), box, jitter=True)
