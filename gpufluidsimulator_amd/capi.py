@@ -50,6 +50,30 @@ class Collider(C.Structure):
     _fields_ = [("center", C.c_float * 3), ("radius", C.c_float), ("velocity", C.c_float * 3), ("pad", C.c_float)]
 
 
+MAX_REGIONS = 8            # SPH_MAX_REGIONS
+REGION_SPHERE, REGION_BOX, REGION_HALFSPACE = 0, 1, 2
+
+
+class Region(C.Structure):
+    """`sph_region` of include/sph_hip.h: what sph_remove / sph_count_in_regions select by position (32 bytes)."""
+    _fields_ = [("kind", C.c_int32), ("a", C.c_float * 3), ("b", C.c_float * 3), ("r", C.c_float)]
+
+    @classmethod
+    def sphere(cls, center, radius):
+        """d = x - center; d.d < radius^2 (strict)."""
+        return cls(REGION_SPHERE, (C.c_float * 3)(*[float(v) for v in center]), (C.c_float * 3)(), float(radius))
+
+    @classmethod
+    def box(cls, lo, hi):
+        """lo <= x < hi on every axis (half open)."""
+        return cls(REGION_BOX, (C.c_float * 3)(*[float(v) for v in lo]), (C.c_float * 3)(*[float(v) for v in hi]), 0.0)
+
+    @classmethod
+    def halfspace(cls, point, normal):
+        """(x - point) . normal < 0 (strict): the side the normal points away from."""
+        return cls(REGION_HALFSPACE, (C.c_float * 3)(*[float(v) for v in point]), (C.c_float * 3)(*[float(v) for v in normal]), 0.0)
+
+
 # name -> (restype, argtypes); also the list the symbol-export test walks
 _P = C.c_void_p
 _U32 = C.c_uint32
@@ -85,6 +109,9 @@ SIGNATURES = {
     "sph_snapshot_info": (C.c_int, [C.c_char_p, C.POINTER(_U32), C.POINTER(Params)]),
     "sph_set_colliders": (C.c_int, [_P, _U32, C.POINTER(Collider)]),
     "sph_get_colliders": (C.c_int, [_P, C.POINTER(_U32), C.POINTER(Collider)]),
+    "sph_emit": (C.c_int, [_P, _U32, _P, _P, _P, C.POINTER(_U32)]),
+    "sph_remove": (C.c_int, [_P, _U32, C.POINTER(Region), C.POINTER(_U32), _P, _U32]),
+    "sph_count_in_regions": (C.c_int, [_P, _U32, C.POINTER(Region), C.POINTER(_U32)]),
     "sph_positions_dev": (C.c_int, [_P, C.POINTER(_P)]),
     "sph_download_positions4": (C.c_int, [_P, _P]),
     "sph_get_keys": (C.c_int, [_P, _P]),
@@ -382,6 +409,47 @@ class Context:
         return {"centers": np.array([list(r.center) for r in rows], np.float32).reshape(-1, 3),
                 "radii": np.array([r.radius for r in rows], np.float32),
                 "velocities": np.array([list(r.velocity) for r in rows], np.float32).reshape(-1, 3)}
+
+    # -- emitters and drains (whole-domain contexts; include/sph_hip.h: sph_emit, sph_remove, sph_count_in_regions) ------------
+    @staticmethod
+    def _regions(regions):
+        regions = [regions] if isinstance(regions, Region) else list(regions)
+        arr = (Region * max(len(regions), 1))()
+        for j, r in enumerate(regions):
+            arr[j] = r
+        return len(regions), arr
+
+    def emit(self, pos, vel=None, index=None):
+        """Append particles behind the owned ones; returns the creation index of the first (index=None: consecutive
+        indices from the context's next unused one).  The next sort is the full stable sort."""
+        pos = _f32(pos, 3)
+        n = pos.shape[0]
+        vel = _f32(vel, 3) if vel is not None else None
+        idx = np.ascontiguousarray(index, dtype=np.uint32).reshape(-1) if index is not None else None
+        if (vel is not None and vel.shape[0] != n) or (idx is not None and idx.shape[0] != n):
+            raise ValueError("pos, vel and index describe different numbers of particles")
+        first = _U32(0)
+        _check(self.L.sph_emit(self.h, n, pos.ctypes.data, vel.ctypes.data if vel is not None else None,
+                               idx.ctypes.data if idx is not None else None, C.byref(first)))
+        return int(first.value)
+
+    def remove(self, regions, max_out=None):
+        """Delete the owned particles inside any of the regions (a Region or up to 8 of them); the survivors keep their slot
+        order.  Returns the creation indices of the removed particles in slot order (the first max_out of them)."""
+        m, arr = self._regions(regions)
+        max_out = self.n if max_out is None else int(max_out)
+        out = np.empty(max(max_out, 1), dtype=np.uint32)
+        cnt = _U32(0)
+        _check(self.L.sph_remove(self.h, m, arr, C.byref(cnt), out.ctypes.data, max_out))
+        self.last_removed = int(cnt.value)
+        return out[:min(self.last_removed, max_out)].copy()
+
+    def count_in(self, regions):
+        """Number of owned particles inside any of the regions (nothing changes)."""
+        m, arr = self._regions(regions)
+        cnt = _U32(0)
+        _check(self.L.sph_count_in_regions(self.h, m, arr, C.byref(cnt)))
+        return int(cnt.value)
 
     def positions4(self):
         out = np.empty((self.capacity, 4), dtype=np.float32)

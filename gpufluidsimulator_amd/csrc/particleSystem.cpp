@@ -88,7 +88,10 @@ ParticleSystem::ParticleSystem(uint numParticles, float3 boxDims, ParticleComput
     : ParticleSystem(numParticles, boxDims, mode, uint3{0u, 0u, 0u}) {}
 
 ParticleSystem::ParticleSystem(uint numParticles, float3 boxDims, ParticleComputeMode mode, uint3 gridDims)
-    : m_bInitialized(false), m_numParticles(numParticles), m_boxDims(boxDims), m_solverIterations(1),
+    : ParticleSystem(numParticles, boxDims, mode, gridDims, numParticles) {}
+
+ParticleSystem::ParticleSystem(uint numParticles, float3 boxDims, ParticleComputeMode mode, uint3 gridDims, uint capacity)
+    : m_bInitialized(false), m_numParticles(numParticles), m_capacity(capacity > numParticles ? capacity : numParticles), m_boxDims(boxDims), m_solverIterations(1),
       m_compute_mode(mode), m_ctx(nullptr), m_colliderOn(false), m_colliderVel{0.f, 0.f, 0.f}, m_hostStale(false), m_log(nullptr), m_logLastMs(0), m_logGlobalMs(0), m_logFreqMs(2000.0), m_logStyle(0), m_logFrames(0) {
     if (mode != CUDA_PARALLEL) {
         fprintf(stderr, "ParticleSystem: only the GPU compute mode exists in this build "
@@ -115,14 +118,16 @@ ParticleSystem::~ParticleSystem() {
 }
 
 void ParticleSystem::_initialize(int numParticles) {
-    m_numParticles = (uint)numParticles;
-    m_hPos.assign((size_t)m_numParticles * 4, 0.f);
-    m_hVel.assign((size_t)m_numParticles * 4, 0.f);
+    m_numParticles = m_numInitial = (uint)numParticles;
+    if (m_capacity < m_numParticles) m_capacity = m_numParticles;
+    if (m_capacity == 0) m_capacity = 1;
+    m_hPos.assign((size_t)m_capacity * 4, 0.f);
+    m_hVel.assign((size_t)m_capacity * 4, 0.f);
     sph_params p;
     const float box[3] = {m_boxDims.x, m_boxDims.y, m_boxDims.z};
     const uint32_t grid[3] = {m_grid.x, m_grid.y, m_grid.z};
     sph_default_params(&p, box, grid);
-    SPH_CHECK(sph_create(&m_ctx, -1, m_numParticles ? m_numParticles : 1, &p));   // -1: sph_select_device's choice
+    SPH_CHECK(sph_create(&m_ctx, -1, m_capacity, &p));   // -1: sph_select_device's choice
     m_bInitialized = true;
 }
 
@@ -146,12 +151,19 @@ void ParticleSystem::uploadAll() {
 
 void ParticleSystem::downloadAll() {
     if (!m_hostStale) return;
-    const size_t n = m_numParticles;
-    m_xyz.resize(n * 3); m_vxyz.resize(n * 3); m_hDens.resize(n);
+    const size_t n = m_capacity;                 // by creation index; an index without a particle (removed, not yet emitted)
+    m_xyz.assign(n * 3, 0.f);                    // is not written by sph_download and shows as a row of zeros
+    m_vxyz.assign(n * 3, 0.f); m_hDens.assign(n, 0.f);
     SPH_CHECK(sph_download(m_ctx, 0, (uint32_t)n, m_xyz.data(), m_vxyz.data(), m_hDens.data(), nullptr));
+    const size_t live = sph_num_particles(m_ctx);
+    for (size_t i = 0; i < n; i++) m_hPos[4 * i + 3] = live == n ? 1.0f : 0.0f;
+    if (live != n) {                             // which indices have a particle: the owned particles' own list
+        m_live.resize(live);
+        SPH_CHECK(sph_download_owned(m_ctx, nullptr, nullptr, m_live.data()));
+        for (uint32_t k : m_live) if (k < n) m_hPos[4 * (size_t)k + 3] = 1.0f;
+    }
     for (size_t i = 0; i < n; i++) {
         for (int a = 0; a < 3; a++) { m_hPos[4 * i + a] = m_xyz[3 * i + a]; m_hVel[4 * i + a] = m_vxyz[3 * i + a]; }
-        m_hPos[4 * i + 3] = 1.0f;
         m_hVel[4 * i + 3] = 0.0f;
     }
     m_hostStale = false;
@@ -217,7 +229,9 @@ void ParticleSystem::update(float deltaTime, float fps) {
 
 // ---- initial conditions (particleSystem.cpp:839-921) ------------------------------------------------------------
 void ParticleSystem::reset(ParticleConfig config) {
-    const size_t n = m_numParticles;
+    const size_t n = m_numParticles = m_numInitial;      // the constructed count, whatever was emitted or removed since
+    m_hPos.assign((size_t)m_capacity * 4, 0.f);
+    m_hVel.assign((size_t)m_capacity * 4, 0.f);
     m_xyz.assign(n * 3, 0.f); m_vxyz.assign(n * 3, 0.f);
     const float box[3] = {m_boxDims.x, m_boxDims.y, m_boxDims.z};
     switch (config) {
@@ -246,15 +260,9 @@ void ParticleSystem::reset(ParticleConfig config) {
     m_hostStale = false;
 }
 
-// particleSystem.cpp:923-961.  Overwrites the positions of particles [start, ...) with a jittered
-// sphere lattice; velocities are left alone and `vel` is unused, as upstream.  Unlike upstream the
-// current device state is fetched first (the reference re-uploads a stale host copy in CUDA mode).
-// particleSystem.cpp:928-961.  The reference edits its host copy from `start` on and copies that range to the
-// device -- after update() the host copy is stale there, so the edit rewinds every particle it copies (SURVEY
-// A.2).  Here only the sphere's own particles change, on the device (sph_set_by_index).
-void ParticleSystem::addSphere(int start, float* pos, float* vel, int r, float spacing) {
-    (void)vel;
-    uint index = (uint)start;
+// the jittered sphere lattice of addSphere (particleSystem.cpp:928-950), at most `limit` points, xyz triples
+std::vector<float> ParticleSystem::spherePoints(const float* pos, int r, float spacing, uint limit) {
+    uint index = 0;
     const float w = m_boxDims.x, h = m_boxDims.y, d = m_boxDims.z;
     const float jitter = m_params.particleRadius * 0.01f;
     uint32_t counter = 0;
@@ -264,7 +272,7 @@ void ParticleSystem::addSphere(int start, float* pos, float* vel, int r, float s
             for (int x = -r; x <= r; x++) {
                 const float dx = x * spacing, dy = y * spacing, dz = z * spacing;
                 const float l = sqrtf(dx * dx + dy * dy + dz * dz);
-                if ((l <= m_params.particleRadius * 2.0f * r) && (index < m_numParticles)) {
+                if ((l <= m_params.particleRadius * 2.0f * r) && (index < limit)) {
                     xyz.push_back(pos[0] + dx + (w * uniform01(counter, 0, kSeed + 1) - w / 2) * jitter);
                     xyz.push_back(pos[1] + dy + (h * uniform01(counter, 1, kSeed + 1) - h / 2) * jitter);
                     xyz.push_back(pos[2] + dz + (d * uniform01(counter, 2, kSeed + 1) - d / 2) * jitter);
@@ -272,6 +280,18 @@ void ParticleSystem::addSphere(int start, float* pos, float* vel, int r, float s
                     counter++;
                 }
             }
+    return xyz;
+}
+
+// particleSystem.cpp:923-961.  Overwrites the positions of particles [start, ...) with a jittered
+// sphere lattice; velocities are left alone and `vel` is unused, as upstream.  Unlike upstream the
+// current device state is fetched first (the reference re-uploads a stale host copy in CUDA mode).
+// particleSystem.cpp:928-961.  The reference edits its host copy from `start` on and copies that range to the
+// device -- after update() the host copy is stale there, so the edit rewinds every particle it copies (SURVEY
+// A.2).  Here only the sphere's own particles change, on the device (sph_set_by_index).
+void ParticleSystem::addSphere(int start, float* pos, float* vel, int r, float spacing) {
+    (void)vel;
+    const std::vector<float> xyz = spherePoints(pos, r, spacing, (uint)start < m_numParticles ? m_numParticles - (uint)start : 0u);
     std::vector<float> xyzw(xyz.size() / 3 * 4);
     for (size_t k = 0; k < xyz.size() / 3; k++) {
         xyzw[4 * k] = xyz[3 * k]; xyzw[4 * k + 1] = xyz[3 * k + 1]; xyzw[4 * k + 2] = xyz[3 * k + 2]; xyzw[4 * k + 3] = 1.f;
@@ -279,9 +299,47 @@ void ParticleSystem::addSphere(int start, float* pos, float* vel, int r, float s
     setArray(POSITION, xyzw.data(), start, (int)(xyz.size() / 3));
 }
 
+// ---- emitters and drains (additive; sph_emit / sph_remove) --------------------------------------------------------------------
+int ParticleSystem::addParticles(const float* pos, const float* vel, int n) {
+    if (n < 0 || !pos) { fprintf(stderr, "ParticleSystem::addParticles: bad arguments\n"); exit(EXIT_FAILURE); }
+    std::vector<float> xyz((size_t)n * 3), vxyz((size_t)n * 3, 0.f);
+    for (size_t i = 0; i < (size_t)n; i++)
+        for (int a = 0; a < 3; a++) { xyz[3 * i + a] = pos[4 * i + a]; if (vel) vxyz[3 * i + a] = vel[4 * i + a]; }
+    uint32_t first = 0;
+    SPH_CHECK(sph_emit(m_ctx, (uint32_t)n, xyz.data(), vxyz.data(), nullptr, &first));
+    m_numParticles = sph_num_particles(m_ctx);
+    m_hostStale = true;
+    return (int)first;
+}
+
+int ParticleSystem::emitSphere(const float* pos, const float* vel, int r, float spacing) {
+    const std::vector<float> xyz = spherePoints(pos, r, spacing, 0xFFFFFFFFu);
+    const size_t k = xyz.size() / 3;
+    std::vector<float> vxyz(k * 3, 0.f);
+    if (vel) for (size_t i = 0; i < k; i++) for (int a = 0; a < 3; a++) vxyz[3 * i + a] = vel[a];
+    SPH_CHECK(sph_emit(m_ctx, (uint32_t)k, xyz.data(), vxyz.data(), nullptr, nullptr));
+    m_numParticles = sph_num_particles(m_ctx);
+    m_hostStale = true;
+    return (int)k;
+}
+
+int ParticleSystem::removeParticles(const sph_region* regions, int n) {
+    uint32_t removed = 0;
+    SPH_CHECK(sph_remove(m_ctx, (uint32_t)(n < 0 ? 0 : n), regions, &removed, nullptr, 0));
+    m_numParticles = sph_num_particles(m_ctx);
+    if (removed) m_hostStale = true;
+    return (int)removed;
+}
+
+int ParticleSystem::countParticles(const sph_region* regions, int n) {
+    uint32_t count = 0;
+    SPH_CHECK(sph_count_in_regions(m_ctx, (uint32_t)(n < 0 ? 0 : n), regions, &count));
+    return (int)count;
+}
+
 void ParticleSystem::dumpParticles(uint start, uint count) {   // particleSystem.cpp:819-827
     downloadAll();
-    for (uint i = start; i < start + count && i < m_numParticles; i++)
+    for (uint i = start; i < start + count && i < m_capacity; i++)     // rows are creation indices: one without a particle is zeros
         printf("pos: (%.4f, %.4f, %.4f, %.4f)\n", m_hPos[i * 4 + 0], m_hPos[i * 4 + 1], m_hPos[i * 4 + 2], m_hPos[i * 4 + 3]);
 }
 
@@ -293,8 +351,8 @@ float* ParticleSystem::getArray(ParticleArray array) {
 }
 
 void ParticleSystem::setArray(ParticleArray array, const float* data, int start, int count) {
-    if (start < 0 || count < 0 || (size_t)start + (size_t)count > m_numParticles) {
-        fprintf(stderr, "ParticleSystem::setArray: range [%d, %d) outside 0..%u\n", start, start + count, m_numParticles);
+    if (start < 0 || count < 0 || (size_t)start + (size_t)count > m_capacity) {
+        fprintf(stderr, "ParticleSystem::setArray: range [%d, %d) outside 0..%u\n", start, start + count, m_capacity);
         exit(EXIT_FAILURE);
     }
     if (count == 0) return;
@@ -343,8 +401,8 @@ void ParticleSystem::saveState(const std::string& path) { SPH_CHECK(sph_snapshot
 void ParticleSystem::loadState(const std::string& path) {
     SPH_CHECK(sph_snapshot_load(m_ctx, path.c_str()));
     m_numParticles = sph_num_particles(m_ctx);
-    m_hPos.assign((size_t)m_numParticles * 4, 0.f);
-    m_hVel.assign((size_t)m_numParticles * 4, 0.f);
+    m_hPos.assign((size_t)m_capacity * 4, 0.f);
+    m_hVel.assign((size_t)m_capacity * 4, 0.f);
     m_hostStale = true;
 }
 

@@ -539,9 +539,11 @@ int sph_upload(sph_ctx* c, uint32_t n, const float* pos, const float* vel, const
     SPH_REQUIRE(n == 0 || pos, SPH_E_INVALID, "null positions");
     SPH_HIP(hipSetDevice(c->device));
     std::vector<float4> hp(n), hv(n);
+    uint32_t next_index = 0;
     for (uint32_t i = 0; i < n; i++) {
         uint32_t idx = index ? index[i] : i;
         if (!c->slab) SPH_REQUIRE(idx < c->pos_out_cap, SPH_E_INVALID, "creation index %u >= capacity %u", idx, c->pos_out_cap);
+        if (idx >= next_index) next_index = idx + 1u;        // (a slab's index 0xFFFFFFFF wraps: slabs never emit)
         float w;
         memcpy(&w, &idx, 4);
         hp[i] = make_float4(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], w);
@@ -569,6 +571,7 @@ int sph_upload(sph_ctx* c, uint32_t n, const float* pos, const float* vel, const
         }
     }
     SPH_HIP(hipStreamSynchronize(c->stream));
+    c->next_index = next_index;
     c->stage = sph_ctx::ST_LOADED;
     c->keys_fresh = false;
     c->order_valid = false;     // the slots no longer follow the last sort
@@ -630,6 +633,7 @@ int sph_reset_lattice(sph_ctx* c, const uint32_t lattice[3], int jitter, const f
     c->n = count; c->n_glo = c->n_ghi = 0;
     rc = launch_reset_lattice(c, lattice, jitter, jitter_dims, start, count);
     if (rc) return rc;
+    c->next_index = (uint32_t)(start + count);
     c->stage = sph_ctx::ST_LOADED;
     c->keys_fresh = false;
     c->order_valid = false;     // the slots no longer follow the last sort
@@ -712,8 +716,10 @@ int sph_download_forces(sph_ctx* c, uint32_t base, uint32_t n_out, float* fp, fl
 
 // ---- snapshots --------------------------------------------------------------------------------------------
 // layout: u32 magic 'SPHS', u32 version, u32 n, u32 sizeof(sph_params), sph_params, then n float4 posi
-// (x, y, z, creation index bits) and n float4 velr, both in slot order.
-static const uint32_t kSnapMagic = 0x53485053u, kSnapVersion = 1u;
+// (x, y, z, creation index bits) and n float4 velr, both in slot order.  Behind them an OPTIONAL trailer of two words,
+// u32 'SPHN' and the context's next unused creation index (sph_emit): a file without it (older writers) or a reader that
+// stops after the records (older readers) still work; the load then takes one past the highest stored index.
+static const uint32_t kSnapMagic = 0x53485053u, kSnapVersion = 1u, kSnapNextTag = 0x4E485053u;
 
 int sph_snapshot_save(sph_ctx* c, const char* path) {
     SPH_REQUIRE(c && path, SPH_E_INVALID, "null argument");
@@ -725,6 +731,8 @@ int sph_snapshot_save(sph_ctx* c, const char* path) {
     const uint32_t hdr[4] = {kSnapMagic, kSnapVersion, c->n, (uint32_t)sizeof(sph_params)};
     bool ok = fwrite(hdr, sizeof(hdr), 1, f) == 1 && fwrite(&c->params, sizeof(sph_params), 1, f) == 1;
     if (c->n) ok = ok && fwrite(hp.data(), sizeof(float4), c->n, f) == c->n && fwrite(hv.data(), sizeof(float4), c->n, f) == c->n;
+    const uint32_t trailer[2] = {kSnapNextTag, c->next_index};
+    ok = ok && fwrite(trailer, sizeof(trailer), 1, f) == 1;
     ok = (fclose(f) == 0) && ok;
     SPH_REQUIRE(ok, SPH_E_INVALID, "short write to %s", path);
     return SPH_OK;
@@ -759,6 +767,8 @@ int sph_snapshot_load(sph_ctx* c, const char* path) {
     if (n > c->cap) { fclose(f); set_error("snapshot holds %u particles, context capacity is %u", n, c->cap); return SPH_E_CAPACITY; }
     std::vector<float4> hp(n), hv(n);
     bool ok = n == 0 || (fread(hp.data(), sizeof(float4), n, f) == n && fread(hv.data(), sizeof(float4), n, f) == n);
+    uint32_t trailer[2] = {0u, 0u};
+    const bool have_next = ok && fread(trailer, sizeof(trailer), 1, f) == 1 && trailer[0] == kSnapNextTag;
     fclose(f);
     SPH_REQUIRE(ok, SPH_E_INVALID, "%s: truncated", path);
     rc = sph_set_params(c, &p);            // rejects a different grid
@@ -766,12 +776,13 @@ int sph_snapshot_load(sph_ctx* c, const char* path) {
     std::vector<float> pos((size_t)n * 3), vel((size_t)n * 3);
     std::vector<uint32_t> idx(n);
     if (!c->slab) {
-        // a whole-domain snapshot numbers its particles 0..n-1, each once: a file that says otherwise is
-        // corrupt (external input -- every by-index buffer of the host class is sized from n)
-        std::vector<bool> seen(n, false);
+        // a whole-domain snapshot numbers its particles below the capacity (0..n-1 unless particles were emitted or removed:
+        // sph_emit, sph_remove), each index once: a file that says otherwise is corrupt (external input -- every by-index
+        // buffer is sized from the capacity)
+        std::vector<bool> seen(c->pos_out_cap, false);
         for (uint32_t i = 0; i < n; i++) {
             const uint32_t k = idx_of(hp[i]);
-            SPH_REQUIRE(k < n && !seen[k], SPH_E_INVALID, "%s: creation index %u of record %u is out of range or repeated", path, k, i);
+            SPH_REQUIRE(k < c->pos_out_cap && !seen[k], SPH_E_INVALID, "%s: creation index %u of record %u is out of range or repeated", path, k, i);
             seen[k] = true;
         }
     }
@@ -780,7 +791,12 @@ int sph_snapshot_load(sph_ctx* c, const char* path) {
         vel[3 * i] = hv[i].x; vel[3 * i + 1] = hv[i].y; vel[3 * i + 2] = hv[i].z;
         idx[i] = idx_of(hp[i]);
     }
-    return sph_upload(c, n, pos.data(), vel.data(), idx.data());
+    rc = sph_upload(c, n, pos.data(), vel.data(), idx.data());
+    if (rc) return rc;
+    // (indices of removed particles stay used; a value past the capacity -- a writer of larger capacity, a damaged file --
+    // means no more than "none left")
+    if (have_next && !c->slab && trailer[1] >= c->next_index) c->next_index = trailer[1] < c->pos_out_cap ? trailer[1] : c->pos_out_cap;
+    return SPH_OK;
 }
 
 int sph_set_colliders(sph_ctx* c, uint32_t n, const sph_collider* colliders) {

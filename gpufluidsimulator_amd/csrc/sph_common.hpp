@@ -104,6 +104,9 @@ struct sph_ctx {
     float4* dvel = nullptr;   // delta_velocity xyz, collision count
     float4* pos_out = nullptr;// (x,y,z,1) by creation index: the gl_pos analogue
     uint32_t pos_out_cap = 0;
+    // the creation index sph_emit hands out next when the caller gives none: one past the highest index uploaded, generated,
+    // loaded or emitted so far (sph_upload and sph_reset_lattice start it again from the set they install; sph_edit.hip)
+    uint32_t next_index = 0;
 
     // sphere colliders (sph_set_colliders): every integrate pushes the particles out of them, the centres advance on the host
     // once per step (sph_pairs.hip: push_out_of_spheres, advance_colliders); none by default

@@ -5,6 +5,16 @@
 //                [-log=benchmark.txt [-logstyle=oscar|frames]] [-file=<snapshot>] [-collider=x,y,z,r[,ux,uy,uz]]
 // -collider: the reference's collider sphere (centre, radius, and a velocity: default at rest), made to push the fluid
 // (ParticleSystem::enableCollider; one sphere, as the reference's UI has).
+//   -emit=x,y,z,r,vx,vy,vz,every   a faucet: before every `every`-th update (0, every, 2 every, ...) a lattice ball of radius r
+//                      spacings (the points of addSphere, spacing 2R) is appended at (x, y, z) with velocity (vx, vy, vz)
+//                      (ParticleSystem::emitSphere) -- unless a particle is still inside the ball's sphere (countParticles), or
+//                      the capacity (-capacity=M, default twice -n) would be exceeded
+//   -drain=x0,y0,z0,x1,y1,z1[,every]   a kill volume: before every `every`-th update (default: each) the particles in the box
+//                      [x0, x1) x [y0, y1) x [z0, z1) are removed (ParticleSystem::removeParticles); with -emit, the emission
+//                      comes first.  With either flag -out writes one row per creation index below the capacity (zeros where
+//                      there is no particle).  One device only.
+//   -add=k,count       before update k, `count` particles at rest at the points of sph_ic_random_box(seed 2024) are appended
+//                      (ParticleSystem::addParticles); needs room (-capacity=M)
 // Several GPUs (no counterpart in the reference, which is a single-device program): -gpus=N cuts the dam into N
 // z-slabs and steps them with sph_slab_step through the C ABI --
 //   -gpus=N            N child PROCESSES, forked before anything touches a GPU, rank r on device r (+ -device=), messages
@@ -396,8 +406,11 @@ int main(int argc, char** argv) {
         printf("usage: sph_headless [-benchmark] [-n=<particles>] [-box=<edge>] [-i=<iterations>] [-device=<id>] [-grid=<cells per axis>] "
                "[-ic=grid|random] [-steps=<per update>] [-gpus=<N> [-onegpu] [-slab] [-lattice=nx,ny,nz] [-protocol=1|3]] "
                "[-dump=<count>] [-log=<file> [-logfreq=<ms>] [-logstyle=oscar|frames]] [-sphere=<update>[,<radius>]] "
-               "[-collider=<x>,<y>,<z>,<radius>[,<ux>,<uy>,<uz>]] [-out=<file>] [-save=<file>] [-load=<file>] [-file=<file>]\n"
-               "  -collider: a solid sphere the fluid flows around, moving at (ux, uy, uz) (default: at rest); one device only\n");
+               "[-collider=<x>,<y>,<z>,<radius>[,<ux>,<uy>,<uz>]] [-emit=<x>,<y>,<z>,<r>,<vx>,<vy>,<vz>,<every>] "
+               "[-drain=<x0>,<y0>,<z0>,<x1>,<y1>,<z1>[,<every>]] [-add=<update>,<count>] [-capacity=<particles>] [-out=<file>] [-save=<file>] [-load=<file>] [-file=<file>]\n"
+               "  -collider: a solid sphere the fluid flows around, moving at (ux, uy, uz) (default: at rest); one device only\n"
+               "  -emit: every <every> updates append a lattice ball of radius <r> spacings at (x, y, z) moving at (vx, vy, vz), if its place is clear\n"
+               "  -drain: every <every> updates (default 1) remove the particles inside the box [x0,x1) x [y0,y1) x [z0,z1); one device only\n");
         return 0;
     }
     const int gpus = value(argc, argv, "gpus") ? atoi(value(argc, argv, "gpus")) : 1;
@@ -411,7 +424,40 @@ int main(int argc, char** argv) {
             return EXIT_FAILURE;
         }
     }
+    // -emit=x,y,z,r,vx,vy,vz,every  and  -drain=x0,y0,z0,x1,y1,z1[,every]
+    float em[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, dr[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    int emitR = 0, emitEvery = 0, drainEvery = 1;
+    const char* emitArg = value(argc, argv, "emit");
+    const char* drainArg = value(argc, argv, "drain");
+    if (emitArg) {
+        float rr = 0.f;
+        const int k = sscanf(emitArg, "%f,%f,%f,%f,%f,%f,%f,%d", &em[0], &em[1], &em[2], &rr, &em[4], &em[5], &em[6], &emitEvery);
+        emitR = (int)rr;
+        if (k != 8 || emitR < 0 || (float)emitR != rr || emitEvery < 1) {
+            fprintf(stderr, "-emit=%s: expected x,y,z,r,vx,vy,vz,every with r a whole number of lattice spacings >= 0 and every >= 1\n", emitArg);
+            return EXIT_FAILURE;
+        }
+    }
+    if (drainArg) {
+        const int k = sscanf(drainArg, "%f,%f,%f,%f,%f,%f,%d", &dr[0], &dr[1], &dr[2], &dr[3], &dr[4], &dr[5], &drainEvery);
+        if ((k != 6 && k != 7) || drainEvery < 1) {
+            fprintf(stderr, "-drain=%s: expected x0,y0,z0,x1,y1,z1 or x0,y0,z0,x1,y1,z1,every with every >= 1\n", drainArg);
+            return EXIT_FAILURE;
+        }
+    }
+    int addAt = -1, addCount = 0;
+    const char* addArg = value(argc, argv, "add");
+    if (addArg && (sscanf(addArg, "%d,%d", &addAt, &addCount) != 2 || addAt < 0 || addCount < 1)) {
+        fprintf(stderr, "-add=%s: expected <update>,<count>\n", addArg);
+        return EXIT_FAILURE;
+    }
     if (gpus > 1 || (gpus == 1 && flag(argc, argv, "slab"))) {     // (-gpus=1 -slab: the same machinery with one rank -- fork, RCCL communicator of one)
+        if (emitArg || drainArg || addArg) {
+            fprintf(stderr, "-emit / -drain / -add are not supported with -gpus=%d%s: sph_emit and sph_remove work on a whole-domain context "
+                            "(the slab step sizes its messages from the previous step's counts); run them on one device\n",
+                    gpus, gpus == 1 ? " -slab" : "");
+            return EXIT_FAILURE;
+        }
         if (colliderArg) {
             fprintf(stderr, "-collider is not supported with -gpus=%d%s: run it on one device, or set the sphere on every rank "
                             "through the library (gpufluidsimulator_amd.slab.NativeSlabSimulation(colliders=...))\n",
@@ -448,8 +494,11 @@ int main(int argc, char** argv) {
         fprintf(stderr, "-device=%d: %s\n", device, sph_last_error());
         return EXIT_FAILURE;
     }
+    uint capacity = numParticles;          // -emit needs room to grow: -capacity=M, default twice -n
+    if (emitArg || addArg) capacity = numParticles < 0x7FFFFFFFu / 2u ? 2u * numParticles : numParticles;
+    if (const char* v = value(argc, argv, "capacity")) capacity = (uint)strtoul(v, nullptr, 10);
     ParticleSystem* psystem = new ParticleSystem(numParticles, make_float3(box, box, box), ParticleSystem::HIP_PARALLEL,
-                                                 uint3{gridDim, gridDim, gridDim});
+                                                 uint3{gridDim, gridDim, gridDim}, capacity);
     psystem->reset(ic);                                   // initParticleSystem, particles.cpp:119-132
     if (const char* v = load) {
         psystem->loadState(v);
@@ -482,7 +531,40 @@ int main(int argc, char** argv) {
         sphereAt = atoi(v);
         if (const char* c = strchr(v, ',')) ballr = atoi(c + 1);
     }
+    // the faucet's ball: as many lattice points as addSphere's loops accept; its place is the sphere around them
+    uint ballPoints = 0, emittedTotal = 0;
+    const uint startParticles = (uint)psystem->getNumParticles();
+    bool fullNoted = false;
+    if (emitArg) {
+        const float sp = psystem->getParticleRadius() * 2.0f;
+        for (int z = -emitR; z <= emitR; z++)
+            for (int y = -emitR; y <= emitR; y++)
+                for (int x = -emitR; x <= emitR; x++) {
+                    const float dx = x * sp, dy = y * sp, dz = z * sp;
+                    if (sqrtf(dx * dx + dy * dy + dz * dz) <= psystem->getParticleRadius() * 2.0f * emitR) ballPoints++;
+                }
+    }
     for (int i = 0; i < iterations; ++i) {
+        if (emitArg && i % emitEvery == 0) {
+            const float pr = psystem->getParticleRadius();
+            sph_region nozzle = {SPH_REGION_SPHERE, {em[0], em[1], em[2]}, {0.f, 0.f, 0.f}, pr + (pr * 2.0f) * emitR};
+            const bool room = (uint64_t)psystem->getNumParticles() + ballPoints <= (uint64_t)psystem->getCapacity() &&
+                              (uint64_t)startParticles + emittedTotal + ballPoints <= (uint64_t)psystem->getCapacity();
+            if (!room && !fullNoted) { fprintf(stderr, "note: -emit stops at update %d: the capacity %d is used up (-capacity=)\n", i, psystem->getCapacity()); fullNoted = true; }
+            if (room && psystem->countParticles(&nozzle, 1) == 0) emittedTotal += (uint)psystem->emitSphere(em, em + 4, emitR, pr * 2.0f);
+        }
+        if (drainArg && i % drainEvery == 0) {
+            sph_region kill = {SPH_REGION_BOX, {dr[0], dr[1], dr[2]}, {dr[3], dr[4], dr[5]}, 0.f};
+            psystem->removeParticles(&kill, 1);
+        }
+        if (i == addAt) {
+            std::vector<float> xyz((size_t)addCount * 3), xyzw((size_t)addCount * 4, 1.0f);
+            const float dims[3] = {box, box, box};
+            sph_ic_random_box((uint64_t)addCount, dims, 0.f, 2024u, 1.0f, xyz.data(), nullptr);
+            for (int k = 0; k < addCount; k++) for (int a = 0; a < 3; a++) xyzw[4 * (size_t)k + a] = xyz[3 * (size_t)k + a];
+            emittedTotal += (uint)addCount;
+            psystem->addParticles(xyzw.data(), nullptr, addCount);
+        }
         if (i == sphereAt) {
             const float pr = psystem->getParticleRadius(), tr = pr + (pr * 2.0f) * ballr;
             float pos[4] = {0.0f, psystem->getBoxMax().y - tr, 0.0f, 0.0f}, vel[4] = {0.f, 0.f, 0.f, 0.f};
@@ -495,6 +577,7 @@ int main(int argc, char** argv) {
     const double secs = std::chrono::duration<double>(t1 - t0).count();
     const double avg = secs / (iterations > 0 ? iterations : 1);
     // the reference's line, particles.cpp:191-192
+    if (emitArg || drainArg || addArg) printf("emitted %u particles, %d left of %u + %u\n", emittedTotal, psystem->getNumParticles(), startParticles, emittedTotal);
     printf("particles, Throughput = %.4f KParticles/s, Time = %.5f s, Size = %u particles, NumDevsUsed = %u, Workgroup = %u\n",
            (1.0e-3 * numParticles) / avg, avg, numParticles, 1, 0);
     printf("{\"particle_steps_per_s\": %.1f, \"particles\": %u, \"iterations\": %d, \"steps_per_update\": %d, \"seconds\": %.6f}\n",
@@ -503,8 +586,9 @@ int main(int argc, char** argv) {
     if (const char* v = value(argc, argv, "out")) {      // xyzw per creation index, then vxyz0, raw fp32
         FILE* f = fopen(v, "wb");
         if (!f) { fprintf(stderr, "cannot open %s\n", v); return EXIT_FAILURE; }
-        fwrite(psystem->getArray(ParticleSystem::POSITION), sizeof(float) * 4, numParticles, f);
-        fwrite(psystem->getArray(ParticleSystem::VELOCITY), sizeof(float) * 4, numParticles, f);
+        const size_t rows = (emitArg || drainArg || addArg) ? (size_t)psystem->getCapacity() : (size_t)numParticles;     // by creation index
+        fwrite(psystem->getArray(ParticleSystem::POSITION), sizeof(float) * 4, rows, f);
+        fwrite(psystem->getArray(ParticleSystem::VELOCITY), sizeof(float) * 4, rows, f);
         fclose(f);
     }
     if (const char* v = value(argc, argv, "save")) psystem->saveState(v);

@@ -14,6 +14,8 @@
 //     gpufluidsimulator_amd/ic.py); the reference's ceil(powf(N,1/3)) + rand() is not portable.
 //   * additive API named by the north star: getArray / setArray / setSimParams, plus
 //     getDensities(), getPositionsDevice(), phaseTimings(), saveState()/loadState().
+//   * additive: particles enter and leave a running system (addParticles / emitSphere / removeParticles, on top of
+//     sph_emit / sph_remove); the reference's particle set is fixed at construction.
 //   * errors abort the process like checkCudaErrors (common/inc/helper_cuda.h:566-579).
 #ifndef SPH_PARTICLESYSTEM_H
 #define SPH_PARTICLESYSTEM_H
@@ -62,6 +64,9 @@ public:
     ParticleSystem(uint numParticles, float3 boxDims, ParticleComputeMode mode);
     // additive: an explicit grid instead of nextPow2(box / (0.66666 h)) per axis (a 0 keeps the formula)
     ParticleSystem(uint numParticles, float3 boxDims, ParticleComputeMode mode, uint3 gridDims);
+    // additive: room for up to `capacity` particles (and creation indices below it), so that addParticles / emitSphere can
+    // grow the system; anything below numParticles means numParticles, the fixed size of the other constructors
+    ParticleSystem(uint numParticles, float3 boxDims, ParticleComputeMode mode, uint3 gridDims, uint capacity);
     ~ParticleSystem();
 
     enum ParticleConfig { CONFIG_RANDOM, CONFIG_GRID, _NUM_CONFIGS };
@@ -69,13 +74,14 @@ public:
 
     // n = m_solverIterations full time steps; fps is only logged (particleSystem.cpp:720,806)
     void update(float deltaTime, float fps);
-    void reset(ParticleConfig config);
+    void reset(ParticleConfig config);                                // back to the constructed count, whatever was emitted or removed
 
-    int getNumParticles() const { return (int)m_numParticles; }
+    int getNumParticles() const { return (int)m_numParticles; }      // follows the context: addParticles / removeParticles change it
+    int getCapacity() const { return (int)m_capacity; }
     unsigned int getCurrentReadBuffer() const { return 0; }   // no GL buffer in headless builds
     unsigned int getColorBuffer() const { return 0; }
 
-    void dumpParticles(uint start, uint count);
+    void dumpParticles(uint start, uint count);                       // rows by creation index, up to getCapacity()
 
     void setIterations(int i) { m_solverIterations = i; }
     void setGravity(float x) { m_params.gravity = make_float3(0.0f, x, 0.0f); }   // a physics no-op, as upstream
@@ -91,6 +97,18 @@ public:
 
     void addSphere(int index, float* pos, float* vel, int r, float spacing);
 
+    // ---- additive: emitters and drains (sph_emit / sph_remove / sph_count_in_regions of sph_hip.h) ---------------------------
+    // Append n particles, 4 floats each like getArray (w ignored; vel may be null: at rest).  They take consecutive creation
+    // indices from the system's next unused one; the first is returned.  Exceeding the capacity aborts like every error here.
+    int addParticles(const float* pos, const float* vel, int n);
+    // The lattice points of addSphere (same loops, same jitter stream) around pos[0..2], APPENDED instead of written over
+    // existing particles, all with the velocity vel[0..2] (null: at rest).  Returns how many particles that were.
+    int emitSphere(const float* pos, const float* vel, int r, float spacing);
+    // Delete the particles inside any of the n regions (1..SPH_MAX_REGIONS); returns how many.  getArray() shows zeros in
+    // the rows of creation indices that hold no particle.
+    int removeParticles(const sph_region* regions, int n);
+    int countParticles(const sph_region* regions, int n);      // the same selection, nothing removed
+
     // ---- additive: the collider sphere pushes the fluid (absent upstream, where it is drawn but inert) -----------------------
     void enableCollider(bool on);
     bool colliderEnabled() const { return m_colliderOn; }
@@ -99,7 +117,7 @@ public:
     float3 getColliderVelocity() const { return m_colliderVel; }
 
     // ---- additive (absent upstream; named by BASELINE.json's north star) ------------------------
-    // 4 floats per particle, by creation index (the original NVIDIA sample's layout); the pointer
+    // 4 floats per particle, by creation index (the original NVIDIA sample's layout), getCapacity() rows; the pointer
     // stays valid until the next getArray call.
     float* getArray(ParticleArray array);
     void setArray(ParticleArray array, const float* data, int start, int count);
@@ -129,11 +147,15 @@ protected:
     void _finalize();
     void uploadAll();
     void downloadAll();
+    std::vector<float> spherePoints(const float* pos, int r, float spacing, uint limit);
 
     bool m_bInitialized;
     uint m_numParticles;
+    uint m_numInitial;                               // what the constructor was given: reset() goes back to it
+    uint m_capacity;                                 // rows of the by-index mirrors = capacity of the context
     std::vector<float> m_hPos, m_hVel, m_hDens;     // host mirrors: xyzw, xyzw, scalar
     std::vector<float> m_xyz, m_vxyz;                // packed xyz staging for the C ABI
+    std::vector<uint32_t> m_live;                    // creation indices of the owned particles (downloadAll)
     SimParams m_params;
     float3 m_boxDims;
     uint3 m_grid;

@@ -29,7 +29,7 @@
  *                  sph_set_params sph_get_params sph_sync sph_num_particles sph_capacity sph_ghost_layers sph_set_precision
  *                  sph_get_precision | sph_upload sph_set_by_index sph_reset_lattice sph_download sph_download_owned
  *                  sph_positions_dev sph_download_positions4 sph_snapshot_save sph_snapshot_load sph_snapshot_info |
- *                  sph_set_colliders sph_get_colliders |
+ *                  sph_set_colliders sph_get_colliders | sph_emit sph_remove sph_count_in_regions |
  *                  sph_hash sph_sort sph_build_cells sph_density sph_force sph_collide sph_integrate sph_step sph_step_phased
  *                  sph_force_collide_integrate | sph_timing_enable sph_timing_get sph_timing_reset | the z-slab phase calls
  *                  (sph_migrants_* sph_slab_counts sph_halo_* sph_layer_histogram) | sph_rccl_unique_id
@@ -242,12 +242,62 @@ int sph_set_colliders(sph_ctx* c, uint32_t n, const sph_collider* colliders);
 /* The current set with the ADVANCED centres: *n spheres into out (room for SPH_MAX_COLLIDERS; may be NULL if only *n is wanted). */
 int sph_get_colliders(const sph_ctx* c, uint32_t* n, sph_collider* out);
 
+/* ---- emitters and drains: particles enter and leave a running simulation (no counterpart in the reference, whose particle
+ *      set is fixed at construction; sph_set_by_index, its addSphere, only rewrites particles that exist) -----------------------
+ * Whole-domain contexts only: on a slab context all three calls return SPH_E_STATE (the slab step sizes its messages from the
+ * previous step's counts, and the ranks would have to agree on who owns a new particle); the reference seam has none.
+ *
+ * A REGION selects particles by position x (fp32, every operation rounded, no multiply-add fusion, sums left to right:
+ * tests/region_model.py is the same arithmetic in numpy and decides every particle identically):
+ *   SPH_REGION_SPHERE     centre a, radius r:      d = x - a;  d.x*d.x + d.y*d.y + d.z*d.z < r*r                 (strict)
+ *   SPH_REGION_BOX        corners a, b:            a[k] <= x[k] && x[k] < b[k] on all three axes  (half open: boxes that share
+ *                                                  a face partition space)
+ *   SPH_REGION_HALFSPACE  point a, normal b:       (x[0]-a[0])*b[0] + (x[1]-a[1])*b[1] + (x[2]-a[2])*b[2] < 0     (strict: the
+ *                                                  side the normal points AWAY from)
+ * A call takes 1..SPH_MAX_REGIONS regions and selects a particle that lies in ANY of them.  A kind outside the enum, or a
+ * field its kind uses (sphere: a, r; box and half-space: a, b) that is not finite: SPH_E_INVALID. */
+#define SPH_MAX_REGIONS 8
+enum { SPH_REGION_SPHERE = 0, SPH_REGION_BOX = 1, SPH_REGION_HALFSPACE = 2 };
+typedef struct sph_region {
+    int32_t kind;
+    float a[3];
+    float b[3];
+    float r;
+} sph_region;   /* 32 bytes */
+/* Append n particles (xyz triples; vel_xyz NULL = at rest) behind the owned ones.  index[i] is the creation index of particle
+ * i; that no two live particles share an index is the CALLER's duty, as in sph_upload.  index = NULL hands out consecutive
+ * indices from the context's next unused one -- one past the highest index uploaded, generated (sph_reset_lattice), loaded
+ * (sph_snapshot_load) or emitted so far; sph_upload and sph_reset_lattice start it again from the set they install.  The first
+ * index goes to *first_index_out (may be NULL).  The by-index position buffer (sph_positions_dev) shows (x, y, z, 1) at once.
+ *   SPH_E_CAPACITY  n + sph_num_particles > capacity, or (index = NULL) an index would reach the capacity, which is the size
+ *                   of the by-index buffers: a long faucet-plus-drain run passes the indices sph_remove returned;
+ *   SPH_E_INVALID   a position that is not finite or outside [box_min, box_max], a velocity that is not finite, an explicit
+ *                   index >= capacity.
+ * On any error nothing has changed.  The new particles sit behind the sorted range, so the NEXT sort is the full stable sort
+ * (not the merge): within a cell the residents come first, the emitted particles behind them in call order -- the order an
+ * sph_upload of the same particles in the same sequence gives, bit for bit.  Copies from host memory: synchronises. */
+int sph_emit(sph_ctx* c, uint32_t n, const float* pos_xyz, const float* vel_xyz, const uint32_t* index,
+             uint32_t* first_index_out);
+/* Delete the owned particles the regions select.  The survivors keep their relative slot order (a stable compaction on the
+ * device), so the range stays in the order of the last sort and the next sort may take the merge path.  *n_removed (may be
+ * NULL) is the number deleted; removed_index (may be NULL) receives the creation indices of the first min(n_removed, max_out)
+ * of them in slot order; the row of each removed particle in the by-index position buffer becomes (0, 0, 0, 0), what
+ * sph_upload writes for an index without a particle.  Densities and forces of the current step are dropped: until the next
+ * step sph_download gives density and pressure 0 for every survivor (as for an emitted particle), and that step starts with
+ * sph_hash, as after sph_set_by_index.  With nothing selected the context is left exactly as it was -- the next
+ * step does what it would have done without the call.  Returns data to the host: synchronises. */
+int sph_remove(sph_ctx* c, uint32_t n_regions, const sph_region* regions, uint32_t* n_removed, uint32_t* removed_index,
+               uint32_t max_out);
+/* The same selection without the removal -- a sensor: a fill level, "is the nozzle clear".  Changes nothing; synchronises. */
+int sph_count_in_regions(sph_ctx* c, uint32_t n_regions, const sph_region* regions, uint32_t* count);
+
 /* State snapshot (checkpoint / resume; absent in the reference, whose device state is never
  * serialised -- SURVEY.md section 5).  The file holds the parameters and, IN SLOT ORDER, position,
  * velocity and creation index of every owned particle, so that a resumed run repeats the
- * original one bit for bit (the sort is stable).  Little-endian, see csrc/sph_capi.hip. */
+ * original one bit for bit (the sort is stable), and behind them the next unused creation index (sph_emit; files without it
+ * load as before).  Little-endian, see csrc/sph_capi.hip. */
 int sph_snapshot_save(sph_ctx* c, const char* path);
-/* Load into an existing context (same grid; capacity >= the stored particle count). */
+/* Load into an existing context (same grid; capacity >= the stored particle count and > every stored creation index). */
 int sph_snapshot_load(sph_ctx* c, const char* path);
 /* Number of particles and the parameters stored in a snapshot (to size a context for it). */
 int sph_snapshot_info(const char* path, uint32_t* n, sph_params* p);
