@@ -111,6 +111,21 @@ static int dev_alloc(T** p, size_t count) {
     return SPH_OK;
 }
 
+// an array that starts as zeros
+template <class T>
+static int dev_alloc_zero(T** p, size_t count) {
+    int rc = dev_alloc(p, count);
+    if (rc) return rc;
+    if (hipMemset(*p, 0, count * sizeof(T)) != hipSuccess) {
+        hipFree(*p);
+        *p = nullptr;
+        set_error("hipMemset of %zu bytes failed", count * sizeof(T));
+        return SPH_E_DEVICE;
+    }
+    return SPH_OK;
+}
+
+// every array create_impl allocates (keep the two lists in step)
 static void free_all(sph_ctx* c) {
     hipFree(c->posi); hipFree(c->velr); hipFree(c->posi2); hipFree(c->velr2); hipFree(c->keyS); hipFree(c->dp); hipFree(c->cw);
     hipFree(c->fpress); hipFree(c->fvisc); hipFree(c->dvel); hipFree(c->pos_out); hipFree(c->cells_base);
@@ -153,22 +168,24 @@ static int create_impl(sph_ctx** out, int device, uint32_t capacity, const sph_p
     c->own_off = gcap;
     c->sort_blocks_cap = ceil_div(capacity, SORT_TILE_KEYS) + 1;
     c->pos_out_cap = slab ? 0 : capacity;
+    // The arrays: every one of them is in free_all's list as well.  dev_alloc_zero for those a kernel may read before any
+    // kernel wrote them (padding slots, look-back words, tickets, counts); the others are written first.
     // + 2*PIECE entries: the pair kernels stage whole 128-entry pieces without bounds predicates
     const size_t tot = (size_t)c->tot + 256;
-    rc = dev_alloc(&c->posi, tot);
-    if (!rc) rc = dev_alloc(&c->velr, tot);
-    if (!rc) rc = dev_alloc(&c->posi2, tot);
-    if (!rc) rc = dev_alloc(&c->velr2, tot);
-    if (!rc) rc = dev_alloc(&c->keyS, tot);
-    if (!rc) rc = dev_alloc(&c->keyS2, tot);
-    if (!rc) rc = dev_alloc(&c->dp, tot);
-    if (!rc) rc = dev_alloc(&c->cw, tot);
+    rc = dev_alloc_zero(&c->posi, tot);
+    if (!rc) rc = dev_alloc_zero(&c->velr, tot);
+    if (!rc) rc = dev_alloc_zero(&c->posi2, tot);
+    if (!rc) rc = dev_alloc_zero(&c->velr2, tot);
+    if (!rc) rc = dev_alloc_zero(&c->keyS, tot);
+    if (!rc) rc = dev_alloc_zero(&c->keyS2, tot);
+    if (!rc) rc = dev_alloc_zero(&c->dp, tot);
+    if (!rc) rc = dev_alloc_zero(&c->cw, tot);
     if (!rc) rc = dev_alloc(&c->fpress, tot);
     if (!rc) rc = dev_alloc(&c->fvisc, tot);
     if (!rc) rc = dev_alloc(&c->dvel, tot);
     if (!rc) rc = dev_alloc(&c->pos_out, (size_t)c->pos_out_cap);
     // one guard entry on either side: the pair kernels read cells[key - 1 .. key + 1] of a row unconditionally
-    if (!rc) rc = dev_alloc(&c->cells_base, (size_t)c->grid.ncells + 2);
+    if (!rc) rc = dev_alloc_zero(&c->cells_base, (size_t)c->grid.ncells + 2);
     if (!rc) { c->cells = c->cells_base + 1; c->cells_alloc = c->grid.ncells; }
     if (!rc) rc = dev_alloc(&c->k0, (size_t)capacity);
     if (!rc) rc = dev_alloc(&c->v0, (size_t)capacity);
@@ -176,12 +193,12 @@ static int create_impl(sph_ctx** out, int device, uint32_t capacity, const sph_p
     if (!rc) rc = dev_alloc(&c->v1, (size_t)capacity);
     const size_t os_groups = (size_t)c->sort_blocks_cap / 4 + 3;   // enough for groups of >= 4 tiles
     c->os_groups_cap = (uint32_t)os_groups;
-    if (!rc) rc = dev_alloc(&c->os_hist, os_groups * 4 * 512);
+    if (!rc) rc = dev_alloc_zero(&c->os_hist, os_groups * 4 * 512);
     if (!rc) rc = dev_alloc(&c->os_base, os_groups * 4 * 512);
-    if (!rc) rc = dev_alloc(&c->os_tickets, (size_t)4 * os_groups);
+    if (!rc) rc = dev_alloc_zero(&c->os_tickets, (size_t)4 * os_groups);
     if (!rc) rc = dev_alloc(&c->os_tot, (size_t)4 * 512);
-    if (!rc) rc = dev_alloc(&c->os_status, (size_t)512 * c->sort_blocks_cap);
-    if (!rc) rc = dev_alloc(&c->os_status32, (size_t)512 * c->sort_blocks_cap);
+    if (!rc) rc = dev_alloc_zero(&c->os_status, (size_t)512 * c->sort_blocks_cap);
+    if (!rc) rc = dev_alloc_zero(&c->os_status32, (size_t)512 * c->sort_blocks_cap);
     if (!rc) rc = dev_alloc(&c->mm_tileL, (size_t)c->sort_blocks_cap + 2);
     if (!rc) rc = dev_alloc(&c->mm_tileA, (size_t)c->sort_blocks_cap + 2);
     if (!rc && (hipHostMalloc((void**)&c->os_err_host, sizeof(uint32_t), hipHostMallocMapped) != hipSuccess ||
@@ -189,18 +206,7 @@ static int create_impl(sph_ctx** out, int device, uint32_t capacity, const sph_p
         set_error("hipHostMalloc(mapped) failed");
         rc = SPH_E_NOMEM;
     }
-    if (!rc) {
-        *c->os_err_host = 0;
-        if (hipMemset(c->os_status, 0, (size_t)512 * c->sort_blocks_cap * sizeof(unsigned long long)) != hipSuccess ||
-            hipMemset(c->os_status32, 0, (size_t)512 * c->sort_blocks_cap * sizeof(uint32_t)) != hipSuccess ||
-            hipMemset(c->os_tickets, 0, 4 * os_groups * sizeof(uint32_t)) != hipSuccess ||
-            hipMemset(c->os_hist, 0, os_groups * 4 * 512 * sizeof(uint32_t)) != hipSuccess ||
-            hipMemset(c->keyS, 0, tot * sizeof(uint32_t)) != hipSuccess ||
-            hipMemset(c->keyS2, 0, tot * sizeof(uint32_t)) != hipSuccess) {
-            set_error("hipMemset failed");
-            rc = SPH_E_DEVICE;
-        }
-    }
+    if (!rc) *c->os_err_host = 0;
     if (!rc) rc = dev_alloc(&c->d_scratch, (size_t)64);
     if (!rc && hipHostMalloc((void**)&c->h_scratch, 64 * sizeof(uint32_t)) != hipSuccess) {
         set_error("hipHostMalloc failed");
@@ -223,13 +229,13 @@ static int create_impl(sph_ctx** out, int device, uint32_t capacity, const sph_p
         const size_t nchunks = (size_t)ceil_div(capacity, 64u) + 1, ntiles = nchunks / 256 + 2;
         if (!rc) rc = dev_alloc(&c->mm_mask, nchunks);
         if (!rc) rc = dev_alloc(&c->mm_M64, nchunks);
-        if (!rc) rc = dev_alloc(&c->mm_tile_cnt, ntiles);
+        if (!rc) rc = dev_alloc_zero(&c->mm_tile_cnt, ntiles);
         if (!rc) rc = dev_alloc(&c->mm_tile_off, ntiles);
         if (!rc) rc = dev_alloc(&c->mm_k0, (size_t)capacity);
         if (!rc) rc = dev_alloc(&c->mm_k1, (size_t)capacity);
         if (!rc) rc = dev_alloc(&c->mm_v1, (size_t)capacity);
-        if (!rc) rc = dev_alloc(&c->mm_count, (size_t)1);
-        if (!rc) rc = dev_alloc(&c->mm_total, (size_t)1);
+        if (!rc) rc = dev_alloc_zero(&c->mm_count, (size_t)1);
+        if (!rc) rc = dev_alloc_zero(&c->mm_total, (size_t)1);
         if (!rc && (hipHostMalloc((void**)&c->mm_count_host, 8 * sizeof(uint32_t), hipHostMallocMapped) != hipSuccess ||
                     hipHostGetDevicePointer((void**)&c->mm_count_host_dev, c->mm_count_host, 0) != hipSuccess)) {
             set_error("hipHostMalloc(mapped) failed");
@@ -239,26 +245,7 @@ static int create_impl(sph_ctx** out, int device, uint32_t capacity, const sph_p
             c->mm_count_host[0] = 0;
             c->mm_count_host[1] = 1; c->mm_count_host[2] = 0;          // "no estimate yet" (first key > last key)
             for (int k = 3; k < 8; k++) c->mm_count_host[k] = 0;
-            if (hipMemset(c->mm_tile_cnt, 0, ntiles * sizeof(uint32_t)) != hipSuccess ||
-                hipMemset(c->mm_count, 0, sizeof(uint32_t)) != hipSuccess ||
-                hipMemset(c->mm_total, 0, sizeof(unsigned long long)) != hipSuccess) {
-                set_error("hipMemset failed");
-                rc = SPH_E_DEVICE;
-            }
         }
-    }
-    if (!rc && hipMemset(c->cells_base, 0, ((size_t)c->grid.ncells + 2) * sizeof(uint2)) != hipSuccess) {
-        set_error("hipMemset(cells) failed");
-        rc = SPH_E_DEVICE;
-    }
-    if (!rc && (hipMemset(c->dp, 0, tot * sizeof(float2)) != hipSuccess ||
-                hipMemset(c->cw, 0, tot * sizeof(float2)) != hipSuccess ||
-                hipMemset(c->posi, 0, tot * sizeof(float4)) != hipSuccess ||
-                hipMemset(c->velr, 0, tot * sizeof(float4)) != hipSuccess ||
-                hipMemset(c->posi2, 0, tot * sizeof(float4)) != hipSuccess ||
-                hipMemset(c->velr2, 0, tot * sizeof(float4)) != hipSuccess)) {
-        set_error("hipMemset failed");
-        rc = SPH_E_DEVICE;
     }
     if (rc) { free_all(c); delete c; return rc; }
     *out = c;
@@ -286,7 +273,7 @@ static int do_hash(sph_ctx* c) {
     // cells the movers leave can become empty, and the sort clears just those (the table is rebuilt by the
     // sort's reorder pass over exactly the same owned slots).  The cells of a slab's old ghosts die here.
     const uint32_t lo = c->own_off - c->n_glo, hi = c->own_off + c->n + c->n_ghi;
-    c->cells_clear_deferred = c->sort_merge && c->order_valid && c->cells_valid && c->cells_lo == lo && c->cells_hi == hi;
+    c->cells_clear_deferred = c->sort_merge && c->order_valid && table_covers(c, lo, hi);
     int rc;
     c->ghost_clear_pending = false;
     if (c->cells_clear_deferred && c->defer_ghost_clear && (c->n_glo | c->n_ghi)) {
@@ -316,14 +303,14 @@ static int do_sort(sph_ctx* c) {
     c->n_glo = c->n_ghi = 0;
     c->halo_n_valid = false;
     c->stage = sph_ctx::ST_SORTED;
-    c->have_dens = c->have_force = c->have_coll = false;
+    results_stale(c);
     return SPH_OK;
 }
 
 static int do_cells(sph_ctx* c) {
     PhaseTimer t(c, SPH_PH_BGRID);
     const uint32_t lo = c->own_off - c->n_glo, hi = c->own_off + c->n + c->n_ghi;
-    if (!(c->cells_valid && c->cells_lo == lo && c->cells_hi == hi)) {   // whole-domain: built by the sort's reorder pass
+    if (!table_covers(c, lo, hi)) {   // whole-domain: built by the sort's reorder pass
         int rc = launch_cells_build(c);      // slab: adds the ghost cells to the owned ones the sort built
         if (rc) return rc;
     }
@@ -359,21 +346,16 @@ int set_slab_range(sph_ctx* c, uint32_t z_lo, uint32_t z_hi) {
     if (tmp.grid.ncells > c->cells_alloc) {
         SPH_HIP(hipStreamSynchronize(c->stream));
         uint2* base = nullptr;
-        rc = dev_alloc(&base, (size_t)tmp.grid.ncells + 2);
+        rc = dev_alloc_zero(&base, (size_t)tmp.grid.ncells + 2);
         if (rc) return rc;
-        if (hipMemset(base, 0, ((size_t)tmp.grid.ncells + 2) * sizeof(uint2)) != hipSuccess) {
-            hipFree(base);
-            set_error("set_slab_range: clearing the new cell table failed");
-            return SPH_E_DEVICE;
-        }
         hipFree(c->cells_base);
         c->cells_base = base; c->cells = base + 1; c->cells_alloc = tmp.grid.ncells;
     }
     c->grid = tmp.grid; c->z_lo = z_lo; c->z_hi = z_hi; c->key_bits = tmp.key_bits;
     c->cells_valid = false; c->cells_clear_deferred = false;
-    c->keys_fresh = false; c->order_valid = false;
-    c->stage = sph_ctx::ST_LOADED;
-    c->have_dens = c->have_force = c->have_coll = false;
+    order_lost(c);
+    // (no mover_count_unknown, kept as found: the slab step is host-paced and never reads it, and the next sort is the full one)
+    results_stale(c);
     c->n_glo = c->n_ghi = 0;
     c->halo_n_valid = false;
     return SPH_OK;
@@ -404,6 +386,46 @@ __global__ __launch_bounds__(256) void k_gather_cells(const uint32_t* __restrict
                                                       const uint2* __restrict__ cells, uint2* __restrict__ out) {
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
     if (k < m) out[k] = cells[keys[k]];
+}
+
+static inline uint32_t idx_of(const float4& p) { uint32_t u; memcpy(&u, &p.w, 4); return u; }
+
+// The body of sph_upload, and of sph_snapshot_load (whose file holds these records): the context's particles become the n
+// records hp / hv (pack_records), in this slot order.
+static int install_records(sph_ctx* c, uint32_t n, const float4* hp, const float4* hv) {
+    SPH_REQUIRE(n <= c->cap, SPH_E_CAPACITY, "%u particles > capacity %u", n, c->cap);
+    SPH_HIP(hipSetDevice(c->device));
+    uint32_t next_index = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t idx = idx_of(hp[i]);
+        if (!c->slab) SPH_REQUIRE(idx < c->pos_out_cap, SPH_E_INVALID, "creation index %u >= capacity %u", idx, c->pos_out_cap);
+        if (idx >= next_index) next_index = idx + 1u;        // (a slab's index 0xFFFFFFFF wraps: slabs never emit)
+    }
+    SPH_HIP(hipStreamSynchronize(c->stream));
+    int rc = launch_cells_clear(c);
+    if (rc) return rc;
+    c->own_off = c->gcap;
+    c->n = n; c->n_glo = c->n_ghi = 0;
+    if (n) {
+        SPH_HIP(hipMemcpyAsync(c->posi + c->own_off, hp, n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+        SPH_HIP(hipMemcpyAsync(c->velr + c->own_off, hv, n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+        SPH_HIP(hipMemsetAsync(c->dp + c->own_off, 0, n * sizeof(float2), c->stream));
+        SPH_HIP(hipMemsetAsync(c->cw + c->own_off, 0, n * sizeof(float2), c->stream));
+        if (!c->slab) {
+            // gl_pos starts as the initial positions (initGrid writes m_hPos, particleSystem.cpp:865-868)
+            std::vector<float4> ho(c->pos_out_cap, make_float4(0.f, 0.f, 0.f, 0.f));
+            for (uint32_t i = 0; i < n; i++) ho[idx_of(hp[i])] = make_float4(hp[i].x, hp[i].y, hp[i].z, 1.0f);
+            SPH_HIP(hipMemcpyAsync(c->pos_out, ho.data(), ho.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+            SPH_HIP(hipStreamSynchronize(c->stream));
+        }
+    }
+    SPH_HIP(hipStreamSynchronize(c->stream));
+    c->next_index = next_index;
+    // (no mm_drop_marks, kept as found: the next sort is the full one, whose own branch scans and forgets the marks)
+    order_lost(c);
+    mover_count_unknown(c);
+    results_stale(c);
+    return SPH_OK;
 }
 
 extern "C" {
@@ -510,9 +532,11 @@ int sph_set_params(sph_ctx* c, const sph_params* p) {
     int rc = derive(&tmp, p, c->z_lo, c->z_hi, c->slab);
     if (rc) return rc;
     c->params = tmp.params; c->grid = tmp.grid; c->phys = tmp.phys;
-    c->keys_fresh = false;      // the box may have moved: keys of the old box are stale
+    // the box may have moved: keys of the old box are stale.  Not order_lost(): the stage and the results stay (no position
+    // changed; a caller between two phases goes on where it was)
+    c->keys_fresh = false;
     c->order_valid = false;
-    c->sort_form_both_until = c->sort_calls + 5;
+    mover_count_unknown(c);
     return SPH_OK;
 }
 
@@ -535,49 +559,11 @@ uint32_t sph_capacity(const sph_ctx* c) { return c ? c->cap : 0; }
 
 int sph_upload(sph_ctx* c, uint32_t n, const float* pos, const float* vel, const uint32_t* index) {
     SPH_REQUIRE(c, SPH_E_INVALID, "null context");
-    SPH_REQUIRE(n <= c->cap, SPH_E_CAPACITY, "%u particles > capacity %u", n, c->cap);
+    SPH_REQUIRE(n <= c->cap, SPH_E_CAPACITY, "%u particles > capacity %u", n, c->cap);   // (reported before a null array, as ever)
     SPH_REQUIRE(n == 0 || pos, SPH_E_INVALID, "null positions");
-    SPH_HIP(hipSetDevice(c->device));
     std::vector<float4> hp(n), hv(n);
-    uint32_t next_index = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        uint32_t idx = index ? index[i] : i;
-        if (!c->slab) SPH_REQUIRE(idx < c->pos_out_cap, SPH_E_INVALID, "creation index %u >= capacity %u", idx, c->pos_out_cap);
-        if (idx >= next_index) next_index = idx + 1u;        // (a slab's index 0xFFFFFFFF wraps: slabs never emit)
-        float w;
-        memcpy(&w, &idx, 4);
-        hp[i] = make_float4(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], w);
-        hv[i] = vel ? make_float4(vel[3 * i], vel[3 * i + 1], vel[3 * i + 2], 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    SPH_HIP(hipStreamSynchronize(c->stream));
-    int rc = launch_cells_clear(c);
-    if (rc) return rc;
-    c->own_off = c->gcap;
-    c->n = n; c->n_glo = c->n_ghi = 0;
-    if (n) {
-        SPH_HIP(hipMemcpyAsync(c->posi + c->own_off, hp.data(), n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-        SPH_HIP(hipMemcpyAsync(c->velr + c->own_off, hv.data(), n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-        SPH_HIP(hipMemsetAsync(c->dp + c->own_off, 0, n * sizeof(float2), c->stream));
-        SPH_HIP(hipMemsetAsync(c->cw + c->own_off, 0, n * sizeof(float2), c->stream));
-        if (!c->slab) {
-            // gl_pos starts as the initial positions (initGrid writes m_hPos, particleSystem.cpp:865-868)
-            std::vector<float4> ho(c->pos_out_cap, make_float4(0.f, 0.f, 0.f, 0.f));
-            for (uint32_t i = 0; i < n; i++) {
-                uint32_t idx = index ? index[i] : i;
-                ho[idx] = make_float4(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], 1.0f);
-            }
-            SPH_HIP(hipMemcpyAsync(c->pos_out, ho.data(), ho.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-            SPH_HIP(hipStreamSynchronize(c->stream));
-        }
-    }
-    SPH_HIP(hipStreamSynchronize(c->stream));
-    c->next_index = next_index;
-    c->stage = sph_ctx::ST_LOADED;
-    c->keys_fresh = false;
-    c->order_valid = false;     // the slots no longer follow the last sort
-    c->sort_form_both_until = c->sort_calls + 5;
-    c->have_dens = c->have_force = c->have_coll = false;
-    return SPH_OK;
+    pack_records(n, pos, vel, index, 0u, hp.data(), hv.data());
+    return install_records(c, n, hp.data(), hv.data());
 }
 
 int sph_set_by_index(sph_ctx* c, uint32_t first_index, uint32_t count, const float* pos_xyz, const float* vel_xyz) {
@@ -608,10 +594,9 @@ int sph_set_by_index(sph_ctx* c, uint32_t first_index, uint32_t count, const flo
     if (rc) return rc;
     // positions moved under the keys: hash again; the slots still follow the last sort (order_valid stays)
     mm_drop_marks(c);
-    c->keys_fresh = false;
-    c->sort_form_both_until = c->sort_calls + 5;      // the last reported mover count says nothing about these particles
-    c->stage = sph_ctx::ST_LOADED;
-    c->have_dens = c->have_force = c->have_coll = false;
+    positions_moved(c);
+    mover_count_unknown(c);
+    results_stale(c);
     return SPH_OK;
 }
 
@@ -634,11 +619,9 @@ int sph_reset_lattice(sph_ctx* c, const uint32_t lattice[3], int jitter, const f
     rc = launch_reset_lattice(c, lattice, jitter, jitter_dims, start, count);
     if (rc) return rc;
     c->next_index = (uint32_t)(start + count);
-    c->stage = sph_ctx::ST_LOADED;
-    c->keys_fresh = false;
-    c->order_valid = false;     // the slots no longer follow the last sort
-    c->sort_form_both_until = c->sort_calls + 5;
-    c->have_dens = c->have_force = c->have_coll = false;
+    order_lost(c);              // (no mm_drop_marks: as sph_upload)
+    mover_count_unknown(c);
+    results_stale(c);
     return SPH_OK;
 }
 
@@ -651,8 +634,6 @@ static int fetch_sorted(sph_ctx* c, std::vector<float4>* hp, std::vector<float4>
     SPH_HIP(hipStreamSynchronize(c->stream));
     return SPH_OK;
 }
-
-static inline uint32_t idx_of(const float4& p) { uint32_t u; memcpy(&u, &p.w, 4); return u; }
 
 // Particles whose creation index lies outside [base, base + count) are not written: the caller's arrays hold
 // `count` entries and nothing beyond them is touched (an index below `base` wraps to a huge offset and fails
@@ -773,8 +754,6 @@ int sph_snapshot_load(sph_ctx* c, const char* path) {
     SPH_REQUIRE(ok, SPH_E_INVALID, "%s: truncated", path);
     rc = sph_set_params(c, &p);            // rejects a different grid
     if (rc) return rc;
-    std::vector<float> pos((size_t)n * 3), vel((size_t)n * 3);
-    std::vector<uint32_t> idx(n);
     if (!c->slab) {
         // a whole-domain snapshot numbers its particles below the capacity (0..n-1 unless particles were emitted or removed:
         // sph_emit, sph_remove), each index once: a file that says otherwise is corrupt (external input -- every by-index
@@ -786,12 +765,8 @@ int sph_snapshot_load(sph_ctx* c, const char* path) {
             seen[k] = true;
         }
     }
-    for (uint32_t i = 0; i < n; i++) {
-        pos[3 * i] = hp[i].x; pos[3 * i + 1] = hp[i].y; pos[3 * i + 2] = hp[i].z;
-        vel[3 * i] = hv[i].x; vel[3 * i + 1] = hv[i].y; vel[3 * i + 2] = hv[i].z;
-        idx[i] = idx_of(hp[i]);
-    }
-    rc = sph_upload(c, n, pos.data(), vel.data(), idx.data());
+    for (uint32_t i = 0; i < n; i++) hv[i].w = 0.f;        // the records as pack_records makes them, whatever the writer's w held
+    rc = install_records(c, n, hp.data(), hv.data());
     if (rc) return rc;
     // (indices of removed particles stay used; a value past the capacity -- a writer of larger capacity, a damaged file --
     // means no more than "none left")

@@ -6,7 +6,9 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/sph_hip.h"
@@ -218,7 +220,7 @@ struct sph_ctx {
 namespace sph {
 
 void set_error(const char* fmt, ...);
-void mm_drop_marks(sph_ctx* c);     // sph_sort.hip
+void mm_drop_marks(sph_ctx* c, bool counted = false);     // sph_sort.hip
 void mm_scan_marks(sph_ctx* c);     // sph_sort.hip
 int hip_fail(hipError_t e, const char* what, const char* file, int line);
 
@@ -270,6 +272,39 @@ int step_cells(sph_ctx* c);
 int launch_integrate(sph_ctx* c, float dt);
 
 inline uint32_t ceil_div(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
+
+// ---- the host-side state of a context: the events its entry points compose (DESIGN.md section 2 has the table) ----
+// results stale: density, forces and collision terms describe particles that have changed since
+inline void results_stale(sph_ctx* c) { c->have_dens = c->have_force = c->have_coll = false; }
+// mover count unknown: the count the device last reported says nothing about these particles (both sort forms for a while)
+inline void mover_count_unknown(sph_ctx* c) { c->sort_form_both_until = c->sort_calls + 5; }
+// positions moved under the keys: k0 is stale, the step starts again at the hash
+inline void positions_moved(sph_ctx* c) { c->keys_fresh = false; c->stage = sph_ctx::ST_LOADED; }
+// order lost: positions moved, and the slots no longer follow the last sort (the next sort is the full, stable one)
+inline void order_lost(sph_ctx* c) { positions_moved(c); c->order_valid = false; }
+// ping-pong: what a kernel wrote into posi2 / velr2 is the state now; `keys`: a sort or a compaction wrote keyS2 as well, and
+// put the owned range at its canonical offset
+inline void swap_state(sph_ctx* c, bool keys) {
+    std::swap(c->posi, c->posi2);
+    std::swap(c->velr, c->velr2);
+    if (keys) { std::swap(c->keyS, c->keyS2); c->own_off = c->gcap; }
+}
+// the cell table is live and was built from exactly the slots [lo, hi)
+inline bool table_covers(const sph_ctx* c, uint32_t lo, uint32_t hi) { return c->cells_valid && c->cells_lo == lo && c->cells_hi == hi; }
+// a table build over the slots [lo, hi) has been queued
+inline void set_table(sph_ctx* c, uint32_t lo, uint32_t hi) { c->cells_lo = lo; c->cells_hi = hi; c->cells_valid = true; }
+
+// the records of posi / velr as sph_upload, sph_emit and a snapshot hold them: (x, y, z, creation index bits), (vx, vy, vz, 0);
+// particle i gets index[i], or first + i without an index array
+inline void pack_records(uint32_t n, const float* pos, const float* vel, const uint32_t* index, uint32_t first, float4* hp, float4* hv) {
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t idx = index ? index[i] : first + (uint32_t)i;
+        float w;
+        memcpy(&w, &idx, 4);
+        hp[i] = make_float4(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], w);
+        hv[i] = vel ? make_float4(vel[3 * i], vel[3 * i + 1], vel[3 * i + 2], 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
 
 // ---- device timing: a pair of HIP events on the context's stream around a phase (only while sph_timing_enable) ----
 struct PhaseTimer {

@@ -359,10 +359,9 @@ void cudaMapZIndex(sph_compat_particle* p, unsigned int n, sph_compat_simparams*
                            x->velr + x->own_off);
         CKH(hipGetLastError());
     }
-    x->stage = sph_ctx::ST_LOADED;
-    x->keys_fresh = false;
-    x->order_valid = false;     // the slots no longer follow the last sort
-    x->have_dens = x->have_force = x->have_coll = false;
+    order_lost(x);
+    // (no mover_count_unknown: every sort of the seam is the full one, which has no form to pick)
+    results_stale(x);
     c.sorted = false;
     CK(sph_hash(x));
     writeback(c, p, F_ZINDEX);

@@ -234,19 +234,14 @@ int sph_remove(sph_ctx* c, uint32_t n_regions, const sph_region* regions, uint32
     }
     if (take) SPH_HIP(hipMemcpyAsync(removed_index, c->k0, (size_t)take * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     SPH_HIP(hipStreamSynchronize(c->stream));
-    float4* t4;
-    t4 = c->posi; c->posi = c->posi2; c->posi2 = t4;
-    t4 = c->velr; c->velr = c->velr2; c->velr2 = t4;
-    uint32_t* tk = c->keyS; c->keyS = c->keyS2; c->keyS2 = tk;
-    c->own_off = c->gcap;
+    swap_state(c, true);
     c->n = n - total;
     // order_valid stays as it was: the survivors follow the last sort, keyS holds its keys.  Everything derived from the
     // old slot numbers is stale -- the treatment of sph_set_by_index, plus the table (cleared above).
-    c->keys_fresh = false;                    // k0 held the keys of the old slots (and now the removed indices)
+    positions_moved(c);                       // k0 held the keys of the old slots (and now the removed indices)
     c->last_perm = nullptr;
-    c->sort_form_both_until = c->sort_calls + 5;
-    c->stage = sph_ctx::ST_LOADED;
-    c->have_dens = c->have_force = c->have_coll = false;
+    mover_count_unknown(c);
+    results_stale(c);
     if (n_removed) *n_removed = total;
     return SPH_OK;
 }
@@ -279,14 +274,7 @@ int sph_emit(sph_ctx* c, uint32_t n, const float* pos_xyz, const float* vel_xyz,
     if (n == 0) return SPH_OK;
     SPH_HIP(hipSetDevice(c->device));
     std::vector<float4> hp(n), hv(n);
-    for (uint32_t i = 0; i < n; i++) {
-        const uint32_t idx = index ? index[i] : first + i;
-        float w;
-        memcpy(&w, &idx, 4);
-        hp[i] = make_float4(pos_xyz[3 * (size_t)i], pos_xyz[3 * (size_t)i + 1], pos_xyz[3 * (size_t)i + 2], w);
-        hv[i] = vel_xyz ? make_float4(vel_xyz[3 * (size_t)i], vel_xyz[3 * (size_t)i + 1], vel_xyz[3 * (size_t)i + 2], 0.f)
-                        : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    pack_records(n, pos_xyz, vel_xyz, index, first, hp.data(), hv.data());
     const uint32_t at = c->own_off + c->n;                   // behind the owned range, as sph_migrants_append does
     SPH_HIP(hipMemcpyAsync(c->posi + at, hp.data(), (size_t)n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
     SPH_HIP(hipMemcpyAsync(c->velr + at, hv.data(), (size_t)n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
@@ -298,11 +286,9 @@ int sph_emit(sph_ctx* c, uint32_t n, const float* pos_xyz, const float* vel_xyz,
     SPH_HIP(hipStreamSynchronize(c->stream));                // the host staging goes away now
     c->n += n;
     c->next_index = next;
-    c->keys_fresh = false;
-    c->order_valid = false;                   // the slots no longer follow the last sort: the next sort is the full stable one
-    c->sort_form_both_until = c->sort_calls + 5;
-    c->stage = sph_ctx::ST_LOADED;
-    c->have_dens = c->have_force = c->have_coll = false;
+    order_lost(c);
+    mover_count_unknown(c);
+    results_stale(c);
     return SPH_OK;
 }
 

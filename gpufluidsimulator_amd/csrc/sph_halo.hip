@@ -119,7 +119,7 @@ int sph_migrants_pack(sph_ctx* c, void* buf_dev[2], uint32_t capacity) {
     rc = pack_slice(c, c->own_off, m[0], buf_dev[0], capacity);
     if (!rc) rc = pack_slice(c, c->own_off + c->n - m[1], m[1], buf_dev[1], capacity);
     if (rc) return rc;
-    if (c->cells_valid && c->cells_lo == c->own_off && c->cells_hi == c->own_off + c->n) {
+    if (table_covers(c, c->own_off, c->own_off + c->n)) {
         // the sort built the table over all owned slots: drop the cells of the particles that leave (they sit in
         // the two ghost layers, which hold nothing else until the ghosts are installed)
         rc = launch_cells_clear_range(c, c->own_off, c->own_off + m[0]);
@@ -145,9 +145,10 @@ int sph_migrants_append(sph_ctx* c, const void* buf_dev, uint32_t n_in) {
                        c->posi + at, c->velr + at, (uint32_t*)nullptr, c->grid, 0);
     SPH_HIP(hipGetLastError());
     c->n += n_in;
-    c->keys_fresh = false;
-    c->order_valid = false;     // the slots no longer follow the last sort
-    c->stage = sph_ctx::ST_LOADED;   // order destroyed: hash + sort again
+    order_lost(c);              // hash + sort again
+    // (no results_stale: kept as found.  The sort that must follow calls it; only a caller that asks for forces or packs
+    // densities BEFORE that sort is served those of the old slots.  No mover_count_unknown: that sort is the full one, and the
+    // slab step is host-paced and never reads it)
     return SPH_OK;
 }
 
@@ -191,7 +192,7 @@ int sph_halo_unpack(sph_ctx* c, const void* lo_dev, uint32_t n_lo, const void* h
     SPH_REQUIRE(n_lo <= c->own_off && c->own_off + c->n + n_hi <= c->tot && n_lo <= c->gcap && n_hi <= c->gcap,
                 SPH_E_CAPACITY, "ghost layers of %u / %u records exceed the ghost capacity %u", n_lo, n_hi, c->gcap);
     SPH_HIP(hipSetDevice(c->device));
-    if (!(c->cells_valid && c->cells_lo == c->own_off && c->cells_hi == c->own_off + c->n)) {
+    if (!table_covers(c, c->own_off, c->own_off + c->n)) {
         int rc = launch_cells_clear(c);   // a table that includes old ghosts; one over just the owned slots is kept
         if (rc) return rc;
     }

@@ -140,7 +140,7 @@ int launch_cells_build_range(sph_ctx* c, uint32_t lo, uint32_t hi) {
 int launch_cells_build(sph_ctx* c) {
     const uint32_t lo = c->own_off - c->n_glo, hi = c->own_off + c->n + c->n_ghi;
     int rc;
-    if (c->cells_valid && c->cells_lo == c->own_off && c->cells_hi == c->own_off + c->n) {
+    if (table_covers(c, c->own_off, c->own_off + c->n)) {
         // the sort's reorder pass built the owned cells; ghost layers hold no owned particle, so their
         // cells are disjoint from those: add them from the two ghost ranges only
         rc = launch_cells_build_2ranges(c, lo, c->own_off, c->own_off + c->n, hi);
@@ -149,7 +149,7 @@ int launch_cells_build(sph_ctx* c) {
         if (!rc) rc = launch_cells_build_range(c, lo, hi);
     }
     if (rc) return rc;
-    c->cells_lo = lo; c->cells_hi = hi; c->cells_valid = true;
+    set_table(c, lo, hi);
     return SPH_OK;
 }
 
@@ -1198,14 +1198,15 @@ static Spheres sphere_table(const sph_ctx* c) {
     return t;
 }
 
-// one launch of k_force over `threads` slots; sp: empty, or the sphere table (the collider instantiation)
+// one launch of k_force over `threads` slots; sp: empty, or the sphere table (the collider instantiation).  `early`: the slab
+// step's launch in front of the settling (launch_force_dev_range) -- the next keys go to keyS2 by ABSOLUTE slot
 template <bool F, bool C, bool I, class... Sph>
-static void force_kernel(sph_ctx* c, bool small, const Targets& tg, uint32_t threads, float dt, bool mark, Sph... sp) {
+static void force_kernel(sph_ctx* c, bool small, const Targets& tg, uint32_t threads, float dt, bool mark, bool early, Sph... sp) {
 #define SPH_LAUNCH_FORCE_T(T)                                                                                                   \
     hipLaunchKernelGGL((k_force<F, C, I, T, Sph...>), dim3(ceil_div(threads, (uint32_t)T)), dim3(T), 0, c->stream, c->posi,       \
                        c->velr, c->dp, c->cw, c->keyS, c->cells, c->fpress, c->fvisc, c->dvel, c->posi2, c->velr2,                \
-                       c->slab ? nullptr : c->pos_out, c->k0, mark ? c->mm_mask : nullptr, c->mm_tile_cnt, tg, c->own_off, dt, \
-                       c->grid, c->phys, sp...)
+                       c->slab ? nullptr : c->pos_out, early ? c->keyS2 : c->k0, mark ? c->mm_mask : nullptr, c->mm_tile_cnt, tg,       \
+                       early ? 0u : c->own_off, dt, c->grid, c->phys, sp...)
     if (small) SPH_LAUNCH_FORCE_T(SMALL_THREADS_PAIR); else SPH_LAUNCH_FORCE_T(PAIR_THREADS);
 #undef SPH_LAUNCH_FORCE_T
 }
@@ -1233,12 +1234,12 @@ int launch_force_hole(sph_ctx* c, uint32_t lo, uint32_t hi, uint32_t hole_lo, ui
     SPH_REQUIRE(tg.gap_len == 0u || (((tg.gap_lo - lo) | tg.gap_len) & 63u) == 0u || tg.gap_lo + tg.gap_len == hi, SPH_E_INVALID,
                 "force hole is not made of whole 64-slot chunks");
     if (threads == 0) return SPH_OK;
-    if (force && collide && integrate) {
-        if (c->n_colliders) force_kernel<true, true, true>(c, small, tg, threads, dt, mark, sphere_table(c));
-        else force_kernel<true, true, true>(c, small, tg, threads, dt, mark);
-    } else if (force && !collide && !integrate) force_kernel<true, false, false>(c, small, tg, threads, dt, mark);
-    else if (!force && collide && !integrate) force_kernel<false, true, false>(c, small, tg, threads, dt, mark);
-    else {
+    if (force && !collide && !integrate) force_kernel<true, false, false>(c, small, tg, threads, dt, mark, false);
+    else if (!force && collide && !integrate) force_kernel<false, true, false>(c, small, tg, threads, dt, mark, false);
+    else if (force && collide && integrate) {
+        if (c->n_colliders) force_kernel<true, true, true>(c, small, tg, threads, dt, mark, false, sphere_table(c));
+        else force_kernel<true, true, true>(c, small, tg, threads, dt, mark, false);
+    } else {
         set_error("launch_force: unsupported combination");
         return SPH_E_INVALID;
     }
@@ -1253,18 +1254,9 @@ int launch_force_hole(sph_ctx* c, uint32_t lo, uint32_t hi, uint32_t hole_lo, ui
 int launch_force_dev_range(sph_ctx* c, const uint32_t* range_dev, uint32_t max_count, float dt) {
     if (max_count == 0) return SPH_OK;
     const Targets tg{0u, 0u, 0xFFFFFFFFu, 0u, range_dev, c->direct_hull, BlockOrder{0u, 0u, 0u, 0u, 0u}};
-#define SPH_LAUNCH_EARLY(T, ...)                                                                                                    \
-    hipLaunchKernelGGL((k_force<true, true, true, T __VA_OPT__(, ) __VA_ARGS__>), dim3(ceil_div(max_count, (uint32_t)T)), dim3(T), 0,   \
-                       c->stream, c->posi, c->velr, c->dp, c->cw, c->keyS, c->cells, c->fpress, c->fvisc, c->dvel, c->posi2, c->velr2,  \
-                       c->slab ? nullptr : c->pos_out, c->keyS2, (uint64_t*)nullptr, c->mm_tile_cnt, tg, 0u, dt, c->grid, c->phys      \
-                       __VA_OPT__(, sphere_table(c)))
     // (the same centres as the step's other launches: force_finish advances them once all are queued)
-    if (c->n_colliders) {
-        if (small_blocks(c)) SPH_LAUNCH_EARLY(SMALL_THREADS_PAIR, Spheres); else SPH_LAUNCH_EARLY(PAIR_THREADS, Spheres);
-    } else {
-        if (small_blocks(c)) SPH_LAUNCH_EARLY(SMALL_THREADS_PAIR); else SPH_LAUNCH_EARLY(PAIR_THREADS);
-    }
-#undef SPH_LAUNCH_EARLY
+    if (c->n_colliders) force_kernel<true, true, true>(c, small_blocks(c), tg, max_count, dt, false, true, sphere_table(c));
+    else force_kernel<true, true, true>(c, small_blocks(c), tg, max_count, dt, false, true);
     SPH_HIP(hipGetLastError());
     return SPH_OK;
 }
@@ -1283,9 +1275,7 @@ bool force_begin(sph_ctx* c, bool integrate) {
 void force_finish(sph_ctx* c, bool integrate, bool mark, float dt) {
     if (!integrate) return;
     advance_colliders(c, dt);
-    float4* t;
-    t = c->posi; c->posi = c->posi2; c->posi2 = t;
-    t = c->velr; c->velr = c->velr2; c->velr2 = t;
+    swap_state(c, false);
     c->keys_fresh = true;
     if (mark) {
         c->mm_marked = true; c->mm_scanned = false; c->mm_marked_off = c->own_off; c->mm_marked_n = c->n;

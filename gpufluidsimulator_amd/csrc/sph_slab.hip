@@ -1404,7 +1404,7 @@ int step_settle(sph_slab* s, Step& st) {
     // ---- drop the leavers (their cells hold nothing else until the ghosts arrive; the clearing must precede the
     //      ghost cells, so it runs on the stream that builds those) ---------------------------------------------------
     if (m_lo || m_hi) {
-        if (c->cells_valid && c->cells_lo == c->own_off && c->cells_hi == c->own_off + c->n) {
+        if (table_covers(c, c->own_off, c->own_off + c->n)) {
             OnComm on(s, st.early_halo);
             rc = launch_cells_clear_2ranges(c, c->own_off, c->own_off + m_lo, c->own_off + c->n - m_hi, c->own_off + c->n);
             if (rc) return rc;
@@ -1421,8 +1421,7 @@ int step_settle(sph_slab* s, Step& st) {
     SPH_REQUIRE(c->n + in_lo + in_hi <= c->cap && c->own_off + c->n + in_lo + in_hi <= c->tot, SPH_E_CAPACITY,
                 "rank %d: %u + %u arriving particles exceed the capacity %u", s->rank, c->n, in_lo + in_hi, c->cap);
     rc = after_comm(s); if (rc) return rc;                      // the received records are in mig_recv
-    const bool merge = c->sort_merge && c->order_valid && c->cells_valid && c->cells_lo == c->own_off &&
-                       c->cells_hi == c->own_off + c->n;
+    const bool merge = c->sort_merge && c->order_valid && table_covers(c, c->own_off, c->own_off + c->n);
     const bool in_place = merge && st.far_in_lo == 0 && st.far_in_hi == 0 && in_lo <= SLAB_INSERT_MAX &&
                           in_hi <= SLAB_INSERT_MAX && in_lo <= c->own_off && st.own_lo + st.own_hi <= c->n;
     if (in_place) {
@@ -1484,9 +1483,7 @@ int step_settle(sph_slab* s, Step& st) {
     } else {
         if (front_slots) { c->own_off -= in_lo; c->n += in_lo; }
         c->n += appended;
-        c->keys_fresh = false;
-        c->order_valid = false;
-        c->stage = sph_ctx::ST_LOADED;
+        order_lost(c);          // (results_stale: step_sort, two lines down; no mover_count_unknown: host-paced, never read)
         rc = step_hash(c); if (rc) return rc;
         rc = step_sort(c); if (rc) return rc;
     }
@@ -1607,7 +1604,7 @@ int step_ghosts(sph_slab* s, Step& st) {
     SPH_HIP(hipGetLastError());
     c->n_glo = g_lo; c->n_ghi = g_hi;
     s->ghosts += g_lo + g_hi;
-    c->cells_lo = c->own_off - g_lo; c->cells_hi = c->own_off + n + g_hi; c->cells_valid = true;
+    set_table(c, c->own_off - g_lo, c->own_off + n + g_hi);
     c->stage = sph_ctx::ST_CELLS;
     if (early_halo) {
         // all that is left of the density pass (the boundary layers and the two layers next to them), queued on the COMM

@@ -1244,10 +1244,11 @@ void mm_scan_marks(sph_ctx* c) {
     c->mm_scanned = true;
 }
 
-// forget the marks the integrate epilogue left (the scan re-zeroes the tile counts they added to)
-void mm_drop_marks(sph_ctx* c) {
+// forget the marks the integrate epilogue left (the scan re-zeroes the tile counts they added to); `counted`: a full sort
+// stands in for the merge they were meant for, so the count still reports to the host and adds to the total
+void mm_drop_marks(sph_ctx* c, bool counted) {
     if (!c->mm_marked) return;
-    if (!c->mm_scanned) mm_tilescan(c, c->mm_marked_n, false);
+    if (!c->mm_scanned) mm_tilescan(c, c->mm_marked_n, counted);
     c->mm_marked = false;
     c->mm_scanned = false;
 }
@@ -1415,9 +1416,7 @@ int launch_sort(sph_ctx* c) {
         // keep the hint alive, or it would stay high for ever: for free when the integrate epilogue marked
         // the movers (the scan also re-zeroes the tile counts those marks added to), else every 8th sort
         if (c->mm_marked) {
-            if (!c->mm_scanned) mm_tilescan(c, c->mm_marked_n, true);
-            c->mm_marked = false;
-            c->mm_scanned = false;
+            mm_drop_marks(c, true);
         } else if (can_merge && (c->sort_calls & 7u) == 0) {
             hipLaunchKernelGGL(k_mm_mark, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, c->keyS + c->own_off, c->k0, n,
                                c->mm_mask, c->mm_tile_cnt);
@@ -1434,11 +1433,7 @@ int launch_sort(sph_ctx* c) {
         SPH_HIP(hipGetLastError());
         c->last_perm = vin;
     }
-    float4* t4;
-    t4 = c->posi; c->posi = c->posi2; c->posi2 = t4;
-    t4 = c->velr; c->velr = c->velr2; c->velr2 = t4;
-    uint32_t* tk = c->keyS; c->keyS = c->keyS2; c->keyS2 = tk;
-    c->own_off = c->gcap;
+    swap_state(c, true);
     // the cell table of the owned slots from boundary flags on the new keys (no atomics, no scan, no host sync).
     // A slab context adds the cells of its ghost layers later (launch_cells_build), and drops those of the
     // particles that leave (sph_migrants_pack).
@@ -1453,7 +1448,7 @@ int launch_sort(sph_ctx* c) {
         if (rc) return rc;
     }
     c->order_valid = true;
-    c->cells_lo = c->gcap; c->cells_hi = c->gcap + n; c->cells_valid = true;
+    set_table(c, c->gcap, c->gcap + n);
     return SPH_OK;
 }
 
@@ -1465,35 +1460,28 @@ int launch_sort(sph_ctx* c) {
 // of the whole-domain stable sort, see Front), the others behind them.
 int launch_merge_arrivals(sph_ctx* c, uint32_t n_in, uint32_t n_front) {
     const uint32_t n = c->n, n_tot = n + n_in;
-    SPH_REQUIRE(c->order_valid && c->cells_valid && c->cells_lo == c->own_off && c->cells_hi == c->own_off + n, SPH_E_STATE,
+    SPH_REQUIRE(c->order_valid && table_covers(c, c->own_off, c->own_off + n), SPH_E_STATE,
                 "launch_merge_arrivals needs the sorted owned range and its cell table");
     SPH_REQUIRE(ceil_div(n_tot, SORT_TILE) <= c->sort_blocks_cap, SPH_E_CAPACITY, "sort: capacity exceeded");
     mm_drop_marks(c);
     const uint32_t nchunks = ceil_div(n_tot, 64u);
     hipLaunchKernelGGL(k_mm_mark_tail, dim3(ceil_div(nchunks, 256u)), dim3(256), 0, c->stream, n, n_tot, c->mm_mask,
                        c->mm_tile_cnt);
-    const uint32_t nt = ceil_div(nchunks, MM_TILE_CHUNKS);
-    hipLaunchKernelGGL(k_mm_tilescan, dim3(1), dim3(1024), 0, c->stream, c->mm_tile_cnt, nt, c->mm_tile_off, c->mm_count,
-                       c->mm_count_host_dev, (unsigned long long*)nullptr, 0u);
-    c->mm_counted_valid = false;
+    mm_tilescan(c, n_tot, false);
     SPH_HIP(hipGetLastError());
     int rc = launch_sort_merge(c, n, n_tot, true, n_in, Front{n, n_front < n_in ? n_front : n_in});
     if (rc) return rc;
-    float4* t4;
-    t4 = c->posi; c->posi = c->posi2; c->posi2 = t4;
-    t4 = c->velr; c->velr = c->velr2; c->velr2 = t4;
-    uint32_t* tk = c->keyS; c->keyS = c->keyS2; c->keyS2 = tk;
-    c->own_off = c->gcap;
+    swap_state(c, true);
     c->n = n_tot;
     c->cells_valid = false;
     rc = launch_cells_build_range(c, c->gcap, c->gcap + n_tot);
     if (rc) return rc;
-    c->cells_lo = c->gcap; c->cells_hi = c->gcap + n_tot; c->cells_valid = true;
+    set_table(c, c->gcap, c->gcap + n_tot);
     c->order_valid = true;
     c->keys_fresh = false;
     c->n_glo = c->n_ghi = 0;
     c->stage = sph_ctx::ST_SORTED;
-    c->have_dens = c->have_force = c->have_coll = false;
+    results_stale(c);
     return SPH_OK;
 }
 
