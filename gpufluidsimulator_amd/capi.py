@@ -50,6 +50,11 @@ class Collider(C.Structure):
     _fields_ = [("center", C.c_float * 3), ("radius", C.c_float), ("velocity", C.c_float * 3), ("pad", C.c_float)]
 
 
+class ColliderBody(C.Structure):
+    """`sph_collider_body` of include/sph_hip.h: mass 0 = kinematic, > 0 = a free body under the constant `accel`."""
+    _fields_ = [("mass", C.c_float), ("accel", C.c_float * 3)]
+
+
 MAX_REGIONS = 8            # SPH_MAX_REGIONS
 REGION_SPHERE, REGION_BOX, REGION_HALFSPACE = 0, 1, 2
 
@@ -109,6 +114,8 @@ SIGNATURES = {
     "sph_snapshot_info": (C.c_int, [C.c_char_p, C.POINTER(_U32), C.POINTER(Params)]),
     "sph_set_colliders": (C.c_int, [_P, _U32, C.POINTER(Collider)]),
     "sph_get_colliders": (C.c_int, [_P, C.POINTER(_U32), C.POINTER(Collider)]),
+    "sph_set_collider_bodies": (C.c_int, [_P, _U32, C.POINTER(ColliderBody)]),
+    "sph_get_collider_impulses": (C.c_int, [_P, C.POINTER(_U32), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "sph_emit": (C.c_int, [_P, _U32, _P, _P, _P, C.POINTER(_U32)]),
     "sph_remove": (C.c_int, [_P, _U32, C.POINTER(Region), C.POINTER(_U32), _P, _U32]),
     "sph_count_in_regions": (C.c_int, [_P, _U32, C.POINTER(Region), C.POINTER(_U32)]),
@@ -400,8 +407,32 @@ class Context:
             arr[j].velocity[:] = [float(v) for v in velocities[j]]
         _check(self.L.sph_set_colliders(self.h, n, arr))
 
+    def set_collider_bodies(self, masses, accels=None):
+        """One body per sphere (include/sph_hip.h: sph_set_collider_bodies): masses (n,) -- 0 kinematic, > 0 a free body the
+        fluid pushes --, accels (n, 3) or None (zero).  The context is then tracked: collider_impulses() reports what every
+        sphere took from the fluid, and the spheres live on the device.  An empty `masses` stops the tracking."""
+        masses = np.ascontiguousarray(masses, dtype=np.float32).reshape(-1)
+        n = masses.shape[0]
+        accels = np.zeros((n, 3), np.float32) if accels is None else _f32(accels, 3)
+        if accels.shape[0] != n:
+            raise ValueError("masses and accels describe different numbers of spheres")
+        arr = (ColliderBody * max(n, 1))()
+        for j in range(n):
+            arr[j].mass = float(masses[j])
+            arr[j].accel[:] = [float(v) for v in accels[j]]
+        _check(self.L.sph_set_collider_bodies(self.h, n, arr))
+
+    def collider_impulses(self):
+        """(J, steps): J float64 (n, 3), the momentum each sphere took from the fluid in the LAST integrate, and the number
+        of integrates since tracking began; ((0, 3) array, 0) on a context that is not tracked.  Synchronises."""
+        J = (C.c_double * (3 * MAX_COLLIDERS))()
+        n, steps = _U32(), C.c_uint64()
+        _check(self.L.sph_get_collider_impulses(self.h, C.byref(n), J, C.byref(steps)))
+        return np.array(J[:3 * n.value], np.float64).reshape(-1, 3), int(steps.value)
+
     def colliders(self):
-        """The current spheres, centres advanced: {"centers": (n, 3), "radii": (n,), "velocities": (n, 3)} float32."""
+        """The current spheres, centres advanced: {"centers": (n, 3), "radii": (n,), "velocities": (n, 3)} float32 (on a
+        tracked context: the device's centres and velocities; synchronises)."""
         arr = (Collider * MAX_COLLIDERS)()
         n = _U32()
         _check(self.L.sph_get_colliders(self.h, C.byref(n), arr))

@@ -92,7 +92,7 @@ ParticleSystem::ParticleSystem(uint numParticles, float3 boxDims, ParticleComput
 
 ParticleSystem::ParticleSystem(uint numParticles, float3 boxDims, ParticleComputeMode mode, uint3 gridDims, uint capacity)
     : m_bInitialized(false), m_numParticles(numParticles), m_capacity(capacity > numParticles ? capacity : numParticles), m_boxDims(boxDims), m_solverIterations(1),
-      m_compute_mode(mode), m_ctx(nullptr), m_colliderOn(false), m_colliderVel{0.f, 0.f, 0.f}, m_hostStale(false), m_log(nullptr), m_logLastMs(0), m_logGlobalMs(0), m_logFreqMs(2000.0), m_logStyle(0), m_logFrames(0) {
+      m_compute_mode(mode), m_ctx(nullptr), m_colliderOn(false), m_colliderVel{0.f, 0.f, 0.f}, m_colliderMass(0.f), m_colliderAccel{0.f, 0.f, 0.f}, m_colliderSense(false), m_bodyLive(false), m_hostStale(false), m_log(nullptr), m_logLastMs(0), m_logGlobalMs(0), m_logFreqMs(2000.0), m_logStyle(0), m_logFrames(0) {
     if (mode != CUDA_PARALLEL) {
         fprintf(stderr, "ParticleSystem: only the GPU compute mode exists in this build "
                         "(SEQUENTIAL / OMP_PARALLEL are the reference's CPU paths; there is no CPU fallback)\n");
@@ -171,17 +171,40 @@ void ParticleSystem::downloadAll() {
 
 void ParticleSystem::enableCollider(bool on) {
     m_colliderOn = on;
+    m_bodyLive = false;
     if (!on) SPH_CHECK(sph_set_colliders(m_ctx, 0, nullptr));   // (on: update() sets the sphere before every run of steps)
+}
+
+void ParticleSystem::setColliderMass(float mass, const float* accel) {
+    if (!(mass >= 0.f) || !std::isfinite(mass)) { fprintf(stderr, "ParticleSystem::setColliderMass: %g is not a mass\n", (double)mass); exit(EXIT_FAILURE); }
+    m_colliderMass = mass;
+    for (int a = 0; a < 3; a++) m_colliderAccel[a] = accel ? accel[a] : 0.f;
+    m_bodyLive = false;          // (the next update() hands the sphere over again, where it is now)
+}
+
+void ParticleSystem::getColliderImpulse(double out[3]) {
+    out[0] = out[1] = out[2] = 0.0;
+    if (!m_bodyLive) return;
+    uint32_t n = 0;
+    double J[3 * SPH_MAX_COLLIDERS];
+    SPH_CHECK(sph_get_collider_impulses(m_ctx, &n, J, nullptr));
+    if (n) for (int a = 0; a < 3; a++) out[a] = J[a];
 }
 
 // ---- stepping (particleSystem.cpp:719-817) ------------------------------------------------------------------
 void ParticleSystem::update(float deltaTime, float fps) {
     if (!m_bInitialized) { fprintf(stderr, "ParticleSystem::update before initialisation\n"); exit(EXIT_FAILURE); }
     if (m_solverIterations > 0) {
-        if (m_colliderOn) {
+        if (m_colliderOn && !(m_bodyLive && m_colliderMass > 0.f)) {       // (a free body the context already holds is the device's to move)
             const sph_collider s = {{m_params.colliderPos.x, m_params.colliderPos.y, m_params.colliderPos.z}, m_params.colliderRadius,
                                     {m_colliderVel.x, m_colliderVel.y, m_colliderVel.z}, 0.f};
             SPH_CHECK(sph_set_colliders(m_ctx, 1, &s));
+            m_bodyLive = false;
+            if (m_colliderMass > 0.f || m_colliderSense) {       // (mass 0: tracked for its impulse, kinematic as before)
+                const sph_collider_body b = {m_colliderMass, {m_colliderAccel[0], m_colliderAccel[1], m_colliderAccel[2]}};
+                SPH_CHECK(sph_set_collider_bodies(m_ctx, 1, &b));
+                m_bodyLive = true;
+            }
         }
         SPH_CHECK(sph_step(m_ctx, deltaTime, (uint32_t)m_solverIterations));
         if (m_colliderOn) {                                  // the centre the steps advanced it to
@@ -189,6 +212,7 @@ void ParticleSystem::update(float deltaTime, float fps) {
             sph_collider s;
             SPH_CHECK(sph_get_colliders(m_ctx, &n, &s));
             m_params.colliderPos = make_float3(s.center[0], s.center[1], s.center[2]);
+            if (m_bodyLive && m_colliderMass > 0.f) m_colliderVel = make_float3(s.velocity[0], s.velocity[1], s.velocity[2]);
         }
     }
     m_hostStale = true;

@@ -136,6 +136,7 @@ static void free_all(sph_ctx* c) {
     hipFree(c->mm_k0); hipFree(c->mm_k1); hipFree(c->mm_v1); hipFree(c->mm_count); hipFree(c->mm_total);
     if (c->mm_count_host) hipHostFree(c->mm_count_host);
     if (c->h_scratch) hipHostFree(c->h_scratch);
+    hipFree(c->trk_table); hipFree(c->trk_partial); hipFree(c->trk_mask); hipFree(c->trk_J);   // (sph_set_collider_bodies)
 }
 
 static int create_impl(sph_ctx** out, int device, uint32_t capacity, const sph_params* p, uint32_t z_lo, uint32_t z_hi,
@@ -537,6 +538,10 @@ int sph_set_params(sph_ctx* c, const sph_params* p) {
     c->keys_fresh = false;
     c->order_valid = false;
     mover_count_unknown(c);
+    if (c->tracked) {                // R + wall_eps of the device's sphere table
+        SPH_HIP(hipSetDevice(c->device));
+        return launch_spheres_radii(c);
+    }
     return SPH_OK;
 }
 
@@ -791,14 +796,90 @@ int sph_set_colliders(sph_ctx* c, uint32_t n, const sph_collider* colliders) {
         c->colliders[j].pad = 0.f;
     }
     c->n_colliders = n;
+    c->tracked = false;              // the new set is kinematic: the bodies go with the old one
+    return SPH_OK;
+}
+
+// the centres and velocities of a tracked context, from the device (synchronises)
+static int fetch_tracked(const sph_ctx* c, sph_collider* out) {
+    Spheres t;
+    SPH_HIP(hipSetDevice(c->device));
+    SPH_HIP(hipStreamSynchronize(c->stream));
+    SPH_HIP(hipMemcpy(&t, c->trk_table, sizeof(t), hipMemcpyDeviceToHost));
+    for (uint32_t j = 0; j < c->n_colliders; j++) {
+        out[j] = c->colliders[j];
+        out[j].center[0] = t.c[j].x; out[j].center[1] = t.c[j].y; out[j].center[2] = t.c[j].z;
+        out[j].velocity[0] = t.u[j].x; out[j].velocity[1] = t.u[j].y; out[j].velocity[2] = t.u[j].z;
+    }
     return SPH_OK;
 }
 
 int sph_get_colliders(const sph_ctx* c, uint32_t* n, sph_collider* out) {
     SPH_REQUIRE(c && n, SPH_E_INVALID, "null argument");
     *n = c->n_colliders;
+    if (out && c->tracked) return fetch_tracked(c, out);
     if (out)
         for (uint32_t j = 0; j < c->n_colliders; j++) out[j] = c->colliders[j];
+    return SPH_OK;
+}
+
+int sph_set_collider_bodies(sph_ctx* c, uint32_t n, const sph_collider_body* bodies) {
+    SPH_REQUIRE(c, SPH_E_INVALID, "null context");
+    SPH_REQUIRE(!c->slab, SPH_E_STATE, "sph_set_collider_bodies: whole-domain contexts only (a slab's partial impulses would need an all-reduce)");
+    SPH_REQUIRE(n == 0 || n == c->n_colliders, SPH_E_INVALID, "%u bodies for %u colliders", n, c->n_colliders);
+    SPH_REQUIRE(n == 0 || bodies, SPH_E_INVALID, "null bodies");
+    for (uint32_t j = 0; j < n; j++) {
+        SPH_REQUIRE(std::isfinite(bodies[j].mass) && bodies[j].mass >= 0.f, SPH_E_INVALID, "body %u: mass %g is negative or not finite", j,
+                    (double)bodies[j].mass);
+        for (int a = 0; a < 3; a++) SPH_REQUIRE(std::isfinite(bodies[j].accel[a]), SPH_E_INVALID, "body %u: accel is not finite", j);
+    }
+    if (n == 0) {                    // stop tracking: the spheres stay where the device has them, kinematic
+        if (c->tracked) {
+            sph_collider now[SPH_MAX_COLLIDERS];
+            int rc = fetch_tracked(c, now);
+            if (rc) return rc;
+            for (uint32_t j = 0; j < c->n_colliders; j++) c->colliders[j] = now[j];
+            c->tracked = false;
+        }
+        return SPH_OK;
+    }
+    SPH_HIP(hipSetDevice(c->device));
+    if (!c->trk_table) {             // first use: buffers by capacity
+        const size_t waves = ceil_div(c->cap, 64u);
+        Spheres* table = nullptr; double* partial = nullptr; uint32_t* mask = nullptr; double* J = nullptr;
+        int rc = dev_alloc_zero(&table, 1);
+        if (!rc) rc = dev_alloc(&partial, waves * SPH_MAX_COLLIDERS * 3);
+        if (!rc) rc = dev_alloc_zero(&mask, ((waves + 3) & ~(size_t)3) + 4);
+        if (!rc) rc = dev_alloc_zero(&J, SPH_MAX_COLLIDERS * 3 + 1);
+        if (rc) { hipFree(table); hipFree(partial); hipFree(mask); hipFree(J); return rc; }
+        c->trk_table = table; c->trk_partial = partial; c->trk_mask = mask; c->trk_J = J;
+    }
+    SphereBodies b{};
+    for (uint32_t j = 0; j < n; j++) {
+        b.am[j] = make_float4(bodies[j].accel[0], bodies[j].accel[1], bodies[j].accel[2], bodies[j].mass);
+        b.radius[j] = c->colliders[j].radius;
+    }
+    if (!c->tracked) {               // the host's set goes to the device; J and the step count start at zero
+        int rc = launch_spheres_install(c);
+        if (rc) return rc;
+    }
+    c->bodies = b;
+    c->tracked = true;
+    return SPH_OK;
+}
+
+int sph_get_collider_impulses(sph_ctx* c, uint32_t* n, double* J, uint64_t* steps) {
+    SPH_REQUIRE(c && n, SPH_E_INVALID, "null argument");
+    *n = 0;
+    if (steps) *steps = 0;
+    if (!c->tracked) return SPH_OK;
+    double h[SPH_MAX_COLLIDERS * 3 + 1];
+    SPH_HIP(hipSetDevice(c->device));
+    SPH_HIP(hipStreamSynchronize(c->stream));
+    SPH_HIP(hipMemcpy(h, c->trk_J, sizeof(h), hipMemcpyDeviceToHost));
+    *n = c->n_colliders;
+    if (J) memcpy(J, h, sizeof(double) * 3 * c->n_colliders);
+    if (steps) memcpy(steps, &h[SPH_MAX_COLLIDERS * 3], sizeof(uint64_t));
     return SPH_OK;
 }
 

@@ -63,6 +63,25 @@ struct Spheres {
     uint32_t n;
 };
 
+// The same table for a TRACKED context (sph_set_collider_bodies): it lives in device memory, where k_spheres_step moves the
+// spheres once per step, and the tracked instantiations of k_force / k_integrate take a pointer to it plus the per-step outputs.
+// Every wave of a tracked launch stores one mask word -- which spheres it wrote a row of partial sums for -- so that nothing
+// has to be cleared between steps.
+struct SpheresTracked {
+    const Spheres* table;     // device
+    double* partial;          // [wave][SPH_MAX_COLLIDERS][3]: the wave's sum of -(mass * (k * nrm)) for sphere j
+    uint32_t* mask;           // [wave]: bit j = partial[wave][j] was written by this launch
+    uint32_t rel;             // the lane's slot relative to the first owned slot (filled in by the kernel: wave = rel / 64)
+};
+
+// The bodies of a tracked context as k_spheres_step takes them: by value.
+struct SphereBodies {
+    float4 am[SPH_MAX_COLLIDERS];    // accel, mass (0: kinematic)
+    float radius[SPH_MAX_COLLIDERS]; // R (the wall rule's eps of a free body)
+};
+
+constexpr uint32_t SPHERES_STEP_THREADS = 256;   // k_spheres_step: one block (sph_pairs.hip)
+
 }  // namespace sph
 
 // The opaque context of include/sph_hip.h.
@@ -114,6 +133,15 @@ struct sph_ctx {
     // once per step (sph_pairs.hip: push_out_of_spheres, advance_colliders); none by default
     uint32_t n_colliders = 0;
     sph_collider colliders[SPH_MAX_COLLIDERS] = {};
+    // bodies (sph_set_collider_bodies): while `tracked`, the table trk_table on the device holds the centres and velocities
+    // (`colliders` above keeps the radii and is otherwise stale), the tracked kernel instantiations run, and k_spheres_step
+    // sums the impulses and moves the spheres once per step.  The buffers are allocated when tracking is first switched on.
+    bool tracked = false;
+    sph::SphereBodies bodies{};
+    sph::Spheres* trk_table = nullptr;
+    double* trk_partial = nullptr;      // ceil(cap / 64) rows of SPH_MAX_COLLIDERS x 3
+    uint32_t* trk_mask = nullptr;       // ceil(cap / 64) words, padded to a multiple of 4
+    double* trk_J = nullptr;            // SPH_MAX_COLLIDERS x 3 doubles of the last integrate, then the step count (uint64)
 
     // pair kernels: a (dz, dy) row whose staged hull would exceed this many slots is read straight from global memory
     // by every lane instead (sph_pairs.hip: traverse; sph_set_direct_hull)
@@ -263,13 +291,16 @@ int launch_force_hole(sph_ctx* c, uint32_t lo, uint32_t hi, uint32_t hole_lo, ui
                       bool integrate, float dt, bool mark);
 bool force_begin(sph_ctx* c, bool integrate);
 int launch_force_range(sph_ctx* c, uint32_t lo, uint32_t hi, bool force, bool collide, bool integrate, float dt, bool mark);
-void force_finish(sph_ctx* c, bool integrate, bool mark, float dt);   // also advances the colliders' centres by dt
+int force_finish(sph_ctx* c, bool integrate, bool mark, float dt);   // also advances the colliders' centres by dt (a tracked context: queues k_spheres_step)
 // phase bodies of sph_capi.hip (with their bookkeeping), for the slab driver
 int set_slab_range(sph_ctx* c, uint32_t z_lo, uint32_t z_hi);   // sph_capi.hip: a slab context takes over another layer range (its table must be clear)
 int step_hash(sph_ctx* c);
 int step_sort(sph_ctx* c);
 int step_cells(sph_ctx* c);
 int launch_integrate(sph_ctx* c, float dt);
+// tracked contexts (sph_pairs.hip): write the host's sphere set into trk_table and zero J and the step count; refresh R + eps
+int launch_spheres_install(sph_ctx* c);
+int launch_spheres_radii(sph_ctx* c);
 
 inline uint32_t ceil_div(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 

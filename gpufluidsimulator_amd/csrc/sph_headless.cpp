@@ -2,7 +2,7 @@
 // (SPH/particles.cpp:676-706: -n= -box= -i= -benchmark -device= -file=) and its runBenchmark()
 // output line (:176-192), on top of include/particleSystem.h.  No GLUT / OpenGL.
 //   sph_headless -benchmark -n=262144 -box=8 -i=100 [-device=0] [-grid=128] [-ic=grid|random] [-steps=1] [-dump=8]
-//                [-log=benchmark.txt [-logstyle=oscar|frames]] [-file=<snapshot>] [-collider=x,y,z,r[,ux,uy,uz]]
+//                [-log=benchmark.txt [-logstyle=oscar|frames]] [-file=<snapshot>] [-collider=x,y,z,r[,ux,uy,uz]] [-collidermass=M[,ax,ay,az]]
 // -collider: the reference's collider sphere (centre, radius, and a velocity: default at rest), made to push the fluid
 // (ParticleSystem::enableCollider; one sphere, as the reference's UI has).
 //   -emit=x,y,z,r,vx,vy,vz,every   a faucet: before every `every`-th update (0, every, 2 every, ...) a lattice ball of radius r
@@ -406,9 +406,12 @@ int main(int argc, char** argv) {
         printf("usage: sph_headless [-benchmark] [-n=<particles>] [-box=<edge>] [-i=<iterations>] [-device=<id>] [-grid=<cells per axis>] "
                "[-ic=grid|random] [-steps=<per update>] [-gpus=<N> [-onegpu] [-slab] [-lattice=nx,ny,nz] [-protocol=1|3]] "
                "[-dump=<count>] [-log=<file> [-logfreq=<ms>] [-logstyle=oscar|frames]] [-sphere=<update>[,<radius>]] "
-               "[-collider=<x>,<y>,<z>,<radius>[,<ux>,<uy>,<uz>]] [-emit=<x>,<y>,<z>,<r>,<vx>,<vy>,<vz>,<every>] "
+               "[-collider=<x>,<y>,<z>,<radius>[,<ux>,<uy>,<uz>]] [-collidermass=<M>[,<ax>,<ay>,<az>]] [-emit=<x>,<y>,<z>,<r>,<vx>,<vy>,<vz>,<every>] "
                "[-drain=<x0>,<y0>,<z0>,<x1>,<y1>,<z1>[,<every>]] [-add=<update>,<count>] [-capacity=<particles>] [-out=<file>] [-save=<file>] [-load=<file>] [-file=<file>]\n"
                "  -collider: a solid sphere the fluid flows around, moving at (ux, uy, uz) (default: at rest); one device only\n"
+               "  -collidermass: the -collider sphere is a free body of mass M > 0 that the fluid pushes, under the acceleration (ax, ay, az) "
+               "(default: (0, gravity_y, 0) of the run), or with M = 0 a kinematic obstacle whose load is wanted; prints its centre, velocity "
+               "and last impulse at the end; one device only\n"
                "  -emit: every <every> updates append a lattice ball of radius <r> spacings at (x, y, z) moving at (vx, vy, vz), if its place is clear\n"
                "  -drain: every <every> updates (default 1) remove the particles inside the box [x0,x1) x [y0,y1) x [z0,z1); one device only\n");
         return 0;
@@ -421,6 +424,18 @@ int main(int argc, char** argv) {
         const int k = sscanf(colliderArg, "%f,%f,%f,%f,%f,%f,%f", &col[0], &col[1], &col[2], &col[3], &col[4], &col[5], &col[6]);
         if ((k != 4 && k != 7) || !(col[3] > 0.f)) {
             fprintf(stderr, "-collider=%s: expected x,y,z,r or x,y,z,r,ux,uy,uz with r > 0\n", colliderArg);
+            return EXIT_FAILURE;
+        }
+    }
+    // -collidermass=M[,ax,ay,az]
+    float cm[4] = {0.f, 0.f, 0.f, 0.f};
+    int cmFields = 0;
+    const char* colliderMassArg = value(argc, argv, "collidermass");
+    if (colliderMassArg) {
+        cmFields = sscanf(colliderMassArg, "%f,%f,%f,%f", &cm[0], &cm[1], &cm[2], &cm[3]);
+        if (!colliderArg || (cmFields != 1 && cmFields != 4) || !(cm[0] >= 0.f) || !std::isfinite(cm[0]) || !std::isfinite(cm[1]) ||
+            !std::isfinite(cm[2]) || !std::isfinite(cm[3])) {
+            fprintf(stderr, "-collidermass=%s: expected M or M,ax,ay,az with M >= 0, next to a -collider\n", colliderMassArg);
             return EXIT_FAILURE;
         }
     }
@@ -510,6 +525,13 @@ int main(int argc, char** argv) {
         psystem->setColliderRadius(col[3]);
         psystem->setColliderVelocity(make_float3(col[4], col[5], col[6]));
         psystem->enableCollider(true);
+        if (colliderMassArg) {
+            sph_params rp;
+            sph_get_params(psystem->context(), &rp);
+            const float grav[3] = {0.f, rp.gravity_y, 0.f};
+            psystem->setColliderMass(cm[0], cmFields == 4 ? cm + 1 : grav);
+            if (cm[0] == 0.f) psystem->senseColliderImpulse(true);       // a kinematic obstacle: the impulse is all that is asked for
+        }
     }
     if (const char* v = value(argc, argv, "log")) {
         const char* fq = value(argc, argv, "logfreq");
@@ -582,6 +604,13 @@ int main(int argc, char** argv) {
            (1.0e-3 * numParticles) / avg, avg, numParticles, 1, 0);
     printf("{\"particle_steps_per_s\": %.1f, \"particles\": %u, \"iterations\": %d, \"steps_per_update\": %d, \"seconds\": %.6f}\n",
            (double)numParticles * iterations * substeps / secs, numParticles, iterations, substeps, secs);
+    if (colliderMassArg) {       // floats with 9, doubles with 17 digits: they read back exactly
+        double J[3];
+        psystem->getColliderImpulse(J);
+        const float3 cc = psystem->getColliderPos(), cu = psystem->getColliderVelocity();
+        printf("collider: centre %.9g %.9g %.9g velocity %.9g %.9g %.9g impulse %.17g %.17g %.17g\n", cc.x, cc.y, cc.z, cu.x, cu.y, cu.z,
+               J[0], J[1], J[2]);
+    }
     if (dump > 0) psystem->dumpParticles(0, (uint)dump);
     if (const char* v = value(argc, argv, "out")) {      // xyzw per creation index, then vxyz0, raw fp32
         FILE* f = fopen(v, "wb");

@@ -816,6 +816,86 @@ __device__ __forceinline__ void push_out_of_spheres(const Phys& ph, float4& pi, 
     }
 }
 
+// The same rule on a TRACKED context (sph_set_collider_bodies): the table is read from device memory through a wave-uniform
+// address, and where sphere j changes a velocity by k * nrm the lane also forms t = -(mass * (k * nrm)), the momentum the sphere
+// takes.  A wave in which sphere j kicked any lane (a second ballot, wave-uniform) adds the terms of its kicked lanes in
+// ascending lane order in float64 -- a scalar-indexed read per lane, no per-lane accumulators -- and its first lane stores the
+// three sums to partial[wave][j].  Every wave stores one mask word saying which rows it wrote (0 for nearly every wave), so
+// k_spheres_step never reads a row of an earlier step and nothing is cleared in between.  The particle arithmetic is the
+// function above, operation for operation.
+__device__ __forceinline__ float lane_value(float v, uint32_t l) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), (int)l));
+}
+__device__ __forceinline__ void push_out_of_spheres(const Phys& ph, float4& pi, float4& vi, const SpheresTracked& st) {
+#pragma clang fp contract(off)
+    const Spheres& sp = *st.table;
+    const uint32_t n = sp.n;
+    const uint32_t wave = st.rel >> 6;
+    const bool first = (st.rel & 63u) == (uint32_t)__builtin_ctzll(__ballot(true));     // the wave's first lane that is here
+    bool inside = false;
+    for (uint32_t j = 0; j < n; j++) {
+        const float dx = pi.x - sp.c[j].x, dy = pi.y - sp.c[j].y, dz = pi.z - sp.c[j].z;
+        inside |= dx * dx + dy * dy + dz * dz < sp.u[j].w;
+    }
+    if (__ballot(inside) == 0ull) {
+        if (first) st.mask[wave] = 0u;
+        return;
+    }
+    bool hit = false;
+    uint32_t wrote = 0u;
+    for (uint32_t j = 0; j < n; j++) {
+        const float dx = pi.x - sp.c[j].x, dy = pi.y - sp.c[j].y, dz = pi.z - sp.c[j].z;
+        const float r2 = dx * dx + dy * dy + dz * dz;
+        float tx = 0.f, ty = 0.f, tz = 0.f;
+        bool kicked = false;
+        if (r2 < sp.u[j].w) {
+            float nx = 0.f, ny = 1.f, nz = 0.f;
+            if (r2 > 0.f) {
+                const float r = sqrtf(r2);
+                nx = dx / r; ny = dy / r; nz = dz / r;
+            }
+            const float rp = sp.c[j].w;
+            pi.x = sp.c[j].x + rp * nx;
+            pi.y = sp.c[j].y + rp * ny;
+            pi.z = sp.c[j].z + rp * nz;
+            const float wn = (vi.x - sp.u[j].x) * nx + (vi.y - sp.u[j].y) * ny + (vi.z - sp.u[j].z) * nz;
+            if (wn < 0.f) {
+                const float k = (ph.wall_damping - 1.f) * wn;
+                const float kx = k * nx, ky = k * ny, kz = k * nz;
+                vi.x += kx; vi.y += ky; vi.z += kz;
+                tx = -(ph.mass * kx); ty = -(ph.mass * ky); tz = -(ph.mass * kz);
+                kicked = true;
+            }
+            hit = true;
+        }
+        const uint64_t km = __ballot(kicked);
+        if (km != 0ull) {                                            // wave-uniform
+            double sx = 0.0, sy = 0.0, sz = 0.0;
+            for (uint64_t m = km; m != 0ull; m &= m - 1ull) {
+                const uint32_t l = (uint32_t)__builtin_ctzll(m);
+                sx += (double)lane_value(tx, l); sy += (double)lane_value(ty, l); sz += (double)lane_value(tz, l);
+            }
+            if (first) {
+                double* row = st.partial + ((size_t)wave * SPH_MAX_COLLIDERS + j) * 3u;
+                row[0] = sx; row[1] = sy; row[2] = sz;
+            }
+            wrote |= 1u << j;
+        }
+    }
+    if (first) st.mask[wave] = wrote;
+    if (hit) {
+        wall(pi.x, vi.x, ph.box_min[0], ph.box_max[0], ph.wall_eps, ph.wall_damping);
+        wall(pi.y, vi.y, ph.box_min[1], ph.box_max[1], ph.wall_eps, ph.wall_damping);
+        wall(pi.z, vi.z, ph.box_min[2], ph.box_max[2], ph.wall_eps, ph.wall_damping);
+    }
+}
+
+// the pack as one lane's integrate takes it: the tracked form learns the lane's slot relative to the first owned slot
+__device__ __forceinline__ const Spheres& at_slot(const Spheres& sp, uint32_t) { return sp; }
+__device__ __forceinline__ SpheresTracked at_slot(const SpheresTracked& st, uint32_t rel) {
+    return SpheresTracked{st.table, st.partial, st.mask, rel};
+}
+
 // `sp`: empty, or the sphere table (the collider instantiations of k_force / k_integrate, launched only while a context has
 // colliders); an empty pack compiles to exactly the code without them.
 template <class... Sph>
@@ -875,7 +955,8 @@ extern "C" void sph_debug_pair_stats(unsigned long long* out, int on) {     // r
 #else
 #define PAIR_STAT(k, v) do { } while (0)
 #endif
-// Sph: empty, or Spheres for the collider instantiation of the fused pass (one more argument: the sphere table, by value)
+// Sph: empty, or Spheres for the collider instantiation of the fused pass (one more argument: the sphere table, by value), or
+// SpheresTracked for a tracked context's (the table by pointer and the impulse outputs)
 template <bool FORCE, bool COLL, bool INTEG, int THREADS, class... Sph>
 __global__ __launch_bounds__(THREADS, SPH_FORCE_OCC) void k_force(
     const float4* __restrict__ posi, const float4* __restrict__ velr, const float2* __restrict__ dp,
@@ -1019,7 +1100,7 @@ __global__ __launch_bounds__(THREADS, SPH_FORCE_OCC) void k_force(
 #endif
             }
             if (INTEG) {
-                integrate_one(ph, dt, pi, vi, dpi.x, fpx + fvx, fpy + fvy, fpz + fvz, dvx, dvy, dvz, sp...);
+                integrate_one(ph, dt, pi, vi, dpi.x, fpx + fvx, fpy + fvy, fpz + fvz, dvx, dvy, dvz, at_slot(sp, i - slot0)...);
                 posi_out[i] = pi;
                 velr_out[i] = vi;
                 if (pos_by_index) pos_by_index[__float_as_uint(pi.w)] = make_float4(pi.x, pi.y, pi.z, 1.0f);
@@ -1211,11 +1292,114 @@ static void force_kernel(sph_ctx* c, bool small, const Targets& tg, uint32_t thr
 #undef SPH_LAUNCH_FORCE_T
 }
 
-// centres of the colliders after a step of dt (once per step: the fused pass's force_finish, launch_integrate)
-static void advance_colliders(sph_ctx* c, float dt) {
+// ---- tracked contexts: the spheres' step on the device (sph_set_collider_bodies, include/sph_hip.h) ----------------------------
+// One block, once per step, behind the step's force launch on the context's stream.  Thread t takes the waves [t K, (t + 1) K)
+// (K a multiple of 4: one 16-byte load brings four mask words), adds the rows the masks point to in ascending wave order in
+// float64; the threads' sums are then added in ascending thread order (only the threads that found a row: a list of ballots),
+// so the order of the whole sum depends on the wave count alone.  Then J and the step count are stored and sphere j's thread
+// applies the body update of the header to the table the next step's kernels read.
+__global__ __launch_bounds__(SPHERES_STEP_THREADS) void k_spheres_step(Spheres* table, const double* __restrict__ partial,
+                                                                       const uint32_t* __restrict__ mask, uint32_t n_waves,
+                                                                       double* J, SphereBodies b, float dt, Phys ph) {
 #pragma clang fp contract(off)
+    constexpr uint32_t T = SPHERES_STEP_THREADS, NJ = SPH_MAX_COLLIDERS * 3;
+    __shared__ double s_acc[T][NJ];
+    __shared__ double s_J[NJ];
+    __shared__ uint64_t s_found[T / 64];
+    const uint32_t t = threadIdx.x;
+    const uint32_t K = ((n_waves + T - 1u) / T + 3u) & ~3u;
+    const uint32_t w0 = t * K, w1 = min(w0 + K, n_waves);
+    double acc[SPH_MAX_COLLIDERS][3] = {};
+    bool found = false;
+    for (uint32_t q = w0; q < w1; q += 4u) {
+        const uint4 m4 = *reinterpret_cast<const uint4*>(mask + q);          // (the buffer is padded to whole quads)
+        const uint32_t mm[4] = {m4.x, m4.y, m4.z, m4.w};
+#pragma unroll
+        for (uint32_t e = 0; e < 4u; e++) {
+            const uint32_t m = q + e < w1 ? mm[e] : 0u;
+            if (m) {
+                found = true;
+                const double* row = partial + (size_t)(q + e) * NJ;
+#pragma unroll
+                for (uint32_t j = 0; j < SPH_MAX_COLLIDERS; j++)
+                    if ((m >> j) & 1u) { acc[j][0] += row[j * 3u]; acc[j][1] += row[j * 3u + 1u]; acc[j][2] += row[j * 3u + 2u]; }
+            }
+        }
+    }
+    const uint64_t fb = __ballot(found);
+    if ((t & 63u) == 0u) s_found[t >> 6] = fb;
+    if (found) {
+#pragma unroll
+        for (uint32_t j = 0; j < SPH_MAX_COLLIDERS; j++) { s_acc[t][j * 3u] = acc[j][0]; s_acc[t][j * 3u + 1u] = acc[j][1]; s_acc[t][j * 3u + 2u] = acc[j][2]; }
+    }
+    __syncthreads();
+    if (t < NJ) {
+        double sum = 0.0;
+        for (uint32_t w = 0; w < T / 64u; w++)
+            for (uint64_t m = s_found[w]; m != 0ull; m &= m - 1ull) sum += s_acc[w * 64u + (uint32_t)__builtin_ctzll(m)][t];
+        s_J[t] = sum;
+        J[t] = sum;
+    }
+    if (t == NJ) reinterpret_cast<unsigned long long*>(J)[NJ] += 1ull;       // integrates since tracking began
+    __syncthreads();
+    if (t >= table->n) return;
+    const float4 c = table->c[t], u = table->u[t], am = b.am[t];
+    float cx[3] = {c.x, c.y, c.z}, ux[3] = {u.x, u.y, u.z};
+    const float ax[3] = {am.x, am.y, am.z};
+    if (am.w > 0.f) {
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            ux[a] = (float)(((double)ux[a] + s_J[t * 3u + a] / (double)am.w) + (double)dt * (double)ax[a]);
+            wall(cx[a], ux[a], ph.box_min[a], ph.box_max[a], b.radius[t], ph.wall_damping);
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 3; a++) cx[a] = cx[a] + dt * ux[a];
+    table->c[t] = make_float4(cx[0], cx[1], cx[2], c.w);
+    table->u[t] = make_float4(ux[0], ux[1], ux[2], u.w);
+}
+
+// Installing the set, or refreshing R + eps and its square after sph_set_params: the table travels by value, so no host buffer
+// has to outlive the call and the host does not wait.  The full form also zeroes J and the step count.
+__global__ void k_spheres_install(Spheres* table, Spheres v, double* J, int radii_only) {
+    const uint32_t t = threadIdx.x;
+    if (t < SPH_MAX_COLLIDERS) {
+        if (radii_only) { table->c[t].w = v.c[t].w; table->u[t].w = v.u[t].w; }
+        else { table->c[t] = v.c[t]; table->u[t] = v.u[t]; }
+    }
+    if (radii_only) return;
+    if (t == 0) table->n = v.n;
+    if (t <= SPH_MAX_COLLIDERS * 3) J[t] = 0.0;         // (the word behind the 24 sums is the step count: the same zero bits)
+}
+
+int launch_spheres_install(sph_ctx* c) {
+    hipLaunchKernelGGL(k_spheres_install, dim3(1), dim3(64), 0, c->stream, c->trk_table, sphere_table(c), c->trk_J, 0);
+    SPH_HIP(hipGetLastError());
+    return SPH_OK;
+}
+
+// (the host's centres and velocities are stale on a tracked context: only the radius columns are written)
+int launch_spheres_radii(sph_ctx* c) {
+    hipLaunchKernelGGL(k_spheres_install, dim3(1), dim3(64), 0, c->stream, c->trk_table, sphere_table(c), c->trk_J, 1);
+    SPH_HIP(hipGetLastError());
+    return SPH_OK;
+}
+
+static SpheresTracked tracked_pack(const sph_ctx* c) { return SpheresTracked{c->trk_table, c->trk_partial, c->trk_mask, 0u}; }
+
+// centres of the colliders after a step of dt (once per step: the fused pass's force_finish, launch_integrate).  A tracked
+// context queues k_spheres_step instead: the impulses of the launch just queued, the bodies and the centres, on the device.
+static int advance_colliders(sph_ctx* c, float dt) {
+#pragma clang fp contract(off)
+    if (c->tracked) {
+        hipLaunchKernelGGL(k_spheres_step, dim3(1), dim3(SPHERES_STEP_THREADS), 0, c->stream, c->trk_table, c->trk_partial,
+                           c->trk_mask, ceil_div(c->n, 64u), c->trk_J, c->bodies, dt, c->phys);
+        SPH_HIP(hipGetLastError());
+        return SPH_OK;
+    }
     for (uint32_t j = 0; j < c->n_colliders; j++)
         for (int a = 0; a < 3; a++) c->colliders[j].center[a] = c->colliders[j].center[a] + dt * c->colliders[j].velocity[a];
+    return SPH_OK;
 }
 
 // One launch of the pair kernel over the owned slots [lo, hi) minus the hole [hole_lo, hole_hi) (lo - own_off,
@@ -1237,7 +1421,8 @@ int launch_force_hole(sph_ctx* c, uint32_t lo, uint32_t hi, uint32_t hole_lo, ui
     if (force && !collide && !integrate) force_kernel<true, false, false>(c, small, tg, threads, dt, mark, false);
     else if (!force && collide && !integrate) force_kernel<false, true, false>(c, small, tg, threads, dt, mark, false);
     else if (force && collide && integrate) {
-        if (c->n_colliders) force_kernel<true, true, true>(c, small, tg, threads, dt, mark, false, sphere_table(c));
+        if (c->tracked) force_kernel<true, true, true>(c, small, tg, threads, dt, mark, false, tracked_pack(c));
+        else if (c->n_colliders) force_kernel<true, true, true>(c, small, tg, threads, dt, mark, false, sphere_table(c));
         else force_kernel<true, true, true>(c, small, tg, threads, dt, mark, false);
     } else {
         set_error("launch_force: unsupported combination");
@@ -1272,27 +1457,26 @@ bool force_begin(sph_ctx* c, bool integrate) {
     return integrate && c->sort_merge && c->order_valid;
 }
 
-void force_finish(sph_ctx* c, bool integrate, bool mark, float dt) {
-    if (!integrate) return;
-    advance_colliders(c, dt);
+int force_finish(sph_ctx* c, bool integrate, bool mark, float dt) {
+    if (!integrate) return SPH_OK;
+    const int rc = advance_colliders(c, dt);      // (the step's launches are queued: the state below is theirs either way)
     swap_state(c, false);
     c->keys_fresh = true;
     if (mark) {
         c->mm_marked = true; c->mm_scanned = false; c->mm_marked_off = c->own_off; c->mm_marked_n = c->n;
         mm_scan_marks(c);          // count them now: the next sort finds the number ready
     }
+    return rc;
 }
 
 int launch_force(sph_ctx* c, bool force, bool collide, bool integrate, float dt) {
     if (c->n == 0) {
-        if (integrate) advance_colliders(c, dt);      // (a step without particles still moves the spheres)
-        return SPH_OK;
+        return integrate ? advance_colliders(c, dt) : SPH_OK;      // (a step without particles still moves the spheres)
     }
     const bool mark = force_begin(c, integrate);
     int rc = launch_force_range(c, c->own_off, c->own_off + c->n, force, collide, integrate, dt, mark);
     if (rc) return rc;
-    force_finish(c, integrate, mark, dt);
-    return SPH_OK;
+    return force_finish(c, integrate, mark, dt);
 }
 
 static int launch_density_targets(sph_ctx* c, const Targets& tg, uint32_t threads) {
@@ -1344,27 +1528,26 @@ __global__ __launch_bounds__(256) void k_integrate(float4* __restrict__ posi, fl
     if (i >= hi) return;
     float4 pi = posi[i], vi = velr[i];
     const float4 fp = fpress[i], fv = fvisc[i], dv = dvel[i];
-    integrate_one(ph, dt, pi, vi, dp[i].x, fp.x + fv.x, fp.y + fv.y, fp.z + fv.z, dv.x, dv.y, dv.z, sp...);
+    integrate_one(ph, dt, pi, vi, dp[i].x, fp.x + fv.x, fp.y + fv.y, fp.z + fv.z, dv.x, dv.y, dv.z, at_slot(sp, i - lo)...);
     posi[i] = pi;
     velr[i] = vi;
     if (pos_by_index) pos_by_index[__float_as_uint(pi.w)] = make_float4(pi.x, pi.y, pi.z, 1.0f);
 }
 
 int launch_integrate(sph_ctx* c, float dt) {
-    if (c->n == 0) {
-        advance_colliders(c, dt);
-        return SPH_OK;
-    }
+    if (c->n == 0) return advance_colliders(c, dt);
     float4* const pos_out = c->slab ? nullptr : c->pos_out;
-    if (c->n_colliders)
+    if (c->tracked)
+        hipLaunchKernelGGL(k_integrate<SpheresTracked>, dim3(ceil_div(c->n, 256)), dim3(256), 0, c->stream, c->posi, c->velr, c->dp,
+                           c->fpress, c->fvisc, c->dvel, pos_out, c->own_off, c->own_off + c->n, dt, c->phys, tracked_pack(c));
+    else if (c->n_colliders)
         hipLaunchKernelGGL(k_integrate<Spheres>, dim3(ceil_div(c->n, 256)), dim3(256), 0, c->stream, c->posi, c->velr, c->dp,
                            c->fpress, c->fvisc, c->dvel, pos_out, c->own_off, c->own_off + c->n, dt, c->phys, sphere_table(c));
     else
         hipLaunchKernelGGL(k_integrate<>, dim3(ceil_div(c->n, 256)), dim3(256), 0, c->stream, c->posi, c->velr, c->dp,
                            c->fpress, c->fvisc, c->dvel, pos_out, c->own_off, c->own_off + c->n, dt, c->phys);
     SPH_HIP(hipGetLastError());
-    advance_colliders(c, dt);
-    return SPH_OK;
+    return advance_colliders(c, dt);
 }
 
 }  // namespace sph

@@ -1690,7 +1690,7 @@ int step_forces(sph_slab* s, Step& st) {
         if (rc) return rc;
     }
     rc = after_comm(s); if (rc) return rc;                      // the mover count (force_finish) needs both launches
-    force_finish(c, true, mark, st.dt);
+    rc = force_finish(c, true, mark, st.dt); if (rc) return rc;
     c->have_force = c->have_coll = false;
     // (no event here: the comm stream's first action of the next step waits for an event the main stream records behind
     // k_slab_bounds_pack, i.e. behind everything queued above)

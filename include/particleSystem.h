@@ -88,7 +88,7 @@ public:
     // The collider sphere (sph_set_colliders): inert until enableCollider(true).  While it is enabled, update() hands
     // colliderPos / colliderRadius and the velocity to the context before its steps and reads the advanced centre back
     // into colliderPos after them.
-    void setColliderPos(float3 x) { m_params.colliderPos = x; }
+    void setColliderPos(float3 x) { m_params.colliderPos = x; m_bodyLive = false; }
     float3 getColliderPos() { return m_params.colliderPos; }
     float getColliderRadius() { return m_params.colliderRadius; }
     float getParticleRadius() { return m_params.particleRadius; }
@@ -112,9 +112,21 @@ public:
     // ---- additive: the collider sphere pushes the fluid (absent upstream, where it is drawn but inert) -----------------------
     void enableCollider(bool on);
     bool colliderEnabled() const { return m_colliderOn; }
-    void setColliderRadius(float r) { m_params.colliderRadius = r; }
-    void setColliderVelocity(float3 u) { m_colliderVel = u; }     // box units per unit time; kinematic (the fluid never pushes it)
+    void setColliderRadius(float r) { m_params.colliderRadius = r; m_bodyLive = false; }
+    void setColliderVelocity(float3 u) { m_colliderVel = u; m_bodyLive = false; }     // box units per unit time; kinematic unless the sphere has a mass
     float3 getColliderVelocity() const { return m_colliderVel; }
+    // A mass > 0 makes the sphere a free body (sph_set_collider_bodies of sph_hip.h): the fluid pushes it, it falls under
+    // `accel` (3 floats; null: none) and bounces off the walls; 0: back to kinematic.  While it is free the context moves it on
+    // the device: update() hands the sphere over once -- and again after any of the set* calls above, which re-place it -- and
+    // reads centre AND velocity back after its steps.  getColliderImpulse: the momentum the sphere took from the fluid in the
+    // last step of the last update().  A KINEMATIC sphere is a sensor too once senseColliderImpulse(true) is set: update() then
+    // gives it a body of mass 0 behind every sph_set_colliders (the sphere stays the caller's to move), which starts the tracking
+    // anew each time: the context's count of integrates behind the impulse then runs per update(), not since the sensor was
+    // switched on.  Zeros before the first update, and for a kinematic sphere without the sensor.
+    void setColliderMass(float mass, const float* accel = nullptr);
+    float getColliderMass() const { return m_colliderMass; }
+    void senseColliderImpulse(bool on) { m_colliderSense = on; m_bodyLive = false; }
+    void getColliderImpulse(double out[3]);
 
     // ---- additive (absent upstream; named by BASELINE.json's north star) ------------------------
     // 4 floats per particle, by creation index (the original NVIDIA sample's layout), getCapacity() rows; the pointer
@@ -164,6 +176,10 @@ protected:
     sph_ctx* m_ctx;
     bool m_colliderOn;
     float3 m_colliderVel;
+    float m_colliderMass;        // 0: kinematic
+    float m_colliderAccel[3];
+    bool m_colliderSense;        // a kinematic sphere gets a body of mass 0, for its impulse
+    bool m_bodyLive;             // the context holds a body for the sphere (mass > 0: its centre and velocity are the device's)
     bool m_hostStale;
     std::string m_logPath;
     void* m_log;

@@ -29,7 +29,7 @@
  *                  sph_set_params sph_get_params sph_sync sph_num_particles sph_capacity sph_ghost_layers sph_set_precision
  *                  sph_get_precision | sph_upload sph_set_by_index sph_reset_lattice sph_download sph_download_owned
  *                  sph_positions_dev sph_download_positions4 sph_snapshot_save sph_snapshot_load sph_snapshot_info |
- *                  sph_set_colliders sph_get_colliders | sph_emit sph_remove sph_count_in_regions |
+ *                  sph_set_colliders sph_get_colliders sph_set_collider_bodies sph_get_collider_impulses | sph_emit sph_remove sph_count_in_regions |
  *                  sph_hash sph_sort sph_build_cells sph_density sph_force sph_collide sph_integrate sph_step sph_step_phased
  *                  sph_force_collide_integrate | sph_timing_enable sph_timing_get sph_timing_reset | the z-slab phase calls
  *                  (sph_migrants_* sph_slab_counts sph_halo_* sph_layer_histogram) | sph_rccl_unique_id
@@ -207,7 +207,8 @@ int sph_download_positions4(sph_ctx* c, float* pos_xyzw);
 
 /* ---- sphere colliders (the reference's SimParams.colliderPos / colliderRadius, which no kernel of the reference reads) ----
  * A context holds 0 (the default) to SPH_MAX_COLLIDERS solid spheres, each with a centre c, a radius R > 0 and a velocity u,
- * all in box coordinates.  The velocity is kinematic: the fluid never pushes a sphere.  On EVERY integrate the context
+ * all in box coordinates.  The velocity is kinematic: the fluid never pushes a sphere (unless the sphere has a body with a mass:
+ * sph_set_collider_bodies below).  On EVERY integrate the context
  * performs (sph_step, sph_step_phased / sph_integrate, sph_force_collide_integrate, sph_slab_step), after the integration and
  * the wall rule, each particle with position x and velocity v goes through the spheres in order j = 0..n-1:
  *
@@ -239,8 +240,54 @@ typedef struct sph_collider {
 /* Replace the set by n spheres (n = 0 clears it).  n > SPH_MAX_COLLIDERS, a radius that is not finite or not positive, or a
  * centre or velocity that is not finite: SPH_E_INVALID, and the set is left unchanged. */
 int sph_set_colliders(sph_ctx* c, uint32_t n, const sph_collider* colliders);
-/* The current set with the ADVANCED centres: *n spheres into out (room for SPH_MAX_COLLIDERS; may be NULL if only *n is wanted). */
+/* The current set with the ADVANCED centres: *n spheres into out (room for SPH_MAX_COLLIDERS; may be NULL if only *n is wanted).
+ * On a tracked context (below) the centres and velocities live on the device: the call then synchronises the context's stream. */
 int sph_get_colliders(const sph_ctx* c, uint32_t* n, sph_collider* out);
+
+/* ---- spheres the fluid pushes back: the impulse sensor and free bodies ---------------------------------------------------------
+ * A context with colliders may hold one BODY per sphere.  While bodies are set the context is TRACKED:
+ *
+ * Tracking.  In every integrate, where sphere j's branch `if wn < 0` above adds k * nrm (k = (wall_damping - 1) * wn) to a
+ * particle's velocity, the same particle also forms  t = -(mass * (k * nrm))  -- fp32 products, each rounded (k itself, k * nrm
+ * as the velocity takes it, and the one by mass), no multiply-add fusion; mass is sph_params.mass.  J_j is the sum of these terms over all owned particles of that step,
+ * accumulated in float64: the momentum sphere j took from the fluid in the step.  Nothing else contributes -- not the position
+ * projection, not the wall pass that follows it -- and the particle rule itself does not change by one bit.  The order of the
+ * sum is fixed (lanes of a 64-slot wave in ascending order, then waves in ascending order within 256 equal runs of waves, then
+ * the runs in ascending order): two runs of the same calls give the same bits in J, in the centres and in every particle.  No
+ * floating-point atomic is involved.
+ *
+ * Sensor.  sph_get_collider_impulses synchronises the context's stream and returns J of the LAST integrate (3 doubles per
+ * sphere) and the number of integrates since tracking began; J / dt is the force on an obstacle.  It works for kinematic spheres
+ * (mass 0) too.  On a context that is not tracked it returns *n = 0 and *steps = 0 (and SPH_OK).
+ *
+ * Free bodies.  After the step's force launch, once per step and on the device (the host never waits), sphere j with mass > 0
+ * is updated in this order, per component a:
+ *     u[a] = (float)(((double)u[a] + J_j[a] / (double)mass_j) + (double)dt * (double)accel_j[a])     float64, one rounding to fp32
+ *     wall rule of the particles on (c[a], u[a]) with eps = R_j and the context's wall_damping:
+ *         if c - R < box_min: c = box_min + R, u *= wall_damping ;  if c + R > box_max: c = box_max - R, u *= wall_damping
+ *     c[a] = c[a] + dt * u[a]                                                                        fp32, as for a kinematic sphere
+ * so the wall rule puts the centre into [box_min + R, box_max - R] and the advance that follows moves it by one step's
+ * dt * u from there: a centre that has left that range by this much is put back by the next update.  A sphere with mass 0 keeps
+ * the caller's velocity and only advances, by the same fp32 expression as on an untracked context.  Spheres do NOT collide with
+ * each other, and a free body's push on the fluid is the kinematic rule above with its current velocity.
+ *
+ * sph_set_collider_bodies(n == number of colliders) starts tracking (or, on a tracked context, replaces the bodies and keeps the
+ * centres, the velocities, J and the step count); n == 0 stops it and leaves the spheres kinematic where they are.  It writes none of the
+ * context's step flags.  sph_set_colliders drops the bodies: the new set is kinematic and untracked, and a caller who never calls
+ * sph_set_collider_bodies keeps the behaviour described above call for call, kernel for kernel.  sph_set_params on a tracked
+ * context refreshes R + wall_eps on the device.  Device buffers (24 bytes per sphere and 64 particles of CAPACITY, plus one word
+ * per 64 particles) are allocated when tracking is first switched on.
+ *   SPH_E_STATE    a slab context: a rank's partial sums would need an all-reduce per step, and the N-slab = one-context bit
+ *                  identity would not hold.  Out of scope.
+ *   SPH_E_INVALID  n neither 0 nor the collider count; a mass that is negative or not finite; an accel that is not finite.
+ * In every refused case nothing has changed.  Snapshots do not carry bodies, as they do not carry colliders. */
+typedef struct sph_collider_body {
+    float mass;       /* 0: kinematic (its velocity is the caller's; the default) ; > 0 and finite: a free body */
+    float accel[3];   /* constant acceleration of a free body, e.g. (0, gravity_y, 0); ignored for mass 0 */
+} sph_collider_body;
+int sph_set_collider_bodies(sph_ctx* c, uint32_t n, const sph_collider_body* bodies);
+/* *n spheres; J: 3 doubles per sphere (room for SPH_MAX_COLLIDERS; may be NULL); steps may be NULL.  Synchronises. */
+int sph_get_collider_impulses(sph_ctx* c, uint32_t* n, double* J, uint64_t* steps);
 
 /* ---- emitters and drains: particles enter and leave a running simulation (no counterpart in the reference, whose particle
  *      set is fixed at construction; sph_set_by_index, its addSphere, only rewrites particles that exist) -----------------------
