@@ -79,6 +79,23 @@ class Region(C.Structure):
         return cls(REGION_HALFSPACE, (C.c_float * 3)(*[float(v) for v in point]), (C.c_float * 3)(*[float(v) for v in normal]), 0.0)
 
 
+RENDER_MAX_RADIUS_PX = 64   # SPH_RENDER_MAX_RADIUS_PX
+RENDER_MAX_SIZE = 4096      # SPH_RENDER_MAX_SIZE
+COLOR_MODES = {"index": 0, "speed": 1, "density": 2}      # SPH_COLOR_*
+
+
+class Camera(C.Structure):
+    """`sph_camera` of include/sph_hip.h: eye space has +x right, +y up, +z forward."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("rot", C.c_float * 9), ("trans", C.c_float * 3),
+                ("focal_px", C.c_float), ("near_z", C.c_float), ("far_z", C.c_float)]
+
+
+class RenderStyle(C.Structure):
+    """`sph_render_style` of include/sph_hip.h."""
+    _fields_ = [("color_mode", C.c_int32), ("lo", C.c_float), ("hi", C.c_float), ("radius", C.c_float),
+                ("index_count", C.c_uint32), ("background", C.c_uint8 * 4)]
+
+
 # name -> (restype, argtypes); also the list the symbol-export test walks
 _P = C.c_void_p
 _U32 = C.c_uint32
@@ -119,6 +136,11 @@ SIGNATURES = {
     "sph_emit": (C.c_int, [_P, _U32, _P, _P, _P, C.POINTER(_U32)]),
     "sph_remove": (C.c_int, [_P, _U32, C.POINTER(Region), C.POINTER(_U32), _P, _U32]),
     "sph_count_in_regions": (C.c_int, [_P, _U32, C.POINTER(Region), C.POINTER(_U32)]),
+    "sph_camera_look_at": (C.c_int, [C.POINTER(Camera), _U32, _U32, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                     C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float]),
+    "sph_render": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(RenderStyle)]),
+    "sph_render_read": (C.c_int, [_P, _P, _P, _P]),
+    "sph_render_image_dev": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_U32), C.POINTER(_U32)]),
     "sph_positions_dev": (C.c_int, [_P, C.POINTER(_P)]),
     "sph_download_positions4": (C.c_int, [_P, _P]),
     "sph_get_keys": (C.c_int, [_P, _P]),
@@ -246,6 +268,17 @@ def device_count():
     flag = C.c_int(0)
     n = load().sph_device_count(C.byref(flag))
     return n, bool(flag.value)
+
+
+def look_at(width, height, eye=(0.0, 0.0, 3.0), target=(0.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), fovy_deg=60.0, near_z=0.1,
+            far_z=100.0) -> Camera:
+    """`sph_camera_look_at` (a host helper: no GPU needed).  The defaults are the reference's view (SPH/particles.cpp:64-65,
+    324): three units back on +z, looking at the origin, 60 degrees."""
+    cam = Camera()
+    v3 = lambda v: (C.c_float * 3)(*[float(x) for x in v])
+    _check(load().sph_camera_look_at(C.byref(cam), int(width), int(height), v3(eye), v3(target), v3(up), float(fovy_deg),
+                                     float(near_z), float(far_z)))
+    return cam
 
 
 class LocalHub:
@@ -481,6 +514,29 @@ class Context:
         cnt = _U32(0)
         _check(self.L.sph_count_in_regions(self.h, m, arr, C.byref(cnt)))
         return int(cnt.value)
+
+    # -- pictures (whole-domain contexts; include/sph_hip.h: sph_render, sph_render_read, sph_render_image_dev) ----------------
+    def render(self, camera: Camera, color="index", lo=0.0, hi=1.0, radius=0.0, background=(0, 0, 0, 255), index_count=0):
+        """Queue one render of the owned particles as sphere sprites (asynchronous).  color: "index" (the reference's
+        colouring), "speed" or "density", the last two mapped from [lo, hi] onto the ramp; radius 0: the particle radius."""
+        if color not in COLOR_MODES:
+            raise ValueError(f"color {color!r}: one of {sorted(COLOR_MODES)}")
+        st = RenderStyle(COLOR_MODES[color], float(lo), float(hi), float(radius), int(index_count),
+                         (C.c_uint8 * 4)(*[int(v) for v in background]))
+        _check(self.L.sph_render(self.h, C.byref(camera), C.byref(st)))
+
+    def read_image(self):
+        """(rgba[h, w, 4] uint8, id[h, w] uint32, depth[h, w] float32) of the last render; synchronises."""
+        _, w, h = self.image_dev()
+        rgba, ident, depth = np.empty((h, w, 4), np.uint8), np.empty((h, w), np.uint32), np.empty((h, w), np.float32)
+        _check(self.L.sph_render_read(self.h, rgba.ctypes.data, ident.ctypes.data, depth.ctypes.data))
+        return rgba, ident, depth
+
+    def image_dev(self):
+        """(device pointer of the RGBA8 image of the last render, width, height)."""
+        p, w, h = _P(), _U32(), _U32()
+        _check(self.L.sph_render_image_dev(self.h, C.byref(p), C.byref(w), C.byref(h)))
+        return p.value, int(w.value), int(h.value)
 
     def positions4(self):
         out = np.empty((self.capacity, 4), dtype=np.float32)

@@ -110,6 +110,9 @@ ParticleSystem::ParticleSystem(uint numParticles, float3 boxDims, ParticleComput
     m_params.boxDims = boxDims;
     m_params.gridDim = m_grid.x;
     _initialize((int)numParticles);
+    const float eye[3] = {0.f, 0.f, 3.f}, target[3] = {0.f, 0.f, 0.f};      // camera_trans / the 60-degree gluPerspective, particles.cpp:64-65, 324
+    setCamera(640, 480, eye, target, 60.0f);
+    setRenderColor(SPH_COLOR_INDEX);
 }
 
 ParticleSystem::~ParticleSystem() {
@@ -418,6 +421,45 @@ void* ParticleSystem::getPositionsDevice() {
     void* p = nullptr;
     SPH_CHECK(sph_positions_dev(m_ctx, &p));
     return p;
+}
+
+// ---- pictures (sph_render; stands in for ParticleRenderer::display, render_particles.cpp) ---------------------
+void ParticleSystem::setCamera(uint width, uint height, const float* eye, const float* target, float fovyDeg) {
+    const float up[3] = {0.f, 1.f, 0.f};
+    SPH_CHECK(sph_camera_look_at(&m_camera, width, height, eye, target, up, fovyDeg, 0.1f, 100.0f));
+}
+
+void ParticleSystem::setRenderColor(int mode, float lo, float hi) {
+    memset(&m_renderStyle, 0, sizeof m_renderStyle);      // radius 0: the particle radius; index_count 0: the particle count
+    m_renderStyle.color_mode = mode;
+    m_renderStyle.lo = lo;
+    m_renderStyle.hi = hi;
+    m_renderStyle.background[3] = 255;                    // black, as glClearColor's default
+}
+
+void ParticleSystem::renderFrame() { SPH_CHECK(sph_render(m_ctx, &m_camera, &m_renderStyle)); }
+
+void* ParticleSystem::getFrameDevice(uint* width, uint* height) {
+    void* p = nullptr;
+    uint32_t w = 0, h = 0;
+    SPH_CHECK(sph_render_image_dev(m_ctx, &p, &w, &h));
+    if (width) *width = w;
+    if (height) *height = h;
+    return p;
+}
+
+void ParticleSystem::writeFrame(const char* path) {
+    uint w = 0, h = 0;
+    getFrameDevice(&w, &h);
+    m_frame.resize((size_t)w * h * 4);
+    SPH_CHECK(sph_render_read(m_ctx, m_frame.data(), nullptr, nullptr));
+    for (size_t i = 0; i < (size_t)w * h; i++)             // RGBA -> RGB in place (the write position never passes the read position)
+        for (int k = 0; k < 3; k++) m_frame[3 * i + k] = m_frame[4 * i + k];
+    FILE* f = fopen(path, "wb");
+    if (!f) { fprintf(stderr, "ParticleSystem: cannot open %s\n", path); exit(EXIT_FAILURE); }
+    fprintf(f, "P6\n%u %u\n255\n", w, h);
+    const bool ok = fwrite(m_frame.data(), 3, (size_t)w * h, f) == (size_t)w * h;
+    if (fclose(f) != 0 || !ok) { fprintf(stderr, "ParticleSystem: cannot write %s\n", path); exit(EXIT_FAILURE); }
 }
 
 void ParticleSystem::saveState(const std::string& path) { SPH_CHECK(sph_snapshot_save(m_ctx, path.c_str())); }

@@ -137,6 +137,7 @@ static void free_all(sph_ctx* c) {
     if (c->mm_count_host) hipHostFree(c->mm_count_host);
     if (c->h_scratch) hipHostFree(c->h_scratch);
     hipFree(c->trk_table); hipFree(c->trk_partial); hipFree(c->trk_mask); hipFree(c->trk_J);   // (sph_set_collider_bodies)
+    render_release(c);   // (sph_render)
 }
 
 static int create_impl(sph_ctx** out, int device, uint32_t capacity, const sph_params* p, uint32_t z_lo, uint32_t z_hi,

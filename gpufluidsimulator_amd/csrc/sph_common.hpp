@@ -143,6 +143,18 @@ struct sph_ctx {
     uint32_t* trk_mask = nullptr;       // ceil(cap / 64) words, padded to a multiple of 4
     double* trk_J = nullptr;            // SPH_MAX_COLLIDERS x 3 doubles of the last integrate, then the step count (uint64)
 
+    // the image of the last sph_render (sph_render.hip): per pixel a 64-bit key (depth bits << 32 | slot) and the resolved
+    // RGBA8, creation index and depth.  Allocated at the first render, again when the image size changes; never by a caller
+    // who does not render.
+    uint64_t* rd_keys = nullptr;
+    uint32_t* rd_rgba = nullptr;
+    uint32_t* rd_id = nullptr;
+    float* rd_depth = nullptr;
+    uint32_t rd_alloc_w = 0, rd_alloc_h = 0;    // what the buffers were allocated for
+    uint32_t rd_w = 0, rd_h = 0;                // the last image
+    bool rd_valid = false;
+    unsigned long long* rd_counts = nullptr;    // fragment counters of the measuring build (SPH_RENDER_STATS); else never allocated
+
     // pair kernels: a (dz, dy) row whose staged hull would exceed this many slots is read straight from global memory
     // by every lane instead (sph_pairs.hip: traverse; sph_set_direct_hull)
     uint32_t direct_hull = 512;
@@ -301,6 +313,7 @@ int launch_integrate(sph_ctx* c, float dt);
 // tracked contexts (sph_pairs.hip): write the host's sphere set into trk_table and zero J and the step count; refresh R + eps
 int launch_spheres_install(sph_ctx* c);
 int launch_spheres_radii(sph_ctx* c);
+void render_release(sph_ctx* c);      // sph_render.hip: frees the image buffers (sph_destroy)
 
 inline uint32_t ceil_div(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 

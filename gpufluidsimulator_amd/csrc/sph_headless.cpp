@@ -15,6 +15,11 @@
 //                      there is no particle).  One device only.
 //   -add=k,count       before update k, `count` particles at rest at the points of sph_ic_random_box(seed 2024) are appended
 //                      (ParticleSystem::addParticles); needs room (-capacity=M)
+//   -frames=DIR [-frameevery=K] [-framesize=WxH] [-camera=ex,ey,ez,tx,ty,tz[,fovy]] [-color=index|speed:lo:hi|density:lo:hi]
+//                      pictures: after the updates 0, K, 2K, ... (K = 1 by default) the particles are rendered on the device
+//                      (ParticleSystem::renderFrame) and written to DIR/frame_NNNNNN.ppm, NNNNNN the 0-based number of the update
+//                      the picture follows.  Defaults: 640x480, the reference's view (eye 0,0,3, the origin, 60 degrees), the
+//                      reference's colouring by creation index.  One device only.
 // Several GPUs (no counterpart in the reference, which is a single-device program): -gpus=N cuts the dam into N
 // z-slabs and steps them with sph_slab_step through the C ABI --
 //   -gpus=N            N child PROCESSES, forked before anything touches a GPU, rank r on device r (+ -device=), messages
@@ -42,6 +47,7 @@
 #include <poll.h>
 #include <signal.h>
 #include <sys/mman.h>
+#include <sys/stat.h>
 #include <sys/wait.h>
 #include <unistd.h>
 
@@ -407,13 +413,18 @@ int main(int argc, char** argv) {
                "[-ic=grid|random] [-steps=<per update>] [-gpus=<N> [-onegpu] [-slab] [-lattice=nx,ny,nz] [-protocol=1|3]] "
                "[-dump=<count>] [-log=<file> [-logfreq=<ms>] [-logstyle=oscar|frames]] [-sphere=<update>[,<radius>]] "
                "[-collider=<x>,<y>,<z>,<radius>[,<ux>,<uy>,<uz>]] [-collidermass=<M>[,<ax>,<ay>,<az>]] [-emit=<x>,<y>,<z>,<r>,<vx>,<vy>,<vz>,<every>] "
-               "[-drain=<x0>,<y0>,<z0>,<x1>,<y1>,<z1>[,<every>]] [-add=<update>,<count>] [-capacity=<particles>] [-out=<file>] [-save=<file>] [-load=<file>] [-file=<file>]\n"
+               "[-drain=<x0>,<y0>,<z0>,<x1>,<y1>,<z1>[,<every>]] [-add=<update>,<count>] [-capacity=<particles>] [-out=<file>] [-save=<file>] [-load=<file>] [-file=<file>] "
+               "[-frames=<dir> [-frameevery=<K>] [-framesize=<W>x<H>] [-camera=<ex>,<ey>,<ez>,<tx>,<ty>,<tz>[,<fovy>]] [-color=index|speed:<lo>:<hi>|density:<lo>:<hi>]]\n"
                "  -collider: a solid sphere the fluid flows around, moving at (ux, uy, uz) (default: at rest); one device only\n"
                "  -collidermass: the -collider sphere is a free body of mass M > 0 that the fluid pushes, under the acceleration (ax, ay, az) "
                "(default: (0, gravity_y, 0) of the run), or with M = 0 a kinematic obstacle whose load is wanted; prints its centre, velocity "
                "and last impulse at the end; one device only\n"
                "  -emit: every <every> updates append a lattice ball of radius <r> spacings at (x, y, z) moving at (vx, vy, vz), if its place is clear\n"
-               "  -drain: every <every> updates (default 1) remove the particles inside the box [x0,x1) x [y0,y1) x [z0,z1); one device only\n");
+               "  -drain: every <every> updates (default 1) remove the particles inside the box [x0,x1) x [y0,y1) x [z0,z1); one device only\n"
+               "  -frames: render the particles on the device after the updates 0, K, 2K, ... (-frameevery=K, default 1) and write "
+               "<dir>/frame_NNNNNN.ppm (binary PPM), NNNNNN = the 0-based number of the update the picture follows; -framesize default 640x480 "
+               "(1..4096 each), -camera default 0,0,3,0,0,0,60 (eye, target, vertical field of view in degrees: the reference's view), "
+               "-color default index (the reference's colouring), or speed / density mapped from [lo, hi]; one device only\n");
         return 0;
     }
     const int gpus = value(argc, argv, "gpus") ? atoi(value(argc, argv, "gpus")) : 1;
@@ -460,6 +471,43 @@ int main(int argc, char** argv) {
             return EXIT_FAILURE;
         }
     }
+    // -frames=DIR [-frameevery=K] [-framesize=WxH] [-camera=ex,ey,ez,tx,ty,tz[,fovy]] [-color=index|speed:lo:hi|density:lo:hi]
+    const char* framesDir = value(argc, argv, "frames");
+    int frameEvery = 1, colorMode = SPH_COLOR_INDEX;
+    unsigned frameW = 640, frameH = 480;
+    float camv[7] = {0.f, 0.f, 3.f, 0.f, 0.f, 0.f, 60.f}, colorLo = 0.f, colorHi = 1.f;
+    char extra = 0;
+    if (flag(argc, argv, "frames") && (!framesDir || !*framesDir)) { fprintf(stderr, "-frames: expected -frames=<directory>\n"); return EXIT_FAILURE; }
+    if (const char* v = value(argc, argv, "frameevery")) {
+        if (sscanf(v, "%d%c", &frameEvery, &extra) != 1 || frameEvery < 1) { fprintf(stderr, "-frameevery=%s: expected a whole number >= 1\n", v); return EXIT_FAILURE; }
+    }
+    if (const char* v = value(argc, argv, "framesize")) {
+        int fw = 0, fh = 0;
+        if (sscanf(v, "%dx%d%c", &fw, &fh, &extra) != 2 || fw < 1 || fw > SPH_RENDER_MAX_SIZE || fh < 1 || fh > SPH_RENDER_MAX_SIZE) {
+            fprintf(stderr, "-framesize=%s: expected <W>x<H> with 1..%d each\n", v, SPH_RENDER_MAX_SIZE);
+            return EXIT_FAILURE;
+        }
+        frameW = (unsigned)fw; frameH = (unsigned)fh;
+    }
+    if (const char* v = value(argc, argv, "camera")) {
+        const int k = sscanf(v, "%f,%f,%f,%f,%f,%f,%f%c", &camv[0], &camv[1], &camv[2], &camv[3], &camv[4], &camv[5], &camv[6], &extra);
+        bool ok = (k == 6 || k == 7) && camv[6] > 0.f && camv[6] < 180.f;
+        for (int a = 0; a < 7; a++) ok = ok && std::isfinite(camv[a]);
+        ok = ok && !(camv[0] == camv[3] && camv[2] == camv[5]);      // up is +y: the view direction must not be vertical (nor null)
+        if (!ok) {
+            fprintf(stderr, "-camera=%s: expected ex,ey,ez,tx,ty,tz or ex,ey,ez,tx,ty,tz,fovy with 0 < fovy < 180 and a view direction that is not vertical\n", v);
+            return EXIT_FAILURE;
+        }
+    }
+    if (const char* v = value(argc, argv, "color")) {
+        bool ok = true;
+        if (!strcmp(v, "index")) colorMode = SPH_COLOR_INDEX;
+        else if (!strncmp(v, "speed:", 6) || !strncmp(v, "density:", 8)) {
+            colorMode = v[0] == 's' ? SPH_COLOR_SPEED : SPH_COLOR_DENSITY;
+            ok = sscanf(strchr(v, ':') + 1, "%f:%f%c", &colorLo, &colorHi, &extra) == 2 && std::isfinite(colorLo) && std::isfinite(colorHi) && colorLo != colorHi;
+        } else ok = false;
+        if (!ok) { fprintf(stderr, "-color=%s: expected index, speed:<lo>:<hi> or density:<lo>:<hi> with lo != hi\n", v); return EXIT_FAILURE; }
+    }
     int addAt = -1, addCount = 0;
     const char* addArg = value(argc, argv, "add");
     if (addArg && (sscanf(addArg, "%d,%d", &addAt, &addCount) != 2 || addAt < 0 || addCount < 1)) {
@@ -471,6 +519,11 @@ int main(int argc, char** argv) {
             fprintf(stderr, "-emit / -drain / -add are not supported with -gpus=%d%s: sph_emit and sph_remove work on a whole-domain context "
                             "(the slab step sizes its messages from the previous step's counts); run them on one device\n",
                     gpus, gpus == 1 ? " -slab" : "");
+            return EXIT_FAILURE;
+        }
+        if (framesDir) {
+            fprintf(stderr, "-frames is not supported with -gpus=%d%s: sph_render works on a whole-domain context (the ranks would have to "
+                            "composite their images); run it on one device\n", gpus, gpus == 1 ? " -slab" : "");
             return EXIT_FAILURE;
         }
         if (colliderArg) {
@@ -541,6 +594,11 @@ int main(int argc, char** argv) {
         if (st && strcmp(st, "oscar") && strcmp(st, "frames")) { fprintf(stderr, "-logstyle=%s: expected oscar or frames\n", st); return EXIT_FAILURE; }
         psystem->setBenchmarkLog(v, fq ? atof(fq) : 2000.0, st && !strcmp(st, "oscar") ? ParticleSystem::LOG_OSCAR : ParticleSystem::LOG_FRAMES);
     }
+    if (framesDir) {
+        if (mkdir(framesDir, 0755) != 0 && errno != EEXIST) { fprintf(stderr, "-frames=%s: cannot create the directory\n", framesDir); return EXIT_FAILURE; }
+        psystem->setCamera(frameW, frameH, camv, camv + 3, camv[6]);
+        psystem->setRenderColor(colorMode, colorLo, colorHi);
+    }
     uint3 g = psystem->getGridSize();
     printf("Run %u particles simulation for %d iterations... (grid %ux%ux%u, box %g)\n\n", numParticles, iterations, g.x, g.y, g.z, box);
     if (!flag(argc, argv, "nowarmup")) psystem->update(timestep, 0);   // warm-up step, not timed
@@ -593,6 +651,11 @@ int main(int argc, char** argv) {
             psystem->addSphere(0, pos, vel, ballr, pr * 2.0f);
         }
         psystem->update(timestep, (float)i);
+        if (framesDir && i % frameEvery == 0) {
+            const std::string path = std::string(framesDir) + "/frame_" + std::to_string(1000000 + i % 1000000).substr(1) + ".ppm";
+            psystem->renderFrame();
+            psystem->writeFrame(path.c_str());
+        }
     }
     sph_sync(psystem->context());
     auto t1 = std::chrono::steady_clock::now();

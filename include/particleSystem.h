@@ -7,6 +7,8 @@
 //   * headless: no OpenGL.  getCurrentReadBuffer()/getColorBuffer() return 0; positions are read
 //     with getArray(POSITION) or through getPositionsDevice() (the `gl_pos` analogue).  The
 //     reference constructor needs a GL context even in -benchmark mode.
+//     Pictures come from the device renderer instead (setCamera / renderFrame / writeFrame, on top of
+//     sph_render): the reference's sphere sprites and colour ramp, written as PPM files.
 //   * only the GPU mode exists: SEQUENTIAL / OMP_PARALLEL abort with a message (no CPU fallback).
 //   * the grid follows the box: nextPow2((uint)(boxDims/(0.66666f*h))) per axis; the reference
 //     always uses the BOX_SIZE macro, i.e. 32^3 whatever the box (particleSystem.cpp:46, A.2-3).
@@ -128,6 +130,18 @@ public:
     void senseColliderImpulse(bool on) { m_colliderSense = on; m_bodyLive = false; }
     void getColliderImpulse(double out[3]);
 
+    // ---- additive: pictures without OpenGL (sph_render of sph_hip.h; the reference draws with render_particles.cpp) -----------
+    // The view of the next renderFrame: an image of width x height, the camera at eye[0..2] looking at target[0..2], up +y.
+    // Default: 640 x 480 and the reference's view -- eye (0, 0, 3), the origin, 60 degrees, 0.1 .. 100 (particles.cpp:64-65, 324).
+    void setCamera(uint width, uint height, const float* eye, const float* target, float fovyDeg = 60.0f);
+    // SPH_COLOR_INDEX (the reference's colouring; the default), or SPH_COLOR_SPEED / SPH_COLOR_DENSITY mapped from [lo, hi]
+    void setRenderColor(int mode, float lo = 0.0f, float hi = 1.0f);
+    // Queue one render of the particles as they are (asynchronous, no copy of the state); getFrameDevice: its RGBA8 image on
+    // the device.  writeFrame: the last rendered image as a binary PPM (P6, RGB, no alpha), rows top to bottom.
+    void renderFrame();
+    void* getFrameDevice(uint* width, uint* height);
+    void writeFrame(const char* path);
+
     // ---- additive (absent upstream; named by BASELINE.json's north star) ------------------------
     // 4 floats per particle, by creation index (the original NVIDIA sample's layout), getCapacity() rows; the pointer
     // stays valid until the next getArray call.
@@ -181,6 +195,9 @@ protected:
     bool m_colliderSense;        // a kinematic sphere gets a body of mass 0, for its impulse
     bool m_bodyLive;             // the context holds a body for the sphere (mass > 0: its centre and velocity are the device's)
     bool m_hostStale;
+    sph_camera m_camera;
+    sph_render_style m_renderStyle;
+    std::vector<unsigned char> m_frame;              // RGBA staging of writeFrame
     std::string m_logPath;
     void* m_log;
     double m_logLastMs, m_logGlobalMs, m_logFreqMs;

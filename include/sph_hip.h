@@ -30,6 +30,7 @@
  *                  sph_get_precision | sph_upload sph_set_by_index sph_reset_lattice sph_download sph_download_owned
  *                  sph_positions_dev sph_download_positions4 sph_snapshot_save sph_snapshot_load sph_snapshot_info |
  *                  sph_set_colliders sph_get_colliders sph_set_collider_bodies sph_get_collider_impulses | sph_emit sph_remove sph_count_in_regions |
+ *                  sph_camera_look_at sph_render sph_render_read sph_render_image_dev |
  *                  sph_hash sph_sort sph_build_cells sph_density sph_force sph_collide sph_integrate sph_step sph_step_phased
  *                  sph_force_collide_integrate | sph_timing_enable sph_timing_get sph_timing_reset | the z-slab phase calls
  *                  (sph_migrants_* sph_slab_counts sph_halo_* sph_layer_histogram) | sph_rccl_unique_id
@@ -337,6 +338,78 @@ int sph_remove(sph_ctx* c, uint32_t n_regions, const sph_region* regions, uint32
                uint32_t max_out);
 /* The same selection without the removal -- a sensor: a fill level, "is the nozzle clear".  Changes nothing; synchronises. */
 int sph_count_in_regions(sph_ctx* c, uint32_t n_regions, const sph_region* regions, uint32_t* count);
+
+/* ---- pictures: the fluid rendered on the device as depth-tested sphere sprites ----------------------------------------------------
+ * The reference hands its positions to an OpenGL point-sprite renderer (SPH/render_particles.cpp, SPH/shaders.cpp).  Here the
+ * same look -- point sprites shaded as spheres, the rainbow ramp -- is a software pass on the device over the sorted positions:
+ * no GL context, no copy of the state to the host.  Whole-domain contexts only.  A caller who never renders gets the launches
+ * and the allocations of a library without this section.
+ *
+ * THE RULE (fp32, every operation rounded, no multiply-add fusion, sums left to right, IEEE division and square root;
+ * tests/render_model.py is the same arithmetic in numpy and gives the same id and depth images bit for bit).
+ * Eye space has +x right, +y up and +z FORWARD.  For a particle at (x, y, z), k = 0, 1, 2:
+ *     pe[k] = ((rot[3k]*x + rot[3k+1]*y) + rot[3k+2]*z) + trans[k] ;  d = pe[2]
+ * A particle with d < near_z or d > far_z draws nothing.  Its sprite, with R the style's radius:
+ *     rp = (R * focal_px) / d ;  rp = min(rp, SPH_RENDER_MAX_RADIUS_PX) ;  rp = max(rp, 0.75f)
+ *     cx = 0.5f*width + (focal_px*pe[0]) / d ;  cy = 0.5f*height - (focal_px*pe[1]) / d
+ * (the floor of 0.75 px makes every visible particle cover at least one pixel centre).  Pixel (i, j), column i, row j, row 0
+ * on top:
+ *     u = ((i + 0.5f) - cx) / rp ;  v = ((j + 0.5f) - cy) / rp ;  mag = u*u + v*v ;  covered iff mag <= 1
+ * (the reference's `if (mag > 1.0) discard`).  The fragment's depth is d, flat per sprite, as a point sprite's is.  Per pixel
+ * the winner is the smallest d, among equal d the lowest SLOT (the particle's place in the owned range: the order of
+ * sph_download_owned and sph_get_order).  Shading of the winner:
+ *     nx = u ; ny = -v ; nz = sqrtf(1 - mag) ;  diffuse = max(0, (0.577f*nx + 0.577f*ny) + 0.577f*nz)
+ *     channel8 = (uint8)(min(c*diffuse, 1.0f)*255.0f + 0.5f) ;  alpha = 255
+ * with the colour c from the seven-colour ramp red, orange (1, 0.5, 0), yellow, green, cyan, blue, magenta:
+ *     t clamped to [0, 1] ;  s = t*6 ;  i = min((int)s, 5) ;  f = s - (float)i ;  c = a + f*(b - a) per channel (a, b: colours i, i+1)
+ *     SPH_COLOR_INDEX    t = (float)index / (float)index_count               (the reference's colouring)
+ *     SPH_COLOR_SPEED    t = (|v| - lo) / (hi - lo),  |v| = sqrtf((vx*vx + vy*vy) + vz*vz)
+ *     SPH_COLOR_DENSITY  t = (rho - lo) / (hi - lo),  rho of the last density pass: what sph_download reports (0 after an
+ *                        upload, an emission or a removal)
+ * A background pixel holds the style's background colour, id 0xFFFFFFFF and depth +inf.
+ * How: every pixel has a 64-bit key (bits of d) << 32 | slot; d is a positive fp32, so its bits order as the float does, and one
+ * 64-bit unsigned atomic min per fragment decides the pixel -- min does not depend on arrival order, so two renders of one
+ * state give the same bits, and no floating-point atomic is involved. */
+#define SPH_RENDER_MAX_RADIUS_PX 64
+#define SPH_RENDER_MAX_SIZE 4096
+typedef struct sph_camera {
+    uint32_t width, height;        /* 1..SPH_RENDER_MAX_SIZE each */
+    float rot[9];                  /* row-major world -> eye rotation */
+    float trans[3];
+    float focal_px;                /* > 0 */
+    float near_z, far_z;           /* 0 < near_z < far_z */
+} sph_camera;
+enum { SPH_COLOR_INDEX = 0, SPH_COLOR_SPEED = 1, SPH_COLOR_DENSITY = 2 };
+typedef struct sph_render_style {
+    int32_t  color_mode;
+    float    lo, hi;               /* SPH_COLOR_SPEED / SPH_COLOR_DENSITY */
+    float    radius;               /* world units; 0 = params.particle_radius */
+    uint32_t index_count;          /* SPH_COLOR_INDEX; 0 = sph_num_particles */
+    uint8_t  background[4];        /* r, g, b, a */
+} sph_render_style;
+/* Host helper: the camera at `eye` looking at `target`, vertical field of view fovy_deg, focal_px = 0.5*height / tan(fovy/2).
+ * The arithmetic is double and every field is rounded once to fp32; the kernels use only the struct's fields.  The upper
+ * layers default to the reference's view: eye (0, 0, 3), target the origin, up +y, 60 degrees, 0.1 .. 100
+ * (SPH/particles.cpp:64-65, 324) -- rot = diag(1, 1, -1), trans = (0, 0, 3).
+ *   SPH_E_INVALID  eye == target, up parallel to the view direction, anything not finite, a size outside 1..4096, fovy outside
+ *                  (0, 180), near_z <= 0 or far_z <= near_z.  *out is then untouched. */
+int sph_camera_look_at(sph_camera* out, uint32_t width, uint32_t height, const float eye[3], const float target[3],
+                       const float up[3], float fovy_deg, float near_z, float far_z);
+/* Render the owned particles as they are now: three kernels queued on the context's stream, no host wait.  Legal at any
+ * stage (also before the first step, between two phases, with no particle at all: all background); writes none of the context's
+ * step flags and no particle array.  Device buffers (8 + 4 + 4 + 4 bytes per pixel) are allocated at the first call, again
+ * when the image size changes (that call waits for the stream first), and freed by sph_destroy.
+ *   SPH_E_INVALID  a size outside 1..4096, a camera field that is not finite, focal_px <= 0, near_z <= 0, far_z <= near_z, an
+ *                  unknown colour mode, hi == lo (or either not finite) in a mode that uses them, a radius that is negative or
+ *                  not finite: the previous image stays;
+ *   SPH_E_STATE    a slab context: the ranks would have to composite their images.  Out of scope, as for emitters and bodies. */
+int sph_render(sph_ctx* c, const sph_camera* camera, const sph_render_style* style);
+/* The last image to the host: rgba width*height*4 bytes (r, g, b, a per pixel, rows top to bottom), id the winner's creation
+ * index, depth its d.  Any pointer may be NULL.  Synchronises.  SPH_E_STATE if nothing was rendered yet. */
+int sph_render_read(sph_ctx* c, uint8_t* rgba, uint32_t* id, float* depth);
+/* The device pointer of the RGBA8 image of the last render, and its size, for a consumer on the same stream: what
+ * sph_positions_dev is one stage earlier.  Valid until the next render of another size.  SPH_E_STATE if nothing was rendered. */
+int sph_render_image_dev(sph_ctx* c, void** rgba_dev, uint32_t* width, uint32_t* height);
 
 /* State snapshot (checkpoint / resume; absent in the reference, whose device state is never
  * serialised -- SURVEY.md section 5).  The file holds the parameters and, IN SLOT ORDER, position,
