@@ -622,6 +622,8 @@ int sph_reset_lattice(sph_ctx* c, const uint32_t lattice[3], int jitter, const f
     if (rc) return rc;
     c->own_off = c->gcap;
     c->n = count; c->n_glo = c->n_ghi = 0;
+    // an index without a particle reads (0, 0, 0, 0) in the by-index buffer, as after sph_upload: rows of an earlier, larger set
+    if (!c->slab) SPH_HIP(hipMemsetAsync(c->pos_out, 0, (size_t)c->pos_out_cap * sizeof(float4), c->stream));
     rc = launch_reset_lattice(c, lattice, jitter, jitter_dims, start, count);
     if (rc) return rc;
     c->next_index = (uint32_t)(start + count);

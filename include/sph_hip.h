@@ -152,7 +152,13 @@ int sph_create_slab_layers(sph_ctx** out, int device, uint32_t capacity, const s
 uint32_t sph_ghost_layers(const sph_ctx* c);        /* 0 for a whole-domain context */
 void sph_destroy(sph_ctx* c);                       /* freeArray x4, particleSystem.cpp:180-183 */
 int sph_set_stream(sph_ctx* c, void* hip_stream);   /* hipStream_t; NULL = default stream */
-int sph_set_params(sph_ctx* c, const sph_params* p);/* the per-update SimParams upload, :723 */
+/* The per-update SimParams upload, :723.  Legal at any stage; the grid cannot change.  A caller between two phases goes on where
+ * it was: the stage and the results of the phases that have run stay, and every later phase uses the new values.  Where the BOX
+ * moved between two phases, the cell keys and the cell table in use are still those of the old box until the next sph_hash: the
+ * neighbour stencil of that step is that of the cells the keys in use were computed with (the old box), its walls are the new
+ * box's, and the integrate's keys for the next step are the new box's.  The next sort is the full one
+ * (tests/test_gpu_context_walk.py holds such a step to the float64 model with exactly this stencil). */
+int sph_set_params(sph_ctx* c, const sph_params* p);
 int sph_get_params(const sph_ctx* c, sph_params* p);
 int sph_sync(sph_ctx* c);                           /* threadSync, particleSystem.cu:467 */
 uint32_t sph_num_particles(const sph_ctx* c);       /* owned particles */
@@ -185,7 +191,8 @@ int sph_set_by_index(sph_ctx* c, uint32_t first_index, uint32_t count, const flo
 /* Generate the dam-break lattice ON THE DEVICE (no host arrays, no PCIe): particles with creation index
  * index_start .. index_start+count of an (nx, ny, nz) lattice in the min corner of the box, spacing 2R,
  * zero velocity, counter-based jitter (amplitude from jitter_dims, NULL = the box; jitter = 0 switches it
- * off).  Bit-identical to sph_ic_dam_break / gpufluidsimulator_amd.ic.dam_break_lattice.  Replaces
+ * off).  Bit-identical to sph_ic_dam_break / gpufluidsimulator_amd.ic.dam_break_lattice.  Like sph_upload it replaces the set:
+ * the by-index position buffer of a whole-domain context reads (0, 0, 0, 0) for every index outside the range.  Replaces
  * initGrid + the AoS upload of reset(CONFIG_GRID) (SPH/particleSystem.cpp:839-874, 909-920). */
 int sph_reset_lattice(sph_ctx* c, const uint32_t lattice[3], int jitter, const float jitter_dims[3],
                       uint64_t index_start, uint32_t count);

@@ -13,10 +13,10 @@ import pytest
 import sph_model
 from conftest import bits
 from gpufluidsimulator_amd import capi, slab
+from phase_checks import REL_TOL, close as _close, phases_vs_model as _phases_vs_model      # shared with the state walk
 
 pytestmark = pytest.mark.gpu
 
-REL_TOL, FORCE_REL_TOL, POS_TOL_PER_BOX = 1e-5, 2e-5, 1e-6          # tests/test_gpu_parity.py
 RHO_MAX, RHO_RMS = 2e-2, 4e-3                                         # tests/test_gpu_mixed_precision.py
 FUSED_POS, FUSED_VEL = 1e-7, 2e-6                                     # tests/test_gpu_parity.py: fused vs phased
 DT = 5e-7
@@ -90,44 +90,6 @@ def _case(p, kind):
         pos[k, a] = (hi[a] - F(1e-6)) if upper else (lo[a] + F(1e-6))
         vel[k, a] = F(3000.0) if upper else F(-3000.0)
     return pos, vel
-
-
-def _close(name, a, b, rel, scale=None):
-    scale = float(np.abs(b).max()) if scale is None else scale
-    err = float(np.abs(np.asarray(a, np.float64) - np.asarray(b, np.float64)).max())
-    assert np.isfinite(a).all(), f"{name}: not finite"
-    assert err <= rel * max(scale, 1e-30), f"{name}: max abs err {err:.3e} > {rel:g} * {scale:.3e}"
-
-
-def _phases_vs_model(c, p, coll, dt, steps=2):
-    """`steps` phased steps of context c, each phase against the model fed the GPU's inputs."""
-    box = float(np.max(np.array(p.box_max[:]) - np.array(p.box_min[:])))
-    for _ in range(steps):
-        s0 = c.download(want=("pos", "vel"))
-        m = sph_model.Model(p, None if coll is None else (c.colliders()["centers"], coll[1], coll[2]))
-        pairs = m.pairs(s0["pos"])
-        c.hash(); c.sort(); c.build_cells(); c.density()
-        st = c.download(want=("density", "pressure"))
-        rho, pr = m.density(s0["pos"], pairs)
-        _close("density", st["density"], rho, REL_TOL)
-        _close("pressure", st["pressure"], pr, REL_TOL)
-        c.force(); c.collide()
-        f = c.download_forces()
-        fp, fv = m.forces(s0["pos"], s0["vel"], st["density"], st["pressure"], pairs)
-        fscale = float(max(np.abs(fp).max(), np.abs(fv).max()))
-        _close("f_press", f["fpress"], fp, FORCE_REL_TOL, fscale)
-        _close("f_visc", f["fvisc"], fv, FORCE_REL_TOL, fscale)
-        dv, count = m.collide(s0["pos"], s0["vel"], pairs)
-        assert np.array_equal(f["count"], count), "collision counts"
-        _close("delta_v", f["dv"], dv, FORCE_REL_TOL, max(float(np.abs(dv).max()), 1e-12))
-        out = m.integrate(s0["pos"], s0["vel"], st["density"], f["fpress"].astype(np.float64) + f["fvisc"], f["dv"], dt)
-        c.integrate(dt)
-        s1 = c.download(want=("pos", "vel"))
-        assert np.isfinite(s1["pos"]).all() and np.isfinite(s1["vel"]).all()
-        bad = sph_model.integrate_mismatch(out, s1["pos"], s1["vel"], POS_TOL_PER_BOX * box,
-                                           REL_TOL * float(np.abs(out[1]).max()))
-        assert bad.size == 0, ("integrate", bad.size, bad[:8], s1["pos"][bad[:2]], out[0][bad[:2]], s1["vel"][bad[:2]], out[1][bad[:2]])
-        yield count
 
 
 def _ctx(p, coll, n):
