@@ -96,6 +96,16 @@ class RenderStyle(C.Structure):
                 ("index_count", C.c_uint32), ("background", C.c_uint8 * 4)]
 
 
+class SurfaceStyle(C.Structure):
+    """`sph_surface_style` of include/sph_hip.h (sph_render_surface); surface_defaults() fills one."""
+    _fields_ = [("smooth_radius_px", C.c_uint32), ("smooth_iterations", C.c_uint32), ("depth_falloff", C.c_float),
+                ("flat_color", C.c_int32), ("tint", C.c_float * 3), ("absorb", C.c_float * 3), ("light", C.c_float * 3),
+                ("specular", C.c_float)]
+
+
+SURFACE_MAX_RADIUS_PX = 16   # SPH_SURFACE_MAX_RADIUS_PX
+SURFACE_MAX_ITERATIONS = 8   # SPH_SURFACE_MAX_ITERATIONS
+
 # name -> (restype, argtypes); also the list the symbol-export test walks
 _P = C.c_void_p
 _U32 = C.c_uint32
@@ -141,6 +151,9 @@ SIGNATURES = {
     "sph_render": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(RenderStyle)]),
     "sph_render_read": (C.c_int, [_P, _P, _P, _P]),
     "sph_render_image_dev": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_U32), C.POINTER(_U32)]),
+    "sph_surface_defaults": (None, [C.POINTER(SurfaceStyle)]),
+    "sph_render_surface": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(RenderStyle), C.POINTER(SurfaceStyle)]),
+    "sph_render_surface_read": (C.c_int, [_P, _P, _P, _P]),
     "sph_positions_dev": (C.c_int, [_P, C.POINTER(_P)]),
     "sph_download_positions4": (C.c_int, [_P, _P]),
     "sph_get_keys": (C.c_int, [_P, _P]),
@@ -279,6 +292,20 @@ def look_at(width, height, eye=(0.0, 0.0, 3.0), target=(0.0, 0.0, 0.0), up=(0.0,
     _check(load().sph_camera_look_at(C.byref(cam), int(width), int(height), v3(eye), v3(target), v3(up), float(fovy_deg),
                                      float(near_z), float(far_z)))
     return cam
+
+
+def surface_defaults(**fields) -> SurfaceStyle:
+    """`sph_surface_defaults` (a host helper: no GPU needed), with any field replaced: smooth_radius_px, smooth_iterations,
+    depth_falloff, flat_color, tint, absorb, light, specular."""
+    s = SurfaceStyle()
+    load().sph_surface_defaults(C.byref(s))
+    for k, v in fields.items():
+        if k in ("tint", "absorb", "light"):
+            v = (C.c_float * 3)(*[float(x) for x in v])
+        elif k not in ("smooth_radius_px", "smooth_iterations", "depth_falloff", "flat_color", "specular"):
+            raise TypeError(f"sph_surface_style has no field {k!r}")
+        setattr(s, k, v)
+    return s
 
 
 class LocalHub:
@@ -519,11 +546,31 @@ class Context:
     def render(self, camera: Camera, color="index", lo=0.0, hi=1.0, radius=0.0, background=(0, 0, 0, 255), index_count=0):
         """Queue one render of the owned particles as sphere sprites (asynchronous).  color: "index" (the reference's
         colouring), "speed" or "density", the last two mapped from [lo, hi] onto the ramp; radius 0: the particle radius."""
+        st = self._render_style(color, lo, hi, radius, background, index_count)
+        _check(self.L.sph_render(self.h, C.byref(camera), C.byref(st)))
+
+    @staticmethod
+    def _render_style(color="index", lo=0.0, hi=1.0, radius=0.0, background=(0, 0, 0, 255), index_count=0):
         if color not in COLOR_MODES:
             raise ValueError(f"color {color!r}: one of {sorted(COLOR_MODES)}")
-        st = RenderStyle(COLOR_MODES[color], float(lo), float(hi), float(radius), int(index_count),
-                         (C.c_uint8 * 4)(*[int(v) for v in background]))
-        _check(self.L.sph_render(self.h, C.byref(camera), C.byref(st)))
+        return RenderStyle(COLOR_MODES[color], float(lo), float(hi), float(radius), int(index_count),
+                           (C.c_uint8 * 4)(*[int(v) for v in background]))
+
+    def render_surface(self, camera: Camera, surface: "SurfaceStyle | None" = None, **style):
+        """Queue one render of the owned particles as a surface (asynchronous): sphere depth, thickness, smoothed depth,
+        normals, a water-like shading.  surface: a SurfaceStyle (None: surface_defaults()); style: the keywords of render().
+        read_image() then gives the RGBA image, the front particle's id and the SMOOTHED depth; read_surface() the rest."""
+        sf = surface_defaults() if surface is None else surface
+        st = self._render_style(**style)
+        _check(self.L.sph_render_surface(self.h, C.byref(camera), C.byref(st), C.byref(sf)))
+
+    def read_surface(self):
+        """(raw_depth[h, w] float32, thickness_q[h, w] uint32, normals[h, w, 3] float32) of the last surface render;
+        synchronises."""
+        _, w, h = self.image_dev()
+        raw, thick, normal = np.empty((h, w), np.float32), np.empty((h, w), np.uint32), np.empty((h, w, 3), np.float32)
+        _check(self.L.sph_render_surface_read(self.h, raw.ctypes.data, thick.ctypes.data, normal.ctypes.data))
+        return raw, thick, normal
 
     def read_image(self):
         """(rgba[h, w, 4] uint8, id[h, w] uint32, depth[h, w] float32) of the last render; synchronises."""

@@ -113,6 +113,7 @@ ParticleSystem::ParticleSystem(uint numParticles, float3 boxDims, ParticleComput
     const float eye[3] = {0.f, 0.f, 3.f}, target[3] = {0.f, 0.f, 0.f};      // camera_trans / the 60-degree gluPerspective, particles.cpp:64-65, 324
     setCamera(640, 480, eye, target, 60.0f);
     setRenderColor(SPH_COLOR_INDEX);
+    setRenderSurface(false);
 }
 
 ParticleSystem::~ParticleSystem() {
@@ -437,7 +438,16 @@ void ParticleSystem::setRenderColor(int mode, float lo, float hi) {
     m_renderStyle.background[3] = 255;                    // black, as glClearColor's default
 }
 
-void ParticleSystem::renderFrame() { SPH_CHECK(sph_render(m_ctx, &m_camera, &m_renderStyle)); }
+void ParticleSystem::setRenderSurface(bool on, const sph_surface_style* s) {
+    m_surfaceOn = on;
+    if (s) m_surfaceStyle = *s;
+    else sph_surface_defaults(&m_surfaceStyle);
+}
+
+void ParticleSystem::renderFrame() {
+    if (m_surfaceOn) SPH_CHECK(sph_render_surface(m_ctx, &m_camera, &m_renderStyle, &m_surfaceStyle));
+    else SPH_CHECK(sph_render(m_ctx, &m_camera, &m_renderStyle));
+}
 
 void* ParticleSystem::getFrameDevice(uint* width, uint* height) {
     void* p = nullptr;

@@ -154,6 +154,15 @@ struct sph_ctx {
     uint32_t rd_w = 0, rd_h = 0;                // the last image
     bool rd_valid = false;
     unsigned long long* rd_counts = nullptr;    // fragment counters of the measuring build (SPH_RENDER_STATS); else never allocated
+    // the extra planes of sph_render_surface, of the size of the image above: the raw sphere depth, the second plane of the
+    // filter's ping-pong (the first is rd_depth), the thickness counts and the normals (4 + 4 + 4 + 12 bytes per pixel).
+    // Allocated at the first surface render only, freed with the image.
+    float* rd_sf_raw = nullptr;
+    float* rd_sf_pong = nullptr;
+    uint32_t* rd_sf_thick = nullptr;
+    float* rd_sf_normal = nullptr;
+    bool rd_surface = false;                    // the last render was a surface render (sph_render_surface_read)
+    bool rd_sf_thick_on = false;                // ... and its thickness pass ran
 
     // pair kernels: a (dz, dy) row whose staged hull would exceed this many slots is read straight from global memory
     // by every lane instead (sph_pairs.hip: traverse; sph_set_direct_hull)

@@ -20,6 +20,11 @@
 //                      (ParticleSystem::renderFrame) and written to DIR/frame_NNNNNN.ppm, NNNNNN the 0-based number of the update
 //                      the picture follows.  Defaults: 640x480, the reference's view (eye 0,0,3, the origin, 60 degrees), the
 //                      reference's colouring by creation index.  One device only.
+//   -surface[=r,K[,tau]] [-tint=r,g,b] [-absorb=r,g,b]   with -frames: the pictures show the fluid as a surface
+//                      (ParticleSystem::setRenderSurface, sph_render_surface): sphere depth smoothed K times over a radius of r
+//                      pixels (r 0..16, K 0..8; default 5,2) with the depth falloff tau (world units; default 0: four particle
+//                      radii), normals from it, a water-like shading with the base colour -tint (default 0.25,0.55,0.95) and
+//                      the absorption -absorb per unit of thickness (default 6,2,0.5; 0,0,0: no thickness pass)
 // Several GPUs (no counterpart in the reference, which is a single-device program): -gpus=N cuts the dam into N
 // z-slabs and steps them with sph_slab_step through the C ABI --
 //   -gpus=N            N child PROCESSES, forked before anything touches a GPU, rank r on device r (+ -device=), messages
@@ -414,7 +419,8 @@ int main(int argc, char** argv) {
                "[-dump=<count>] [-log=<file> [-logfreq=<ms>] [-logstyle=oscar|frames]] [-sphere=<update>[,<radius>]] "
                "[-collider=<x>,<y>,<z>,<radius>[,<ux>,<uy>,<uz>]] [-collidermass=<M>[,<ax>,<ay>,<az>]] [-emit=<x>,<y>,<z>,<r>,<vx>,<vy>,<vz>,<every>] "
                "[-drain=<x0>,<y0>,<z0>,<x1>,<y1>,<z1>[,<every>]] [-add=<update>,<count>] [-capacity=<particles>] [-out=<file>] [-save=<file>] [-load=<file>] [-file=<file>] "
-               "[-frames=<dir> [-frameevery=<K>] [-framesize=<W>x<H>] [-camera=<ex>,<ey>,<ez>,<tx>,<ty>,<tz>[,<fovy>]] [-color=index|speed:<lo>:<hi>|density:<lo>:<hi>]]\n"
+               "[-frames=<dir> [-frameevery=<K>] [-framesize=<W>x<H>] [-camera=<ex>,<ey>,<ez>,<tx>,<ty>,<tz>[,<fovy>]] [-color=index|speed:<lo>:<hi>|density:<lo>:<hi>] "
+               "[-surface[=<r>,<K>[,<tau>]] [-tint=<r>,<g>,<b>] [-absorb=<r>,<g>,<b>]]]\n"
                "  -collider: a solid sphere the fluid flows around, moving at (ux, uy, uz) (default: at rest); one device only\n"
                "  -collidermass: the -collider sphere is a free body of mass M > 0 that the fluid pushes, under the acceleration (ax, ay, az) "
                "(default: (0, gravity_y, 0) of the run), or with M = 0 a kinematic obstacle whose load is wanted; prints its centre, velocity "
@@ -424,7 +430,11 @@ int main(int argc, char** argv) {
                "  -frames: render the particles on the device after the updates 0, K, 2K, ... (-frameevery=K, default 1) and write "
                "<dir>/frame_NNNNNN.ppm (binary PPM), NNNNNN = the 0-based number of the update the picture follows; -framesize default 640x480 "
                "(1..4096 each), -camera default 0,0,3,0,0,0,60 (eye, target, vertical field of view in degrees: the reference's view), "
-               "-color default index (the reference's colouring), or speed / density mapped from [lo, hi]; one device only\n");
+               "-color default index (the reference's colouring), or speed / density mapped from [lo, hi]; one device only\n"
+               "  -surface: with -frames, draw the fluid as a surface instead of sphere sprites: the spheres' depth smoothed <K> times (0..8, "
+               "default 2) over a radius of <r> pixels (0..16, default 5) with the depth falloff <tau> (world units, default 0 = four particle "
+               "radii), normals from the smoothed depth and a water-like shading; -tint the base colour (default 0.25,0.55,0.95), -absorb the "
+               "absorption per unit of thickness and channel (default 6,2,0.5; 0,0,0 = no thickness pass); one device only\n");
         return 0;
     }
     const int gpus = value(argc, argv, "gpus") ? atoi(value(argc, argv, "gpus")) : 1;
@@ -508,6 +518,39 @@ int main(int argc, char** argv) {
         } else ok = false;
         if (!ok) { fprintf(stderr, "-color=%s: expected index, speed:<lo>:<hi> or density:<lo>:<hi> with lo != hi\n", v); return EXIT_FAILURE; }
     }
+    // -surface[=r,K[,tau]] [-tint=r,g,b] [-absorb=r,g,b]
+    const bool surfaceOn = flag(argc, argv, "surface");
+    sph_surface_style surfaceStyle;
+    sph_surface_defaults(&surfaceStyle);
+    if (surfaceOn || value(argc, argv, "tint") || value(argc, argv, "absorb")) {
+        if (!framesDir || !surfaceOn) {
+            fprintf(stderr, "-surface / -tint / -absorb: expected -frames=<directory> -surface[=<r>,<K>[,<tau>]] [-tint=<r>,<g>,<b>] [-absorb=<r>,<g>,<b>]\n");
+            return EXIT_FAILURE;
+        }
+        if (const char* v = value(argc, argv, "surface")) {
+            int sr = 0, sk = 0;
+            float tau = 0.f;
+            const int k = sscanf(v, "%d,%d,%f%c", &sr, &sk, &tau, &extra);
+            if ((k != 2 && k != 3) || sr < 0 || sr > SPH_SURFACE_MAX_RADIUS_PX || sk < 0 || sk > SPH_SURFACE_MAX_ITERATIONS || !std::isfinite(tau) || tau < 0.f) {
+                fprintf(stderr, "-surface=%s: expected <r>,<K> or <r>,<K>,<tau> with r 0..%d, K 0..%d and tau >= 0\n", v, SPH_SURFACE_MAX_RADIUS_PX,
+                        SPH_SURFACE_MAX_ITERATIONS);
+                return EXIT_FAILURE;
+            }
+            surfaceStyle.smooth_radius_px = (uint32_t)sr;
+            surfaceStyle.smooth_iterations = (uint32_t)sk;
+            surfaceStyle.depth_falloff = tau;
+        }
+        const char* names[2] = {"tint", "absorb"};
+        float* fields[2] = {surfaceStyle.tint, surfaceStyle.absorb};
+        for (int a = 0; a < 2; a++)
+            if (const char* v = value(argc, argv, names[a])) {
+                float c3[3] = {0.f, 0.f, 0.f};
+                bool ok = sscanf(v, "%f,%f,%f%c", &c3[0], &c3[1], &c3[2], &extra) == 3;
+                for (int q = 0; q < 3; q++) ok = ok && std::isfinite(c3[q]) && c3[q] >= 0.f;
+                if (!ok) { fprintf(stderr, "-%s=%s: expected <r>,<g>,<b>, each finite and >= 0\n", names[a], v); return EXIT_FAILURE; }
+                for (int q = 0; q < 3; q++) fields[a][q] = c3[q];
+            }
+    }
     int addAt = -1, addCount = 0;
     const char* addArg = value(argc, argv, "add");
     if (addArg && (sscanf(addArg, "%d,%d", &addAt, &addCount) != 2 || addAt < 0 || addCount < 1)) {
@@ -519,6 +562,11 @@ int main(int argc, char** argv) {
             fprintf(stderr, "-emit / -drain / -add are not supported with -gpus=%d%s: sph_emit and sph_remove work on a whole-domain context "
                             "(the slab step sizes its messages from the previous step's counts); run them on one device\n",
                     gpus, gpus == 1 ? " -slab" : "");
+            return EXIT_FAILURE;
+        }
+        if (surfaceOn) {
+            fprintf(stderr, "-surface is not supported with -gpus=%d%s: sph_render_surface works on a whole-domain context (the ranks would "
+                            "have to composite their images); run it on one device\n", gpus, gpus == 1 ? " -slab" : "");
             return EXIT_FAILURE;
         }
         if (framesDir) {
@@ -598,6 +646,7 @@ int main(int argc, char** argv) {
         if (mkdir(framesDir, 0755) != 0 && errno != EEXIST) { fprintf(stderr, "-frames=%s: cannot create the directory\n", framesDir); return EXIT_FAILURE; }
         psystem->setCamera(frameW, frameH, camv, camv + 3, camv[6]);
         psystem->setRenderColor(colorMode, colorLo, colorHi);
+        psystem->setRenderSurface(surfaceOn, &surfaceStyle);
     }
     uint3 g = psystem->getGridSize();
     printf("Run %u particles simulation for %d iterations... (grid %ux%ux%u, box %g)\n\n", numParticles, iterations, g.x, g.y, g.z, box);

@@ -16,6 +16,21 @@
 //
 // Everything of the rule is fp32 with each operation rounded (fp contract off), sums left to right, IEEE division and square
 // root: tests/render_model.py is the same arithmetic in numpy and gives the same id and depth images bit for bit.
+//
+// The fluid as a surface (sph_surface_defaults, sph_render_surface, sph_render_surface_read): the same camera, sprites, walk and
+// key image, and an image-space half behind them.
+//
+//   k_render_clear    as above; the thickness words are cleared by a memset node on the stream
+//   k_surface_splat   the walk of k_render_splat; per covered pixel the SPHERE's depth d - R*sqrt(1 - mag) goes into the key, and
+//                     (THICK) every fragment, occluded or not, adds its quantised chord to the pixel's 32-bit thickness word: an
+//                     integer atomic add, so the plane does not depend on the order of arrival
+//   k_surface_depth   one pixel per lane: the key's depth bits -> the raw depth plane Z_0 (+inf on background)
+//   k_surface_filter  the hot kernel, K launches: a 32 x 8 tile of pixels per workgroup, the tile and its halo of r pixels staged
+//                     in LDS (+inf outside the image), (2r+1)^2 taps per pixel in the header's order; ping-pong between rd_depth
+//                     and rd_sf_pong, arranged so that Z_K lands in rd_depth and Z_0 stays readable
+//   k_surface_shade   one pixel per lane: normals from Z_K and its four neighbours, the front particle's colour, the thickness,
+//                     the shading; RGBA8 + creation index + normals
+// tests/surface_model.py is its arithmetic in numpy; every plane is compared bit for bit.
 #include "sph_common.hpp"
 
 #include <cmath>
@@ -74,6 +89,21 @@ __global__ __launch_bounds__(RENDER_THREADS) void k_render_clear(uint64_t* __res
     if (p < npix) keys[p] = RENDER_EMPTY;
 }
 
+// The walk: a superset of the covered pixels -- |(i + 0.5) - cx| <= rp up to rounding -- with one pixel of margin on either
+// side (tests/render_model.py: walk_bounds, held against the whole image in tests/test_render_model_cpu.py); clamped to the
+// image as floats, before the conversion (cx may be far outside): no pixel outside the image is ever addressed.  A tighter
+// walk (a quarter of the pixel tests for the smallest sprites) was measured and is SLOWER in a dense scene: the pass is
+// bound by the atomics on hot pixels, and lanes that arrive faster read staler words.
+// false: nothing to walk (also for a NaN centre); else [i0, i1) x [j0, j1), within the image.
+__device__ __forceinline__ bool sprite_walk(const RenderArgs& A, const Sprite& s, uint32_t& i0, uint32_t& i1, uint32_t& j0, uint32_t& j1) {
+    const float wf = (float)A.width, hf = (float)A.height;
+    const float x0 = fminf(fmaxf(floorf(s.cx - s.rp) - 1.0f, 0.0f), wf), x1 = fminf(fmaxf(ceilf(s.cx + s.rp) + 1.0f, 0.0f), wf);
+    const float y0 = fminf(fmaxf(floorf(s.cy - s.rp) - 1.0f, 0.0f), hf), y1 = fminf(fmaxf(ceilf(s.cy + s.rp) + 1.0f, 0.0f), hf);
+    if (!(x0 < x1 && y0 < y1)) return false;
+    i0 = (uint32_t)x0; i1 = (uint32_t)x1; j0 = (uint32_t)y0; j1 = (uint32_t)y1;
+    return true;
+}
+
 // COUNT: the measuring build (SPH_RENDER_STATS) also counts the covered fragments [0] and those that reached the atomic [1]
 template <bool COUNT>
 __global__ __launch_bounds__(RENDER_THREADS) void k_render_splat(const float4* __restrict__ posi, uint32_t n, RenderArgs A,
@@ -84,16 +114,8 @@ __global__ __launch_bounds__(RENDER_THREADS) void k_render_splat(const float4* _
     const float4 p = posi[slot];
     const Sprite s = sprite_of(A, p.x, p.y, p.z);
     if (!s.visible) return;
-    // The walk: a superset of the covered pixels -- |(i + 0.5) - cx| <= rp up to rounding -- with one pixel of margin on either
-    // side (tests/render_model.py: walk_bounds, held against the whole image in tests/test_render_model_cpu.py); clamped to the
-    // image as floats, before the conversion (cx may be far outside): no pixel outside the image is ever addressed.  A tighter
-    // walk (a quarter of the pixel tests for the smallest sprites) was measured and is SLOWER in a dense scene: the pass is
-    // bound by the atomics on hot pixels, and lanes that arrive faster read staler words.
-    const float wf = (float)A.width, hf = (float)A.height;
-    const float x0 = fminf(fmaxf(floorf(s.cx - s.rp) - 1.0f, 0.0f), wf), x1 = fminf(fmaxf(ceilf(s.cx + s.rp) + 1.0f, 0.0f), wf);
-    const float y0 = fminf(fmaxf(floorf(s.cy - s.rp) - 1.0f, 0.0f), hf), y1 = fminf(fmaxf(ceilf(s.cy + s.rp) + 1.0f, 0.0f), hf);
-    if (!(x0 < x1 && y0 < y1)) return;            // (also a NaN centre: nothing to draw)
-    const uint32_t i0 = (uint32_t)x0, i1 = (uint32_t)x1, j0 = (uint32_t)y0, j1 = (uint32_t)y1;   // [i0, i1) x [j0, j1), within the image
+    uint32_t i0, i1, j0, j1;
+    if (!sprite_walk(A, s, i0, i1, j0, j1)) return;
     const uint64_t key = ((uint64_t)__float_as_uint(s.d) << 32) | (uint64_t)slot;
     uint32_t covered = 0, sent = 0;
     for (uint32_t j = j0; j < j1; j++) {
@@ -139,6 +161,18 @@ __device__ __forceinline__ void ramp(float t, float c[3]) {
     }
 }
 
+// the ramp's argument of the particle in `slot` under the style's colour mode
+__device__ __forceinline__ float ramp_t(const RenderArgs& A, uint32_t slot, uint32_t index, const float4* __restrict__ velr,
+                                        const float2* __restrict__ dp) {
+#pragma clang fp contract(off)
+    if (A.mode == SPH_COLOR_INDEX) return (float)index / A.index_count;
+    if (A.mode == SPH_COLOR_SPEED) {
+        const float4 w = velr[slot];
+        return (sqrtf((w.x * w.x + w.y * w.y) + w.z * w.z) - A.lo) / A.span;
+    }
+    return (dp[slot].x - A.lo) / A.span;
+}
+
 __global__ __launch_bounds__(RENDER_THREADS) void k_render_resolve(const uint64_t* __restrict__ keys, const float4* __restrict__ posi,
                                                                    const float4* __restrict__ velr, const float2* __restrict__ dp,
                                                                    uint32_t n, RenderArgs A, uint32_t* __restrict__ rgba,
@@ -161,17 +195,8 @@ __global__ __launch_bounds__(RENDER_THREADS) void k_render_resolve(const uint64_
     const float nz = sqrtf(1.0f - mag);
     const float diffuse = fmaxf(0.0f, (0.577f * u + 0.577f * (-v)) + 0.577f * nz);
     const uint32_t index = __float_as_uint(p.w);
-    float t;
-    if (A.mode == SPH_COLOR_INDEX) {
-        t = (float)index / A.index_count;
-    } else if (A.mode == SPH_COLOR_SPEED) {
-        const float4 w = velr[slot];
-        t = (sqrtf((w.x * w.x + w.y * w.y) + w.z * w.z) - A.lo) / A.span;
-    } else {
-        t = (dp[slot].x - A.lo) / A.span;
-    }
     float c[3];
-    ramp(t, c);
+    ramp(ramp_t(A, slot, index, velr, dp), c);
     uint32_t out = 0xFF000000u;
 #pragma unroll
     for (int k = 0; k < 3; k++) out |= (uint32_t)(fminf(c[k] * diffuse, 1.0f) * 255.0f + 0.5f) << (8 * k);
@@ -180,9 +205,234 @@ __global__ __launch_bounds__(RENDER_THREADS) void k_render_resolve(const uint64_
     depth[pix] = __uint_as_float((uint32_t)(key >> 32));
 }
 
+// ---- the surface (sph_render_surface) -----------------------------------------------------------------------------------------------
+
+constexpr uint32_t SF_TX = 32, SF_TY = 8;             // the filter's tile of pixels: one workgroup of RENDER_THREADS lanes
+constexpr uint32_t SF_MAX_R = SPH_SURFACE_MAX_RADIUS_PX;
+constexpr uint32_t SF_TILE_MAX = (SF_TX + 2 * SF_MAX_R) * (SF_TY + 2 * SF_MAX_R);      // 64 x 40 floats = 10 KiB
+static_assert(SF_TX * SF_TY == RENDER_THREADS, "one pixel per lane");
+
+// the surface style of one call as the kernels take it: by value
+struct SurfaceArgs {
+    uint32_t r;
+    float tau;
+    float S[SF_MAX_R + 1];       // the filter's weights, from the host
+    int32_t flat, thick;         // thick: the thickness pass ran
+    float tint[3], absorb[3], L[3];
+    float specular;
+    float thick_unit;            // R * 0.125f: world thickness of one count
+    float bg[3];                 // (float)background[k] / 255.0f
+};
+
+#define SF_INF __uint_as_float(0x7F800000u)
+__device__ __forceinline__ bool sf_finite(float z) { return fabsf(z) < SF_INF; }
+
+// MIN: the depth key; THICK: the thickness word.  One launch does both; the measuring build SPH_SURFACE_SPLIT_WALK launches
+// them as two walks (profiles/scripts/surface_time.py).
+template <bool MIN, bool THICK>
+__global__ __launch_bounds__(RENDER_THREADS) void k_surface_splat(const float4* __restrict__ posi, uint32_t n, RenderArgs A,
+                                                                  uint64_t* __restrict__ keys, uint32_t* __restrict__ thick) {
+#pragma clang fp contract(off)
+    const uint32_t slot = blockIdx.x * RENDER_THREADS + threadIdx.x;
+    if (slot >= n) return;
+    const float4 p = posi[slot];
+    const Sprite s = sprite_of(A, p.x, p.y, p.z);
+    if (!(s.d - A.radius >= A.near_z && s.d <= A.far_z)) return;      // (also a NaN depth)
+    uint32_t i0, i1, j0, j1;
+    if (!sprite_walk(A, s, i0, i1, j0, j1)) return;
+    for (uint32_t j = j0; j < j1; j++) {
+        const size_t row = (size_t)j * A.width;
+        for (uint32_t i = i0; i < i1; i++) {
+            float u, v;
+            const float mag = sprite_mag(s, i, j, u, v);
+            if (!(mag <= 1.0f)) continue;
+            const float nz = sqrtf(1.0f - mag);
+            if (THICK) {
+                const uint32_t q = (uint32_t)(nz * 16.0f + 0.5f);
+                if (q) __hip_atomic_fetch_add(thick + row + i, q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (result unused: no return)
+            }
+            if (MIN) {
+                const float dz = s.d - A.radius * nz;
+                const uint64_t key = ((uint64_t)__float_as_uint(dz) << 32) | (uint64_t)slot;
+                const uint64_t seen = keys[row + i];
+                if (key < seen) __hip_atomic_fetch_min(keys + row + i, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+}
+
+// raw: Z_0.  also: a second copy where nothing is smoothed (Z_K = Z_0), else null
+__global__ __launch_bounds__(RENDER_THREADS) void k_surface_depth(const uint64_t* __restrict__ keys, uint32_t npix,
+                                                                  float* __restrict__ raw, float* __restrict__ also) {
+    const uint32_t pix = blockIdx.x * RENDER_THREADS + threadIdx.x;
+    if (pix >= npix) return;
+    const uint64_t key = keys[pix];
+    const float z = key == RENDER_EMPTY ? SF_INF : __uint_as_float((uint32_t)(key >> 32));
+    raw[pix] = z;
+    if (also) also[pix] = z;
+}
+
+// One iteration Z_{it-1} (src) -> Z_it (dst).  Lanes 0..31 of a wave hold one row of the tile and lanes 32..63 the next: every
+// LDS read of a half wave is 32 consecutive floats, free of bank conflicts whatever r.  The weights come by value and are put in
+// LDS once, so that |di| can index them.
+__global__ __launch_bounds__(RENDER_THREADS) void k_surface_filter(const float* __restrict__ src, float* __restrict__ dst, uint32_t w,
+                                                                   uint32_t h, SurfaceArgs F) {
+#pragma clang fp contract(off)
+    __shared__ float tile[SF_TILE_MAX];
+    __shared__ float wS[SF_MAX_R + 1];
+    const uint32_t r = F.r, tw = SF_TX + 2 * r, th = SF_TY + 2 * r;
+    const uint32_t tid = threadIdx.y * SF_TX + threadIdx.x;
+#pragma unroll
+    for (uint32_t k = 0; k <= SF_MAX_R; k++)
+        if (tid == k) wS[k] = F.S[k];
+    const int x0 = (int)(blockIdx.x * SF_TX) - (int)r, y0 = (int)(blockIdx.y * SF_TY) - (int)r;
+    for (uint32_t t = tid; t < tw * th; t += RENDER_THREADS) {          // tw * th <= SF_TILE_MAX because r <= SF_MAX_R
+        const uint32_t ly = t / tw, lx = t - ly * tw;
+        const int gx = x0 + (int)lx, gy = y0 + (int)ly;
+        const bool in = gx >= 0 && gx < (int)w && gy >= 0 && gy < (int)h;
+        tile[t] = in ? src[(size_t)gy * w + (uint32_t)gx] : SF_INF;
+    }
+    __syncthreads();
+    const uint32_t i = blockIdx.x * SF_TX + threadIdx.x, j = blockIdx.y * SF_TY + threadIdx.y;
+    if (i >= w || j >= h) return;
+    const float zc = tile[(threadIdx.y + r) * tw + threadIdx.x + r];
+    float out = zc;                                                      // a background pixel stays background
+    if (sf_finite(zc)) {
+        float num = 0.0f, den = 0.0f;
+        for (uint32_t dj = 0; dj <= 2 * r; dj++) {
+            const float sj = wS[dj < r ? r - dj : dj - r];
+            const float* row = tile + (threadIdx.y + dj) * tw + threadIdx.x;
+            for (uint32_t di = 0; di <= 2 * r; di++) {
+                const float zn = row[di];
+                if (!sf_finite(zn)) continue;
+                const float e = (zn - zc) / F.tau;
+                const float q = 1.0f - e * e;
+                if (q > 0.0f) {
+                    const float wt = (wS[di < r ? r - di : di - r] * sj) * (q * q);
+                    num = num + wt * zn;
+                    den = den + wt;
+                }
+            }
+        }
+        out = num / den;
+    }
+    dst[(size_t)j * w + i] = out;
+}
+
+// P(i, j) of the header
+__device__ __forceinline__ void eye_point(const RenderArgs& A, uint32_t i, uint32_t j, float z, float P[3]) {
+#pragma clang fp contract(off)
+    P[0] = ((((float)i + 0.5f) - A.half_w) * z) / A.focal;
+    P[1] = ((A.half_h - ((float)j + 0.5f)) * z) / A.focal;
+    P[2] = z;
+}
+
+// ddx / ddy of the header: Pf the forward neighbour's point (has_f: it is inside the image and surface), Pb the backward one's
+__device__ __forceinline__ void slope(const float P[3], bool has_f, const float Pf[3], bool has_b, const float Pb[3], float d[3]) {
+#pragma clang fp contract(off)
+    float f[3], b[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) { f[k] = Pf[k] - P[k]; b[k] = P[k] - Pb[k]; }
+    const bool use_f = has_f && (!has_b || fabsf(f[2]) <= fabsf(b[2]));
+#pragma unroll
+    for (int k = 0; k < 3; k++) d[k] = use_f ? f[k] : b[k];          // (neither: the caller's default)
+}
+
+__device__ __forceinline__ float dot3(const float a[3], const float b[3]) {
+#pragma clang fp contract(off)
+    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2];
+}
+
+__global__ __launch_bounds__(RENDER_THREADS) void k_surface_shade(const uint64_t* __restrict__ keys, const float* __restrict__ Z,
+                                                                  const uint32_t* __restrict__ thick, const float4* __restrict__ posi,
+                                                                  const float4* __restrict__ velr, const float2* __restrict__ dp,
+                                                                  uint32_t n, RenderArgs A, SurfaceArgs F, uint32_t* __restrict__ rgba,
+                                                                  uint32_t* __restrict__ id, float* __restrict__ normal) {
+#pragma clang fp contract(off)
+    const uint32_t pix = blockIdx.x * RENDER_THREADS + threadIdx.x;
+    if (pix >= A.width * A.height) return;
+    const uint64_t key = keys[pix];
+    const uint32_t slot = (uint32_t)key;
+    if (key == RENDER_EMPTY || slot >= n) {      // (slot >= n cannot happen: the splat only writes slots below n)
+        rgba[pix] = A.background;
+        id[pix] = 0xFFFFFFFFu;
+        normal[3 * (size_t)pix] = 0.0f; normal[3 * (size_t)pix + 1] = 0.0f; normal[3 * (size_t)pix + 2] = 0.0f;
+        return;
+    }
+    const uint32_t i = pix % A.width, j = pix / A.width;
+    const float z = Z[pix];
+    float P[3], Pf[3] = {0.0f, 0.0f, 0.0f}, Pb[3] = {0.0f, 0.0f, 0.0f}, ddx[3], ddy[3];
+    eye_point(A, i, j, z, P);
+    {   // ddx: forward is column i + 1
+        const float zf = i + 1 < A.width ? Z[pix + 1] : SF_INF, zb = i > 0 ? Z[pix - 1] : SF_INF;
+        const bool hf = sf_finite(zf), hb = sf_finite(zb);
+        if (hf) eye_point(A, i + 1, j, zf, Pf);
+        if (hb) eye_point(A, i - 1, j, zb, Pb);
+        slope(P, hf, Pf, hb, Pb, ddx);
+        if (!hf && !hb) { ddx[0] = z / A.focal; ddx[1] = 0.0f; ddx[2] = 0.0f; }
+    }
+    {   // ddy: forward is row j - 1 (+y in eye space)
+        const float zf = j > 0 ? Z[pix - A.width] : SF_INF, zb = j + 1 < A.height ? Z[pix + A.width] : SF_INF;
+        const bool hf = sf_finite(zf), hb = sf_finite(zb);
+        if (hf) eye_point(A, i, j - 1, zf, Pf);
+        if (hb) eye_point(A, i, j + 1, zb, Pb);
+        slope(P, hf, Pf, hb, Pb, ddy);
+        if (!hf && !hb) { ddy[0] = 0.0f; ddy[1] = z / A.focal; ddy[2] = 0.0f; }
+    }
+    float nv[3];
+    nv[0] = ddy[1] * ddx[2] - ddy[2] * ddx[1];
+    nv[1] = ddy[2] * ddx[0] - ddy[0] * ddx[2];
+    nv[2] = ddy[0] * ddx[1] - ddy[1] * ddx[0];
+    const float len2 = dot3(nv, nv);
+    if (len2 > 0.0f && sf_finite(len2)) {
+        const float len = sqrtf(len2);
+#pragma unroll
+        for (int k = 0; k < 3; k++) nv[k] = nv[k] / len;
+    } else {
+        nv[0] = 0.0f; nv[1] = 0.0f; nv[2] = -1.0f;
+    }
+    const float pl = sqrtf(dot3(P, P));
+    float V[3], H[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) V[k] = (-P[k]) / pl;
+    const float ndl = fmaxf(0.0f, dot3(nv, F.L));
+#pragma unroll
+    for (int k = 0; k < 3; k++) H[k] = F.L[k] + V[k];
+    const float hl = sqrtf(dot3(H, H));
+#pragma unroll
+    for (int k = 0; k < 3; k++) H[k] = hl > 0.0f ? H[k] / hl : nv[k];
+    float spec = fmaxf(0.0f, dot3(nv, H));
+#pragma unroll
+    for (int k = 0; k < 5; k++) spec = spec * spec;
+    const float ndv = fminf(fmaxf(dot3(nv, V), 0.0f), 1.0f);
+    const float m = 1.0f - ndv;
+    const float fres = 0.02f + 0.98f * (((m * m) * (m * m)) * m);
+    const float lit = 0.25f + 0.75f * ndl;
+    const float4 p = posi[slot];
+    const uint32_t index = __float_as_uint(p.w);
+    float c[3] = {1.0f, 1.0f, 1.0f};
+    if (!F.flat) ramp(ramp_t(A, slot, index, velr, dp), c);
+    const float T = F.thick ? (float)thick[pix] * F.thick_unit : 0.0f;
+    uint32_t out = 0xFF000000u;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const float base = F.flat ? F.tint[k] : F.tint[k] * c[k];
+        const float tr = F.thick ? 1.0f / (1.0f + F.absorb[k] * T) : 0.0f;
+        const float body = (base * lit) * (1.0f - tr) + F.bg[k] * tr;
+        const float o = (body * (1.0f - fres) + fres) + F.specular * spec;
+        out |= (uint32_t)(fminf(fmaxf(o, 0.0f), 1.0f) * 255.0f + 0.5f) << (8 * k);
+    }
+    rgba[pix] = out;
+    id[pix] = index;
+#pragma unroll
+    for (int k = 0; k < 3; k++) normal[3 * (size_t)pix + k] = nv[k];
+}
+
 static void free_image(sph_ctx* c) {
     hipFree(c->rd_keys); hipFree(c->rd_rgba); hipFree(c->rd_id); hipFree(c->rd_depth);
     c->rd_keys = nullptr; c->rd_rgba = nullptr; c->rd_id = nullptr; c->rd_depth = nullptr;
+    hipFree(c->rd_sf_raw); hipFree(c->rd_sf_pong); hipFree(c->rd_sf_thick); hipFree(c->rd_sf_normal);
+    c->rd_sf_raw = nullptr; c->rd_sf_pong = nullptr; c->rd_sf_thick = nullptr; c->rd_sf_normal = nullptr;
     c->rd_alloc_w = c->rd_alloc_h = 0;
 }
 
@@ -251,15 +501,16 @@ int sph_camera_look_at(sph_camera* out, uint32_t width, uint32_t height, const f
     return SPH_OK;
 }
 
-int sph_render(sph_ctx* c, const sph_camera* cam, const sph_render_style* style) {
+// What sph_render and sph_render_surface check alike; `who` names the entry point in the messages.
+static int check_render(sph_ctx* c, const sph_camera* cam, const sph_render_style* style, const char* who) {
     SPH_REQUIRE(c && cam && style, SPH_E_INVALID, "null argument");
-    SPH_REQUIRE(!c->slab, SPH_E_STATE, "sph_render is not supported on a slab context (the ranks would have to composite "
-                "their images)");
+    SPH_REQUIRE(!c->slab, SPH_E_STATE, "%s is not supported on a slab context (the ranks would have to composite "
+                "their images)", who);
     SPH_REQUIRE(cam->width >= 1u && cam->width <= (uint32_t)SPH_RENDER_MAX_SIZE && cam->height >= 1u &&
                 cam->height <= (uint32_t)SPH_RENDER_MAX_SIZE, SPH_E_INVALID, "image %u x %u: 1..%d each", cam->width, cam->height,
                 SPH_RENDER_MAX_SIZE);
     SPH_REQUIRE(finite3(cam->rot, 9) && finite3(cam->trans, 3) && std::isfinite(cam->focal_px) && std::isfinite(cam->near_z) &&
-                std::isfinite(cam->far_z), SPH_E_INVALID, "sph_render: a camera field is not finite");
+                std::isfinite(cam->far_z), SPH_E_INVALID, "%s: a camera field is not finite", who);
     SPH_REQUIRE(cam->focal_px > 0.f, SPH_E_INVALID, "focal_px %g: must be positive", (double)cam->focal_px);
     SPH_REQUIRE(cam->near_z > 0.f && cam->far_z > cam->near_z, SPH_E_INVALID, "0 < near_z < far_z");
     SPH_REQUIRE(style->color_mode == SPH_COLOR_INDEX || style->color_mode == SPH_COLOR_SPEED || style->color_mode == SPH_COLOR_DENSITY,
@@ -270,41 +521,57 @@ int sph_render(sph_ctx* c, const sph_camera* cam, const sph_render_style* style)
                     (double)style->lo, (double)style->hi);
     SPH_REQUIRE(std::isfinite(style->radius) && style->radius >= 0.f, SPH_E_INVALID, "sprite radius %g: finite and >= 0 (0: the particle radius)",
                 (double)style->radius);
-    SPH_HIP(hipSetDevice(c->device));
-    const uint32_t w = cam->width, h = cam->height, npix = w * h;
-    if (w != c->rd_alloc_w || h != c->rd_alloc_h) {      // first call, or another image size
-        SPH_HIP(hipStreamSynchronize(c->stream));        // (a consumer of the old image on this stream has finished)
+    return SPH_OK;
+}
+
+// The image buffers for w x h: kept when they have that size, else (first call, or another image size) allocated anew.
+static int ensure_image(sph_ctx* c, uint32_t w, uint32_t h, const char* who) {
+    if (w == c->rd_alloc_w && h == c->rd_alloc_h) return SPH_OK;
+    const uint32_t npix = w * h;
+    SPH_HIP(hipStreamSynchronize(c->stream));        // (a consumer of the old image on this stream has finished)
+    free_image(c);
+    c->rd_valid = false;
+    hipError_t e = hipMalloc((void**)&c->rd_keys, (size_t)npix * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&c->rd_rgba, (size_t)npix * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&c->rd_id, (size_t)npix * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&c->rd_depth, (size_t)npix * 4);
+    if (e != hipSuccess) {
         free_image(c);
-        c->rd_valid = false;
-        hipError_t e = hipMalloc((void**)&c->rd_keys, (size_t)npix * 8);
-        if (e == hipSuccess) e = hipMalloc((void**)&c->rd_rgba, (size_t)npix * 4);
-        if (e == hipSuccess) e = hipMalloc((void**)&c->rd_id, (size_t)npix * 4);
-        if (e == hipSuccess) e = hipMalloc((void**)&c->rd_depth, (size_t)npix * 4);
-        if (e != hipSuccess) {
-            free_image(c);
-            set_error("sph_render: hipMalloc of a %u x %u image failed: %s", w, h, hipGetErrorString(e));
-            return SPH_E_NOMEM;
-        }
-        c->rd_alloc_w = w;
-        c->rd_alloc_h = h;
+        set_error("%s: hipMalloc of a %u x %u image failed: %s", who, w, h, hipGetErrorString(e));
+        return SPH_E_NOMEM;
     }
+    c->rd_alloc_w = w;
+    c->rd_alloc_h = h;
+    return SPH_OK;
+}
+
+static RenderArgs render_args(const sph_ctx* c, const sph_camera* cam, const sph_render_style* style) {
     RenderArgs A;
     memset(&A, 0, sizeof(A));
-    A.width = w;
-    A.height = h;
+    A.width = cam->width;
+    A.height = cam->height;
     for (int k = 0; k < 9; k++) A.rot[k] = cam->rot[k];
     for (int k = 0; k < 3; k++) A.trans[k] = cam->trans[k];
     A.focal = cam->focal_px;
     A.near_z = cam->near_z;
     A.far_z = cam->far_z;
     A.radius = style->radius > 0.f ? style->radius : c->params.particle_radius;
-    A.half_w = 0.5f * (float)w;
-    A.half_h = 0.5f * (float)h;
+    A.half_w = 0.5f * (float)cam->width;
+    A.half_h = 0.5f * (float)cam->height;
     A.mode = style->color_mode;
     A.lo = style->lo;
     A.span = style->hi - style->lo;
     A.index_count = (float)(style->index_count ? style->index_count : c->n);
     memcpy(&A.background, style->background, 4);
+    return A;
+}
+
+int sph_render(sph_ctx* c, const sph_camera* cam, const sph_render_style* style) {
+    if (int e = check_render(c, cam, style, "sph_render")) return e;
+    SPH_HIP(hipSetDevice(c->device));
+    const uint32_t w = cam->width, h = cam->height, npix = w * h;
+    if (int e = ensure_image(c, w, h, "sph_render")) return e;
+    const RenderArgs A = render_args(c, cam, style);
     const uint32_t pix_blocks = ceil_div(npix, RENDER_THREADS);
     hipLaunchKernelGGL(k_render_clear, dim3(pix_blocks), dim3(RENDER_THREADS), 0, c->stream, c->rd_keys, npix);
     if (c->n) {
@@ -326,6 +593,124 @@ int sph_render(sph_ctx* c, const sph_camera* cam, const sph_render_style* style)
     c->rd_w = w;
     c->rd_h = h;
     c->rd_valid = true;
+    c->rd_surface = false;
+    return SPH_OK;
+}
+
+void sph_surface_defaults(sph_surface_style* s) {
+    if (!s) return;
+    memset(s, 0, sizeof *s);
+    s->smooth_radius_px = 5;
+    s->smooth_iterations = 2;
+    s->depth_falloff = 0.0f;
+    s->flat_color = 1;
+    s->tint[0] = 0.25f; s->tint[1] = 0.55f; s->tint[2] = 0.95f;
+    s->absorb[0] = 6.0f; s->absorb[1] = 2.0f; s->absorb[2] = 0.5f;
+    s->light[0] = 1.0f; s->light[1] = 1.0f; s->light[2] = -1.0f;
+    s->specular = 0.6f;
+}
+
+int sph_render_surface(sph_ctx* c, const sph_camera* cam, const sph_render_style* style, const sph_surface_style* sf) {
+    if (int e = check_render(c, cam, style, "sph_render_surface")) return e;
+    SPH_REQUIRE(sf, SPH_E_INVALID, "null argument");
+    SPH_REQUIRE(sf->smooth_radius_px <= (uint32_t)SPH_SURFACE_MAX_RADIUS_PX, SPH_E_INVALID, "smooth_radius_px %u: 0..%d",
+                sf->smooth_radius_px, SPH_SURFACE_MAX_RADIUS_PX);
+    SPH_REQUIRE(sf->smooth_iterations <= (uint32_t)SPH_SURFACE_MAX_ITERATIONS, SPH_E_INVALID, "smooth_iterations %u: 0..%d",
+                sf->smooth_iterations, SPH_SURFACE_MAX_ITERATIONS);
+    SPH_REQUIRE(std::isfinite(sf->depth_falloff) && sf->depth_falloff >= 0.f, SPH_E_INVALID, "depth_falloff %g: finite and >= 0 "
+                "(0: four sprite radii)", (double)sf->depth_falloff);
+    for (int k = 0; k < 3; k++)
+        SPH_REQUIRE(std::isfinite(sf->tint[k]) && sf->tint[k] >= 0.f && std::isfinite(sf->absorb[k]) && sf->absorb[k] >= 0.f,
+                    SPH_E_INVALID, "tint / absorb channel %d: finite and >= 0", k);
+    SPH_REQUIRE(std::isfinite(sf->specular) && sf->specular >= 0.f, SPH_E_INVALID, "specular %g: finite and >= 0", (double)sf->specular);
+    const double ll = std::sqrt((double)sf->light[0] * sf->light[0] + (double)sf->light[1] * sf->light[1] +
+                                (double)sf->light[2] * sf->light[2]);
+    SPH_REQUIRE(finite3(sf->light, 3) && ll > 0.0, SPH_E_INVALID, "light: a finite vector that is not zero");
+    SPH_REQUIRE(c->n < (1u << 28), SPH_E_CAPACITY, "sph_render_surface: %u particles: the thickness word holds fewer than 2^28", c->n);
+    SPH_HIP(hipSetDevice(c->device));
+    const uint32_t w = cam->width, h = cam->height, npix = w * h;
+    if (int e = ensure_image(c, w, h, "sph_render_surface")) return e;
+    if (!c->rd_sf_raw) {                                  // the first surface render of an image of this size
+        hipError_t e = hipMalloc((void**)&c->rd_sf_raw, (size_t)npix * 4);
+        if (e == hipSuccess) e = hipMalloc((void**)&c->rd_sf_pong, (size_t)npix * 4);
+        if (e == hipSuccess) e = hipMalloc((void**)&c->rd_sf_thick, (size_t)npix * 4);
+        if (e == hipSuccess) e = hipMalloc((void**)&c->rd_sf_normal, (size_t)npix * 12);
+        if (e != hipSuccess) {
+            SPH_HIP(hipStreamSynchronize(c->stream));
+            free_image(c);
+            c->rd_valid = false;
+            set_error("sph_render_surface: hipMalloc of the planes of a %u x %u image failed: %s", w, h, hipGetErrorString(e));
+            return SPH_E_NOMEM;
+        }
+    }
+    const RenderArgs A = render_args(c, cam, style);
+    SurfaceArgs F;
+    memset(&F, 0, sizeof(F));
+    const uint32_t K = sf->smooth_radius_px ? sf->smooth_iterations : 0;
+    F.r = K ? sf->smooth_radius_px : 0;
+    F.tau = sf->depth_falloff > 0.f ? sf->depth_falloff : 4.0f * A.radius;
+    for (uint32_t k = 0; k <= F.r; k++) {
+        const double sigma = 0.5 * (double)F.r;
+        F.S[k] = (float)std::exp(-((double)k * (double)k) / (2.0 * sigma * sigma));
+    }
+    F.flat = sf->flat_color ? 1 : 0;
+    F.thick = (sf->absorb[0] > 0.f || sf->absorb[1] > 0.f || sf->absorb[2] > 0.f) ? 1 : 0;
+    for (int k = 0; k < 3; k++) {
+        F.tint[k] = sf->tint[k];
+        F.absorb[k] = sf->absorb[k];
+        F.L[k] = (float)((double)sf->light[k] / ll);
+        F.bg[k] = (float)style->background[k] / 255.0f;
+    }
+    F.specular = sf->specular;
+    F.thick_unit = A.radius * 0.125f;
+    const uint32_t pix_blocks = ceil_div(npix, RENDER_THREADS), part_blocks = ceil_div(c->n, RENDER_THREADS);
+    hipLaunchKernelGGL(k_render_clear, dim3(pix_blocks), dim3(RENDER_THREADS), 0, c->stream, c->rd_keys, npix);
+    if (F.thick) SPH_HIP(hipMemsetAsync(c->rd_sf_thick, 0, (size_t)npix * 4, c->stream));
+    if (c->n) {
+        const float4* posi = c->posi + c->own_off;
+#ifdef SPH_SURFACE_SPLIT_WALK      // measuring builds only: the thickness in a walk of its own (profiles/scripts/surface_time.py)
+        hipLaunchKernelGGL((k_surface_splat<true, false>), dim3(part_blocks), dim3(RENDER_THREADS), 0, c->stream, posi, c->n, A, c->rd_keys, c->rd_sf_thick);
+        if (F.thick)
+            hipLaunchKernelGGL((k_surface_splat<false, true>), dim3(part_blocks), dim3(RENDER_THREADS), 0, c->stream, posi, c->n, A, c->rd_keys, c->rd_sf_thick);
+#else
+        if (F.thick)
+            hipLaunchKernelGGL((k_surface_splat<true, true>), dim3(part_blocks), dim3(RENDER_THREADS), 0, c->stream, posi, c->n, A, c->rd_keys, c->rd_sf_thick);
+        else
+            hipLaunchKernelGGL((k_surface_splat<true, false>), dim3(part_blocks), dim3(RENDER_THREADS), 0, c->stream, posi, c->n, A, c->rd_keys, c->rd_sf_thick);
+#endif
+    }
+    hipLaunchKernelGGL(k_surface_depth, dim3(pix_blocks), dim3(RENDER_THREADS), 0, c->stream, c->rd_keys, npix, c->rd_sf_raw,
+                       K ? (float*)nullptr : c->rd_depth);
+    // Z_0 = rd_sf_raw stays; the iterations alternate between rd_depth and rd_sf_pong so that the last one writes rd_depth
+    const float* src = c->rd_sf_raw;
+    for (uint32_t it = 1; it <= K; it++) {
+        float* dst = (K - it) % 2 == 0 ? c->rd_depth : c->rd_sf_pong;
+        hipLaunchKernelGGL(k_surface_filter, dim3(ceil_div(w, SF_TX), ceil_div(h, SF_TY)), dim3(SF_TX, SF_TY), 0, c->stream, src, dst, w, h, F);
+        src = dst;
+    }
+    hipLaunchKernelGGL(k_surface_shade, dim3(pix_blocks), dim3(RENDER_THREADS), 0, c->stream, c->rd_keys, c->rd_depth, c->rd_sf_thick,
+                       c->posi + c->own_off, c->velr + c->own_off, c->dp + c->own_off, c->n, A, F, c->rd_rgba, c->rd_id, c->rd_sf_normal);
+    SPH_HIP(hipGetLastError());
+    c->rd_w = w;
+    c->rd_h = h;
+    c->rd_valid = true;
+    c->rd_surface = true;
+    c->rd_sf_thick_on = F.thick != 0;
+    return SPH_OK;
+}
+
+int sph_render_surface_read(sph_ctx* c, float* raw_depth, uint32_t* thickness_q, float* normal_xyz) {
+    SPH_REQUIRE(c, SPH_E_INVALID, "null context");
+    SPH_REQUIRE(c->rd_valid && c->rd_surface, SPH_E_STATE, "sph_render_surface_read: the last render was not a surface render");
+    SPH_HIP(hipSetDevice(c->device));
+    const size_t npix = (size_t)c->rd_w * c->rd_h;
+    if (raw_depth) SPH_HIP(hipMemcpyAsync(raw_depth, c->rd_sf_raw, npix * 4, hipMemcpyDeviceToHost, c->stream));
+    if (thickness_q) {
+        if (c->rd_sf_thick_on) SPH_HIP(hipMemcpyAsync(thickness_q, c->rd_sf_thick, npix * 4, hipMemcpyDeviceToHost, c->stream));
+        else memset(thickness_q, 0, npix * 4);
+    }
+    if (normal_xyz) SPH_HIP(hipMemcpyAsync(normal_xyz, c->rd_sf_normal, npix * 12, hipMemcpyDeviceToHost, c->stream));
+    SPH_HIP(hipStreamSynchronize(c->stream));
     return SPH_OK;
 }
 

@@ -8,7 +8,8 @@
 //     with getArray(POSITION) or through getPositionsDevice() (the `gl_pos` analogue).  The
 //     reference constructor needs a GL context even in -benchmark mode.
 //     Pictures come from the device renderer instead (setCamera / renderFrame / writeFrame, on top of
-//     sph_render): the reference's sphere sprites and colour ramp, written as PPM files.
+//     sph_render): the reference's sphere sprites and colour ramp, written as PPM files; or, with setRenderSurface, the
+//     fluid as a smoothed surface (sph_render_surface).
 //   * only the GPU mode exists: SEQUENTIAL / OMP_PARALLEL abort with a message (no CPU fallback).
 //   * the grid follows the box: nextPow2((uint)(boxDims/(0.66666f*h))) per axis; the reference
 //     always uses the BOX_SIZE macro, i.e. 32^3 whatever the box (particleSystem.cpp:46, A.2-3).
@@ -136,6 +137,9 @@ public:
     void setCamera(uint width, uint height, const float* eye, const float* target, float fovyDeg = 60.0f);
     // SPH_COLOR_INDEX (the reference's colouring; the default), or SPH_COLOR_SPEED / SPH_COLOR_DENSITY mapped from [lo, hi]
     void setRenderColor(int mode, float lo = 0.0f, float hi = 1.0f);
+    // on: renderFrame draws the fluid as a surface (sph_render_surface: smoothed depth, normals, thickness, a water-like
+    // shading) in the style *s (nullptr: sph_surface_defaults); off (the default): the sphere sprites of sph_render.
+    void setRenderSurface(bool on, const sph_surface_style* s = nullptr);
     // Queue one render of the particles as they are (asynchronous, no copy of the state); getFrameDevice: its RGBA8 image on
     // the device.  writeFrame: the last rendered image as a binary PPM (P6, RGB, no alpha), rows top to bottom.
     void renderFrame();
@@ -197,6 +201,8 @@ protected:
     bool m_hostStale;
     sph_camera m_camera;
     sph_render_style m_renderStyle;
+    bool m_surfaceOn;
+    sph_surface_style m_surfaceStyle;
     std::vector<unsigned char> m_frame;              // RGBA staging of writeFrame
     std::string m_logPath;
     void* m_log;

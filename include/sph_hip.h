@@ -30,7 +30,8 @@
  *                  sph_get_precision | sph_upload sph_set_by_index sph_reset_lattice sph_download sph_download_owned
  *                  sph_positions_dev sph_download_positions4 sph_snapshot_save sph_snapshot_load sph_snapshot_info |
  *                  sph_set_colliders sph_get_colliders sph_set_collider_bodies sph_get_collider_impulses | sph_emit sph_remove sph_count_in_regions |
- *                  sph_camera_look_at sph_render sph_render_read sph_render_image_dev |
+ *                  sph_camera_look_at sph_render sph_render_read sph_render_image_dev sph_surface_defaults sph_render_surface
+ *                  sph_render_surface_read |
  *                  sph_hash sph_sort sph_build_cells sph_density sph_force sph_collide sph_integrate sph_step sph_step_phased
  *                  sph_force_collide_integrate | sph_timing_enable sph_timing_get sph_timing_reset | the z-slab phase calls
  *                  (sph_migrants_* sph_slab_counts sph_halo_* sph_layer_histogram) | sph_rccl_unique_id
@@ -417,6 +418,80 @@ int sph_render_read(sph_ctx* c, uint8_t* rgba, uint32_t* id, float* depth);
 /* The device pointer of the RGBA8 image of the last render, and its size, for a consumer on the same stream: what
  * sph_positions_dev is one stage earlier.  Valid until the next render of another size.  SPH_E_STATE if nothing was rendered. */
 int sph_render_image_dev(sph_ctx* c, void** rgba_dev, uint32_t* width, uint32_t* height);
+
+/* ---- pictures: the fluid as a SURFACE, in screen space -- sphere depth, thickness, smoothed depth, normals, a water-like shading ------
+ * Same camera, same key image, same read-back as sph_render; the image-space half is new.  Nothing transcendental runs on the
+ * device, no floating-point atomic, every sum in a fixed order.
+ *
+ * THE RULE (fp32, every operation rounded, no multiply-add fusion, sums left to right, IEEE division and square root;
+ * tests/surface_model.py is the same arithmetic in numpy and gives every plane bit for bit).
+ * FRAGMENTS.  pe, d, rp, cx, cy, u, v, mag and the coverage test mag <= 1 are sph_render's, above.  With R the style's radius
+ * (0: params.particle_radius) a particle is drawn iff  d - R >= near_z && d <= far_z.  The fragment's depth is the sphere's:
+ *     nz = sqrtf(1 - mag) ;  dz = d - R*nz            (so dz >= near_z > 0, and its bits order as the float does)
+ * The key is (bits(dz) << 32) | slot: the smallest dz wins the pixel, among equal dz the lowest slot.  RAW DEPTH Z_0 is the
+ * winner's dz, +inf on background.
+ * THICKNESS (only if some absorb[k] > 0).  Every covered fragment, occluded or not, adds
+ *     q = (uint32_t)(nz*16.0f + 0.5f)                 (0..16)
+ * to the pixel's 32-bit word with an integer atomic add: the sum does not depend on the order of arrival.  At most 16 per
+ * particle, hence sph_num_particles < 2^28.  World thickness  T = (float)count * (R*0.125f).
+ * SMOOTHING.  r = smooth_radius_px, K = smooth_iterations, tau = depth_falloff (0: 4.0f*R).  Weights, computed on the host in
+ * double and rounded once:  S[k] = (float)exp(-(k*k) / (2*sigma*sigma)), sigma = r/2, k = 0..r.  K == 0 or r == 0: Z_K = Z_0.
+ * Else for it = 1..K, for every pixel (i, j): a background pixel stays +inf; otherwise zc = Z_{it-1}(i, j), num = den = 0, and
+ * for dj = -r..r ascending, inside it di = -r..r ascending, where (i+di, j+dj) is inside the image and
+ * zn = Z_{it-1}(i+di, j+dj) is finite:
+ *     e = (zn - zc) / tau ;  q = 1.0f - e*e ;  if (q > 0) { w = (S[|di|]*S[|dj|]) * (q*q) ;  num = num + w*zn ;  den = den + w }
+ * and Z_it(i, j) = num / den  (the centre tap gives den >= S[0]^2 = 1).  A neighbour further than tau in depth weighs exactly 0:
+ * edges between sheets of fluid survive, the silhouette never grows.
+ * NORMALS from Z = Z_K.  The eye-space point of a surface pixel, z = Z(i, j):
+ *     P(i, j) = ( (((i + 0.5f) - 0.5f*width) * z) / focal_px ,  ((0.5f*height - (j + 0.5f)) * z) / focal_px ,  z )
+ * ddx: fwd = P(i+1, j) - P(i, j), bwd = P(i, j) - P(i-1, j), each available only where that neighbour is inside the image and is
+ * surface (finite Z).  Both: fwd if |fwd.z| <= |bwd.z|, else bwd.  One: that one.  None: (z/focal_px, 0, 0).
+ * ddy: the same with fwd = P(i, j-1) - P(i, j) (row j-1 is +y), bwd = P(i, j) - P(i, j+1); none: (0, z/focal_px, 0).
+ *     n = cross(ddy, ddx):  nx = ddy.y*ddx.z - ddy.z*ddx.y ;  ny = ddy.z*ddx.x - ddy.x*ddx.z ;  nz = ddy.x*ddx.y - ddy.y*ddx.x
+ *     len2 = (nx*nx + ny*ny) + nz*nz ;  n = n / sqrtf(len2) per component ;  n = (0, 0, -1) unless len2 is finite and > 0
+ * (a wall seen head-on has n = (0, 0, -1): it faces the eye).  Background: n = (0, 0, 0).
+ * SHADING.  With P = P(i, j), L the style's light normalised on the host in double and rounded once:
+ *     pl = sqrtf((P.x*P.x + P.y*P.y) + P.z*P.z) ;  V = (-P) / pl per component
+ *     ndl = max(0, (n.x*L.x + n.y*L.y) + n.z*L.z)                               (every dot product in this order)
+ *     H = L + V ;  hl = sqrtf((H.x*H.x + H.y*H.y) + H.z*H.z) ;  H = H / hl if hl > 0, else H = n
+ *     spec = max(0, n.H), then five times spec = spec*spec                      (the 32nd power)
+ *     ndv = min(max(n.V, 0), 1) ;  m = 1.0f - ndv ;  F = 0.02f + 0.98f * (((m*m)*(m*m))*m)
+ *     base_k = flat_color ? tint_k : tint_k * c_k         (c: sph_render's ramp colour of the front particle, style.color_mode)
+ *     tr_k = 1.0f / (1.0f + absorb_k*T) if the thickness pass ran, else 0       (a rational stand-in for Beer-Lambert: no exp)
+ *     bg_k = (float)background[k] / 255.0f
+ *     body_k = (base_k * (0.25f + 0.75f*ndl)) * (1.0f - tr_k) + bg_k*tr_k
+ *     out_k = (body_k * (1.0f - F) + F) + specular*spec
+ *     channel8 = (uint8)(min(max(out_k, 0), 1)*255.0f + 0.5f) ;  alpha = 255
+ * id is the creation index of the front particle.  A background pixel holds the style's background colour, id 0xFFFFFFFF,
+ * depth +inf, as after sph_render. */
+#define SPH_SURFACE_MAX_RADIUS_PX 16
+#define SPH_SURFACE_MAX_ITERATIONS 8
+typedef struct sph_surface_style {
+    uint32_t smooth_radius_px;   /* r: 0..SPH_SURFACE_MAX_RADIUS_PX; 0 = no smoothing */
+    uint32_t smooth_iterations;  /* K: 0..SPH_SURFACE_MAX_ITERATIONS; 0 = no smoothing */
+    float    depth_falloff;      /* tau, world units; 0 = 4 * the resolved sprite radius */
+    int32_t  flat_color;         /* 1: base colour = tint; 0: tint * the ramp colour of the front particle (style.color_mode) */
+    float    tint[3];
+    float    absorb[3];          /* >= 0 per channel, per world unit of thickness; all 0 = no thickness pass at all */
+    float    light[3];           /* eye space (+x right, +y up, +z forward); any non-zero finite vector */
+    float    specular;           /* >= 0, strength of the highlight */
+} sph_surface_style;
+/* r 5, K 2, tau 0, flat 1, tint (0.25, 0.55, 0.95), absorb (6, 2, 0.5), light (1, 1, -1), specular 0.6 */
+void sph_surface_defaults(sph_surface_style* s);
+/* Render the owned particles as a surface.  Validates as sph_render does, is legal wherever sph_render is, writes none of the
+ * step's flags and no particle array; its kernels are queued on the context's stream with no host wait (but for the call that
+ * (re)allocates the image, as in sph_render).  The results land where sph_render's do: sph_render_read and
+ * sph_render_image_dev give the RGBA8 image, id, and as depth the SMOOTHED depth Z_K.  The extra device buffers (4 + 4 + 4 + 12
+ * bytes per pixel) are allocated at the first surface render only, and freed with the image.
+ *   SPH_E_INVALID   what sph_render refuses; r or K out of range; depth_falloff negative or not finite; a tint, absorb or
+ *                   specular that is negative or not finite; a light that is zero or not finite: the previous image stays;
+ *   SPH_E_CAPACITY  sph_num_particles >= 2^28 (the thickness word);
+ *   SPH_E_STATE     a slab context. */
+int sph_render_surface(sph_ctx* c, const sph_camera* camera, const sph_render_style* style, const sph_surface_style* surface);
+/* The extra planes of the last surface render to the host: raw_depth width*height floats (Z_0), thickness_q the counts (all 0
+ * when the thickness pass was off), normal_xyz 3 floats per pixel.  Any pointer may be NULL.  Synchronises.  SPH_E_STATE unless
+ * the last render was a surface render. */
+int sph_render_surface_read(sph_ctx* c, float* raw_depth, uint32_t* thickness_q, float* normal_xyz);
 
 /* State snapshot (checkpoint / resume; absent in the reference, whose device state is never
  * serialised -- SURVEY.md section 5).  The file holds the parameters and, IN SLOT ORDER, position,
