@@ -128,7 +128,7 @@ static int dev_alloc_zero(T** p, size_t count) {
 // every array create_impl allocates (keep the two lists in step)
 static void free_all(sph_ctx* c) {
     hipFree(c->posi); hipFree(c->velr); hipFree(c->posi2); hipFree(c->velr2); hipFree(c->keyS); hipFree(c->dp); hipFree(c->cw);
-    hipFree(c->fpress); hipFree(c->fvisc); hipFree(c->dvel); hipFree(c->pos_out); hipFree(c->cells_base);
+    hipFree(c->fpress); hipFree(c->fvisc); hipFree(c->dvel); hipFree(c->pos_out); hipFree(c->table.base);
     hipFree(c->k0); hipFree(c->v0); hipFree(c->k1); hipFree(c->v1); hipFree(c->os_hist); hipFree(c->os_base); hipFree(c->os_tickets); hipFree(c->os_tot); hipFree(c->os_status); hipFree(c->os_status32); hipFree(c->keyS2); hipFree(c->mm_tileL); hipFree(c->mm_tileA);
     if (c->os_err_host) hipHostFree(c->os_err_host);
     hipFree(c->d_scratch);
@@ -187,8 +187,8 @@ static int create_impl(sph_ctx** out, int device, uint32_t capacity, const sph_p
     if (!rc) rc = dev_alloc(&c->dvel, tot);
     if (!rc) rc = dev_alloc(&c->pos_out, (size_t)c->pos_out_cap);
     // one guard entry on either side: the pair kernels read cells[key - 1 .. key + 1] of a row unconditionally
-    if (!rc) rc = dev_alloc_zero(&c->cells_base, (size_t)c->grid.ncells + 2);
-    if (!rc) { c->cells = c->cells_base + 1; c->cells_alloc = c->grid.ncells; }
+    if (!rc) rc = dev_alloc_zero(&c->table.base, (size_t)c->grid.ncells + 2);
+    if (!rc) table_init(c, c->table.base, c->grid.ncells);
     if (!rc) rc = dev_alloc(&c->k0, (size_t)capacity);
     if (!rc) rc = dev_alloc(&c->v0, (size_t)capacity);
     if (!rc) rc = dev_alloc(&c->k1, (size_t)capacity);
@@ -269,27 +269,13 @@ void timing_collect(sph_ctx* c) {
 }
 
 // ---- phase bodies ------------------------------------------------------------------------------------------
-static int do_hash(sph_ctx* c) {
+int step_hash(sph_ctx* c, bool ghosts_to_sort) {
     PhaseTimer t(c, SPH_PH_ZINDEX);
-    // the table of the previous step dies with its keys -- unless the sort is going to merge: then only the
-    // cells the movers leave can become empty, and the sort clears just those (the table is rebuilt by the
-    // sort's reorder pass over exactly the same owned slots).  The cells of a slab's old ghosts die here.
-    const uint32_t lo = c->own_off - c->n_glo, hi = c->own_off + c->n + c->n_ghi;
-    c->cells_clear_deferred = c->sort_merge && c->order_valid && table_covers(c, lo, hi);
-    int rc;
-    c->ghost_clear_pending = false;
-    if (c->cells_clear_deferred && c->defer_ghost_clear && (c->n_glo | c->n_ghi)) {
-        // (the slab step: launch_sort, called next, clears them -- sph_ctx::defer_ghost_clear; cells_lo / cells_hi keep the ghosts
-        // until then, so that a full sort's clearing of the whole table range still covers them)
-        c->ghost_clear[0] = lo; c->ghost_clear[1] = c->own_off; c->ghost_clear[2] = c->own_off + c->n; c->ghost_clear[3] = hi;
-        c->ghost_clear_pending = true;
-        rc = SPH_OK;
-    } else if (c->cells_clear_deferred) {
-        rc = launch_cells_clear_2ranges(c, lo, c->own_off, c->own_off + c->n, hi);      // both ghost ranges, one launch
-        c->cells_lo = c->own_off; c->cells_hi = c->own_off + c->n;
-    } else {
-        rc = launch_cells_clear(c);
-    }
+    // the table of the previous step dies with its keys -- unless the sort is going to merge: then it stays live for that
+    // sort (the table is rebuilt by the sort's reorder pass over exactly the same owned slots; table_leave_to_sort)
+    const SlotRange live = live_slots(c);
+    int rc = c->sort_merge && c->order_valid && table_covers(c, live.lo, live.hi) ? table_leave_to_sort(c, ghosts_to_sort)
+                                                                                 : launch_cells_clear(c);
     if (rc) return rc;
     rc = launch_hash(c);
     if (rc) return rc;
@@ -298,9 +284,9 @@ static int do_hash(sph_ctx* c) {
     return SPH_OK;
 }
 
-static int do_sort(sph_ctx* c) {
+int step_sort(sph_ctx* c, bool* owned_build_pending) {
     PhaseTimer t(c, SPH_PH_SORT);
-    int rc = launch_sort(c);
+    int rc = launch_sort(c, owned_build_pending);
     if (rc) return rc;
     c->n_glo = c->n_ghi = 0;
     c->halo_n_valid = false;
@@ -309,20 +295,16 @@ static int do_sort(sph_ctx* c) {
     return SPH_OK;
 }
 
-static int do_cells(sph_ctx* c) {
+int step_cells(sph_ctx* c) {
     PhaseTimer t(c, SPH_PH_BGRID);
-    const uint32_t lo = c->own_off - c->n_glo, hi = c->own_off + c->n + c->n_ghi;
-    if (!table_covers(c, lo, hi)) {   // whole-domain: built by the sort's reorder pass
+    const SlotRange live = live_slots(c);
+    if (!table_covers(c, live.lo, live.hi)) {   // whole-domain: built by the sort's reorder pass
         int rc = launch_cells_build(c);      // slab: adds the ghost cells to the owned ones the sort built
         if (rc) return rc;
     }
     c->stage = sph_ctx::ST_CELLS;
     return SPH_OK;
 }
-
-int step_hash(sph_ctx* c) { return do_hash(c); }
-int step_sort(sph_ctx* c) { return do_sort(c); }
-int step_cells(sph_ctx* c) { return do_cells(c); }
 
 static int do_density(sph_ctx* c) {
     PhaseTimer t(c, SPH_PH_DENS);
@@ -345,16 +327,16 @@ int set_slab_range(sph_ctx* c, uint32_t z_lo, uint32_t z_hi) {
     tmp.ghost_layers = c->ghost_layers;
     int rc = derive(&tmp, &c->params, z_lo, z_hi, true);
     if (rc) return rc;
-    if (tmp.grid.ncells > c->cells_alloc) {
+    if (tmp.grid.ncells > c->table.alloc) {
         SPH_HIP(hipStreamSynchronize(c->stream));
         uint2* base = nullptr;
         rc = dev_alloc_zero(&base, (size_t)tmp.grid.ncells + 2);
         if (rc) return rc;
-        hipFree(c->cells_base);
-        c->cells_base = base; c->cells = base + 1; c->cells_alloc = tmp.grid.ncells;
+        hipFree(c->table.base);
+        table_init(c, base, tmp.grid.ncells);
     }
     c->grid = tmp.grid; c->z_lo = z_lo; c->z_hi = z_hi; c->key_bits = tmp.key_bits;
-    c->cells_valid = false; c->cells_clear_deferred = false;
+    table_forget(c);                    // (the caller has cleared the entries)
     order_lost(c);
     // (no mover_count_unknown, kept as found: the slab step is host-paced and never reads it, and the next sort is the full one)
     results_stale(c);
@@ -923,12 +905,12 @@ int sph_get_order(sph_ctx* c, uint32_t* index) {
 
 int sph_get_cell_range(sph_ctx* c, uint32_t cell, uint32_t* start, uint32_t* end) {
     SPH_REQUIRE(c && start && end, SPH_E_INVALID, "null argument");
-    SPH_REQUIRE(c->cells_valid, SPH_E_STATE, "sph_build_cells has not run");
+    SPH_REQUIRE(c->table.valid, SPH_E_STATE, "sph_build_cells has not run");
     SPH_REQUIRE(cell < c->grid.ncells, SPH_E_INVALID, "cell %u out of range", cell);
     uint2 v;
     SPH_HIP(hipSetDevice(c->device));
     SPH_HIP(hipStreamSynchronize(c->stream));
-    SPH_HIP(hipMemcpy(&v, c->cells + cell, sizeof(v), hipMemcpyDeviceToHost));
+    SPH_HIP(hipMemcpy(&v, c->table.cells + cell, sizeof(v), hipMemcpyDeviceToHost));
     *start = v.x - (v.y > v.x ? c->own_off - c->n_glo : 0);
     *end = v.y - (v.y > v.x ? c->own_off - c->n_glo : 0);
     return SPH_OK;
@@ -936,10 +918,10 @@ int sph_get_cell_range(sph_ctx* c, uint32_t cell, uint32_t* start, uint32_t* end
 
 int sph_get_cells(sph_ctx* c, uint32_t max_cells, uint32_t* key, uint32_t* start, uint32_t* count) {
     SPH_REQUIRE(c, SPH_E_INVALID, "null context");
-    SPH_REQUIRE(c->cells_valid, SPH_E_STATE, "sph_build_cells has not run");
+    SPH_REQUIRE(c->table.valid, SPH_E_STATE, "sph_build_cells has not run");
     SPH_HIP(hipSetDevice(c->device));
     SPH_HIP(hipStreamSynchronize(c->stream));
-    const uint32_t lo = c->cells_lo, hi = c->cells_hi;
+    const uint32_t lo = c->table.lo, hi = c->table.hi;
     std::vector<uint32_t> ks(hi - lo);
     if (hi > lo) SPH_HIP(hipMemcpy(ks.data(), c->keyS + lo, (hi - lo) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     std::vector<uint32_t> uniq;                         // occupied cells, in slot order
@@ -954,7 +936,7 @@ int sph_get_cells(sph_ctx* c, uint32_t max_cells, uint32_t* key, uint32_t* start
         if (!rc) {
             hipError_t e = hipMemcpy(d_keys, uniq.data(), take * sizeof(uint32_t), hipMemcpyHostToDevice);
             if (e == hipSuccess) {
-                hipLaunchKernelGGL(k_gather_cells, dim3(ceil_div(take, 256)), dim3(256), 0, c->stream, d_keys, take, c->cells,
+                hipLaunchKernelGGL(k_gather_cells, dim3(ceil_div(take, 256)), dim3(256), 0, c->stream, d_keys, take, c->table.cells,
                                    d_out);
                 e = hipGetLastError();
             }
@@ -982,26 +964,26 @@ uint32_t sph_cell_key(const sph_ctx* c, uint32_t x, uint32_t y, uint32_t z) {
 int sph_hash(sph_ctx* c) {
     SPH_REQUIRE(c, SPH_E_INVALID, "null context");
     SPH_HIP(hipSetDevice(c->device));
-    return do_hash(c);
+    return step_hash(c);
 }
 
 int sph_sort(sph_ctx* c) {
     SPH_REQUIRE(c, SPH_E_INVALID, "null context");
     SPH_REQUIRE(c->stage == sph_ctx::ST_HASHED, SPH_E_STATE, "sph_sort needs sph_hash first");
     SPH_HIP(hipSetDevice(c->device));
-    return do_sort(c);
+    return step_sort(c);
 }
 
 int sph_build_cells(sph_ctx* c) {
     SPH_REQUIRE(c, SPH_E_INVALID, "null context");
     SPH_REQUIRE(c->stage >= sph_ctx::ST_SORTED, SPH_E_STATE, "sph_build_cells needs sph_sort first");
     SPH_HIP(hipSetDevice(c->device));
-    return do_cells(c);
+    return step_cells(c);
 }
 
 int sph_density(sph_ctx* c) {
     SPH_REQUIRE(c, SPH_E_INVALID, "null context");
-    SPH_REQUIRE(c->stage >= sph_ctx::ST_CELLS && c->cells_valid, SPH_E_STATE, "sph_density needs sph_build_cells first");
+    SPH_REQUIRE(c->stage >= sph_ctx::ST_CELLS && c->table.valid, SPH_E_STATE, "sph_density needs sph_build_cells first");
     SPH_HIP(hipSetDevice(c->device));
     return do_density(c);
 }
@@ -1019,7 +1001,7 @@ int sph_force(sph_ctx* c) {
 
 int sph_collide(sph_ctx* c) {
     SPH_REQUIRE(c, SPH_E_INVALID, "null context");
-    SPH_REQUIRE(c->stage >= sph_ctx::ST_CELLS && c->cells_valid, SPH_E_STATE, "sph_collide needs sph_build_cells first");
+    SPH_REQUIRE(c->stage >= sph_ctx::ST_CELLS && c->table.valid, SPH_E_STATE, "sph_collide needs sph_build_cells first");
     SPH_HIP(hipSetDevice(c->device));
     PhaseTimer t(c, SPH_PH_COLLISION);
     int rc = launch_force(c, false, true, false, 0.f);
@@ -1044,9 +1026,9 @@ int sph_step(sph_ctx* c, float dt, uint32_t n_steps) {
     SPH_REQUIRE(c, SPH_E_INVALID, "null context");
     SPH_HIP(hipSetDevice(c->device));
     for (uint32_t s = 0; s < n_steps; s++) {
-        int rc = do_hash(c);
-        if (!rc) rc = do_sort(c);
-        if (!rc) rc = do_cells(c);
+        int rc = step_hash(c);
+        if (!rc) rc = step_sort(c);
+        if (!rc) rc = step_cells(c);
         if (!rc) rc = do_density(c);
         if (rc) return rc;
         {

@@ -82,6 +82,36 @@ struct SphereBodies {
 
 constexpr uint32_t SPHERES_STEP_THREADS = 256;   // k_spheres_step: one block (sph_pairs.hip)
 
+// What sph_hash leaves of the old cell table to the sort that follows it.  It lives in the context because the two are
+// separate public calls; launch_sort takes it (table_take_left), and clearing or forgetting the table resets it.
+enum class TableLeft : uint8_t {
+    NOTHING,            // the hash cleared the table (or there was none)
+    OWNED,              // the table of the owned slots stays live for a merging sort, which clears only the cells the movers leave
+    OWNED_AND_GHOSTS    // ... and the cells of the old ghosts are still in it (the slab step: spare blocks of the sort's
+                        // k_mm_compact clear them, ~6 us less than a kernel of their own at the head of every rank's step)
+};
+
+// The cell table and what the host knows of it.  Everybody reads it (table_covers); it is written only by the operations next
+// to the launch_cells_* launchers (sph_pairs.hip) and by table_set below.
+struct CellTable {
+    uint2* cells = nullptr;        // = base + 1
+    uint2* base = nullptr;         // the allocation: ncells + one zero guard entry on either side
+    uint32_t alloc = 0;            // cells the allocation holds (a slab whose layer range grows gets a bigger table: set_slab_range)
+    uint32_t lo = 0, hi = 0;       // slot range the table was built from
+    bool valid = false;
+    TableLeft left = TableLeft::NOTHING;
+};
+
+// The movers the fused integrate epilogue marked for the next sort, and the count of them the host may look at.  Owned by
+// sph_sort.hip (mm_set_marks, mm_scan_marks, mm_drop_marks, launch_merge_count).
+struct MoverMarks {
+    bool marked = false;           // mm_mask / mm_tile_cnt hold the marks of the slots [off, off + n)
+    bool scanned = false;          // ... and the scan that counts them is already queued (mm_scan_marks)
+    uint32_t off = 0, n = 0;
+    uint32_t scan_seq = 0;         // mover counts queued so far (k_mm_tilescan; k_mm_compact when it counts itself)
+    bool counted_valid = false;    // the last count queued (scan_seq) is that of the CURRENT marks
+};
+
 }  // namespace sph
 
 // The opaque context of include/sph_hip.h.
@@ -176,21 +206,9 @@ struct sph_ctx {
     bool order_ztile_dens = true, order_xrot = true;        // (SPH_BLOCK_ORDER fields 4 and 5: the strips for the density pass too; XCD x starts at strip x * strips / 8)
     uint32_t order_strip_sh = 4;
 
-    // cell table: {start, end} per local cell, zero = empty
-    uint2* cells = nullptr;        // = cells_base + 1
-    uint2* cells_base = nullptr;   // the allocation: ncells + one zero guard entry on either side
-    uint32_t cells_alloc = 0;      // cells the allocation holds (a slab whose layer range grows gets a bigger table: set_slab_range)
-    uint32_t cells_lo = 0, cells_hi = 0;   // slot range the table was built from
-    bool cells_valid = false;
-    bool cells_clear_deferred = false;   // sph_hash left the clearing of the old table to the sort (merge path)
-    // the slab step builds the table of the owned slots INSIDE its bounds kernel (one dispatch less on every rank's critical
-    // path): it sets `owned_cells_in_bounds` around its sort, the sort then leaves the build `pending` instead of launching it
-    bool owned_cells_in_bounds = false, owned_cells_pending = false;
-    // ... and the clearing of the OLD ghosts' cells (a kernel of its own at hash time: k_cells_clear2, ~6 us at the head of every
-    // rank's step) to spare blocks of the sort's k_mm_compact: the slab step sets `defer_ghost_clear` around its hash, the hash
-    // then only notes the two ranges, and launch_sort clears them -- in k_mm_compact when it merges, else with the kernel
-    bool defer_ghost_clear = false, ghost_clear_pending = false;
-    uint32_t ghost_clear[4] = {0, 0, 0, 0};       // slot ranges [0],[1]) and [2],[3])
+    // cell table: {start, end} per local cell, zero = empty (sph::CellTable above; changed only by the operations at the head
+    // of sph_pairs.hip)
+    sph::CellTable table;
     bool keys_fresh = false;   // k0 already holds the keys of the current positions (written by the integrate epilogue)
 
     // radix sort scratch
@@ -225,9 +243,6 @@ struct sph_ctx {
     // run-ahead to four sorts), [4] the number of the last mover count, stored AFTER the count [0] (the skip of a sort with
     // nothing to do needs the count of the CURRENT marks: it is looked at, never waited for).
     uint32_t sort_seq_issued = 0;   // sorts that queued a table build so far
-    uint32_t scan_seq_issued = 0;   // mover counts queued so far (k_mm_tilescan; k_mm_compact when it counts itself)
-    uint32_t cells_seq_next = 0;    // what the next whole-range table build echoes into mm_count_host[3] (0: nothing)
-    bool mm_counted_valid = false;  // the last count queued (scan_seq_issued) is that of the CURRENT marks
     uint64_t sort_merges = 0, sort_calls = 0, sort_skips = 0;   // skips: merges with no mover at all (nothing done)
     // A whole-domain context picks ONE form of the movers' sort from a count up to four steps old (radix_sort_bits).  A flow
     // changes that count slowly; the caller can change it at once (new positions or velocities for everybody: an upload, a
@@ -246,12 +261,9 @@ struct sph_ctx {
                                             // [3] / [4] sequence numbers of the last table build / the last count (above); 8 words
     uint32_t* mm_count_host_dev = nullptr;  // device view of the same word
     unsigned long long* mm_total = nullptr; // movers of all sorts so far (device; sph_sort_stats)
-    // the fused integrate epilogue already wrote mm_mask / mm_tile_cnt for the range it was launched on
-    bool mm_marked = false;
-    bool mm_scanned = false;        // ... and the scan that counts them is already queued (mm_scan_marks)
+    sph::MoverMarks marks;          // the fused integrate epilogue already wrote mm_mask / mm_tile_cnt for a range
     uint32_t* mm_tileL = nullptr;   // coarse mover ranks per 4096 slots (k_mm_tile_rank)
     uint32_t* mm_tileA = nullptr;   // first key of every 4096-slot tile of the old order (k_mm_tile_rank)
-    uint32_t mm_marked_off = 0, mm_marked_n = 0;
     uint32_t* d_scratch = nullptr;  // small device scratch (counts)
     uint32_t* h_scratch = nullptr;  // pinned host mirror
 
@@ -269,8 +281,9 @@ struct sph_ctx {
 namespace sph {
 
 void set_error(const char* fmt, ...);
-void mm_drop_marks(sph_ctx* c, bool counted = false);     // sph_sort.hip
-void mm_scan_marks(sph_ctx* c);     // sph_sort.hip
+void mm_set_marks(sph_ctx* c);      // sph_sort.hip: the integrate epilogue has marked the movers of the owned range
+void mm_scan_marks(sph_ctx* c);     // ... count them now if the next sort could be skipped
+void mm_drop_marks(sph_ctx* c, bool counted = false);     // ... forget them
 int hip_fail(hipError_t e, const char* what, const char* file, int line);
 
 #define SPH_HIP(call)                                                        \
@@ -291,11 +304,19 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line);
 int launch_hash(sph_ctx* c);
 int launch_reset_lattice(sph_ctx* c, const uint32_t lattice[3], int jitter, const float jitter_dims[3], uint64_t start,
                          uint32_t count);
-int launch_sort(sph_ctx* c);          // radix sort of (k0,v0)[0,n) + reorder into posi2/velr2/keyS
+// radix sort of (k0,v0)[0,n) + reorder into posi2/velr2/keyS, or the merge, or nothing (at rest); `owned_build_pending`: step_sort
+int launch_sort(sph_ctx* c, bool* owned_build_pending = nullptr);
 int launch_merge_arrivals(sph_ctx* c, uint32_t n_in, uint32_t n_front = 0);   // particles appended behind the sorted range join it
-int launch_cells_clear(sph_ctx* c);
+// the cell table (sph_pairs.hip): the first six keep c->table's description, the *_range / *_2ranges launchers only touch entries
+int launch_cells_clear(sph_ctx* c);                   // clears the entries of the built range and forgets it (table_forget)
+void table_forget(sph_ctx* c);                        // no table any more, nothing left to a sort (the entries are the caller's business)
+int table_drop_ends(sph_ctx* c, uint32_t m_lo, uint32_t m_hi);   // a table over the owned slots loses the first m_lo and the last m_hi of them
+int table_drop_ghosts(sph_ctx* c);                    // a table over the owned slots and the ghosts shrinks to the owned slots
+int table_leave_to_sort(sph_ctx* c, bool ghosts_too); // sph_hash: the table stays live for a merging sort (TableLeft)
+TableLeft table_take_left(sph_ctx* c);                // launch_sort: what the hash left, if the table is still there; taken once
 int launch_cells_clear_range(sph_ctx* c, uint32_t lo, uint32_t hi);
-int launch_cells_build_range(sph_ctx* c, uint32_t lo, uint32_t hi);
+// (`seq`: what a build over the whole owned range echoes into mm_count_host[3] -- the sort's number, sort_throttle)
+int launch_cells_build_range(sph_ctx* c, uint32_t lo, uint32_t hi, uint32_t seq = 0);
 int launch_cells_clear_2ranges(sph_ctx* c, uint32_t lo0, uint32_t hi0, uint32_t lo1, uint32_t hi1);
 int launch_cells_build_2ranges(sph_ctx* c, uint32_t lo0, uint32_t hi0, uint32_t lo1, uint32_t hi1);
 int launch_cells_build(sph_ctx* c);
@@ -315,8 +336,11 @@ int launch_force_range(sph_ctx* c, uint32_t lo, uint32_t hi, bool force, bool co
 int force_finish(sph_ctx* c, bool integrate, bool mark, float dt);   // also advances the colliders' centres by dt (a tracked context: queues k_spheres_step)
 // phase bodies of sph_capi.hip (with their bookkeeping), for the slab driver
 int set_slab_range(sph_ctx* c, uint32_t z_lo, uint32_t z_hi);   // sph_capi.hip: a slab context takes over another layer range (its table must be clear)
-int step_hash(sph_ctx* c);
-int step_sort(sph_ctx* c);
+// `ghosts_to_sort`: the cells of the old ghosts are cleared by the sort that the caller runs next, not by a kernel of their own
+int step_hash(sph_ctx* c, bool ghosts_to_sort = false);
+// non-null `owned_build_pending`: the caller builds the table of the owned slots itself (the slab step: inside
+// k_slab_bounds_pack, one dispatch less on every rank's critical path); set to whether a build is owed (not after a skipped sort)
+int step_sort(sph_ctx* c, bool* owned_build_pending = nullptr);
 int step_cells(sph_ctx* c);
 int launch_integrate(sph_ctx* c, float dt);
 // tracked contexts (sph_pairs.hip): write the host's sphere set into trk_table and zero J and the step count; refresh R + eps
@@ -343,9 +367,14 @@ inline void swap_state(sph_ctx* c, bool keys) {
     if (keys) { std::swap(c->keyS, c->keyS2); c->own_off = c->gcap; }
 }
 // the cell table is live and was built from exactly the slots [lo, hi)
-inline bool table_covers(const sph_ctx* c, uint32_t lo, uint32_t hi) { return c->cells_valid && c->cells_lo == lo && c->cells_hi == hi; }
+inline bool table_covers(const sph_ctx* c, uint32_t lo, uint32_t hi) { return c->table.valid && c->table.lo == lo && c->table.hi == hi; }
+// the allocation of `alloc` cells at `base`, all zero, is the table now (create; a slab that takes over more layers)
+inline void table_init(sph_ctx* c, uint2* base, uint32_t alloc) { c->table.base = base; c->table.cells = base + 1; c->table.alloc = alloc; }
 // a table build over the slots [lo, hi) has been queued
-inline void set_table(sph_ctx* c, uint32_t lo, uint32_t hi) { c->cells_lo = lo; c->cells_hi = hi; c->cells_valid = true; }
+inline void table_set(sph_ctx* c, uint32_t lo, uint32_t hi) { c->table.lo = lo; c->table.hi = hi; c->table.valid = true; }
+// the slots that hold particles: the owned range and the ghosts installed on either side of it
+struct SlotRange { uint32_t lo, hi; };
+inline SlotRange live_slots(const sph_ctx* c) { return SlotRange{c->own_off - c->n_glo, c->own_off + c->n + c->n_ghi}; }
 
 // the records of posi / velr as sph_upload, sph_emit and a snapshot hold them: (x, y, z, creation index bits), (vx, vy, vz, 0);
 // particle i gets index[i], or first + i without an index array

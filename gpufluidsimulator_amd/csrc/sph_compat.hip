@@ -402,7 +402,7 @@ void cudaConstructBGrid(sph_compat_particle* p, unsigned int n, sph_compat_grid_
     if (B && B_size) {     // the caller's table, as kernelConstructBGrid leaves it (particleSystem.cu:503-509)
         CKH(hipMemsetAsync(B, 0, (size_t)B_size * sizeof(sph_compat_grid_item), x->stream));
         if (n) {
-            hipLaunchKernelGGL(k_compat_B, dim3(ceil_div(n, 256)), dim3(256), 0, x->stream, x->keyS + x->own_off, x->cells,
+            hipLaunchKernelGGL(k_compat_B, dim3(ceil_div(n, 256)), dim3(256), 0, x->stream, x->keyS + x->own_off, x->table.cells,
                                c.sorted ? c.m2n : (const uint32_t*)nullptr, n, B_size, x->grid.g[0], x->grid.g[1], B);
             CKH(hipGetLastError());
         }
@@ -421,11 +421,11 @@ void cudaConstructGridArray(sph_compat_particle* p, unsigned int n, sph_compat_g
     if (n) {
         const uint32_t nt = ceil_div(n, 256u);
         sph_compat_grid_item* out = Bp ? *Bp : nullptr;
-        hipLaunchKernelGGL(k_compat_Bprime<0>, dim3(nt), dim3(256), 0, x->stream, x->keyS + x->own_off, x->cells,
+        hipLaunchKernelGGL(k_compat_Bprime<0>, dim3(nt), dim3(256), 0, x->stream, x->keyS + x->own_off, x->table.cells,
                            c.sorted ? c.m2n : (const uint32_t*)nullptr, n, x->own_off, c.bp_cnt, c.bp_off, out, n);
         hipLaunchKernelGGL(k_compat_scan, dim3(1), dim3(1024), 0, x->stream, c.bp_cnt, nt, c.bp_off, c.bp_total);
         if (out)
-            hipLaunchKernelGGL(k_compat_Bprime<1>, dim3(nt), dim3(256), 0, x->stream, x->keyS + x->own_off, x->cells,
+            hipLaunchKernelGGL(k_compat_Bprime<1>, dim3(nt), dim3(256), 0, x->stream, x->keyS + x->own_off, x->table.cells,
                                c.sorted ? c.m2n : (const uint32_t*)nullptr, n, x->own_off, c.bp_cnt, c.bp_off, out, n);
         CKH(hipGetLastError());
         CKH(hipStreamSynchronize(x->stream));

@@ -219,7 +219,6 @@ int sph_remove(sph_ctx* c, uint32_t n_regions, const sph_region* regions, uint32
     // the table of the last sort describes slots that are about to move: clear it from the OLD keys while they are in place
     rc = launch_cells_clear(c);
     if (rc) return rc;
-    c->cells_clear_deferred = false;
     mm_drop_marks(c);                         // per-slot marks of the integrate epilogue: the slots are renumbered
     const uint32_t n = c->n, take = removed_index ? (max_out < total ? max_out : total) : 0u;
     hipLaunchKernelGGL(k_edit_compact, dim3(ceil_div(n, EDIT_TILE)), dim3(EDIT_THREADS), 0, c->stream, c->posi + c->own_off,

@@ -119,15 +119,8 @@ int sph_migrants_pack(sph_ctx* c, void* buf_dev[2], uint32_t capacity) {
     rc = pack_slice(c, c->own_off, m[0], buf_dev[0], capacity);
     if (!rc) rc = pack_slice(c, c->own_off + c->n - m[1], m[1], buf_dev[1], capacity);
     if (rc) return rc;
-    if (table_covers(c, c->own_off, c->own_off + c->n)) {
-        // the sort built the table over all owned slots: drop the cells of the particles that leave (they sit in
-        // the two ghost layers, which hold nothing else until the ghosts are installed)
-        rc = launch_cells_clear_range(c, c->own_off, c->own_off + m[0]);
-        if (!rc) rc = launch_cells_clear_range(c, c->own_off + c->n - m[1], c->own_off + c->n);
-        if (rc) return rc;
-        c->cells_lo += m[0];
-        c->cells_hi -= m[1];
-    }
+    rc = table_drop_ends(c, m[0], m[1]);      // the cells of the particles that leave
+    if (rc) return rc;
     c->own_off += m[0];
     c->n -= m[0] + m[1];
     return SPH_OK;

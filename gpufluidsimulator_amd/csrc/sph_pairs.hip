@@ -94,7 +94,7 @@ int launch_cells_clear_2ranges(sph_ctx* c, uint32_t lo0, uint32_t hi0, uint32_t 
     if (hi1 < lo1) hi1 = lo1;
     const uint32_t tot = (hi0 - lo0) + (hi1 - lo1);
     if (!tot) return SPH_OK;
-    hipLaunchKernelGGL(k_cells_clear2, dim3(ceil_div(tot, 256)), dim3(256), 0, c->stream, c->keyS, lo0, hi0, lo1, hi1, c->cells);
+    hipLaunchKernelGGL(k_cells_clear2, dim3(ceil_div(tot, 256)), dim3(256), 0, c->stream, c->keyS, lo0, hi0, lo1, hi1, c->table.cells);
     SPH_HIP(hipGetLastError());
     return SPH_OK;
 }
@@ -104,52 +104,92 @@ int launch_cells_build_2ranges(sph_ctx* c, uint32_t lo0, uint32_t hi0, uint32_t 
     if (hi1 < lo1) hi1 = lo1;
     const uint32_t tot = (hi0 - lo0) + (hi1 - lo1);
     if (!tot) return SPH_OK;
-    hipLaunchKernelGGL(k_cells_build2, dim3(ceil_div(tot, 256)), dim3(256), 0, c->stream, c->keyS, lo0, hi0, lo1, hi1, c->cells);
+    hipLaunchKernelGGL(k_cells_build2, dim3(ceil_div(tot, 256)), dim3(256), 0, c->stream, c->keyS, lo0, hi0, lo1, hi1, c->table.cells);
     SPH_HIP(hipGetLastError());
     return SPH_OK;
 }
 
+// ---- what the host knows of the table (sph_ctx::table): every change of it is one of the operations from here down to
+//      launch_cells_build ----
+void table_forget(sph_ctx* c) { c->table.valid = false; c->table.left = TableLeft::NOTHING; }
+
 int launch_cells_clear(sph_ctx* c) {
-    if (!c->cells_valid || c->cells_hi <= c->cells_lo) { c->cells_valid = false; return SPH_OK; }
-    hipLaunchKernelGGL(k_cells_clear, dim3(ceil_div(c->cells_hi - c->cells_lo, 256)), dim3(256), 0, c->stream, c->keyS,
-                       c->cells_lo, c->cells_hi, c->cells);
-    SPH_HIP(hipGetLastError());
-    c->cells_valid = false;
+    const CellTable& t = c->table;
+    if (t.valid && t.hi > t.lo) {
+        hipLaunchKernelGGL(k_cells_clear, dim3(ceil_div(t.hi - t.lo, 256)), dim3(256), 0, c->stream, c->keyS, t.lo, t.hi, t.cells);
+        SPH_HIP(hipGetLastError());
+    }
+    table_forget(c);
     return SPH_OK;
+}
+
+// The first m_lo and the last m_hi owned slots leave (a slab's leavers: they sit in the two ghost layers, which hold nothing
+// else until the ghosts are installed).  A table the sort built over all owned slots drops their cells; any other table is
+// left alone (the next build replaces it).  The caller moves own_off and n afterwards.
+int table_drop_ends(sph_ctx* c, uint32_t m_lo, uint32_t m_hi) {
+    const uint32_t lo = c->own_off, hi = c->own_off + c->n;
+    if (!table_covers(c, lo, hi)) return SPH_OK;
+    const int rc = launch_cells_clear_2ranges(c, lo, lo + m_lo, hi - m_hi, hi);
+    if (rc) return rc;
+    c->table.lo += m_lo;
+    c->table.hi -= m_hi;
+    return SPH_OK;
+}
+
+// the table covers the owned slots and the ghosts around them: the ghosts' cells leave it (both ranges, one launch)
+int table_drop_ghosts(sph_ctx* c) {
+    const uint32_t lo = c->own_off, hi = c->own_off + c->n;
+    const int rc = launch_cells_clear_2ranges(c, c->table.lo, lo, hi, c->table.hi);
+    c->table.lo = lo; c->table.hi = hi;
+    return rc;
+}
+
+// sph_hash, when the sort that follows can merge: only the cells the movers leave can become empty, and the sort clears just
+// those.  The cells of a slab's old ghosts die here -- or, `ghosts_too`, in that sort (lo / hi keep the ghosts until then, so
+// that a full sort's clearing of the whole table range still covers them).
+int table_leave_to_sort(sph_ctx* c, bool ghosts_too) {
+    if (ghosts_too && (c->n_glo | c->n_ghi)) { c->table.left = TableLeft::OWNED_AND_GHOSTS; return SPH_OK; }
+    c->table.left = TableLeft::OWNED;
+    return table_drop_ghosts(c);
+}
+
+TableLeft table_take_left(sph_ctx* c) {
+    const TableLeft left = c->table.valid ? c->table.left : TableLeft::NOTHING;
+    c->table.left = TableLeft::NOTHING;
+    return left;
 }
 
 // clear / build the table entries of the cells that occur in the slot range [lo, hi) (no bookkeeping)
 int launch_cells_clear_range(sph_ctx* c, uint32_t lo, uint32_t hi) {
     if (hi <= lo) return SPH_OK;
-    hipLaunchKernelGGL(k_cells_clear, dim3(ceil_div(hi - lo, 256)), dim3(256), 0, c->stream, c->keyS, lo, hi, c->cells);
+    hipLaunchKernelGGL(k_cells_clear, dim3(ceil_div(hi - lo, 256)), dim3(256), 0, c->stream, c->keyS, lo, hi, c->table.cells);
     SPH_HIP(hipGetLastError());
     return SPH_OK;
 }
 
-int launch_cells_build_range(sph_ctx* c, uint32_t lo, uint32_t hi) {
+int launch_cells_build_range(sph_ctx* c, uint32_t lo, uint32_t hi, uint32_t seq) {
     if (hi <= lo) return SPH_OK;
-    // (the whole owned range: the sort's table build -- also tells the host the first and the last key)
+    // (the whole owned range: the sort's table build -- also tells the host the first and the last key, and the sort's number)
     uint32_t* ends = (lo == c->own_off && hi == c->own_off + c->n) ? c->mm_count_host_dev + 1 : (uint32_t*)nullptr;
-    const uint32_t seq = ends ? c->cells_seq_next : 0u;
-    if (ends) c->cells_seq_next = 0u;
-    hipLaunchKernelGGL(k_cells_build, dim3(cells_build_blocks(hi - lo)), dim3(256), 0, c->stream, c->keyS, lo, hi, c->cells, ends, seq);
+    hipLaunchKernelGGL(k_cells_build, dim3(cells_build_blocks(hi - lo)), dim3(256), 0, c->stream, c->keyS, lo, hi, c->table.cells, ends,
+                       ends ? seq : 0u);
     SPH_HIP(hipGetLastError());
     return SPH_OK;
 }
 
 int launch_cells_build(sph_ctx* c) {
-    const uint32_t lo = c->own_off - c->n_glo, hi = c->own_off + c->n + c->n_ghi;
+    const SlotRange live = live_slots(c);
     int rc;
     if (table_covers(c, c->own_off, c->own_off + c->n)) {
         // the sort's reorder pass built the owned cells; ghost layers hold no owned particle, so their
         // cells are disjoint from those: add them from the two ghost ranges only
-        rc = launch_cells_build_2ranges(c, lo, c->own_off, c->own_off + c->n, hi);
+        rc = launch_cells_build_2ranges(c, live.lo, c->own_off, c->own_off + c->n, live.hi);
     } else {
         rc = launch_cells_clear(c);      // a table over another slot set, if any
-        if (!rc) rc = launch_cells_build_range(c, lo, hi);
+        if (!rc) rc = launch_cells_build_range(c, live.lo, live.hi);
     }
     if (rc) return rc;
-    set_table(c, lo, hi);
+    table_set(c, live.lo, live.hi);
     return SPH_OK;
 }
 
@@ -1285,7 +1325,7 @@ template <bool F, bool C, bool I, class... Sph>
 static void force_kernel(sph_ctx* c, bool small, const Targets& tg, uint32_t threads, float dt, bool mark, bool early, Sph... sp) {
 #define SPH_LAUNCH_FORCE_T(T)                                                                                                   \
     hipLaunchKernelGGL((k_force<F, C, I, T, Sph...>), dim3(ceil_div(threads, (uint32_t)T)), dim3(T), 0, c->stream, c->posi,       \
-                       c->velr, c->dp, c->cw, c->keyS, c->cells, c->fpress, c->fvisc, c->dvel, c->posi2, c->velr2,                \
+                       c->velr, c->dp, c->cw, c->keyS, c->table.cells, c->fpress, c->fvisc, c->dvel, c->posi2, c->velr2,                \
                        c->slab ? nullptr : c->pos_out, early ? c->keyS2 : c->k0, mark ? c->mm_mask : nullptr, c->mm_tile_cnt, tg,       \
                        early ? 0u : c->own_off, dt, c->grid, c->phys, sp...)
     if (small) SPH_LAUNCH_FORCE_T(SMALL_THREADS_PAIR); else SPH_LAUNCH_FORCE_T(PAIR_THREADS);
@@ -1463,7 +1503,7 @@ int force_finish(sph_ctx* c, bool integrate, bool mark, float dt) {
     swap_state(c, false);
     c->keys_fresh = true;
     if (mark) {
-        c->mm_marked = true; c->mm_scanned = false; c->mm_marked_off = c->own_off; c->mm_marked_n = c->n;
+        mm_set_marks(c);
         mm_scan_marks(c);          // count them now: the next sort finds the number ready
     }
     return rc;
@@ -1483,13 +1523,13 @@ static int launch_density_targets(sph_ctx* c, const Targets& tg, uint32_t thread
     if (threads == 0) return SPH_OK;
     if (c->precision == SPH_PRECISION_MIXED_F16)
         hipLaunchKernelGGL(k_density_h, dim3(ceil_div(threads, PAIR_THREADS)), dim3(PAIR_THREADS), 0, c->stream, c->posi,
-                           c->keyS, c->cells, c->dp, c->cw, tg, c->grid, c->phys);
+                           c->keyS, c->table.cells, c->dp, c->cw, tg, c->grid, c->phys);
     else if (small_blocks(c))
         hipLaunchKernelGGL(k_density<SMALL_THREADS_PAIR>, dim3(ceil_div(threads, (uint32_t)SMALL_THREADS_PAIR)), dim3(SMALL_THREADS_PAIR), 0, c->stream,
-                           c->posi, c->keyS, c->cells, c->dp, c->cw, tg, c->grid, c->phys);
+                           c->posi, c->keyS, c->table.cells, c->dp, c->cw, tg, c->grid, c->phys);
     else
         hipLaunchKernelGGL(k_density<DENS_THREADS>, dim3(ceil_div(threads, (uint32_t)DENS_THREADS)), dim3(DENS_THREADS), 0, c->stream, c->posi,
-                           c->keyS, c->cells, c->dp, c->cw, tg, c->grid, c->phys);
+                           c->keyS, c->table.cells, c->dp, c->cw, tg, c->grid, c->phys);
     SPH_HIP(hipGetLastError());
     return SPH_OK;
 }

@@ -135,7 +135,7 @@ __device__ __forceinline__ uint32_t wave_lower_bound(const uint32_t* __restrict_
 }
 
 // Round 6: the blocks from `pack_blocks` on build the cell table of the owned slots [own_off, own_off + n) (the sort leaves that
-// to this kernel in a slab step: sph_ctx::owned_cells_in_bounds) -- the build and the bounds / leavers work read the same sorted
+// to this kernel in a slab step: step_sort's owned_build_pending) -- the build and the bounds / leavers work read the same sorted
 // keys and nobody needs either before the other, so they share one dispatch on every rank's critical path (~5 us).
 __global__ __launch_bounds__(256) void k_slab_bounds_pack(const uint32_t* __restrict__ keys, const float4* __restrict__ posi,
                                                           const float4* __restrict__ velr, uint32_t n, uint32_t own_off,
@@ -1209,14 +1209,10 @@ int step_pre_wait(sph_slab* s, Step& st) {
     }
     rc = slab_check_device_flags(s); if (rc) return rc;
     // ---- hash + sort the owned particles (leavers end up at the two ends of the owned range) -----------------------
-    c->defer_ghost_clear = true;                  // the old ghosts' cells are cleared by the sort's first kernel, not by one of their own
-    rc = step_hash(c);
-    c->defer_ghost_clear = false;
+    rc = step_hash(c, true);                      // the old ghosts' cells are cleared by the sort's first kernel, not by one of their own
     if (rc) return rc;
-    c->owned_cells_in_bounds = true;              // the sort leaves the table of the owned slots to the bounds kernel below
-    c->owned_cells_pending = false;
-    rc = step_sort(c);
-    c->owned_cells_in_bounds = false;
+    bool owned_build_pending;                     // the sort leaves the table of the owned slots to the bounds kernel below
+    rc = step_sort(c, &owned_build_pending);
     if (rc) return rc;
     st.layer = c->grid.g[0] * c->grid.g[1];
     st.n0 = c->n; st.off0 = c->own_off;
@@ -1224,11 +1220,10 @@ int step_pre_wait(sph_slab* s, Step& st) {
     s->seq++;
     // a few blocks (many when they also copy two layers): every block finds the bounds for itself, the leavers and residents are packed in
     // grid-stride loops; behind them the blocks that build the cell table of the owned slots when the sort left it pending (not on a skipped sort)
-    const uint32_t pack_blocks = st.p1 ? 128u : min(ceil_div(s->mcap, 256u), 16u), build_blocks = c->owned_cells_pending ? cells_build_blocks(st.n0) : 0u;
-    c->owned_cells_pending = false;
+    const uint32_t pack_blocks = st.p1 ? 128u : min(ceil_div(s->mcap, 256u), 16u), build_blocks = owned_build_pending ? cells_build_blocks(st.n0) : 0u;
     hipLaunchKernelGGL(k_slab_bounds_pack, dim3(pack_blocks + build_blocks), dim3(256), 0, c->stream, c->keyS + st.off0, c->posi + st.off0,
                        c->velr + st.off0, st.n0, st.off0, st.layer, s->mcap, c->grid, s->early_cap, s->d_lb, s->mig_send[0], s->mig_send[1],
-                       pack_blocks, c->keyS, c->cells, c->mm_count_host_dev + 1, c->ghost_layers, st.p1 ? 1u : 0u, s->gcap);
+                       pack_blocks, c->keyS, c->table.cells, c->mm_count_host_dev + 1, c->ghost_layers, st.p1 ? 1u : 0u, s->gcap);
     SPH_HIP(hipGetLastError());
     rc = after_main(s); if (rc) return rc;
     // ---- the density of the deep interior goes into the main stream's queue BEFORE the host waits: its slot range
@@ -1404,12 +1399,10 @@ int step_settle(sph_slab* s, Step& st) {
     // ---- drop the leavers (their cells hold nothing else until the ghosts arrive; the clearing must precede the
     //      ghost cells, so it runs on the stream that builds those) ---------------------------------------------------
     if (m_lo || m_hi) {
-        if (table_covers(c, c->own_off, c->own_off + c->n)) {
+        {
             OnComm on(s, st.early_halo);
-            rc = launch_cells_clear_2ranges(c, c->own_off, c->own_off + m_lo, c->own_off + c->n - m_hi, c->own_off + c->n);
+            rc = table_drop_ends(c, m_lo, m_hi);
             if (rc) return rc;
-            c->cells_lo += m_lo;
-            c->cells_hi -= m_hi;
         }
         c->own_off += m_lo;
         c->n -= m_lo + m_hi;
@@ -1442,7 +1435,7 @@ int step_settle(sph_slab* s, Step& st) {
             SPH_HIP(hipGetLastError());
             if (side == 0) c->own_off = d0;
             c->n += k;
-            c->cells_lo = c->own_off; c->cells_hi = c->own_off + c->n;
+            table_set(c, c->own_off, c->own_off + c->n);
             rc = launch_cells_build_range(c, d0, d0 + nl + k); if (rc) return rc;
         }
         st.own_lo += in_lo;
@@ -1581,7 +1574,7 @@ int step_ghosts(sph_slab* s, Step& st) {
         // the owned slots (comm stream, one kernel: none of it is touched by the interior passes)
         if (g_lo + g_hi)
             hipLaunchKernelGGL(k_slab_unpack_ghosts, dim3(ceil_div(g_lo + g_hi, 256u)), dim3(256), 0, s->comm, s->halo_recv[0], g_lo,
-                               c->own_off - g_lo, s->halo_recv[1], g_hi, c->own_off + n, c->posi, c->velr, c->keyS, c->cells, c->grid);
+                               c->own_off - g_lo, s->halo_recv[1], g_hi, c->own_off + n, c->posi, c->velr, c->keyS, c->table.cells, c->grid);
     } else if (g_lo + g_hi) {
         // The one-message step: the neighbours' two layers came with their headers and leavers (behind those, in the same
         // buffer); no message here.  A side this rank sent nobody to is unpacked as it is; else its own leavers -- still in the
@@ -1591,7 +1584,7 @@ int step_ghosts(sph_slab* s, Step& st) {
         const uint32_t nr_lo = s->has_lo ? st.peer_own_lo + st.n2p_lo : 0u, nr_hi = s->has_hi ? st.peer_own_hi + st.n2p_hi : 0u;
         if (m_lo + m_hi == 0u) {
             hipLaunchKernelGGL(k_slab_unpack_ghosts, dim3(ceil_div(g_lo + g_hi, 256u)), dim3(256), 0, s->comm, res_lo, g_lo, c->own_off - g_lo,
-                               res_hi, g_hi, c->own_off + n, c->posi, c->velr, c->keyS, c->cells, c->grid);
+                               res_hi, g_hi, c->own_off + n, c->posi, c->velr, c->keyS, c->table.cells, c->grid);
         } else {
             hipLaunchKernelGGL(k_slab_unpack_ghosts_merge, dim3(ceil_div(g_lo + g_hi, 256u)), dim3(256), 0, s->comm, res_lo, nr_lo,
                                s->mig_send[0] + 2, s->has_lo ? m_lo : 0u, c->own_off - g_lo, res_hi, nr_hi, s->mig_send[1] + 2, s->has_hi ? m_hi : 0u,
@@ -1604,7 +1597,7 @@ int step_ghosts(sph_slab* s, Step& st) {
     SPH_HIP(hipGetLastError());
     c->n_glo = g_lo; c->n_ghi = g_hi;
     s->ghosts += g_lo + g_hi;
-    set_table(c, c->own_off - g_lo, c->own_off + n + g_hi);
+    table_set(c, c->own_off - g_lo, c->own_off + n + g_hi);
     c->stage = sph_ctx::ST_CELLS;
     if (early_halo) {
         // all that is left of the density pass (the boundary layers and the two layers next to them), queued on the COMM

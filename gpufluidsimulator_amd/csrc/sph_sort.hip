@@ -1012,7 +1012,7 @@ __global__ __launch_bounds__(256) void k_mm_compact(const uint64_t* __restrict__
                                                     uint32_t g1lo, uint32_t g1hi) {
     if (blockIdx.x >= nt) {
         // spare blocks (a slab step): the cells of the OLD ghost ranges [g0lo, g0hi) and [g1lo, g1hi) die here -- what
-        // k_cells_clear2 did in a launch of its own at hash time (sph_ctx::defer_ghost_clear).  Ghost cells hold no owned
+        // k_cells_clear2 did in a launch of its own at hash time (TableLeft::OWNED_AND_GHOSTS).  Ghost cells hold no owned
         // particle, so nothing the other blocks clear or read is touched.
         const uint32_t t = (blockIdx.x - nt) * 256u + threadIdx.x, n0 = g0hi - g0lo;
         const uint32_t lo = t < n0 ? g0lo : g1lo, hi = t < n0 ? g0hi : g1hi;
@@ -1218,19 +1218,31 @@ static uint32_t merge_grid_for(uint32_t movers_hint, uint32_t n) {
     return min(want, max(ceil_div(n, SORT_TILE), 1u));
 }
 
+// ---- the mover marks (sph_ctx::marks): every change of them is in the functions from here down to launch_merge_count ----
 // `counted`: the movers belong to a sort (they add to the running total), not to marks being dropped
 static void mm_tilescan(sph_ctx* c, uint32_t n, bool counted) {
     const uint32_t nt = ceil_div(ceil_div(n, 64u), MM_TILE_CHUNKS);
     // `counted`: the kernel echoes the scan's number behind the count, so that launch_sort can tell "the count of the CURRENT
-    // marks is there" by looking at two words of mapped host memory (no event: see sph_ctx::scan_seq_issued)
+    // marks is there" by looking at two words of mapped host memory (no event: see sph_ctx::sort_seq_issued)
     uint32_t seq = 0u;
-    if (counted) { if (++c->scan_seq_issued == 0u) c->scan_seq_issued = 1u; seq = c->scan_seq_issued; }     // (never 0: that is "no echo")
+    if (counted) { if (++c->marks.scan_seq == 0u) c->marks.scan_seq = 1u; seq = c->marks.scan_seq; }     // (never 0: that is "no echo")
     hipLaunchKernelGGL(k_mm_tilescan, dim3(1), dim3(1024), 0, c->stream, c->mm_tile_cnt, nt, c->mm_tile_off, c->mm_count,
                        c->mm_count_host_dev, counted ? c->mm_total : (unsigned long long*)nullptr, seq);
-    c->mm_counted_valid = counted;
+    c->marks.counted_valid = counted;
 }
 
 static uint32_t mm_tiles(uint32_t n) { return ceil_div(ceil_div(n, 64u), MM_TILE_CHUNKS); }
+
+// the owned slots whose key differs from the one the hash left in k0, marked by a kernel of its own
+static void launch_mm_mark(sph_ctx* c, uint32_t n) {
+    hipLaunchKernelGGL(k_mm_mark, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, c->keyS + c->own_off, c->k0, n, c->mm_mask,
+                       c->mm_tile_cnt);
+}
+
+// the integrate epilogue of a launch over the whole owned range has marked the movers of the next sort (force_finish)
+void mm_set_marks(sph_ctx* c) {
+    c->marks.marked = true; c->marks.scanned = false; c->marks.off = c->own_off; c->marks.n = c->n;
+}
 
 // Called right after the integrate epilogue has marked the movers.  While the fluid is AT REST (the last count the device
 // reported is 0) they are counted at the END of the step, so that the next sort finds the number ready: a caller in lockstep
@@ -1238,38 +1250,43 @@ static uint32_t mm_tiles(uint32_t n) { return ceil_div(ceil_div(n, 64u), MM_TILE
 // cell no sort is skipped, and the count is left to the sort itself (k_mm_compact adds the per-tile counts up: one dispatch
 // less per step, ~4.5 us); a range of more than MM_FUSED_SCAN_TILES tiles keeps the scan kernel.
 void mm_scan_marks(sph_ctx* c) {
-    if (!c->mm_marked || c->mm_scanned) return;
-    if (*c->mm_count_host != 0u && mm_tiles(c->mm_marked_n) <= MM_FUSED_SCAN_TILES) return;     // the sort will count them
-    mm_tilescan(c, c->mm_marked_n, true);
-    c->mm_scanned = true;
+    if (!c->marks.marked || c->marks.scanned) return;
+    if (*c->mm_count_host != 0u && mm_tiles(c->marks.n) <= MM_FUSED_SCAN_TILES) return;     // the sort will count them
+    mm_tilescan(c, c->marks.n, true);
+    c->marks.scanned = true;
 }
 
 // forget the marks the integrate epilogue left (the scan re-zeroes the tile counts they added to); `counted`: a full sort
 // stands in for the merge they were meant for, so the count still reports to the host and adds to the total
 void mm_drop_marks(sph_ctx* c, bool counted) {
-    if (!c->mm_marked) return;
-    if (!c->mm_scanned) mm_tilescan(c, c->mm_marked_n, counted);
-    c->mm_marked = false;
-    c->mm_scanned = false;
+    if (!c->marks.marked) return;
+    if (!c->marks.scanned) mm_tilescan(c, c->marks.n, counted);
+    c->marks.marked = false;
+    c->marks.scanned = false;
 }
 
 // step 1 of the merge: the movers are marked (by the integrate epilogue, or here) and counted -- by the scan kernel, or, when
 // this returns true, by k_mm_compact itself (launch_sort_merge: `count_in_compact`)
 static bool launch_merge_count(sph_ctx* c, uint32_t n) {
-    if (c->mm_marked && !(c->mm_marked_off == c->own_off && c->mm_marked_n == n)) mm_drop_marks(c);   // another range
-    if (!c->mm_marked) {                         // else: the fused integrate epilogue compared the keys already
-        hipLaunchKernelGGL(k_mm_mark, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, c->keyS + c->own_off, c->k0, n,
-                           c->mm_mask, c->mm_tile_cnt);
-        c->mm_scanned = false;
+    if (c->marks.marked && !(c->marks.off == c->own_off && c->marks.n == n)) mm_drop_marks(c);   // another range
+    if (!c->marks.marked) {                      // else: the fused integrate epilogue compared the keys already
+        launch_mm_mark(c, n);
+        c->marks.scanned = false;
     }
     bool in_compact = false;
-    if (!c->mm_scanned) {
-        if (mm_tiles(n) <= MM_FUSED_SCAN_TILES) { in_compact = true; c->mm_counted_valid = false; }
+    if (!c->marks.scanned) {
+        if (mm_tiles(n) <= MM_FUSED_SCAN_TILES) { in_compact = true; c->marks.counted_valid = false; }
         else mm_tilescan(c, n, true);
     }
-    c->mm_marked = false;
-    c->mm_scanned = false;
+    c->marks.marked = false;
+    c->marks.scanned = false;
     return in_compact;
+}
+
+// the count of the CURRENT marks has arrived from the device (looked at, never waited for), and it is 0
+static bool mm_counted_none(const sph_ctx* c) {
+    volatile const uint32_t* hw = c->mm_count_host;
+    return c->marks.counted_valid && hw[4] == c->marks.scan_seq && (std::atomic_thread_fence(std::memory_order_acquire), hw[0] == 0u);
 }
 
 // every slot from n_old on is a mover, none below (particles appended behind a sorted range)
@@ -1291,18 +1308,19 @@ __global__ __launch_bounds__(256) void k_mm_mark_tail(uint32_t n_old, uint32_t n
 // an old key (A) and a new one (B); slots [n, n_tot) -- particles that arrived from a neighbouring slab -- only a
 // new one, and all of them are movers.
 static int launch_sort_merge(sph_ctx* c, uint32_t n, uint32_t n_tot, bool table_live, uint32_t hint, Front front = Front{0u, 0u},
-                             bool count_in_compact = false, const uint32_t* ghost_clear = nullptr) {
+                             bool count_in_compact = false, bool clear_ghosts = false) {
     const uint32_t* A = c->keyS + c->own_off;
     const uint32_t* B = c->k0;
     const uint32_t nchunks = ceil_div(n_tot, 64u), nt = ceil_div(nchunks, MM_TILE_CHUNKS);
     uint32_t* mk = c->mm_k0; uint32_t* mi = c->v0; uint32_t* mk2 = c->mm_k1; uint32_t* mi2 = c->mm_v1;
-    // (ghost_clear: the old ghosts' cells, cleared by spare blocks of this launch -- launch_sort)
-    const uint32_t gc[4] = {ghost_clear ? ghost_clear[0] : 0u, ghost_clear ? ghost_clear[1] : 0u, ghost_clear ? ghost_clear[2] : 0u,
-                            ghost_clear ? ghost_clear[3] : 0u};
+    // (clear_ghosts: the old ghosts' cells, still in the table on either side of the owned slots, are cleared by spare blocks of
+    // this launch -- launch_sort)
+    const uint32_t gc[4] = {clear_ghosts ? c->table.lo : 0u, clear_ghosts ? c->own_off : 0u, clear_ghosts ? c->own_off + n : 0u,
+                            clear_ghosts ? c->table.hi : 0u};
     const uint32_t gc_blocks = ceil_div((gc[1] - gc[0]) + (gc[3] - gc[2]), 256u);
     hipLaunchKernelGGL(k_mm_compact, dim3(nt + gc_blocks), dim3(256), 0, c->stream, c->mm_mask, nchunks, n, c->mm_tile_off,
                        count_in_compact ? c->mm_tile_cnt : (const uint32_t*)nullptr, nt, c->mm_count, c->mm_count_host_dev, c->mm_total, A, B,
-                       c->mm_M64, mk, mi, table_live ? c->cells : (uint2*)nullptr, c->keyS, gc[0], gc[1], gc[2], gc[3]);
+                       c->mm_M64, mk, mi, table_live ? c->table.cells : (uint2*)nullptr, c->keyS, gc[0], gc[1], gc[2], gc[3]);
     SPH_HIP(hipGetLastError());
     SmallTail tail;
     int form = SORT_FORM_BOTH;
@@ -1323,7 +1341,7 @@ static int launch_sort_merge(sph_ctx* c, uint32_t n, uint32_t n_tot, bool table_
     hipLaunchKernelGGL(k_mm_move, dim3(place_blocks + ceil_div(n, 256)), dim3(256), 0, c->stream, place_blocks,
                        count_in_compact ? c->mm_tile_cnt : (uint32_t*)nullptr, nt, A, n, nchunks,
                        c->mm_mask, c->mm_M64, mk, mi, c->mm_count, c->mm_tileL, c->mm_tileA,
-                       table_live ? c->cells : (const uint2*)nullptr, c->own_off, ps, vs, po, vo, ko, perm, front);
+                       table_live ? c->table.cells : (const uint2*)nullptr, c->own_off, ps, vs, po, vo, ko, perm, front);
     SPH_HIP(hipGetLastError());
     c->last_perm = perm;
     return SPH_OK;
@@ -1350,106 +1368,112 @@ static int sort_throttle(sph_ctx* c) {
     return SPH_OK;
 }
 
-int launch_sort(sph_ctx* c) {
+// Nothing moved last time (a fluid at rest: no particle crosses a cell face for many steps).  If that is still so, the
+// order, the keys and the cell table are already those of this step and the whole sort -- 0.25 ms of copying at C3 -- can
+// be left out.  Only the device knows, and the host does not wait for it: the count is looked at only if the device has
+// ALREADY produced it (it is queued at the end of the previous step, so a caller in lockstep with the device -- one
+// update() per frame -- finds it); a host that runs ahead of the device queues the merge, which does the same job for 0
+// movers.  sph_step stays asynchronous.  Returns whether the sort was skipped (`rc`: how that went).
+static bool sort_skip_if_still(sph_ctx* c, bool was_still, TableLeft left, bool count_in_compact, int* rc) {
+    if (!(was_still && left != TableLeft::NOTHING && c->own_off == c->gcap && !count_in_compact && mm_counted_none(c))) return false;
+    c->sort_merges++;
+    c->sort_skips++;
+    c->last_sort_skipped = true;
+    c->last_perm = nullptr;            // identity
+    c->order_valid = true;             // the table of the owned slots: unchanged and still true
+    // the old ghosts' cells a slab step's hash left to this sort: no k_mm_compact to clear them, so with the kernel
+    *rc = left == TableLeft::OWNED_AND_GHOSTS ? table_drop_ghosts(c) : SPH_OK;
+    return true;
+}
+
+// the merge: the movers are sorted by themselves and merged into the order of the last sort (launch_sort_merge)
+static int sort_by_merge(sph_ctx* c, uint32_t n, TableLeft left, bool count_in_compact) {
+    const bool table_live = left != TableLeft::NOTHING;
+    // the old ghosts' cells, left by the hash of a slab step: spare blocks of k_mm_compact clear them
+    int rc = launch_sort_merge(c, n, n, table_live, *c->mm_count_host, Front{0u, 0u}, count_in_compact,   // hint: whatever step last reported
+                               left == TableLeft::OWNED_AND_GHOSTS);
+    if (rc) return rc;
+    c->sort_merges++;
+    if (c->table.valid && !table_live) rc = launch_cells_clear(c);   // a table nobody cleared (e.g. sph_sort without sph_hash): start clean
+    return rc;
+}
+
+// the full, stable radix sort of all owned particles
+static int sort_full(sph_ctx* c, uint32_t n, bool can_merge) {
+    if (c->table.valid) {                          // live or not: the full sort rebuilds the table from nothing (a table range
+        int rc = launch_cells_clear(c);            // that still holds the old ghosts is cleared with them)
+        if (rc) return rc;
+    }
+    // keep the hint alive, or it would stay high for ever: for free when the integrate epilogue marked
+    // the movers (the scan also re-zeroes the tile counts those marks added to), else every 8th sort
+    if (c->marks.marked) {
+        mm_drop_marks(c, true);
+    } else if (can_merge && (c->sort_calls & 7u) == 0) {
+        launch_mm_mark(c, n);
+        mm_tilescan(c, n, true);
+        SPH_HIP(hipGetLastError());
+    }
+    uint32_t* kin = c->k0; uint32_t* vin = c->v0;
+    uint32_t* kout = c->k1; uint32_t* vout = c->v1;
+    int rc = radix_sort_pairs(c, n, nullptr, ceil_div(n, SORT_TILE), true, kin, vin, kout, vout);
+    if (rc) return rc;
+    // (kin, vin) now hold the sorted pairs; gather the payload to the canonical offset gcap
+    hipLaunchKernelGGL(k_reorder, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, kin, vin, n, c->posi + c->own_off,
+                       c->velr + c->own_off, c->posi2 + c->gcap, c->velr2 + c->gcap, c->keyS2 + c->gcap);
+    SPH_HIP(hipGetLastError());
+    c->last_perm = vin;
+    return SPH_OK;
+}
+
+// what every sort that ran ends with: the new order is the state, and the cell table of the owned slots follows from
+// boundary flags on the new keys (no atomics, no scan, no host sync) -- built here, or, `owned_build_pending`, by the caller.
+// A slab context adds the cells of its ghost layers later (launch_cells_build), and drops those of the particles that leave
+// (table_drop_ends).
+static int sort_finish(sph_ctx* c, uint32_t n, bool* owned_build_pending) {
+    swap_state(c, true);
+    table_forget(c);
+    if (++c->sort_seq_issued == 0u) c->sort_seq_issued = 1u;       // the table build echoes the sort's number (sort_throttle)
+    if (owned_build_pending) {
+        *owned_build_pending = true;               // the slab step's bounds kernel, queued next, builds it (sph_slab.hip)
+    } else {
+        int rc = launch_cells_build_range(c, c->gcap, c->gcap + n, c->sort_seq_issued);
+        if (rc) return rc;
+    }
+    c->order_valid = true;
+    table_set(c, c->gcap, c->gcap + n);
+    return SPH_OK;
+}
+
+int launch_sort(sph_ctx* c, bool* owned_build_pending) {
+    if (owned_build_pending) *owned_build_pending = false;
     const uint32_t n = c->n;
     if (n == 0) return SPH_OK;
     const uint32_t nblocks = ceil_div(n, SORT_TILE);
     SPH_REQUIRE(nblocks <= c->sort_blocks_cap, SPH_E_CAPACITY, "sort: %u blocks > capacity %u", nblocks,
                 c->sort_blocks_cap);
-    // The merge needs the order of the last sort to be intact; it is correct for any number of movers but
-    // only cheaper than the full sort while they are few (last known count: a hint, never a condition).
     // The mover count the host reads below is whatever the device last reported.  A caller that queues many
     // steps without synchronising would decide all of them on one stale value, so the host never runs more
     // than four sorts ahead of the device (the queue stays several steps deep: the device never waits).
     if (c->sort_merge && !c->host_paced) { const int rc = sort_throttle(c); if (rc) return rc; }
     c->sort_calls++;
     c->last_sort_skipped = false;
+    // The merge needs the order of the last sort to be intact; it is correct for any number of movers but
+    // only cheaper than the full sort while they are few (last known count: a hint, never a condition).
     const bool can_merge = c->sort_merge && c->order_valid;
-    // whole-domain contexts: sph_hash left the old cell table in place (cells_clear_deferred) when this
-    // sort could take the merge path, which clears only the cells the movers left
-    const bool table_live = c->cells_clear_deferred && c->cells_valid;
-    c->cells_clear_deferred = false;
-    // the old ghosts' cells, left by the hash of a slab step (sph_ctx::defer_ghost_clear): spare blocks of k_mm_compact clear
-    // them when this sort merges; a sort that is skipped does it with the kernel; the full sort clears the whole table range,
-    // which still includes them
-    const bool ghosts_left = c->ghost_clear_pending && table_live;
-    c->ghost_clear_pending = false;
+    // sph_hash left the old cell table in place when this sort could take the merge path, which clears only the cells the
+    // movers left -- and, in a slab step, those of the old ghosts
+    const TableLeft left = table_take_left(c);
+    int rc;
     if (can_merge && (*c->mm_count_host <= n / 8u || c->sort_merge_always)) {
         const bool was_still = *c->mm_count_host == 0u;
         const bool count_in_compact = launch_merge_count(c, n);
-        if (was_still && table_live && c->own_off == c->gcap && !count_in_compact) {
-            // Nothing moved last time (a fluid at rest: no particle crosses a cell face for many steps).  If that
-            // is still so, the order, the keys and the cell table are already those of this step and the whole
-            // sort -- 0.25 ms of copying at C3 -- can be left out.  Only the device knows, and the host does not
-            // wait for it: the count is looked at only if the device has ALREADY produced it (it is queued at the
-            // end of the previous step, so a caller in lockstep with the device -- one update() per frame --
-            // finds it); a host that runs ahead of the device queues the merge, which does the same job for 0
-            // movers.  sph_step stays asynchronous.
-            volatile const uint32_t* hw = c->mm_count_host;
-            if (c->mm_counted_valid && hw[4] == c->scan_seq_issued && (std::atomic_thread_fence(std::memory_order_acquire), hw[0] == 0u)) {
-                c->sort_merges++;
-                c->sort_skips++;
-                c->last_sort_skipped = true;
-                c->last_perm = nullptr;            // identity
-                c->order_valid = true;             // cells_valid / cells_lo / cells_hi: unchanged and still true
-                if (ghosts_left) {
-                    const int rc2 = launch_cells_clear_2ranges(c, c->ghost_clear[0], c->ghost_clear[1], c->ghost_clear[2], c->ghost_clear[3]);
-                    if (rc2) return rc2;
-                    c->cells_lo = c->own_off; c->cells_hi = c->own_off + n;
-                }
-                return SPH_OK;
-            }
-        }
-        int rc = launch_sort_merge(c, n, n, table_live, *c->mm_count_host, Front{0u, 0u}, count_in_compact,   // hint: whatever step last reported
-                                   ghosts_left ? c->ghost_clear : (const uint32_t*)nullptr);
-        if (rc) return rc;
-        c->sort_merges++;
-        if (c->cells_valid && !table_live) {       // a table nobody cleared (e.g. sph_sort without sph_hash): start clean
-            rc = launch_cells_clear(c);
-            if (rc) return rc;
-        }
+        if (sort_skip_if_still(c, was_still, left, count_in_compact, &rc)) return rc;
+        rc = sort_by_merge(c, n, left, count_in_compact);
     } else {
-        if (c->cells_valid) {                      // live or not: the full sort rebuilds the table from nothing
-            int rc = launch_cells_clear(c);
-            if (rc) return rc;
-        }
-        // keep the hint alive, or it would stay high for ever: for free when the integrate epilogue marked
-        // the movers (the scan also re-zeroes the tile counts those marks added to), else every 8th sort
-        if (c->mm_marked) {
-            mm_drop_marks(c, true);
-        } else if (can_merge && (c->sort_calls & 7u) == 0) {
-            hipLaunchKernelGGL(k_mm_mark, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, c->keyS + c->own_off, c->k0, n,
-                               c->mm_mask, c->mm_tile_cnt);
-            mm_tilescan(c, n, true);
-            SPH_HIP(hipGetLastError());
-        }
-        uint32_t* kin = c->k0; uint32_t* vin = c->v0;
-        uint32_t* kout = c->k1; uint32_t* vout = c->v1;
-        int rc = radix_sort_pairs(c, n, nullptr, nblocks, true, kin, vin, kout, vout);
-        if (rc) return rc;
-        // (kin, vin) now hold the sorted pairs; gather the payload to the canonical offset gcap
-        hipLaunchKernelGGL(k_reorder, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, kin, vin, n, c->posi + c->own_off,
-                           c->velr + c->own_off, c->posi2 + c->gcap, c->velr2 + c->gcap, c->keyS2 + c->gcap);
-        SPH_HIP(hipGetLastError());
-        c->last_perm = vin;
+        rc = sort_full(c, n, can_merge);
     }
-    swap_state(c, true);
-    // the cell table of the owned slots from boundary flags on the new keys (no atomics, no scan, no host sync).
-    // A slab context adds the cells of its ghost layers later (launch_cells_build), and drops those of the
-    // particles that leave (sph_migrants_pack).
-    c->cells_valid = false;
-    if (++c->sort_seq_issued == 0u) c->sort_seq_issued = 1u;       // the table build echoes the sort's number (sort_throttle)
-    c->cells_seq_next = c->sort_seq_issued;
-    if (c->owned_cells_in_bounds) {
-        c->owned_cells_pending = true;             // the slab step's bounds kernel, queued next, builds it (sph_slab.hip)
-        c->cells_seq_next = 0u;
-    } else {
-        int rc = launch_cells_build_range(c, c->gcap, c->gcap + n);
-        if (rc) return rc;
-    }
-    c->order_valid = true;
-    set_table(c, c->gcap, c->gcap + n);
-    return SPH_OK;
+    if (rc) return rc;
+    return sort_finish(c, n, owned_build_pending);
 }
 
 // `n_in` particles were appended behind the SORTED owned range (positions, velocities and their new keys in
@@ -1473,10 +1497,10 @@ int launch_merge_arrivals(sph_ctx* c, uint32_t n_in, uint32_t n_front) {
     if (rc) return rc;
     swap_state(c, true);
     c->n = n_tot;
-    c->cells_valid = false;
+    table_forget(c);
     rc = launch_cells_build_range(c, c->gcap, c->gcap + n_tot);
     if (rc) return rc;
-    set_table(c, c->gcap, c->gcap + n_tot);
+    table_set(c, c->gcap, c->gcap + n_tot);
     c->order_valid = true;
     c->keys_fresh = false;
     c->n_glo = c->n_ghi = 0;

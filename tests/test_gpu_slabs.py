@@ -104,6 +104,55 @@ def test_slabs_with_migration_match_whole_domain(case, world, transport):
     _same_bits(st, ref)
 
 
+def test_slab_at_rest_skips_its_sort_and_matches():
+    """A slab at rest skips its sort like a whole-domain context does (sph_sort.hip: sort_skip_if_still).  Its hash has left the
+    cells of the old ghosts to that sort, which then has no k_mm_compact to clear them in: the skip clears them with a kernel
+    of its own, the one place where that happens.  Three slabs (the middle one has ghosts on both sides), the block of
+    make_case with no velocity field, one step per call with a sync in between -- a host in lockstep with the device, which is
+    what a skip needs; then a kick through set_by_index on slabs and whole-domain twin alike, and six steps of flow: 0.036 in
+    all, more than the lattice's layer spacing of half a cell (0.03125), so a layer crosses every cut inside the fluid and there
+    are migrants.  A ghost cell the skip forgot, or cleared wrongly, shows in the bits."""
+    pos, vel, box, grid = make_case("at rest")                 # (any name but a flow's: the lattice with zero velocities)
+    kick = vel.copy()
+    kick[:, 2] = 12000.0
+    world, rest_steps, flow_steps = 3, 12, 6
+    hub, dev_hub = slab.LocalComm.Hub(world), capi.LocalHub(world, timeout_s=60)
+    results, errors = [None] * world, []
+
+    def rank_main(r):
+        try:
+            sim = slab.NativeSlabSimulation(_comm(hub, dev_hub, r), box, grid, device_index=0, transport="local", particles=(pos, vel))
+            for _ in range(rest_steps):
+                sim.run(DT, 1)
+                sim.sync()
+            skips = sim.engine.ctx.sort_stats()["skips"]
+            sim.engine.ctx.set_by_index(0, vel=kick)
+            for _ in range(flow_steps):
+                sim.run(DT, 1)
+                sim.sync()
+            results[r] = (sim.gather_state(), skips, dict(sim.stats))
+            sim.close()
+        except BaseException as e:     # noqa: BLE001
+            errors.append(e)
+            hub.bar.abort()
+
+    threads = [threading.Thread(target=rank_main, args=(r,)) for r in range(world)]
+    for t in threads: t.start()
+    for t in threads: t.join(timeout=300)
+    dev_hub.close()
+    assert not errors, errors
+    with capi.Context(pos.shape[0], box=box, grid=grid) as c:
+        c.upload(pos, vel)
+        c.step(DT, rest_steps)
+        c.set_by_index(0, vel=kick)
+        c.step(DT, flow_steps)
+        ref = c.download()
+    print("skips per rank", [r[1] for r in results], "migrants", [r[2]["migrants"] for r in results])
+    assert results[1][1] > 0, "the middle slab never skipped a sort"
+    assert sum(r[2]["migrants"] for r in results) > 0
+    _same_bits(results[0][0], ref)
+
+
 @pytest.mark.parametrize("case,world,transport", [("up", 3, "local"), ("shear", 3, "local"), ("down", 3, "local"), ("up", 3, "host"),
                                                   ("tall_up", 2, "local"), ("tall_up", 2, "host")])
 def test_one_message_step_matches_whole_domain_bit_for_bit(case, world, transport):
