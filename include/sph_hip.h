@@ -679,6 +679,9 @@ typedef struct sph_slab sph_slab;
 /* Bind a slab context (sph_create_slab, particles uploaded) to its place in the chain of `world` slabs.  The halo
  * capacity is the context's ghost capacity; migrant_capacity (records per side and step, 0 = half the ghost capacity)
  * bounds the leavers / arrivals of one step and side (only 255 of them ride in the fixed-size message of every step).  The transport struct is copied.
+ * A slab with a neighbour (world > 1) owns at least TWO cell layers, SPH_E_INVALID otherwise: its lowest and its highest layer are
+ * two different boundary layers.  Two is enough -- such a slab has no interior -- for the three-group protocol; the one-message
+ * step needs four (sph_slab_set_protocol, which refuses a thinner slab with SPH_E_STATE and leaves the slab as it was).
  * The step orders its streams by sequence numbers (hipStreamWriteValue32 / hipStreamWaitValue32 on a word of device memory) where the
  * device serves that pair -- tried once here, with both streams drained -- and by events otherwise; SPH_SLAB_HOPS=event in the
  * environment forces events (A/B runs, kernel traces: the runtime's wait is a spinning one-workgroup kernel). */
