@@ -183,6 +183,8 @@ SIGNATURES = {
     "sph_set_block_order": (C.c_int, [_P, C.c_int, C.c_int, C.c_uint32]),
     "sph_sort_forms": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "sph_test_trust_mover_hint": (C.c_int, [_P]),
+    "sph_memory_stats": (None, [C.POINTER(C.c_uint64)]),
+    "sph_test_fail_alloc": (None, [C.c_uint32]),
     "sph_set_precision": (C.c_int, [_P, C.c_int]),
     "sph_get_precision": (C.c_int, [_P]),
     "sph_migrants_count": (C.c_int, [_P, C.POINTER(_U32)]),
@@ -268,6 +270,18 @@ def _check(rc):
     if rc < 0:
         raise SphError(f"libsph_hip error {rc}: {load().sph_last_error().decode()}")
     return rc
+
+
+def memory_stats():
+    """Test hook: (live device bytes, live pinned bytes, live buffers) of this process's library."""
+    out = (C.c_uint64 * 3)()
+    load().sph_memory_stats(out)
+    return tuple(int(v) for v in out)
+
+
+def fail_alloc(k):
+    """Test hook: the k-th allocation from now fails with SPH_E_NOMEM, once; 0 disarms."""
+    load().sph_test_fail_alloc(int(k))
 
 
 def default_params(box, grid) -> Params:

@@ -99,47 +99,6 @@ static int derive(sph_ctx* c, const sph_params* p, uint32_t z_lo, uint32_t z_hi,
     return SPH_OK;
 }
 
-template <class T>
-static int dev_alloc(T** p, size_t count) {
-    *p = nullptr;
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc((void**)p, count * sizeof(T));
-    if (e != hipSuccess) {
-        set_error("hipMalloc of %zu bytes failed: %s", count * sizeof(T), hipGetErrorString(e));
-        return SPH_E_NOMEM;
-    }
-    return SPH_OK;
-}
-
-// an array that starts as zeros
-template <class T>
-static int dev_alloc_zero(T** p, size_t count) {
-    int rc = dev_alloc(p, count);
-    if (rc) return rc;
-    if (hipMemset(*p, 0, count * sizeof(T)) != hipSuccess) {
-        hipFree(*p);
-        *p = nullptr;
-        set_error("hipMemset of %zu bytes failed", count * sizeof(T));
-        return SPH_E_DEVICE;
-    }
-    return SPH_OK;
-}
-
-// every array create_impl allocates (keep the two lists in step)
-static void free_all(sph_ctx* c) {
-    hipFree(c->posi); hipFree(c->velr); hipFree(c->posi2); hipFree(c->velr2); hipFree(c->keyS); hipFree(c->dp); hipFree(c->cw);
-    hipFree(c->fpress); hipFree(c->fvisc); hipFree(c->dvel); hipFree(c->pos_out); hipFree(c->table.base);
-    hipFree(c->k0); hipFree(c->v0); hipFree(c->k1); hipFree(c->v1); hipFree(c->os_hist); hipFree(c->os_base); hipFree(c->os_tickets); hipFree(c->os_tot); hipFree(c->os_status); hipFree(c->os_status32); hipFree(c->keyS2); hipFree(c->mm_tileL); hipFree(c->mm_tileA);
-    if (c->os_err_host) hipHostFree(c->os_err_host);
-    hipFree(c->d_scratch);
-    hipFree(c->mm_mask); hipFree(c->mm_M64); hipFree(c->mm_tile_cnt); hipFree(c->mm_tile_off);
-    hipFree(c->mm_k0); hipFree(c->mm_k1); hipFree(c->mm_v1); hipFree(c->mm_count); hipFree(c->mm_total);
-    if (c->mm_count_host) hipHostFree(c->mm_count_host);
-    if (c->h_scratch) hipHostFree(c->h_scratch);
-    hipFree(c->trk_table); hipFree(c->trk_partial); hipFree(c->trk_mask); hipFree(c->trk_J);   // (sph_set_collider_bodies)
-    render_release(c);   // (sph_render)
-}
-
 static int create_impl(sph_ctx** out, int device, uint32_t capacity, const sph_params* p, uint32_t z_lo, uint32_t z_hi,
                        uint32_t gcap, bool slab, uint32_t ghost_layers = 1) {
     SPH_REQUIRE(out && p, SPH_E_INVALID, "null argument");
@@ -168,52 +127,29 @@ static int create_impl(sph_ctx** out, int device, uint32_t capacity, const sph_p
     if (rc) { delete c; return rc; }
     c->cap = capacity; c->gcap = gcap; c->tot = capacity + 2 * gcap; c->slab = slab;
     c->own_off = gcap;
-    c->sort_blocks_cap = ceil_div(capacity, SORT_TILE_KEYS) + 1;
     c->pos_out_cap = slab ? 0 : capacity;
-    // The arrays: every one of them is in free_all's list as well.  dev_alloc_zero for those a kernel may read before any
-    // kernel wrote them (padding slots, look-back words, tickets, counts); the others are written first.
-    // + 2*PIECE entries: the pair kernels stage whole 128-entry pieces without bounds predicates
+    // The particle arrays, `tot` slots + 2*PIECE: the pair kernels stage whole 128-entry pieces without bounds predicates.
+    // Zeroed where a kernel may read a slot before any kernel wrote it (the padding slots of the state and of its ping-pong,
+    // the keys, and dp / cw, whose zeros make padding neighbours contribute nothing) ...
+    Buffers& m = c->mem;
     const size_t tot = (size_t)c->tot + 256;
-    rc = dev_alloc_zero(&c->posi, tot);
-    if (!rc) rc = dev_alloc_zero(&c->velr, tot);
-    if (!rc) rc = dev_alloc_zero(&c->posi2, tot);
-    if (!rc) rc = dev_alloc_zero(&c->velr2, tot);
-    if (!rc) rc = dev_alloc_zero(&c->keyS, tot);
-    if (!rc) rc = dev_alloc_zero(&c->keyS2, tot);
-    if (!rc) rc = dev_alloc_zero(&c->dp, tot);
-    if (!rc) rc = dev_alloc_zero(&c->cw, tot);
-    if (!rc) rc = dev_alloc(&c->fpress, tot);
-    if (!rc) rc = dev_alloc(&c->fvisc, tot);
-    if (!rc) rc = dev_alloc(&c->dvel, tot);
-    if (!rc) rc = dev_alloc(&c->pos_out, (size_t)c->pos_out_cap);
-    // one guard entry on either side: the pair kernels read cells[key - 1 .. key + 1] of a row unconditionally
-    if (!rc) rc = dev_alloc_zero(&c->table.base, (size_t)c->grid.ncells + 2);
+    rc = m.alloc(&c->posi, tot, true);
+    if (!rc) rc = m.alloc(&c->velr, tot, true);
+    if (!rc) rc = m.alloc(&c->posi2, tot, true);
+    if (!rc) rc = m.alloc(&c->velr2, tot, true);
+    if (!rc) rc = m.alloc(&c->keyS, tot, true);
+    if (!rc) rc = m.alloc(&c->keyS2, tot, true);
+    if (!rc) rc = m.alloc(&c->dp, tot, true);
+    if (!rc) rc = m.alloc(&c->cw, tot, true);
+    // ... and not where the kernel that owns the array writes every slot it later reads: the phase outputs, positions by index
+    if (!rc) rc = m.alloc(&c->fpress, tot, false);
+    if (!rc) rc = m.alloc(&c->fvisc, tot, false);
+    if (!rc) rc = m.alloc(&c->dvel, tot, false);
+    if (!rc) rc = m.alloc(&c->pos_out, (size_t)c->pos_out_cap, false);
+    // the cell table, zero = empty, one guard entry on either side: the pair kernels read cells[key - 1 .. key + 1] of a row unconditionally
+    if (!rc) rc = m.alloc(&c->table.base, (size_t)c->grid.ncells + 2, true);
     if (!rc) table_init(c, c->table.base, c->grid.ncells);
-    if (!rc) rc = dev_alloc(&c->k0, (size_t)capacity);
-    if (!rc) rc = dev_alloc(&c->v0, (size_t)capacity);
-    if (!rc) rc = dev_alloc(&c->k1, (size_t)capacity);
-    if (!rc) rc = dev_alloc(&c->v1, (size_t)capacity);
-    const size_t os_groups = (size_t)c->sort_blocks_cap / 4 + 3;   // enough for groups of >= 4 tiles
-    c->os_groups_cap = (uint32_t)os_groups;
-    if (!rc) rc = dev_alloc_zero(&c->os_hist, os_groups * 4 * 512);
-    if (!rc) rc = dev_alloc(&c->os_base, os_groups * 4 * 512);
-    if (!rc) rc = dev_alloc_zero(&c->os_tickets, (size_t)4 * os_groups);
-    if (!rc) rc = dev_alloc(&c->os_tot, (size_t)4 * 512);
-    if (!rc) rc = dev_alloc_zero(&c->os_status, (size_t)512 * c->sort_blocks_cap);
-    if (!rc) rc = dev_alloc_zero(&c->os_status32, (size_t)512 * c->sort_blocks_cap);
-    if (!rc) rc = dev_alloc(&c->mm_tileL, (size_t)c->sort_blocks_cap + 2);
-    if (!rc) rc = dev_alloc(&c->mm_tileA, (size_t)c->sort_blocks_cap + 2);
-    if (!rc && (hipHostMalloc((void**)&c->os_err_host, sizeof(uint32_t), hipHostMallocMapped) != hipSuccess ||
-                hipHostGetDevicePointer((void**)&c->os_err_dev, c->os_err_host, 0) != hipSuccess)) {
-        set_error("hipHostMalloc(mapped) failed");
-        rc = SPH_E_NOMEM;
-    }
-    if (!rc) *c->os_err_host = 0;
-    if (!rc) rc = dev_alloc(&c->d_scratch, (size_t)64);
-    if (!rc && hipHostMalloc((void**)&c->h_scratch, 64 * sizeof(uint32_t)) != hipSuccess) {
-        set_error("hipHostMalloc failed");
-        rc = SPH_E_NOMEM;
-    }
+    if (!rc) rc = sort_buffers_alloc(c);
     if (const char* env = getenv("SPH_BLOCK_ORDER")) {          // "xcd,ztile,strip_log2" at create time: A/B runs (sph_set_block_order)
         int x = 1, z = 1, sh = 4, zd = 1, xr = 1;
         if (sscanf(env, "%d,%d,%d,%d,%d", &x, &z, &sh, &zd, &xr) >= 1) {
@@ -225,31 +161,7 @@ static int create_impl(sph_ctx** out, int device, uint32_t capacity, const sph_p
         unsigned long v = 0;
         if (sscanf(env, "%lu", &v) == 1) c->pair_small_slots = v > 0xFFFFFFFFul ? 0xFFFFFFFFu : (uint32_t)v;
     }
-    {   // merge sort scratch
-        const char* env = getenv("SPH_SORT_MERGE");
-        c->sort_merge = !(env && env[0] == '0');
-        const size_t nchunks = (size_t)ceil_div(capacity, 64u) + 1, ntiles = nchunks / 256 + 2;
-        if (!rc) rc = dev_alloc(&c->mm_mask, nchunks);
-        if (!rc) rc = dev_alloc(&c->mm_M64, nchunks);
-        if (!rc) rc = dev_alloc_zero(&c->mm_tile_cnt, ntiles);
-        if (!rc) rc = dev_alloc(&c->mm_tile_off, ntiles);
-        if (!rc) rc = dev_alloc(&c->mm_k0, (size_t)capacity);
-        if (!rc) rc = dev_alloc(&c->mm_k1, (size_t)capacity);
-        if (!rc) rc = dev_alloc(&c->mm_v1, (size_t)capacity);
-        if (!rc) rc = dev_alloc_zero(&c->mm_count, (size_t)1);
-        if (!rc) rc = dev_alloc_zero(&c->mm_total, (size_t)1);
-        if (!rc && (hipHostMalloc((void**)&c->mm_count_host, 8 * sizeof(uint32_t), hipHostMallocMapped) != hipSuccess ||
-                    hipHostGetDevicePointer((void**)&c->mm_count_host_dev, c->mm_count_host, 0) != hipSuccess)) {
-            set_error("hipHostMalloc(mapped) failed");
-            rc = SPH_E_NOMEM;
-        }
-        if (!rc) {
-            c->mm_count_host[0] = 0;
-            c->mm_count_host[1] = 1; c->mm_count_host[2] = 0;          // "no estimate yet" (first key > last key)
-            for (int k = 3; k < 8; k++) c->mm_count_host[k] = 0;
-        }
-    }
-    if (rc) { free_all(c); delete c; return rc; }
+    if (rc) { m.free_all(); delete c; return rc; }
     *out = c;
     return SPH_OK;
 }
@@ -329,10 +241,10 @@ int set_slab_range(sph_ctx* c, uint32_t z_lo, uint32_t z_hi) {
     if (rc) return rc;
     if (tmp.grid.ncells > c->table.alloc) {
         SPH_HIP(hipStreamSynchronize(c->stream));
-        uint2* base = nullptr;
-        rc = dev_alloc_zero(&base, (size_t)tmp.grid.ncells + 2);
+        uint2* base = nullptr;                  // the larger table first: a failure leaves the context as it was
+        rc = c->mem.alloc(&base, (size_t)tmp.grid.ncells + 2, true);
         if (rc) return rc;
-        hipFree(c->table.base);
+        c->mem.release(&c->table.base);
         table_init(c, base, tmp.grid.ncells);
     }
     c->grid = tmp.grid; c->z_lo = z_lo; c->z_hi = z_hi; c->key_bits = tmp.key_bits;
@@ -496,7 +408,7 @@ void sph_destroy(sph_ctx* c) {
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
     timing_collect(c);
-    free_all(c);
+    c->mem.free_all();
     delete c;
 }
 
@@ -563,8 +475,9 @@ int sph_set_by_index(sph_ctx* c, uint32_t first_index, uint32_t count, const flo
     float* d_pos = nullptr; float* d_vel = nullptr;
     const size_t bytes = (size_t)count * 3 * sizeof(float);
     int rc = SPH_OK;
-    if (pos_xyz) rc = dev_alloc(&d_pos, (size_t)count * 3);
-    if (!rc && vel_xyz) rc = dev_alloc(&d_vel, (size_t)count * 3);
+    Buffers tmp;
+    if (pos_xyz) rc = tmp.alloc(&d_pos, (size_t)count * 3, false);
+    if (!rc && vel_xyz) rc = tmp.alloc(&d_vel, (size_t)count * 3, false);
     if (!rc) {
         hipError_t e = hipSuccess;
         if (pos_xyz) e = hipMemcpyAsync(d_pos, pos_xyz, bytes, hipMemcpyHostToDevice, c->stream);
@@ -578,7 +491,7 @@ int sph_set_by_index(sph_ctx* c, uint32_t first_index, uint32_t count, const flo
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);        // the host buffers may go away now
         if (e != hipSuccess) { set_error("sph_set_by_index: %s", hipGetErrorString(e)); rc = SPH_E_DEVICE; }
     }
-    hipFree(d_pos); hipFree(d_vel);
+    tmp.free_all();
     if (rc) return rc;
     // positions moved under the keys: hash again; the slots still follow the last sort (order_valid stays)
     mm_drop_marks(c);
@@ -830,14 +743,8 @@ int sph_set_collider_bodies(sph_ctx* c, uint32_t n, const sph_collider_body* bod
     }
     SPH_HIP(hipSetDevice(c->device));
     if (!c->trk_table) {             // first use: buffers by capacity
-        const size_t waves = ceil_div(c->cap, 64u);
-        Spheres* table = nullptr; double* partial = nullptr; uint32_t* mask = nullptr; double* J = nullptr;
-        int rc = dev_alloc_zero(&table, 1);
-        if (!rc) rc = dev_alloc(&partial, waves * SPH_MAX_COLLIDERS * 3);
-        if (!rc) rc = dev_alloc_zero(&mask, ((waves + 3) & ~(size_t)3) + 4);
-        if (!rc) rc = dev_alloc_zero(&J, SPH_MAX_COLLIDERS * 3 + 1);
-        if (rc) { hipFree(table); hipFree(partial); hipFree(mask); hipFree(J); return rc; }
-        c->trk_table = table; c->trk_partial = partial; c->trk_mask = mask; c->trk_J = J;
+        int rc = tracked_buffers_alloc(c);
+        if (rc) return rc;
     }
     SphereBodies b{};
     for (uint32_t j = 0; j < n; j++) {
@@ -930,8 +837,9 @@ int sph_get_cells(sph_ctx* c, uint32_t max_cells, uint32_t* key, uint32_t* start
     const uint32_t m = (uint32_t)uniq.size(), take = m < max_cells ? m : max_cells;
     if (take) {                                         // one gather on the device, one copy back
         uint32_t* d_keys = nullptr; uint2* d_out = nullptr;
-        int rc = dev_alloc(&d_keys, (size_t)take);
-        if (!rc) rc = dev_alloc(&d_out, (size_t)take);
+        Buffers tmp;
+        int rc = tmp.alloc(&d_keys, (size_t)take, false);
+        if (!rc) rc = tmp.alloc(&d_out, (size_t)take, false);
         std::vector<uint2> got(take);
         if (!rc) {
             hipError_t e = hipMemcpy(d_keys, uniq.data(), take * sizeof(uint32_t), hipMemcpyHostToDevice);
@@ -944,7 +852,7 @@ int sph_get_cells(sph_ctx* c, uint32_t max_cells, uint32_t* key, uint32_t* start
             if (e == hipSuccess) e = hipMemcpy(got.data(), d_out, take * sizeof(uint2), hipMemcpyDeviceToHost);
             if (e != hipSuccess) { set_error("sph_get_cells: %s", hipGetErrorString(e)); rc = SPH_E_DEVICE; }
         }
-        hipFree(d_keys); hipFree(d_out);
+        tmp.free_all();
         if (rc) return rc;
         for (uint32_t k = 0; k < take; k++) {
             if (key) key[k] = uniq[k];
@@ -1158,8 +1066,16 @@ int sph_sort_stats(sph_ctx* c, uint64_t* sorts, uint64_t* merges, uint64_t* skip
     if (sorts) *sorts = c->sort_calls;
     if (merges) *merges = c->sort_merges;
     if (skips) *skips = c->sort_skips;
-    if (last_movers) *last_movers = *c->mm_count_host;
+    if (last_movers) *last_movers = c->mm_count_host[HW_MOVERS];
     return SPH_OK;
 }
+
+// [test hook] what the library's owners (sph::Buffers) hold in this process right now
+void sph_memory_stats(uint64_t out[3]) {
+    if (out) for (int k = 0; k < 3; k++) out[k] = g_mem_stats[k].load();
+}
+
+// [test hook] the k-th allocation from now returns SPH_E_NOMEM without calling HIP, once; 0 disarms
+void sph_test_fail_alloc(uint32_t k) { g_fail_alloc.store(k); }
 
 }  // extern "C"

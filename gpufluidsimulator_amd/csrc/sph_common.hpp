@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -24,6 +25,7 @@ constexpr uint32_t SORT_TILE_KEYS = 256 * SPH_SORT_KPT;   // keys per radix-sort
 #define SPH_PAIR_SMALL_SLOTS_DEFAULT 524288u
 #endif
 constexpr uint32_t MM_TILE_CHUNKS = 256;   // merge sort: 64-slot chunks per scan tile (sph_sort.hip)
+constexpr uint32_t SCRATCH_WORDS = 64;     // words of a context's d_scratch / h_scratch pair (counts; sph_halo.hip splits it in halves)
 
 // Grid description passed by value to kernels (replaces the device-resident SimParams*
 // every reference kernel dereferences, particleSystem.cu:93-103,127-130).
@@ -82,6 +84,70 @@ struct SphereBodies {
 
 constexpr uint32_t SPHERES_STEP_THREADS = 256;   // k_spheres_step: one block (sph_pairs.hip)
 
+void set_error(const char* fmt, ...);
+
+// ---- device and pinned memory: one owner per object ----
+// A Buffers allocates, remembers and frees: sph_ctx, sph_slab, the compat seam's scratch and every call with temporaries hold one.
+// free_all frees what is left in reverse order of allocation -- the owner's destroy calls it; there is no destructor, so that
+// nothing is freed while the process exits -- and release frees one buffer early (an image that changes size, a table that
+// grows).  The four HIP allocation calls appear nowhere else in the library.
+inline std::atomic<uint64_t> g_mem_stats[3];   // live device bytes, live pinned bytes, live buffers (sph_memory_stats)
+inline std::atomic<uint32_t> g_fail_alloc{0};  // [test hook] sph_test_fail_alloc: the k-th allocation from now fails, once
+struct Buffers {
+    struct Rec { void* p; size_t bytes; bool pinned; };
+    std::vector<Rec> live;
+    Buffers() = default;
+    Buffers(const Buffers&) = delete;
+    Buffers& operator=(const Buffers&) = delete;
+    // `count` elements of device memory (0: one element), as zeros if `zero`
+    template <class T> int alloc(T** p, size_t count, bool zero) {
+        const size_t bytes = (count ? count : 1) * sizeof(T);
+        int rc = take((void**)p, bytes, false, false);
+        if (rc || !zero || hipMemset((void*)*p, 0, bytes) == hipSuccess) return rc;
+        release(p);
+        set_error("hipMemset of %zu bytes failed", bytes);
+        return SPH_E_DEVICE;
+    }
+    // pinned host memory; with `dev_view` it is mapped, and *dev_view is the device's pointer to it
+    template <class T> int alloc_host(T** p, size_t count, T** dev_view = nullptr) {
+        int rc = take((void**)p, count * sizeof(T), true, dev_view != nullptr);
+        if (rc || !dev_view || hipHostGetDevicePointer((void**)dev_view, (void*)*p, 0) == hipSuccess) return rc;
+        release(p);
+        set_error("hipHostGetDevicePointer failed");
+        return SPH_E_NOMEM;
+    }
+    template <class T> void release(T** p) {
+        for (size_t k = live.size(); k-- > 0;)
+            if (live[k].p == (void*)*p) { drop(live[k]); live.erase(live.begin() + k); break; }
+        *p = nullptr;
+    }
+    void free_all() {
+        while (!live.empty()) { drop(live.back()); live.pop_back(); }
+    }
+
+private:
+    int take(void** p, size_t bytes, bool pinned, bool mapped) {
+        const char* fn = !pinned ? "hipMalloc" : mapped ? "hipHostMalloc(mapped)" : "hipHostMalloc";
+        *p = nullptr;
+        uint32_t k = g_fail_alloc.load();
+        while (k && !g_fail_alloc.compare_exchange_weak(k, k - 1)) {}
+        const hipError_t e = k == 1 ? hipErrorOutOfMemory
+                           : pinned ? hipHostMalloc(p, bytes, mapped ? hipHostMallocMapped : hipHostMallocDefault) : hipMalloc(p, bytes);
+        if (e != hipSuccess) {
+            *p = nullptr;
+            set_error("%s of %zu bytes failed: %s", fn, bytes, hipGetErrorString(e));
+            return SPH_E_NOMEM;
+        }
+        live.push_back(Rec{*p, bytes, pinned});
+        g_mem_stats[pinned] += bytes; g_mem_stats[2] += 1;
+        return SPH_OK;
+    }
+    static void drop(const Rec& r) {
+        if (r.pinned) hipHostFree(r.p); else hipFree(r.p);
+        g_mem_stats[r.pinned] -= r.bytes; g_mem_stats[2] -= 1;
+    }
+};
+
 // What sph_hash leaves of the old cell table to the sort that follows it.  It lives in the context because the two are
 // separate public calls; launch_sort takes it (table_take_left), and clearing or forgetting the table resets it.
 enum class TableLeft : uint8_t {
@@ -112,12 +178,23 @@ struct MoverMarks {
     bool counted_valid = false;    // the last count queued (scan_seq) is that of the CURRENT marks
 };
 
+// The words of the mapped host block mm_count_host, which the device writes and the host only looks at (sph_ctx below).
+enum HostWord : uint32_t {
+    HW_MOVERS = 0,     // the last known mover count (a hint)
+    HW_FIRST_KEY,      // the keys of the first / last owned slot after the last table build (block_order's estimate):
+    HW_LAST_KEY,       // the two words cells_build_thread writes through `ends`
+    HW_BUILD_SEQ,      // the number of the last sort whose table build has started (sort_throttle)
+    HW_COUNT_SEQ,      // the number of the last mover count, stored AFTER the count itself (launch_sort's skip)
+    HW_WORDS = 8
+};
+
 }  // namespace sph
 
 // The opaque context of include/sph_hip.h.
 struct sph_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
+    sph::Buffers mem;        // every device and pinned buffer below (sph_destroy frees them all)
     sph_params params{};
     int precision = SPH_PRECISION_F32;   // sph_set_precision
     sph::GridDesc grid{};
@@ -239,8 +316,8 @@ struct sph_ctx {
     // What the host learns from the device about the sorts WITHOUT events (every event recorded on a stream costs the device
     // ~5.5 us of idle at its next dispatch; rounds 1-5 recorded two per step in a whole-domain context: 11 us of a 92 us step
     // at 131,072 particles, profiles/r06base_headless_n131072_kernel_stats.csv): the kernels echo sequence numbers into the
-    // mapped host block mm_count_host -- [3] the number of the last sort whose table build has started (bounds the host's
-    // run-ahead to four sorts), [4] the number of the last mover count, stored AFTER the count [0] (the skip of a sort with
+    // mapped host block mm_count_host -- HW_BUILD_SEQ the number of the last sort whose table build has started (bounds the host's
+    // run-ahead to four sorts), HW_COUNT_SEQ the number of the last mover count, stored AFTER the count HW_MOVERS (the skip of a sort with
     // nothing to do needs the count of the CURRENT marks: it is looked at, never waited for).
     uint32_t sort_seq_issued = 0;   // sorts that queued a table build so far
     uint64_t sort_merges = 0, sort_calls = 0, sort_skips = 0;   // skips: merges with no mover at all (nothing done)
@@ -256,9 +333,7 @@ struct sph_ctx {
     uint32_t* mm_tile_cnt = nullptr; uint32_t* mm_tile_off = nullptr;
     uint32_t* mm_k0 = nullptr; uint32_t* mm_k1 = nullptr; uint32_t* mm_v1 = nullptr;   // mover (key, slot) ping-pong (+ v0)
     uint32_t* mm_count = nullptr;           // movers of the current sort (device)
-    uint32_t* mm_count_host = nullptr;      // pinned, written by the device: [0] last known count (a hint), [1], [2] the keys of
-                                            // the first / last owned slot after the last table build (block_order's estimate),
-                                            // [3] / [4] sequence numbers of the last table build / the last count (above); 8 words
+    uint32_t* mm_count_host = nullptr;      // pinned, written by the device: the HW_WORDS words of sph::HostWord above
     uint32_t* mm_count_host_dev = nullptr;  // device view of the same word
     unsigned long long* mm_total = nullptr; // movers of all sorts so far (device; sph_sort_stats)
     sph::MoverMarks marks;          // the fused integrate epilogue already wrote mm_mask / mm_tile_cnt for a range
@@ -280,7 +355,6 @@ struct sph_ctx {
 
 namespace sph {
 
-void set_error(const char* fmt, ...);
 void mm_set_marks(sph_ctx* c);      // sph_sort.hip: the integrate epilogue has marked the movers of the owned range
 void mm_scan_marks(sph_ctx* c);     // ... count them now if the next sort could be skipped
 void mm_drop_marks(sph_ctx* c, bool counted = false);     // ... forget them
@@ -315,7 +389,7 @@ int table_drop_ghosts(sph_ctx* c);                    // a table over the owned 
 int table_leave_to_sort(sph_ctx* c, bool ghosts_too); // sph_hash: the table stays live for a merging sort (TableLeft)
 TableLeft table_take_left(sph_ctx* c);                // launch_sort: what the hash left, if the table is still there; taken once
 int launch_cells_clear_range(sph_ctx* c, uint32_t lo, uint32_t hi);
-// (`seq`: what a build over the whole owned range echoes into mm_count_host[3] -- the sort's number, sort_throttle)
+// (`seq`: what a build over the whole owned range echoes into mm_count_host[HW_BUILD_SEQ] -- the sort's number, sort_throttle)
 int launch_cells_build_range(sph_ctx* c, uint32_t lo, uint32_t hi, uint32_t seq = 0);
 int launch_cells_clear_2ranges(sph_ctx* c, uint32_t lo0, uint32_t hi0, uint32_t lo1, uint32_t hi1);
 int launch_cells_build_2ranges(sph_ctx* c, uint32_t lo0, uint32_t hi0, uint32_t lo1, uint32_t hi1);
@@ -346,7 +420,9 @@ int launch_integrate(sph_ctx* c, float dt);
 // tracked contexts (sph_pairs.hip): write the host's sphere set into trk_table and zero J and the step count; refresh R + eps
 int launch_spheres_install(sph_ctx* c);
 int launch_spheres_radii(sph_ctx* c);
-void render_release(sph_ctx* c);      // sph_render.hip: frees the image buffers (sph_destroy)
+// what each subsystem allocates in the context's owner, sized next to the kernels that index it
+int sort_buffers_alloc(sph_ctx* c);       // sph_sort.hip: the sorts' scratch and the mapped word block (create_impl)
+int tracked_buffers_alloc(sph_ctx* c);    // sph_pairs.hip: the table, partial sums and masks of a tracked context (first tracking)
 
 inline uint32_t ceil_div(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 

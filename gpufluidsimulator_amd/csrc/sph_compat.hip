@@ -23,6 +23,7 @@ using namespace sph;
 
 struct Compat {
     sph_ctx* ctx = nullptr;
+    Buffers mem;                            // the scratch below (release)
     uint32_t n = 0;
     sph_compat_particle* tmp = nullptr;     // scratch for the AoS permutation
     const uint32_t* perm = nullptr;
@@ -221,12 +222,7 @@ void configure(Compat& c, unsigned int n, const sph_compat_simparams* params_dev
         CK(sph_set_params(c.ctx, &q));       // box or radius changed between two updates
     } else {
         if (c.ctx) { sph_destroy(c.ctx); c.ctx = nullptr; }
-        if (c.tmp) { hipFree(c.tmp); c.tmp = nullptr; }
-        if (c.bp_cnt) { hipFree(c.bp_cnt); c.bp_cnt = nullptr; }
-        if (c.bp_off) { hipFree(c.bp_off); c.bp_off = nullptr; }
-        if (c.m2n) { hipFree(c.m2n); c.m2n = nullptr; }
-        if (c.scr0) { hipFree(c.scr0); c.scr0 = nullptr; }
-        if (c.scr1) { hipFree(c.scr1); c.scr1 = nullptr; }
+        c.mem.free_all();                    // the scratch of the old size (every pointer into it is set again below)
         if (h.gridDim > 1024u) {
             fprintf(stderr, "libsph_hip compat seam: gridDim %u > 1024: the reference's z-index holds 10 bits per axis "
                     "(particleSystem.cu:67)\n", h.gridDim);
@@ -234,14 +230,15 @@ void configure(Compat& c, unsigned int n, const sph_compat_simparams* params_dev
         }
         CK(sph_create(&c.ctx, -1, n ? n : 1, &q));      // -1: the device cudaInit / sph_select_device chose
         c.ctx->keep_perm = true;                        // cudaSortParticles moves the caller's structs by it
-        CKH(hipMalloc((void**)&c.tmp, (size_t)(n ? n : 1) * sizeof(sph_compat_particle)));
         const size_t nt = (size_t)ceil_div(n ? n : 1, 256u);
-        CKH(hipMalloc((void**)&c.bp_cnt, nt * sizeof(uint32_t)));
-        CKH(hipMalloc((void**)&c.bp_off, nt * sizeof(uint32_t)));
-        CKH(hipMalloc((void**)&c.m2n, (size_t)(n ? n : 1) * sizeof(uint32_t)));
-        CKH(hipMalloc((void**)&c.scr0, (size_t)(n ? n : 1) * sizeof(uint32_t)));
-        CKH(hipMalloc((void**)&c.scr1, (size_t)(n ? n : 1) * sizeof(uint32_t)));
-        if (!c.bp_total) CKH(hipHostMalloc((void**)&c.bp_total, sizeof(uint32_t), hipHostMallocMapped));
+        uint32_t* bp_total_dev = nullptr;               // (unused: the kernel writes through the host pointer)
+        CK(c.mem.alloc(&c.tmp, n, false));
+        CK(c.mem.alloc(&c.bp_cnt, nt, false));
+        CK(c.mem.alloc(&c.bp_off, nt, false));
+        CK(c.mem.alloc(&c.m2n, n, false));
+        CK(c.mem.alloc(&c.scr0, n, false));
+        CK(c.mem.alloc(&c.scr1, n, false));
+        CK(c.mem.alloc_host(&c.bp_total, 1, &bp_total_dev));
         c.n = n;
     }
     c.prm = h;
@@ -249,14 +246,7 @@ void configure(Compat& c, unsigned int n, const sph_compat_simparams* params_dev
 
 void release(Compat& c) {
     if (c.ctx) sph_destroy(c.ctx);
-    if (c.tmp) hipFree(c.tmp);
-    if (c.bp_cnt) hipFree(c.bp_cnt);
-    if (c.bp_off) hipFree(c.bp_off);
-    if (c.m2n) hipFree(c.m2n);
-    if (c.scr0) hipFree(c.scr0);
-    if (c.scr1) hipFree(c.scr1);
-    if (c.bp_total) hipHostFree(c.bp_total);
-    c = Compat();
+    c.mem.free_all();                        // (both callers erase the entry next)
 }
 
 Compat& lookup(const void* p, const char* who) {

@@ -96,15 +96,15 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
 //      step's bounds kernel runs the same build in its spare blocks, sph_slab.hip) ------------------------------------------------
 // Thread t of the build takes CELLS_SPT = 4 consecutive slots from lo + 4 t: six key reads for four slots instead of twelve, a
 // quarter of the threads (one slot per thread took 51 us for 16.7 M slots: far from any bandwidth).  No atomics: the first /
-// last slot of a cell's run writes .x / .y.  ends_host (the whole owned range only): the first and the last key, and the sort's
-// sequence number, into mapped host memory (block_order's estimate; launch_sort's throttle).
+// last slot of a cell's run writes .x / .y.  ends_host (the whole owned range only) points at the word HW_FIRST_KEY of the mapped
+// host block: the first and the last key, and the sort's sequence number, go there (block_order's estimate; launch_sort's throttle).
 __device__ __forceinline__ void cells_build_thread(const uint32_t* __restrict__ key, uint32_t lo, uint32_t hi, uint2* __restrict__ cells,
                                                    volatile uint32_t* __restrict__ ends_host, uint32_t seq, uint32_t t) {
     const uint32_t s0 = lo + t * CELLS_SPT;
     if (s0 >= hi) return;
     if (ends_host && s0 == lo) {
-        ends_host[0] = key[lo]; ends_host[1] = key[hi - 1u];
-        if (seq) ends_host[2] = seq;
+        ends_host[0] = key[lo]; ends_host[HW_LAST_KEY - HW_FIRST_KEY] = key[hi - 1u];
+        if (seq) ends_host[HW_BUILD_SEQ - HW_FIRST_KEY] = seq;
     }
     uint32_t kk[CELLS_SPT + 2];                          // key[s0 - 1 .. s0 + 4]
     kk[1] = key[s0];

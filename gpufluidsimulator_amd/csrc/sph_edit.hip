@@ -9,7 +9,7 @@
 //                   slot - (selected particles in front of it) with 16-byte loads and stores, the selected ones leave their
 //                   creation index in slot order and their row of the by-index position buffer is zeroed
 //
-// The tile counts and offsets live in the movers' ping-pong scratch of the sort (mm_k1 / mm_v1) and the removed indices in k0:
+// The tile counts and offsets live in the movers' ping-pong scratch of the sort (edit_tiles below) and the removed indices in k0:
 // all three are dead between two steps, so a call that selects nothing leaves every bit of the context as it was.
 #include "sph_common.hpp"
 
@@ -175,13 +175,20 @@ static int check_regions(const sph_ctx* c, uint32_t n_regions, const sph_region*
     return SPH_OK;
 }
 
-// the selection of the owned range: tile counts into mm_k1, their offsets into mm_v1, the total to the host (synchronises)
+// The tile counts and offsets of a selection borrow the movers' ping-pong of the sort: `cap` words each (sort_buffers_alloc),
+// dead between two steps.
+struct EditTiles { uint32_t* cnt; uint32_t* off; };
+static EditTiles edit_tiles(sph_ctx* c) { return EditTiles{c->mm_k1, c->mm_v1}; }
+
+// the selection of the owned range: tile counts and their offsets into edit_tiles, the total to the host (synchronises)
 static int count_selected(sph_ctx* c, const Regions& R, uint32_t* total) {
     *total = 0;
     if (c->n == 0) return SPH_OK;
-    const uint32_t nt = ceil_div(c->n, EDIT_TILE);           // <= n <= cap words of either scratch array
-    hipLaunchKernelGGL(k_edit_count, dim3(nt), dim3(EDIT_THREADS), 0, c->stream, c->posi + c->own_off, c->n, R, c->mm_k1);
-    hipLaunchKernelGGL(k_edit_scan, dim3(1), dim3(1024), 0, c->stream, c->mm_k1, nt, c->mm_v1, c->d_scratch);
+    const uint32_t nt = ceil_div(c->n, EDIT_TILE);
+    SPH_REQUIRE(nt <= c->cap, SPH_E_CAPACITY, "%u selection tiles > the %u words of the scratch they borrow", nt, c->cap);
+    const EditTiles t = edit_tiles(c);
+    hipLaunchKernelGGL(k_edit_count, dim3(nt), dim3(EDIT_THREADS), 0, c->stream, c->posi + c->own_off, c->n, R, t.cnt);
+    hipLaunchKernelGGL(k_edit_scan, dim3(1), dim3(1024), 0, c->stream, t.cnt, nt, t.off, c->d_scratch);
     SPH_HIP(hipGetLastError());
     SPH_HIP(hipMemcpyAsync(c->h_scratch, c->d_scratch, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     SPH_HIP(hipStreamSynchronize(c->stream));
@@ -222,7 +229,7 @@ int sph_remove(sph_ctx* c, uint32_t n_regions, const sph_region* regions, uint32
     mm_drop_marks(c);                         // per-slot marks of the integrate epilogue: the slots are renumbered
     const uint32_t n = c->n, take = removed_index ? (max_out < total ? max_out : total) : 0u;
     hipLaunchKernelGGL(k_edit_compact, dim3(ceil_div(n, EDIT_TILE)), dim3(EDIT_THREADS), 0, c->stream, c->posi + c->own_off,
-                       c->velr + c->own_off, c->keyS + c->own_off, n, R, c->mm_v1, c->posi2 + c->gcap, c->velr2 + c->gcap,
+                       c->velr + c->own_off, c->keyS + c->own_off, n, R, edit_tiles(c).off, c->posi2 + c->gcap, c->velr2 + c->gcap,
                        c->keyS2 + c->gcap, c->k0, take, c->pos_out, c->pos_out_cap);
     SPH_HIP(hipGetLastError());
     // dp / cw are not compacted (the next step rewrites them): what a slot holds now belongs to another particle, so the

@@ -52,18 +52,20 @@ __global__ __launch_bounds__(256) void k_unpack(const float4* __restrict__ rec, 
     if (write_key) key[i] = cell_key(g, p.x, p.y, p.z);
 }
 
-// lower bounds of up to 62 key targets in the owned sorted keys, returned through pinned memory
+// lower bounds of a few key targets in the owned sorted keys, returned through pinned memory: the targets travel in the first
+// half of the context's scratch pair, the answers in the second
+constexpr uint32_t LB_ANSWERS = SCRATCH_WORDS / 2;
 static int lower_bounds(sph_ctx* c, const uint32_t* targets, uint32_t m, uint32_t* out) {
-    SPH_REQUIRE(m <= 31, SPH_E_INVALID, "too many targets");
+    SPH_REQUIRE(m < LB_ANSWERS, SPH_E_INVALID, "too many targets");
     SPH_HIP(hipSetDevice(c->device));
     for (uint32_t k = 0; k < m; k++) c->h_scratch[k] = targets[k];
     SPH_HIP(hipMemcpyAsync(c->d_scratch, c->h_scratch, m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_lower_bounds, dim3(1), dim3(64), 0, c->stream, c->keyS + c->own_off, c->n, c->d_scratch, m,
-                       c->d_scratch + 32);
+                       c->d_scratch + LB_ANSWERS);
     SPH_HIP(hipGetLastError());
-    SPH_HIP(hipMemcpyAsync(c->h_scratch + 32, c->d_scratch + 32, m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    SPH_HIP(hipMemcpyAsync(c->h_scratch + LB_ANSWERS, c->d_scratch + LB_ANSWERS, m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     SPH_HIP(hipStreamSynchronize(c->stream));
-    for (uint32_t k = 0; k < m; k++) out[k] = c->h_scratch[32 + k];
+    for (uint32_t k = 0; k < m; k++) out[k] = c->h_scratch[LB_ANSWERS + k];
     return SPH_OK;
 }
 

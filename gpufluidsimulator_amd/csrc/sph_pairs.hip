@@ -170,7 +170,7 @@ int launch_cells_clear_range(sph_ctx* c, uint32_t lo, uint32_t hi) {
 int launch_cells_build_range(sph_ctx* c, uint32_t lo, uint32_t hi, uint32_t seq) {
     if (hi <= lo) return SPH_OK;
     // (the whole owned range: the sort's table build -- also tells the host the first and the last key, and the sort's number)
-    uint32_t* ends = (lo == c->own_off && hi == c->own_off + c->n) ? c->mm_count_host_dev + 1 : (uint32_t*)nullptr;
+    uint32_t* ends = (lo == c->own_off && hi == c->own_off + c->n) ? c->mm_count_host_dev + HW_FIRST_KEY : (uint32_t*)nullptr;
     hipLaunchKernelGGL(k_cells_build, dim3(cells_build_blocks(hi - lo)), dim3(256), 0, c->stream, c->keyS, lo, hi, c->table.cells, ends,
                        ends ? seq : 0u);
     SPH_HIP(hipGetLastError());
@@ -1276,7 +1276,7 @@ __global__ __launch_bounds__(THREADS, SPH_FORCE_OCC) void k_force(
 static BlockOrder block_order(const sph_ctx* c, uint32_t nblocks, bool ztile) {
     BlockOrder o{c->order_xcd ? 1u : 0u, 0u, 0u, 0u, c->order_xrot ? 1u : 0u};
     if (!o.xcd || !ztile || !c->order_ztile || nblocks < 1024u) return o;
-    const uint32_t k0 = c->mm_count_host[1], k1 = c->mm_count_host[2], layer = c->grid.g[0] * c->grid.g[1];
+    const uint32_t k0 = c->mm_count_host[HW_FIRST_KEY], k1 = c->mm_count_host[HW_LAST_KEY], layer = c->grid.g[0] * c->grid.g[1];
     if (k1 < k0 || layer == 0u) return o;
     const uint32_t nz = k1 / layer - k0 / layer + 1u;                    // occupied cell layers
     const uint32_t per_layer = nblocks / nz;                             // blocks per layer, about
@@ -1423,6 +1423,24 @@ int launch_spheres_radii(sph_ctx* c) {
     hipLaunchKernelGGL(k_spheres_install, dim3(1), dim3(64), 0, c->stream, c->trk_table, sphere_table(c), c->trk_J, 1);
     SPH_HIP(hipGetLastError());
     return SPH_OK;
+}
+
+// The buffers of a tracked context, by capacity (the first sph_set_collider_bodies): one row of partial sums and one mask word
+// per wave of the owned slots.  k_spheres_step reads the masks in quads of SPHERES_MASK_QUAD words from a multiple of it, as far
+// as one quad past the last wave: the array is the wave count rounded up to whole quads, plus one quad.  Zero where a kernel
+// reads before any kernel wrote: the table's count, the masks of waves no launch covered, J and the step count.
+constexpr size_t SPHERES_MASK_QUAD = 4;      // (the uint4 load and the `+ 3u) & ~3u` of k_spheres_step)
+int tracked_buffers_alloc(sph_ctx* c) {
+    Buffers& m = c->mem;
+    const size_t waves = ceil_div(c->cap, (uint32_t)WAVE);
+    int rc = m.alloc(&c->trk_table, 1, true);
+    if (!rc) rc = m.alloc(&c->trk_partial, waves * SPH_MAX_COLLIDERS * 3, false);
+    if (!rc) rc = m.alloc(&c->trk_mask, ((waves + SPHERES_MASK_QUAD - 1) & ~(SPHERES_MASK_QUAD - 1)) + SPHERES_MASK_QUAD, true);
+    if (!rc) rc = m.alloc(&c->trk_J, SPH_MAX_COLLIDERS * 3 + 1, true);
+    if (rc) {                                  // all four or none: trk_table doubles as "the buffers are there"
+        m.release(&c->trk_J); m.release(&c->trk_mask); m.release(&c->trk_partial); m.release(&c->trk_table);
+    }
+    return rc;
 }
 
 static SpheresTracked tracked_pack(const sph_ctx* c) { return SpheresTracked{c->trk_table, c->trk_partial, c->trk_mask, 0u}; }

@@ -428,18 +428,13 @@ __global__ __launch_bounds__(RENDER_THREADS) void k_surface_shade(const uint64_t
     for (int k = 0; k < 3; k++) normal[3 * (size_t)pix + k] = nv[k];
 }
 
-static void free_image(sph_ctx* c) {
-    hipFree(c->rd_keys); hipFree(c->rd_rgba); hipFree(c->rd_id); hipFree(c->rd_depth);
-    c->rd_keys = nullptr; c->rd_rgba = nullptr; c->rd_id = nullptr; c->rd_depth = nullptr;
-    hipFree(c->rd_sf_raw); hipFree(c->rd_sf_pong); hipFree(c->rd_sf_thick); hipFree(c->rd_sf_normal);
-    c->rd_sf_raw = nullptr; c->rd_sf_pong = nullptr; c->rd_sf_thick = nullptr; c->rd_sf_normal = nullptr;
+// the image and its surface planes leave the context's owner before the context does: another image size, a failed allocation
+static void release_image(sph_ctx* c) {
+    Buffers& m = c->mem;
+    m.release(&c->rd_sf_normal); m.release(&c->rd_sf_thick); m.release(&c->rd_sf_pong); m.release(&c->rd_sf_raw);
+    m.release(&c->rd_depth); m.release(&c->rd_id); m.release(&c->rd_rgba); m.release(&c->rd_keys);
     c->rd_alloc_w = c->rd_alloc_h = 0;
-}
-
-void render_release(sph_ctx* c) {
-    free_image(c);
-    hipFree(c->rd_counts);
-    c->rd_counts = nullptr;
+    c->rd_valid = false;
 }
 
 static bool finite3(const float* v, int n) {
@@ -525,21 +520,16 @@ static int check_render(sph_ctx* c, const sph_camera* cam, const sph_render_styl
 }
 
 // The image buffers for w x h: kept when they have that size, else (first call, or another image size) allocated anew.
-static int ensure_image(sph_ctx* c, uint32_t w, uint32_t h, const char* who) {
+static int ensure_image(sph_ctx* c, uint32_t w, uint32_t h) {
     if (w == c->rd_alloc_w && h == c->rd_alloc_h) return SPH_OK;
     const uint32_t npix = w * h;
     SPH_HIP(hipStreamSynchronize(c->stream));        // (a consumer of the old image on this stream has finished)
-    free_image(c);
-    c->rd_valid = false;
-    hipError_t e = hipMalloc((void**)&c->rd_keys, (size_t)npix * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->rd_rgba, (size_t)npix * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->rd_id, (size_t)npix * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->rd_depth, (size_t)npix * 4);
-    if (e != hipSuccess) {
-        free_image(c);
-        set_error("%s: hipMalloc of a %u x %u image failed: %s", who, w, h, hipGetErrorString(e));
-        return SPH_E_NOMEM;
-    }
+    release_image(c);
+    int rc = c->mem.alloc(&c->rd_keys, npix, false);     // (every plane is written by the render before anything reads it)
+    if (!rc) rc = c->mem.alloc(&c->rd_rgba, npix, false);
+    if (!rc) rc = c->mem.alloc(&c->rd_id, npix, false);
+    if (!rc) rc = c->mem.alloc(&c->rd_depth, npix, false);
+    if (rc) { release_image(c); return rc; }
     c->rd_alloc_w = w;
     c->rd_alloc_h = h;
     return SPH_OK;
@@ -570,14 +560,14 @@ int sph_render(sph_ctx* c, const sph_camera* cam, const sph_render_style* style)
     if (int e = check_render(c, cam, style, "sph_render")) return e;
     SPH_HIP(hipSetDevice(c->device));
     const uint32_t w = cam->width, h = cam->height, npix = w * h;
-    if (int e = ensure_image(c, w, h, "sph_render")) return e;
+    if (int e = ensure_image(c, w, h)) return e;
     const RenderArgs A = render_args(c, cam, style);
     const uint32_t pix_blocks = ceil_div(npix, RENDER_THREADS);
     hipLaunchKernelGGL(k_render_clear, dim3(pix_blocks), dim3(RENDER_THREADS), 0, c->stream, c->rd_keys, npix);
     if (c->n) {
 #ifdef SPH_RENDER_STATS
         if (!c->rd_counts) {
-            SPH_HIP(hipMalloc((void**)&c->rd_counts, 2 * sizeof(unsigned long long)));
+            if (int e = c->mem.alloc(&c->rd_counts, 2, false)) return e;
             SPH_HIP(hipMemsetAsync(c->rd_counts, 0, 2 * sizeof(unsigned long long), c->stream));
         }
         hipLaunchKernelGGL(k_render_splat<true>, dim3(ceil_div(c->n, RENDER_THREADS)), dim3(RENDER_THREADS), 0, c->stream,
@@ -629,18 +619,16 @@ int sph_render_surface(sph_ctx* c, const sph_camera* cam, const sph_render_style
     SPH_REQUIRE(c->n < (1u << 28), SPH_E_CAPACITY, "sph_render_surface: %u particles: the thickness word holds fewer than 2^28", c->n);
     SPH_HIP(hipSetDevice(c->device));
     const uint32_t w = cam->width, h = cam->height, npix = w * h;
-    if (int e = ensure_image(c, w, h, "sph_render_surface")) return e;
+    if (int e = ensure_image(c, w, h)) return e;
     if (!c->rd_sf_raw) {                                  // the first surface render of an image of this size
-        hipError_t e = hipMalloc((void**)&c->rd_sf_raw, (size_t)npix * 4);
-        if (e == hipSuccess) e = hipMalloc((void**)&c->rd_sf_pong, (size_t)npix * 4);
-        if (e == hipSuccess) e = hipMalloc((void**)&c->rd_sf_thick, (size_t)npix * 4);
-        if (e == hipSuccess) e = hipMalloc((void**)&c->rd_sf_normal, (size_t)npix * 12);
-        if (e != hipSuccess) {
+        int rc = c->mem.alloc(&c->rd_sf_raw, npix, false);
+        if (!rc) rc = c->mem.alloc(&c->rd_sf_pong, npix, false);
+        if (!rc) rc = c->mem.alloc(&c->rd_sf_thick, npix, false);
+        if (!rc) rc = c->mem.alloc(&c->rd_sf_normal, (size_t)npix * 3, false);
+        if (rc) {
             SPH_HIP(hipStreamSynchronize(c->stream));
-            free_image(c);
-            c->rd_valid = false;
-            set_error("sph_render_surface: hipMalloc of the planes of a %u x %u image failed: %s", w, h, hipGetErrorString(e));
-            return SPH_E_NOMEM;
+            release_image(c);
+            return rc;
         }
     }
     const RenderArgs A = render_args(c, cam, style);

@@ -873,6 +873,7 @@ struct Msg {
 
 struct sph_slab {
     sph_ctx* c = nullptr;
+    sph::Buffers mem;                    // every device and pinned buffer below (slab_free)
     int rank = 0, world = 1;
     bool has_lo = false, has_hi = false;
     sph_transport tr{};
@@ -957,16 +958,7 @@ namespace {
 
 void slab_free(sph_slab* s) {
     if (!s) return;
-    for (int k = 0; k < 2; k++) {
-        hipFree(s->mig_send[k]); hipFree(s->mig_recv[k]); hipFree(s->halo_send[k]); hipFree(s->halo_recv[k]);
-        hipFree(s->dens_send[k]); hipFree(s->dens_recv[k]);
-        if (s->stage_send[k]) hipHostFree(s->stage_send[k]);
-        if (s->stage_recv[k]) hipHostFree(s->stage_recv[k]);
-    }
-    hipFree(s->d_lb);
-    hipFree(s->recut_blk);
-    if (s->h_lb) hipHostFree((void*)s->h_lb);
-    if (s->hop_mem) hipFree(s->hop_mem);
+    s->mem.free_all();
     if (s->ev_main) hipEventDestroy(s->ev_main);
     if (s->ev_comm) hipEventDestroy(s->ev_comm);
     if (s->ev_deep) hipEventDestroy(s->ev_deep);
@@ -1223,7 +1215,7 @@ int step_pre_wait(sph_slab* s, Step& st) {
     const uint32_t pack_blocks = st.p1 ? 128u : min(ceil_div(s->mcap, 256u), 16u), build_blocks = owned_build_pending ? cells_build_blocks(st.n0) : 0u;
     hipLaunchKernelGGL(k_slab_bounds_pack, dim3(pack_blocks + build_blocks), dim3(256), 0, c->stream, c->keyS + st.off0, c->posi + st.off0,
                        c->velr + st.off0, st.n0, st.off0, st.layer, s->mcap, c->grid, s->early_cap, s->d_lb, s->mig_send[0], s->mig_send[1],
-                       pack_blocks, c->keyS, c->table.cells, c->mm_count_host_dev + 1, c->ghost_layers, st.p1 ? 1u : 0u, s->gcap);
+                       pack_blocks, c->keyS, c->table.cells, c->mm_count_host_dev + HW_FIRST_KEY, c->ghost_layers, st.p1 ? 1u : 0u, s->gcap);
     SPH_HIP(hipGetLastError());
     rc = after_main(s); if (rc) return rc;
     // ---- the density of the deep interior goes into the main stream's queue BEFORE the host waits: its slot range
@@ -1815,13 +1807,14 @@ int sph_rccl_transport_selftest(sph_transport* t, size_t bytes) {
     RcclLink* L = (RcclLink*)t->self;
     char *sa = nullptr, *sb = nullptr, *ra = nullptr, *rb = nullptr;
     hipStream_t st = nullptr;
-    int rc = SPH_OK;
+    Buffers tmp;
     std::vector<char> ha(bytes), hb(bytes);
+    int rc = SPH_OK;
     auto fail = [&](const char* what, hipError_t e) { set_error("selftest: %s: %s", what, hipGetErrorString(e)); rc = SPH_E_DEVICE; };
     hipError_t e;
-    if ((e = hipMalloc((void**)&sa, bytes)) || (e = hipMalloc((void**)&sb, bytes)) || (e = hipMalloc((void**)&ra, bytes)) ||
-        (e = hipMalloc((void**)&rb, bytes)) || (e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking)))
-        fail("allocation", e);
+    if (!(rc = tmp.alloc(&sa, bytes, false)) && !(rc = tmp.alloc(&sb, bytes, false)) && !(rc = tmp.alloc(&ra, bytes, false)) &&
+        !(rc = tmp.alloc(&rb, bytes, false)) && (e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking)))
+        fail("stream", e);
     if (!rc) {
         for (size_t i = 0; i < bytes; i++) { ha[i] = (char)(i * 7u + 1u); hb[i] = (char)(i * 13u + 5u); }
         if ((e = hipMemcpy(sa, ha.data(), bytes, hipMemcpyHostToDevice)) || (e = hipMemcpy(sb, hb.data(), bytes, hipMemcpyHostToDevice)) ||
@@ -1853,7 +1846,7 @@ int sph_rccl_transport_selftest(sph_transport* t, size_t bytes) {
         }
     }
     if (st) hipStreamDestroy(st);
-    hipFree(sa); hipFree(sb); hipFree(ra); hipFree(rb);
+    tmp.free_all();
     return rc;
 }
 
@@ -1961,41 +1954,43 @@ int sph_slab_create(sph_slab** out, sph_ctx* ctx, int rank, int world, const sph
               hipEventCreateWithFlags(&s->ev_deep, hipEventDisableTiming) == hipSuccess &&
               hipStreamCreateWithFlags(&s->early, hipStreamNonBlocking) == hipSuccess &&
               hipEventCreateWithFlags(&s->ev_early_go, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&s->ev_early_done, hipEventDisableTiming) == hipSuccess &&
-              hipMalloc((void**)&s->d_lb, DL_WORDS * sizeof(uint32_t)) == hipSuccess &&
-              hipMemset(s->d_lb, 0, DL_WORDS * sizeof(uint32_t)) == hipSuccess &&
-              hipHostMalloc((void**)&s->h_lb, HL_WORDS * sizeof(uint32_t), hipHostMallocMapped) == hipSuccess &&
-              hipHostGetDevicePointer((void**)&s->h_lb_dev, (void*)s->h_lb, 0) == hipSuccess;
+              hipEventCreateWithFlags(&s->ev_early_done, hipEventDisableTiming) == hipSuccess;
+    if (!ok) { set_error("sph_slab_create: creating the streams and events failed"); slab_free(s); return SPH_E_NOMEM; }
+    Buffers& m = s->mem;
+    int rc = m.alloc(&s->d_lb, DL_WORDS, true);
+    if (!rc) rc = m.alloc_host(&s->h_lb, HL_WORDS, (volatile uint32_t**)&s->h_lb_dev);
     // (a context with two ghost layers may run the one-message step: leavers AND two layers of residents in one buffer)
     s->msg_cap = ctx->ghost_layers >= 2u ? s->mcap + s->gcap + 64u : s->mcap;
     const size_t mig_bytes = (size_t)(1 + s->msg_cap) * 2 * sizeof(float4), halo_bytes = (size_t)(s->gcap + 1) * 2 * sizeof(float4);
-    for (int k = 0; k < 2 && ok; k++)
-        ok = hipMalloc((void**)&s->mig_send[k], mig_bytes) == hipSuccess && hipMalloc((void**)&s->mig_recv[k], mig_bytes) == hipSuccess &&
-             hipMalloc((void**)&s->halo_send[k], halo_bytes) == hipSuccess && hipMalloc((void**)&s->halo_recv[k], halo_bytes) == hipSuccess &&
-             hipMalloc((void**)&s->dens_send[k], (size_t)(s->gcap + 1) * sizeof(float2)) == hipSuccess &&
-             hipMalloc((void**)&s->dens_recv[k], (size_t)(s->gcap + 1) * sizeof(float2)) == hipSuccess &&
-             hipMemset(s->mig_send[k], 0, mig_bytes) == hipSuccess && hipMemset(s->mig_recv[k], 0, mig_bytes) == hipSuccess;
-    if (ok && s->host_staged) {
-        s->stage_bytes = mig_bytes > halo_bytes ? mig_bytes : halo_bytes;
-        for (int k = 0; k < 2 && ok; k++)
-            ok = hipHostMalloc((void**)&s->stage_send[k], s->stage_bytes) == hipSuccess &&
-                 hipHostMalloc((void**)&s->stage_recv[k], s->stage_bytes) == hipSuccess;
+    for (int k = 0; k < 2 && !rc; k++) {      // (the migrant buffers start as zeros: a header nobody wrote yet reads "nothing")
+        rc = m.alloc(&s->mig_send[k], mig_bytes / sizeof(float4), true);
+        if (!rc) rc = m.alloc(&s->mig_recv[k], mig_bytes / sizeof(float4), true);
+        if (!rc) rc = m.alloc(&s->halo_send[k], halo_bytes / sizeof(float4), false);
+        if (!rc) rc = m.alloc(&s->halo_recv[k], halo_bytes / sizeof(float4), false);
+        if (!rc) rc = m.alloc(&s->dens_send[k], (size_t)s->gcap + 1, false);
+        if (!rc) rc = m.alloc(&s->dens_recv[k], (size_t)s->gcap + 1, false);
     }
-    if (!ok) { set_error("sph_slab_create: allocation failed"); slab_free(s); return SPH_E_NOMEM; }
+    if (!rc && s->host_staged) {
+        s->stage_bytes = mig_bytes > halo_bytes ? mig_bytes : halo_bytes;
+        for (int k = 0; k < 2 && !rc; k++) {
+            rc = m.alloc_host(&s->stage_send[k], s->stage_bytes);
+            if (!rc) rc = m.alloc_host(&s->stage_recv[k], s->stage_bytes);
+        }
+    }
     {   // cross-stream edges by write / wait value where that works on this device (see hop_mem)
         const char* e = getenv("SPH_SLAB_HOPS");
         int can = 0;
-        if (!(e && e[0] == 'e') && hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, ctx->device) == hipSuccess && can &&
-            hipMalloc((void**)&s->hop_mem, 5 * 16 * sizeof(uint32_t)) == hipSuccess && hipMemset(s->hop_mem, 0, 5 * 16 * sizeof(uint32_t)) == hipSuccess &&
-            hipDeviceSynchronize() == hipSuccess) {
+        if (!rc && !(e && e[0] == 'e') && hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, ctx->device) == hipSuccess && can &&
+            !(rc = m.alloc(&s->hop_mem, 5 * 16, true)) && hipDeviceSynchronize() == hipSuccess) {
             // one pair each way, waited for here: a runtime that accepts the calls but cannot serve them must not be found out mid-step
             s->hops_by_value = true;
             const bool fine = after_main(s) == SPH_OK && after_comm(s) == SPH_OK && hipStreamSynchronize(s->comm) == hipSuccess &&
                               hipStreamSynchronize(ctx->stream) == hipSuccess;
             if (!fine) { s->hops_by_value = false; (void)hipGetLastError(); }
         }
-        if (!s->hops_by_value && s->hop_mem) { hipFree(s->hop_mem); s->hop_mem = nullptr; }
+        if (!s->hops_by_value) m.release(&s->hop_mem);      // (the probe rejected it: events)
     }
+    if (rc) { slab_free(s); return rc; }                    // (the owner's message names what failed)
     for (int k = 0; k < HL_WORDS; k++) s->h_lb[k] = 0u;
     ctx->host_paced = true;            // sph_slab_step waits for the device once per step
     *out = s;
@@ -2235,7 +2230,7 @@ static int slab_recut_body(sph_slab* s, uint32_t new_lo, uint32_t new_hi) {
     rc = launch_cells_clear(c); if (rc) return rc;        // no entry of the old numbering survives
     mm_drop_marks(c);
     const uint32_t n = c->n, off = c->own_off, nblk = ceil_div(max(n, 1u), RECUT_BLOCK);
-    if (!s->recut_blk) SPH_HIP(hipMalloc((void**)&s->recut_blk, (size_t)2 * (ceil_div(c->cap, RECUT_BLOCK) + 1) * sizeof(uint32_t)));
+    if (!s->recut_blk) { rc = s->mem.alloc(&s->recut_blk, (size_t)2 * (ceil_div(c->cap, RECUT_BLOCK) + 1), false); if (rc) return rc; }
     s->h_lb[HL_RECUT] = s->h_lb[HL_RECUT + 1] = 0u;
     hipLaunchKernelGGL(k_recut_count, dim3(nblk), dim3(256), 0, c->stream, c->posi + off, n, c->grid, new_lo, new_hi, s->recut_blk);
     hipLaunchKernelGGL(k_recut_scan, dim3(1), dim3(1024), 0, c->stream, s->recut_blk, nblk, s->h_lb_dev + HL_RECUT);

@@ -9,6 +9,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <cstdlib>
 
 namespace sph {
 
@@ -52,6 +53,10 @@ __global__ __launch_bounds__(256) void k_hash(const float4* __restrict__ posi, u
 // All kernels take the element count by value or from device memory (n_dev, clamped to n): the movers' sort of
 // the merge path is sized from a stale estimate and is correct for any count.
 constexpr int OS_TILE = SORT_TILE;                       // 4096 keys per tile
+// What the per-digit tables are laid out for: digits of up to 9 bits, and the passes 32 key bits need at 8 bits each
+// (radix_sort_bits asserts both; sort_buffers_alloc sizes os_hist / os_base / os_tot / os_tickets / os_status by them).
+constexpr uint32_t OS_DIGITS = 512;
+constexpr uint32_t OS_PASSES = 4;
 // Tiles per look-back group.  One chain over all 4096 tiles of C3 made a pass take 240 us (~58 ns per tile), so a
 // big sort uses groups of 16 tiles whose chains run in parallel -- at the price of one histogram kernel PER PASS (the
 // digit counts of a group are those of the keys as that pass finds them).  Up to OS_ONE_GROUP_TILES tiles (the movers'
@@ -120,7 +125,7 @@ __device__ __forceinline__ void wave_count_digit(uint32_t* counts, uint32_t d, b
     }
 }
 
-// digit counts of the passes pass0 .. pass0+passes-1 per group of tiles: hist[(group * 4 + pass) * 512 + digit],
+// digit counts of the passes pass0 .. pass0+passes-1 per group of tiles: hist[(group * OS_PASSES + pass) * OS_DIGITS + digit],
 // ACCUMULATED (k_os_scan zeroes what it has read).  A block counts OS_HIST_TILES consecutive tiles (all of one
 // group) in LDS and adds what it found; 16-byte loads.
 constexpr uint32_t OS_HIST_TILES = 2;
@@ -160,13 +165,13 @@ __global__ __launch_bounds__(SORT_THREADS) void k_os_hist(const uint32_t* __rest
         __syncthreads();
         const uint32_t grp = group_tiles == OS_ALL_TILES ? 0u : t0 / group_tiles;
         for (uint32_t d = threadIdx.x; d < passes * RADIX; d += SORT_THREADS)
-            if (h[d]) atomicAdd(&hist[(grp * 4u + pass0 + d / RADIX) * 512u + (d % RADIX)], h[d]);
+            if (h[d]) atomicAdd(&hist[(grp * OS_PASSES + pass0 + d / RADIX) * OS_DIGITS + (d % RADIX)], h[d]);
         __syncthreads();
     }
 }
 
-// One wave per digit (blockIdx.y = pass - pass0): base[(group * 4 + pass) * 512 + digit] = keys with this digit in
-// EARLIER groups, tot[pass * 512 + digit] = keys with this digit; the counts are zeroed for the next sort and the
+// One wave per digit (blockIdx.y = pass - pass0): base[(group * OS_PASSES + pass) * OS_DIGITS + digit] = keys with this digit in
+// EARLIER groups, tot[pass * OS_DIGITS + digit] = keys with this digit; the counts are zeroed for the next sort and the
 // pass's ticket is re-armed.
 template <int BITS>
 __global__ __launch_bounds__(256) void k_os_scan(uint32_t* __restrict__ hist, uint32_t* __restrict__ base,
@@ -186,7 +191,7 @@ __global__ __launch_bounds__(256) void k_os_scan(uint32_t* __restrict__ hist, ui
     uint32_t carry = 0;
     for (uint32_t g0 = 0; g0 < ngroups; g0 += 64u) {
         const uint32_t g = g0 + lane;
-        const uint32_t idx = (g * 4u + p) * 512u + d;
+        const uint32_t idx = (g * OS_PASSES + p) * OS_DIGITS + d;
         uint32_t v = 0;
         if (g < ngroups) { v = hist[idx]; hist[idx] = 0u; }
         if (d == 0 && g < ngroups) tickets[(size_t)p * tickets_stride + g] = 0u;   // grouped form: one ticket per group
@@ -199,7 +204,7 @@ __global__ __launch_bounds__(256) void k_os_scan(uint32_t* __restrict__ hist, ui
         if (g < ngroups) base[idx] = carry + inc - v;
         carry += (uint32_t)__shfl((int)inc, 63);
     }
-    if (lane == 0) tot[p * 512u + d] = carry;
+    if (lane == 0) tot[p * OS_DIGITS + d] = carry;
 }
 
 typedef unsigned long long os_word;
@@ -488,7 +493,7 @@ __global__ __launch_bounds__(PASS_THREADS, SPH_OS_PASS_OCC) void k_os_pass(const
 #pragma unroll
             for (int k = 0; k < DPT; k++) {
                 const uint32_t d = threadIdx.x * DPT + k;
-                if (has_d) s_delta[d] = dbase[k] + group_base[(grp * 4u) * 512u + d] + excl[k] - tstart[k];
+                if (has_d) s_delta[d] = dbase[k] + group_base[(grp * OS_PASSES) * OS_DIGITS + d] + excl[k] - tstart[k];
             }
         }
         OS_STAT(5);                                 // look-back (thread 0)
@@ -852,6 +857,7 @@ template <int BITS>
 static int radix_sort_bits(sph_ctx* c, uint32_t n, const uint32_t* n_dev, uint32_t grid, bool first, uint32_t passes,
                            uint32_t*& kin, uint32_t*& vin, uint32_t*& kout, uint32_t*& vout, const SmallTail& tail) {
     constexpr uint32_t RADIX = 1u << BITS;
+    static_assert(RADIX <= OS_DIGITS && 32 <= BITS * OS_PASSES, "the per-digit tables are laid out for OS_DIGITS x OS_PASSES");
     // counts the device may hand to the one-block sort (only when the count lives on the device: the movers' sort)
     uint32_t small_max = (n_dev && !first) ? OS_SMALL_MAX : 0u;
     // The count lives on the device, so in general BOTH forms are launched and each looks at the count first -- six
@@ -902,13 +908,13 @@ static int radix_sort_bits(sph_ctx* c, uint32_t n, const uint32_t* n_dev, uint32
         c->os_epoch++;
         if ((c->os_epoch & 0x7FFFFu) == 0u) {
             c->os_epoch++;
-            SPH_HIP(hipMemsetAsync(c->os_status32, 0, (size_t)512 * c->sort_blocks_cap * sizeof(uint32_t), c->stream));
+            SPH_HIP(hipMemsetAsync(c->os_status32, 0, (size_t)OS_DIGITS * c->sort_blocks_cap * sizeof(uint32_t), c->stream));
         }
         const uint32_t epoch = one_group ? (c->os_epoch & 0x7FFFFFFFu) : (c->os_epoch & 0x7FFFFu);
         uint32_t* tk = c->os_tickets + (size_t)p * gcap;
 #define SPH_OS_LAUNCH(F, G)                                                                                             \
         hipLaunchKernelGGL((k_os_pass<BITS, F, G>), dim3(G ? min((grid + 7u) & ~7u, OS_PASS_GRID_MAX) : grid), dim3(PASS_THREADS), 0, c->stream, kin, vin, kout, vout, n, \
-                           n_dev, p * BITS, c->os_base + p * 512u, c->os_tot + p * 512u, group_tiles, c->os_status,         \
+                           n_dev, p * BITS, c->os_base + p * OS_DIGITS, c->os_tot + p * OS_DIGITS, group_tiles, c->os_status,         \
                            c->os_status32, tk, epoch,                                                                    \
                            c->os_err_dev, small_max)
         if (first && p == 0) { if (one_group) SPH_OS_LAUNCH(true, false); else SPH_OS_LAUNCH(true, true); }
@@ -989,9 +995,9 @@ __global__ __launch_bounds__(1024) void k_mm_tilescan(uint32_t* __restrict__ til
         run += v;
     }
     if (threadIdx.x == 1023) {
-        *m_dev = part[1023]; *m_host = part[1023];
+        *m_dev = part[1023]; m_host[HW_MOVERS] = part[1023];
         if (m_total) *m_total += part[1023];          // one block: no atomic needed (sph_sort_stats: movers_total)
-        if (seq) { __threadfence_system(); m_host[4] = seq; }     // "the count of scan number seq is in [0]" (launch_sort's skip)
+        if (seq) { __threadfence_system(); m_host[HW_COUNT_SEQ] = seq; }     // "the count of scan number seq is in HW_MOVERS" (launch_sort's skip)
     }
 }
 
@@ -1034,7 +1040,7 @@ __global__ __launch_bounds__(256) void k_mm_compact(const uint64_t* __restrict__
         tile_start = part[0] + part[1] + part[2] + part[3];
         if (blockIdx.x == 0 && threadIdx.x == 0) {
             const uint32_t m = part[4] + part[5] + part[6] + part[7];
-            *m_dev = m; *m_host = m;
+            *m_dev = m; m_host[HW_MOVERS] = m;
             if (m_total) *m_total += m;               // one writer: no atomic needed (sph_sort_stats: movers_total)
         }
         __syncthreads();                              // part is reused below
@@ -1251,7 +1257,7 @@ void mm_set_marks(sph_ctx* c) {
 // less per step, ~4.5 us); a range of more than MM_FUSED_SCAN_TILES tiles keeps the scan kernel.
 void mm_scan_marks(sph_ctx* c) {
     if (!c->marks.marked || c->marks.scanned) return;
-    if (*c->mm_count_host != 0u && mm_tiles(c->marks.n) <= MM_FUSED_SCAN_TILES) return;     // the sort will count them
+    if (c->mm_count_host[HW_MOVERS] != 0u && mm_tiles(c->marks.n) <= MM_FUSED_SCAN_TILES) return;     // the sort will count them
     mm_tilescan(c, c->marks.n, true);
     c->marks.scanned = true;
 }
@@ -1286,7 +1292,7 @@ static bool launch_merge_count(sph_ctx* c, uint32_t n) {
 // the count of the CURRENT marks has arrived from the device (looked at, never waited for), and it is 0
 static bool mm_counted_none(const sph_ctx* c) {
     volatile const uint32_t* hw = c->mm_count_host;
-    return c->marks.counted_valid && hw[4] == c->marks.scan_seq && (std::atomic_thread_fence(std::memory_order_acquire), hw[0] == 0u);
+    return c->marks.counted_valid && hw[HW_COUNT_SEQ] == c->marks.scan_seq && (std::atomic_thread_fence(std::memory_order_acquire), hw[HW_MOVERS] == 0u);
 }
 
 // every slot from n_old on is a mover, none below (particles appended behind a sorted range)
@@ -1353,9 +1359,9 @@ static int launch_sort_merge(sph_ctx* c, uint32_t n, uint32_t n_tot, bool table_
 // build echoes into mapped host memory (rounds 1-5: a ring of four events, each ~5.5 us of device idle at the next dispatch).
 static int sort_throttle(sph_ctx* c) {
     volatile const uint32_t* hw = c->mm_count_host;
-    if ((int32_t)(c->sort_seq_issued - hw[3]) < 4) return SPH_OK;
+    if ((int32_t)(c->sort_seq_issued - hw[HW_BUILD_SEQ]) < 4) return SPH_OK;
     const auto t0 = std::chrono::steady_clock::now();
-    for (uint32_t spins = 1; (int32_t)(c->sort_seq_issued - hw[3]) >= 4; spins++) {
+    for (uint32_t spins = 1; (int32_t)(c->sort_seq_issued - hw[HW_BUILD_SEQ]) >= 4; spins++) {
         __builtin_ia32_pause();
         if ((spins & 0xFFFu) == 0u) {
             const hipError_t q = hipStreamQuery(c->stream);
@@ -1390,7 +1396,7 @@ static bool sort_skip_if_still(sph_ctx* c, bool was_still, TableLeft left, bool 
 static int sort_by_merge(sph_ctx* c, uint32_t n, TableLeft left, bool count_in_compact) {
     const bool table_live = left != TableLeft::NOTHING;
     // the old ghosts' cells, left by the hash of a slab step: spare blocks of k_mm_compact clear them
-    int rc = launch_sort_merge(c, n, n, table_live, *c->mm_count_host, Front{0u, 0u}, count_in_compact,   // hint: whatever step last reported
+    int rc = launch_sort_merge(c, n, n, table_live, c->mm_count_host[HW_MOVERS], Front{0u, 0u}, count_in_compact,   // hint: whatever step last reported
                                left == TableLeft::OWNED_AND_GHOSTS);
     if (rc) return rc;
     c->sort_merges++;
@@ -1464,8 +1470,8 @@ int launch_sort(sph_ctx* c, bool* owned_build_pending) {
     // movers left -- and, in a slab step, those of the old ghosts
     const TableLeft left = table_take_left(c);
     int rc;
-    if (can_merge && (*c->mm_count_host <= n / 8u || c->sort_merge_always)) {
-        const bool was_still = *c->mm_count_host == 0u;
+    if (can_merge && (c->mm_count_host[HW_MOVERS] <= n / 8u || c->sort_merge_always)) {
+        const bool was_still = c->mm_count_host[HW_MOVERS] == 0u;
         const bool count_in_compact = launch_merge_count(c, n);
         if (sort_skip_if_still(c, was_still, left, count_in_compact, &rc)) return rc;
         rc = sort_by_merge(c, n, left, count_in_compact);
@@ -1534,6 +1540,55 @@ int sort_indices_by_key(sph_ctx* c, const uint32_t* keys_dev, uint32_t n, uint32
     c->last_perm = nullptr;
     *perm_out = vin;
     return SPH_OK;
+}
+
+// Every buffer of the sorts, sized by the constants their kernels index them with; the order of allocation is part of the
+// layout (device addresses decide cache and channel behaviour) and is kept as it has always been.
+int sort_buffers_alloc(sph_ctx* c) {
+    Buffers& m = c->mem;
+    const size_t cap = c->cap;
+    c->sort_blocks_cap = ceil_div(c->cap, (uint32_t)OS_TILE) + 1;
+    const size_t tiles = c->sort_blocks_cap, groups = tiles / 4 + 3;        // enough for groups of >= 4 tiles
+    c->os_groups_cap = (uint32_t)groups;
+    static_assert(MM_RANK_TILE >= (uint32_t)OS_TILE, "mm_tileL / mm_tileA: an entry per MM_RANK_TILE slots + the end fit into one per sort tile + 2");
+    // written before they are read: the (key, value) ping-pong ...
+    int rc = m.alloc(&c->k0, cap, false);
+    if (!rc) rc = m.alloc(&c->v0, cap, false);
+    if (!rc) rc = m.alloc(&c->k1, cap, false);
+    if (!rc) rc = m.alloc(&c->v1, cap, false);
+    // ... zero where a kernel accumulates into, or polls, what no kernel of the same sort wrote: counts, tickets, look-back words
+    if (!rc) rc = m.alloc(&c->os_hist, groups * OS_PASSES * OS_DIGITS, true);
+    if (!rc) rc = m.alloc(&c->os_base, groups * OS_PASSES * OS_DIGITS, false);
+    if (!rc) rc = m.alloc(&c->os_tickets, (size_t)OS_PASSES * groups, true);
+    if (!rc) rc = m.alloc(&c->os_tot, (size_t)OS_PASSES * OS_DIGITS, false);
+    if (!rc) rc = m.alloc(&c->os_status, (size_t)OS_DIGITS * tiles, true);
+    if (!rc) rc = m.alloc(&c->os_status32, (size_t)OS_DIGITS * tiles, true);
+    if (!rc) rc = m.alloc(&c->mm_tileL, tiles + 2, false);
+    if (!rc) rc = m.alloc(&c->mm_tileA, tiles + 2, false);
+    if (!rc) rc = m.alloc_host(&c->os_err_host, 1, &c->os_err_dev);
+    if (!rc) *c->os_err_host = 0;
+    // the context's small scratch pair (SCRATCH_WORDS, sph_common.hpp): here because this is its place in the order
+    if (!rc) rc = m.alloc(&c->d_scratch, (size_t)SCRATCH_WORDS, false);
+    if (!rc) rc = m.alloc_host(&c->h_scratch, (size_t)SCRATCH_WORDS);
+    // the sort as a merge: one mask word per 64-slot chunk, one count per tile of MM_TILE_CHUNKS chunks
+    const char* env = getenv("SPH_SORT_MERGE");
+    c->sort_merge = !(env && env[0] == '0');
+    const size_t nchunks = (size_t)ceil_div(c->cap, 64u) + 1, ntiles = nchunks / MM_TILE_CHUNKS + 2;
+    if (!rc) rc = m.alloc(&c->mm_mask, nchunks, false);
+    if (!rc) rc = m.alloc(&c->mm_M64, nchunks, false);
+    if (!rc) rc = m.alloc(&c->mm_tile_cnt, ntiles, true);
+    if (!rc) rc = m.alloc(&c->mm_tile_off, ntiles, false);
+    if (!rc) rc = m.alloc(&c->mm_k0, cap, false);
+    if (!rc) rc = m.alloc(&c->mm_k1, cap, false);
+    if (!rc) rc = m.alloc(&c->mm_v1, cap, false);
+    if (!rc) rc = m.alloc(&c->mm_count, 1, true);
+    if (!rc) rc = m.alloc(&c->mm_total, 1, true);
+    if (!rc) rc = m.alloc_host(&c->mm_count_host, (size_t)HW_WORDS, &c->mm_count_host_dev);
+    if (!rc) {
+        for (uint32_t k = 0; k < HW_WORDS; k++) c->mm_count_host[k] = 0;
+        c->mm_count_host[HW_FIRST_KEY] = 1;                        // "no estimate yet" (first key > last key)
+    }
+    return rc;
 }
 
 }  // namespace sph

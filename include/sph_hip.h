@@ -45,7 +45,7 @@
  *   [tuning]       switches whose defaults are the product's settings; in fp32 results do not depend on them (A/B runs):
  *                  sph_set_sort_mode sph_set_direct_hull sph_set_pair_small_launch sph_set_block_order sph_slab_set_early_force
  *   [test hook]    exist for tests and measurement harnesses only: sph_test_trust_mover_hint sph_slab_test_raise_flag
- *                  sph_rccl_transport_selftest sph_loop_transport_create/_destroy
+ *                  sph_rccl_transport_selftest sph_loop_transport_create/_destroy sph_memory_stats sph_test_fail_alloc
  */
 #ifndef SPH_HIP_H
 #define SPH_HIP_H
@@ -782,6 +782,12 @@ int sph_slab_set_protocol(sph_slab* s, int groups);
 /* TEST HOOK: raise sticky device-side error word `flag` (0: an arrival outside its boundary layer, 1: an arrival outside
  * the slab) as the insert / unpack kernels would; the next sph_slab_step then fails before it has sent anything. */
 /* [test hook] */ int sph_slab_test_raise_flag(sph_slab* s, int flag);
+/* TEST HOOK: what this process's library holds right now: out = {live device bytes, live pinned bytes, live buffers}.  Counted
+ * where the library allocates and frees (hipMemGetInfo on a shared card sees everybody's processes): an exact leak check. */
+/* [test hook] */ void sph_memory_stats(uint64_t out[3]);
+/* TEST HOOK: the k-th device or pinned allocation the library makes from now on returns the ordinary SPH_E_NOMEM -- a host-side
+ * return, taken before any HIP call -- once; then the hook is disarmed.  k = 0 disarms it.  Process-wide. */
+/* [test hook] */ void sph_test_fail_alloc(uint32_t k);
 /* 0, or the first error of this slab: a slab that failed stays failed -- it has told its neighbours (they return
  * SPH_E_PEER at their next step), every later sph_slab_step returns the same error, and the state of its context is that
  * of a half-done step: download / destroy only */
