@@ -105,6 +105,15 @@ class SurfaceStyle(C.Structure):
 
 SURFACE_MAX_RADIUS_PX = 16   # SPH_SURFACE_MAX_RADIUS_PX
 SURFACE_MAX_ITERATIONS = 8   # SPH_SURFACE_MAX_ITERATIONS
+MESH_MAX_REACH = 8           # SPH_MESH_MAX_REACH
+MESH_MAX_DIM = 2048          # SPH_MESH_MAX_DIM
+MESH_MAX_NODES = 1 << 27     # SPH_MESH_MAX_NODES
+
+
+class MeshParams(C.Structure):
+    """`sph_mesh_params` of include/sph_hip.h (sph_mesh_extract); 0 in a field = its default."""
+    _fields_ = [("spacing", C.c_float), ("radius", C.c_float), ("iso", C.c_float)]
+
 
 # name -> (restype, argtypes); also the list the symbol-export test walks
 _P = C.c_void_p
@@ -154,6 +163,14 @@ SIGNATURES = {
     "sph_surface_defaults": (None, [C.POINTER(SurfaceStyle)]),
     "sph_render_surface": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(RenderStyle), C.POINTER(SurfaceStyle)]),
     "sph_render_surface_read": (C.c_int, [_P, _P, _P, _P]),
+    "sph_mesh_defaults": (None, [C.POINTER(MeshParams)]),
+    "sph_mesh_lattice": (C.c_int, [_P, C.POINTER(MeshParams), C.POINTER(_U32), C.POINTER(C.c_float)]),
+    "sph_mesh_extract": (C.c_int, [_P, C.POINTER(MeshParams), C.POINTER(_U32), C.POINTER(_U32)]),
+    "sph_mesh_read": (C.c_int, [_P, _P, _P, _P]),
+    "sph_mesh_dev": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_U32), C.POINTER(_U32)]),
+    "sph_mesh_save_obj": (C.c_int, [_P, C.c_char_p]),
+    "sph_mesh_field_dims": (C.c_int, [_P, C.POINTER(_U32)]),
+    "sph_mesh_field_read": (C.c_int, [_P, _P]),
     "sph_positions_dev": (C.c_int, [_P, C.POINTER(_P)]),
     "sph_download_positions4": (C.c_int, [_P, _P]),
     "sph_get_keys": (C.c_int, [_P, _P]),
@@ -320,6 +337,17 @@ def surface_defaults(**fields) -> SurfaceStyle:
             raise TypeError(f"sph_surface_style has no field {k!r}")
         setattr(s, k, v)
     return s
+
+
+def mesh_defaults(**fields) -> MeshParams:
+    """`sph_mesh_defaults` (a host helper: no GPU needed), with any field replaced: spacing, radius, iso."""
+    p = MeshParams()
+    load().sph_mesh_defaults(C.byref(p))
+    for k, v in fields.items():
+        if k not in ("spacing", "radius", "iso"):
+            raise TypeError(f"sph_mesh_params has no field {k!r}")
+        setattr(p, k, float(v))
+    return p
 
 
 class LocalHub:
@@ -598,6 +626,45 @@ class Context:
         p, w, h = _P(), _U32(), _U32()
         _check(self.L.sph_render_image_dev(self.h, C.byref(p), C.byref(w), C.byref(h)))
         return p.value, int(w.value), int(h.value)
+
+    # -- geometry (whole-domain contexts; include/sph_hip.h: sph_mesh_extract and the calls next to it) --------------------------
+    def mesh_lattice(self, params: "MeshParams | None" = None):
+        """((n_x, n_y, n_z), origin float32[3]) of the lattice extract_mesh would use (a host helper)."""
+        dims, origin = (_U32 * 3)(), (C.c_float * 3)()
+        _check(self.L.sph_mesh_lattice(self.h, None if params is None else C.byref(params), dims, origin))
+        return tuple(int(v) for v in dims), np.array(list(origin), np.float32)
+
+    def extract_mesh(self, params: "MeshParams | None" = None):
+        """Extract the surface of the owned particles as a triangle mesh on the device (params None: mesh_defaults());
+        returns (vertices, triangles).  Waits once for the two counts."""
+        nv, nt = _U32(0), _U32(0)
+        _check(self.L.sph_mesh_extract(self.h, None if params is None else C.byref(params), C.byref(nv), C.byref(nt)))
+        return int(nv.value), int(nt.value)
+
+    def mesh_dev(self):
+        """(positions, normals, triangles: device pointers or None; vertices; triangles) of the last mesh."""
+        a, b, t, nv, nt = _P(), _P(), _P(), _U32(), _U32()
+        _check(self.L.sph_mesh_dev(self.h, C.byref(a), C.byref(b), C.byref(t), C.byref(nv), C.byref(nt)))
+        return a.value, b.value, t.value, int(nv.value), int(nt.value)
+
+    def read_mesh(self):
+        """(pos[nv, 3] float32, normal[nv, 3] float32, tri[nt, 3] uint32) of the last mesh; synchronises."""
+        *_, nv, nt = self.mesh_dev()
+        pos, nrm, tri = np.empty((nv, 3), np.float32), np.empty((nv, 3), np.float32), np.empty((nt, 3), np.uint32)
+        _check(self.L.sph_mesh_read(self.h, pos.ctypes.data, nrm.ctypes.data, tri.ctypes.data))
+        return pos, nrm, tri
+
+    def mesh_field(self):
+        """The counts of the lattice of the last extract_mesh, uint32[n_z, n_y, n_x]; synchronises."""
+        dims = (_U32 * 3)()
+        _check(self.L.sph_mesh_field_dims(self.h, dims))
+        out = np.empty((dims[2], dims[1], dims[0]), np.uint32)
+        _check(self.L.sph_mesh_field_read(self.h, out.ctypes.data))
+        return out
+
+    def save_obj(self, path):
+        """The last mesh as a Wavefront OBJ file (v, vn, f a//a b//b c//c)."""
+        _check(self.L.sph_mesh_save_obj(self.h, os.fsencode(path)))
 
     def positions4(self):
         out = np.empty((self.capacity, 4), dtype=np.float32)

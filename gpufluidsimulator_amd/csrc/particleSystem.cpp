@@ -114,6 +114,7 @@ ParticleSystem::ParticleSystem(uint numParticles, float3 boxDims, ParticleComput
     setCamera(640, 480, eye, target, 60.0f);
     setRenderColor(SPH_COLOR_INDEX);
     setRenderSurface(false);
+    setMeshParams(nullptr);
 }
 
 ParticleSystem::~ParticleSystem() {
@@ -470,6 +471,27 @@ void ParticleSystem::writeFrame(const char* path) {
     fprintf(f, "P6\n%u %u\n255\n", w, h);
     const bool ok = fwrite(m_frame.data(), 3, (size_t)w * h, f) == (size_t)w * h;
     if (fclose(f) != 0 || !ok) { fprintf(stderr, "ParticleSystem: cannot write %s\n", path); exit(EXIT_FAILURE); }
+}
+
+// ---- geometry (sph_mesh_extract) ---------------------------------------------------------------------------
+void ParticleSystem::setMeshParams(const sph_mesh_params* p) {
+    if (p) m_meshParams = *p;
+    else sph_mesh_defaults(&m_meshParams);
+}
+
+uint ParticleSystem::extractMesh(std::vector<float>& pos, std::vector<float>& nrm, std::vector<uint32_t>& tri) {
+    uint32_t nv = 0, nt = 0;
+    SPH_CHECK(sph_mesh_extract(m_ctx, &m_meshParams, &nv, &nt));
+    pos.resize((size_t)nv * 3);
+    nrm.resize((size_t)nv * 3);
+    tri.resize((size_t)nt * 3);
+    SPH_CHECK(sph_mesh_read(m_ctx, pos.data(), nrm.data(), tri.data()));
+    return nt;
+}
+
+void ParticleSystem::writeMeshOBJ(const char* path) {
+    SPH_CHECK(sph_mesh_extract(m_ctx, &m_meshParams, nullptr, nullptr));
+    SPH_CHECK(sph_mesh_save_obj(m_ctx, path));
 }
 
 void ParticleSystem::saveState(const std::string& path) { SPH_CHECK(sph_snapshot_save(m_ctx, path.c_str())); }

@@ -271,6 +271,20 @@ struct sph_ctx {
     bool rd_surface = false;                    // the last render was a surface render (sph_render_surface_read)
     bool rd_sf_thick_on = false;                // ... and its thickness pass ran
 
+    // the mesh of the last sph_mesh_extract (sph_mesh.hip): the lattice's counts and vertex bases (4 + 4 bytes per node), the
+    // scans' block sums with the two totals and the case table in front (mesh_aux), and the vertices, normals and triangles.
+    // Allocated at the first extraction or when one must grow; never by a caller who does not mesh.
+    uint32_t* mesh_field = nullptr;
+    uint32_t* mesh_vbase = nullptr;
+    uint32_t* mesh_aux = nullptr;
+    float* mesh_vpos = nullptr;
+    float* mesh_vnrm = nullptr;
+    uint32_t* mesh_tri = nullptr;
+    uint32_t mesh_nodes_cap = 0, mesh_v_cap = 0, mesh_t_cap = 0;   // what the buffers hold: nodes, vertices, triangles
+    uint32_t mesh_dims[3] = {0, 0, 0};          // the lattice of the last extraction
+    uint32_t mesh_nv = 0, mesh_nt = 0;
+    bool mesh_valid = false;
+
     // pair kernels: a (dz, dy) row whose staged hull would exceed this many slots is read straight from global memory
     // by every lane instead (sph_pairs.hip: traverse; sph_set_direct_hull)
     uint32_t direct_hull = 512;

@@ -25,6 +25,13 @@
 //                      pixels (r 0..16, K 0..8; default 5,2) with the depth falloff tau (world units; default 0: four particle
 //                      radii), normals from it, a water-like shading with the base colour -tint (default 0.25,0.55,0.95) and
 //                      the absorption -absorb per unit of thickness (default 6,2,0.5; 0,0,0: no thickness pass)
+//   -mesh=DIR [-meshevery=K] [-meshcell=s] [-meshradius=r] [-iso=v]   geometry: after the updates 0, K, 2K, ... (K = 1 by default)
+//                      the fluid's surface is extracted on the device as a triangle mesh (ParticleSystem::writeMeshOBJ,
+//                      sph_mesh_extract) and written to DIR/mesh_NNNNN.obj (Wavefront OBJ: v, vn, f), NNNNN the 0-based number of
+//                      the update the mesh follows.  -meshcell the lattice spacing (default: the particle radius), -meshradius
+//                      the particles' reach (default: three spacings, at most eight), -iso the level (default 0.5).  Independent
+//                      of -frames; both may be given.  One device only.  At the end one line tells the mesh of the final state
+//                      (ParticleSystem::extractMesh): vertices, triangles and an FNV-1a hash of positions, normals, triangles.
 // Several GPUs (no counterpart in the reference, which is a single-device program): -gpus=N cuts the dam into N
 // z-slabs and steps them with sph_slab_step through the C ABI --
 //   -gpus=N            N child PROCESSES, forked before anything touches a GPU, rank r on device r (+ -device=), messages
@@ -420,7 +427,8 @@ int main(int argc, char** argv) {
                "[-collider=<x>,<y>,<z>,<radius>[,<ux>,<uy>,<uz>]] [-collidermass=<M>[,<ax>,<ay>,<az>]] [-emit=<x>,<y>,<z>,<r>,<vx>,<vy>,<vz>,<every>] "
                "[-drain=<x0>,<y0>,<z0>,<x1>,<y1>,<z1>[,<every>]] [-add=<update>,<count>] [-capacity=<particles>] [-out=<file>] [-save=<file>] [-load=<file>] [-file=<file>] "
                "[-frames=<dir> [-frameevery=<K>] [-framesize=<W>x<H>] [-camera=<ex>,<ey>,<ez>,<tx>,<ty>,<tz>[,<fovy>]] [-color=index|speed:<lo>:<hi>|density:<lo>:<hi>] "
-               "[-surface[=<r>,<K>[,<tau>]] [-tint=<r>,<g>,<b>] [-absorb=<r>,<g>,<b>]]]\n"
+               "[-surface[=<r>,<K>[,<tau>]] [-tint=<r>,<g>,<b>] [-absorb=<r>,<g>,<b>]]] "
+               "[-mesh=<dir> [-meshevery=<K>] [-meshcell=<s>] [-meshradius=<r>] [-iso=<v>]]\n"
                "  -collider: a solid sphere the fluid flows around, moving at (ux, uy, uz) (default: at rest); one device only\n"
                "  -collidermass: the -collider sphere is a free body of mass M > 0 that the fluid pushes, under the acceleration (ax, ay, az) "
                "(default: (0, gravity_y, 0) of the run), or with M = 0 a kinematic obstacle whose load is wanted; prints its centre, velocity "
@@ -434,7 +442,11 @@ int main(int argc, char** argv) {
                "  -surface: with -frames, draw the fluid as a surface instead of sphere sprites: the spheres' depth smoothed <K> times (0..8, "
                "default 2) over a radius of <r> pixels (0..16, default 5) with the depth falloff <tau> (world units, default 0 = four particle "
                "radii), normals from the smoothed depth and a water-like shading; -tint the base colour (default 0.25,0.55,0.95), -absorb the "
-               "absorption per unit of thickness and channel (default 6,2,0.5; 0,0,0 = no thickness pass); one device only\n");
+               "absorption per unit of thickness and channel (default 6,2,0.5; 0,0,0 = no thickness pass); one device only\n"
+               "  -mesh: extract the fluid's surface on the device as a closed triangle mesh after the updates 0, K, 2K, ... (-meshevery=K, "
+               "default 1) and write <dir>/mesh_NNNNN.obj (Wavefront OBJ), NNNNN = the 0-based number of the update the mesh follows; "
+               "-meshcell the lattice spacing (default: the particle radius), -meshradius each particle's reach (default three spacings, "
+               "at most eight), -iso the level of the surface (default 0.5); independent of -frames; one device only\n");
         return 0;
     }
     const int gpus = value(argc, argv, "gpus") ? atoi(value(argc, argv, "gpus")) : 1;
@@ -551,6 +563,29 @@ int main(int argc, char** argv) {
                 for (int q = 0; q < 3; q++) fields[a][q] = c3[q];
             }
     }
+    // -mesh=DIR [-meshevery=K] [-meshcell=s] [-meshradius=r] [-iso=v]
+    const char* meshDir = value(argc, argv, "mesh");
+    int meshEvery = 1;
+    sph_mesh_params meshParams;
+    sph_mesh_defaults(&meshParams);
+    if (flag(argc, argv, "mesh") && (!meshDir || !*meshDir)) { fprintf(stderr, "-mesh: expected -mesh=<directory>\n"); return EXIT_FAILURE; }
+    if (const char* v = value(argc, argv, "meshevery")) {
+        if (sscanf(v, "%d%c", &meshEvery, &extra) != 1 || meshEvery < 1) { fprintf(stderr, "-meshevery=%s: expected a whole number >= 1\n", v); return EXIT_FAILURE; }
+    }
+    {
+        const char* names[3] = {"meshcell", "meshradius", "iso"};
+        float* fields[3] = {&meshParams.spacing, &meshParams.radius, &meshParams.iso};
+        for (int a = 0; a < 3; a++)
+            if (const char* v = value(argc, argv, names[a])) {
+                float x = 0.f;
+                if (sscanf(v, "%f%c", &x, &extra) != 1 || !std::isfinite(x) || !(x > 0.f)) { fprintf(stderr, "-%s=%s: expected a number > 0 (an option of -mesh=<directory>)\n", names[a], v); return EXIT_FAILURE; }
+                *fields[a] = x;
+            }
+        if (!meshDir && (value(argc, argv, "meshevery") || value(argc, argv, "meshcell") || value(argc, argv, "meshradius") || value(argc, argv, "iso"))) {
+            fprintf(stderr, "-meshevery / -meshcell / -meshradius / -iso: expected -mesh=<directory> next to them\n");
+            return EXIT_FAILURE;
+        }
+    }
     int addAt = -1, addCount = 0;
     const char* addArg = value(argc, argv, "add");
     if (addArg && (sscanf(addArg, "%d,%d", &addAt, &addCount) != 2 || addAt < 0 || addCount < 1)) {
@@ -567,6 +602,11 @@ int main(int argc, char** argv) {
         if (surfaceOn) {
             fprintf(stderr, "-surface is not supported with -gpus=%d%s: sph_render_surface works on a whole-domain context (the ranks would "
                             "have to composite their images); run it on one device\n", gpus, gpus == 1 ? " -slab" : "");
+            return EXIT_FAILURE;
+        }
+        if (meshDir) {
+            fprintf(stderr, "-mesh is not supported with -gpus=%d%s: sph_mesh_extract works on a whole-domain context (the ranks would have to "
+                            "share a lattice seam); run it on one device\n", gpus, gpus == 1 ? " -slab" : "");
             return EXIT_FAILURE;
         }
         if (framesDir) {
@@ -648,6 +688,13 @@ int main(int argc, char** argv) {
         psystem->setRenderColor(colorMode, colorLo, colorHi);
         psystem->setRenderSurface(surfaceOn, &surfaceStyle);
     }
+    if (meshDir) {
+        uint32_t md[3];
+        float mo[3];
+        if (sph_mesh_lattice(psystem->context(), &meshParams, md, mo) < 0) { fprintf(stderr, "-mesh: %s\n", sph_last_error()); return EXIT_FAILURE; }
+        if (mkdir(meshDir, 0755) != 0 && errno != EEXIST) { fprintf(stderr, "-mesh=%s: cannot create the directory\n", meshDir); return EXIT_FAILURE; }
+        psystem->setMeshParams(&meshParams);
+    }
     uint3 g = psystem->getGridSize();
     printf("Run %u particles simulation for %d iterations... (grid %ux%ux%u, box %g)\n\n", numParticles, iterations, g.x, g.y, g.z, box);
     if (!flag(argc, argv, "nowarmup")) psystem->update(timestep, 0);   // warm-up step, not timed
@@ -705,6 +752,10 @@ int main(int argc, char** argv) {
             psystem->renderFrame();
             psystem->writeFrame(path.c_str());
         }
+        if (meshDir && i % meshEvery == 0) {
+            const std::string path = std::string(meshDir) + "/mesh_" + std::to_string(100000 + i % 100000).substr(1) + ".obj";
+            psystem->writeMeshOBJ(path.c_str());
+        }
     }
     sph_sync(psystem->context());
     auto t1 = std::chrono::steady_clock::now();
@@ -722,6 +773,18 @@ int main(int argc, char** argv) {
         const float3 cc = psystem->getColliderPos(), cu = psystem->getColliderVelocity();
         printf("collider: centre %.9g %.9g %.9g velocity %.9g %.9g %.9g impulse %.17g %.17g %.17g\n", cc.x, cc.y, cc.z, cu.x, cu.y, cu.z,
                J[0], J[1], J[2]);
+    }
+    if (meshDir) {       // the mesh of the final state through ParticleSystem::extractMesh: its size and an FNV-1a hash of its bytes
+        std::vector<float> mp, mn;
+        std::vector<uint32_t> mt;
+        psystem->extractMesh(mp, mn, mt);
+        unsigned long long hsh = 1469598103934665603ull;
+        auto mix = [&hsh](const void* data, size_t bytes) {
+            const unsigned char* b = (const unsigned char*)data;
+            for (size_t q = 0; q < bytes; q++) { hsh ^= b[q]; hsh *= 1099511628211ull; }
+        };
+        mix(mp.data(), mp.size() * 4); mix(mn.data(), mn.size() * 4); mix(mt.data(), mt.size() * 4);
+        printf("mesh: %zu vertices, %zu triangles, fnv1a64 %016llx\n", mp.size() / 3, mt.size() / 3, hsh);
     }
     if (dump > 0) psystem->dumpParticles(0, (uint)dump);
     if (const char* v = value(argc, argv, "out")) {      // xyzw per creation index, then vxyz0, raw fp32

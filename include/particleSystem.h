@@ -146,6 +146,16 @@ public:
     void* getFrameDevice(uint* width, uint* height);
     void writeFrame(const char* path);
 
+    // ---- additive: geometry (sph_mesh_extract of sph_hip.h; the reference has nothing here) ----------------------------------
+    // The parameters of the next extractMesh / writeMeshOBJ (nullptr: sph_mesh_defaults -- spacing = the particle radius,
+    // radius = three spacings, iso = 0.5).
+    void setMeshParams(const sph_mesh_params* p = nullptr);
+    // The surface of the particles as they are, extracted on the device: 3 floats per vertex, 3 per normal, 3 vertex numbers
+    // per triangle, in the fixed order of the rule; returns the number of triangles.  Waits for the device.
+    uint extractMesh(std::vector<float>& pos, std::vector<float>& nrm, std::vector<uint32_t>& tri);
+    // Extract, and write a Wavefront OBJ (sph_mesh_save_obj).
+    void writeMeshOBJ(const char* path);
+
     // ---- additive (absent upstream; named by BASELINE.json's north star) ------------------------
     // 4 floats per particle, by creation index (the original NVIDIA sample's layout), getCapacity() rows; the pointer
     // stays valid until the next getArray call.
@@ -204,6 +214,7 @@ protected:
     bool m_surfaceOn;
     sph_surface_style m_surfaceStyle;
     std::vector<unsigned char> m_frame;              // RGBA staging of writeFrame
+    sph_mesh_params m_meshParams;
     std::string m_logPath;
     void* m_log;
     double m_logLastMs, m_logGlobalMs, m_logFreqMs;

@@ -31,7 +31,8 @@
  *                  sph_positions_dev sph_download_positions4 sph_snapshot_save sph_snapshot_load sph_snapshot_info |
  *                  sph_set_colliders sph_get_colliders sph_set_collider_bodies sph_get_collider_impulses | sph_emit sph_remove sph_count_in_regions |
  *                  sph_camera_look_at sph_render sph_render_read sph_render_image_dev sph_surface_defaults sph_render_surface
- *                  sph_render_surface_read |
+ *                  sph_render_surface_read | sph_mesh_defaults sph_mesh_lattice sph_mesh_extract sph_mesh_read sph_mesh_dev
+ *                  sph_mesh_save_obj |
  *                  sph_hash sph_sort sph_build_cells sph_density sph_force sph_collide sph_integrate sph_step sph_step_phased
  *                  sph_force_collide_integrate | sph_timing_enable sph_timing_get sph_timing_reset | the z-slab phase calls
  *                  (sph_migrants_* sph_slab_counts sph_halo_* sph_layer_histogram) | sph_rccl_unique_id
@@ -40,7 +41,7 @@
  *                  sph_slab_failed sph_slab_timing_enable/_reset/_get
  *   [introspect]   read-only views for parity tests, profiles and bench lines; may grow or change with the implementation:
  *                  sph_get_keys sph_get_order sph_get_cell_range sph_get_cells sph_cell_key sph_download_forces sph_sort_stats
- *                  sph_sort_forms sph_last_sort_skipped sph_slab_stats sph_slab_counters sph_slab_in_place_merges
+ *                  sph_mesh_field_dims sph_mesh_field_read sph_sort_forms sph_last_sort_skipped sph_slab_stats sph_slab_counters sph_slab_in_place_merges
  *                  sph_slab_exchanges sph_slab_recut_stats sph_slab_early_force_stats sph_slab_protocol sph_rccl_transport_info
  *   [tuning]       switches whose defaults are the product's settings; in fp32 results do not depend on them (A/B runs):
  *                  sph_set_sort_mode sph_set_direct_hull sph_set_pair_small_launch sph_set_block_order sph_slab_set_early_force
@@ -492,6 +493,89 @@ int sph_render_surface(sph_ctx* c, const sph_camera* camera, const sph_render_st
  * when the thickness pass was off), normal_xyz 3 floats per pixel.  Any pointer may be NULL.  Synchronises.  SPH_E_STATE unless
  * the last render was a surface render. */
 int sph_render_surface_read(sph_ctx* c, float* raw_depth, uint32_t* thickness_q, float* normal_xyz);
+
+/* ---- geometry: the fluid's surface as a triangle mesh, extracted on the device (no counterpart in the reference, which only draws
+ *      into a GL window) ---------------------------------------------------------------------------------------------------------
+ * A count field is splatted onto a regular lattice over the box, and the level set count >= iso_q is triangulated by cutting
+ * every lattice cube into six tetrahedra.  Whole-domain contexts only.  Reads the sorted positions; writes none of the context's
+ * step flags and no particle array.  A caller who never meshes gets the launches and the allocations of a library without this
+ * section.
+ *
+ * THE RULE (fp32, every operation rounded, no multiply-add fusion, sums left to right, IEEE division and square root;
+ * tests/mesh_model.py is the same arithmetic in numpy and gives counts, positions, normals and triangles bit for bit).
+ * PARAMETERS.  s = spacing (0: params.particle_radius), r = radius (0: 3.0f * s), iso (0: 0.5f).  r / s <= SPH_MESH_MAX_REACH.
+ * LATTICE (sph_mesh_lattice; in double on the host, each result rounded once):
+ *     pad = ceil(r / s) + 1 ;  n_k = ceil((box_max_k - box_min_k) / s) + 1 + 2*pad ;  origin_k = box_min_k - (float)pad * s  (fp32)
+ * Node i of axis k sits at X = origin_k + (float)i * s.  The pad leaves the outermost nodes at 0 for every particle inside the
+ * box, so EVERY MESH IS CLOSED, also where fluid lies against a wall (particles outside the box can break that).  Limits: every
+ * n_k <= SPH_MESH_MAX_DIM, n_x*n_y*n_z <= SPH_MESH_MAX_NODES (hence fewer than 2^32 vertices and triangles): else SPH_E_CAPACITY.
+ * (The default r = 3.0f * s divided by s in double is 3 up to fp32 rounding: where the product rounded up, ceil gives a reach of
+ * 4 and a pad of 5 -- s = 1/15 --, else 3 and 4 -- s = 1/64.  The default spacing, the particle radius 1/64, fits a box of edge up
+ * to about 7.8: of the standard scenes only config 1's; configs 2 and 3 (edges 8 and 32) need a wider spacing and are refused
+ * at the defaults.)
+ * FIELD: one uint32 count per node.  For every owned particle p and every node of the lattice, r2 = r*r:
+ *     dx = X - p.x (likewise dy, dz) ;  d2 = (dx*dx + dy*dy) + dz*dz ;  if d2 < r2:
+ *         t = 1.0f - d2 / r2 ;  w = (t*t)*t ;  q = (uint32_t)(w*4096.0f + 0.5f) ;  count += q
+ * with a 32-bit INTEGER atomic add: the sum does not depend on the order of arrival, and no floating-point atomic is involved.
+ * (The kernel walks the nodes within ceil(r/s) + 1 of floor((p.x - origin_x) / s) per axis -- a superset of those that pass while
+ * |X| / s stays below 2^20.)  A count overflows only with 2^20 particles within r of one node; that is not checked.
+ *     v = iso*4096.0f + 0.5f ;  iso_q = max(1, v < 2^32 ? (uint32_t)v : 0xFFFFFFFF) ;  a node is INSIDE iff count >= iso_q  (integers)
+ * CELLS.  The cube with base node (i, j, k), i < n_x - 1 and likewise j, k, has corners c = 0..7 with bit 0 = +x, bit 1 = +y,
+ * bit 2 = +z, and is cut into the six Kuhn tetrahedra (0, e_a, e_a|e_b, 7) of the axis orders m = 0..5: xyz, xzy, yxz, yzx, zxy,
+ * zyx.  Every edge of a tetrahedron joins corners cu, cv with cu a subset of cv: it is the LATTICE EDGE (node base + bits(cu),
+ * direction d = cu ^ cv in 1..7), which neighbouring tetrahedra and neighbouring cubes share -- the triangulation is
+ * face-compatible with nothing but 16 cases per tetrahedron.
+ * VERTICES.  A lattice edge (node a, direction d) whose far node b = a + bits(d) is in the lattice and whose ends differ in
+ * inside-ness owns one vertex.  With the counts Ca, Cb and the node positions Xa, Xb:
+ *     t = ((float)iso_q - (float)Ca) / ((float)Cb - (float)Ca) ;  position = Xa + t*(Xb - Xa) per component
+ *     G at a node = ((float)((int64)C(i+1,j,k) - (int64)C(i-1,j,k)), likewise y, z), neighbours outside the lattice counting 0
+ *     g = Ga + t*(Gb - Ga) per component ;  len2 = (g.x*g.x + g.y*g.y) + g.z*g.z
+ *     normal = (-g) / sqrtf(len2) per component, or (0, 0, 0) unless len2 is finite and > 0        (it points out of the fluid)
+ * VERTEX ORDER: the node's linear index (k*n_y + j)*n_x + i ascending, then d ascending.  A node whose count equals iso_q gives
+ * t = 0 on its edges: coincident vertices and triangles of zero area; the mesh stays closed combinatorially.
+ * TRIANGLES are uint32 triples of vertex numbers.  Per tetrahedron with corners v0..v3 (XY: the vertex on the edge X-Y):
+ *     one corner A unlike the other three B, C, D (in corner order):           (AB, AC, AD)
+ *     two inside A, B and two outside C, D (each pair in corner order):        (AC, AD, BD) then (AC, BD, BC)
+ * each wound so that (p1 - p0) x (p2 - p0) points from the inside corners to the outside ones.  That sign is a constant of
+ * (m, case): it is evaluated with every vertex at its edge's midpoint against (centroid of the outside corners - centroid of the
+ * inside corners), and where it is negative the last two vertices are swapped.
+ * TRIANGLE ORDER: the cube's linear index (the same formula, on its base node) ascending, then m ascending, then as listed. */
+#define SPH_MESH_MAX_REACH 8
+#define SPH_MESH_MAX_DIM 2048
+#define SPH_MESH_MAX_NODES (1u << 27)
+typedef struct sph_mesh_params {
+    float spacing;    /* s > 0; 0 = params.particle_radius */
+    float radius;     /* r > 0; 0 = 3 * s */
+    float iso;        /* > 0; 0 = 0.5 (a lone particle's count is 1 at its centre) */
+} sph_mesh_params;
+void sph_mesh_defaults(sph_mesh_params* p);      /* all three 0 */
+/* Host helper: the lattice sph_mesh_extract would use for these parameters (NULL: the defaults) in this context's box.
+ * SPH_E_INVALID / SPH_E_CAPACITY as sph_mesh_extract; dims and origin are then untouched. */
+int sph_mesh_lattice(const sph_ctx* c, const sph_mesh_params* p, uint32_t dims[3], float origin[3]);
+/* Extract the surface of the owned particles as they are now (p NULL: the defaults).  Queues the field and the counting kernels,
+ * waits ONCE for the two totals (an export call, not part of a step), grows the vertex and triangle buffers if it must and queues
+ * the kernels that fill them.  Legal at any stage, like sph_render: before the first step, between two phases, with no
+ * particle (0 vertices, 0 triangles, SPH_OK).  Device buffers (8 bytes per lattice node and 2 words per 256 nodes; 24 bytes per
+ * vertex, 12 per triangle) are allocated at the first extraction or when one must grow, and freed by sph_destroy.
+ *   SPH_E_INVALID   a parameter that is negative or not finite; r / s > SPH_MESH_MAX_REACH;
+ *   SPH_E_CAPACITY  the lattice limits above;
+ *   SPH_E_STATE     a slab context: the ranks would have to share a lattice seam.  Out of scope, as for render, emitters and bodies.
+ * In every refused case nothing has changed and nothing was allocated.  SPH_E_NOMEM: the mesh buffers are all released and there
+ * is no mesh until the next extraction. */
+int sph_mesh_extract(sph_ctx* c, const sph_mesh_params* p, uint32_t* n_vertices, uint32_t* n_triangles);
+/* The last mesh to the host: 3 floats per vertex, 3 floats per vertex, 3 vertex numbers per triangle.  Any pointer may be NULL.
+ * Synchronises.  SPH_E_STATE before any extraction (also for sph_mesh_dev, sph_mesh_save_obj, sph_mesh_field_dims / _read). */
+int sph_mesh_read(sph_ctx* c, float* pos_xyz, float* normal_xyz, uint32_t* tri);
+/* Device pointers of the last mesh for a consumer on the same stream (any may be NULL; the pointers are NULL while no extraction
+ * has produced a vertex yet).  Valid until the next extraction. */
+int sph_mesh_dev(sph_ctx* c, void** pos_dev, void** normal_dev, void** tri_dev, uint32_t* n_vertices, uint32_t* n_triangles);
+/* Wavefront OBJ: "v x y z" and "vn x y z" per vertex with %.9g (an fp32 survives the round trip), "f a//a b//b c//c" per
+ * triangle, 1-based.  Synchronises.  SPH_E_INVALID if the file cannot be written. */
+int sph_mesh_save_obj(sph_ctx* c, const char* path);
+/* The lattice of the last extraction: its dimensions (no synchronisation), and its counts, n_x*n_y*n_z words, x fastest
+ * (synchronises). */
+/* [introspect] */ int sph_mesh_field_dims(sph_ctx* c, uint32_t dims[3]);
+/* [introspect] */ int sph_mesh_field_read(sph_ctx* c, uint32_t* counts);
 
 /* State snapshot (checkpoint / resume; absent in the reference, whose device state is never
  * serialised -- SURVEY.md section 5).  The file holds the parameters and, IN SLOT ORDER, position,
