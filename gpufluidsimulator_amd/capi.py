@@ -79,6 +79,45 @@ class Region(C.Structure):
         return cls(REGION_HALFSPACE, (C.c_float * 3)(*[float(v) for v in point]), (C.c_float * 3)(*[float(v) for v in normal]), 0.0)
 
 
+MAX_SHAPES = 16                       # SPH_MAX_SHAPES
+OBSTACLE_MAX_DIM = 2048               # SPH_OBSTACLE_MAX_DIM
+OBSTACLE_MAX_NODES = 1 << 27          # SPH_OBSTACLE_MAX_NODES
+OBSTACLE_PUSH_ITERATIONS = 4          # SPH_OBSTACLE_PUSH_ITERATIONS
+SHAPE_SPHERE, SHAPE_BOX, SHAPE_CAPSULE, SHAPE_HALFSPACE = 0, 1, 2, 3
+
+
+def _f3(v):
+    return (C.c_float * 3)(*[float(x) for x in v])
+
+
+class Shape(C.Structure):
+    """`sph_shape` of include/sph_hip.h: one analytic solid of sph_obstacle_build (36 bytes)."""
+    _fields_ = [("kind", C.c_int32), ("invert", C.c_int32), ("a", C.c_float * 3), ("b", C.c_float * 3), ("r", C.c_float)]
+
+    @classmethod
+    def sphere(cls, center, radius, invert=False):
+        return cls(SHAPE_SPHERE, int(bool(invert)), _f3(center), _f3((0, 0, 0)), float(radius))
+
+    @classmethod
+    def box(cls, center, half_extents, rounding=0.0, invert=False):
+        """Axis-aligned, optionally with rounded edges."""
+        return cls(SHAPE_BOX, int(bool(invert)), _f3(center), _f3(half_extents), float(rounding))
+
+    @classmethod
+    def capsule(cls, end_a, end_b, radius, invert=False):
+        return cls(SHAPE_CAPSULE, int(bool(invert)), _f3(end_a), _f3(end_b), float(radius))
+
+    @classmethod
+    def halfspace(cls, point, normal, invert=False):
+        """Solid on the side the normal points away from."""
+        return cls(SHAPE_HALFSPACE, int(bool(invert)), _f3(point), _f3(normal), 0.0)
+
+
+class ObstacleGrid(C.Structure):
+    """`sph_obstacle_grid` of include/sph_hip.h: node (i, j, k) sits at origin + (i, j, k) * spacing; x fastest."""
+    _fields_ = [("dims", C.c_uint32 * 3), ("origin", C.c_float * 3), ("spacing", C.c_float)]
+
+
 RENDER_MAX_RADIUS_PX = 64   # SPH_RENDER_MAX_RADIUS_PX
 RENDER_MAX_SIZE = 4096      # SPH_RENDER_MAX_SIZE
 COLOR_MODES = {"index": 0, "speed": 1, "density": 2}      # SPH_COLOR_*
@@ -163,6 +202,14 @@ SIGNATURES = {
     "sph_surface_defaults": (None, [C.POINTER(SurfaceStyle)]),
     "sph_render_surface": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(RenderStyle), C.POINTER(SurfaceStyle)]),
     "sph_render_surface_read": (C.c_int, [_P, _P, _P, _P]),
+    "sph_obstacle_lattice": (C.c_int, [_P, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(ObstacleGrid)]),
+    "sph_obstacle_build": (C.c_int, [_P, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), _U32, C.POINTER(Shape)]),
+    "sph_obstacle_set_grid": (C.c_int, [_P, C.POINTER(ObstacleGrid), _P]),
+    "sph_obstacle_clear": (C.c_int, [_P]),
+    "sph_obstacle_set_motion": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "sph_obstacle_get": (C.c_int, [_P, C.POINTER(ObstacleGrid), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "sph_obstacle_read": (C.c_int, [_P, _P]),
+    "sph_obstacle_sample": (C.c_int, [_P, _U32, _P, _P, _P, _P]),
     "sph_mesh_defaults": (None, [C.POINTER(MeshParams)]),
     "sph_mesh_lattice": (C.c_int, [_P, C.POINTER(MeshParams), C.POINTER(_U32), C.POINTER(C.c_float)]),
     "sph_mesh_extract": (C.c_int, [_P, C.POINTER(MeshParams), C.POINTER(_U32), C.POINTER(_U32)]),
@@ -542,6 +589,70 @@ class Context:
         return {"centers": np.array([list(r.center) for r in rows], np.float32).reshape(-1, 3),
                 "radii": np.array([r.radius for r in rows], np.float32),
                 "velocities": np.array([list(r.velocity) for r in rows], np.float32).reshape(-1, 3)}
+
+    # -- obstacles (whole-domain contexts; include/sph_hip.h: sph_obstacle_build and the calls next to it) -------------------------
+    @staticmethod
+    def _bounds(bounds):
+        if bounds is None:
+            return None, None
+        lo, hi = bounds
+        return _f3(lo), _f3(hi)
+
+    def obstacle_lattice(self, spacing=0.0, bounds=None) -> ObstacleGrid:
+        """The lattice build_obstacle would use: a host helper.  bounds = (lo, hi) or None (the box)."""
+        g = ObstacleGrid()
+        lo, hi = self._bounds(bounds)
+        _check(self.L.sph_obstacle_lattice(self.h, float(spacing), lo, hi, C.byref(g)))
+        return g
+
+    def build_obstacle(self, shapes, spacing=0.0, bounds=None):
+        """Rasterise the union of `shapes` (Shape.sphere / box / capsule / halfspace) on the device and install it as the
+        context's obstacle: every later integrate pushes the particles out of it.  spacing 0 = the particle diameter."""
+        shapes = list(shapes)
+        arr = (Shape * max(len(shapes), 1))(*shapes)
+        lo, hi = self._bounds(bounds)
+        _check(self.L.sph_obstacle_build(self.h, float(spacing), lo, hi, len(shapes), arr))
+
+    def set_obstacle_grid(self, phi, origin, spacing):
+        """Install the caller's signed distances: phi of shape (n_z, n_y, n_x) (x fastest), float32; negative inside the solid."""
+        phi = np.ascontiguousarray(phi, dtype=np.float32)
+        if phi.ndim != 3:
+            raise ValueError("phi must have the shape (n_z, n_y, n_x)")
+        g = ObstacleGrid((_U32 * 3)(phi.shape[2], phi.shape[1], phi.shape[0]), _f3(origin), float(spacing))
+        _check(self.L.sph_obstacle_set_grid(self.h, C.byref(g), phi.ctypes.data))
+
+    def clear_obstacle(self):
+        _check(self.L.sph_obstacle_clear(self.h))
+
+    def set_obstacle_motion(self, offset=None, velocity=None):
+        """Offset and / or velocity of the grid (None = keep): the offset advances by dt * velocity once per step."""
+        _check(self.L.sph_obstacle_set_motion(self.h, None if offset is None else _f3(offset),
+                                              None if velocity is None else _f3(velocity)))
+
+    def obstacle(self, read=False):
+        """None without an obstacle, else {"dims": (n_x, n_y, n_z), "origin", "spacing", "offset", "velocity"} with the advanced
+        offset; read=True adds "phi", the installed (clamped) field of shape (n_z, n_y, n_x) (synchronises)."""
+        g, off, vel = ObstacleGrid(), (C.c_float * 3)(), (C.c_float * 3)()
+        _check(self.L.sph_obstacle_get(self.h, C.byref(g), off, vel))
+        if not any(g.dims):
+            return None
+        out = {"dims": tuple(int(v) for v in g.dims), "origin": np.array(list(g.origin), np.float32),
+               "spacing": np.float32(g.spacing), "offset": np.array(list(off), np.float32),
+               "velocity": np.array(list(vel), np.float32)}
+        if read:
+            phi = np.empty(out["dims"][::-1], np.float32)
+            _check(self.L.sph_obstacle_read(self.h, phi.ctypes.data))
+            out["phi"] = phi
+        return out
+
+    def sample_obstacle(self, points):
+        """(phi (n,), normal (n, 3), inside_grid (n,) bool) of the obstacle at `points`, by the rule the particles see: phi =
+        +inf and normal 0 outside the grid.  Synchronises."""
+        pts = _f32(points, 3)
+        n = pts.shape[0]
+        phi, nrm, inside = np.empty(n, np.float32), np.empty((n, 3), np.float32), np.empty(n, np.uint8)
+        _check(self.L.sph_obstacle_sample(self.h, n, pts.ctypes.data, phi.ctypes.data, nrm.ctypes.data, inside.ctypes.data))
+        return phi, nrm, inside.astype(bool)
 
     # -- emitters and drains (whole-domain contexts; include/sph_hip.h: sph_emit, sph_remove, sph_count_in_regions) ------------
     @staticmethod

@@ -494,6 +494,19 @@ void ParticleSystem::writeMeshOBJ(const char* path) {
     SPH_CHECK(sph_mesh_save_obj(m_ctx, path));
 }
 
+// ---- solid obstacles (sph_obstacle_build) -------------------------------------------------------------------
+void ParticleSystem::setObstacles(const sph_shape* shapes, uint n, float spacing, const float* lo, const float* hi) {
+    SPH_CHECK(sph_obstacle_build(m_ctx, spacing, lo, hi, n, shapes));
+}
+
+void ParticleSystem::setObstacleGrid(const sph_obstacle_grid& grid, const float* phi) { SPH_CHECK(sph_obstacle_set_grid(m_ctx, &grid, phi)); }
+
+void ParticleSystem::setObstacleMotion(const float* offset, const float* velocity) {
+    SPH_CHECK(sph_obstacle_set_motion(m_ctx, offset, velocity));
+}
+
+void ParticleSystem::clearObstacles() { SPH_CHECK(sph_obstacle_clear(m_ctx)); }
+
 void ParticleSystem::saveState(const std::string& path) { SPH_CHECK(sph_snapshot_save(m_ctx, path.c_str())); }
 
 void ParticleSystem::loadState(const std::string& path) {

@@ -250,6 +250,15 @@ struct sph_ctx {
     uint32_t* trk_mask = nullptr;       // ceil(cap / 64) words, padded to a multiple of 4
     double* trk_J = nullptr;            // SPH_MAX_COLLIDERS x 3 doubles of the last integrate, then the step count (uint64)
 
+    // the obstacle (sph_obstacle.hip): the clamped signed distances, 4 bytes per node, and the minimum of every brick of
+    // OBSTACLE_BRICK^3 cells; ob_grid.dims = 0, 0, 0 and null pointers while there is none.  Allocated by the call that
+    // installs a grid, freed by sph_obstacle_clear; never by a caller who sets no obstacle.  The offset advances on the host
+    // once per step, next to the spheres' centres (sph_pairs.hip: advance_colliders).
+    sph_obstacle_grid ob_grid{};
+    float* ob_phi = nullptr;
+    float* ob_brick = nullptr;
+    float ob_off[3] = {0.f, 0.f, 0.f}, ob_vel[3] = {0.f, 0.f, 0.f};
+
     // the image of the last sph_render (sph_render.hip): per pixel a 64-bit key (depth bits << 32 | slot) and the resolved
     // RGBA8, creation index and depth.  Allocated at the first render, again when the image size changes; never by a caller
     // who does not render.
@@ -431,6 +440,11 @@ int step_hash(sph_ctx* c, bool ghosts_to_sort = false);
 int step_sort(sph_ctx* c, bool* owned_build_pending = nullptr);
 int step_cells(sph_ctx* c);
 int launch_integrate(sph_ctx* c, float dt);
+// the obstacle (sph_obstacle.hip): push the owned particles an integrate just wrote out of the solid.  `fused`: the launch wrote
+// posi2 / velr2 and the next keys k0, and, with `mark`, the movers' marks, which the pass keeps right; else posi / velr alone
+inline bool have_obstacle(const sph_ctx* c) { return c->ob_phi != nullptr; }
+int launch_obstacle_push(sph_ctx* c, bool fused, bool mark);
+void advance_obstacle(sph_ctx* c, float dt);
 // tracked contexts (sph_pairs.hip): write the host's sphere set into trk_table and zero J and the step count; refresh R + eps
 int launch_spheres_install(sph_ctx* c);
 int launch_spheres_radii(sph_ctx* c);

@@ -171,4 +171,11 @@ __device__ __forceinline__ uint32_t cell_key(const GridDesc& g, float x, float y
     return ((uint32_t)lz * g.g[1] + cy) * g.g[0] + cx;
 }
 
+// ---- the wall rule of one axis (kernelIntegrate, particleSystem.cu:375-420): lower wall first; x = wall +- eps, v *= damping.
+//      Used by the integrate (sph_pairs.hip), after the spheres, and after the obstacle's push (sph_obstacle.hip).
+__device__ __forceinline__ void wall(float& x, float& v, float lo, float hi, float eps, float damp) {
+    if (x - eps < lo) { x = lo + eps; v *= damp; }
+    if (x + eps > hi) { x = hi - eps; v *= damp; }
+}
+
 }  // namespace sph

@@ -3,6 +3,8 @@
 // output line (:176-192), on top of include/particleSystem.h.  No GLUT / OpenGL.
 //   sph_headless -benchmark -n=262144 -box=8 -i=100 [-device=0] [-grid=128] [-ic=grid|random] [-steps=1] [-dump=8]
 //                [-log=benchmark.txt [-logstyle=oscar|frames]] [-file=<snapshot>] [-collider=x,y,z,r[,ux,uy,uz]] [-collidermass=M[,ax,ay,az]]
+//                [-obstacle=<shape> ... [-obstaclecell=s] [-obstaclevel=ux,uy,uz]]
+// -obstacle: solid shapes the fluid collides with (ParticleSystem::setObstacles, sph_obstacle_build); see parse_obstacle below
 // -collider: the reference's collider sphere (centre, radius, and a velocity: default at rest), made to push the fluid
 // (ParticleSystem::enableCollider; one sphere, as the reference's UI has).
 //   -emit=x,y,z,r,vx,vy,vz,every   a faucet: before every `every`-th update (0, every, 2 every, ...) a lattice ball of radius r
@@ -81,6 +83,27 @@ static const char* value(int argc, char** argv, const char* name) {
         if (!strncmp(a, name, l) && a[l] == '=') return a + l + 1;
     }
     return nullptr;
+}
+
+// ---- -obstacle=sphere:cx,cy,cz,r | box:cx,cy,cz,hx,hy,hz[,r] | capsule:ax,ay,az,bx,by,bz,r | plane:px,py,pz,nx,ny,nz -------------
+// (repeatable; a leading `!` inverts the shape).  The library checks the values; this only checks the form.
+static bool parse_obstacle(const char* arg, sph_shape* out) {
+    sph_shape s{};
+    if (*arg == '!') { s.invert = 1; arg++; }
+    float v[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const char* colon = strchr(arg, ':');
+    if (!colon) return false;
+    const std::string kind(arg, colon);
+    char tail = 0;
+    const int k = sscanf(colon + 1, "%f,%f,%f,%f,%f,%f,%f%c", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &tail);
+    for (int a = 0; a < 3; a++) s.a[a] = v[a];
+    if (kind == "sphere" && k == 4) { s.kind = SPH_SHAPE_SPHERE; s.r = v[3]; }
+    else if (kind == "box" && (k == 6 || k == 7)) { s.kind = SPH_SHAPE_BOX; for (int a = 0; a < 3; a++) s.b[a] = v[3 + a]; s.r = k == 7 ? v[6] : 0.f; }
+    else if (kind == "capsule" && k == 7) { s.kind = SPH_SHAPE_CAPSULE; for (int a = 0; a < 3; a++) s.b[a] = v[3 + a]; s.r = v[6]; }
+    else if (kind == "plane" && k == 6) { s.kind = SPH_SHAPE_HALFSPACE; for (int a = 0; a < 3; a++) s.b[a] = v[3 + a]; }
+    else return false;
+    *out = s;
+    return true;
 }
 
 // ---- -gpus=N: z-slabs through the C ABI ---------------------------------------------------------------------------
@@ -424,7 +447,8 @@ int main(int argc, char** argv) {
         printf("usage: sph_headless [-benchmark] [-n=<particles>] [-box=<edge>] [-i=<iterations>] [-device=<id>] [-grid=<cells per axis>] "
                "[-ic=grid|random] [-steps=<per update>] [-gpus=<N> [-onegpu] [-slab] [-lattice=nx,ny,nz] [-protocol=1|3]] "
                "[-dump=<count>] [-log=<file> [-logfreq=<ms>] [-logstyle=oscar|frames]] [-sphere=<update>[,<radius>]] "
-               "[-collider=<x>,<y>,<z>,<radius>[,<ux>,<uy>,<uz>]] [-collidermass=<M>[,<ax>,<ay>,<az>]] [-emit=<x>,<y>,<z>,<r>,<vx>,<vy>,<vz>,<every>] "
+               "[-collider=<x>,<y>,<z>,<radius>[,<ux>,<uy>,<uz>]] [-collidermass=<M>[,<ax>,<ay>,<az>]] "
+               "[-obstacle=<shape> ... [-obstaclecell=<s>] [-obstaclevel=<ux>,<uy>,<uz>]] [-emit=<x>,<y>,<z>,<r>,<vx>,<vy>,<vz>,<every>] "
                "[-drain=<x0>,<y0>,<z0>,<x1>,<y1>,<z1>[,<every>]] [-add=<update>,<count>] [-capacity=<particles>] [-out=<file>] [-save=<file>] [-load=<file>] [-file=<file>] "
                "[-frames=<dir> [-frameevery=<K>] [-framesize=<W>x<H>] [-camera=<ex>,<ey>,<ez>,<tx>,<ty>,<tz>[,<fovy>]] [-color=index|speed:<lo>:<hi>|density:<lo>:<hi>] "
                "[-surface[=<r>,<K>[,<tau>]] [-tint=<r>,<g>,<b>] [-absorb=<r>,<g>,<b>]]] "
@@ -433,6 +457,10 @@ int main(int argc, char** argv) {
                "  -collidermass: the -collider sphere is a free body of mass M > 0 that the fluid pushes, under the acceleration (ax, ay, az) "
                "(default: (0, gravity_y, 0) of the run), or with M = 0 a kinematic obstacle whose load is wanted; prints its centre, velocity "
                "and last impulse at the end; one device only\n"
+               "  -obstacle: a solid the fluid collides with, [!]sphere:cx,cy,cz,r | [!]box:cx,cy,cz,hx,hy,hz[,r] | [!]capsule:ax,ay,az,bx,by,bz,r "
+               "| [!]plane:px,py,pz,nx,ny,nz (solid behind the normal); repeatable, the union is rasterised on the device as one grid of signed "
+               "distances over the box, `!` inverts a shape; -obstaclecell the grid spacing (default: the particle diameter), -obstaclevel a "
+               "uniform velocity of the whole grid; one device only\n"
                "  -emit: every <every> updates append a lattice ball of radius <r> spacings at (x, y, z) moving at (vx, vy, vz), if its place is clear\n"
                "  -drain: every <every> updates (default 1) remove the particles inside the box [x0,x1) x [y0,y1) x [z0,z1); one device only\n"
                "  -frames: render the particles on the device after the updates 0, K, 2K, ... (-frameevery=K, default 1) and write "
@@ -459,6 +487,31 @@ int main(int argc, char** argv) {
             fprintf(stderr, "-collider=%s: expected x,y,z,r or x,y,z,r,ux,uy,uz with r > 0\n", colliderArg);
             return EXIT_FAILURE;
         }
+    }
+    // -obstacle=<shape> (repeatable), -obstaclecell=s, -obstaclevel=ux,uy,uz
+    std::vector<sph_shape> obstacles;
+    for (int i = 1; i < argc; i++) {
+        const char* a = argv[i];
+        while (*a == '-') a++;
+        if (strncmp(a, "obstacle=", 9)) continue;
+        sph_shape sh;
+        if (!parse_obstacle(a + 9, &sh)) {
+            fprintf(stderr, "-obstacle=%s: expected [!]sphere:cx,cy,cz,r | [!]box:cx,cy,cz,hx,hy,hz[,r] | [!]capsule:ax,ay,az,bx,by,bz,r | "
+                            "[!]plane:px,py,pz,nx,ny,nz\n", a + 9);
+            return EXIT_FAILURE;
+        }
+        obstacles.push_back(sh);
+    }
+    float obstacleCell = 0.f, obstacleVel[3] = {0.f, 0.f, 0.f};
+    if (const char* v = value(argc, argv, "obstaclecell")) obstacleCell = (float)atof(v);
+    const char* obstacleVelArg = value(argc, argv, "obstaclevel");
+    if (obstacleVelArg && sscanf(obstacleVelArg, "%f,%f,%f", &obstacleVel[0], &obstacleVel[1], &obstacleVel[2]) != 3) {
+        fprintf(stderr, "-obstaclevel=%s: expected ux,uy,uz\n", obstacleVelArg);
+        return EXIT_FAILURE;
+    }
+    if (obstacles.empty() && (obstacleVelArg || value(argc, argv, "obstaclecell"))) {
+        fprintf(stderr, "-obstaclecell / -obstaclevel go with an -obstacle\n");
+        return EXIT_FAILURE;
     }
     // -collidermass=M[,ax,ay,az]
     float cm[4] = {0.f, 0.f, 0.f, 0.f};
@@ -620,6 +673,11 @@ int main(int argc, char** argv) {
                     gpus, gpus == 1 ? " -slab" : "");
             return EXIT_FAILURE;
         }
+        if (!obstacles.empty()) {
+            fprintf(stderr, "-obstacle is not supported with -gpus=%d%s: sph_obstacle_build works on a whole-domain context (the slab step "
+                            "makes several force launches per step); run it on one device\n", gpus, gpus == 1 ? " -slab" : "");
+            return EXIT_FAILURE;
+        }
         if (ic != ParticleSystem::CONFIG_GRID || load || value(argc, argv, "sphere") || value(argc, argv, "save") || value(argc, argv, "log") || dump) {
             fprintf(stderr, "-gpus=%d runs the dam-break lattice (-ic=grid) and takes -n -box -grid -i -steps -lattice -out -device -onegpu -nowarmup\n", gpus);
             return EXIT_FAILURE;
@@ -673,6 +731,10 @@ int main(int argc, char** argv) {
             psystem->setColliderMass(cm[0], cmFields == 4 ? cm + 1 : grav);
             if (cm[0] == 0.f) psystem->senseColliderImpulse(true);       // a kinematic obstacle: the impulse is all that is asked for
         }
+    }
+    if (!obstacles.empty()) {
+        psystem->setObstacles(obstacles.data(), (uint)obstacles.size(), obstacleCell);
+        if (obstacleVelArg) psystem->setObstacleMotion(nullptr, obstacleVel);
     }
     if (const char* v = value(argc, argv, "log")) {
         const char* fq = value(argc, argv, "logfreq");

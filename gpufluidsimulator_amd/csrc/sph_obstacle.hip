@@ -1,0 +1,519 @@
+// sph_obstacle.hip -- solid obstacles of any shape: one grid of signed distances per whole-domain context, which the fluid
+// collides with (sph_obstacle_lattice, _build, _set_grid, _clear, _set_motion, _get, _read, _sample of include/sph_hip.h, which
+// states the rule).  The reference has no counterpart.
+//
+//   k_obstacle_raster  one node per lane: the union of the analytic shapes, clamped                         (sph_obstacle_build)
+//   k_obstacle_clamp   one node per lane: the clamp of an uploaded field                                    (sph_obstacle_set_grid)
+//   k_obstacle_bricks  one brick of OBSTACLE_BRICK^3 cells per lane: the minimum over its (OBSTACLE_BRICK + 1)^3 nodes
+//   k_obstacle_sample  one caller point per lane: the sample rule                                           (sph_obstacle_sample)
+//   k_obstacle_push    one owned slot per lane, behind every integrate of a context with an obstacle: the push
+//
+// The push is a pass of its own and not a fourth pack of k_force / k_integrate (sph_pairs.hip): the fused kernel sits at the edge
+// of its occupancy, and an eight-node gather in its epilogue would cost it.  Reading the integrate's STORED output is also what
+// makes the result equal tests/obstacle_model.py bit for bit.  Everything of the rule is fp32 with each operation rounded (fp
+// contract off, IEEE division and square root).
+#include "sph_device.hpp"
+
+#include <cmath>
+#include <cstring>
+
+namespace sph {
+
+constexpr uint32_t OBSTACLE_THREADS = 256;
+constexpr uint32_t OBSTACLE_BRICK_SH = 2;                         // a brick is 4 x 4 x 4 cells
+constexpr uint32_t OBSTACLE_BRICK = 1u << OBSTACLE_BRICK_SH;
+static_assert(OBSTACLE_THREADS % WAVE == 0, "a wave of the push is one 64-slot chunk of the movers' marks");
+
+// the grid, its motion and its buffers as the kernels take them: by value
+struct ObstacleArgs {
+    const float* phi;
+    const float* brick;
+    float origin[3];
+    float s;
+    uint32_t n[3];
+    float nm1[3];          // (float)(n - 1)
+    uint32_t nb[3];        // bricks per axis: ceil((n - 1) / OBSTACLE_BRICK)
+    float off[3], u[3];
+};
+
+// the shapes of one build: a kernel argument by value, like Spheres (the half-spaces' normals already normalised)
+struct Shapes {
+    sph_shape s[SPH_MAX_SHAPES];
+    uint32_t n;
+};
+
+__device__ __forceinline__ float ob_lerp(float p, float q, float t) {
+#pragma clang fp contract(off)
+    return p + t * (q - p);
+}
+
+// the cell of x and the fractions inside it; false: outside the grid (NaN and +-inf too)
+__device__ __forceinline__ bool ob_locate(const ObstacleArgs& A, float x, float y, float z, uint32_t i[3], float f[3]) {
+#pragma clang fp contract(off)
+    const float g0 = ((x - A.off[0]) - A.origin[0]) / A.s;
+    const float g1 = ((y - A.off[1]) - A.origin[1]) / A.s;
+    const float g2 = ((z - A.off[2]) - A.origin[2]) / A.s;
+    if (!(g0 >= 0.f) || !(g0 < A.nm1[0]) || !(g1 >= 0.f) || !(g1 < A.nm1[1]) || !(g2 >= 0.f) || !(g2 < A.nm1[2])) return false;
+    const int i0 = (int)g0, i1 = (int)g1, i2 = (int)g2;
+    i[0] = (uint32_t)i0; i[1] = (uint32_t)i1; i[2] = (uint32_t)i2;
+    f[0] = g0 - (float)i0; f[1] = g1 - (float)i1; f[2] = g2 - (float)i2;
+    return true;
+}
+
+// phi and the unit normal in a cell: the eight-node gather (i[k] <= n[k] - 2, so every node is inside the array)
+__device__ __forceinline__ void ob_sample_cell(const ObstacleArgs& A, const uint32_t i[3], const float f[3], float& phi, float& nx,
+                                               float& ny, float& nz) {
+#pragma clang fp contract(off)
+    const uint32_t sy = A.n[0], sz = A.n[0] * A.n[1];
+    const float* __restrict__ p = A.phi + ((size_t)i[2] * A.n[1] + i[1]) * A.n[0] + i[0];
+    const float P000 = p[0], P100 = p[1], P010 = p[sy], P110 = p[sy + 1u];
+    const float P001 = p[sz], P101 = p[sz + 1u], P011 = p[sz + sy], P111 = p[sz + sy + 1u];
+    const float fx = f[0], fy = f[1], fz = f[2];
+    phi = ob_lerp(ob_lerp(ob_lerp(P000, P100, fx), ob_lerp(P010, P110, fx), fy),
+                  ob_lerp(ob_lerp(P001, P101, fx), ob_lerp(P011, P111, fx), fy), fz);
+    const float gx = ob_lerp(ob_lerp(P100 - P000, P110 - P010, fy), ob_lerp(P101 - P001, P111 - P011, fy), fz);
+    const float gy = ob_lerp(ob_lerp(P010 - P000, P110 - P100, fx), ob_lerp(P011 - P001, P111 - P101, fx), fz);
+    const float gz = ob_lerp(ob_lerp(P001 - P000, P101 - P100, fx), ob_lerp(P011 - P010, P111 - P110, fx), fy);
+    const float len2 = (gx * gx + gy * gy) + gz * gz;
+    nx = 0.f; ny = 1.f; nz = 0.f;
+    if (len2 > 0.f && len2 < INFINITY) {
+        const float len = sqrtf(len2);
+        nx = gx / len; ny = gy / len; nz = gz / len;
+    }
+}
+
+// ---- the push ---------------------------------------------------------------------------------------------------------------
+// One owned slot per lane, blocks of OBSTACLE_THREADS from the first owned slot: a wave is one 64-slot chunk of the marks.
+// Nearly every wave is nowhere near a solid, so the kernel should cost what reading the positions costs: a lane reads its
+// position (16 bytes), finds its cell and reads ONE word, the minimum of phi over the nodes of its brick.  WHY THAT IS ENOUGH:
+// a lerp p + t * (q - p), 0 <= t < 1, lies between p and q but for its three roundings, each at most an ulp of 2 D (every phi is
+// clamped to [-D, D], D <= 6144 s): about 7e-4 s apiece, under 0.01 s over the three levels.  So where the brick's minimum is
+// at least eps + 0.25 s the interpolated phi is above eps, the rule's first iteration stops with `!(phi < eps)` and the particle
+// is not touched -- whatever field the caller uploaded.  A wave in which no lane can be in contact (one ballot) leaves after 20
+// bytes per lane.  The guard only ever SKIPS work whose outcome is known: the lanes it lets through run the rule as written,
+// every later iteration with a full sample (the particle has moved).
+// Fused (keys_out != null): a particle with `hit` also gets the next step's key, and, where the launch marked the movers, the
+// wave's mask word is put right -- bit = (key != keyS[slot]) for the lanes that hit -- and the tile's count takes the difference
+// of the popcounts with one integer atomic add (force_finish scans the counts afterwards).
+__global__ __launch_bounds__(OBSTACLE_THREADS) void k_obstacle_push(float4* __restrict__ posi, float4* __restrict__ velr,
+                                                                    float4* __restrict__ pos_by_index,
+                                                                    uint32_t* __restrict__ keys_out,
+                                                                    const uint32_t* __restrict__ keyS,
+                                                                    uint64_t* __restrict__ mm_mask,
+                                                                    uint32_t* __restrict__ mm_tile_cnt, uint32_t lo, uint32_t n,
+                                                                    ObstacleArgs A, GridDesc g, Phys ph) {
+#pragma clang fp contract(off)
+    const uint32_t rel = blockIdx.x * OBSTACLE_THREADS + threadIdx.x;
+    const bool active = rel < n;
+    const uint32_t slot = lo + (active ? rel : n - 1u);
+    float4 pi = posi[slot];
+    const float eps = ph.wall_eps;
+    const float guard = eps + 0.25f * A.s;
+    uint32_t ci[3];
+    float cf[3];
+    bool may = false;
+    if (active && ob_locate(A, pi.x, pi.y, pi.z, ci, cf)) {
+        const uint32_t b = ((ci[2] >> OBSTACLE_BRICK_SH) * A.nb[1] + (ci[1] >> OBSTACLE_BRICK_SH)) * A.nb[0] + (ci[0] >> OBSTACLE_BRICK_SH);
+        may = A.brick[b] < guard;
+    }
+    if (__ballot(may) == 0ull) return;                                   // wave-uniform: nearly every wave
+    bool hit = false;
+    float4 vi = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (may) {
+        vi = velr[slot];
+        for (int it = 0; it < SPH_OBSTACLE_PUSH_ITERATIONS; it++) {
+            if (it > 0 && !ob_locate(A, pi.x, pi.y, pi.z, ci, cf)) break;
+            float phi, nx, ny, nz;
+            ob_sample_cell(A, ci, cf, phi, nx, ny, nz);
+            if (!(phi < eps)) break;
+            const float wn = ((vi.x - A.u[0]) * nx + (vi.y - A.u[1]) * ny) + (vi.z - A.u[2]) * nz;
+            if (wn < 0.f) {
+                const float k = (ph.wall_damping - 1.f) * wn;
+                vi.x = vi.x + k * nx; vi.y = vi.y + k * ny; vi.z = vi.z + k * nz;
+            }
+            const float t = eps - phi;
+            pi.x = pi.x + t * nx; pi.y = pi.y + t * ny; pi.z = pi.z + t * nz;
+            hit = true;
+        }
+    }
+    bool moved = false;
+    if (hit) {
+        wall(pi.x, vi.x, ph.box_min[0], ph.box_max[0], eps, ph.wall_damping);
+        wall(pi.y, vi.y, ph.box_min[1], ph.box_max[1], eps, ph.wall_damping);
+        wall(pi.z, vi.z, ph.box_min[2], ph.box_max[2], eps, ph.wall_damping);
+        posi[slot] = pi;
+        velr[slot] = vi;
+        pos_by_index[__float_as_uint(pi.w)] = make_float4(pi.x, pi.y, pi.z, 1.0f);
+        if (keys_out) {
+            const uint32_t key = cell_key(g, pi.x, pi.y, pi.z);
+            keys_out[rel] = key;
+            moved = key != keyS[slot];
+        }
+    }
+    if (mm_mask) {
+        const uint64_t hm = __ballot(hit);
+        if (hm != 0ull) {                                                // wave-uniform
+            const uint64_t mv = __ballot(moved);                         // (a subset of hm)
+            if ((threadIdx.x & 63u) == 0u) {                             // (lane 0 of a wave that got here owns a slot)
+                const uint32_t chunk = rel >> 6;
+                const uint64_t old = mm_mask[chunk], now = (old & ~hm) | mv;
+                if (now != old) {
+                    mm_mask[chunk] = now;
+                    atomicAdd(&mm_tile_cnt[chunk / MM_TILE_CHUNKS], (uint32_t)__popcll(now) - (uint32_t)__popcll(old));
+                }
+            }
+        }
+    }
+}
+
+// ---- the sample rule for caller points ----------------------------------------------------------------------------------------
+__global__ __launch_bounds__(OBSTACLE_THREADS) void k_obstacle_sample(const float* __restrict__ pos, uint32_t n, ObstacleArgs A,
+                                                                      float* __restrict__ phi_out, float* __restrict__ nrm_out,
+                                                                      uint8_t* __restrict__ in_out) {
+    const uint32_t t = blockIdx.x * OBSTACLE_THREADS + threadIdx.x;
+    if (t >= n) return;
+    uint32_t ci[3];
+    float cf[3];
+    float phi = INFINITY, nx = 0.f, ny = 0.f, nz = 0.f;
+    const bool in = ob_locate(A, pos[3u * t], pos[3u * t + 1u], pos[3u * t + 2u], ci, cf);
+    if (in) ob_sample_cell(A, ci, cf, phi, nx, ny, nz);
+    phi_out[t] = phi;
+    nrm_out[3u * t] = nx; nrm_out[3u * t + 1u] = ny; nrm_out[3u * t + 2u] = nz;
+    in_out[t] = in ? 1 : 0;
+}
+
+// ---- installation ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float ob_shape_phi(const sph_shape& S, float px, float py, float pz) {
+#pragma clang fp contract(off)
+    float phi;
+    if (S.kind == SPH_SHAPE_SPHERE) {
+        const float dx = px - S.a[0], dy = py - S.a[1], dz = pz - S.a[2];
+        phi = sqrtf((dx * dx + dy * dy) + dz * dz) - S.r;
+    } else if (S.kind == SPH_SHAPE_BOX) {
+        const float qx = fabsf(px - S.a[0]) - S.b[0], qy = fabsf(py - S.a[1]) - S.b[1], qz = fabsf(pz - S.a[2]) - S.b[2];
+        const float ox = fmaxf(qx, 0.f), oy = fmaxf(qy, 0.f), oz = fmaxf(qz, 0.f);
+        phi = (sqrtf((ox * ox + oy * oy) + oz * oz) + fminf(fmaxf(qx, fmaxf(qy, qz)), 0.f)) - S.r;
+    } else if (S.kind == SPH_SHAPE_CAPSULE) {
+        const float pax = px - S.a[0], pay = py - S.a[1], paz = pz - S.a[2];
+        const float bax = S.b[0] - S.a[0], bay = S.b[1] - S.a[1], baz = S.b[2] - S.a[2];
+        float t = ((pax * bax + pay * bay) + paz * baz) / ((bax * bax + bay * bay) + baz * baz);
+        t = fminf(fmaxf(t, 0.f), 1.f);
+        const float dx = pax - t * bax, dy = pay - t * bay, dz = paz - t * baz;
+        phi = sqrtf((dx * dx + dy * dy) + dz * dz) - S.r;
+    } else {
+        phi = ((px - S.a[0]) * S.b[0] + (py - S.a[1]) * S.b[1]) + (pz - S.a[2]) * S.b[2];
+    }
+    return S.invert ? -phi : phi;
+}
+
+__global__ __launch_bounds__(OBSTACLE_THREADS) void k_obstacle_raster(float* __restrict__ phi, uint32_t nodes, ObstacleArgs A, Shapes sh,
+                                                                      float D) {
+#pragma clang fp contract(off)
+    const uint32_t t = blockIdx.x * OBSTACLE_THREADS + threadIdx.x;
+    if (t >= nodes) return;
+    const uint32_t i = t % A.n[0], jk = t / A.n[0], j = jk % A.n[1], k = jk / A.n[1];
+    const float px = A.origin[0] + (float)i * A.s, py = A.origin[1] + (float)j * A.s, pz = A.origin[2] + (float)k * A.s;
+    float v = ob_shape_phi(sh.s[0], px, py, pz);
+    for (uint32_t q = 1; q < sh.n; q++) v = fminf(v, ob_shape_phi(sh.s[q], px, py, pz));
+    phi[t] = fminf(fmaxf(v, -D), D);
+}
+
+__global__ __launch_bounds__(OBSTACLE_THREADS) void k_obstacle_clamp(float* __restrict__ phi, uint32_t nodes, float D) {
+    const uint32_t t = blockIdx.x * OBSTACLE_THREADS + threadIdx.x;
+    if (t < nodes) phi[t] = fminf(fmaxf(phi[t], -D), D);
+}
+
+// brick (bx, by, bz) covers the cells [4 b, 4 b + 4) of each axis, i.e. the nodes [4 b, 4 b + 4] (clipped to the lattice)
+__global__ __launch_bounds__(OBSTACLE_THREADS) void k_obstacle_bricks(ObstacleArgs A, float* __restrict__ brick, uint32_t bricks) {
+    const uint32_t t = blockIdx.x * OBSTACLE_THREADS + threadIdx.x;
+    if (t >= bricks) return;
+    const uint32_t bx = t % A.nb[0], r = t / A.nb[0], by = r % A.nb[1], bz = r / A.nb[1];
+    const uint32_t x0 = bx * OBSTACLE_BRICK, y0 = by * OBSTACLE_BRICK, z0 = bz * OBSTACLE_BRICK;
+    const uint32_t x1 = min(x0 + OBSTACLE_BRICK, A.n[0] - 1u), y1 = min(y0 + OBSTACLE_BRICK, A.n[1] - 1u), z1 = min(z0 + OBSTACLE_BRICK, A.n[2] - 1u);
+    float m = INFINITY;
+    for (uint32_t z = z0; z <= z1; z++)
+        for (uint32_t y = y0; y <= y1; y++) {
+            const float* __restrict__ row = A.phi + ((size_t)z * A.n[1] + y) * A.n[0];
+            for (uint32_t x = x0; x <= x1; x++) m = fminf(m, row[x]);
+        }
+    brick[t] = m;
+}
+
+// ---- the host side --------------------------------------------------------------------------------------------------------------
+
+static uint32_t ob_bricks_axis(uint32_t n) { return ceil_div(n - 1u, OBSTACLE_BRICK); }
+
+static ObstacleArgs obstacle_args(const sph_ctx* c) {
+    ObstacleArgs A{};
+    A.phi = c->ob_phi;
+    A.brick = c->ob_brick;
+    A.s = c->ob_grid.spacing;
+    for (int k = 0; k < 3; k++) {
+        A.origin[k] = c->ob_grid.origin[k];
+        A.n[k] = c->ob_grid.dims[k];
+        A.nm1[k] = (float)(A.n[k] - 1u);
+        A.nb[k] = ob_bricks_axis(A.n[k]);
+        A.off[k] = c->ob_off[k];
+        A.u[k] = c->ob_vel[k];
+    }
+    return A;
+}
+
+static float ob_clamp_distance(const sph_obstacle_grid& G) {
+#pragma clang fp contract(off)
+    return G.spacing * (float)(G.dims[0] + G.dims[1] + G.dims[2]);
+}
+
+int launch_obstacle_push(sph_ctx* c, bool fused, bool mark) {
+    if (c->n == 0) return SPH_OK;
+    hipLaunchKernelGGL(k_obstacle_push, dim3(ceil_div(c->n, OBSTACLE_THREADS)), dim3(OBSTACLE_THREADS), 0, c->stream,
+                       fused ? c->posi2 : c->posi, fused ? c->velr2 : c->velr, c->pos_out, fused ? c->k0 : nullptr, c->keyS,
+                       fused && mark ? c->mm_mask : nullptr, c->mm_tile_cnt, c->own_off, c->n, obstacle_args(c), c->grid, c->phys);
+    SPH_HIP(hipGetLastError());
+    return SPH_OK;
+}
+
+void advance_obstacle(sph_ctx* c, float dt) {
+#pragma clang fp contract(off)
+    if (!have_obstacle(c)) return;
+    for (int k = 0; k < 3; k++) c->ob_off[k] = c->ob_off[k] + dt * c->ob_vel[k];
+}
+
+static void release_obstacle(sph_ctx* c) {
+    c->mem.release(&c->ob_brick);
+    c->mem.release(&c->ob_phi);
+    c->ob_grid = sph_obstacle_grid{};
+}
+
+static int check_grid(const sph_obstacle_grid& G) {
+    double nodes = 1.0;
+    for (int k = 0; k < 3; k++) {
+        SPH_REQUIRE(G.dims[k] >= 2u, SPH_E_INVALID, "obstacle grid: %u nodes on axis %d, at least 2", G.dims[k], k);
+        SPH_REQUIRE(G.dims[k] <= (uint32_t)SPH_OBSTACLE_MAX_DIM, SPH_E_CAPACITY, "obstacle grid: %u nodes on axis %d, at most %d",
+                    G.dims[k], k, SPH_OBSTACLE_MAX_DIM);
+        SPH_REQUIRE(std::isfinite(G.origin[k]), SPH_E_INVALID, "obstacle grid: the origin is not finite");
+        nodes *= (double)G.dims[k];
+    }
+    SPH_REQUIRE(nodes <= (double)SPH_OBSTACLE_MAX_NODES, SPH_E_CAPACITY, "obstacle grid: %u x %u x %u nodes, at most 2^27", G.dims[0],
+                G.dims[1], G.dims[2]);
+    SPH_REQUIRE(std::isfinite(G.spacing) && G.spacing > 0.f && std::isfinite(ob_clamp_distance(G)), SPH_E_INVALID,
+                "obstacle grid: spacing %g is not a positive finite number", (double)G.spacing);
+    return SPH_OK;
+}
+
+// The lattice of a build: checks only, allocates nothing.
+static int lattice_resolve(const sph_ctx* c, float spacing, const float* lo, const float* hi, sph_obstacle_grid* G) {
+#pragma clang fp contract(off)
+    SPH_REQUIRE(std::isfinite(spacing) && spacing >= 0.f, SPH_E_INVALID, "obstacle spacing %g: finite and >= 0 (0: the particle diameter)",
+                (double)spacing);
+    SPH_REQUIRE((lo == nullptr) == (hi == nullptr), SPH_E_INVALID, "obstacle bounds: give both corners or neither");
+    const float s = spacing > 0.f ? spacing : (float)(2.0 * (double)c->params.particle_radius);
+    SPH_REQUIRE(std::isfinite(s) && s > 0.f, SPH_E_INVALID, "obstacle spacing %g is not a positive finite number", (double)s);
+    sph_obstacle_grid R{};
+    R.spacing = s;
+    for (int k = 0; k < 3; k++) {
+        const float l = lo ? lo[k] : c->params.box_min[k], h = hi ? hi[k] : c->params.box_max[k];
+        SPH_REQUIRE(std::isfinite(l) && std::isfinite(h) && h >= l, SPH_E_INVALID, "obstacle bounds: axis %d is [%g, %g]", k, (double)l,
+                    (double)h);
+        const double nk = std::ceil(((double)h - (double)l) / (double)s) + 3.0;
+        SPH_REQUIRE(nk <= (double)SPH_OBSTACLE_MAX_DIM, SPH_E_CAPACITY, "obstacle lattice: %.0f nodes on axis %d, at most %d (a wider "
+                    "spacing, or bounds around the solid?)", nk, k, SPH_OBSTACLE_MAX_DIM);
+        R.dims[k] = (uint32_t)nk;
+        R.origin[k] = l - s;
+    }
+    if (int e = check_grid(R)) return e;
+    *G = R;
+    return SPH_OK;
+}
+
+static int check_shapes(uint32_t n, const sph_shape* shapes, Shapes* out) {
+#pragma clang fp contract(off)
+    SPH_REQUIRE(n >= 1u && n <= (uint32_t)SPH_MAX_SHAPES, SPH_E_INVALID, "%u shapes: 1..%d", n, SPH_MAX_SHAPES);
+    SPH_REQUIRE(shapes, SPH_E_INVALID, "null shapes");
+    out->n = n;
+    for (uint32_t j = 0; j < n; j++) {
+        sph_shape S = shapes[j];
+        SPH_REQUIRE(S.kind >= SPH_SHAPE_SPHERE && S.kind <= SPH_SHAPE_HALFSPACE, SPH_E_INVALID, "shape %u: unknown kind %d", j, S.kind);
+        const bool uses_b = S.kind != SPH_SHAPE_SPHERE, uses_r = S.kind != SPH_SHAPE_HALFSPACE;
+        for (int k = 0; k < 3; k++)
+            SPH_REQUIRE(std::isfinite(S.a[k]) && (!uses_b || std::isfinite(S.b[k])), SPH_E_INVALID, "shape %u: a field is not finite", j);
+        SPH_REQUIRE(!uses_r || std::isfinite(S.r), SPH_E_INVALID, "shape %u: r is not finite", j);
+        if (S.kind == SPH_SHAPE_SPHERE || S.kind == SPH_SHAPE_CAPSULE)
+            SPH_REQUIRE(S.r > 0.f, SPH_E_INVALID, "shape %u: radius %g is not positive", j, (double)S.r);
+        if (S.kind == SPH_SHAPE_BOX) {
+            SPH_REQUIRE(S.r >= 0.f, SPH_E_INVALID, "shape %u: rounding %g is negative", j, (double)S.r);
+            SPH_REQUIRE(S.b[0] > 0.f && S.b[1] > 0.f && S.b[2] > 0.f, SPH_E_INVALID, "shape %u: a half extent is not positive", j);
+        }
+        if (S.kind == SPH_SHAPE_CAPSULE) {
+            const float bx = S.b[0] - S.a[0], by = S.b[1] - S.a[1], bz = S.b[2] - S.a[2];
+            const float bb = (bx * bx + by * by) + bz * bz;
+            SPH_REQUIRE(std::isfinite(bb) && bb > 0.f, SPH_E_INVALID, "shape %u: the capsule's ends coincide", j);
+        }
+        if (S.kind == SPH_SHAPE_HALFSPACE) {
+            const double len = std::sqrt((double)S.b[0] * S.b[0] + (double)S.b[1] * S.b[1] + (double)S.b[2] * S.b[2]);
+            SPH_REQUIRE(len > 0.0 && std::isfinite(len), SPH_E_INVALID, "shape %u: the normal is zero", j);
+            for (int k = 0; k < 3; k++) S.b[k] = (float)((double)S.b[k] / len);
+            S.r = 0.f;
+        }
+        if (S.kind == SPH_SHAPE_SPHERE) S.b[0] = S.b[1] = S.b[2] = 0.f;
+        out->s[j] = S;
+    }
+    return SPH_OK;
+}
+
+static int obstacle_ctx(const sph_ctx* c, const char* who) {
+    SPH_REQUIRE(c, SPH_E_INVALID, "null context");
+    SPH_REQUIRE(!c->slab, SPH_E_STATE, "%s is not supported on a slab context (its step makes several force launches with holes, "
+                "and ghosts arrive integrated)", who);
+    return SPH_OK;
+}
+
+// The checked grid G becomes the context's: the old obstacle leaves (once the stream is idle), the two buffers are allocated.
+// On failure there is no obstacle.
+static int install_begin(sph_ctx* c, const sph_obstacle_grid& G) {
+    SPH_HIP(hipSetDevice(c->device));
+    if (have_obstacle(c)) {
+        SPH_HIP(hipStreamSynchronize(c->stream));          // (a push of the old grid may still be running)
+        release_obstacle(c);
+    }
+    const size_t nodes = (size_t)G.dims[0] * G.dims[1] * G.dims[2];
+    const size_t bricks = (size_t)ob_bricks_axis(G.dims[0]) * ob_bricks_axis(G.dims[1]) * ob_bricks_axis(G.dims[2]);
+    int rc = c->mem.alloc(&c->ob_phi, nodes, false);
+    if (!rc) rc = c->mem.alloc(&c->ob_brick, bricks, false);
+    if (rc) { release_obstacle(c); return rc; }
+    c->ob_grid = G;
+    return SPH_OK;
+}
+
+static int install_finish(sph_ctx* c) {
+    const ObstacleArgs A = obstacle_args(c);
+    const uint32_t bricks = A.nb[0] * A.nb[1] * A.nb[2];
+    hipLaunchKernelGGL(k_obstacle_bricks, dim3(ceil_div(bricks, OBSTACLE_THREADS)), dim3(OBSTACLE_THREADS), 0, c->stream, A, c->ob_brick,
+                       bricks);
+    SPH_HIP(hipGetLastError());
+    return SPH_OK;
+}
+
+}  // namespace sph
+
+using namespace sph;
+
+extern "C" {
+
+int sph_obstacle_lattice(const sph_ctx* c, float spacing, const float lo[3], const float hi[3], sph_obstacle_grid* out) {
+    SPH_REQUIRE(c && out, SPH_E_INVALID, "null argument");
+    return lattice_resolve(c, spacing, lo, hi, out);
+}
+
+int sph_obstacle_build(sph_ctx* c, float spacing, const float lo[3], const float hi[3], uint32_t n, const sph_shape* shapes) {
+    if (int e = obstacle_ctx(c, "sph_obstacle_build")) return e;
+    sph_obstacle_grid G;
+    Shapes sh{};
+    if (int e = lattice_resolve(c, spacing, lo, hi, &G)) return e;
+    if (int e = check_shapes(n, shapes, &sh)) return e;
+    if (int e = install_begin(c, G)) return e;
+    const uint32_t nodes = G.dims[0] * G.dims[1] * G.dims[2];
+    hipLaunchKernelGGL(k_obstacle_raster, dim3(ceil_div(nodes, OBSTACLE_THREADS)), dim3(OBSTACLE_THREADS), 0, c->stream, c->ob_phi, nodes,
+                       obstacle_args(c), sh, ob_clamp_distance(G));
+    SPH_HIP(hipGetLastError());
+    return install_finish(c);
+}
+
+int sph_obstacle_set_grid(sph_ctx* c, const sph_obstacle_grid* grid, const float* phi) {
+    if (int e = obstacle_ctx(c, "sph_obstacle_set_grid")) return e;
+    SPH_REQUIRE(grid && phi, SPH_E_INVALID, "null argument");
+    const sph_obstacle_grid G = *grid;
+    if (int e = check_grid(G)) return e;
+    const size_t nodes = (size_t)G.dims[0] * G.dims[1] * G.dims[2];
+    for (size_t i = 0; i < nodes; i++)
+        SPH_REQUIRE(std::isfinite(phi[i]), SPH_E_INVALID, "obstacle grid: phi[%zu] is not finite", i);
+    if (int e = install_begin(c, G)) return e;
+    hipError_t he = hipMemcpyAsync(c->ob_phi, phi, nodes * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (he == hipSuccess) {
+        hipLaunchKernelGGL(k_obstacle_clamp, dim3(ceil_div((uint32_t)nodes, OBSTACLE_THREADS)), dim3(OBSTACLE_THREADS), 0, c->stream,
+                           c->ob_phi, (uint32_t)nodes, ob_clamp_distance(G));
+        he = hipGetLastError();
+    }
+    int rc = he == hipSuccess ? install_finish(c) : hip_fail(he, "obstacle upload", __FILE__, __LINE__);
+    if (!rc) {
+        he = hipStreamSynchronize(c->stream);              // (the caller's array is free again)
+        if (he != hipSuccess) rc = hip_fail(he, "hipStreamSynchronize", __FILE__, __LINE__);
+    }
+    if (rc) release_obstacle(c);
+    return rc;
+}
+
+int sph_obstacle_clear(sph_ctx* c) {
+    if (int e = obstacle_ctx(c, "sph_obstacle_clear")) return e;
+    if (have_obstacle(c)) {
+        SPH_HIP(hipSetDevice(c->device));
+        SPH_HIP(hipStreamSynchronize(c->stream));
+        release_obstacle(c);
+    }
+    for (int k = 0; k < 3; k++) c->ob_off[k] = c->ob_vel[k] = 0.f;
+    return SPH_OK;
+}
+
+int sph_obstacle_set_motion(sph_ctx* c, const float offset[3], const float velocity[3]) {
+    if (int e = obstacle_ctx(c, "sph_obstacle_set_motion")) return e;
+    for (int k = 0; k < 3; k++)
+        SPH_REQUIRE((!offset || std::isfinite(offset[k])) && (!velocity || std::isfinite(velocity[k])), SPH_E_INVALID,
+                    "obstacle motion: offset or velocity is not finite");
+    for (int k = 0; k < 3; k++) {
+        if (offset) c->ob_off[k] = offset[k];
+        if (velocity) c->ob_vel[k] = velocity[k];
+    }
+    return SPH_OK;
+}
+
+int sph_obstacle_get(const sph_ctx* c, sph_obstacle_grid* grid, float offset[3], float velocity[3]) {
+    SPH_REQUIRE(c, SPH_E_INVALID, "null context");
+    if (grid) *grid = c->ob_grid;
+    for (int k = 0; k < 3; k++) {
+        if (offset) offset[k] = c->ob_off[k];
+        if (velocity) velocity[k] = c->ob_vel[k];
+    }
+    return SPH_OK;
+}
+
+int sph_obstacle_read(sph_ctx* c, float* phi) {
+    SPH_REQUIRE(c && phi, SPH_E_INVALID, "null argument");
+    SPH_REQUIRE(have_obstacle(c), SPH_E_STATE, "sph_obstacle_read: no obstacle is installed");
+    SPH_HIP(hipSetDevice(c->device));
+    const size_t nodes = (size_t)c->ob_grid.dims[0] * c->ob_grid.dims[1] * c->ob_grid.dims[2];
+    SPH_HIP(hipMemcpyAsync(phi, c->ob_phi, nodes * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    SPH_HIP(hipStreamSynchronize(c->stream));
+    return SPH_OK;
+}
+
+int sph_obstacle_sample(sph_ctx* c, uint32_t n, const float* pos_xyz, float* phi, float* normal_xyz, uint8_t* inside_grid) {
+    SPH_REQUIRE(c, SPH_E_INVALID, "null context");
+    SPH_REQUIRE(have_obstacle(c), SPH_E_STATE, "sph_obstacle_sample: no obstacle is installed");
+    SPH_REQUIRE(n == 0 || pos_xyz, SPH_E_INVALID, "null positions");
+    if (n == 0) return SPH_OK;
+    SPH_HIP(hipSetDevice(c->device));
+    Buffers tmp;                                   // the call's temporaries: points in, three planes out
+    float* d_pos = nullptr; float* d_phi = nullptr; float* d_nrm = nullptr; uint8_t* d_in = nullptr;
+    int rc = tmp.alloc(&d_pos, (size_t)n * 3, false);
+    if (!rc) rc = tmp.alloc(&d_phi, n, false);
+    if (!rc) rc = tmp.alloc(&d_nrm, (size_t)n * 3, false);
+    if (!rc) rc = tmp.alloc(&d_in, n, false);
+    auto hip = [&](hipError_t e, const char* what) { if (!rc && e != hipSuccess) rc = hip_fail(e, what, __FILE__, __LINE__); };
+    if (!rc) {
+        hip(hipMemcpyAsync(d_pos, pos_xyz, (size_t)n * 12, hipMemcpyHostToDevice, c->stream), "copy of the points");
+        if (!rc) {
+            hipLaunchKernelGGL(k_obstacle_sample, dim3(ceil_div(n, OBSTACLE_THREADS)), dim3(OBSTACLE_THREADS), 0, c->stream, d_pos, n,
+                               obstacle_args(c), d_phi, d_nrm, d_in);
+            hip(hipGetLastError(), "k_obstacle_sample");
+        }
+        if (!rc && phi) hip(hipMemcpyAsync(phi, d_phi, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream), "copy of phi");
+        if (!rc && normal_xyz) hip(hipMemcpyAsync(normal_xyz, d_nrm, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream), "copy of the normals");
+        if (!rc && inside_grid) hip(hipMemcpyAsync(inside_grid, d_in, n, hipMemcpyDeviceToHost, c->stream), "copy of the flags");
+        hipError_t e = hipStreamSynchronize(c->stream);    // (also on an error: the temporaries are about to go)
+        hip(e, "hipStreamSynchronize");
+    }
+    tmp.free_all();
+    return rc;
+}
+
+}  // extern "C"

@@ -808,10 +808,7 @@ int launch_density(sph_ctx* c) {
 // ---- integrate one particle (kernelIntegrate, particleSystem.cu:375-420) ------------------------------
 // a = (f_press + f_visc + (0, g*G*rho, 0)) / rho ; v += dt*a + dv ; x += dt*v ; walls per axis X,Y,Z
 // (lower wall first): x = wall +- eps, v *= -0.75 ; out[index] = (x, y, z, 1).
-__device__ __forceinline__ void wall(float& x, float& v, float lo, float hi, float eps, float damp) {
-    if (x - eps < lo) { x = lo + eps; v *= damp; }
-    if (x + eps > hi) { x = hi - eps; v *= damp; }
-}
+// (wall(), the rule of one axis, lives in sph_device.hpp: the obstacle pass of sph_obstacle.hip applies it too)
 
 // ---- sphere colliders (sph_set_colliders, include/sph_hip.h) ------------------------------------------------------------
 // After the walls, sphere j = 0..n-1 in order: a particle inside R_j + eps goes onto that shell along the radial direction
@@ -1449,6 +1446,7 @@ static SpheresTracked tracked_pack(const sph_ctx* c) { return SpheresTracked{c->
 // context queues k_spheres_step instead: the impulses of the launch just queued, the bodies and the centres, on the device.
 static int advance_colliders(sph_ctx* c, float dt) {
 #pragma clang fp contract(off)
+    advance_obstacle(c, dt);                      // (the obstacle's offset: once per step as well)
     if (c->tracked) {
         hipLaunchKernelGGL(k_spheres_step, dim3(1), dim3(SPHERES_STEP_THREADS), 0, c->stream, c->trk_table, c->trk_partial,
                            c->trk_mask, ceil_div(c->n, 64u), c->trk_J, c->bodies, dt, c->phys);
@@ -1534,6 +1532,8 @@ int launch_force(sph_ctx* c, bool force, bool collide, bool integrate, float dt)
     const bool mark = force_begin(c, integrate);
     int rc = launch_force_range(c, c->own_off, c->own_off + c->n, force, collide, integrate, dt, mark);
     if (rc) return rc;
+    // the obstacle's pass works on what the launch just wrote (posi2, velr2, k0, the marks), before force_finish scans the marks
+    if (integrate && have_obstacle(c) && (rc = launch_obstacle_push(c, true, mark))) return rc;
     return force_finish(c, integrate, mark, dt);
 }
 
@@ -1605,6 +1605,8 @@ int launch_integrate(sph_ctx* c, float dt) {
         hipLaunchKernelGGL(k_integrate<>, dim3(ceil_div(c->n, 256)), dim3(256), 0, c->stream, c->posi, c->velr, c->dp,
                            c->fpress, c->fvisc, c->dvel, pos_out, c->own_off, c->own_off + c->n, dt, c->phys);
     SPH_HIP(hipGetLastError());
+    if (have_obstacle(c))
+        if (int rc = launch_obstacle_push(c, false, false)) return rc;
     return advance_colliders(c, dt);
 }
 

@@ -156,6 +156,16 @@ public:
     // Extract, and write a Wavefront OBJ (sph_mesh_save_obj).
     void writeMeshOBJ(const char* path);
 
+    // ---- additive: solid obstacles of any shape (sph_obstacle_build of sph_hip.h; the reference has nothing here) -----------
+    // The union of n analytic shapes, rasterised on the device over the whole box at `spacing` (0: the particle diameter; bounds
+    // of nullptr: the box) and installed as the context's obstacle: every later update pushes the particles out of it.
+    void setObstacles(const sph_shape* shapes, uint n, float spacing = 0.f, const float* lo = nullptr, const float* hi = nullptr);
+    // The caller's own signed distances (a voxelised mesh): dims[0]*dims[1]*dims[2] floats, x fastest, negative inside.
+    void setObstacleGrid(const sph_obstacle_grid& grid, const float* phi);
+    // Offset and velocity of the grid (either may be nullptr = keep): the offset advances by dt * velocity once per step.
+    void setObstacleMotion(const float* offset, const float* velocity);
+    void clearObstacles();
+
     // ---- additive (absent upstream; named by BASELINE.json's north star) ------------------------
     // 4 floats per particle, by creation index (the original NVIDIA sample's layout), getCapacity() rows; the pointer
     // stays valid until the next getArray call.

@@ -30,6 +30,8 @@
  *                  sph_get_precision | sph_upload sph_set_by_index sph_reset_lattice sph_download sph_download_owned
  *                  sph_positions_dev sph_download_positions4 sph_snapshot_save sph_snapshot_load sph_snapshot_info |
  *                  sph_set_colliders sph_get_colliders sph_set_collider_bodies sph_get_collider_impulses | sph_emit sph_remove sph_count_in_regions |
+ *                  sph_obstacle_lattice sph_obstacle_build sph_obstacle_set_grid sph_obstacle_clear sph_obstacle_set_motion
+ *                  sph_obstacle_get sph_obstacle_read sph_obstacle_sample |
  *                  sph_camera_look_at sph_render sph_render_read sph_render_image_dev sph_surface_defaults sph_render_surface
  *                  sph_render_surface_read | sph_mesh_defaults sph_mesh_lattice sph_mesh_extract sph_mesh_read sph_mesh_dev
  *                  sph_mesh_save_obj |
@@ -298,6 +300,110 @@ typedef struct sph_collider_body {
 int sph_set_collider_bodies(sph_ctx* c, uint32_t n, const sph_collider_body* bodies);
 /* *n spheres; J: 3 doubles per sphere (room for SPH_MAX_COLLIDERS; may be NULL); steps may be NULL.  Synchronises. */
 int sph_get_collider_impulses(sph_ctx* c, uint32_t* n, double* J, uint64_t* steps);
+
+/* ---- solid obstacles of any shape: a signed-distance grid the fluid collides with (no counterpart in the reference) --------------
+ * A whole-domain context holds at most one OBSTACLE: a regular grid of signed distances phi (phi < 0 inside the solid), sampled
+ * trilinearly, built on the device from analytic shapes (sph_obstacle_build) or uploaded by the caller (sph_obstacle_set_grid:
+ * the door for voxelised meshes).  It is static or translates uniformly.  After EVERY integrate -- the fused one of sph_step and
+ * sph_force_collide_integrate, and sph_integrate -- a pass of its own pushes the owned particles out of the solid; a context
+ * without an obstacle launches and allocates exactly what a library without this section does.
+ *
+ * THE RULE (fp32, every operation rounded, no multiply-add fusion, sums left to right, IEEE division and square root;
+ * tests/obstacle_model.py is the same arithmetic in numpy and gives every particle bit for bit: the pass reads the integrate's
+ * STORED output, so there is neither a tolerance nor a tie).
+ * GRID.  dims = (n_x, n_y, n_z), each 2..SPH_OBSTACLE_MAX_DIM, n_x*n_y*n_z <= SPH_OBSTACLE_MAX_NODES; origin finite; spacing
+ * s > 0 and finite.  One float per node, x fastest: node (i, j, k) is phi[(k*n_y + j)*n_x + i] and sits at
+ * origin + ((float)i*s, (float)j*s, (float)k*s).  On installation every phi is clamped to [-D, D], D = s * (float)(n_x + n_y +
+ * n_z): no distance over the lattice exceeds D, and the clamp bounds the rounding error of the interpolation.  A phi that is
+ * not finite is refused.
+ * MOTION.  The grid has an offset `off` and a velocity `u`, both (0, 0, 0) by default: the field a particle at x sees is the
+ * grid's at x - off.  After each step, once per step and on the host, off[k] = off[k] + dt * u[k] in fp32 -- where the spheres'
+ * centres advance; a step without particles still moves it.  The motion belongs to the context: installing another grid keeps
+ * it, sph_obstacle_clear resets it, and the offset only advances while a grid is installed.  The grid moves WITH the solid, and
+ * a particle outside the grid is never in contact: build a moving obstacle with bounds that cover the box along its whole path.
+ * SAMPLE at x.  Per axis k:  q = x[k] - off[k] ;  g = (q - origin[k]) / s.  If !(g >= 0) || !(g < (float)(n_k - 1)) on any axis
+ * the point is OUTSIDE the grid: no contact (NaN and +-inf land here).  Else i_k = (int)g, f_k = g - (float)i_k, the eight nodes
+ * are P_abc = phi at (i_x + a, i_y + b, i_z + c), and with lerp(p, q, t) = p + t * (q - p):
+ *     phi = lerp( lerp( lerp(P000, P100, fx), lerp(P010, P110, fx), fy ),
+ *                 lerp( lerp(P001, P101, fx), lerp(P011, P111, fx), fy ), fz )
+ *     gx  = lerp( lerp(P100 - P000, P110 - P010, fy), lerp(P101 - P001, P111 - P011, fy), fz )
+ *     gy  = lerp( lerp(P010 - P000, P110 - P100, fx), lerp(P011 - P001, P111 - P101, fx), fz )
+ *     gz  = lerp( lerp(P001 - P000, P101 - P100, fx), lerp(P011 - P010, P111 - P110, fx), fy )
+ * (the gradient in node units: no division by s)
+ *     len2 = (gx*gx + gy*gy) + gz*gz ;  n = (gx, gy, gz) / sqrtf(len2) per component, or (0, 1, 0) unless len2 is finite and > 0
+ * PUSH.  After the integration, the wall rule and the spheres (with their wall pass), for every owned particle (x, v), with
+ * eps = wall_eps:
+ *     hit = false
+ *     repeat up to SPH_OBSTACLE_PUSH_ITERATIONS times:
+ *         sample phi, n at x ;  if outside or !(phi < eps): stop
+ *         wn = ((v.x - u.x)*n.x + (v.y - u.y)*n.y) + (v.z - u.z)*n.z
+ *         if wn < 0:  k = (wall_damping - 1) * wn ;  v = v + k * n   (per component)
+ *         t = eps - phi ;  x = x + t * n                              (per component) ;  hit = true
+ *     if hit: the wall rule on x, y, z once more, as after the spheres
+ * One iteration lands on phi = eps where phi is a true distance (|grad phi| = 1).  The interpolated field of a box has
+ * |grad phi| between about 0.15 and 1.4 within half a spacing of its surface, near edges and corners (a float64 measurement):
+ * hence four iterations.  GEOMETRY IS RESOLVED TO THE SPACING: the zero level of the interpolated field cuts a box's corners by
+ * up to about 0.4 s, and an obstacle thinner than a particle's path in one step can be tunnelled through.
+ * A particle with `hit` gets its new position and velocity, its row (x, y, z, 1) of the by-index position buffer and, in the
+ * fused step, the next step's cell key and mover mark; a particle without is not written at all.  No floating-point atomic is
+ * involved, and the pass touches none of the context's step flags.
+ * SHAPES (sph_obstacle_build): the union of 1..SPH_MAX_SHAPES shapes, one node per thread, p the node's position:
+ *     SPH_SHAPE_SPHERE     centre a, radius r > 0:   d = p - a ;  phi = sqrtf((d.x*d.x + d.y*d.y) + d.z*d.z) - r
+ *     SPH_SHAPE_BOX        centre a, half extents b > 0, rounding r >= 0 (axis-aligned):
+ *                          q[k] = fabsf(p[k] - a[k]) - b[k] ;  o[k] = fmaxf(q[k], 0)
+ *                          phi = (sqrtf((o.x*o.x + o.y*o.y) + o.z*o.z) + fminf(fmaxf(q.x, fmaxf(q.y, q.z)), 0)) - r
+ *     SPH_SHAPE_CAPSULE    ends a != b, radius r > 0:   pa = p - a ;  ba = b - a
+ *                          t = ((pa.x*ba.x + pa.y*ba.y) + pa.z*ba.z) / ((ba.x*ba.x + ba.y*ba.y) + ba.z*ba.z)
+ *                          t = fminf(fmaxf(t, 0), 1) ;  d = pa - t*ba ;  phi = sqrtf((d.x*d.x + d.y*d.y) + d.z*d.z) - r
+ *                          (ends so close that ba.ba is not a positive finite fp32 count as equal)
+ *     SPH_SHAPE_HALFSPACE  point a, normal b: finite and non-zero, normalised on the host in double, each component rounded once
+ *                          phi = ((p.x-a.x)*b.x + (p.y-a.y)*b.y) + (p.z-a.z)*b.z
+ *                          (solid on the side the normal points AWAY from, as SPH_REGION_HALFSPACE)
+ * invert != 0 negates the shape's phi (fluid inside a bowl is an inverted sphere); the union is fminf over the shapes in order;
+ * then the clamp to [-D, D].
+ * THE LATTICE OF A BUILD (sph_obstacle_lattice; in double on the host, each result rounded once): s = spacing, 0 meaning
+ * 2 * particle_radius; bounds [lo, hi] the caller's, or the box where the pointer is NULL:
+ *     n_k = ceil((hi_k - lo_k) / s) + 3 ;  origin_k = lo_k - s  (fp32)
+ * Beyond the limits: SPH_E_CAPACITY.  The bounds let a fine grid sit around a pillar in a large box (the standard box of edge
+ * 32 at s = 1/16 would exceed SPH_OBSTACLE_MAX_NODES).  Particles outside the grid are never in contact.
+ *
+ * All calls are legal at any stage of a step, like sph_set_colliders, and every later integrate uses the new state.
+ *   SPH_E_STATE     a slab context (every call that would install a grid or a motion): the slab step makes up to three force
+ *                   launches with holes and ghosts that arrive integrated.  Out of scope, as for render, mesh, emitters, bodies.
+ *                   Also sph_obstacle_read / _sample without an obstacle.
+ *   SPH_E_INVALID   what THE RULE excludes: dims, origin, spacing, a phi that is not finite, a shape count outside
+ *                   1..SPH_MAX_SHAPES, an unknown kind, a field its kind uses that is not finite or out of range, bounds with
+ *                   hi < lo or not finite, a motion that is not finite;
+ *   SPH_E_CAPACITY  a lattice beyond SPH_OBSTACLE_MAX_DIM / SPH_OBSTACLE_MAX_NODES.
+ * In every refused case nothing has changed and nothing was allocated.  SPH_E_NOMEM releases everything the call allocated and
+ * leaves the context with NO obstacle.  Device buffers: 4 bytes per node and 4 per brick of 4 x 4 x 4 cells, freed by
+ * sph_obstacle_clear and sph_destroy.  Installing over an obstacle waits for the context's stream first.  sph_set_params needs
+ * no refresh (eps is read at every launch).  Snapshots do not carry obstacles, as they do not carry colliders. */
+#define SPH_OBSTACLE_MAX_DIM 2048
+#define SPH_OBSTACLE_MAX_NODES (1u << 27)
+#define SPH_OBSTACLE_PUSH_ITERATIONS 4
+#define SPH_MAX_SHAPES 16
+enum { SPH_SHAPE_SPHERE = 0, SPH_SHAPE_BOX = 1, SPH_SHAPE_CAPSULE = 2, SPH_SHAPE_HALFSPACE = 3 };
+typedef struct sph_shape { int32_t kind; int32_t invert; float a[3]; float b[3]; float r; } sph_shape;   /* 36 bytes */
+typedef struct sph_obstacle_grid { uint32_t dims[3]; float origin[3]; float spacing; } sph_obstacle_grid;
+/* Host helper: the lattice sph_obstacle_build would use (lo, hi: both NULL = the context's box).  *out untouched on error. */
+int sph_obstacle_lattice(const sph_ctx* c, float spacing, const float lo[3], const float hi[3], sph_obstacle_grid* out);
+/* Rasterise the union of n shapes on that lattice and install it: kernels on the context's stream, no host wait (unless it
+ * replaces an obstacle). */
+int sph_obstacle_build(sph_ctx* c, float spacing, const float lo[3], const float hi[3], uint32_t n, const sph_shape* shapes);
+/* Install the caller's field (a host array of dims[0]*dims[1]*dims[2] floats, left untouched).  Copies: synchronises. */
+int sph_obstacle_set_grid(sph_ctx* c, const sph_obstacle_grid* grid, const float* phi);
+/* Remove the obstacle, free its buffers, motion back to 0 (waits for the stream if there was one).  Without one: SPH_OK. */
+int sph_obstacle_clear(sph_ctx* c);
+/* Offset and velocity of the grid; either may be NULL = keep. */
+int sph_obstacle_set_motion(sph_ctx* c, const float offset[3], const float velocity[3]);
+/* The installed grid (dims 0, 0, 0 = none) and the ADVANCED offset; any pointer may be NULL. */
+int sph_obstacle_get(const sph_ctx* c, sph_obstacle_grid* grid, float offset[3], float velocity[3]);
+/* The installed (clamped) field to the host.  Synchronises. */
+int sph_obstacle_read(sph_ctx* c, float* phi);
+/* SAMPLE on the device for n caller points (xyz triples) with the current offset: "how far is this point from the solid".
+ * Outside the grid: phi = +inf, normal (0, 0, 0), inside_grid 0.  Any output may be NULL.  Synchronises. */
+int sph_obstacle_sample(sph_ctx* c, uint32_t n, const float* pos_xyz, float* phi, float* normal_xyz, uint8_t* inside_grid);
 
 /* ---- emitters and drains: particles enter and leave a running simulation (no counterpart in the reference, whose particle
  *      set is fixed at construction; sph_set_by_index, its addSphere, only rewrites particles that exist) -----------------------

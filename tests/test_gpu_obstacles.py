@@ -1,0 +1,488 @@
+"""GPU: solid obstacles of any shape (include/sph_hip.h: sph_obstacle_build and the calls next to it) against the numpy model of
+tests/obstacle_model.py, BIT FOR BIT: the rasteriser, the sample rule, the push behind the fused and the phased integrate, the
+brick acceleration on a field that is no distance, the movers' marks, a dam against a pillar, a moving ramp, spheres and an
+obstacle together, a cleared obstacle, the refusals and an installation in the middle of a step."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+
+import obstacle_model as om
+from gpufluidsimulator_amd import capi, ic
+
+pytestmark = pytest.mark.gpu
+F = np.float32
+DT = float(ic.DEFAULT_DT)
+BOX, GRID = (4.0, 4.0, 4.0), (64, 64, 64)          # cell edge 1/16
+BMIN, BMAX = (-2.0, -2.0, -2.0), (2.0, 2.0, 2.0)
+S = 1.0 / 16.0                                     # obstacle spacing: a 67^3 lattice, no multiple of the brick edge
+EPS, DAMP = F(1e-5), F(-0.75)
+ZERO = (0.0, 0.0, 0.0)
+N = 15 * 15 * 15                                   # 3375: the last wave and the last mover tile are partial
+
+
+@functools.lru_cache(maxsize=None)
+def _dam_arrays():
+    return ic.dam_break_lattice((15, 15, 15), BOX, jitter=True)      # fills [-2, -1.53]^3
+
+
+def _dam():
+    pos, vel = _dam_arrays()
+    return pos.copy(), vel.copy()
+
+
+def _flowing(vx=300.0):
+    pos, vel = _dam()
+    pos[:, 1] += F(0.5)
+    vel[:, 0] = vx
+    return pos, vel
+
+
+def _ctx(cap=N):
+    return capi.Context(cap, box=BOX, grid=GRID)
+
+
+def _shape(sh):
+    """a model shape as the library takes it"""
+    f3 = lambda v: (C.c_float * 3)(*[float(x) for x in v])
+    return capi.Shape(int(sh["kind"]), int(sh["invert"]), f3(sh["a"]), f3(sh["b"]), float(sh["r"]))
+
+
+def _build(c, shapes, spacing=S, bounds=None):
+    c.build_obstacle([_shape(s) for s in shapes], spacing, bounds)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def _same(a, b, what=""):
+    assert np.array_equal(_bits(a), _bits(b)), (what, int((_bits(a) != _bits(b)).sum()))
+
+
+def _same_state(sa, sb):
+    for k in ("pos", "vel", "density", "pressure"):
+        _same(sa[k], sb[k], k)
+
+
+def _grid_of(ob):
+    return {"dims": ob["dims"], "origin": ob["origin"], "spacing": ob["spacing"]}
+
+
+def _keys_of(pos):
+    """the cell keys of csrc/sph_device.hpp: cell_key in this box (edge 4: the division is an exact scaling)"""
+    q = (((pos - F(-2.0)) / F(4.0)) * F(64.0)).astype(F)
+    c = np.clip(np.floor(q).astype(np.int64), 0, 63)
+    return ((c[:, 2] * 64 + c[:, 1]) * 64 + c[:, 0]).astype(np.uint32)
+
+
+RAMP = om.halfspace((-1.75, -1.85, 0.0), (-0.5, 1.0, 0.0))             # tilted about z; cuts through the dam
+PILLAR_HALF = (3 * S, 6 * S, 3 * S)
+SHAPES = {
+    "sphere": om.sphere((-1.7, -1.6, -1.8), 0.3),
+    "box": om.box((-1.5, -1.7, -1.6), (0.11, 0.3, 0.17)),
+    "round_box": om.box((-1.2, -1.5, -1.3), (0.2, 0.3, 0.25), 0.07),
+    "capsule": om.capsule((-1.9, -1.9, -1.9), (-1.2, -1.4, -1.0), 0.12),
+    "halfspace": RAMP,
+    "bowl": om.sphere((-1.0, -1.0, -1.0), 1.4, invert=True),
+}
+UNION = [SHAPES[k] for k in ("box", "capsule", "sphere", "halfspace", "round_box")]
+CALLER_BOUNDS = ((-1.9, -2.0, -1.7), (-0.6, -0.9, -0.2))
+
+
+# ---- 1. build equals the model ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("bounds,spacing", [(None, S), (CALLER_BOUNDS, 0.05), (None, 0.0)])
+def test_build_equals_the_model(bounds, spacing):
+    lo, hi = bounds if bounds else (BMIN, BMAX)
+    grid = om.lattice(spacing, lo, hi)
+    with _ctx(64) as c:
+        assert c.obstacle() is None
+        g = c.obstacle_lattice(spacing, bounds)
+        assert tuple(g.dims) == grid["dims"] and g.spacing == grid["spacing"]
+        _same(np.array(list(g.origin), F), grid["origin"])
+        for name, shapes in [(k, [v]) for k, v in SHAPES.items()] + [("union", UNION)]:
+            if spacing == 0.0 and name != "union":
+                continue                                   # (the default spacing: 131^3 nodes, the union only)
+            _build(c, shapes, spacing, bounds)
+            ob = c.obstacle(read=True)
+            assert ob["dims"] == grid["dims"] and ob["spacing"] == grid["spacing"], name
+            _same(ob["origin"], grid["origin"], name)
+            assert not ob["offset"].any() and not ob["velocity"].any()
+            _same(ob["phi"], om.rasterise(shapes, grid), name)
+
+
+def test_set_grid_round_trips_with_the_clamp():
+    rng = np.random.default_rng(3)
+    phi = rng.normal(0.0, 3.0, (9, 14, 23)).astype(F)
+    grid = {"dims": (23, 14, 9), "origin": np.array([-1.0, -0.5, 0.25], F), "spacing": F(0.05)}
+    D = om.clamp_distance(grid)                            # 2.3: a third of the values lie beyond it
+    assert (np.abs(phi) > D).sum() > 500
+    with _ctx(64) as c:
+        c.set_obstacle_grid(phi, grid["origin"], grid["spacing"])
+        ob = c.obstacle(read=True)
+        assert ob["dims"] == grid["dims"]
+        _same(ob["phi"], om.clamp(phi, grid))
+        assert np.abs(ob["phi"]).max() == D
+
+
+# ---- 2. sample equals the model ---------------------------------------------------------------------------------------------
+def smooth_field(grid, seed):
+    """A smooth field that is NOT a distance: a low-frequency sum of products of cosines, values in about [-0.1, 0.4], with the
+    phases drawn around those that make every mode lowest at the dam's centre: the negative pocket overlaps the dam."""
+    rng = np.random.default_rng(seed)
+    x, y, z = (a.astype(np.float64) for a in om.node_positions(grid))
+    centre = np.array([-1.77, -1.77, -1.77])
+    f = np.full((z.size, y.size, x.size), 0.15)
+    for _ in range(4):
+        k = rng.uniform(4.0, 14.0, 3)                      # wavelengths 0.45 .. 1.6: the dam is 0.47 wide
+        p = -k * centre + rng.uniform(-0.6, 0.6, 3) + np.array([0.0, 0.0, np.pi])
+        f += 0.0625 * np.cos(k[0] * x + p[0])[None, None, :] * np.cos(k[1] * y + p[1])[None, :, None] * np.cos(k[2] * z + p[2])[:, None, None]
+    return f.astype(F)
+
+
+def _sample_points(grid, off, rng):
+    x, y, z = om.node_positions(grid)
+    n = [a.size for a in (x, y, z)]
+    pts = [rng.uniform(-2.2, 2.2, (16000, 3))]
+    on = rng.uniform(-2.0, 2.0, (1500, 3))                 # on node planes (before the offset)
+    for k, ax in enumerate((x, y, z)):
+        on[k * 500:(k + 1) * 500, k] = rng.choice(ax, 500)
+    pts.append(on)
+    last = rng.uniform(-2.0, 2.0, (1500, 3))               # in the last cell of every axis, and on its far node plane
+    for k, ax in enumerate((x, y, z)):
+        last[k * 500:(k + 1) * 500, k] = rng.uniform(ax[n[k] - 2], ax[n[k] - 1], 500)
+        last[k * 500:k * 500 + 5, k] = [ax[n[k] - 1], ax[n[k] - 2], ax[0], np.nextafter(ax[0], F(-9)), np.nextafter(ax[n[k] - 1], F(-9))]
+    pts.append(last)
+    bad = rng.uniform(-2.0, 2.0, (1000, 3))
+    bad[:300, 0] = np.inf; bad[300:500, 1] = -np.inf; bad[500:800, 2] = np.nan; bad[800:, 0] = rng.uniform(5.0, 1e30, 200)
+    pts.append(bad)
+    pts = np.concatenate(pts).astype(F)
+    return (pts + np.asarray(off, F)).astype(F)            # (inf and NaN stay what they are)
+
+
+@pytest.mark.parametrize("field", ["box_and_capsule", "random"])
+def test_sample_equals_the_model(field):
+    grid = om.lattice(S, BMIN, BMAX)
+    off = np.array([0.03, -0.02, 0.01], F)
+    pts = _sample_points(grid, off, np.random.default_rng(17))
+    assert pts.shape == (20000, 3)
+    with _ctx(64) as c:
+        if field == "random":
+            phi = smooth_field(grid, FIELD_SEED)
+            c.set_obstacle_grid(phi, grid["origin"], grid["spacing"])
+        else:
+            shapes = [SHAPES["box"], SHAPES["capsule"]]
+            phi = om.rasterise(shapes, grid)
+            _build(c, shapes)
+        c.set_obstacle_motion(offset=off)
+        got_phi, got_n, got_in = c.sample_obstacle(pts)
+        ob = c.obstacle()
+        _same(ob["offset"], off)
+    want_phi, want_n, want_in = om.sample(grid, phi, off, pts)
+    assert 15000 < want_in.sum() < 19500 and np.array_equal(got_in, want_in)
+    _same(got_phi, want_phi)
+    _same(got_n, want_n)
+    assert np.isinf(got_phi[~got_in]).all() and not got_n[~got_in].any()
+
+
+# ---- 3, 4, 8, 11. one step of A (with the obstacle) is the model applied to B's output (without) ------------------------------
+def _check_step(stepper, install, fused, min_touched, spheres=None, before_b=None):
+    """A and B from the same upload; `install(a)` gives A its obstacle (before the step, or inside it: `stepper` calls it).
+    Returns (A's state, the model's statistics)."""
+    pos, vel = _dam()
+    with _ctx() as a, _ctx() as b:
+        for c in (a, b):
+            if spheres:
+                c.set_colliders(*spheres)
+            c.upload(pos, vel)
+        stepper(a, lambda: install(a))
+        stepper(b, lambda: None)
+        sa, sb = a.download(), b.download()
+        ob = a.obstacle(read=True)
+        p4 = a.positions4()
+        a.hash()                                           # the NEXT hash: after a fused step it takes the keys the pass left
+        keys = a.keys()
+        slot_pos, _, slot_idx = a.download_owned()
+        assert not ob["offset"].any()
+    st = {}
+    want_p, want_v, touched = om.push(sb["pos"], sb["vel"], _grid_of(ob), ob["phi"], ZERO, ZERO, BMIN, BMAX, EPS, DAMP, stats=st)
+    st["touched"] = touched
+    assert touched.sum() >= min_touched, touched.sum()
+    _same(sa["pos"], want_p, "pos")                        # every particle, touched or not
+    _same(sa["vel"], want_v, "vel")
+    _same(sa["density"], sb["density"], "density")
+    _same(sa["pressure"], sb["pressure"], "pressure")
+    assert not np.array_equal(sa["pos"], sb["pos"])
+    _same(p4[:, :3], want_p, "positions by index")
+    assert (p4[:, 3] == 1.0).all()
+    _same(slot_pos, want_p[slot_idx])
+    assert np.array_equal(keys, _keys_of(slot_pos)), int((keys != _keys_of(slot_pos)).sum())
+    moved_cell = _keys_of(want_p) != _keys_of(sb["pos"])
+    if fused:                                              # (so the key fix is exercised: the push took particles to other cells)
+        assert (moved_cell & touched).sum() > 0
+    return sa, st
+
+
+def _fused(c, install):
+    install()
+    c.step(DT, 1)
+
+
+def _phased(c, install):
+    install()
+    c.step_phased(DT, 1)
+
+
+def _mid_step(c, install):
+    c.hash(); c.sort(); c.build_cells(); c.density()
+    install()                                              # between sph_density and sph_force: this step's integrate uses it
+    c.force(); c.collide(); c.integrate(DT)
+
+
+def test_one_fused_step_is_the_model_on_the_twins_output():
+    _check_step(_fused, lambda a: _build(a, [RAMP]), True, 501)
+
+
+def test_one_phased_step_is_the_model_on_the_twins_output():
+    _check_step(_phased, lambda a: _build(a, [RAMP]), False, 501)
+
+
+FIELD_SEED = 20         # chosen on the CPU (the model on the dam as uploaded: 184 touched, 49 at the 4th push): both cases below occur
+
+
+@pytest.mark.parametrize("stepper,fused", [(_fused, True), (_phased, False)])
+def test_the_acceleration_is_exact_on_a_field_that_is_no_distance(stepper, fused):
+    grid = om.lattice(S, BMIN, BMAX)
+    phi = smooth_field(grid, FIELD_SEED)
+    assert -0.12 < phi.min() < -0.02 and 0.3 < phi.max() < 0.42
+    sa, st = _check_step(stepper, lambda a: a.set_obstacle_grid(phi, grid["origin"], grid["spacing"]), fused, 100)
+    it = st["iterations"]
+    assert (it >= 2).sum() > 0, np.bincount(it)
+    four = it == om.ITERATIONS
+    after, _, inside = om.sample(grid, phi, ZERO, sa["pos"][four])
+    assert (inside & (after < EPS)).sum() > 0, (int(four.sum()), np.bincount(it))     # stopped by the count, not by phi >= eps
+
+
+def test_spheres_and_an_obstacle_together():
+    sphere = ([[-1.75, -1.72, -1.74]], [0.1875], [[300.0, -150.0, 80.0]])
+    sa, st = _check_step(_fused, lambda a: _build(a, [RAMP]), True, 400, spheres=sphere)
+    # (and B's sphere did move particles: the obstacle's pass ran behind the spheres' push)
+    pos, vel = _dam()
+    with _ctx() as plain:
+        plain.upload(pos, vel); plain.step(DT, 1)
+        assert not np.array_equal(plain.download()["pos"][~st["touched"]], sa["pos"][~st["touched"]])
+
+
+def test_installed_between_density_and_force_the_integrate_uses_it():
+    _check_step(_mid_step, lambda a: _build(a, [RAMP]), False, 501)
+
+
+# ---- 5. marks stay consistent ---------------------------------------------------------------------------------------------------
+PILLAR5 = om.box((-1.5, -1.2, -1.75), (0.09, 0.3, 0.1))     # overlaps the flowing dam's front by a cell
+
+
+def test_marks_stay_consistent_with_the_merge_sort():
+    pos, vel = _flowing()
+    grid = om.lattice(S, BMIN, BMAX)
+    first, _, _ = om.push(pos, vel, grid, om.rasterise([PILLAR5], grid), ZERO, ZERO, BMIN, BMAX, EPS, DAMP)
+    assert (_keys_of(first) != _keys_of(pos)).sum() >= 20    # the push itself takes particles to other cells: marks the pass must set
+    out = []
+    for merge in (True, False):
+        with _ctx() as c:
+            c.set_sort_mode(merge)
+            _build(c, [PILLAR5])
+            c.upload(pos, vel)
+            c.step(DT, 40)
+            out.append((c.download(), c.sort_stats(), c.positions4()))
+    (sm, stm, pm), (sf, stf, pf) = out
+    _same_state(sm, sf)
+    _same(pm, pf)
+    assert stm["merges"] >= 30 and stm["movers_total"] > 0, stm
+    assert stf["merges"] == 0, stf
+    pos0, vel0 = _flowing()
+    with _ctx() as b:                                      # (and the pillar did change the flow)
+        b.upload(pos0, vel0); b.step(DT, 40)
+        assert not np.array_equal(b.download()["pos"], sm["pos"])
+
+
+# ---- 6. a dam against a pillar ----------------------------------------------------------------------------------------------------
+PILLAR = om.box((-1.5 + 3 * S, -1.7, -1.75), PILLAR_HALF)   # its -x face 0.03 in front of the dam
+FLOW_VX = 833.0                                             # 300 steps of 5e-7: 0.125, two cells
+
+
+def test_a_dam_against_a_pillar():
+    pos, vel = _dam()
+    vel[:, 0] = FLOW_VX
+    deep = {}
+    for name, pillar in (("with", True), ("without", False)):
+        with _ctx() as c:
+            if pillar:
+                _build(c, [PILLAR])
+            c.upload(pos, vel)
+            for _ in range(6):
+                c.step(DT, 50)
+                st = c.download()
+                assert np.isfinite(st["pos"]).all() and np.isfinite(st["vel"]).all()
+                assert (np.abs(st["pos"]) <= 2.0).all() and c.n == N
+                d = om.analytic(PILLAR, st["pos"])
+                if pillar:
+                    assert d.min() >= -S, d.min()          # the interpolation's worst error is half a spacing
+            deep[name] = int((d < -S).sum())
+    assert deep["with"] == 0 and deep["without"] >= 20, deep
+
+
+# ---- 7. a moving ramp pushes the dam ------------------------------------------------------------------------------------------------
+PISTON = om.halfspace((-1.97, -2.0, 0.0), (1.0, 0.5, 0.0))
+PISTON_BOUNDS = ((-2.5, -2.0, -2.0), (2.0, 2.0, 2.0))      # the grid moves with the solid: it must still cover the wall it leaves
+
+
+def test_a_moving_ramp_pushes_the_dam():
+    pos, vel = _dam()
+    u = np.array([FLOW_VX, 0.0, 0.0], F)
+    nrm = om.unit_normal(PISTON["b"]).astype(np.float64)
+    runs = {}
+    for name, piston in (("with", True), ("without", False)):
+        with _ctx() as c:
+            if piston:
+                _build(c, [PISTON], S, PISTON_BOUNDS)
+                c.set_obstacle_motion(velocity=u)
+            c.upload(pos, vel)
+            done = 0
+            for _ in range(6):
+                c.step(DT, 50)
+                done += 50
+                st = c.download()
+                assert np.isfinite(st["pos"]).all() and np.isfinite(st["vel"]).all() and c.n == N
+                if piston:
+                    _same(c.obstacle()["offset"], om.advance(ZERO, u, DT, done))
+            runs[name] = st
+    used = om.advance(ZERO, u, DT, 299).astype(np.float64)     # the offset the last step pushed with
+    st = runs["with"]
+    d = (st["pos"].astype(np.float64) - used - PISTON["a"].astype(np.float64)) @ nrm
+    assert d.min() >= -1e-5 * 4.0, d.min()
+    ahead = (d >= 0) & (d < 0.1)                               # within h in front of the plane
+    assert ahead.sum() >= 20, ahead.sum()
+    along = float(st["vel"][ahead, 0].mean())
+    along0 = float(runs["without"]["vel"][ahead, 0].mean())
+    assert along > 0.2 * FLOW_VX, (along, along0)
+    assert abs(along0) < 0.05 * FLOW_VX, (along, along0)
+
+
+# ---- 9. cleared means gone --------------------------------------------------------------------------------------------------------
+def test_cleared_means_gone():
+    pos, vel = _flowing()
+    with _ctx() as a, _ctx() as b:
+        before = capi.memory_stats()
+        _build(a, [PILLAR5])
+        a.set_obstacle_motion(offset=(0.1, 0.0, 0.0), velocity=(5.0, 0.0, 0.0))
+        assert capi.memory_stats()[2] == before[2] + 2 and capi.memory_stats()[0] > before[0]
+        a.clear_obstacle()
+        assert capi.memory_stats() == before
+        assert a.obstacle() is None
+        a.clear_obstacle()                                 # twice: still fine
+        a.upload(pos, vel); b.upload(pos, vel)
+        a.step(DT, 50); b.step(DT, 50)
+        _same_state(a.download(), b.download())
+        _same(a.positions4(), b.positions4())
+        assert capi.memory_stats() == before
+        _build(a, [PILLAR5])                               # the motion went with it
+        ob = a.obstacle()
+        assert not ob["offset"].any() and not ob["velocity"].any()
+
+
+# ---- 10. refusals change nothing ------------------------------------------------------------------------------------------------------
+def test_refusals_change_nothing():
+    L = capi.load()
+    INVALID, CAPACITY, STATE, NOMEM = -1, -4, -5, -3
+    pos, vel = _dam()
+    ok_shape = _shape(SHAPES["box"])
+    f3 = lambda *v: (C.c_float * 3)(*v)
+    with capi.Context(N, params=capi.default_params(BOX, GRID), slab=(0, GRID[2]), ghost_capacity=256) as s:
+        base = capi.memory_stats()
+        g = capi.ObstacleGrid((C.c_uint32 * 3)(2, 2, 2), f3(0, 0, 0), 0.1)
+        assert L.sph_obstacle_build(s.h, S, None, None, 1, C.byref(ok_shape)) == STATE
+        assert L.sph_obstacle_set_grid(s.h, C.byref(g), np.zeros(8, F).ctypes.data) == STATE
+        assert L.sph_obstacle_set_motion(s.h, f3(0, 0, 0), f3(1, 0, 0)) == STATE
+        assert s.obstacle() is None and capi.memory_stats() == base
+    with _ctx() as a, _ctx() as b:
+        base = capi.memory_stats()
+
+        def build(shapes, spacing=S, lo=None, hi=None, n=None):
+            arr = (capi.Shape * max(len(shapes), 1))(*shapes)
+            return L.sph_obstacle_build(a.h, spacing, lo, hi, len(shapes) if n is None else n, arr)
+
+        def shape(kind, a3=(0, 0, 0), b3=(0, 0, 0), r=0.0):
+            return capi.Shape(kind, 0, f3(*a3), f3(*b3), r)
+
+        def grid(dims, spacing=0.1, origin=(0, 0, 0), phi=None):
+            g = capi.ObstacleGrid((C.c_uint32 * 3)(*dims), f3(*origin), spacing)
+            phi = np.zeros(min(int(np.prod(dims, dtype=np.int64)), 1 << 16) or 1, F) if phi is None else phi
+            return L.sph_obstacle_set_grid(a.h, C.byref(g), phi.ctypes.data)
+
+        # shapes
+        assert build([]) == INVALID and build([ok_shape] * 17) == INVALID
+        assert build([ok_shape], n=0) == INVALID
+        assert L.sph_obstacle_build(a.h, S, None, None, 1, None) == INVALID
+        assert build([shape(4, r=1.0)]) == INVALID and build([shape(-1, r=1.0)]) == INVALID
+        assert build([shape(capi.SHAPE_BOX, b3=(0.1, 0.0, 0.1))]) == INVALID
+        assert build([shape(capi.SHAPE_BOX, b3=(0.1, -0.2, 0.1))]) == INVALID
+        assert build([shape(capi.SHAPE_BOX, b3=(0.1, 0.2, 0.1), r=-0.01)]) == INVALID
+        assert build([shape(capi.SHAPE_CAPSULE, a3=(0.1, 0.2, 0.3), b3=(0.1, 0.2, 0.3), r=0.1)]) == INVALID
+        assert build([shape(capi.SHAPE_CAPSULE, b3=(1, 0, 0), r=-0.1)]) == INVALID
+        assert build([shape(capi.SHAPE_HALFSPACE, b3=(0, 0, 0))]) == INVALID
+        assert build([shape(capi.SHAPE_HALFSPACE, b3=(0, float("nan"), 1))]) == INVALID
+        assert build([shape(capi.SHAPE_SPHERE, r=0.0)]) == INVALID and build([shape(capi.SHAPE_SPHERE, r=-1.0)]) == INVALID
+        assert build([shape(capi.SHAPE_SPHERE, a3=(float("inf"), 0, 0), r=1.0)]) == INVALID
+        assert build([ok_shape, shape(capi.SHAPE_SPHERE, r=0.0)]) == INVALID          # all or nothing
+        # the lattice of a build
+        assert build([ok_shape], spacing=-0.1) == INVALID and build([ok_shape], spacing=float("nan")) == INVALID
+        assert build([ok_shape], spacing=float("inf")) == INVALID
+        assert build([ok_shape], spacing=0.001) == CAPACITY                            # 4003 nodes per axis
+        assert build([ok_shape], spacing=0.004) == CAPACITY                            # 1003^3 nodes
+        assert build([ok_shape], lo=f3(0, 0, 0)) == INVALID                            # one corner only
+        assert build([ok_shape], lo=f3(0, 0, 0), hi=f3(1, -1, 1)) == INVALID
+        assert build([ok_shape], lo=f3(0, 0, 0), hi=f3(1, float("nan"), 1)) == INVALID
+        out = capi.ObstacleGrid((C.c_uint32 * 3)(7, 7, 7), f3(1, 1, 1), 9.0)
+        assert L.sph_obstacle_lattice(a.h, 0.001, None, None, C.byref(out)) == CAPACITY and tuple(out.dims) == (7, 7, 7)
+        # a caller's grid
+        assert grid((1, 5, 5)) == INVALID and grid((5, 5, 0)) == INVALID
+        assert grid((2049, 2, 2)) == CAPACITY and grid((1024, 1024, 256)) == CAPACITY
+        assert grid((4, 4, 4), spacing=0.0) == INVALID and grid((4, 4, 4), spacing=-1.0) == INVALID
+        assert grid((4, 4, 4), spacing=float("nan")) == INVALID and grid((4, 4, 4), spacing=float("inf")) == INVALID
+        assert grid((4, 4, 4), origin=(0, float("inf"), 0)) == INVALID
+        bad = np.zeros(64, F); bad[37] = np.nan
+        assert grid((4, 4, 4), phi=bad) == INVALID
+        bad[37] = np.inf
+        assert grid((4, 4, 4), phi=bad) == INVALID
+        assert L.sph_obstacle_set_grid(a.h, None, bad.ctypes.data) == INVALID
+        # a motion
+        assert L.sph_obstacle_set_motion(a.h, f3(0, float("nan"), 0), None) == INVALID
+        assert L.sph_obstacle_set_motion(a.h, f3(1, 2, 3), f3(0, 0, float("inf"))) == INVALID
+        assert L.sph_obstacle_read(a.h, bad.ctypes.data) == STATE
+        assert L.sph_obstacle_sample(a.h, 1, bad.ctypes.data, None, None, None) == STATE
+        # every allocation of a build failing once
+        for k in (1, 2):
+            capi.fail_alloc(k)
+            assert build([ok_shape]) == NOMEM, k
+            capi.fail_alloc(0)
+            assert a.obstacle() is None and capi.memory_stats() == base, k
+        # ... also over an installed obstacle: none is left
+        assert build([ok_shape]) == 0 and a.obstacle() is not None
+        capi.fail_alloc(2)
+        assert grid((4, 4, 4)) == NOMEM
+        capi.fail_alloc(0)
+        assert a.obstacle() is None and capi.memory_stats() == base
+        capi.fail_alloc(3)                                 # one more than a build makes: it goes through
+        assert build([ok_shape]) == 0
+        capi.fail_alloc(0)
+        a.clear_obstacle()
+        # nothing of all this is left: a step equals the twin's
+        ob = a.obstacle()
+        assert ob is None and capi.memory_stats() == base
+        g = capi.ObstacleGrid()
+        off, vel3 = f3(9, 9, 9), f3(9, 9, 9)
+        assert L.sph_obstacle_get(a.h, C.byref(g), off, vel3) == 0 and not any(g.dims) and not any(off) and not any(vel3)
+        a.upload(pos, vel); b.upload(pos, vel)
+        a.step(DT, 2); b.step(DT, 2)
+        _same_state(a.download(), b.download())
