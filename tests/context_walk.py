@@ -8,7 +8,8 @@ Three things live here, all of them plain data or plain Python:
            tests/test_context_walk_cpu.py parses the document and compares -- and the SPH_REQUIRE conditions of the phase
            calls, and says "accepted" (0) or SPH_E_STATE for any call, and which phase calls must now be refused.
 
-  Walker   a context under test, its Mirror and its TWIN.  The twin is the expected value of everything that is NOT
+  Walker   a context under test, its Mirror, its TWIN and, where an obstacle is about, a BARE twin (the twin without the obstacle:
+           the first integrate behind a boundary must be obstacle_model.push of ITS output) and a numpy record of the obstacle.  The twin is the expected value of everything that is NOT
            observable (keys_fresh, the mover marks, the cell table, the scan bookkeeping): a FRESH context that is given what
            the public API showed at the last BOUNDARY -- the last moment particles changed: an integrate or an edit -- by
            sph_upload in slot order, with the same parameters, colliders, bodies and settings, and that then makes the calls
@@ -21,6 +22,7 @@ Three things live here, all of them plain data or plain Python:
 An op is a tuple (name, args...); call_id() names it.  Nothing here peeks into the struct."""
 import numpy as np
 
+import obstacle_model as om
 import region_model
 
 LOADED, HASHED, SORTED, CELLS = 0, 1, 2, 3
@@ -40,6 +42,8 @@ TABLE = {
     "sph_set_collider_bodies": _NONE, "sph_set_colliders": _NONE,
     "sph_sort": ("set SORTED", "set", "cleared", "kept"),
     "force_finish": _NONE,
+    "sph_obstacle_build": _NONE,         # ... and _set_grid, _clear, _set_motion, _sample: one row of the document
+    "sph_mesh_extract": _NONE,           # the views: sph_render, sph_render_surface, sph_mesh_extract, one row as well
 }
 # rows of the document that a whole-domain context under the native API cannot execute (named by an identifier of their
 # first cell): not walked, and said so
@@ -58,13 +62,35 @@ BOX, GRID = (2.0, 2.0, 2.0), (32, 32, 32)
 DT_FLOW, DT_REST = 2e-5, 5e-7
 SNAP_N, SNAP_SEED = 3000, 7
 SBI_FIRST, SBI_COUNT = 100, 300                 # creation indices every installed set of this module holds
-# regions of sph_remove: z-slabs of 0.05 (every set of this module has particles in each of them: the lattice has a layer
-# every 0.03125, the random boxes fill z in [-1, -0.1)); no box variant below moves a z wall
+# regions of sph_remove: z-slabs of 0.05 (every set of this module has particles in each of 0 .. 4: the lattices have a layer
+# every 0.03125 from -0.984 up to -0.766 at least, the random boxes fill z in [-1, -0.1); slab 5 is for the histories, which hold
+# the random boxes when they get there); no box variant below moves a z wall
 REGIONS = {k: [("box", (-4.0, -4.0, -1.0 + 0.05 * k), (4.0, 4.0, -1.0 + 0.05 * (k + 1)))] for k in range(6)}
 REGIONS["none"] = [("box", (0.5, 0.5, 0.5), (0.75, 0.75, 0.75)), ("sphere", (0.5, 0.5, -0.5), 0.2)]
 PARAM_VARIANTS = ("P0", "visc", "shift", "wall")
 COLLIDER = (np.array([[-0.5, -0.6, -0.55]], np.float32), np.array([0.12], np.float32), np.array([[300.0, 0.0, -200.0]], np.float32))
 BODY = (np.array([2.0e4], np.float32), np.array([[0.0, -9.81 * 11000, 0.0]], np.float32))
+# the solid of ("obstacle_build", "both"): a ramp under the fluid and a pillar in it (it touches particles of EVERY set this
+# module installs: tests/test_context_walk_cpu.py), and the motion of ("obstacle_motion", "on")
+OBSTACLE_SPACING = 1.0 / 16.0
+OBSTACLES = {"both": [om.halfspace((-0.9, -0.93, 0.0), (-0.5, 1.0, 0.0)), om.box((-0.55, -0.6, -0.5), (0.1, 0.4, 0.1))]}
+MOTION = {"on": (np.array([0.013, -0.007, 0.004], np.float32), np.array([300.0, 0.0, -200.0], np.float32)),
+          "off": (np.zeros(3, np.float32), np.zeros(3, np.float32))}
+CALLER_GRID = {"dims": (23, 21, 19), "origin": np.array([-1.13, -1.11, -1.07], np.float32), "spacing": np.float32(0.1)}
+OBSTACLE_OPS = ("obstacle_build", "obstacle_set_grid", "obstacle_motion", "obstacle_clear", "obstacle_sample")
+VIEWS = ("render", "render_surface", "extract_mesh")
+MESH = dict(spacing=1.0 / 16.0, radius=1.0 / 8.0)
+
+
+def caller_field(seed):
+    """the field of ("obstacle_set_grid", seed): a ball in the fluid, roughened -- no distance"""
+    x, y, z = (a.astype(np.float64) for a in om.node_positions(CALLER_GRID))
+    d = np.sqrt((x[None, None, :] + 0.6) ** 2 + (y[None, :, None] + 0.8) ** 2 + (z[:, None, None] + 0.6) ** 2) - 0.35
+    return (d + np.random.default_rng(seed).normal(0.0, 0.02, d.shape)).astype(np.float32)
+
+
+def sample_points():
+    return np.random.default_rng(77).uniform(-1.2, 1.2, (500, 3)).astype(np.float32)
 
 
 def params_variant(name):
@@ -90,7 +116,8 @@ def call_id(op):
     if name == "set_by_index": return f"set_by_index:{op[1]}"
     if name == "emit": return "emit:explicit" if op[3] else "emit:auto"
     if name == "remove": return "remove:nothing" if op[1] == "none" else "remove:something"
-    if name in ("set_params", "set_colliders", "set_collider_bodies", "set_precision", "set_sort_mode"): return f"{name}:{op[1]}"
+    if name in ("set_params", "set_colliders", "set_collider_bodies", "set_precision", "set_sort_mode", "obstacle_build",
+                "obstacle_motion"): return f"{name}:{op[1]}"
     return name
 
 
@@ -110,6 +137,8 @@ class Mirror:
         self.direct_hull, self.small_launch, self.block_order = None, None, None
         self.params = self.params_at_hash = "P0"
         self.n_colliders, self.tracked = 0, False
+        self.obstacle, self.motion = None, None     # the installed grid (None, or a tag that names the field) and the last motion set
+        self.ob_steps = 0                # integrates that advanced the obstacle's offset (those with a grid installed)
         self.sorts = []                  # what apply() predicted for the sorts of the last op: (merge: True/False/None, both forms: True/False/None)
         self.reached, self.calls = set(), set()     # coverage: (row, column, observable), (stage, call id)
 
@@ -171,6 +200,7 @@ class Mirror:
         self._row("force_finish")
         self.have_force = self.have_coll = False
         self.integrated = True
+        self.ob_steps += self.obstacle is not None
 
     def _phase(self, name):
         if name == "hash": self._hash()
@@ -179,7 +209,9 @@ class Mirror:
         elif name == "density": self.have_dens = True
         elif name == "force": self.have_force = True
         elif name == "collide": self.have_coll = True
-        elif name == "integrate": self.have_force = self.have_coll = False; self.integrated = True
+        elif name == "integrate":
+            self.have_force = self.have_coll = False; self.integrated = True
+            self.ob_steps += self.obstacle is not None
         elif name == "fci": self._fused()
 
     # -- every entry point -------------------------------------------------------------------------------------------------------
@@ -228,7 +260,15 @@ class Mirror:
         elif name == "set_pair_small_launch": self.small_launch = int(op[1])
         elif name == "set_block_order": self.block_order = (int(op[1]), int(op[2]))
         elif name == "trust_mover_hint": self.both_until = 0
-        elif name not in ("render", "count_in", "download", "sync"):
+        elif name == "obstacle_build": self.obstacle = ("build", op[1]); self._row("sph_obstacle_build")
+        elif name == "obstacle_set_grid": self.obstacle = ("grid", int(op[1])); self._row("sph_obstacle_build")
+        elif name == "obstacle_motion": self.motion = op[1]; self._row("sph_obstacle_build")
+        elif name == "obstacle_clear": self.obstacle = self.motion = None; self._row("sph_obstacle_build")     # (the motion goes with it)
+        elif name == "obstacle_sample":
+            if self.obstacle is None: return E_STATE
+            self._row("sph_obstacle_build")
+        elif name in VIEWS: self._row("sph_mesh_extract")
+        elif name not in ("count_in", "download", "sync"):
             raise KeyError(name)
         return 0
 
@@ -274,16 +314,25 @@ PREFIXES = {     # name -> dict(before: ops in front of the boundary, after: ops
     "skipped": dict(before=[("upload", 512, "rest"), ("step_until_skipped", 3), ("trust_mover_hint",)], after=[], dt=DT_REST, capacity=4096),
     "uploaded": dict(before=[_UP], after=[]),
     "edited": dict(before=[_UP] + _STEPPED, after=[("set_by_index", "both", 21)]),
-    # more than one sort tile (4096 keys) and more than one 4096-slot mover tile; the merge path behind a deferred table clear
+    # more than one sort tile (4096 keys) and more than one 16384-slot mover tile; the merge path behind a deferred table clear
     "hashed_20k": dict(before=[("upload", 20000, "flow")] + _STEPPED, after=[("hash",)], capacity=24576, calls="few"),
     # a collider with a free body (tracked: the spheres live on the device), and the mixed-precision density pass
     "density_body": dict(before=[("set_colliders", "one"), ("set_collider_bodies", "on"), _UP] + _STEPPED,
                          after=[("hash",), ("sort",), ("build_cells",), ("density",)], calls="few"),
     "sorted_mixed": dict(before=[("set_precision", 1), _UP] + _STEPPED, after=[("hash",), ("sort",)], calls="few"),
+    # a moving obstacle installed before anything else: every call of CALLS meets a context that already has one
+    "stepped_obstacle": dict(before=[("obstacle_build", "both"), ("obstacle_motion", "on"), _UP] + _STEPPED, after=[]),
+    # ... and with two tiles of the movers' marks (16384 slots each) under the obstacle's pass
+    "hashed_20k_obstacle": dict(before=[("obstacle_build", "both"), ("upload", 20000, "flow")] + _STEPPED, after=[("hash",)],
+                                capacity=24576, calls="few"),
 }
 CONTINUATIONS = ("phases", "fci", "step")
 
-# name -> (class, ops, anchor): anchor = the step that follows also runs against the float64 model
+# name -> (class, ops, anchor): anchor True = the step that follows also runs against the float64 model; "bare" = the first
+# integrate that follows is tests/obstacle_model.py's push applied to the output of a BARE twin (Walker.bare), a context without
+# the obstacle.  (A prefix that installs an obstacle runs every call it has with the bare twin, and none against the float64
+# model, which knows no obstacle.)
+_OB = ("obstacle_build", "both")
 CALLS = {
     "upload_smaller": ("edit", [("upload", 3000, "flow")], False),
     "load_snapshot": ("edit", [("load_snapshot",)], False),
@@ -322,9 +371,25 @@ CALLS = {
     "cells_again": ("keep", [("build_cells",)], False),
     "density_again": ("keep", [("density",)], False),
     "refused_phase": ("keep", [], False),          # the walker probes every refused phase call after every call: here nothing else happens
+    "obstacle_on": ("keep", [_OB], "bare"),
+    "obstacle_off": ("keep", [_OB, ("obstacle_clear",)], "bare"),
+    "obstacle_moving": ("keep", [_OB, ("obstacle_motion", "on")], "bare"),
+    "obstacle_replaced": ("keep", [("obstacle_set_grid", 51), _OB], "bare"),
+    "obstacle_caller_grid": ("keep", [_OB, ("obstacle_set_grid", 52), ("obstacle_motion", "on")], "bare"),
+    "obstacle_motion_alone": ("keep", [("obstacle_motion", "on")], "bare"),       # no grid: nothing pushes, the offset stays
+    "obstacle_sample": ("keep", [_OB, ("obstacle_motion", "on"), ("obstacle_sample",)], "bare"),
+    "obstacle_sample_none": ("keep", [("obstacle_sample",)], False),               # refused without a grid
+    "render_surface": ("keep", [("render_surface",)], False),
+    "extract_mesh": ("keep", [("extract_mesh",)], False),
+    "obstacle_remove": ("edit", [_OB, ("remove", 0)], "bare"),
+    "obstacle_emit": ("edit", [_OB, ("emit", 120, 46, False)], "bare"),
+    "obstacle_set_by_index": ("edit", [_OB, ("set_by_index", "both", 35)], "bare"),
+    "obstacle_load_snapshot": ("edit", [_OB, ("load_snapshot",)], "bare"),
+    "obstacle_box_moved": ("keep", [_OB, ("set_params", "shift")], "bare"),        # the walls are the new box's; the solid stays
 }
 FEW = ("upload_smaller", "reset_lattice", "set_by_index_both", "emit_auto", "remove_something", "remove_nothing", "remove_emit",
-       "emit_remove", "params_box_moved", "precision_mixed", "sort_mode_0", "hash_again", "refused_phase")
+       "emit_remove", "params_box_moved", "precision_mixed", "sort_mode_0", "hash_again", "refused_phase",
+       "obstacle_on", "obstacle_off", "obstacle_moving", "obstacle_remove", "obstacle_emit")
 
 
 def calls_for(prefix):
@@ -339,11 +404,16 @@ def usable(m, ops):
 
 # ---- long histories ----------------------------------------------------------------------------------------------------------
 FUZZ_SEEDS = (101, 102, 103, 104, 106, 107, 108, 109)       # each holds at least one refused call
+# histories that also draw the obstacle calls and the views (extended=True): each holds at least two installations, a clear, a
+# change of motion, a view and a refused call (tests/test_context_walk_cpu.py); their steps are single ones, so that the bare
+# twin anchors every completed step that has an obstacle
+FUZZ_SEEDS_OBSTACLE = (201, 202, 203, 204, 206, 211)
 FUZZ_CAPACITY = 16384
 
 
-def fuzz_ops(seed, n_ops=40):
-    """The operation list of one seed: an upload and n_ops calls, each legal or deliberately illegal by the mirror."""
+def fuzz_ops(seed, n_ops=40, extended=False):
+    """The operation list of one seed: an upload and n_ops calls, each legal or deliberately illegal by the mirror.  extended: a
+    quarter of the calls are the obstacle's or a view (drawn first, so the lists of the plain seeds are what they always were)."""
     rng = np.random.default_rng(seed)
     m = Mirror(FUZZ_CAPACITY)
     ops = []
@@ -359,9 +429,22 @@ def fuzz_ops(seed, n_ops=40):
     push(("upload", 6000, "flow"))
     head = len(ops)
     while len(ops) < head + n_ops:
+        if extended and rng.random() < 0.25:
+            k = int(rng.integers(12))
+            s = int(rng.integers(1 << 20))
+            if k in (0, 1, 2): push(("obstacle_build", "both"))
+            elif k in (3, 4): push(("obstacle_set_grid", s))
+            elif k == 5: push(("obstacle_clear",))
+            elif k in (6, 7): push(("obstacle_motion", ("on", "off")[s % 2]))
+            elif k == 8: push(("obstacle_sample",))           # refused while no grid is installed
+            elif k == 9: push(("render",))
+            elif k == 10: push(("render_surface",))
+            else: push(("extract_mesh",))
+            continue
         r = rng.random()
         if r < 0.20:
-            push([("step", 1), ("step", 2), ("step_phased", 1)][rng.integers(3)])
+            push([("step", 1), ("step", 2), ("step_phased", 1)][rng.integers(3)] if not extended else
+                 [("step", 1), ("step_phased", 1)][rng.integers(2)])
         elif r < 0.50:
             push((m.next_phase(fused=rng.random() < 0.4),))
         elif r < 0.72:
@@ -482,12 +565,20 @@ class Walker:
         self.live = np.zeros(0, np.uint32)
         self.trace = []
         self.cam = capi.look_at(32, 24, eye=(0.0, 0.0, 3.0))
+        # the obstacle as numpy knows it (never read from the library): the grid and the field of the last installation, and the
+        # offset advanced by obstacle_model.advance once per integrate with a grid installed
+        self.ob, self.off, self.u = None, np.zeros(3, np.float32), np.zeros(3, np.float32)
+        # the bare twin: like the twin, but without the obstacle and its calls; good for ONE integrate behind its boundary
+        self.bare = False
+        self.b = self.bm = None
+        self.b_fresh = False
+        self.anchored = self.anchor_touched = 0
 
     def close(self):
-        for c in (self.c, self.t):
+        for c in (self.c, self.t, self.b):
             if c is not None:
                 c.close()
-        self.c = self.t = None
+        self.c = self.t = self.b = None
 
     def __enter__(self):
         return self
@@ -550,6 +641,21 @@ class Walker:
         if name == "render":
             rc, _ = _rc(c.render, self.cam, color="speed", lo=0.0, hi=80.0)
             return (rc, None) if rc else _rc(c.read_image)
+        if name == "render_surface":               # the defaults: absorption (the thickness pass) on
+            rc, _ = _rc(c.render_surface, self.cam)
+            return (rc, None) if rc else _rc(lambda: c.read_image() + c.read_surface())
+        if name == "extract_mesh":
+            mp = self.capi.mesh_defaults(**MESH)
+            rc, counts = _rc(c.extract_mesh, mp)
+            return (rc, None) if rc else _rc(lambda: (c.mesh_lattice(mp), counts, c.mesh_field()) + c.read_mesh())
+        if name == "obstacle_build":
+            shapes = [self.capi.Shape(int(sh["kind"]), int(sh["invert"]), self.capi._f3(sh["a"]), self.capi._f3(sh["b"]), float(sh["r"]))
+                      for sh in OBSTACLES[op[1]]]
+            return _rc(c.build_obstacle, shapes, OBSTACLE_SPACING)
+        if name == "obstacle_set_grid": return _rc(c.set_obstacle_grid, caller_field(op[1]), CALLER_GRID["origin"], CALLER_GRID["spacing"])
+        if name == "obstacle_motion": return _rc(c.set_obstacle_motion, offset=MOTION[op[1]][0], velocity=MOTION[op[1]][1])
+        if name == "obstacle_clear": return _rc(c.clear_obstacle)
+        if name == "obstacle_sample": return _rc(c.sample_obstacle, sample_points())
         if name == "download": return _rc(c.download)
         if name == "download_forces": return _rc(c.download_forces)
         if name == "set_precision": return _rc(c.set_precision, bool(op[1]))
@@ -574,6 +680,7 @@ class Walker:
             assert (sel > 0) == (op[1] != "none"), ("the region of this walk selects", sel)
         if name in ("sort", "step", "step_phased"):
             before = (c.sort_stats(), c.sort_forms())
+        ob_steps, off_before = m.ob_steps, self.off
         want_rc = m.apply(op, sel)
         rc, out = self._perform(c, op)
         assert rc == want_rc, f"{op}: returned {rc}, the table says {want_rc}"
@@ -592,6 +699,11 @@ class Walker:
             assert out == int(region_model.selected(c.download_owned()[0], REGIONS[op[1]]).sum()), f"{op}: count"
         elif name in ("upload", "load_snapshot", "reset_lattice"):
             self.live = np.arange(m.n, dtype=np.uint32)
+        elif name in OBSTACLE_OPS:
+            self._obstacle_call(op, out)
+        elif name in VIEWS:
+            self._check_view(op, out)
+        self.off = om.advance(self.off, self.u, self.dt, m.ob_steps - ob_steps)
         if before is not None and m.sorts and all(s[0] is not None for s in m.sorts):
             stats, forms = c.sort_stats(), c.sort_forms()
             assert stats["sorts"] - before[0]["sorts"] == len(m.sorts), f"{op}: sorts"
@@ -612,7 +724,113 @@ class Walker:
             rc2, _ = self._perform(self.t, op)
             assert rc2 == 0, f"{op}: the twin returned {rc2}"
             c.sync(); self.t.sync()               # lockstep: a sort may look at a count the device has produced
+            self._bare_follows(op, m.ob_steps - ob_steps, off_before)
         return 0
+
+    # -- the obstacle, by numpy -------------------------------------------------------------------------------------------------
+    def _params(self):
+        p = self.capi.Params()
+        self.capi._check(self.c.L.sph_get_params(self.c.h, p))
+        return p
+
+    def _obstacle_call(self, op, out):
+        name = op[0]
+        if name == "obstacle_build":               # the lattice is that of the box AS IT IS NOW; a later sph_set_params leaves it
+            p = self._params()
+            grid = om.lattice(OBSTACLE_SPACING, tuple(p.box_min), tuple(p.box_max), p.particle_radius)
+            self.ob = {"grid": grid, "phi": om.rasterise(OBSTACLES[op[1]], grid)}
+        elif name == "obstacle_set_grid":
+            self.ob = {"grid": CALLER_GRID, "phi": om.clamp(caller_field(op[1]), CALLER_GRID)}
+        elif name == "obstacle_motion":
+            self.off, self.u = MOTION[op[1]]
+        elif name == "obstacle_clear":
+            self.ob, self.off, self.u = None, np.zeros(3, np.float32), np.zeros(3, np.float32)
+        elif name == "obstacle_sample":
+            want = om.sample(self.ob["grid"], self.ob["phi"], self.off, sample_points())
+            assert 100 < want[2].sum() < 500
+            assert np.array_equal(out[2], want[2]), f"{op}: inside the grid"
+            assert np.array_equal(_bits(out[0]), _bits(want[0])) and np.array_equal(_bits(out[1]), _bits(want[1])), f"{op}: phi, normal"
+
+    def obstacle_state(self, c):
+        """(grid dims, origin, spacing, offset, velocity, field) as sph_obstacle_get / _read show them; dims (0, 0, 0): none"""
+        capi = self.capi
+        import ctypes as C
+        g, off, vel = capi.ObstacleGrid(), (C.c_float * 3)(), (C.c_float * 3)()
+        capi._check(c.L.sph_obstacle_get(c.h, C.byref(g), off, vel))
+        ob = c.obstacle(read=True)
+        assert (ob is None) == (not any(g.dims))
+        return (tuple(int(v) for v in g.dims), np.array(list(g.origin), np.float32), np.float32(g.spacing),
+                np.array(list(off), np.float32), np.array(list(vel), np.float32), None if ob is None else ob["phi"])
+
+    def _check_obstacle(self, tag):
+        """what the library shows of the obstacle against numpy's record, and the twin's against the context's"""
+        m = self.m
+        got = self.obstacle_state(self.c)
+        assert (m.obstacle is None) == (self.ob is None) == (got[5] is None), f"obstacle installed {tag}"
+        assert np.array_equal(_bits(got[3]), _bits(self.off)), f"obstacle offset {got[3]}, by numpy {self.off} {tag}"
+        assert np.array_equal(_bits(got[4]), _bits(self.u)), f"obstacle velocity {tag}"
+        if self.ob is not None:
+            grid = self.ob["grid"]
+            assert got[0] == tuple(grid["dims"]) and got[2] == grid["spacing"], f"obstacle lattice {tag}"
+            assert np.array_equal(_bits(got[1]), _bits(grid["origin"])), f"obstacle origin {tag}"
+            assert np.array_equal(_bits(got[5]), _bits(self.ob["phi"])), f"obstacle field {tag}"
+        twin = self.obstacle_state(self.t)
+        assert twin[0] == got[0] and twin[2] == got[2] and (twin[5] is None) == (got[5] is None), f"the twin's obstacle {tag}"
+        for x, y in zip(got[1:], twin[1:]):
+            assert x is None or np.array_equal(_bits(x), _bits(y)), f"the twin's obstacle {tag}"
+
+    # -- the views, by numpy ------------------------------------------------------------------------------------------------------
+    def _check_view(self, op, out):
+        import mesh_model, render_model, surface_model
+        c, p = self.c, self._params()
+        pos, vel, idx = c.download_owned()
+        R = p.particle_radius
+        if op[0] == "render":
+            want = render_model.render(pos, self.cam, vel=vel, index=idx, color="speed", lo=0.0, hi=80.0, radius=R)
+            assert np.array_equal(out[1], want[1]), f"{op}: id"
+            assert np.array_equal(_bits(out[2]), _bits(want[2])) and np.array_equal(out[0], want[0]), f"{op}: depth, rgba"
+            assert (want[1] != render_model.NO_ID).any()
+        elif op[0] == "render_surface":
+            w = surface_model.render(pos, self.cam, surface_model.surface_style(), vel=vel, index=idx, radius=R)
+            assert (w.id != render_model.NO_ID).any()
+            for got, want, what in zip(out, (w.rgba, w.id, w.depth, w.raw, w.thick, w.normal), ("rgba", "id", "depth", "raw", "thick", "normal")):
+                assert got.shape == want.shape and np.array_equal(got.view(np.uint8), np.ascontiguousarray(want).view(np.uint8)), f"{op}: {what}"
+        else:
+            counts, origin, _, mpos, mnrm, mtri = mesh_model.mesh_of(pos, tuple(p.box_min), tuple(p.box_max), R, **MESH)
+            (dims, got_origin), (nv, nt), got_counts, gpos, gnrm, gtri = out
+            assert dims == counts.shape[::-1] and np.array_equal(_bits(got_origin), _bits(origin)), f"{op}: lattice"
+            assert nt == len(mtri) > 100 and nv == len(mpos), f"{op}: {nv} vertices, {nt} triangles; the model {len(mpos)}, {len(mtri)}"
+            assert np.array_equal(got_counts, counts), f"{op}: counts"
+            assert np.array_equal(_bits(gpos), _bits(mpos)) and np.array_equal(_bits(gnrm), _bits(mnrm)), f"{op}: vertices"
+            assert np.array_equal(gtri, mtri), f"{op}: triangles"
+
+    # -- the bare twin --------------------------------------------------------------------------------------------------------
+    def _bare_follows(self, op, integrates, off_before):
+        """the bare twin makes the call too, unless it is the obstacle's; behind the first integrate since its boundary the context
+        must hold the model's push of the bare twin's output"""
+        if self.b is None or op[0] in OBSTACLE_OPS:
+            return
+        if self.bm.apply(op) == 0:
+            assert self._perform(self.b, op)[0] == 0, f"{op}: the bare twin"
+            self.b.sync()
+        if op[0] in ("integrate", "fci", "step", "step_phased"):
+            if self.b_fresh and integrates == 1:
+                self._check_against_model(off_before)
+            self.b_fresh = False
+
+    def _check_against_model(self, off_before):
+        c, p, live = self.c, self._params(), self.live
+        tag = f"behind {self.trace[-3:]}"
+        got, bare = c.download(), self.b.download()
+        want_p, want_v, touched = om.push(bare["pos"][live], bare["vel"][live], self.ob["grid"], self.ob["phi"], off_before, self.u,
+                                          tuple(p.box_min), tuple(p.box_max), p.wall_eps, p.wall_damping)
+        assert np.array_equal(_bits(got["pos"][live]), _bits(want_p)), \
+            f"positions against obstacle_model.push of the bare twin's: {int((_bits(got['pos'][live]) != _bits(want_p)).any(axis=1).sum())} of {touched.sum()} touched differ {tag}"
+        assert np.array_equal(_bits(got["vel"][live]), _bits(want_v)), f"velocities against obstacle_model.push of the bare twin's {tag}"
+        for k in ("density", "pressure"):
+            assert np.array_equal(_bits(got[k][live]), _bits(bare[k][live])), f"{k} against the bare twin's {tag}"
+        self.anchored += 1
+        self.anchor_touched += int(touched.sum())
 
     def probe_refusals(self):
         """every phase call the table says is illegal now returns SPH_E_STATE (and changes nothing: the twin never makes it)"""
@@ -621,14 +839,11 @@ class Walker:
             rc, _ = self._perform(self.c, (ph,))
             assert rc == E_STATE, f"{ph} at stage {self.m.stage} after {self.trace[-3:]}: returned {rc}, the table says refused"
 
-    def rebase(self):
-        """a boundary: the twin becomes a fresh context that holds what the public API shows now"""
+    def _fresh(self, pos, vel, idx, p, obstacle):
+        """a new context that holds what the public API shows of this one: parameters, settings, spheres, particles in slot order
+        -- and, `obstacle`, the obstacle THROUGH ANOTHER DOOR: the clamped field sph_obstacle_read gives goes in by
+        sph_obstacle_set_grid (never by the rasteriser), the ADVANCED offset sph_obstacle_get shows by sph_obstacle_set_motion"""
         capi, c, m = self.capi, self.c, self.m
-        if self.t is not None:
-            self.t.close()
-        pos, vel, idx = c.download_owned()
-        p = capi.Params()
-        capi._check(c.L.sph_get_params(c.h, p))
         t = capi.Context(self.capacity, params=p)
         tm = Mirror(self.capacity)
         for op in (("set_precision", m.precision), ("set_sort_mode", m.sort_mode)) + \
@@ -637,18 +852,39 @@ class Walker:
                   ((("set_block_order",) + m.block_order,) if m.block_order is not None else ()):
             tm.apply(op)
             assert self._perform(t, op)[0] == 0
-        assert c.L.sph_get_precision(c.h) == m.precision
         if m.n_colliders:
             col = c.colliders()
             t.set_colliders(col["centers"], col["radii"], col["velocities"])
             if m.tracked:
                 t.set_collider_bodies(*BODY)
         tm.n_colliders, tm.tracked, tm.params = m.n_colliders, m.tracked, m.params
+        if obstacle:
+            dims, origin, spacing, off, vel3, phi = self.obstacle_state(c)
+            if phi is not None:
+                t.set_obstacle_grid(phi, origin, spacing)
+            t.set_obstacle_motion(offset=off, velocity=vel3)
+            tm.obstacle, tm.motion = m.obstacle, m.motion
         t.upload(pos, vel, idx)
         tm.n, tm.next_index = m.n, m.next_index
         tm._row("sph_upload")
-        self.t, self.tm = t, tm
-        c.sync(); t.sync()
+        return t, tm
+
+    def rebase(self):
+        """a boundary: the twin becomes a fresh context that holds what the public API shows now (and so does the bare twin, but
+        for the obstacle)"""
+        capi, c, m = self.capi, self.c, self.m
+        for old in (self.t, self.b):
+            if old is not None:
+                old.close()
+        self.t = self.b = None
+        pos, vel, idx = c.download_owned()
+        p = self._params()
+        assert c.L.sph_get_precision(c.h) == m.precision
+        self.t, self.tm = self._fresh(pos, vel, idx, p, True)
+        if self.bare:
+            self.b, self.bm = self._fresh(pos, vel, idx, p, False)
+            self.b_fresh = True
+        c.sync(); self.t.sync()
 
     # -- the identities -------------------------------------------------------------------------------------------------------
     def check_set(self):
@@ -678,8 +914,14 @@ class Walker:
         assert np.array_equal(_bits(a[0]), _bits(b[0])), f"positions {tag}"
         assert np.array_equal(_bits(a[1]), _bits(b[1])), f"velocities {tag}"
         assert np.array_equal(_bits(c.positions4()), _bits(t.positions4())), f"positions4 {tag}"
+        self._check_obstacle(tag)
         if m.stage >= HASHED and tm.stage == m.stage:
             assert np.array_equal(c.keys(), t.keys()), f"keys {tag}"
+        if m.stage == HASHED and m.mid_step() and m.params_at_hash == m.params:
+            import small_grids           # the keys of a hash: those of the slots' positions in the box as it is now
+            p = self._params()
+            lo, hi = np.array(list(p.box_min), np.float32), np.array(list(p.box_max), np.float32)
+            assert np.array_equal(c.keys(), small_grids.np_keys(a[0], lo, hi, tuple(p.grid))), f"keys against numpy {tag}"
         if m.stage >= SORTED and tm.stage >= SORTED:
             for x, y, k in zip(c.cells(), t.cells(), ("keys", "starts", "counts")):
                 assert np.array_equal(x, y), f"cell table: {k} {tag}"

@@ -2,7 +2,11 @@
 of context_walk.CALLS plus whole fused and phased steps, each legal or deliberately illegal by the mirror.  At every boundary
 (an integrate or an edit) the twin is rebuilt from what the public API shows; at every completed step the state, order, keys
 and cell table are compared with it bit for bit, and after every call the particle set tracked by creation index on the host
-must be what sph_download_owned, sph_download and sph_download_positions4 report."""
+must be what sph_download_owned, sph_download and sph_download_positions4 report.
+
+Six more seeds also draw the obstacle calls and the views.  There every view is compared with its numpy model, the obstacle the
+library shows with numpy's record of it, and every completed step that has an obstacle is obstacle_model.push applied to the
+output of a bare twin (a context without the obstacle, rebuilt at the same boundaries)."""
 import pytest
 
 import context_walk as cw
@@ -17,11 +21,11 @@ def snapshot(tmp_path_factory):
     return path
 
 
-@pytest.mark.parametrize("seed", cw.FUZZ_SEEDS)
-def test_history(seed, snapshot):
-    ops = cw.fuzz_ops(seed)
+def _history(seed, snapshot, extended):
+    ops = cw.fuzz_ops(seed, extended=extended)
     with cw.Walker(cw.FUZZ_CAPACITY, cw.DT_FLOW, snapshot) as w:
         w.twinning = True
+        w.bare = extended
         done = []
         try:
             for op in ops:
@@ -33,3 +37,15 @@ def test_history(seed, snapshot):
                     w.rebase()                    # a completed step is a boundary
         except AssertionError as e:
             raise AssertionError(f"seed {seed}, call {len(done)} of {ops}: {e}") from e
+        if extended:         # every integrate with an obstacle installed was the first behind a boundary, and was held to the model
+            assert w.anchored == w.m.ob_steps >= 2 and w.anchor_touched > 0, (w.anchored, w.m.ob_steps, w.anchor_touched)
+
+
+@pytest.mark.parametrize("seed", cw.FUZZ_SEEDS)
+def test_history(seed, snapshot):
+    _history(seed, snapshot, False)
+
+
+@pytest.mark.parametrize("seed", cw.FUZZ_SEEDS_OBSTACLE)
+def test_history_with_obstacles_and_views(seed, snapshot):
+    _history(seed, snapshot, True)

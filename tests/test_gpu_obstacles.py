@@ -1,14 +1,19 @@
 """GPU: solid obstacles of any shape (include/sph_hip.h: sph_obstacle_build and the calls next to it) against the numpy model of
 tests/obstacle_model.py, BIT FOR BIT: the rasteriser, the sample rule, the push behind the fused and the phased integrate, the
 brick acceleration on a field that is no distance, the movers' marks, a dam against a pillar, a moving ramp, spheres and an
-obstacle together, a cleared obstacle, the refusals and an installation in the middle of a step."""
+obstacle together, a cleared obstacle, the refusals and an installation in the middle of a step; then, on the inputs of
+tests/obstacle_cases.py, the pass on the sort's bookkeeping (two tiles of the movers' marks, a fluid at rest whose sorts are being
+skipped), rough fields through the brick guard, lattice edges, and the first step beside a tracked body, the mixed-precision
+pass, sph_emit and sph_remove."""
 import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 
+import obstacle_cases as oc
 import obstacle_model as om
+import sort_reference as sr
 from gpufluidsimulator_amd import capi, ic
 
 pytestmark = pytest.mark.gpu
@@ -486,3 +491,385 @@ def test_refusals_change_nothing():
         a.upload(pos, vel); b.upload(pos, vel)
         a.step(DT, 2); b.step(DT, 2)
         _same_state(a.download(), b.download())
+
+
+# ==== the pass on the sort's bookkeeping, on rough fields, on lattice edges and beside other features ============================
+# The inputs are those of tests/obstacle_cases.py: each is chosen so that an edge is reached, and each test asserts that
+# condition from the numpy model BEFORE it looks at what the device computed.
+def _against_model(pos, vel, install, stepper, off=ZERO, u=ZERO, setup=None, before_step=None, probe=None, cap=None):
+    """_check_step for any particle set: A and B from the same upload (and the same `setup` and `before_step` calls), A with the
+    obstacle; A's step is the model applied to B's output.  Returns what the model and the contexts said; `probe(a, b)` runs
+    while both are open and its result comes back under "probe"."""
+    n = pos.shape[0]
+    cap = n if cap is None else cap
+    with _ctx(cap) as a, _ctx(cap) as b:
+        for c in (a, b):
+            if setup:
+                setup(c)
+            c.upload(pos, vel)
+            if before_step:
+                before_step(c)
+        stepper(a, lambda: install(a))
+        stepper(b, lambda: None)
+        sa, sb = a.download(), b.download()
+        ob = a.obstacle(read=True)
+        p4 = a.positions4()
+        out = {"probe": probe(a, b) if probe else None}
+        a.hash()
+        keys = a.keys()
+        slot_pos, _, slot_idx = a.download_owned()
+        m = a.n
+    _same(ob["offset"], om.advance(off, u, DT, 1), "the offset advances once per step")
+    st = {}
+    want_p, want_v, touched = om.push(sb["pos"][:m], sb["vel"][:m], _grid_of(ob), ob["phi"], off, u, BMIN, BMAX, EPS, DAMP, stats=st)
+    out.update(sa=sa, sb=sb, want_p=want_p, want_v=want_v, touched=touched, iterations=st["iterations"], ob=ob, keys=keys,
+               slot_pos=slot_pos, slot_idx=slot_idx, p4=p4, n=m)
+    return out
+
+
+def _assert_model(r):
+    """the assertions of _check_step on what _against_model returned (after the caller's preconditions)"""
+    m, sa, sb = r["n"], r["sa"], r["sb"]
+    _same(sa["pos"][:m], r["want_p"], "pos")
+    _same(sa["vel"][:m], r["want_v"], "vel")
+    _same(sa["density"][:m], sb["density"][:m], "density")
+    _same(sa["pressure"][:m], sb["pressure"][:m], "pressure")
+    assert not np.array_equal(sa["pos"][:m], sb["pos"][:m])
+    _same(r["p4"][:m, :3], r["want_p"], "positions by index")
+    assert (r["p4"][:m, 3] == 1.0).all()
+    _same(r["slot_pos"], r["want_p"][r["slot_idx"]])
+    assert np.array_equal(r["keys"], _keys_of(r["slot_pos"])), int((r["keys"] != _keys_of(r["slot_pos"])).sum())
+
+
+STEPPERS = [pytest.param(_fused, id="fused"), pytest.param(_phased, id="phased")]
+
+
+# ---- A1. two tiles of the movers' marks -----------------------------------------------------------------------------------------
+def test_both_mover_tiles_take_the_pushs_marks():
+    """27000 particles fill two 16384-slot tiles of the movers' counts (the second partial); the ramp takes more than 1000
+    particles of EACH to other cells.  One fused step, then the merge sort: particles, keys, the reported mover count, the order
+    and the cell table against numpy; then 20 more steps against the full sort."""
+    pos, vel = (x.copy() for x in oc.two_tiles())
+    n = pos.shape[0]
+    keys0 = _keys_of(pos)
+    slot = oc.slots_of(keys0)                              # the first sort of the step is the full stable sort of the upload
+    assert n == 27000 and slot.max() // oc.MM_TILE == 1
+
+    def sorted_state(c):
+        st0 = c.sort_stats()
+        c.hash(); c.sort(); c.sync(); c.build_cells()
+        st1 = c.sort_stats()
+        assert np.array_equal(c.keys(), _keys_of(c.download_owned()[0])), "the keys of the slots' positions"
+        return {"keys": c.keys(), "order": c.order(), "cells": c.cells(), "movers": st1["last_movers"],
+                "merges": st1["merges"] - st0["merges"], "skipped": c.sort_skipped()}
+
+    run = {}
+    with _ctx(n) as a, _ctx(n) as z, _ctx(n) as b:
+        for c, mode in ((a, 2), (z, 0), (b, 2)):
+            c.set_sort_mode(mode)
+            if c is not b:
+                _build(c, [RAMP])
+            c.upload(pos, vel)
+            c.step(DT, 1)
+        sa, sb = a.download(), b.download()
+        ob = a.obstacle(read=True)
+        p4 = a.positions4()
+        run["a"], run["z"] = sorted_state(a), sorted_state(z)
+        # the condition, from the model on the twin's output alone
+        want_p, want_v, touched = om.push(sb["pos"], sb["vel"], _grid_of(ob), ob["phi"], ZERO, ZERO, BMIN, BMAX, EPS, DAMP)
+        per_tile = oc.movers_per_tile(sb["pos"], want_p, touched, slot)
+        assert per_tile.shape == (2,) and per_tile.min() >= 1000, per_tile
+        # the particles
+        _same(sa["pos"], want_p, "pos"); _same(sa["vel"], want_v, "vel")
+        _same(sa["density"], sb["density"]); _same(sa["pressure"], sb["pressure"])
+        _same(p4[:, :3], want_p, "positions by index")
+        # the bookkeeping: the keys the pass left, the count the sort found, the order and the table
+        new_keys = _keys_of(want_p)
+        _, order0 = sr.full_sort_expected(keys0, np.arange(n))
+        want_keys, want_order = sr.resort_expected(order0, new_keys)
+        got = run["a"]
+        assert got["merges"] == 1 and not got["skipped"] and run["z"]["merges"] == 0
+        assert got["movers"] == int((new_keys != keys0).sum()), (got["movers"], int((new_keys != keys0).sum()))
+        assert got["movers"] >= int(per_tile.sum())           # (counted from the keys: the push need not be the only source of movers)
+        for which in ("a", "z"):
+            g = run[which]
+            assert np.array_equal(g["keys"], want_keys), (which, int((g["keys"] != want_keys).sum()))
+            assert np.array_equal(g["order"], want_order), which
+            for x, y, what in zip(g["cells"], sr.cells_expected(want_keys), ("keys", "starts", "counts")):
+                assert np.array_equal(x, y), (which, "cell table", what)
+        a.step(DT, 20); z.step(DT, 20)
+        _same_state(a.download(), z.download())
+        _same(a.positions4(), z.positions4())
+        sta, stz = a.sort_stats(), z.sort_stats()
+        assert sta["merges"] == 21 and stz["merges"] == 0, (sta, stz)
+
+
+# ---- A2. from rest, through skipped sorts ---------------------------------------------------------------------------------------
+def _lockstep(c, dt=oc.REST_DT):
+    c.step(dt, 1); c.sync()
+
+
+def _start_from_rest(install):
+    """A (merge mode 1) and B (full sort) with `install`, T (mode 1) without: all three make the same steps in lockstep from the
+    same upload until A's sort has been skipped.  Returns the open contexts and the number of steps."""
+    pos, vel = (x.copy() for x in oc.rest_block())
+    a, b, t = _ctx(), _ctx(), _ctx()
+    try:
+        for c, mode in ((a, 1), (b, 0), (t, 1)):
+            c.set_sort_mode(mode)
+            c.upload(pos, vel)
+        steps = 0
+        while not a.sort_skipped():
+            assert steps < 8, "the lattice at rest never skipped a sort"
+            for c in (a, b, t):
+                _lockstep(c)
+            steps += 1
+        assert a.sort_stats()["skips"] >= 1 and t.sort_skipped()
+        install(a); install(b)
+    except BaseException:
+        for c in (a, b, t):
+            c.close()
+        raise
+    return a, b, t, steps
+
+
+def _same_bookkeeping(a, b, what):
+    _same_state(a.download(), b.download())
+    _same(a.positions4(), b.positions4(), what)
+    assert np.array_equal(a.keys(), b.keys()), (what, "keys")
+    for x, y, k in zip(a.cells(), b.cells(), ("keys", "starts", "counts")):
+        assert np.array_equal(x, y), (what, "cell table", k)
+
+
+def _pushing_step(a, b, t, off, u):
+    """the step in which the obstacle first moves particles, on a context whose sorts are being skipped: the model on T's output,
+    and the movers by numpy.  Returns that count."""
+    slot_before = a.download_owned()
+    skips = a.sort_stats()["skips"]
+    for c in (a, b, t):
+        _lockstep(c)
+    assert a.sort_stats()["skips"] == skips + 1            # this step's own sort still had nothing to do: the slots are where they were
+    sa, st = a.download(), t.download()
+    ob = a.obstacle(read=True)
+    want_p, want_v, touched = om.push(st["pos"], st["vel"], _grid_of(ob), ob["phi"], off, u, BMIN, BMAX, EPS, DAMP)
+    movers = int((_keys_of(want_p[slot_before[2]]) != _keys_of(slot_before[0])).sum())
+    assert 50 <= movers <= N // 8, movers                  # (no more than n / 8: mode 1 still merges)
+    assert int((touched & (_keys_of(want_p) != _keys_of(st["pos"]))).sum()) == movers      # (without the push nothing changes cell)
+    _same(sa["pos"], want_p, "pos"); _same(sa["vel"], want_v, "vel")
+    _same(sa["density"], st["density"]); _same(sa["pressure"], st["pressure"])
+    _same(a.positions4()[:, :3], want_p)
+    _same(ob["offset"], om.advance(off, u, oc.REST_DT, 1))
+    _same_bookkeeping(a, b, "the pushing step")
+    return movers
+
+
+def _after_the_push(a, b, movers):
+    """the sort behind the pushing step is not skipped and finds the count; then A and B stay together"""
+    st0 = a.sort_stats()
+    _lockstep(a); _lockstep(b)
+    st1 = a.sort_stats()
+    assert not a.sort_skipped() and st1["skips"] == st0["skips"] and st1["merges"] == st0["merges"] + 1, (st0, st1)
+    assert st1["last_movers"] == movers, (st1, movers)
+    _same_bookkeeping(a, b, "step 2")
+    for k in range(3, 11):
+        _lockstep(a); _lockstep(b)
+        _same_bookkeeping(a, b, f"step {k}")
+    assert b.sort_stats()["merges"] == 0
+
+
+def test_an_obstacle_starts_to_push_a_fluid_at_rest():
+    a, b, t, _ = _start_from_rest(lambda c: _build(c, [oc.REST_PILLAR]))
+    with a, b, t:
+        movers = _pushing_step(a, b, t, ZERO, ZERO)
+        _after_the_push(a, b, movers)
+
+
+def test_a_paddle_reaches_a_fluid_at_rest():
+    def install(c):
+        _build(c, [oc.PADDLE], S, oc.PADDLE_BOUNDS)
+        c.set_obstacle_motion(velocity=oc.PADDLE_U)
+
+    a, b, t, _ = _start_from_rest(install)
+    with a, b, t:
+        grid = om.lattice(S, *oc.PADDLE_BOUNDS)
+        phi = om.rasterise([oc.PADDLE], grid)
+        off = np.zeros(3, F)
+        for k in range(1, oc.PADDLE_CONTACT):              # on its way: nothing is touched, every sort is skipped
+            skips = a.sort_stats()["skips"]
+            for c in (a, b, t):
+                _lockstep(c)
+            sa, st = a.download(), t.download()
+            assert not om.push(st["pos"], st["vel"], grid, phi, off, oc.PADDLE_U, BMIN, BMAX, EPS, DAMP)[2].any(), k
+            _same_state(sa, st)
+            assert a.sort_skipped() and a.sort_stats()["skips"] == skips + 1, k
+            off = om.advance(off, oc.PADDLE_U, oc.REST_DT, 1)
+            _same(a.obstacle()["offset"], off)
+        movers = _pushing_step(a, b, t, off, oc.PADDLE_U)
+        _after_the_push(a, b, movers)
+
+
+# ---- A3. rough fields through the brick guard -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("stepper", STEPPERS)
+@pytest.mark.parametrize("field", ["amp0.2", "amp3.0", "guard"])
+def test_rough_fields_pass_the_brick_guard_exactly(field, stepper):
+    pos, vel = _dam()
+    grid, phi = oc.rough_field(field, pos)
+    r = _against_model(pos, vel, lambda a: a.set_obstacle_grid(phi, grid["origin"], grid["spacing"]), stepper)
+    _same(r["ob"]["phi"], om.clamp(phi, grid))
+    assert r["touched"].sum() >= 500, r["touched"].sum()
+    if field == "guard":
+        _guard_is_straddled(r["sb"]["pos"], grid, r["ob"]["phi"])
+    else:
+        assert np.bincount(r["iterations"], minlength=5)[1:].min() >= 1, np.bincount(r["iterations"])
+    _assert_model(r)
+
+
+def _guard_is_straddled(pos, grid, phi):
+    """among the bricks that hold particles: minima of eps + 0.25 s + k ulp for every k in -4 .. 4, and some well below"""
+    b, _ = oc.bricks_of(pos, grid)
+    low = oc.brick_minima(phi)
+    mins = np.array([low[z, y, x] for x, y, z in np.unique(b, axis=0)])
+    guard = oc.guard_of(grid)
+    for k in range(-4, 5):
+        assert (mins == oc.ulps(guard, k)).sum() >= 1, k
+    assert (mins < 0).sum() >= 1
+
+
+# ---- A4. lattice edges ------------------------------------------------------------------------------------------------------------
+def _probes_straddle_the_far_faces(grid, phi, off, pos, touched, probes, rest):
+    _, _, inside = om.sample(grid, phi, off, pos)
+    assert 500 < inside.sum() < pos.shape[0] - 500         # the block reaches the last cells and beyond them
+    for k in range(3):
+        rows = np.array([row for axis, row in probes if axis == k])
+        _same(pos[rows], rest[rows])                       # a lone particle at rest: the integrate left it where it was
+        g = (((pos[rows, k] - off[k]) - grid["origin"][k]) / grid["spacing"]).astype(F)
+        assert (np.abs(g - F(grid["dims"][k] - 1)) < 1e-5).all()
+        assert (g >= F(grid["dims"][k] - 1)).sum() >= 1 and (~inside[rows]).sum() >= 1, k       # on the face: outside
+        assert (inside[rows] & touched[rows]).sum() >= 1, k                                      # just below it: inside, pushed
+
+
+@pytest.mark.parametrize("stepper", STEPPERS)
+@pytest.mark.parametrize("lattice", list(oc.EDGE_LATTICES))
+def test_the_push_on_lattice_edges(lattice, stepper):
+    grid, phi, off, pos, vel, probes = oc.edge_lattice(lattice)
+
+    def install(a):
+        a.set_obstacle_grid(phi, grid["origin"], grid["spacing"])
+        a.set_obstacle_motion(offset=off)
+
+    r = _against_model(pos, vel, install, stepper, off=off)
+    assert r["ob"]["dims"] == grid["dims"]
+    _probes_straddle_the_far_faces(grid, r["ob"]["phi"], off, r["sb"]["pos"], r["touched"], probes, pos)
+    _assert_model(r)
+
+
+@pytest.mark.parametrize("lattice", list(oc.EDGE_LATTICES))
+def test_sample_on_lattice_edges(lattice):
+    grid, phi, off, _, _, _ = oc.edge_lattice(lattice)
+    pts = oc.face_points(grid, off)
+    with _ctx(64) as c:
+        c.set_obstacle_grid(phi, grid["origin"], grid["spacing"])
+        c.set_obstacle_motion(offset=off)
+        got_phi, got_n, got_in = c.sample_obstacle(pts)
+    want_phi, want_n, want_in = om.sample(grid, om.clamp(phi, grid), off, pts)
+    for k in range(6):                                     # each face: points on either side of it
+        face = want_in[2000 + 200 * k:2200 + 200 * k]
+        assert 20 <= face.sum() <= 180, (k, face.sum())
+    assert np.array_equal(got_in, want_in), int((got_in != want_in).sum())
+    _same(got_phi, want_phi)
+    _same(got_n, want_n)
+
+
+# ---- A5. beside other features, first step from an upload -------------------------------------------------------------------------
+BODY_SPHERE = ([[-1.75, -1.72, -1.74]], [0.1875], [[300.0, -150.0, 80.0]])
+BODY = ([2.0e4], [[0.0, -9.81 * 11000, 0.0]])
+
+
+@pytest.mark.parametrize("stepper", STEPPERS)
+def test_beside_a_tracked_free_body(stepper):
+    """nothing but the spheres contributes to J: impulses, centres and velocities are the obstacle-free twin's"""
+    def setup(c):
+        c.set_colliders(*BODY_SPHERE)
+        c.set_collider_bodies(*BODY)
+
+    def probe(a, b):
+        return a.collider_impulses(), b.collider_impulses(), a.colliders(), b.colliders()
+
+    pos, vel = _dam()
+    r = _against_model(pos, vel, lambda a: _build(a, [RAMP]), stepper, setup=setup, probe=probe)
+    assert r["touched"].sum() >= 400
+    _assert_model(r)
+    (ja, na), (jb, nb), ca, cb = r["probe"]
+    assert na == nb == 1 and np.abs(jb).max() > 0          # the sphere did take momentum from the fluid
+    assert np.array_equal(ja.view(np.uint64), jb.view(np.uint64)), (ja, jb)
+    for k in ca:
+        _same(ca[k], cb[k], f"collider {k}")
+    assert not np.array_equal(cb["velocities"], np.array(BODY_SPHERE[2], F))      # (a free body: the fluid and gravity moved it)
+
+
+@pytest.mark.parametrize("stepper", STEPPERS)
+def test_beside_the_mixed_precision_pass(stepper):
+    pos, vel = _dam()
+    r = _against_model(pos, vel, lambda a: _build(a, [RAMP]), stepper, setup=lambda c: c.set_precision(True))
+    assert r["touched"].sum() >= 501
+    _assert_model(r)                                       # density and pressure: the twin's bits, from the fp16 pass
+    with _ctx() as plain:
+        plain.upload(pos, vel); plain.step(DT, 1)
+        assert not np.array_equal(plain.download()["density"], r["sb"]["density"])
+
+
+EMIT_N = 200
+
+
+def _emitted_into_the_ramp():
+    rng = np.random.default_rng(29)
+    p = np.stack([rng.uniform(-1.4, -1.0, EMIT_N), rng.uniform(-1.98, -1.9, EMIT_N), rng.uniform(-1.9, -1.6, EMIT_N)], 1).astype(F)
+    return p, rng.uniform(-40.0, 40.0, (EMIT_N, 3)).astype(F)
+
+
+@pytest.mark.parametrize("stepper", STEPPERS)
+def test_particles_emitted_into_the_solid_are_pushed_out(stepper):
+    pos, vel = _dam()
+    ep, ev = _emitted_into_the_ramp()
+    assert om.analytic(RAMP, ep).max() < -0.15
+    r = _against_model(pos, vel, lambda a: _build(a, [RAMP]), stepper, before_step=lambda c: c.emit(ep, ev), cap=N + EMIT_N)
+    assert r["n"] == N + EMIT_N
+    new = np.arange(N, N + EMIT_N)
+    assert r["touched"][new].all() and r["touched"][:N].sum() >= 501
+    _assert_model(r)                                       # (positions4 of the new rows included)
+    after, _, inside = om.sample(_grid_of(r["ob"]), r["ob"]["phi"], ZERO, r["sa"]["pos"][new])
+    assert inside.all() and (after > -1e-4).all(), after.min()
+    assert om.analytic(RAMP, r["sa"]["pos"][new]).min() > -1e-3
+
+
+@pytest.mark.parametrize("mode", [2, 0])
+def test_remove_right_after_the_pushing_step_equals_a_reupload(mode):
+    pos, vel = _dam()
+    region = capi.Region.box((-2.0, -2.0, -2.0), (-1.7, -1.8, 2.0))       # across the ramp's contact line
+    with _ctx() as a, _ctx() as t:
+        a.set_sort_mode(mode)
+        _build(a, [RAMP])
+        a.upload(pos, vel); t.upload(pos, vel)
+        a.step(DT, 1); t.step(DT, 1)
+        st, ob = t.download(), a.obstacle(read=True)
+        touched = om.push(st["pos"], st["vel"], _grid_of(ob), ob["phi"], ZERO, ZERO, BMIN, BMAX, EPS, DAMP)[2]
+        removed = a.remove(region)
+        assert 100 < removed.size < N - 1000
+        assert 50 < touched[removed].sum() < touched.sum() - 50            # pushed particles leave, pushed particles stay
+        survivors = a.download_owned()
+        merges = a.sort_stats()["merges"]
+        a.step(DT, 1)
+        assert a.sort_stats()["merges"] == (merges + 1 if mode == 2 else 0)
+        a.step(DT, 2)
+        got = (a.download_owned(), a.positions4(), a.download(want=("density", "pressure")))
+    with _ctx() as b:
+        _build(b, [RAMP])
+        b.upload(*survivors)
+        b.step(DT, 3)
+        want = (b.download_owned(), b.positions4(), b.download(want=("density", "pressure")))
+    assert np.array_equal(got[0][2], want[0][2]), "slot order"
+    _same(got[0][0], want[0][0], "pos"); _same(got[0][1], want[0][1], "vel")
+    _same(got[1], want[1], "positions4")
+    live = np.sort(got[0][2])
+    for k in ("density", "pressure"):
+        _same(got[2][k][live], want[2][k][live], k)
