@@ -161,6 +161,10 @@ static int create_impl(sph_ctx** out, int device, uint32_t capacity, const sph_p
         unsigned long v = 0;
         if (sscanf(env, "%lu", &v) == 1) c->pair_small_slots = v > 0xFFFFFFFFul ? 0xFFFFFFFFu : (uint32_t)v;
     }
+    if (const char* env = getenv("SPH_PAIR_CLAMP")) {           // at create time: "0" keeps the v_max_f32 form of the pair loops (A/B runs)
+        int v = 1;
+        if (sscanf(env, "%d", &v) == 1) c->pair_clamp = v != 0;
+    }
     if (rc) { m.free_all(); delete c; return rc; }
     *out = c;
     return SPH_OK;

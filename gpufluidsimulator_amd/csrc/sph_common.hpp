@@ -300,6 +300,9 @@ struct sph_ctx {
     // pair kernels: a context with fewer owned particles than this launches blocks of 128 threads instead of 256 (sph_pairs.hip:
     // SMALL_THREADS_PAIR; same results bit for bit; sph_set_pair_small_launch)
     uint32_t pair_small_slots = SPH_PAIR_SMALL_SLOTS_DEFAULT;
+    // pair kernels: the r < h cut of the hot launches as the fma's clamp modifier while h <= 1 (sph_pairs.hip: pair_clamp; same
+    // results bit for bit); false (SPH_PAIR_CLAMP=0 at create time) keeps the v_max_f32 form at every h
+    bool pair_clamp = true;
     // block order of the pair kernels (sph_device.hpp: BlockOrder; sph_set_block_order): every XCD walks a contiguous eighth
     // of the slots; the fused force pass also walks strips of 2^order_strip_sh blocks through the z layers of that eighth
     bool order_xcd = true, order_ztile = true;

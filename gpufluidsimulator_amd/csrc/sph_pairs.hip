@@ -40,6 +40,10 @@ constexpr int DENS_THREADS = SPH_DENS_THREADS;
 // launches of a 2.1 M-particle slab lose ~1 % of its step.  Measured: profiles/r06_pair_block_size.txt.
 constexpr int SMALL_THREADS_PAIR = 128;
 static inline bool small_blocks(const sph_ctx* c) { return c->n < c->pair_small_slots; }
+// Which form of the r < h cut the hot pair launches take (cut_below_zero): the fma's clamp modifier caps at 1, so it stands in
+// for max(., 0) only while h - r <= h <= 1 and h^2 - r^2 <= h^2 <= 1 -- decided per launch from the derived Phys, same bits
+// either way.  A larger h, or SPH_PAIR_CLAMP=0 at create time (A/B runs), takes the v_max_f32 instantiations.
+static inline bool pair_clamp(const sph_ctx* c) { return c->pair_clamp && c->phys.h <= 1.f && c->phys.h2 <= 1.f; }
 constexpr int PIECE = 128;          // staged candidates per piece (2 coalesced loads per lane)
 
 // The candidate walks read LDS through volatile LDS-address-space pointers: each read then stays ONE
@@ -288,6 +292,16 @@ __device__ __forceinline__ float in_vgpr(float x) {
 
 __device__ __forceinline__ float inv_sqrt(float x) { return __builtin_amdgcn_rsqf(x); }   // v_rsq_f32, 1 ulp
 
+// max(x, 0) of a value with a known upper bound (the r < h cut of the pair loops: h - r <= h, h^2 - r^2 <= h^2).
+// CLAMP: median(x, 0, 1), which hipcc folds into the `clamp` output modifier of the v_fma_f32 that produced x -- the
+// v_max_f32 goes.  Same bits as fmaxf(x, 0) for every x <= 1 (a NaN gives 0 either way), so the host picks the CLAMP
+// instantiation only while that bound is <= 1 (pair_clamp) and a larger h keeps the v_max form.
+template <bool CLAMP>
+__device__ __forceinline__ float cut_below_zero(float x) {
+    if constexpr (CLAMP) return __builtin_amdgcn_fmed3f(x, 0.f, 1.f);
+    else return fmaxf(x, 0.f);
+}
+
 __device__ __forceinline__ void wave_lds_sync() {
     // one wave's LDS operations are processed in issue order; only the compiler must not move them
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -436,7 +450,8 @@ __device__ __forceinline__ bool wave_targets(const Targets& T, uint32_t wave, ui
 // ---- density + pressure (kernelComputeDensities, particleSystem.cu:132-187) ---------------------------
 // rho_i = sum_{j in 27 cells, r2 < h2} m * POLY6 * (h2 - r2)^3   (self included)   (.cu:28-37)
 // p_i   = max(0, k * (rho_i - rho0))                                              (.cu:15-17)
-template <int THREADS>
+// CLAMP: the r < h cut as the fma's clamp modifier (cut_below_zero); the host launches it only while h^2 <= 1
+template <int THREADS, bool CLAMP>
 __global__ __launch_bounds__(THREADS, SPH_DENS_OCC) void k_density(const float4* __restrict__ posi,
                                                                    const uint32_t* __restrict__ keyS,
                                                                    const uint2* __restrict__ cells,
@@ -486,7 +501,7 @@ __global__ __launch_bounds__(THREADS, SPH_DENS_OCC) void k_density(const float4*
     auto pair_math = [&](float x, float y, float z, bool valid) {
         const float dx = pi.x - x, dy = pi.y - y, dz = pi.z - z;
         // h^2 - r^2 in three fmas (the subtraction rides along); max(., 0) is the r < h test
-        float d = fmaxf(fmaf(-dz, dz, fmaf(-dy, dy, fmaf(-dx, dx, h2_v))), 0.f);
+        float d = cut_below_zero<CLAMP>(fmaf(-dz, dz, fmaf(-dy, dy, fmaf(-dx, dx, h2_v))));
         d = valid ? d : 0.f;
         acc = fmaf(d * d, d, acc);
     };
@@ -551,7 +566,9 @@ __global__ __launch_bounds__(THREADS, SPH_DENS_OCC) void k_density(const float4*
             };
             uint32_t t = 0;
             for (; t < tmin; t += UNROLL) group(t, false);
-            for (; __ballot(t < len) != 0ull; t += UNROLL) group(t, true);    // until every lane is through its range
+            // until every lane is through its range.  (A final HALF group for a remainder <= 2 was tried: 3 LDS reads fewer per
+            // wave, but 22 VALU and 21 SALU more -- every row pays the second test; profiles/pair_clamp_drain_ab.txt.)
+            for (; __ballot(t < len) != 0ull; t += UNROLL) group(t, true);
         });
     finish();
 }
@@ -994,7 +1011,8 @@ extern "C" void sph_debug_pair_stats(unsigned long long* out, int on) {     // r
 #endif
 // Sph: empty, or Spheres for the collider instantiation of the fused pass (one more argument: the sphere table, by value), or
 // SpheresTracked for a tracked context's (the table by pointer and the impulse outputs)
-template <bool FORCE, bool COLL, bool INTEG, int THREADS, class... Sph>
+// CLAMP: the r < h cut as the fma's clamp modifier (cut_below_zero); the host launches it only while h <= 1
+template <bool FORCE, bool COLL, bool INTEG, int THREADS, bool CLAMP, class... Sph>
 __global__ __launch_bounds__(THREADS, SPH_FORCE_OCC) void k_force(
     const float4* __restrict__ posi, const float4* __restrict__ velr, const float2* __restrict__ dp,
     const float2* __restrict__ cw, const uint32_t* __restrict__ keyS, const uint2* __restrict__ cells, float4* __restrict__ fpress,
@@ -1076,9 +1094,9 @@ __global__ __launch_bounds__(THREADS, SPH_FORCE_OCC) void k_force(
         r2 = valid ? r2 : 1e30f;
         if (FORCE) {
             const float rinv = inv_sqrt(r2);
-            // both kernels vanish continuously at r = h, so "r < h" is max(h - r, 0): one v_max instead
-            // of a compare and two selects
-            const float hr = fmaxf(fmaf(-r2, rinv, h_v), 0.f);
+            // both kernels vanish continuously at r = h, so "r < h" is max(h - r, 0): one v_max (or the fma's
+            // clamp) instead of a compare and two selects
+            const float hr = cut_below_zero<CLAMP>(fmaf(-r2, rinv, h_v));
             const float w = wj * hr;                                // VISC m VISC_LAP (h-r) / rho_j
             const float s = (cpi + cpj) * w * (hr * rinv);          // m (p_i+p_j)/(2 rho_j) 45/(pi h^6) (h-r)^2 / r
             fpx += s * dx; fpy += s * dy; fpz += s * dz;
@@ -1249,17 +1267,23 @@ __global__ __launch_bounds__(THREADS, SPH_FORCE_OCC) void k_force(
 #endif
                 if (COLL) {
                     // bit (done-1-k) of `near` belongs to the k-th candidate of this chunk; highest bit first
-                    // keeps the candidate order of the sums
-                    while (__ballot(near != 0u) != 0ull) {
-                        PAIR_STAT(4, 1);
-                        if (near != 0u) {
-                            const uint32_t hb = 31u - (uint32_t)__clz((int)near);
-                            near &= ~(1u << hb);
-                            const uint32_t ci = idx0 + (done - 1u - hb);
-                            const float2* e = &s_e[(ci << 2) + ci];          // ci * 5 without v_mul_lo_u32
-                            const float2 qa = e[0], qb = e[1], qc = e[2];
-                            collide_math(qa.x, qa.y, qb.x, qb.y, qc.x, qc.y);
-                        }
+                    // keeps the candidate order of the sums.  A plain divergent loop: every lane leaves when ITS bits are
+                    // gone and the wave goes round while any lane is in.  (Written as a wave-uniform `while (ballot)`
+                    // around `if (near)`, the accumulators became PHIs of the inner branch: four v_mov_b32 at the head of
+                    // every round, four inside it and four at each exit of the chunk.)
+#ifdef SPH_PAIR_STATS
+                    {   // the wave's rounds = the bits of its busiest lane (all lanes: the macro's body runs in lane 0 only)
+                        const uint32_t rounds = wave_max_u32((uint32_t)__popc(near));
+                        PAIR_STAT(4, rounds);
+                    }
+#endif
+                    while (near != 0u) {
+                        const uint32_t hb = 31u - (uint32_t)__clz((int)near);
+                        near &= ~(1u << hb);
+                        const uint32_t ci = idx0 + (done - 1u - hb);
+                        const float2* e = &s_e[(ci << 2) + ci];          // ci * 5 without v_mul_lo_u32
+                        const float2 qa = e[0], qb = e[1], qc = e[2];
+                        collide_math(qa.x, qa.y, qb.x, qb.y, qc.x, qc.y);
                     }
                 }
             }
@@ -1318,14 +1342,22 @@ static Spheres sphere_table(const sph_ctx* c) {
 
 // one launch of k_force over `threads` slots; sp: empty, or the sphere table (the collider instantiation).  `early`: the slab
 // step's launch in front of the settling (launch_force_dev_range) -- the next keys go to keyS2 by ABSOLUTE slot
+// The clamp form of the r < h cut (pair_clamp) exists for the hot instantiation alone, the fused pass without colliders: the two
+// forms give the same bits, so the phase API's and the colliders' launches match it as they are.
 template <bool F, bool C, bool I, class... Sph>
 static void force_kernel(sph_ctx* c, bool small, const Targets& tg, uint32_t threads, float dt, bool mark, bool early, Sph... sp) {
-#define SPH_LAUNCH_FORCE_T(T)                                                                                                   \
-    hipLaunchKernelGGL((k_force<F, C, I, T, Sph...>), dim3(ceil_div(threads, (uint32_t)T)), dim3(T), 0, c->stream, c->posi,       \
+#define SPH_LAUNCH_FORCE_T(T, CL)                                                                                               \
+    hipLaunchKernelGGL((k_force<F, C, I, T, CL, Sph...>), dim3(ceil_div(threads, (uint32_t)T)), dim3(T), 0, c->stream, c->posi,   \
                        c->velr, c->dp, c->cw, c->keyS, c->table.cells, c->fpress, c->fvisc, c->dvel, c->posi2, c->velr2,                \
                        c->slab ? nullptr : c->pos_out, early ? c->keyS2 : c->k0, mark ? c->mm_mask : nullptr, c->mm_tile_cnt, tg,       \
                        early ? 0u : c->own_off, dt, c->grid, c->phys, sp...)
-    if (small) SPH_LAUNCH_FORCE_T(SMALL_THREADS_PAIR); else SPH_LAUNCH_FORCE_T(PAIR_THREADS);
+    if constexpr (F && C && I && sizeof...(Sph) == 0) {
+        if (pair_clamp(c)) {
+            if (small) SPH_LAUNCH_FORCE_T(SMALL_THREADS_PAIR, true); else SPH_LAUNCH_FORCE_T(PAIR_THREADS, true);
+            return;
+        }
+    }
+    if (small) SPH_LAUNCH_FORCE_T(SMALL_THREADS_PAIR, false); else SPH_LAUNCH_FORCE_T(PAIR_THREADS, false);
 #undef SPH_LAUNCH_FORCE_T
 }
 
@@ -1542,12 +1574,17 @@ static int launch_density_targets(sph_ctx* c, const Targets& tg, uint32_t thread
     if (c->precision == SPH_PRECISION_MIXED_F16)
         hipLaunchKernelGGL(k_density_h, dim3(ceil_div(threads, PAIR_THREADS)), dim3(PAIR_THREADS), 0, c->stream, c->posi,
                            c->keyS, c->table.cells, c->dp, c->cw, tg, c->grid, c->phys);
-    else if (small_blocks(c))
-        hipLaunchKernelGGL(k_density<SMALL_THREADS_PAIR>, dim3(ceil_div(threads, (uint32_t)SMALL_THREADS_PAIR)), dim3(SMALL_THREADS_PAIR), 0, c->stream,
-                           c->posi, c->keyS, c->table.cells, c->dp, c->cw, tg, c->grid, c->phys);
-    else
-        hipLaunchKernelGGL(k_density<DENS_THREADS>, dim3(ceil_div(threads, (uint32_t)DENS_THREADS)), dim3(DENS_THREADS), 0, c->stream, c->posi,
-                           c->keyS, c->table.cells, c->dp, c->cw, tg, c->grid, c->phys);
+    else {
+#define SPH_LAUNCH_DENSITY_T(T, CL)                                                                                             \
+    hipLaunchKernelGGL((k_density<T, CL>), dim3(ceil_div(threads, (uint32_t)T)), dim3(T), 0, c->stream, c->posi, c->keyS,        \
+                       c->table.cells, c->dp, c->cw, tg, c->grid, c->phys)
+        if (pair_clamp(c)) {
+            if (small_blocks(c)) SPH_LAUNCH_DENSITY_T(SMALL_THREADS_PAIR, true); else SPH_LAUNCH_DENSITY_T(DENS_THREADS, true);
+        } else {
+            if (small_blocks(c)) SPH_LAUNCH_DENSITY_T(SMALL_THREADS_PAIR, false); else SPH_LAUNCH_DENSITY_T(DENS_THREADS, false);
+        }
+#undef SPH_LAUNCH_DENSITY_T
+    }
     SPH_HIP(hipGetLastError());
     return SPH_OK;
 }
