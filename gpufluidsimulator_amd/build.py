@@ -11,7 +11,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsph_hip.so")
 HIP_SOURCES = ["sph_capi.hip", "sph_sort.hip", "sph_pairs.hip", "sph_halo.hip", "sph_slab.hip", "sph_compat.hip", "sph_edit.hip",
-               "sph_render.hip", "sph_mesh.hip", "sph_obstacle.hip"]
+               "sph_render.hip", "sph_mesh.hip", "sph_obstacle.hip", "sph_obstacle_mesh.hip"]
 CXX_SOURCES = ["particleSystem.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fno-slp-vectorize: hipcc's SLP pass packs neighbouring fp32 adds/multiplies into v_pk_*_f32, which on

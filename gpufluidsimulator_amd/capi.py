@@ -118,6 +118,15 @@ class ObstacleGrid(C.Structure):
     _fields_ = [("dims", C.c_uint32 * 3), ("origin", C.c_float * 3), ("spacing", C.c_float)]
 
 
+OBSTACLE_MESH_MAX_BAND = 16        # SPH_OBSTACLE_MESH_MAX_BAND
+OBSTACLE_MESH_DEFAULT_BAND = 3     # SPH_OBSTACLE_MESH_DEFAULT_BAND
+
+
+class ObstacleMeshParams(C.Structure):
+    """`sph_obstacle_mesh_params` of include/sph_hip.h (sph_obstacle_build_mesh); 0 in a field = its default."""
+    _fields_ = [("spacing", C.c_float), ("band", C.c_uint32), ("invert", C.c_int32)]
+
+
 RENDER_MAX_RADIUS_PX = 64   # SPH_RENDER_MAX_RADIUS_PX
 RENDER_MAX_SIZE = 4096      # SPH_RENDER_MAX_SIZE
 COLOR_MODES = {"index": 0, "speed": 1, "density": 2}      # SPH_COLOR_*
@@ -210,6 +219,12 @@ SIGNATURES = {
     "sph_obstacle_get": (C.c_int, [_P, C.POINTER(ObstacleGrid), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "sph_obstacle_read": (C.c_int, [_P, _P]),
     "sph_obstacle_sample": (C.c_int, [_P, _U32, _P, _P, _P, _P]),
+    "sph_obstacle_build_mesh": (C.c_int, [_P, C.POINTER(ObstacleMeshParams), C.POINTER(C.c_float), C.POINTER(C.c_float), _U32, _P,
+                                          _U32, _P]),
+    "sph_obstacle_build_mesh_dev": (C.c_int, [_P, C.POINTER(ObstacleMeshParams), C.POINTER(C.c_float), C.POINTER(C.c_float), _U32,
+                                              _P, _U32, _P]),
+    "sph_obstacle_build_obj": (C.c_int, [_P, C.POINTER(ObstacleMeshParams), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_char_p]),
+    "sph_obstacle_mesh_stats": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "sph_mesh_defaults": (None, [C.POINTER(MeshParams)]),
     "sph_mesh_lattice": (C.c_int, [_P, C.POINTER(MeshParams), C.POINTER(_U32), C.POINTER(C.c_float)]),
     "sph_mesh_extract": (C.c_int, [_P, C.POINTER(MeshParams), C.POINTER(_U32), C.POINTER(_U32)]),
@@ -653,6 +668,35 @@ class Context:
         phi, nrm, inside = np.empty(n, np.float32), np.empty((n, 3), np.float32), np.empty(n, np.uint8)
         _check(self.L.sph_obstacle_sample(self.h, n, pts.ctypes.data, phi.ctypes.data, nrm.ctypes.data, inside.ctypes.data))
         return phi, nrm, inside.astype(bool)
+
+    # -- obstacles from a triangle mesh (include/sph_hip.h: sph_obstacle_build_mesh and the calls next to it) -----------------------
+    def build_obstacle_mesh(self, vertices, triangles, spacing=0.0, band=0, invert=False, bounds=None):
+        """Voxelise the closed triangle mesh (vertices (nv, 3) float32, triangles (nt, 3) uint32) on the device into a truncated
+        signed distance, `band` nodes wide (0 = 3), and install it as the context's obstacle.  Synchronises."""
+        v, t = _f32(vertices, 3), np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
+        p = ObstacleMeshParams(float(spacing), int(band), int(bool(invert)))
+        lo, hi = self._bounds(bounds)
+        _check(self.L.sph_obstacle_build_mesh(self.h, C.byref(p), lo, hi, v.shape[0], v.ctypes.data, t.shape[0], t.ctypes.data))
+
+    def build_obstacle_from_mesh(self, spacing=0.0, band=0, invert=False, bounds=None):
+        """The same from the context's own last extract_mesh, through its device pointers: no host trip, no host wait."""
+        pos, _, tri, nv, nt = self.mesh_dev()
+        p = ObstacleMeshParams(float(spacing), int(band), int(bool(invert)))
+        lo, hi = self._bounds(bounds)
+        _check(self.L.sph_obstacle_build_mesh_dev(self.h, C.byref(p), lo, hi, nv, pos, nt, tri))
+
+    def build_obstacle_obj(self, path, spacing=0.0, band=0, invert=False, bounds=None):
+        """The same from a Wavefront OBJ file (`v` and `f` lines; polygons are fanned).  Synchronises."""
+        p = ObstacleMeshParams(float(spacing), int(band), int(bool(invert)))
+        lo, hi = self._bounds(bounds)
+        _check(self.L.sph_obstacle_build_obj(self.h, C.byref(p), lo, hi, os.fsencode(path)))
+
+    def obstacle_mesh_stats(self):
+        """(triangles used, triangles skipped, lost crossings, odd columns) of the mesh-built obstacle: a closed mesh has no odd
+        column and no lost crossing.  Synchronises."""
+        out = (C.c_uint64 * 4)()
+        _check(self.L.sph_obstacle_mesh_stats(self.h, out))
+        return tuple(int(v) for v in out)
 
     # -- emitters and drains (whole-domain contexts; include/sph_hip.h: sph_emit, sph_remove, sph_count_in_regions) ------------
     @staticmethod

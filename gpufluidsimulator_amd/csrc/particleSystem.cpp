@@ -507,6 +507,19 @@ void ParticleSystem::setObstacleMotion(const float* offset, const float* velocit
 
 void ParticleSystem::clearObstacles() { SPH_CHECK(sph_obstacle_clear(m_ctx)); }
 
+void ParticleSystem::setObstacleMesh(const float* pos, uint nv, const uint* tri, uint nt, float spacing, uint band, bool invert,
+                                     const float* lo, const float* hi) {
+    const sph_obstacle_mesh_params p = {spacing, band, invert ? 1 : 0};
+    SPH_CHECK(sph_obstacle_build_mesh(m_ctx, &p, lo, hi, nv, pos, nt, tri));
+}
+
+void ParticleSystem::setObstacleMeshOBJ(const char* path, float spacing, uint band, bool invert, const float* lo, const float* hi) {
+    const sph_obstacle_mesh_params p = {spacing, band, invert ? 1 : 0};
+    SPH_CHECK(sph_obstacle_build_obj(m_ctx, &p, lo, hi, path));
+}
+
+void ParticleSystem::getObstacleMeshStats(uint64_t out[4]) { SPH_CHECK(sph_obstacle_mesh_stats(m_ctx, out)); }
+
 void ParticleSystem::saveState(const std::string& path) { SPH_CHECK(sph_snapshot_save(m_ctx, path.c_str())); }
 
 void ParticleSystem::loadState(const std::string& path) {

@@ -258,6 +258,11 @@ struct sph_ctx {
     float* ob_phi = nullptr;
     float* ob_brick = nullptr;
     float ob_off[3] = {0.f, 0.f, 0.f}, ob_vel[3] = {0.f, 0.f, 0.f};
+    // an obstacle voxelised from a triangle mesh (sph_obstacle_mesh.hip) keeps the scratch of its build -- the work list with the
+    // four counters in front, and the parity marks of the columns -- until the next installation, sph_obstacle_clear or
+    // sph_destroy; both null for every other obstacle, and sph_obstacle_mesh_stats reads the counters
+    uint64_t* ob_mesh_work = nullptr;
+    uint32_t* ob_mesh_marks = nullptr;
 
     // the image of the last sph_render (sph_render.hip): per pixel a 64-bit key (depth bits << 32 | slot) and the resolved
     // RGBA8, creation index and depth.  Allocated at the first render, again when the image size changes; never by a caller
@@ -448,6 +453,14 @@ int launch_integrate(sph_ctx* c, float dt);
 inline bool have_obstacle(const sph_ctx* c) { return c->ob_phi != nullptr; }
 int launch_obstacle_push(sph_ctx* c, bool fused, bool mark);
 void advance_obstacle(sph_ctx* c, float dt);
+// the installation helpers of sph_obstacle.hip, for the mesh voxeliser (sph_obstacle_mesh.hip): the context check, the lattice
+// of a build (checks only), the clamp distance D, the exchange of the context's grid (on failure: no obstacle) and the bricks
+int obstacle_ctx(const sph_ctx* c, const char* who);
+int lattice_resolve(const sph_ctx* c, float spacing, const float* lo, const float* hi, sph_obstacle_grid* G);
+float ob_clamp_distance(const sph_obstacle_grid& G);
+int install_begin(sph_ctx* c, const sph_obstacle_grid& G);
+int install_finish(sph_ctx* c);
+void release_obstacle(sph_ctx* c);
 // tracked contexts (sph_pairs.hip): write the host's sphere set into trk_table and zero J and the step count; refresh R + eps
 int launch_spheres_install(sph_ctx* c);
 int launch_spheres_radii(sph_ctx* c);

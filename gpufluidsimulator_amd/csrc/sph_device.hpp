@@ -92,6 +92,32 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 
+// Exclusive scan of one value per lane over a workgroup of WAVES x 64 lanes, in lane order; `total`: the workgroup's sum.
+// lds: WAVES entries, free again on return.  (The mesh extraction's scans, sph_mesh.hip, and the voxeliser's work list,
+// sph_obstacle_mesh.hip.)
+template <uint32_t WAVES, class T = uint32_t>
+__device__ __forceinline__ T block_scan_excl(T v, T* lds, T& total) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    T x = v;
+#pragma unroll
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const T y = __shfl_up(x, d, 64);
+        if (lane >= d) x += y;
+    }
+    if (lane == 63u) lds[wave] = x;
+    __syncthreads();
+    T base = 0, tot = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < WAVES; q++) {
+        const T t = lds[q];
+        if (q < wave) base += t;
+        tot += t;
+    }
+    __syncthreads();
+    total = tot;
+    return base + x - v;
+}
+
 // ---- cell table: {start, end} per occupied cell from boundary flags on the sorted keys (k_cells_build, sph_pairs.hip; the slab
 //      step's bounds kernel runs the same build in its spare blocks, sph_slab.hip) ------------------------------------------------
 // Thread t of the build takes CELLS_SPT = 4 consecutive slots from lo + 4 t: six key reads for four slots instead of twelve, a

@@ -4,6 +4,7 @@
 //   sph_headless -benchmark -n=262144 -box=8 -i=100 [-device=0] [-grid=128] [-ic=grid|random] [-steps=1] [-dump=8]
 //                [-log=benchmark.txt [-logstyle=oscar|frames]] [-file=<snapshot>] [-collider=x,y,z,r[,ux,uy,uz]] [-collidermass=M[,ax,ay,az]]
 //                [-obstacle=<shape> ... [-obstaclecell=s] [-obstaclevel=ux,uy,uz]]
+//                [-obstaclemesh=FILE.obj [-obstacleband=N] [-obstacleinvert] [-obstaclecell=s] [-obstaclevel=ux,uy,uz]]
 // -obstacle: solid shapes the fluid collides with (ParticleSystem::setObstacles, sph_obstacle_build); see parse_obstacle below
 // -collider: the reference's collider sphere (centre, radius, and a velocity: default at rest), made to push the fluid
 // (ParticleSystem::enableCollider; one sphere, as the reference's UI has).
@@ -448,7 +449,8 @@ int main(int argc, char** argv) {
                "[-ic=grid|random] [-steps=<per update>] [-gpus=<N> [-onegpu] [-slab] [-lattice=nx,ny,nz] [-protocol=1|3]] "
                "[-dump=<count>] [-log=<file> [-logfreq=<ms>] [-logstyle=oscar|frames]] [-sphere=<update>[,<radius>]] "
                "[-collider=<x>,<y>,<z>,<radius>[,<ux>,<uy>,<uz>]] [-collidermass=<M>[,<ax>,<ay>,<az>]] "
-               "[-obstacle=<shape> ... [-obstaclecell=<s>] [-obstaclevel=<ux>,<uy>,<uz>]] [-emit=<x>,<y>,<z>,<r>,<vx>,<vy>,<vz>,<every>] "
+               "[-obstacle=<shape> ... [-obstaclecell=<s>] [-obstaclevel=<ux>,<uy>,<uz>]] "
+               "[-obstaclemesh=<file.obj> [-obstacleband=<N>] [-obstacleinvert] [-obstaclecell=<s>] [-obstaclevel=<ux>,<uy>,<uz>]] [-emit=<x>,<y>,<z>,<r>,<vx>,<vy>,<vz>,<every>] "
                "[-drain=<x0>,<y0>,<z0>,<x1>,<y1>,<z1>[,<every>]] [-add=<update>,<count>] [-capacity=<particles>] [-out=<file>] [-save=<file>] [-load=<file>] [-file=<file>] "
                "[-frames=<dir> [-frameevery=<K>] [-framesize=<W>x<H>] [-camera=<ex>,<ey>,<ez>,<tx>,<ty>,<tz>[,<fovy>]] [-color=index|speed:<lo>:<hi>|density:<lo>:<hi>] "
                "[-surface[=<r>,<K>[,<tau>]] [-tint=<r>,<g>,<b>] [-absorb=<r>,<g>,<b>]]] "
@@ -461,6 +463,10 @@ int main(int argc, char** argv) {
                "| [!]plane:px,py,pz,nx,ny,nz (solid behind the normal); repeatable, the union is rasterised on the device as one grid of signed "
                "distances over the box, `!` inverts a shape; -obstaclecell the grid spacing (default: the particle diameter), -obstaclevel a "
                "uniform velocity of the whole grid; one device only\n"
+               "  -obstaclemesh: a closed triangle mesh (Wavefront OBJ: v and f lines) as the solid, voxelised on the device into signed "
+               "distances -obstacleband nodes wide (1..16, default 3); -obstacleinvert: the fluid is inside the mesh; honours -obstaclecell "
+               "and -obstaclevel; prints triangles used and skipped, lost crossings and odd columns (a closed mesh: 0 and 0); not together "
+               "with -obstacle; one device only\n"
                "  -emit: every <every> updates append a lattice ball of radius <r> spacings at (x, y, z) moving at (vx, vy, vz), if its place is clear\n"
                "  -drain: every <every> updates (default 1) remove the particles inside the box [x0,x1) x [y0,y1) x [z0,z1); one device only\n"
                "  -frames: render the particles on the device after the updates 0, K, 2K, ... (-frameevery=K, default 1) and write "
@@ -509,7 +515,32 @@ int main(int argc, char** argv) {
         fprintf(stderr, "-obstaclevel=%s: expected ux,uy,uz\n", obstacleVelArg);
         return EXIT_FAILURE;
     }
-    if (obstacles.empty() && (obstacleVelArg || value(argc, argv, "obstaclecell"))) {
+    // -obstaclemesh=FILE.obj, -obstacleband=N, -obstacleinvert
+    const char* obstacleMesh = value(argc, argv, "obstaclemesh");
+    uint obstacleBand = 0;
+    if (const char* v = value(argc, argv, "obstacleband")) {
+        char* end = nullptr;
+        const long b = strtol(v, &end, 10);
+        if (end == v || *end || b < 1 || b > SPH_OBSTACLE_MESH_MAX_BAND) {
+            fprintf(stderr, "-obstacleband=%s: expected 1..%d\n", v, SPH_OBSTACLE_MESH_MAX_BAND);
+            return EXIT_FAILURE;
+        }
+        obstacleBand = (uint)b;
+    }
+    const bool obstacleInvert = flag(argc, argv, "obstacleinvert");
+    if (obstacleMesh && !obstacles.empty()) {
+        fprintf(stderr, "-obstaclemesh and -obstacle exclude each other: a context holds one grid (no union of a mesh with shapes)\n");
+        return EXIT_FAILURE;
+    }
+    if (obstacleMesh && !*obstacleMesh) {
+        fprintf(stderr, "-obstaclemesh=: expected a Wavefront OBJ file\n");
+        return EXIT_FAILURE;
+    }
+    if (!obstacleMesh && (obstacleBand || obstacleInvert)) {
+        fprintf(stderr, "-obstacleband / -obstacleinvert go with an -obstaclemesh\n");
+        return EXIT_FAILURE;
+    }
+    if (obstacles.empty() && !obstacleMesh && (obstacleVelArg || value(argc, argv, "obstaclecell"))) {
         fprintf(stderr, "-obstaclecell / -obstaclevel go with an -obstacle\n");
         return EXIT_FAILURE;
     }
@@ -678,6 +709,11 @@ int main(int argc, char** argv) {
                             "makes several force launches per step); run it on one device\n", gpus, gpus == 1 ? " -slab" : "");
             return EXIT_FAILURE;
         }
+        if (obstacleMesh) {
+            fprintf(stderr, "-obstaclemesh is not supported with -gpus=%d%s: sph_obstacle_build_obj works on a whole-domain context; run it "
+                            "on one device\n", gpus, gpus == 1 ? " -slab" : "");
+            return EXIT_FAILURE;
+        }
         if (ic != ParticleSystem::CONFIG_GRID || load || value(argc, argv, "sphere") || value(argc, argv, "save") || value(argc, argv, "log") || dump) {
             fprintf(stderr, "-gpus=%d runs the dam-break lattice (-ic=grid) and takes -n -box -grid -i -steps -lattice -out -device -onegpu -nowarmup\n", gpus);
             return EXIT_FAILURE;
@@ -735,6 +771,14 @@ int main(int argc, char** argv) {
     if (!obstacles.empty()) {
         psystem->setObstacles(obstacles.data(), (uint)obstacles.size(), obstacleCell);
         if (obstacleVelArg) psystem->setObstacleMotion(nullptr, obstacleVel);
+    }
+    if (obstacleMesh) {
+        psystem->setObstacleMeshOBJ(obstacleMesh, obstacleCell, obstacleBand, obstacleInvert);
+        if (obstacleVelArg) psystem->setObstacleMotion(nullptr, obstacleVel);
+        uint64_t ms[4];
+        psystem->getObstacleMeshStats(ms);
+        printf("obstacle mesh: %llu triangles used, %llu skipped, %llu lost crossings, %llu odd columns\n", (unsigned long long)ms[0],
+               (unsigned long long)ms[1], (unsigned long long)ms[2], (unsigned long long)ms[3]);
     }
     if (const char* v = value(argc, argv, "log")) {
         const char* fq = value(argc, argv, "logfreq");

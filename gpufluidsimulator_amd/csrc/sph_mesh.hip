@@ -19,7 +19,7 @@
 //
 // The 6 x 16 case table (which edges, in which order) is built on the host from the midpoint geometry (build_case_table), not
 // typed in; tests/mesh_model.py derives its own.  Everything of the rule is fp32 with each operation rounded (fp contract off).
-#include "sph_common.hpp"
+#include "sph_device.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -249,31 +249,6 @@ __device__ __forceinline__ uint32_t mesh_cube_triangles(uint32_t in, uint32_t la
         nt += inside == 2u ? 2u : (inside == 1u || inside == 3u) ? 1u : 0u;
     }
     return nt;
-}
-
-// Exclusive scan of one value per lane over a workgroup of WAVES x 64 lanes, in lane order; `total`: the workgroup's sum.
-// lds: WAVES words, free again on return.
-template <uint32_t WAVES>
-__device__ __forceinline__ uint32_t block_scan_excl(uint32_t v, uint32_t* lds, uint32_t& total) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63u) lds[wave] = x;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-#pragma unroll
-    for (uint32_t q = 0; q < WAVES; q++) {
-        const uint32_t t = lds[q];
-        if (q < wave) base += t;
-        tot += t;
-    }
-    __syncthreads();
-    total = tot;
-    return base + x - v;
 }
 
 __global__ __launch_bounds__(MESH_THREADS) void k_mesh_count(const uint32_t* __restrict__ field, MeshArgs A, uint32_t* __restrict__ vcount,

@@ -1,6 +1,7 @@
 // sph_obstacle.hip -- solid obstacles of any shape: one grid of signed distances per whole-domain context, which the fluid
 // collides with (sph_obstacle_lattice, _build, _set_grid, _clear, _set_motion, _get, _read, _sample of include/sph_hip.h, which
-// states the rule).  The reference has no counterpart.
+// states the rule).  The reference has no counterpart.  A grid voxelised from a triangle mesh (sph_obstacle_mesh.hip) is installed
+// through install_begin / install_finish below and is then this file's like any other.
 //
 //   k_obstacle_raster  one node per lane: the union of the analytic shapes, clamped                         (sph_obstacle_build)
 //   k_obstacle_clamp   one node per lane: the clamp of an uploaded field                                    (sph_obstacle_set_grid)
@@ -259,7 +260,7 @@ static ObstacleArgs obstacle_args(const sph_ctx* c) {
     return A;
 }
 
-static float ob_clamp_distance(const sph_obstacle_grid& G) {
+float ob_clamp_distance(const sph_obstacle_grid& G) {
 #pragma clang fp contract(off)
     return G.spacing * (float)(G.dims[0] + G.dims[1] + G.dims[2]);
 }
@@ -279,7 +280,9 @@ void advance_obstacle(sph_ctx* c, float dt) {
     for (int k = 0; k < 3; k++) c->ob_off[k] = c->ob_off[k] + dt * c->ob_vel[k];
 }
 
-static void release_obstacle(sph_ctx* c) {
+void release_obstacle(sph_ctx* c) {
+    c->mem.release(&c->ob_mesh_marks);
+    c->mem.release(&c->ob_mesh_work);
     c->mem.release(&c->ob_brick);
     c->mem.release(&c->ob_phi);
     c->ob_grid = sph_obstacle_grid{};
@@ -302,7 +305,7 @@ static int check_grid(const sph_obstacle_grid& G) {
 }
 
 // The lattice of a build: checks only, allocates nothing.
-static int lattice_resolve(const sph_ctx* c, float spacing, const float* lo, const float* hi, sph_obstacle_grid* G) {
+int lattice_resolve(const sph_ctx* c, float spacing, const float* lo, const float* hi, sph_obstacle_grid* G) {
 #pragma clang fp contract(off)
     SPH_REQUIRE(std::isfinite(spacing) && spacing >= 0.f, SPH_E_INVALID, "obstacle spacing %g: finite and >= 0 (0: the particle diameter)",
                 (double)spacing);
@@ -361,7 +364,7 @@ static int check_shapes(uint32_t n, const sph_shape* shapes, Shapes* out) {
     return SPH_OK;
 }
 
-static int obstacle_ctx(const sph_ctx* c, const char* who) {
+int obstacle_ctx(const sph_ctx* c, const char* who) {
     SPH_REQUIRE(c, SPH_E_INVALID, "null context");
     SPH_REQUIRE(!c->slab, SPH_E_STATE, "%s is not supported on a slab context (its step makes several force launches with holes, "
                 "and ghosts arrive integrated)", who);
@@ -370,7 +373,7 @@ static int obstacle_ctx(const sph_ctx* c, const char* who) {
 
 // The checked grid G becomes the context's: the old obstacle leaves (once the stream is idle), the two buffers are allocated.
 // On failure there is no obstacle.
-static int install_begin(sph_ctx* c, const sph_obstacle_grid& G) {
+int install_begin(sph_ctx* c, const sph_obstacle_grid& G) {
     SPH_HIP(hipSetDevice(c->device));
     if (have_obstacle(c)) {
         SPH_HIP(hipStreamSynchronize(c->stream));          // (a push of the old grid may still be running)
@@ -385,7 +388,7 @@ static int install_begin(sph_ctx* c, const sph_obstacle_grid& G) {
     return SPH_OK;
 }
 
-static int install_finish(sph_ctx* c) {
+int install_finish(sph_ctx* c) {
     const ObstacleArgs A = obstacle_args(c);
     const uint32_t bricks = A.nb[0] * A.nb[1] * A.nb[2];
     hipLaunchKernelGGL(k_obstacle_bricks, dim3(ceil_div(bricks, OBSTACLE_THREADS)), dim3(OBSTACLE_THREADS), 0, c->stream, A, c->ob_brick,

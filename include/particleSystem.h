@@ -165,6 +165,15 @@ public:
     // Offset and velocity of the grid (either may be nullptr = keep): the offset advances by dt * velocity once per step.
     void setObstacleMotion(const float* offset, const float* velocity);
     void clearObstacles();
+    // A closed triangle mesh (nv xyz triples, nt index triples) voxelised on the device into a signed distance `band` nodes wide
+    // (0: 3) and installed like the grid above (sph_obstacle_build_mesh); invert: the fluid is inside the mesh.
+    void setObstacleMesh(const float* pos, uint nv, const uint* tri, uint nt, float spacing = 0.f, uint band = 0, bool invert = false,
+                         const float* lo = nullptr, const float* hi = nullptr);
+    // The same from a Wavefront OBJ file (sph_obstacle_build_obj).
+    void setObstacleMeshOBJ(const char* path, float spacing = 0.f, uint band = 0, bool invert = false, const float* lo = nullptr,
+                            const float* hi = nullptr);
+    // used, skipped, lost crossings, odd columns of the mesh-built obstacle: a closed mesh gives out[2] = out[3] = 0
+    void getObstacleMeshStats(uint64_t out[4]);
 
     // ---- additive (absent upstream; named by BASELINE.json's north star) ------------------------
     // 4 floats per particle, by creation index (the original NVIDIA sample's layout), getCapacity() rows; the pointer

@@ -31,7 +31,8 @@
  *                  sph_positions_dev sph_download_positions4 sph_snapshot_save sph_snapshot_load sph_snapshot_info |
  *                  sph_set_colliders sph_get_colliders sph_set_collider_bodies sph_get_collider_impulses | sph_emit sph_remove sph_count_in_regions |
  *                  sph_obstacle_lattice sph_obstacle_build sph_obstacle_set_grid sph_obstacle_clear sph_obstacle_set_motion
- *                  sph_obstacle_get sph_obstacle_read sph_obstacle_sample |
+ *                  sph_obstacle_get sph_obstacle_read sph_obstacle_sample sph_obstacle_build_mesh sph_obstacle_build_mesh_dev
+ *                  sph_obstacle_build_obj |
  *                  sph_camera_look_at sph_render sph_render_read sph_render_image_dev sph_surface_defaults sph_render_surface
  *                  sph_render_surface_read | sph_mesh_defaults sph_mesh_lattice sph_mesh_extract sph_mesh_read sph_mesh_dev
  *                  sph_mesh_save_obj |
@@ -43,7 +44,7 @@
  *                  sph_slab_failed sph_slab_timing_enable/_reset/_get
  *   [introspect]   read-only views for parity tests, profiles and bench lines; may grow or change with the implementation:
  *                  sph_get_keys sph_get_order sph_get_cell_range sph_get_cells sph_cell_key sph_download_forces sph_sort_stats
- *                  sph_mesh_field_dims sph_mesh_field_read sph_sort_forms sph_last_sort_skipped sph_slab_stats sph_slab_counters sph_slab_in_place_merges
+ *                  sph_mesh_field_dims sph_mesh_field_read sph_obstacle_mesh_stats sph_sort_forms sph_last_sort_skipped sph_slab_stats sph_slab_counters sph_slab_in_place_merges
  *                  sph_slab_exchanges sph_slab_recut_stats sph_slab_early_force_stats sph_slab_protocol sph_rccl_transport_info
  *   [tuning]       switches whose defaults are the product's settings; in fp32 results do not depend on them (A/B runs):
  *                  sph_set_sort_mode sph_set_direct_hull sph_set_pair_small_launch sph_set_block_order sph_slab_set_early_force
@@ -404,6 +405,77 @@ int sph_obstacle_read(sph_ctx* c, float* phi);
 /* SAMPLE on the device for n caller points (xyz triples) with the current offset: "how far is this point from the solid".
  * Outside the grid: phi = +inf, normal (0, 0, 0), inside_grid 0.  Any output may be NULL.  Synchronises. */
 int sph_obstacle_sample(sph_ctx* c, uint32_t n, const float* pos_xyz, float* phi, float* normal_xyz, uint8_t* inside_grid);
+
+/* ---- obstacles from a triangle mesh: the mesh voxelised on the device into the grid above ----------------------------------------
+ * sph_obstacle_build_mesh turns a closed triangle mesh -- host arrays, device arrays (sph_mesh_dev's pointers feed it with no host
+ * trip) or a Wavefront OBJ file -- into a TRUNCATED signed distance on the lattice of sph_obstacle_build and installs it like any
+ * other grid: the push, the motion, _get, _read, _sample and _clear do not know the difference.  A context that never calls these
+ * allocates and launches what it did before.
+ *
+ * THE RULE (the conventions of THE RULE above: fp32, every operation rounded, no multiply-add fusion, sums left to right, IEEE
+ * division and square root; tests/mesh_obstacle_model.py is the same arithmetic in numpy and gives every node bit for bit).
+ * The lattice is that of sph_obstacle_build for the same spacing, lo, hi: node i of axis k sits at X = origin_k + (float)i * s.
+ * Input: n_vertices xyz triples, n_triangles uint32 triples; band in nodes, 1..SPH_OBSTACLE_MESH_MAX_BAND, 0 meaning
+ * SPH_OBSTACLE_MESH_DEFAULT_BAND; invert.  W = (float)band * s.  The result is phi = +-min(sqrtf(d2), W), negative inside;
+ * invert != 0 then negates it; last the clamp to [-D, D] of every installation.
+ * UNSIGNED PART.  A triangle (A, B, C) with the per-axis minimum lo_k and maximum hi_k of its vertices offers a candidate to
+ * every node of the index box
+ *     i_k in [ max(0, floorf(((lo_k - W) - origin_k) / s)),  min(n_k - 1, ceilf(((hi_k + W) - origin_k) / s)) ]
+ * (the float is clamped to [0, n_k - 1] before it becomes an integer; the box is part of the rule).  The candidate at node P is
+ * the minimum (fminf) of seg(A, B), seg(B, C), seg(C, A) and, where it applies, the plane term:
+ *     seg(a, b):  pa = P - a ;  ba = b - a ;  t = ((pa.x*ba.x + pa.y*ba.y) + pa.z*ba.z) / ((ba.x*ba.x + ba.y*ba.y) + ba.z*ba.z)
+ *                 t = fminf(fmaxf(t, 0), 1), or 0 unless ba.ba is a positive finite number
+ *                 d = pa - t*ba ;  seg = (d.x*d.x + d.y*d.y) + d.z*d.z                  (the capsule's arithmetic without r)
+ *     plane:      n = cross(B - A, C - A), cross(u, v) = (u.y*v.z - u.z*v.y, u.z*v.x - u.x*v.z, u.x*v.y - u.y*v.x)
+ *                 nn = (n.x*n.x + n.y*n.y) + n.z*n.z must be finite and > 0, and for (a, b) = (A, B), (B, C), (C, A):
+ *                 c = cross(b - a, n) ;  (((P-a).x*c.x + (P-a).y*c.y) + (P-a).z*c.z) <= 0       (the projection is inside)
+ *                 h = ((P-A).x*n.x + (P-A).y*n.y) + (P-A).z*n.z ;  the term is (h*h) / nn
+ * d2 of a node is the minimum over all triangles that offer to it, +inf without any: one unsigned 32-bit atomic min on the bits
+ * of a non-negative float, which does not depend on the order of arrival.
+ * SIGN.  The parity of the mesh crossings on the ray from the node towards -x.  A triangle tests the columns (j, k) of the index
+ * box of its y and z extents (the formula above without W, axes 1 and 2).  With q = (Y_j, Z_k), each of its three edges counts
+ * once if, (lo, hi) being its two ends in canonical order (smaller z first, on equal z smaller y first: independent of the
+ * winding),
+ *     lo.z <= q.z && !(hi.z <= q.z)   and   (hi.y - lo.y)*(q.z - lo.z) - (hi.z - lo.z)*(q.y - lo.y) > 0
+ * An odd count means the column crosses the triangle, at
+ *     xc = A.x + ((n.y*(A.y - q.y)) + n.z*(A.z - q.z)) / n.x ;  g = (xc - origin_x) / s
+ * A crossing whose g is not finite is LOST: it marks nothing and is counted.  Otherwise the triangle flips the parity bit of
+ * mark i0 = g <= 0 ? 0 : (g > (float)(n_x - 1) ? n_x : (uint)ceilf(g)) of the column; a column has n_x + 1 marks, the last one
+ * for crossings beyond the lattice.  Node i is inside iff the XOR of the marks 0..i of its column is 1; a column is ODD if the
+ * XOR of all its marks is 1.  Both triangles that share an edge compute the edge's test from the same bits, so every column of a
+ * closed mesh has an even total, whatever the rounding and the winding: odd columns mean an open mesh or lost crossings, and
+ * they are counted, not guessed at.  One integer atomic XOR per mark: two builds of one mesh give the same bits, and so do two
+ * builds with the triangles in another order.  No floating-point atomic.
+ * A triangle with an index >= n_vertices or a vertex that is not finite is SKIPPED on the device and counted (the host form has
+ * refused such input before; the device form cannot look).
+ * LIMITS.  Deeper than W inside the solid the field is flat at -W, where the push's normal falls back to (0, 1, 0): band >= 2 is
+ * needed for a correct trilinear gradient next to the surface.  That the mesh is closed is the CALLER's duty, and
+ * sph_obstacle_mesh_stats is the sensor.  Geometry is resolved to the spacing, as for the analytic shapes.
+ *
+ * Errors as in the section above: SPH_E_STATE on a slab context; SPH_E_INVALID for a band beyond the maximum, a null argument,
+ * no vertex or no triangle, bad bounds or spacing, and (host and OBJ forms) a vertex that is not finite, an index >= n_vertices,
+ * a file that cannot be read or holds no face; SPH_E_CAPACITY from the lattice limits or more than
+ * SPH_OBSTACLE_MESH_MAX_TRIANGLES triangles: all of them with nothing changed and nothing allocated.  SPH_E_NOMEM leaves the
+ * context with NO obstacle and every byte released.  Scratch of a build, kept until the next installation, sph_obstacle_clear
+ * or sph_destroy: 4 bytes per triangle plus 16 per 256 triangles, and one bit per node and column end (n_x + 1 bits per column,
+ * rounded up to words).  The calls touch none of the context's step flags. */
+#define SPH_OBSTACLE_MESH_MAX_BAND 16
+#define SPH_OBSTACLE_MESH_DEFAULT_BAND 3
+#define SPH_OBSTACLE_MESH_MAX_TRIANGLES (1u << 28)
+typedef struct sph_obstacle_mesh_params { float spacing; uint32_t band; int32_t invert; } sph_obstacle_mesh_params;   /* all 0 = defaults */
+/* Host arrays (left untouched): validates, copies to temporaries, voxelises and synchronises.  params NULL = defaults. */
+int sph_obstacle_build_mesh(sph_ctx* c, const sph_obstacle_mesh_params* params, const float lo[3], const float hi[3],
+                            uint32_t n_vertices, const float* pos_xyz, uint32_t n_triangles, const uint32_t* tri);
+/* Device arrays on the context's GPU, read on the context's stream (sph_mesh_dev's pointers are valid arguments): kernels on that
+ * stream, no host wait (unless it replaces an obstacle).  The arrays must stay valid until the stream has run the build. */
+int sph_obstacle_build_mesh_dev(sph_ctx* c, const sph_obstacle_mesh_params* params, const float lo[3], const float hi[3],
+                                uint32_t n_vertices, const void* pos_dev, uint32_t n_triangles, const void* tri_dev);
+/* A Wavefront OBJ file: `v x y z` and `f` lines (entries a, a/b, a//c or a/b/c; negative indices are relative; polygons are
+ * fanned from their first vertex), everything else ignored.  sph_mesh_save_obj writes %.9g: a saved mesh comes back bit for bit. */
+int sph_obstacle_build_obj(sph_ctx* c, const sph_obstacle_mesh_params* params, const float lo[3], const float hi[3], const char* path);
+/* [introspect] of the mesh-built obstacle: triangles used, triangles skipped, lost crossings, odd columns.  SPH_E_STATE unless the
+ * installed obstacle came from a mesh.  Synchronises. */
+int sph_obstacle_mesh_stats(sph_ctx* c, uint64_t out[4]);
 
 /* ---- emitters and drains: particles enter and leave a running simulation (no counterpart in the reference, whose particle
  *      set is fixed at construction; sph_set_by_index, its addSphere, only rewrites particles that exist) -----------------------
