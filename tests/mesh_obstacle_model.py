@@ -135,6 +135,26 @@ def build(grid, vertices, triangles, band=0, invert=False):
     return clamp(phi, grid), (used, skipped, lost, int(parity[:, :, nx].sum()))
 
 
+def tile_extents(grid, vertices, triangles, band=0):
+    """int64[n_used, 4]: per used triangle (across, rows) of the distance pass -- the nodes of its banded x range, the (j, k) rows of
+    its banded y and z ranges -- and (across, rows) of the crossing pass -- the columns of its y range, the rows of its z range"""
+    V = np.asarray(vertices, F).reshape(-1, 3)
+    T = np.asarray(triangles, np.uint32).reshape(-1, 3).astype(np.int64)
+    W = F(F(resolve_band(band)) * F(grid["spacing"]))
+    out = []
+    with np.errstate(all="ignore"):
+        for t in T[good_triangles(V, T)]:
+            ((i0, i1), (j0, j1), (k0, k1)), ((cj0, cj1), (ck0, ck1)) = _boxes(V[t[0]], V[t[1]], V[t[2]], W, grid)
+            out.append((i1 - i0 + 1, (j1 - j0 + 1) * (k1 - k0 + 1), cj1 - cj0 + 1, ck1 - ck0 + 1))
+    return np.array(out, np.int64).reshape(-1, 4)
+
+
+def crossing_tiles(grid, vertices, triangles, band=0):
+    """tiles of the crossing pass per used triangle: 64-column chunks of its y range times 128-row groups of its z range"""
+    e = tile_extents(grid, vertices, triangles, band)
+    return -(-e[:, 2] // TILE_X) * -(-e[:, 3] // TILE_ROWS)
+
+
 def distance_tiles(grid, vertices, triangles, band=0):
     """tiles of the distance pass per used triangle: 64-node chunks of its x range times 128-row groups of its (j, k) rows"""
     V = np.asarray(vertices, F).reshape(-1, 3)

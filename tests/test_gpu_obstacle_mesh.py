@@ -2,7 +2,8 @@
 model of tests/mesh_obstacle_model.py, BIT FOR BIT, on the inputs of tests/mesh_obstacle_cases.py: every case and its four
 counters, the triangles in another order, the device-array path fed by sph_mesh_dev, a fused and a phased step against
 obstacle_model.push on a bare twin's output, motion and replacement, the refusals with every allocation failing once, and the
-triangles the device form skips."""
+triangles the device form skips; then lattices wider than a wave and work lists longer than a launch (mc.LARGE_CASES) and a triangle
+list of more than 1024 blocks, nearly all skipped (mc.sparse_blocks)."""
 import ctypes as C
 
 import numpy as np
@@ -234,3 +235,50 @@ def test_the_device_form_skips_bad_triangles():
         assert L.sph_obstacle_build_mesh_dev(c.h, C.byref(p), lo, hi, len(v), dv.data_ptr(), len(t), dt.data_ptr()) == 0
         _same(c.obstacle(read=True)["phi"], want)
         assert c.obstacle_mesh_stats() == full_stats
+
+
+# ---- 7. the work list beyond one tile per triangle: chunks, row groups, mark words, the stride (tests/mesh_obstacle_cases.py:
+#         LARGE_CASES; what each case reaches is asserted in tests/test_mesh_obstacle_model_cpu.py) ------------------------------------
+def _build_large(c, case):
+    v, t, band, bounds, _, s = case
+    c.build_obstacle_mesh(v, t, float(s), band, False, bounds)
+    return c.obstacle(read=True), c.obstacle_mesh_stats()
+
+
+@pytest.mark.parametrize("name", mc.LARGE_CASES)
+def test_large_lattices_equal_the_model(name):
+    """phi and the four counters, bit for bit: as given, built a second time, and with the triangles in another order"""
+    want, stats = mc.large_model(name)
+    grid = mc.large_grid_of(name)
+    with _ctx() as c:
+        ob, got = _build_large(c, mc.large_case(name))
+        assert ob["dims"] == grid["dims"] and ob["spacing"] == grid["spacing"]
+        _same(ob["origin"], grid["origin"])
+        _same(ob["phi"], want, name)
+        assert got == stats, (got, stats)
+        again, got = _build_large(c, mc.large_case(name))
+        _same(again["phi"], ob["phi"], name + " built twice")
+        assert got == stats
+        ob, got = _build_large(c, mc.large_permuted(name))
+        _same(ob["phi"], want, name + " permuted")
+        assert got == stats
+
+
+def test_the_device_form_with_a_thousand_skipped_blocks():
+    """More blocks of 256 triangles than the second scan level takes at a time, nearly all without a tile (mc.sparse_blocks): the 320
+    used triangles give the field and the counters of `ico_rotated` alone."""
+    v, tri, at = mc.sparse_blocks()
+    nt = len(tri)
+    want, stats = mc.model("ico_rotated")
+    band = mc.case("ico_rotated")[2]
+    assert stats == (320, 0, 0, 0) and len(at) == 320
+    dv, dt = torch.from_numpy(v).cuda(), torch.from_numpy(tri.view(np.int32).copy()).cuda()
+    torch.cuda.synchronize()
+    L = capi.load()
+    with _ctx() as c:
+        p = capi.ObstacleMeshParams(S, band, 0)
+        lo, hi = (C.c_float * 3)(*mc.BMIN), (C.c_float * 3)(*mc.BMAX)
+        for _ in range(2):
+            assert L.sph_obstacle_build_mesh_dev(c.h, C.byref(p), lo, hi, len(v), dv.data_ptr(), nt, dt.data_ptr()) == 0
+            _same(c.obstacle(read=True)["phi"], want)
+            assert c.obstacle_mesh_stats() == (320, nt - 320, 0, 0)
