@@ -264,6 +264,7 @@ SIGNATURES = {
     "sph_test_trust_mover_hint": (C.c_int, [_P]),
     "sph_memory_stats": (None, [C.POINTER(C.c_uint64)]),
     "sph_test_fail_alloc": (None, [C.c_uint32]),
+    "sph_test_scan": (C.c_int, [_P, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sph_set_precision": (C.c_int, [_P, C.c_int]),
     "sph_get_precision": (C.c_int, [_P]),
     "sph_migrants_count": (C.c_int, [_P, C.POINTER(_U32)]),
@@ -899,6 +900,14 @@ class Context:
     def trust_mover_hint(self):
         """Test hook: after set_by_index / upload the next movers' sorts launch both forms; this takes that back."""
         _check(self.L.sph_test_trust_mover_hint(self.h))
+
+    def test_scan(self, values):
+        """Test hook: (exclusive prefix sums, total) of a uint32 or uint64 array by the library's one-block scan."""
+        v = np.ascontiguousarray(values)
+        assert v.ndim == 1 and v.dtype in (np.uint32, np.uint64), v.dtype
+        out, total = np.empty_like(v), np.zeros(1, v.dtype)
+        _check(self.L.sph_test_scan(self.h, 8 * v.dtype.itemsize, v.size, v.ctypes.data, out.ctypes.data, total.ctypes.data))
+        return out, total[0]
 
     def sort_forms(self):
         """Movers' sorts launched as (both forms, one-block sort alone, multi-block passes alone)."""

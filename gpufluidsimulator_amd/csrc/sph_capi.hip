@@ -1,7 +1,7 @@
 // sph_capi.hip -- the C ABI of include/sph_hip.h: context lifetime, state transfer, phase
 // sequencing and device timing.  Host code only; kernels live in sph_sort.hip / sph_pairs.hip /
-// sph_halo.hip.
-#include "sph_common.hpp"
+// sph_halo.hip (the one kernel here is sph_test_scan's).
+#include "sph_device.hpp"
 
 #include <cmath>
 #include <cstdarg>
@@ -10,6 +10,28 @@
 #include <new>
 
 namespace sph {
+
+// [test hook] sph_test_scan: scan_array_one_block (sph_device.hpp) and nothing else
+template <class T>
+__global__ __launch_bounds__(1024) void k_test_scan(const T* __restrict__ in, uint32_t n, T* __restrict__ out, T* __restrict__ total) {
+    __shared__ T lds[1024 / 64];
+    const T sum = scan_array_one_block<1024>(n, lds, [&](uint32_t i) { return in[i]; }, [&](uint32_t i, T before) { out[i] = before; });
+    if (threadIdx.x == 0) *total = sum;
+}
+
+template <class T>
+static int test_scan(sph_ctx* c, Buffers& mem, uint32_t n, const void* in, void* out, void* total) {
+    T *d_in = nullptr, *d_out = nullptr, *d_total = nullptr;
+    int rc;
+    if ((rc = mem.alloc(&d_in, n, false)) || (rc = mem.alloc(&d_out, n, false)) || (rc = mem.alloc(&d_total, 1, false))) return rc;
+    if (n) SPH_HIP(hipMemcpyAsync(d_in, in, (size_t)n * sizeof(T), hipMemcpyHostToDevice, c->stream));
+    k_test_scan<T><<<1, 1024, 0, c->stream>>>(d_in, n, d_out, d_total);
+    SPH_HIP(hipGetLastError());
+    if (n) SPH_HIP(hipMemcpyAsync(out, d_out, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+    SPH_HIP(hipMemcpyAsync(total, d_total, sizeof(T), hipMemcpyDeviceToHost, c->stream));
+    SPH_HIP(hipStreamSynchronize(c->stream));
+    return SPH_OK;
+}
 
 static thread_local std::string g_err;
 static int g_device = 0;        // sph_select_device: what `device < 0` means in sph_create
@@ -1081,5 +1103,16 @@ void sph_memory_stats(uint64_t out[3]) {
 
 // [test hook] the k-th allocation from now returns SPH_E_NOMEM without calling HIP, once; 0 disarms
 void sph_test_fail_alloc(uint32_t k) { g_fail_alloc.store(k); }
+
+// [test hook] the exclusive prefix sums of `n` host values of `bits` (32 or 64) bits and their total, by the one-block scan
+int sph_test_scan(sph_ctx* c, int bits, uint32_t n, const void* in, void* out, void* total) {
+    SPH_REQUIRE(c && total && (n == 0 || (in && out)), SPH_E_INVALID, "null argument");
+    SPH_REQUIRE(bits == 32 || bits == 64, SPH_E_INVALID, "a scan of %d-bit values", bits);
+    SPH_HIP(hipSetDevice(c->device));
+    Buffers mem;
+    const int rc = bits == 32 ? test_scan<uint32_t>(c, mem, n, in, out, total) : test_scan<uint64_t>(c, mem, n, in, out, total);
+    mem.free_all();
+    return rc;
+}
 
 }  // extern "C"

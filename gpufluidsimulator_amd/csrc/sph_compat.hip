@@ -9,7 +9,7 @@
 // the seam holds the permutation between the two orders -- `m2n[a]` = native slot of the caller's a-th particle --
 // and every write-back goes through it.  Only the order INSIDE a cell is this library's (stable); the reference's
 // is whatever thrust::sort / std::sort leave, i.e. unspecified.
-#include "sph_common.hpp"
+#include "sph_device.hpp"
 #include "../../include/sph_compat_seam.h"
 
 #include <cstdlib>
@@ -186,24 +186,13 @@ __global__ __launch_bounds__(256) void k_compat_Bprime(const uint32_t* __restric
     if (begins && at < bp_cap) { Bp[at].nParticles = cnt; Bp[at].start = i; }
 }
 
+// one block: exclusive scan of the tile counts (scan_array_one_block, sph_device.hpp); the total goes to mapped host memory
 __global__ __launch_bounds__(1024) void k_compat_scan(const uint32_t* __restrict__ cnt, uint32_t nt,
                                                       uint32_t* __restrict__ off, volatile uint32_t* __restrict__ total) {
-    __shared__ uint32_t part[1024];
-    const uint32_t per = (nt + 1023u) / 1024u;
-    const uint32_t lo = min(threadIdx.x * per, nt), hi = min(lo + per, nt);
-    uint32_t s = 0;
-    for (uint32_t t = lo; t < hi; t++) s += cnt[t];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const uint32_t v = threadIdx.x >= (uint32_t)o ? part[threadIdx.x - o] : 0u;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    uint32_t run = part[threadIdx.x] - s;
-    for (uint32_t t = lo; t < hi; t++) { off[t] = run; run += cnt[t]; }
-    if (threadIdx.x == 1023) *total = part[1023];
+    __shared__ uint32_t lds[1024 / 64];
+    const uint32_t sum = scan_array_one_block<1024>(nt, lds, [&](uint32_t t) { return cnt[t]; },
+                                                    [&](uint32_t t, uint32_t before) { off[t] = before; });
+    if (threadIdx.x == 1023) *total = sum;
 }
 
 // (re)configure the context of a particle array from the caller's device-resident SimParams; the reference

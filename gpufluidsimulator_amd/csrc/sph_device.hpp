@@ -92,18 +92,27 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 
-// Exclusive scan of one value per lane over a workgroup of WAVES x 64 lanes, in lane order; `total`: the workgroup's sum.
-// lds: WAVES entries, free again on return.  (The mesh extraction's scans, sph_mesh.hip, and the voxeliser's work list,
-// sph_obstacle_mesh.hip.)
-template <uint32_t WAVES, class T = uint32_t>
-__device__ __forceinline__ T block_scan_excl(T v, T* lds, T& total) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    T x = v;
+// ---- prefix sums: THE scans of the library (every count -> scan -> scatter pipeline ends up here) ------------------------------
+// Inclusive scan of one value per lane over the wave, in lane order: six shuffle steps, no LDS.
+template <class T>
+__device__ __forceinline__ T wave_scan_incl(T x) {
+    const uint32_t lane = threadIdx.x & 63u;
 #pragma unroll
     for (uint32_t d = 1; d < 64; d <<= 1) {
         const T y = __shfl_up(x, d, 64);
         if (lane >= d) x += y;
     }
+    return x;
+}
+
+// Exclusive scan of one value per lane over a workgroup of WAVES x 64 lanes, in lane order; `total`, where asked for: the
+// workgroup's sum.  lds: WAVES entries, free again on return.  Two barriers: every thread of the workgroup must come by.
+// One body behind two overloads; WITH_TOTAL is a template flag, not a test of `total`, so that the callers without a total have
+// instantiations to themselves: what hipcc makes of k_os_small changes with who else calls the function it inlines there.
+template <uint32_t WAVES, class T, bool WITH_TOTAL>
+__device__ __forceinline__ T block_scan_excl_(T v, T* lds, T* total) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const T x = wave_scan_incl(v);
     if (lane == 63u) lds[wave] = x;
     __syncthreads();
     T base = 0, tot = 0;
@@ -113,9 +122,33 @@ __device__ __forceinline__ T block_scan_excl(T v, T* lds, T& total) {
         if (q < wave) base += t;
         tot += t;
     }
+    if (WITH_TOTAL) *total = tot;
     __syncthreads();
-    total = tot;
     return base + x - v;
+}
+template <uint32_t WAVES, class T = uint32_t>
+__device__ __forceinline__ T block_scan_excl(T v, T* lds, T& total) { return block_scan_excl_<WAVES, T, true>(v, lds, &total); }
+template <uint32_t WAVES, class T = uint32_t>
+__device__ __forceinline__ T block_scan_excl(T v, T* lds) { return block_scan_excl_<WAVES, T, false>(v, lds, nullptr); }
+
+// Exclusive scan of an array of n items by ONE workgroup of THREADS lanes: chunks of THREADS items with a carry.  load(i) gives
+// item i, store(i, sum of the items before i) consumes it (it may overwrite item i: every load of a chunk precedes its stores);
+// every thread gets the total.  lds: THREADS / 64 entries.  The chunk loop is uniform over the workgroup (block_scan_excl has
+// barriers): lanes past n take part with 0.  n = 0: nothing is stored, the total is 0.  Integer sums: the result does not depend
+// on who adds what, wrap-around included.  (The tile counts of the movers' merge, of sph_remove, of the compat seam's B' and
+// of the slab re-cut; the block sums of the surface mesh and of the voxeliser's work list.)
+template <uint32_t THREADS, class T, class Load, class Store>
+__device__ __forceinline__ T scan_array_one_block(uint32_t n, T* lds, Load load, Store store) {
+    T carry = 0;
+    for (uint32_t base = 0; base < n; base += THREADS) {
+        const uint32_t i = base + threadIdx.x;
+        const T v = i < n ? load(i) : T(0);
+        T sum;
+        const T e = block_scan_excl<THREADS / 64, T>(v, lds, sum);
+        if (i < n) store(i, carry + e);
+        carry += sum;
+    }
+    return carry;
 }
 
 // ---- cell table: {start, end} per occupied cell from boundary flags on the sorted keys (k_cells_build, sph_pairs.hip; the slab

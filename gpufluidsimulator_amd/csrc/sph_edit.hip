@@ -4,14 +4,14 @@
 // the keys of the last sort and the next sort may merge.  No atomic decides an order; every run gives the same slots.
 //
 //   k_edit_count    one pass over posi: the region predicate per slot, a ballot per wave, one count per 2048-slot tile
-//   k_edit_scan     one block: exclusive scan of the tile counts, and their total
+//   k_edit_scan     one block: exclusive scan of the tile counts, and their total (scan_array_one_block, sph_device.hpp)
 //   k_edit_compact  the predicate again (same arithmetic, same answer), ranks from the ballot masks; survivors stream to
 //                   slot - (selected particles in front of it) with 16-byte loads and stores, the selected ones leave their
 //                   creation index in slot order and their row of the by-index position buffer is zeroed
 //
 // The tile counts and offsets live in the movers' ping-pong scratch of the sort (edit_tiles below) and the removed indices in k0:
 // all three are dead between two steps, so a call that selects nothing leaves every bit of the context as it was.
-#include "sph_common.hpp"
+#include "sph_device.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -78,28 +78,13 @@ __global__ __launch_bounds__(EDIT_THREADS) void k_edit_count(const float4* __res
     if (threadIdx.x == 0u) tile_cnt[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
 }
 
-// one block: exclusive scan of the tile counts (the shape of k_mm_tilescan; the counts are left as they are)
+// one block: exclusive scan of the tile counts (scan_array_one_block, sph_device.hpp; the counts are left as they are)
 __global__ __launch_bounds__(1024) void k_edit_scan(const uint32_t* __restrict__ tile_cnt, uint32_t nt,
                                                     uint32_t* __restrict__ tile_off, uint32_t* __restrict__ total) {
-    __shared__ uint32_t part[1024];
-    const uint32_t per = (nt + 1023u) / 1024u;
-    const uint32_t lo = min(threadIdx.x * per, nt), hi = min(lo + per, nt);
-    uint32_t s = 0;
-    for (uint32_t t = lo; t < hi; t++) s += tile_cnt[t];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        uint32_t v = threadIdx.x >= (uint32_t)off ? part[threadIdx.x - off] : 0u;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    uint32_t run = part[threadIdx.x] - s;
-    for (uint32_t t = lo; t < hi; t++) {
-        tile_off[t] = run;
-        run += tile_cnt[t];
-    }
-    if (threadIdx.x == 1023u) *total = part[1023];
+    __shared__ uint32_t lds[1024 / 64];
+    const uint32_t sum = scan_array_one_block<1024>(nt, lds, [&](uint32_t t) { return tile_cnt[t]; },
+                                                    [&](uint32_t t, uint32_t before) { tile_off[t] = before; });
+    if (threadIdx.x == 1023u) *total = sum;
 }
 
 __global__ __launch_bounds__(EDIT_THREADS) void k_edit_compact(const float4* __restrict__ posi, const float4* __restrict__ velr,

@@ -10,7 +10,7 @@
 //   k_mesh_count      one node per lane, MESH_BLOCK nodes per workgroup: the inside flags of the node's cube -> how many of its
 //                     seven edges carry a vertex (kept per node for the scan) and how many triangles its cube gives; the
 //                     workgroup's two sums
-//   k_mesh_scan_sums  ONE workgroup: the exclusive scans of the two rows of sums, MESH_SCAN2 at a time with a carry, and the totals
+//   k_mesh_scan_sums  ONE workgroup: the exclusive scans of the two rows of sums and the totals (scan_array_one_block, sph_device.hpp)
 //   k_mesh_vbase      the in-block scan of the vertex counts + the block's base: the vertex base of every node (4 B per node;
 //                     a vertex's number is base[node] + popcount(mask & ((1 << (d-1)) - 1)), the mask recomputed from the counts)
 //   -- the host reads the two totals here: the call's one wait --
@@ -270,22 +270,18 @@ __global__ __launch_bounds__(MESH_THREADS) void k_mesh_count(const uint32_t* __r
     if (threadIdx.x == 0) { blk_v[blockIdx.x] = tv; blk_t[blockIdx.x] = tt; }
 }
 
-// sums -> exclusive bases, in place; tot[0], tot[1] = the totals.  One workgroup: the carry goes from chunk to chunk.
+// sums -> exclusive bases, in place, one row after the other; tot[0], tot[1] = the totals.  One workgroup (scan_array_one_block,
+// sph_device.hpp).
 __global__ __launch_bounds__(MESH_SCAN2) void k_mesh_scan_sums(uint32_t* __restrict__ blk_v, uint32_t* __restrict__ blk_t, uint32_t nb,
                                                                uint32_t* __restrict__ tot) {
     __shared__ uint32_t lds[MESH_SCAN2 / 64];
-    uint32_t carry_v = 0, carry_t = 0;
-    for (uint32_t base = 0; base < nb; base += MESH_SCAN2) {
-        const uint32_t b = base + threadIdx.x;
-        const uint32_t v = b < nb ? blk_v[b] : 0u, t = b < nb ? blk_t[b] : 0u;
-        uint32_t sv, st;
-        const uint32_t ev = block_scan_excl<MESH_SCAN2 / 64>(v, lds, sv);
-        const uint32_t et = block_scan_excl<MESH_SCAN2 / 64>(t, lds, st);
-        if (b < nb) { blk_v[b] = carry_v + ev; blk_t[b] = carry_t + et; }
-        carry_v += sv;
-        carry_t += st;
+    uint32_t* const rows[2] = {blk_v, blk_t};
+    for (uint32_t r = 0; r < 2; r++) {
+        uint32_t* const row = rows[r];
+        const uint32_t sum = scan_array_one_block<MESH_SCAN2>(nb, lds, [&](uint32_t b) { return row[b]; },
+                                                              [&](uint32_t b, uint32_t before) { row[b] = before; });
+        if (threadIdx.x == 0) tot[r] = sum;
     }
-    if (threadIdx.x == 0) { tot[0] = carry_v; tot[1] = carry_t; }
 }
 
 __global__ __launch_bounds__(MESH_THREADS) void k_mesh_vbase(uint32_t* __restrict__ vbase, uint32_t nodes, const uint32_t* __restrict__ blk_v) {

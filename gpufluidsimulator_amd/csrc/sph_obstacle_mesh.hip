@@ -5,7 +5,8 @@
 //
 //   k_obmesh_count     one triangle per lane: is it usable, and how many TILES of the distance pass and of the crossing pass its
 //                      index boxes give; the in-block scan of both and the block's sums
-//   k_obmesh_scan      ONE workgroup: the exclusive scan of the block sums (64-bit) and the two totals
+//   k_obmesh_scan      ONE workgroup: the exclusive scan of the block sums (64-bit) and the two totals (scan_array_one_block,
+//                      sph_device.hpp)
 //   k_obmesh_distance  one wave per tile, found by binary search in the scanned counts: 64 consecutive x nodes times up to
 //                      OBMESH_TILE_ROWS rows; per node one unsigned atomic min on the bits of the squared distance
 //   k_obmesh_cross     one wave per tile of (j, k) columns: 64 consecutive j times up to OBMESH_TILE_ROWS k; per crossing one atomic
@@ -137,21 +138,17 @@ __global__ __launch_bounds__(OBMESH_THREADS) void k_obmesh_count(const float* __
     }
 }
 
-// sums -> exclusive bases, in place; head[0], head[1] = the totals.  One workgroup: the carry goes from chunk to chunk.
+// sums -> exclusive bases, in place, one row after the other; head[0], head[1] = the totals.  One workgroup (scan_array_one_block,
+// sph_device.hpp), 64-bit: a work list may hold more than 2^32 tiles.
 __global__ __launch_bounds__(OBMESH_SCAN2) void k_obmesh_scan(ObMeshWork w, uint32_t nb) {
     __shared__ uint64_t lds[OBMESH_SCAN2 / 64];
-    uint64_t carry_d = 0, carry_x = 0;
-    for (uint32_t base = 0; base < nb; base += OBMESH_SCAN2) {
-        const uint32_t b = base + threadIdx.x;
-        const uint64_t d = b < nb ? w.blk_d[b] : 0ull, x = b < nb ? w.blk_x[b] : 0ull;
-        uint64_t sd, sx;
-        const uint64_t ed = block_scan_excl<OBMESH_SCAN2 / 64, uint64_t>(d, lds, sd);
-        const uint64_t ex = block_scan_excl<OBMESH_SCAN2 / 64, uint64_t>(x, lds, sx);
-        if (b < nb) { w.blk_d[b] = carry_d + ed; w.blk_x[b] = carry_x + ex; }
-        carry_d += sd;
-        carry_x += sx;
+    uint64_t* const rows[2] = {w.blk_d, w.blk_x};
+    for (uint32_t r = 0; r < 2; r++) {
+        uint64_t* const row = rows[r];
+        const uint64_t sum = scan_array_one_block<OBMESH_SCAN2>(nb, lds, [&](uint32_t b) { return row[b]; },
+                                                                [&](uint32_t b, uint64_t before) { row[b] = before; });
+        if (threadIdx.x == 0) w.head[r] = sum;
     }
-    if (threadIdx.x == 0) { w.head[0] = carry_d; w.head[1] = carry_x; }
 }
 
 // tile `tile` of a pass -> its triangle and the tile's number inside the triangle: the last block whose base is <= tile, then the

@@ -516,23 +516,15 @@ __global__ __launch_bounds__(256) void k_recut_count(const float4* __restrict__ 
     __syncthreads();
     if (threadIdx.x < 2) blk[2 * blockIdx.x + threadIdx.x] = s_c[threadIdx.x];
 }
-// exclusive scan of the per-block {down, up} counts by one block; the totals go to mapped host memory
+// exclusive scan of the per-block {down, up} counts by one block, row by row and in place (scan_array_one_block, sph_device.hpp);
+// the totals go to mapped host memory
 __global__ __launch_bounds__(1024) void k_recut_scan(uint32_t* __restrict__ blk, uint32_t nblk, volatile uint32_t* __restrict__ host) {
-    __shared__ uint32_t part[2][1024];
-    const uint32_t per = (nblk + 1023u) / 1024u, lo = min(threadIdx.x * per, nblk), hi = min(lo + per, nblk);
-    uint32_t s0 = 0, s2 = 0;
-    for (uint32_t b = lo; b < hi; b++) { s0 += blk[2 * b]; s2 += blk[2 * b + 1]; }
-    part[0][threadIdx.x] = s0; part[1][threadIdx.x] = s2;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const uint32_t a = threadIdx.x >= (uint32_t)o ? part[0][threadIdx.x - o] : 0u, b = threadIdx.x >= (uint32_t)o ? part[1][threadIdx.x - o] : 0u;
-        __syncthreads();
-        part[0][threadIdx.x] += a; part[1][threadIdx.x] += b;
-        __syncthreads();
+    __shared__ uint32_t lds[1024 / 64];
+    for (uint32_t row = 0; row < 2; row++) {
+        const uint32_t sum = scan_array_one_block<1024>(nblk, lds, [&](uint32_t b) { return blk[2 * b + row]; },
+                                                        [&](uint32_t b, uint32_t before) { blk[2 * b + row] = before; });
+        if (threadIdx.x == 1023) host[row] = sum;
     }
-    uint32_t r0 = part[0][threadIdx.x] - s0, r2 = part[1][threadIdx.x] - s2;
-    for (uint32_t b = lo; b < hi; b++) { const uint32_t c0 = blk[2 * b], c2 = blk[2 * b + 1]; blk[2 * b] = r0; blk[2 * b + 1] = r2; r0 += c0; r2 += c2; }
-    if (threadIdx.x == 1023) { host[0] = part[0][1023]; host[1] = part[1][1023]; }
 }
 // stable three-way partition: who stays -> [keep0 + rank), who goes down -> [down0 + rank), up -> [up0 + rank) of the
 // ping-pong arrays, each class in slot order (one wave per 64 slots: ranks by ballot, the waves of a block in sequence)

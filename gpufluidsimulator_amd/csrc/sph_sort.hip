@@ -91,26 +91,6 @@ __device__ __forceinline__ uint32_t sort_count(uint32_t n, const uint32_t* __res
     return n_dev ? min(*n_dev, n) : n;
 }
 
-// exclusive scan of one value per thread over a block of NW waves (wave shuffles + NW wave totals in LDS)
-template <int NW>
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_wtot /*[NW]*/, uint32_t* total) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t t = (uint32_t)__shfl_up((int)inc, off);
-        if (lane >= (uint32_t)off) inc += t;
-    }
-    if (lane == 63u) s_wtot[wave] = inc;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < (uint32_t)NW; w++) { const uint32_t t = s_wtot[w]; if (w < wave) base += t; tot += t; }
-    if (total) *total = tot;
-    __syncthreads();                                     // s_wtot may be reused by the caller
-    return base + inc - v;
-}
-
 // count[d] += 1 for every valid lane.  Keys arrive nearly sorted (particle order of the previous step, or lattice
 // order), so the high digits are the same in all 64 lanes more often than not: then one lane adds the popcount
 // instead of 64 lanes queueing up on one LDS word.
@@ -195,12 +175,7 @@ __global__ __launch_bounds__(256) void k_os_scan(uint32_t* __restrict__ hist, ui
         uint32_t v = 0;
         if (g < ngroups) { v = hist[idx]; hist[idx] = 0u; }
         if (d == 0 && g < ngroups) tickets[(size_t)p * tickets_stride + g] = 0u;   // grouped form: one ticket per group
-        uint32_t inc = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t t = (uint32_t)__shfl_up((int)inc, off);
-            if (lane >= (uint32_t)off) inc += t;
-        }
+        const uint32_t inc = wave_scan_incl(v);
         if (g < ngroups) base[idx] = carry + inc - v;
         carry += (uint32_t)__shfl((int)inc, 63);
     }
@@ -272,7 +247,7 @@ __global__ __launch_bounds__(PASS_THREADS, SPH_OS_PASS_OCC) void k_os_pass(const
         uint32_t tot[DPT], sum = 0;
 #pragma unroll
         for (int k = 0; k < DPT; k++) { tot[k] = has_d ? digit_tot[threadIdx.x * DPT + k] : 0u; sum += tot[k]; }
-        uint32_t run = block_excl_scan<PASS_WAVES>(sum, s_wtot, nullptr);
+        uint32_t run = block_scan_excl<PASS_WAVES>(sum, s_wtot);
 #pragma unroll
         for (int k = 0; k < DPT; k++) { dbase[k] = run; run += tot[k]; }
     }
@@ -354,7 +329,7 @@ __global__ __launch_bounds__(PASS_THREADS, SPH_OS_PASS_OCC) void k_os_pass(const
             uint32_t sum = 0;
 #pragma unroll
             for (int k = 0; k < DPT; k++) sum += cnt[k];
-            uint32_t run = block_excl_scan<PASS_WAVES>(sum, s_wtot, nullptr);
+            uint32_t run = block_scan_excl<PASS_WAVES>(sum, s_wtot);
 #pragma unroll
             for (int k = 0; k < DPT; k++) {
                 const uint32_t d = threadIdx.x * DPT + k;
@@ -602,7 +577,7 @@ __global__ __launch_bounds__(SMALL_THREADS) void k_os_small(uint32_t* ak, uint32
             __syncthreads();
             {
                 const uint32_t cnt = threadIdx.x < (uint32_t)RADIX ? ghist[threadIdx.x] : 0u;
-                const uint32_t start = block_excl_scan<SMALL_WAVES>(cnt, s_wtot, nullptr);
+                const uint32_t start = block_scan_excl<SMALL_WAVES>(cnt, s_wtot);
                 if (threadIdx.x < (uint32_t)RADIX) gbase[threadIdx.x] = start;
             }
             __syncthreads();
@@ -699,7 +674,7 @@ __global__ __launch_bounds__(SMALL_THREADS) void k_os_small(uint32_t* ak, uint32
 #pragma unroll
             for (int w = 0; w < SMALL_WAVES; w++) { const uint32_t c = wh[w][threadIdx.x]; wh[w][threadIdx.x] = cnt; cnt += c; }
         }
-        const uint32_t start = block_excl_scan<SMALL_WAVES>(cnt, s_wtot, nullptr);
+        const uint32_t start = block_scan_excl<SMALL_WAVES>(cnt, s_wtot);
         if (has_d) {
 #pragma unroll
             for (int w = 0; w < SMALL_WAVES; w++) wh[w][threadIdx.x] += start;
@@ -969,34 +944,17 @@ __global__ __launch_bounds__(256) void k_mm_mark(const uint32_t* __restrict__ A,
     }
 }
 
-// one block: exclusive scan of the per-tile mover counts; re-zeroes the counts for the next step
+// one block: exclusive scan of the per-tile mover counts (scan_array_one_block, sph_device.hpp); re-zeroes the counts for the next step
 __global__ __launch_bounds__(1024) void k_mm_tilescan(uint32_t* __restrict__ tile_cnt, uint32_t nt,
                                                       uint32_t* __restrict__ tile_off, uint32_t* __restrict__ m_dev,
                                                       volatile uint32_t* __restrict__ m_host,
                                                       unsigned long long* __restrict__ m_total, uint32_t seq) {
-    __shared__ uint32_t part[1024];
-    const uint32_t per = (nt + 1023u) / 1024u;
-    const uint32_t lo = min(threadIdx.x * per, nt), hi = min(lo + per, nt);
-    uint32_t s = 0;
-    for (uint32_t t = lo; t < hi; t++) s += tile_cnt[t];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        uint32_t v = threadIdx.x >= (uint32_t)off ? part[threadIdx.x - off] : 0u;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    uint32_t run = part[threadIdx.x] - s;
-    for (uint32_t t = lo; t < hi; t++) {
-        uint32_t v = tile_cnt[t];
-        tile_off[t] = run;
-        tile_cnt[t] = 0;
-        run += v;
-    }
+    __shared__ uint32_t lds[1024 / 64];
+    const uint32_t m = scan_array_one_block<1024>(nt, lds, [&](uint32_t t) { return tile_cnt[t]; },
+                                                  [&](uint32_t t, uint32_t before) { tile_off[t] = before; tile_cnt[t] = 0; });
     if (threadIdx.x == 1023) {
-        *m_dev = part[1023]; m_host[HW_MOVERS] = part[1023];
-        if (m_total) *m_total += part[1023];          // one block: no atomic needed (sph_sort_stats: movers_total)
+        *m_dev = m; m_host[HW_MOVERS] = m;
+        if (m_total) *m_total += m;                   // one block: no atomic needed (sph_sort_stats: movers_total)
         if (seq) { __threadfence_system(); m_host[HW_COUNT_SEQ] = seq; }     // "the count of scan number seq is in HW_MOVERS" (launch_sort's skip)
     }
 }
@@ -1050,6 +1008,7 @@ __global__ __launch_bounds__(256) void k_mm_compact(const uint64_t* __restrict__
     const uint32_t chunk = blockIdx.x * MM_TILE_CHUNKS + threadIdx.x;
     uint64_t m = chunk < nchunks ? mask[chunk] : 0ull;
     const uint32_t cnt = (uint32_t)__popcll(m);
+    // (eight rounds in LDS, not block_scan_excl: with four waves the shuffle form showed no gain, profiles/scan_unify_ab.txt)
     part[threadIdx.x] = cnt;
     __syncthreads();
     for (int off = 1; off < 256; off <<= 1) {

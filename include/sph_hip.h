@@ -50,6 +50,7 @@
  *                  sph_set_sort_mode sph_set_direct_hull sph_set_pair_small_launch sph_set_block_order sph_slab_set_early_force
  *   [test hook]    exist for tests and measurement harnesses only: sph_test_trust_mover_hint sph_slab_test_raise_flag
  *                  sph_rccl_transport_selftest sph_loop_transport_create/_destroy sph_memory_stats sph_test_fail_alloc
+ *                  sph_test_scan
  */
 #ifndef SPH_HIP_H
 #define SPH_HIP_H
@@ -1050,6 +1051,10 @@ int sph_slab_set_protocol(sph_slab* s, int groups);
 /* TEST HOOK: the k-th device or pinned allocation the library makes from now on returns the ordinary SPH_E_NOMEM -- a host-side
  * return, taken before any HIP call -- once; then the hook is disarmed.  k = 0 disarms it.  Process-wide. */
 /* [test hook] */ void sph_test_fail_alloc(uint32_t k);
+/* TEST HOOK: the library's one-block prefix sum (every count -> scan -> scatter pipeline uses it) on an array of the caller's:
+ * out[i] = in[0] + ... + in[i - 1] and *total = the sum of all n, in unsigned arithmetic of `bits` (32 or 64) bits, wrap-around
+ * included.  in, out (n values) and total (one) are host memory; n = 0 writes only *total = 0.  Waits for the result. */
+/* [test hook] */ int sph_test_scan(sph_ctx* c, int bits, uint32_t n, const void* in, void* out, void* total);
 /* 0, or the first error of this slab: a slab that failed stays failed -- it has told its neighbours (they return
  * SPH_E_PEER at their next step), every later sph_slab_step returns the same error, and the state of its context is that
  * of a half-done step: download / destroy only */

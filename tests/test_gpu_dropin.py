@@ -130,20 +130,17 @@ def test_morton_golden_through_the_seam():
     assert not L.sph_compat_context(d_aos.data_ptr())
 
 
-def test_seam_integers_at_config_2_in_developed_flow():
-    """The same integer work at BASELINE config 2's size in a developed flow (`c2_flow`: 262,144 particles after 2600 reference
-    steps, cells of 1 .. max_cell particles, chunks of 32): cudaMapZIndex / cudaSortParticles / cudaConstructBGrid /
-    cudaConstructGridArray called directly on device arrays, against the oracle's Morton-mode phases (the oracle is pinned
-    bit-exact to the reference's own code, tests/test_oracle_vs_ref.py): Particle::zindex per particle, the sorted z-index
-    sequence, the WHOLE dev_B table (2,097,152 entries) and dev_B_prime with its size, `array_equal`."""
+def _seam_integers(pos, vel, box, grid):
+    """cudaMapZIndex / cudaSortParticles / cudaConstructBGrid / cudaConstructGridArray called directly on device arrays,
+    against the oracle's Morton-mode phases (the oracle is pinned bit-exact to the reference's own code,
+    tests/test_oracle_vs_ref.py): Particle::zindex per particle, the sorted z-index sequence, the WHOLE dev_B table and
+    dev_B_prime with its size, `array_equal`.  Returns the expected dev_B."""
     import ctypes as C
     import torch
     from gpufluidsimulator_amd import capi
     from oracle import oracle
-    g = load_golden("c2_flow")
-    pos, vel = g["pos"], g["vel"]
-    n, grid, box = pos.shape[0], int(g["grid"][0]), [float(b) for b in g["box"]]
-    o = oracle.Oracle(pos, vel, g["box"], g["grid"], oracle.CELL_MORTON)
+    n, box = pos.shape[0], [float(b) for b in box]
+    o = oracle.Oracle(pos, vel, np.float32(box), np.uint32([grid] * 3), oracle.CELL_MORTON)
     o.map_zindex()
     want_z = o.by_index("zindex").copy()
     o.sort(); o.construct_bgrid(); o.construct_grid_array()
@@ -151,7 +148,6 @@ def test_seam_integers_at_config_2_in_developed_flow():
     want_B = np.stack([o.B["nParticles"], o.B["start"]], axis=1).astype(np.uint32)
     want_Bp = np.stack([o.Bprime["nParticles"], o.Bprime["start"]], axis=1).astype(np.uint32)
     o.close()
-    assert int(g["s1_ncells"]) == int((want_B[:, 0] > 0).sum()) and int(g["s1_max_cell"]) == int(want_B[:, 0].max())   # the fixture's own counts
     L = capi.load()
     aos = np.zeros((n, 22), np.uint32)
     aos[:, 0] = np.arange(n)
@@ -191,3 +187,24 @@ def test_seam_integers_at_config_2_in_developed_flow():
         assert np.array_equal(d_Bp.cpu().numpy().view(np.uint32)[:bp_size.value], want_Bp)
     finally:
         L.sph_compat_release(d_aos.data_ptr())
+    return want_B
+
+
+def test_seam_integers_at_config_2_in_developed_flow():
+    """The seam's integer work at BASELINE config 2's size in a developed flow (`c2_flow`: 262,144 particles after 2600
+    reference steps, cells of 1 .. max_cell particles, chunks of 32; dev_B has 2,097,152 entries)."""
+    g = load_golden("c2_flow")
+    want_B = _seam_integers(g["pos"], g["vel"], g["box"], int(g["grid"][0]))
+    assert int(g["s1_ncells"]) == int((want_B[:, 0] > 0).sum()) and int(g["s1_max_cell"]) == int(want_B[:, 0].max())   # the fixture's own counts
+
+
+def test_seam_integers_past_one_chunk_of_the_tile_scan():
+    """The same with 256 more particles: B' is built from 1025 tiles of 256 slots, one more than the one-block scan of the tile
+    counts takes at a time, so the entries of the last tile sit at the carry of the first 1024.  The 256 are copies of
+    the first 256, moved by a hundredth of a cell: most of them lengthen an occupied cell's list by one."""
+    g = load_golden("c2_flow")
+    box, grid = g["box"], int(g["grid"][0])
+    extra = (g["pos"][:256] + np.float32(0.01) * np.float32(box[0]) / np.float32(grid)).astype(np.float32)
+    pos, vel = np.concatenate([g["pos"], extra]), np.concatenate([g["vel"], g["vel"][:256]])
+    assert pos.shape[0] == 1025 * 256 and np.abs(pos).max() < box[0] / 2
+    _seam_integers(pos, vel, box, grid)

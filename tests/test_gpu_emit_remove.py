@@ -105,6 +105,35 @@ def test_remove_against_the_model_at_small_sizes(n):
     assert n == 1 or 0 < k < n
 
 
+def test_remove_against_the_model_past_one_chunk_of_the_tile_scan():
+    """1025 selection tiles of 2048 slots -- one more than the one-block scan of the tile counts takes at a time, so the last
+    tile's offset is the carry of the first 1024: a 128^3 lattice, one particle per cell of a 128^3 grid, and 64 more in the
+    last cell.  A slice of x selects particles in every tile but the last, a box in the last cell 33 of its 65; the sort
+    needs no step (nothing has moved).  The count, the removed indices and the survivors' order against numpy."""
+    m, n = 128, 128 ** 3 + 64
+    edge = f32(8.0 / m)
+    g = (np.arange(m, dtype=f32) + f32(0.5)) * edge - f32(4.0)                   # cell centres: exact in fp32
+    pos = np.empty((n, 3), f32)
+    pos[:m ** 3] = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)[:, ::-1]
+    pos[m ** 3:] = g[-1] + (np.arange(64, dtype=f32)[:, None] - f32(32.0)) * f32(2.0 ** -12)     # +- 2^-7 around the last centre
+    regions = [("box", (g[5] - edge, -4.0, -4.0), (g[6], 4.0, 4.0)), ("box", (g[-1],) * 3, (4.0, 4.0, 4.0))]
+    with capi.Context(n, box=(8.0, 8.0, 8.0), grid=(m, m, m)) as c:
+        c.upload(pos, np.zeros_like(pos))
+        c.hash(); c.sort(); c.build_cells()
+        p0, v0, i0 = c.download_owned()
+        want = selected(p0, regions)
+        tiles = -(-n // 2048)
+        assert tiles == 1025 and want[:2048].any() and want[1024 * 2048:].any() and not want[1024 * 2048:].all()
+        regs = to_capi(regions)
+        assert c.count_in(regs) == int(want.sum()) == 2 * m * m + 33
+        got = c.remove(regs)
+        assert c.last_removed == int(want.sum()) and c.n == n - int(want.sum())
+        assert np.array_equal(got, i0[want])
+        p1, v1, i1 = c.download_owned()
+        assert np.array_equal(i1, i0[~want]) and _same(p1, p0[~want]) and _same(v1, v0[~want])
+        assert c.count_in(regs) == 0
+
+
 # ---- patterns: regions that cover exact cells ----------------------------------------------------------------------------
 EDGE = f32(2.0 / 32)
 

@@ -938,6 +938,39 @@ def test_recut_by_several_layers_in_hops_and_into_an_empty_slab():
     assert all(o[4]["host_waits"] == o[4]["steps"] + o[4]["far_steps"] for o in out)
 
 
+def test_recut_of_slabs_past_one_chunk_of_the_block_scan():
+    """sph_slab_recut partitions a rank's owned range in blocks of 1024 slots and scans the per-block {down, up} counts in one
+    workgroup, 1024 blocks at a time.  Two slabs of 36 cell layers x 32,768 particles = 1,179,648 each, 1152 blocks: the
+    second chunk of the scan starts at the carry of the first.  A slab has ONE neighbour here, so the two directions take two
+    re-cuts: the cut goes up by three layers (slab 1 sends down, from its first blocks: the carry is all of them), then
+    down by five (slab 0, now 1248 blocks, sends up, from its last blocks).  Bit for bit the one-context run."""
+    cfg = ic.CONFIGS["C2"]
+    box, grid, lattice = cfg["box"], cfg["grid"], (128, 128, 144)
+    moves = [3, -5]
+
+    def body(make, r):
+        sim = make(box=box, grid=grid, lattice=lattice)
+        try:
+            cut0, owned = sim.cuts[1], [sim.engine.n]
+            for k in range(len(moves)):
+                sim.run(DT, 2)
+                assert sim.rebalance(cuts=[0, cut0 + sum(moves[:k + 1]), grid[2]])
+                owned.append(sim.engine.n)
+            sim.run(DT, 2)
+            sim.sync()
+            return sim.gather_state(), owned, cut0
+        finally:
+            sim.close()
+
+    out, errors = _with_ranks(2, body, timeout_s=300)
+    assert errors == [None] * 2, errors
+    total, (below, above) = 128 * 128 * 144, (out[0][1], out[1][1])
+    assert all(a + b == total for a, b in zip(below, above)) and below[0] < below[1] > below[2], (below, above)
+    assert above[0] > 1024 * 1024 and below[1] > 1024 * 1024, "the slab that sends has more than 1024 blocks"
+    pos, vel = ic.dam_break_lattice(lattice, box, jitter=True)
+    _same_bits(out[0][0], _whole_domain(pos, vel, box, grid, 2 * (len(moves) + 1)))
+
+
 def test_recut_under_the_one_message_step():
     """sph_slab_recut with the one-message protocol: cuts moved by hand (slabs of >= 4 layers: a thinner one is SPH_E_INVALID
     there), steps in between -- each re-cut is followed by one three-group step that learns the message sizes again."""
