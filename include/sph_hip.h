@@ -268,7 +268,10 @@ int sph_get_colliders(const sph_ctx* c, uint32_t* n, sph_collider* out);
  * projection, not the wall pass that follows it -- and the particle rule itself does not change by one bit.  The order of the
  * sum is fixed (lanes of a 64-slot wave in ascending order, then waves in ascending order within 256 equal runs of waves, then
  * the runs in ascending order): two runs of the same calls give the same bits in J, in the centres and in every particle.  No
- * floating-point atomic is involved.
+ * floating-point atomic is involved.  A run is K = ceil(waves / 256) rounded up to a multiple of 4 waves long, waves =
+ * ceil(owned particles / 64): run t is the waves [t K, min((t + 1) K, waves)), so the last run that holds a wave may be short
+ * and the runs behind it are empty.  Every partial sum starts at 0.0 -- a wave's sum for sphere j (only a wave in which j kicked
+ * a lane has one), a run's sum of its waves' sums, and J_j over the runs that hold any wave's sum for any sphere.
  *
  * Sensor.  sph_get_collider_impulses synchronises the context's stream and returns J of the LAST integrate (3 doubles per
  * sphere) and the number of integrates since tracking began; J / dt is the force on an obstacle.  It works for kinematic spheres

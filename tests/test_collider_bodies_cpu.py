@@ -1,13 +1,13 @@
 """CPU: the numpy model of the tracked sphere colliders (tests/collider_body_model.py, include/sph_hip.h:
-sph_set_collider_bodies) -- the impulse is the momentum the fluid lost, the body update, and the headless driver's
--collidermass flag in its help text."""
+sph_set_collider_bodies) -- the impulse is the momentum the fluid lost, the body update, the sum of the terms in the
+device's order (impulse_sum_in_order, run_length), and the headless driver's -collidermass flag in its help text."""
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from collider_body_model import body_update, impulses, terms_one
+from collider_body_model import body_update, impulse_sum_in_order, impulses, run_length, terms_one, thread_sums
 from collider_model import advance, push, push_one
 
 F = np.float32
@@ -93,6 +93,76 @@ def test_mass_zero_reproduces_advance():
         cur_c, cur_u = body_update(cur_c, cur_u, np.array([1e6, 1e6, 1e6]), 0.0, (0.0, -9.0, 0.0), 0.1, 5e-7, BMIN, BMAX)
     assert np.array_equal(cur_u, u)
     assert np.array_equal(cur_c, advance([c], [u], 5e-7, 5)[0])
+
+
+def _synthetic(n, nsph, seed, every=5):
+    """Terms that are small integers times 2^-10 on every `every`-th slot and sphere (j + slot) % 3 == 0: any float64 sum
+    of them is exact, whatever its order."""
+    rng = np.random.default_rng(seed)
+    terms = (rng.integers(-1000, 1001, (n, nsph, 3)) * 2.0 ** -10).astype(F)
+    kicked = np.zeros((n, nsph), bool)
+    for j in range(nsph):
+        kicked[(np.arange(n) + j) % every == 0, j] = True
+    kicked[:, nsph - 1] = False                              # a sphere that kicks nothing
+    terms[~kicked] = 0
+    return terms, kicked
+
+
+@pytest.mark.parametrize("n", [37, 64, 4096 + 37, 65536, 65573, 131100])
+def test_the_ordered_sum_of_exact_terms_is_the_plain_sum(n):
+    terms, kicked = _synthetic(n, 8, n)
+    J = impulse_sum_in_order(terms, kicked, n)
+    want = terms.astype(np.float64).sum(axis=0)
+    assert J.shape == (8, 3) and J.dtype == np.float64
+    assert np.array_equal(J.view(np.uint64), want.view(np.uint64))
+    assert np.abs(J[:7]).min() > 0 and not J[7].any() and not np.signbit(J[7]).any()
+    assert np.array_equal(impulse_sum_in_order(terms, kicked, n, runs_descending=True), J)
+    # a term of a lane that was not kicked is not part of the sum
+    terms[~kicked] = 7.0
+    assert np.array_equal(impulse_sum_in_order(terms, kicked, n), J)
+
+
+def test_the_order_of_the_runs_can_be_seen_in_the_bits():
+    n = 65573
+    rng = np.random.default_rng(3)
+    mag = 2.0 ** rng.uniform(-20, 20, (n, 1, 3))             # 2^40 between the smallest and the largest: well past 2^30
+    terms = (mag * rng.choice([-1.0, 1.0], (n, 1, 3))).astype(F)
+    kicked = np.zeros((n, 1), bool)
+    kicked[::7] = True
+    up = impulse_sum_in_order(terms, kicked, n)
+    down = impulse_sum_in_order(terms, kicked, n, runs_descending=True)
+    assert (up.view(np.uint64) != down.view(np.uint64)).any(), (up, down)
+    assert np.allclose(up, down, rtol=1e-9, atol=0)          # (the same sum, to rounding)
+    plain = np.array([sum(float(x) for x in terms[kicked[:, 0], 0, a]) for a in range(3)])     # one running sum, slot by slot
+    assert np.allclose(up[0], plain, rtol=1e-9, atol=0)
+
+
+def test_run_length():
+    assert [run_length(n) for n in (64, 65536, 65537, 131100)] == [4, 4, 8, 12]
+    assert [run_length(n) for n in (1, 63, 4096, 65573, 131072, 131073, 196608, 196609)] == [4, 4, 4, 8, 8, 12, 12, 16]
+
+
+def test_a_run_that_starts_beyond_the_waves_contributes_nothing():
+    n = 65573                                                # 1,025 waves, K = 8: threads 0..128 own waves, 129..255 none
+    terms, kicked = _synthetic(n, 2, 1, every=1)
+    kicked[:, 1] = kicked[:, 0]
+    acc, found = thread_sums(terms, kicked, n)
+    assert found[:129].all() and not found[129:].any() and not acc[129:].any()
+    # thread 128 holds the one short wave of 37 lanes, lane by lane
+    last = np.zeros(3)
+    for i in range(1024 * 64, n):
+        last = last + terms[i, 0].astype(np.float64)
+    assert np.array_equal(acc[128, 0], last)
+    # the last run short, not empty: 131,100 slots are 2,049 waves, K = 12, thread 170 owns the 9 waves 2040..2048
+    n = 131100
+    kicked = np.zeros((n, 1), bool)
+    kicked[[0, 2039 * 64 + 63, 2040 * 64, n - 1]] = True
+    terms = np.zeros((n, 1, 3), F)
+    terms[kicked[:, 0]] = [[[1, 2, 3]], [[10, 20, 30]], [[100, 200, 300]], [[1000, 2000, 3000]]]
+    acc, found = thread_sums(terms, kicked, n)
+    assert list(np.nonzero(found)[0]) == [0, 169, 170]
+    assert np.array_equal(acc[170, 0], [1100, 2200, 3300]) and np.array_equal(acc[169, 0], [10, 20, 30])
+    assert np.array_equal(impulse_sum_in_order(terms, kicked, n)[0], [1111, 2222, 3333])
 
 
 def test_headless_help_names_the_collidermass_flag():

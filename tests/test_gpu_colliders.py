@@ -28,13 +28,10 @@ def _dam():
     return ic.dam_break_lattice((16, 16, 16), BOX, jitter=True)
 
 
-def _ulp(a):
-    return np.spacing(np.abs(a).astype(F)).astype(np.float64)
-
-
 def _check_one_step(stepper):
     """One step of a context with a sphere (A) against one without (B), from the same upload: the particles the sphere
-    does not touch keep every bit, the touched ones are the model applied to B's output."""
+    does not touch keep every bit, the touched ones are the model applied to B's output, bit for bit (the rule is + - * /
+    and sqrt on fp32, unfused: tests/test_gpu_collider_sums.py holds eight spheres to the same)."""
     pos, vel = _dam()
     c0, R, u = np.array([-1.75, -1.72, -1.74], F), F(0.1875), np.array([300.0, -150.0, 80.0], F)   # R = 3 cells, inside
     with capi.Context(pos.shape[0], box=BOX, grid=GRID) as a, capi.Context(pos.shape[0], box=BOX, grid=GRID) as b:
@@ -44,30 +41,33 @@ def _check_one_step(stepper):
         sa, sb = a.download(), b.download()
         assert np.array_equal(a.colliders()["centers"][0], (c0 + F(DT) * u).astype(F))
     want_p, want_v, touched = push(sb["pos"], sb["vel"], [c0], [R], [u], (-2, -2, -2), (2, 2, 2))
-    d = sb["pos"].astype(F) - c0
-    r2 = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]
-    rp2 = F(R + EPS) ** 2
-    tie = np.abs(r2.astype(np.float64) - rp2) <= 1e-6 * rp2
-    assert tie.sum() <= 3, tie.sum()
     assert touched.sum() >= 100, touched.sum()
-    keep = ~touched & ~tie
     for k in ("pos", "vel", "density", "pressure"):
-        assert np.array_equal(sa[k][keep].view(np.uint32), sb[k][keep].view(np.uint32)), k
-    t = touched & ~tie
-    assert np.abs(sa["pos"][t] - want_p[t]).max() <= 1e-6 * 4.0
-    vmax = float(np.abs(sa["vel"]).max())
-    assert (np.abs(sa["vel"][t].astype(np.float64) - want_v[t]) <= 1e-6 * vmax + _ulp(want_v[t])).all()
-    return sa, tie
+        assert np.array_equal(sa[k][~touched].view(np.uint32), sb[k][~touched].view(np.uint32)), k
+    assert np.array_equal(sa["pos"].view(np.uint32), want_p.view(np.uint32))
+    assert np.array_equal(sa["vel"].view(np.uint32), want_v.view(np.uint32))
+    return sa, sb, (c0, R)
 
 
 def test_fused_step_against_the_model():
     _check_one_step(lambda c: c.step(DT, 1))
 
 
+def _at_the_shell(sb, c0, R):
+    """Particles whose distance from c0 is within 1e-6 of R + eps before the push (at most 3, usually none): the two step
+    forms agree to a tolerance there, so one of them may push such a particle and the other not."""
+    d = sb["pos"].astype(F) - c0
+    r2 = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]
+    rp2 = F(R + EPS) ** 2
+    tie = np.abs(r2.astype(np.float64) - rp2) <= 1e-6 * rp2
+    assert tie.sum() <= 3, tie.sum()
+    return tie
+
+
 def test_phased_step_against_the_model_and_the_fused_step():
-    sp, tie_p = _check_one_step(lambda c: c.step_phased(DT, 1))
-    sf, tie_f = _check_one_step(lambda c: c.step(DT, 1))
-    ok = ~(tie_p | tie_f)
+    sp, bp, (c0, R) = _check_one_step(lambda c: c.step_phased(DT, 1))
+    sf, bf, _ = _check_one_step(lambda c: c.step(DT, 1))
+    ok = ~(_at_the_shell(bp, c0, R) | _at_the_shell(bf, c0, R))
     # the tolerances of test_gpu_parity.py::test_fused_step_equals_phased_step
     assert np.abs(sf["pos"][ok] - sp["pos"][ok]).max() <= 1e-7 * 4
     assert np.abs(sf["vel"][ok].astype(np.float64) - sp["vel"][ok]).max() <= 2e-6 * np.abs(sp["vel"]).max()
