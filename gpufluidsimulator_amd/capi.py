@@ -264,6 +264,8 @@ SIGNATURES = {
     "sph_test_trust_mover_hint": (C.c_int, [_P]),
     "sph_memory_stats": (None, [C.POINTER(C.c_uint64)]),
     "sph_test_fail_alloc": (None, [C.c_uint32]),
+    "sph_test_guard": (None, [C.c_uint32, C.c_int]),
+    "sph_test_guard_check": (C.c_int, [C.POINTER(C.c_uint64)]),
     "sph_test_scan": (C.c_int, [_P, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sph_set_precision": (C.c_int, [_P, C.c_int]),
     "sph_get_precision": (C.c_int, [_P]),
@@ -362,6 +364,20 @@ def memory_stats():
 def fail_alloc(k):
     """Test hook: the k-th allocation from now fails with SPH_E_NOMEM, once; 0 disarms."""
     load().sph_test_fail_alloc(int(k))
+
+
+def guard(band_bytes, fill=False):
+    """Test hook: bands of `band_bytes` (a multiple of 4096; 0: off) around every allocation from now on, filled with a pattern;
+    fill=True puts the pattern into every range the library does not clear as well."""
+    load().sph_test_guard(int(band_bytes), 1 if fill else 0)
+
+
+def guard_check():
+    """Test hook: (buffers checked, buffers damaged, user bytes of the first damaged one, byte offset of its first damaged word:
+    < 0 in front of the user range, >= 0 from its end) over every guarded buffer, live or freed since the last check; repairs."""
+    out = (C.c_uint64 * 4)()
+    _check(load().sph_test_guard_check(out))
+    return int(out[0]), int(out[1]), int(out[2]), C.c_int64(out[3]).value
 
 
 def default_params(box, grid) -> Params:

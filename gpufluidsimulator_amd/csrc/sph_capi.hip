@@ -7,7 +7,9 @@
 #include <cstdarg>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <new>
+#include <vector>
 
 namespace sph {
 
@@ -30,6 +32,107 @@ static int test_scan(sph_ctx* c, Buffers& mem, uint32_t n, const void* in, void*
     if (n) SPH_HIP(hipMemcpyAsync(out, d_out, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, c->stream));
     SPH_HIP(hipMemcpyAsync(total, d_total, sizeof(T), hipMemcpyDeviceToHost, c->stream));
     SPH_HIP(hipStreamSynchronize(c->stream));
+    return SPH_OK;
+}
+
+// ---- [test hook] sph_test_guard / sph_test_guard_check: the bands Buffers::take puts around every allocation while the mode is on ----
+// A guarded allocation is [band][the caller's bytes, rounded up to a word][band]; word w of it, counted from the base, holds
+// guard_word(w).  The registry holds every live guarded buffer of every owner (slab ranks allocate on their own threads: the lock);
+// what guard_retire finds in a buffer that is freed stays latched until the next check.
+struct GuardRec { char* user; size_t bytes; uint32_t band; bool pinned; int device; };
+struct GuardReport { uint64_t checked = 0, damaged = 0, first_bytes = 0; int64_t first_off = 0; };
+static std::mutex g_guard_lock;
+static std::vector<GuardRec> g_guard_live;
+static GuardReport g_guard_freed;
+
+__global__ void k_guard_fill(uint32_t* __restrict__ p, uint64_t words, uint64_t w0) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (uint64_t)gridDim.x * blockDim.x) p[i] = guard_word(w0 + i);
+}
+
+// words [w0, w0 + words) of the allocation at `base` get the pattern (device memory: on the null stream, waited for)
+static int guard_fill(char* base, uint64_t w0, uint64_t words, bool pinned) {
+    if (!words) return 0;
+    uint32_t* p = (uint32_t*)base + w0;
+    if (pinned) {
+        for (uint64_t i = 0; i < words; i++) p[i] = guard_word(w0 + i);
+        return 0;
+    }
+    const uint64_t blocks = (words + 255u) / 256u;
+    k_guard_fill<<<(uint32_t)(blocks < 4096u ? blocks : 4096u), 256, 0, 0>>>(p, words, w0);
+    return hipGetLastError() != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess;
+}
+
+int guard_adopt(void* base, size_t bytes, uint32_t band, bool pinned, bool fill) {
+    const uint64_t bw = band / 4u, uw = (bytes + 3u) / 4u;
+    int dev = 0;
+    hipGetDevice(&dev);
+    if (guard_fill((char*)base, 0, fill ? bw + uw + bw : bw, pinned)) return 1;
+    if (!fill && guard_fill((char*)base, bw + uw, bw, pinned)) return 1;
+    std::lock_guard<std::mutex> hold(g_guard_lock);
+    g_guard_live.push_back(GuardRec{(char*)base + band, bytes, band, pinned, dev});
+    return 0;
+}
+
+// compares both bands of one buffer with the pattern, adds what it finds to `rep` and, with `repair`, writes the pattern back;
+// the caller has waited for the device
+static void guard_check_one(const GuardRec& r, GuardReport& rep, bool repair, std::vector<uint32_t>& tmp) {
+    const uint64_t bw = r.band / 4u, uw = (r.bytes + 3u) / 4u;
+    char* base = r.user - r.band;
+    rep.checked++;
+    int64_t first = 0;
+    bool bad = false;
+    for (int side = 0; side < 2; side++) {
+        const uint64_t w0 = side ? bw + uw : 0;
+        const uint32_t* got = (const uint32_t*)base + w0;
+        if (!r.pinned) {
+            tmp.resize(bw);
+            if (hipMemcpy(tmp.data(), got, bw * 4u, hipMemcpyDeviceToHost) != hipSuccess) { bad = true; first = side ? 0 : -(int64_t)r.band; break; }
+            got = tmp.data();
+        }
+        bool side_bad = false;
+        for (uint64_t i = 0; i < bw; i++) {
+            if (got[i] == guard_word(w0 + i)) continue;
+            if (!bad) first = (int64_t)((w0 + i) * 4u) - (int64_t)r.band - (side ? (int64_t)r.bytes : 0);
+            bad = side_bad = true;
+            break;
+        }
+        if (side_bad && repair) guard_fill(base, w0, bw, r.pinned);
+    }
+    if (bad && rep.damaged++ == 0) { rep.first_bytes = r.bytes; rep.first_off = first; }
+}
+
+void guard_retire(void* user, size_t bytes, uint32_t band, bool pinned) {
+    hipDeviceSynchronize();     // (what still writes into the buffer has to finish: hipFree would wait for it as well)
+    std::vector<uint32_t> tmp;
+    std::lock_guard<std::mutex> hold(g_guard_lock);
+    for (size_t k = g_guard_live.size(); k-- > 0;)
+        if (g_guard_live[k].user == (char*)user) {
+            guard_check_one(g_guard_live[k], g_guard_freed, false, tmp);
+            g_guard_live.erase(g_guard_live.begin() + k);
+            break;
+        }
+}
+
+// every live guarded buffer and what was freed since the last check: out = {checked, damaged, bytes of the first damaged one,
+// offset of its first damaged word}; repairs what it reports
+static int guard_check_all(uint64_t out[4]) {
+    int dev0 = 0, cur;
+    SPH_HIP(hipGetDevice(&dev0));
+    cur = dev0;
+    std::vector<uint32_t> tmp;
+    std::lock_guard<std::mutex> hold(g_guard_lock);
+    GuardReport rep = g_guard_freed;
+    g_guard_freed = GuardReport{};
+    SPH_HIP(hipDeviceSynchronize());
+    for (const GuardRec& r : g_guard_live) {
+        if (r.device != cur) {
+            SPH_HIP(hipSetDevice(cur = r.device));
+            SPH_HIP(hipDeviceSynchronize());
+        }
+        guard_check_one(r, rep, true, tmp);
+    }
+    if (cur != dev0) SPH_HIP(hipSetDevice(dev0));
+    out[0] = rep.checked; out[1] = rep.damaged; out[2] = rep.first_bytes; out[3] = (uint64_t)rep.first_off;
     return SPH_OK;
 }
 
@@ -1103,6 +1206,20 @@ void sph_memory_stats(uint64_t out[3]) {
 
 // [test hook] the k-th allocation from now returns SPH_E_NOMEM without calling HIP, once; 0 disarms
 void sph_test_fail_alloc(uint32_t k) { g_fail_alloc.store(k); }
+
+// [test hook] guard bands of `band_bytes` (a multiple of 4096; 0: none) around every allocation from now on; with `fill_unzeroed`
+// the pattern also goes into every range the library does not clear.  Process-wide; buffers keep the bands they were given.
+void sph_test_guard(uint32_t band_bytes, int fill_unzeroed) {
+    if (band_bytes % 4096u) { set_error("guard bands of %u bytes: not a multiple of 4096", band_bytes); return; }
+    g_guard_fill.store(band_bytes && fill_unzeroed ? 1u : 0u);
+    g_guard_band.store(band_bytes);
+}
+
+// [test hook] waits for the device and compares the bands of every guarded buffer, live or freed since the last check
+int sph_test_guard_check(uint64_t out[4]) {
+    SPH_REQUIRE(out, SPH_E_INVALID, "null argument");
+    return guard_check_all(out);
+}
 
 // [test hook] the exclusive prefix sums of `n` host values of `bits` (32 or 64) bits and their total, by the one-block scan
 int sph_test_scan(sph_ctx* c, int bits, uint32_t n, const void* in, void* out, void* total) {

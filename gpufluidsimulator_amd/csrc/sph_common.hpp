@@ -93,8 +93,19 @@ void set_error(const char* fmt, ...);
 // grows).  The four HIP allocation calls appear nowhere else in the library.
 inline std::atomic<uint64_t> g_mem_stats[3];   // live device bytes, live pinned bytes, live buffers (sph_memory_stats)
 inline std::atomic<uint32_t> g_fail_alloc{0};  // [test hook] sph_test_fail_alloc: the k-th allocation from now fails, once
+// [test hook] sph_test_guard: while g_guard_band is not 0, every allocation gets a band of that many bytes in front of the
+// caller's range and another behind it, both filled with guard_word; with g_guard_fill the range itself gets the pattern too
+// unless it is zeroed.  sph_test_guard_check compares the bands of every guarded buffer (sph_capi.hip has the registry).
+inline std::atomic<uint32_t> g_guard_band{0};
+inline std::atomic<uint32_t> g_guard_fill{0};
+// word `w` of a guarded allocation, counted from its base pointer (the trailing band starts at the next word boundary behind the
+// caller's bytes): 1 .. 511, a subnormal as fp32, and no two words a small distance apart hold the same sequence
+__host__ __device__ inline uint32_t guard_word(uint64_t w) { return 1u + (uint32_t)((w + 7u * (w >> 8)) % 511u); }
+int guard_adopt(void* base, size_t bytes, uint32_t band, bool pinned, bool fill);   // fills, registers; nonzero: HIP failed
+void guard_retire(void* user, size_t bytes, uint32_t band, bool pinned);            // checks the bands, latches, unregisters
+
 struct Buffers {
-    struct Rec { void* p; size_t bytes; bool pinned; };
+    struct Rec { void* p; size_t bytes; bool pinned; uint32_t band; };   // band: guard bytes on either side of p (0: none)
     std::vector<Rec> live;
     Buffers() = default;
     Buffers(const Buffers&) = delete;
@@ -102,7 +113,7 @@ struct Buffers {
     // `count` elements of device memory (0: one element), as zeros if `zero`
     template <class T> int alloc(T** p, size_t count, bool zero) {
         const size_t bytes = (count ? count : 1) * sizeof(T);
-        int rc = take((void**)p, bytes, false, false);
+        int rc = take((void**)p, bytes, false, false, !zero);
         if (rc || !zero || hipMemset((void*)*p, 0, bytes) == hipSuccess) return rc;
         release(p);
         set_error("hipMemset of %zu bytes failed", bytes);
@@ -110,7 +121,7 @@ struct Buffers {
     }
     // pinned host memory; with `dev_view` it is mapped, and *dev_view is the device's pointer to it
     template <class T> int alloc_host(T** p, size_t count, T** dev_view = nullptr) {
-        int rc = take((void**)p, count * sizeof(T), true, dev_view != nullptr);
+        int rc = take((void**)p, count * sizeof(T), true, dev_view != nullptr, true);
         if (rc || !dev_view || hipHostGetDevicePointer((void**)dev_view, (void*)*p, 0) == hipSuccess) return rc;
         release(p);
         set_error("hipHostGetDevicePointer failed");
@@ -126,24 +137,38 @@ struct Buffers {
     }
 
 private:
-    int take(void** p, size_t bytes, bool pinned, bool mapped) {
+    // `unzeroed`: the caller does not clear the range (what the guard mode's second flag fills with the pattern)
+    int take(void** p, size_t bytes, bool pinned, bool mapped, bool unzeroed) {
         const char* fn = !pinned ? "hipMalloc" : mapped ? "hipHostMalloc(mapped)" : "hipHostMalloc";
         *p = nullptr;
         uint32_t k = g_fail_alloc.load();
         while (k && !g_fail_alloc.compare_exchange_weak(k, k - 1)) {}
+        const uint32_t band = g_guard_band.load();
+        const size_t total = band ? ((bytes + 3) & ~(size_t)3) + 2 * (size_t)band : bytes;
         const hipError_t e = k == 1 ? hipErrorOutOfMemory
-                           : pinned ? hipHostMalloc(p, bytes, mapped ? hipHostMallocMapped : hipHostMallocDefault) : hipMalloc(p, bytes);
+                           : pinned ? hipHostMalloc(p, total, mapped ? hipHostMallocMapped : hipHostMallocDefault) : hipMalloc(p, total);
         if (e != hipSuccess) {
             *p = nullptr;
             set_error("%s of %zu bytes failed: %s", fn, bytes, hipGetErrorString(e));
             return SPH_E_NOMEM;
         }
-        live.push_back(Rec{*p, bytes, pinned});
+        if (band) {
+            if (guard_adopt(*p, bytes, band, pinned, unzeroed && g_guard_fill.load())) {
+                if (pinned) hipHostFree(*p); else hipFree(*p);
+                *p = nullptr;
+                set_error("the guard bands of %zu bytes could not be written", bytes);
+                return SPH_E_DEVICE;
+            }
+            *p = (char*)*p + band;
+        }
+        live.push_back(Rec{*p, bytes, pinned, band});
         g_mem_stats[pinned] += bytes; g_mem_stats[2] += 1;
         return SPH_OK;
     }
     static void drop(const Rec& r) {
-        if (r.pinned) hipHostFree(r.p); else hipFree(r.p);
+        void* base = r.p;
+        if (r.band) { guard_retire(r.p, r.bytes, r.band, r.pinned); base = (char*)r.p - r.band; }
+        if (r.pinned) hipHostFree(base); else hipFree(base);
         g_mem_stats[r.pinned] -= r.bytes; g_mem_stats[2] -= 1;
     }
 };

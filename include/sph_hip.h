@@ -50,7 +50,7 @@
  *                  sph_set_sort_mode sph_set_direct_hull sph_set_pair_small_launch sph_set_block_order sph_slab_set_early_force
  *   [test hook]    exist for tests and measurement harnesses only: sph_test_trust_mover_hint sph_slab_test_raise_flag
  *                  sph_rccl_transport_selftest sph_loop_transport_create/_destroy sph_memory_stats sph_test_fail_alloc
- *                  sph_test_scan
+ *                  sph_test_scan sph_test_guard sph_test_guard_check
  */
 #ifndef SPH_HIP_H
 #define SPH_HIP_H
@@ -1058,6 +1058,17 @@ int sph_slab_set_protocol(sph_slab* s, int groups);
  * out[i] = in[0] + ... + in[i - 1] and *total = the sum of all n, in unsigned arithmetic of `bits` (32 or 64) bits, wrap-around
  * included.  in, out (n values) and total (one) are host memory; n = 0 writes only *total = 0.  Waits for the result. */
 /* [test hook] */ int sph_test_scan(sph_ctx* c, int bits, uint32_t n, const void* in, void* out, void* total);
+/* TEST HOOK: guarded allocations.  While band_bytes (a multiple of 4096; any other value is refused and changes nothing) is not 0,
+ * every device, pinned and mapped allocation the library makes has a band of that many bytes in front of the caller's range and
+ * another behind it, filled with a pattern of 32-bit words: nonzero, below 512 (a subnormal as fp32) and varying with the position.
+ * With fill_unzeroed the pattern also fills every range the library does not clear itself.  0 bytes: off for the allocations from
+ * now on; a buffer keeps the bands it was given, and sph_memory_stats counts the caller's bytes in either mode.  Process-wide. */
+/* [test hook] */ void sph_test_guard(uint32_t band_bytes, int fill_unzeroed);
+/* TEST HOOK: waits for the device, compares both bands of every live guarded buffer of every owner, adds what the buffers freed
+ * since the last check showed when they were freed, and writes the pattern back where it was damaged (the next check is clean).
+ * out = {buffers checked, buffers damaged, the caller's bytes of the first damaged one, the byte offset of its first damaged word
+ * as an int64: < 0 in front of the caller's range, >= 0 counted from its end}. */
+/* [test hook] */ int sph_test_guard_check(uint64_t out[4]);
 /* 0, or the first error of this slab: a slab that failed stays failed -- it has told its neighbours (they return
  * SPH_E_PEER at their next step), every later sph_slab_step returns the same error, and the state of its context is that
  * of a half-done step: download / destroy only */

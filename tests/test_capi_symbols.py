@@ -23,6 +23,7 @@ def test_library_builds_and_exports_the_header():
     lib = capi.load()
     names = _declared("sph_hip.h")
     assert len(names) >= 40
+    assert "sph_test_guard" in names and "sph_test_guard_check" in names
     for n in names:
         assert hasattr(lib, n), f"{n} declared in include/sph_hip.h but not exported"
         assert n in capi.SIGNATURES, f"{n} has no ctypes signature in capi.py"
