@@ -267,6 +267,7 @@ SIGNATURES = {
     "sph_test_guard": (None, [C.c_uint32, C.c_int]),
     "sph_test_guard_check": (C.c_int, [C.POINTER(C.c_uint64)]),
     "sph_test_scan": (C.c_int, [_P, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sph_test_lower_bounds": (C.c_int, [_P, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
     "sph_set_precision": (C.c_int, [_P, C.c_int]),
     "sph_get_precision": (C.c_int, [_P]),
     "sph_migrants_count": (C.c_int, [_P, C.POINTER(_U32)]),
@@ -924,6 +925,15 @@ class Context:
         out, total = np.empty_like(v), np.zeros(1, v.dtype)
         _check(self.L.sph_test_scan(self.h, 8 * v.dtype.itemsize, v.size, v.ctypes.data, out.ctypes.data, total.ctypes.data))
         return out, total[0]
+
+    def test_lower_bounds(self, keys, targets):
+        """Test hook: for each of up to 32 uint32 targets, the first index of the sorted uint32 `keys` whose key is >= it (len(keys)
+        if there is none), by the library's lower-bounds kernel."""
+        k, t = np.ascontiguousarray(keys), np.ascontiguousarray(targets)
+        assert k.ndim == 1 and t.ndim == 1 and k.dtype == np.uint32 and t.dtype == np.uint32, (k.dtype, t.dtype)
+        out = np.empty(t.size, np.uint32)
+        _check(self.L.sph_test_lower_bounds(self.h, k.ctypes.data, k.size, t.ctypes.data, t.size, out.ctypes.data))
+        return out
 
     def sort_forms(self):
         """Movers' sorts launched as (both forms, one-block sort alone, multi-block passes alone)."""

@@ -35,6 +35,18 @@ static int test_scan(sph_ctx* c, Buffers& mem, uint32_t n, const void* in, void*
     return SPH_OK;
 }
 
+// [test hook] sph_test_lower_bounds: the lower-bounds kernel of the slab messages (sph_halo.hip) on keys of the caller's
+static int test_lower_bounds(sph_ctx* c, Buffers& mem, const uint32_t* keys, uint32_t n, const LbTargets& tg, uint32_t* out) {
+    uint32_t *d_keys = nullptr, *d_out = nullptr;
+    int rc;
+    if ((rc = mem.alloc(&d_keys, n, false)) || (rc = mem.alloc(&d_out, LB_MAX, false))) return rc;
+    if (n) SPH_HIP(hipMemcpyAsync(d_keys, keys, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if ((rc = launch_lower_bounds(c->stream, d_keys, n, tg, d_out, nullptr))) return rc;
+    if (tg.m) SPH_HIP(hipMemcpyAsync(out, d_out, tg.m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    SPH_HIP(hipStreamSynchronize(c->stream));
+    return SPH_OK;
+}
+
 // ---- [test hook] sph_test_guard / sph_test_guard_check: the bands Buffers::take puts around every allocation while the mode is on ----
 // A guarded allocation is [band][the caller's bytes, rounded up to a word][band]; word w of it, counted from the base, holds
 // guard_word(w).  The registry holds every live guarded buffer of every owner (slab ranks allocate on their own threads: the lock);
@@ -1228,6 +1240,20 @@ int sph_test_scan(sph_ctx* c, int bits, uint32_t n, const void* in, void* out, v
     SPH_HIP(hipSetDevice(c->device));
     Buffers mem;
     const int rc = bits == 32 ? test_scan<uint32_t>(c, mem, n, in, out, total) : test_scan<uint64_t>(c, mem, n, in, out, total);
+    mem.free_all();
+    return rc;
+}
+
+// [test hook] out[k] = the first index of the caller's sorted keys[0, n) with keys[i] >= targets[k], k < m <= 32: the shared
+// lower-bounds kernel of the slab messages (launch_lower_bounds, sph_halo.hip; first_not, sph_device.hpp) and nothing else
+int sph_test_lower_bounds(sph_ctx* c, const uint32_t* keys, uint32_t n, const uint32_t* targets, uint32_t m, uint32_t* out) {
+    SPH_REQUIRE(c && (n == 0 || keys) && (m == 0 || (targets && out)), SPH_E_INVALID, "null argument");
+    SPH_REQUIRE(m <= LB_MAX, SPH_E_INVALID, "%u targets: at most %u", m, LB_MAX);
+    SPH_HIP(hipSetDevice(c->device));
+    LbTargets tg{{}, m};
+    for (uint32_t k = 0; k < m; k++) tg.v[k] = targets[k];
+    Buffers mem;
+    const int rc = test_lower_bounds(c, mem, keys, n, tg, out);
     mem.free_all();
     return rc;
 }

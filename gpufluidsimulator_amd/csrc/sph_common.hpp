@@ -25,7 +25,7 @@ constexpr uint32_t SORT_TILE_KEYS = 256 * SPH_SORT_KPT;   // keys per radix-sort
 #define SPH_PAIR_SMALL_SLOTS_DEFAULT 524288u
 #endif
 constexpr uint32_t MM_TILE_CHUNKS = 256;   // merge sort: 64-slot chunks per scan tile (sph_sort.hip)
-constexpr uint32_t SCRATCH_WORDS = 64;     // words of a context's d_scratch / h_scratch pair (counts; sph_halo.hip splits it in halves)
+constexpr uint32_t SCRATCH_WORDS = 64;     // words of a context's d_scratch / h_scratch pair (counts; the answers of sph_halo.hip's lower bounds)
 
 // Grid description passed by value to kernels (replaces the device-resident SimParams*
 // every reference kernel dereferences, particleSystem.cu:93-103,127-130).
@@ -489,6 +489,28 @@ void release_obstacle(sph_ctx* c);
 // tracked contexts (sph_pairs.hip): write the host's sphere set into trk_table and zero J and the step count; refresh R + eps
 int launch_spheres_install(sph_ctx* c);
 int launch_spheres_radii(sph_ctx* c);
+// the kernels of a slab's messages (sph_halo.hip), shared by the phase API there and the slab step (sph_slab.hip), which queues them
+// on the context's stream, its comm stream or whichever of the two packs: the stream is the caller's.  No launch for no work.
+// One side of a message: n records (put_record / get_record, sph_device.hpp) and the slots they are packed from or unpacked to
+struct RecSide { float4* rec; float4* posi; float4* velr; uint32_t* key; uint32_t n; };
+int launch_pack_records(hipStream_t st, const RecSide& lo, const RecSide& hi);      // (key: not used)
+// records -> slots; with a key pointer also their cell keys; with `err_word` a record whose cell is not in an owned layer of `g` --
+// the local layers [G, zl - G) -- sets that mapped host word to 1
+int launch_unpack_records(hipStream_t st, const RecSide& lo, const RecSide& hi, const GridDesc& g, uint32_t G, volatile uint32_t* err_word);
+// (rho, p) of n_lo + n_hi ghosts <- a message, with the neighbour terms the force pass reads of them
+int launch_unpack_dp(hipStream_t st, const float2* src_lo, float2* dp_lo, float2* cw_lo, uint32_t n_lo, const float2* src_hi, float2* dp_hi,
+                     float2* cw_hi, uint32_t n_hi, const Phys& ph);
+// out[k] = the first slot of the sorted keys[0, n) whose key is >= v[k], for k < m: to device words and, where given, mapped host words
+constexpr uint32_t LB_MAX = 32;
+struct LbTargets { uint32_t v[LB_MAX]; uint32_t m; };
+int launch_lower_bounds(hipStream_t st, const uint32_t* keys, uint32_t n, const LbTargets& tg, uint32_t* out, volatile uint32_t* out_host);
+// the ends of a slab's boundary layers in its sorted keys, G ghost layers per side: first ghost | first owned layer | ... | last | ghost
+inline LbTargets layer_bound_targets(const sph_ctx* c) {
+    const uint32_t layer = c->grid.g[0] * c->grid.g[1], G = c->ghost_layers, zl = c->grid.zl;
+    return LbTargets{{G * layer, (G + 1u) * layer, (zl - G - 1u) * layer, (zl - G) * layer}, 4u};
+}
+// record 0 of both send buffers (a message's header)
+int launch_headers(hipStream_t st, float4* out_lo, float4* out_hi, float4 lo, float4 hi);
 // what each subsystem allocates in the context's owner, sized next to the kernels that index it
 int sort_buffers_alloc(sph_ctx* c);       // sph_sort.hip: the sorts' scratch and the mapped word block (create_impl)
 int tracked_buffers_alloc(sph_ctx* c);    // sph_pairs.hip: the table, partial sums and masks of a tracked context (first tracking)

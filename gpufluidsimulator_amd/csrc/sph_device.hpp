@@ -151,6 +151,40 @@ __device__ __forceinline__ T scan_array_one_block(uint32_t n, T* lds, Load load,
     return carry;
 }
 
+// ---- binary search: THE search of the library.  (wave_lower_bound, sph_slab.hip, is another algorithm: one wave, 64 probes a round.)
+// first i in [lo, hi) for which less(i) is false; hi if there is none.  less must be monotone: true, ..., true, false, ..., false
+// ("lower bound of v": less = x[i] < v; "first beyond v": x[i] <= v, and that minus one is the LAST i with x[i] <= v.)
+template <class Less>
+__device__ __forceinline__ uint32_t first_not(uint32_t lo, uint32_t hi, Less&& less) {
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (less(mid)) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// ---- slab messages: a record is a particle in a message, rec[2 i] = posi, rec[2 i + 1] = velr (the kernels of sph_halo.hip and
+//      sph_slab.hip; a message may carry header records in front: the caller passes `rec` behind them) ----------------------------
+__device__ __forceinline__ void put_record(float4* rec, uint32_t i, const float4& p, const float4& v) {
+    rec[2 * i] = p;
+    rec[2 * i + 1] = v;
+}
+__device__ __forceinline__ void get_record(const float4* rec, uint32_t i, float4& p, float4& v) {
+    p = rec[2 * i];
+    v = rec[2 * i + 1];
+}
+// Thread t of a launch over both sides of a slab, n_lo items of the lower side first: which side, which item of it, and
+// whether there is one (threads past n_lo + n_hi: not live)
+struct SideSplit {
+    bool hi, live;
+    uint32_t i;
+};
+__device__ __forceinline__ SideSplit side_split(uint32_t t, uint32_t n_lo, uint32_t n_hi) {
+    const bool hi = t >= n_lo;
+    const uint32_t i = hi ? t - n_lo : t;
+    return SideSplit{hi, i < (hi ? n_hi : n_lo), i};
+}
+
 // ---- cell table: {start, end} per occupied cell from boundary flags on the sorted keys (k_cells_build, sph_pairs.hip; the slab
 //      step's bounds kernel runs the same build in its spare blocks, sph_slab.hip) ------------------------------------------------
 // Thread t of the build takes CELLS_SPT = 4 consecutive slots from lo + 4 t: six key reads for four slots instead of twelve, a

@@ -155,17 +155,14 @@ __global__ __launch_bounds__(OBMESH_SCAN2) void k_obmesh_scan(ObMeshWork w, uint
 // last triangle of that block whose offset is <= the rest (triangles without tiles share their successor's offset and lose)
 __device__ __forceinline__ uint32_t obmesh_find(const uint64_t* __restrict__ blk, const uint32_t* __restrict__ off, uint32_t nt,
                                                 uint64_t tile, uint32_t& local) {
-    uint32_t lo = 0, hi = (nt + OBMESH_THREADS - 1u) / OBMESH_THREADS;
-    while (hi - lo > 1u) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (blk[mid] <= tile) lo = mid; else hi = mid;
-    }
-    const uint32_t rest = (uint32_t)(tile - blk[lo]);
-    uint32_t a = lo * OBMESH_THREADS, b = min(nt, a + OBMESH_THREADS);
-    while (b - a > 1u) {
-        const uint32_t mid = a + ((b - a) >> 1);
-        if (off[mid] <= rest) a = mid; else b = mid;
-    }
+    // (both searches start one past their first entry: blk[0] = 0 <= tile and a block's first offset 0 <= rest hold without a
+    // probe, and "the first beyond, minus one" then never goes below the range.  nt >= 1: the caller has tile < the pass's total.
+    // Among equal entries the first beyond them all is found, so the LAST of them wins, as the comment above asks.)
+    const uint32_t nb = (nt + OBMESH_THREADS - 1u) / OBMESH_THREADS;
+    const uint32_t b = first_not(1u, nb, [&](uint32_t i) { return blk[i] <= tile; }) - 1u;
+    const uint32_t rest = (uint32_t)(tile - blk[b]);
+    const uint32_t t0 = b * OBMESH_THREADS;
+    const uint32_t a = first_not(t0 + 1u, min(nt, t0 + OBMESH_THREADS), [&](uint32_t i) { return off[i] <= rest; }) - 1u;
     local = rest - off[a];
     return a;
 }

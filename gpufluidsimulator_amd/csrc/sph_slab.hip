@@ -50,6 +50,10 @@
 // on the comm stream (sph_rccl_transport_create; over the direct xGMI link), or through a caller-supplied
 // transport (tests: host-staged -- several processes over gloo -- or device-to-device between the streams of one
 // process, sph_local_transport_create).
+//
+// The kernels here are the step's own.  The small kernels of the messages -- record pack and unpack, the ghosts' (rho, p) unpack,
+// lower bounds of a few targets, the header writer -- are sph_halo.hip's, shared with the phase API: launch_pack_records,
+// launch_unpack_records, launch_unpack_dp, launch_lower_bounds, launch_headers (sph_common.hpp), each on the stream named here.
 #include "sph_device.hpp"
 #include <vector>
 
@@ -89,22 +93,6 @@ enum { SLAB_ERR_INSERT_LAYER = 0, SLAB_ERR_ARRIVAL_OUTSIDE = 1 };
 enum { DL_DEEP = 4, DL_FAR = 6, DL_CTR = 8, DL_NEAR = 12, DL_PING = 14, DL_EARLY = 16, DL_VFAR = 18, DL_CTR2 = 20, DL_WORDS = 24 };
 
 constexpr uint32_t MIG_INLINE = 255;   // leavers per side that ride in the first (fixed-size, 8 KB) migrant message
-
-// slot of the first key >= target, for 4 targets (one thread each): the layer bounds of the owned range (used
-// after the rare pass over all particles that takes in far arrivals)
-__global__ void k_slab_bounds(const uint32_t* __restrict__ keys, uint32_t n, uint32_t layer, uint32_t zl, uint32_t G,
-                              uint32_t* __restrict__ out, volatile uint32_t* __restrict__ out_host) {
-    const uint32_t t = threadIdx.x;
-    if (t >= 4) return;
-    const uint32_t targets[4] = {G * layer, (G + 1u) * layer, (zl - G - 1u) * layer, (zl - G) * layer};      // G ghost layers per side
-    uint32_t v = targets[t], lo = 0, hi = n;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (keys[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    out[t] = lo;
-    out_host[t] = lo;
-}
 
 // ONE kernel after the sort: every block finds the six layer bounds of the sorted owned keys (six threads, binary
 // searches over L2-resident lines: cheaper than a kernel boundary), then the blocks pack the leavers -- they sit at
@@ -182,14 +170,14 @@ __global__ __launch_bounds__(256) void k_slab_bounds_pack(const uint32_t* __rest
     for (uint32_t k = blockIdx.x * 256u + threadIdx.x; k < cap && (k < m_lo || k < m_hi); k += pack_blocks * 256u) {
         if (k < m_lo) {
             const float4 p = posi[k];
-            out_lo[2 + 2 * k] = p; out_lo[3 + 2 * k] = velr[k];
+            put_record(out_lo + 2, k, p, velr[k]);
             const int lz = (int)cell_coord(p.z, g.box_min[2], g.box_dims[2], g.gf[2], g.g[2]);
             far_l += lz != g.z_off + (int)G - 1 ? 1u : 0u;    // not global layer z_lo - 1
             vfar += lz < g.z_off + (int)G - 2 ? 1u : 0u;
         }
         if (k < m_hi) {
             const float4 p = posi[lb3 + k];
-            out_hi[2 + 2 * k] = p; out_hi[3 + 2 * k] = velr[lb3 + k];
+            put_record(out_hi + 2, k, p, velr[lb3 + k]);
             const int lz = (int)cell_coord(p.z, g.box_min[2], g.box_dims[2], g.gf[2], g.g[2]);
             far_h += lz != g.z_off + (int)zl - (int)G ? 1u : 0u;   // not global layer z_hi
             vfar += lz > g.z_off + (int)zl - (int)G + 1 ? 1u : 0u;
@@ -205,8 +193,8 @@ __global__ __launch_bounds__(256) void k_slab_bounds_pack(const uint32_t* __rest
         float4* const dl_ = out_lo + 2u * (1u + min(m_lo, cap));
         float4* const dh_ = out_hi + 2u * (1u + min(m_hi, cap));
         for (uint32_t k = blockIdx.x * 256u + threadIdx.x; k < n_rl + n_rh; k += pack_blocks * 256u) {
-            if (k < n_rl) { dl_[2 * k] = posi[r_lo0 + k]; dl_[2 * k + 1] = velr[r_lo0 + k]; }
-            else { const uint32_t j = k - n_rl; dh_[2 * j] = posi[r_hi0 + j]; dh_[2 * j + 1] = velr[r_hi0 + j]; }
+            if (k < n_rl) put_record(dl_, k, posi[r_lo0 + k], velr[r_lo0 + k]);
+            else { const uint32_t j = k - n_rl; put_record(dh_, j, posi[r_hi0 + j], velr[r_hi0 + j]); }
         }
     }
     // far counts and the "last block" ticket: RETURNING device-scope atomics (performed at the memory side; the
@@ -275,10 +263,13 @@ __global__ __launch_bounds__(256) void k_slab_early_finish(const uint32_t* __res
     }
 }
 
-// A rank that failed tells its neighbours: the header of its NEXT migrant message says "abort" (word 3), nothing else
-__global__ void k_slab_abort_headers(float4* __restrict__ out_lo, float4* __restrict__ out_hi) {
-    if (threadIdx.x == 0) out_lo[0] = make_float4(0.f, 0.f, 0.f, __uint_as_float(1u));
-    if (threadIdx.x == 1) out_hi[0] = make_float4(0.f, 0.f, 0.f, __uint_as_float(1u));
+// word 0 and word 3 of a header that says nothing else (launch_headers): a count (the re-cut's first message), or "abort" -- a
+// rank that failed tells its neighbours in the header of its NEXT migrant message
+static float4 bare_header(uint32_t count, uint32_t abort) {
+    float4 h = make_float4(0.f, 0.f, 0.f, 0.f);
+    memcpy(&h.x, &count, 4);
+    memcpy(&h.w, &abort, 4);
+    return h;
 }
 
 // comm stream, right behind the migrant exchange: everything the host's one wait needs, in one mapped block, the
@@ -306,34 +297,18 @@ __global__ void k_slab_post_headers(const uint32_t* __restrict__ dl, const float
     if (t == 0u) host[HL_SEQ] = seq;
 }
 
-// both boundary layers -> their halo messages, one launch
-__global__ __launch_bounds__(256) void k_slab_pack2(const float4* __restrict__ posi, const float4* __restrict__ velr,
-                                                    uint32_t first_lo, uint32_t n_lo, uint32_t first_hi, uint32_t n_hi,
-                                                    float4* __restrict__ rec_lo, float4* __restrict__ rec_hi) {
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t < n_lo) { rec_lo[2 * t] = posi[first_lo + t]; rec_lo[2 * t + 1] = velr[first_lo + t]; }
-    else if (t - n_lo < n_hi) {
-        const uint32_t i = t - n_lo;
-        rec_hi[2 * i] = posi[first_hi + i]; rec_hi[2 * i + 1] = velr[first_hi + i];
-    }
-}
-
-// (density, pressure) of both boundary layers -> messages, and of both ghost layers <- messages: one launch each
+// (density, pressure) of both boundary layers -> messages, one launch (the way back, with the neighbour terms: launch_unpack_dp)
 __global__ __launch_bounds__(256) void k_slab_copy_dp2(const float2* __restrict__ src_lo, float2* __restrict__ dst_lo,
                                                        uint32_t n_lo, const float2* __restrict__ src_hi,
                                                        float2* __restrict__ dst_hi, uint32_t n_hi) {
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t < n_lo) dst_lo[t] = src_lo[t];
-    else if (t - n_lo < n_hi) dst_hi[t - n_lo] = src_hi[t - n_lo];
+    const SideSplit s = side_split(blockIdx.x * 256u + threadIdx.x, n_lo, n_hi);
+    if (s.live) (s.hi ? dst_hi : dst_lo)[s.i] = (s.hi ? src_hi : src_lo)[s.i];
 }
 
-// ghost (rho, p) of both sides <- messages, with the neighbour terms the force pass reads of them (cw)
-__global__ __launch_bounds__(256) void k_slab_unpack_dp2(const float2* __restrict__ src_lo, float2* __restrict__ dp_lo,
-                                                         float2* __restrict__ cw_lo, uint32_t n_lo, const float2* __restrict__ src_hi,
-                                                         float2* __restrict__ dp_hi, float2* __restrict__ cw_hi, uint32_t n_hi, Phys ph) {
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t < n_lo) { const float2 v = src_lo[t]; dp_lo[t] = v; cw_lo[t] = neighbour_terms(ph, v.x, v.y); }
-    else if (t - n_lo < n_hi) { const float2 v = src_hi[t - n_lo]; dp_hi[t - n_lo] = v; cw_hi[t - n_lo] = neighbour_terms(ph, v.x, v.y); }
+// the cell key of record i, from its position
+__device__ __forceinline__ uint32_t rec_key(const float4* __restrict__ rec, uint32_t i, const GridDesc& g) {
+    const float4 p = rec[2 * i];
+    return cell_key(g, p.x, p.y, p.z);
 }
 
 // Ghost records of both sides -> the slots in front of / behind the owned range, with their cell keys, AND the cell
@@ -343,20 +318,19 @@ __global__ __launch_bounds__(256) void k_slab_unpack_ghosts(const float4* __rest
                                                             const float4* __restrict__ rec_hi, uint32_t n_hi, uint32_t slot_hi,
                                                             float4* __restrict__ posi, float4* __restrict__ velr,
                                                             uint32_t* __restrict__ key, uint2* __restrict__ cells, GridDesc g) {
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    const bool low = t < n_lo;
-    const uint32_t i = low ? t : t - n_lo, n = low ? n_lo : n_hi;
-    if (i >= n) return;
-    const float4* rec = low ? rec_lo : rec_hi;
-    const uint32_t s = (low ? slot_lo : slot_hi) + i;
+    const SideSplit sp = side_split(blockIdx.x * 256u + threadIdx.x, n_lo, n_hi);
+    if (!sp.live) return;
+    const uint32_t i = sp.i, n = sp.hi ? n_hi : n_lo;
+    const float4* rec = sp.hi ? rec_hi : rec_lo;
+    const uint32_t s = (sp.hi ? slot_hi : slot_lo) + i;
     const float4 p = rec[2 * i];
     const uint32_t k = cell_key(g, p.x, p.y, p.z);
     posi[s] = p;
     velr[s] = rec[2 * i + 1];
     key[s] = k;
     bool first = i == 0, last = i + 1 == n;
-    if (!first) { const float4 q = rec[2 * (i - 1)]; first = cell_key(g, q.x, q.y, q.z) != k; }
-    if (!last) { const float4 q = rec[2 * (i + 1)]; last = cell_key(g, q.x, q.y, q.z) != k; }
+    if (!first) first = rec_key(rec, i - 1, g) != k;
+    if (!last) last = rec_key(rec, i + 1, g) != k;
     if (first) cells[k].x = s;
     if (last) cells[k].y = s + 1;
 }
@@ -369,28 +343,20 @@ __global__ __launch_bounds__(256) void k_slab_unpack_ghosts(const float4* __rest
 // cell, above it (side 1) they arrive from BELOW and go in front.  A thread per record: a resident counts the leavers in front
 // of it, a leaver the residents (binary searches on keys recomputed from the records' positions; with no leavers on a side the
 // count is 0 and this is a plain unpack).  The cell table of the ghost slots is built by k_cells_build2 afterwards.
-__device__ __forceinline__ uint32_t rec_key(const float4* __restrict__ rec, uint32_t i, const GridDesc& g) {
-    const float4 p = rec[2 * i];
-    return cell_key(g, p.x, p.y, p.z);
-}
 __device__ __forceinline__ uint32_t rec_count_below(const float4* __restrict__ rec, uint32_t n, uint32_t bound, const GridDesc& g) {
-    uint32_t lo = 0, hi = n;                                      // first record with key >= bound
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (rec_key(rec, mid, g) < bound) lo = mid + 1; else hi = mid;
-    }
-    return lo;
+    return first_not(0u, n, [&](uint32_t i) { return rec_key(rec, i, g) < bound; });      // first record with key >= bound
 }
 __global__ __launch_bounds__(256) void k_slab_unpack_ghosts_merge(const float4* __restrict__ res_lo, uint32_t nr_lo, const float4* __restrict__ lv_lo,
                                                                   uint32_t k_lo, uint32_t slot_lo, const float4* __restrict__ res_hi,
                                                                   uint32_t nr_hi, const float4* __restrict__ lv_hi, uint32_t k_hi,
                                                                   uint32_t slot_hi, float4* __restrict__ posi, float4* __restrict__ velr,
                                                                   uint32_t* __restrict__ key, GridDesc g) {
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    const bool high = t >= nr_lo + k_lo;
-    const uint32_t u = high ? t - (nr_lo + k_lo) : t;
-    const uint32_t nr = high ? nr_hi : nr_lo, k = high ? k_hi : k_lo;
-    if (u >= nr + k) return;
+    // a side: residents, then leavers.  (52 SGPRs where the hand-written split had 50: both sides' sums are formed as scalars here;
+    // that one selected nr and k per lane first and added once.  VGPRs, occupancy: as before -- profiles/search_unify_resources.txt)
+    const SideSplit sp = side_split(blockIdx.x * 256u + threadIdx.x, nr_lo + k_lo, nr_hi + k_hi);
+    if (!sp.live) return;
+    const bool high = sp.hi;
+    const uint32_t u = sp.i, nr = high ? nr_hi : nr_lo, k = high ? k_hi : k_lo;
     const float4* res = high ? res_hi : res_lo;
     const float4* lv = high ? lv_hi : lv_lo;
     const uint32_t first = high ? 1u : 0u;                        // leavers first among equal keys (above this slab)
@@ -402,25 +368,8 @@ __global__ __launch_bounds__(256) void k_slab_unpack_ghosts_merge(const float4* 
     const uint32_t ahead = resident ? rec_count_below(lv, k, kk + first, g) : rec_count_below(res, nr, kk + 1u - first, g);
     const uint32_t dst = (high ? slot_hi : slot_lo) + j + ahead;
     posi[dst] = p;
-    velr[dst] = rec[1];
+    velr[dst] = rec[1];                                           // (read behind the search: four registers less across it)
     key[dst] = kk;
-}
-
-// arrivals appended behind the owned range for the pass over all particles (launch_merge_arrivals): any owned layer
-// is fine there, but a particle that is not inside this slab at all cannot be represented (its key is clamped into a
-// ghost layer): flagged, the step reports SPH_E_STATE
-__global__ __launch_bounds__(256) void k_slab_unpack(const float4* __restrict__ rec, uint32_t n, float4* __restrict__ posi,
-                                                     float4* __restrict__ velr, uint32_t* __restrict__ key, GridDesc g, uint32_t G,
-                                                     volatile uint32_t* __restrict__ err_host) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    const float4 p = rec[2 * i];
-    posi[i] = p;
-    velr[i] = rec[2 * i + 1];
-    const uint32_t k = cell_key(g, p.x, p.y, p.z);
-    if (key) key[i] = k;
-    const uint32_t lz = k / (g.g[0] * g.g[1]);
-    if (lz < G || lz + G >= g.zl) err_host[SLAB_ERR_ARRIVAL_OUTSIDE] = 1u;
 }
 
 // Arrivals join a BOUNDARY LAYER in place.  A particle a neighbour sent lies in the cell layer next to the cut it
@@ -468,15 +417,9 @@ __global__ __launch_bounds__(256) void k_slab_insert(const float4* __restrict__ 
         const uint32_t r = t - nl, key = s_ak[r];
         uint32_t among = 0;
         for (uint32_t q = 0; q < k; q++) among += (s_ak[q] < key || (s_ak[q] == key && q < r)) ? 1u : 0u;
-        uint32_t lo = 0, hi = nl;                       // residents in front of me: key < mine (low side) / <= mine (high side)
-        const uint32_t bound = key + (arrivals_first ? 0u : 1u);
-        while (lo < hi) {
-            const uint32_t mid = lo + ((hi - lo) >> 1);
-            if (keyS[l0 + mid] < bound) lo = mid + 1; else hi = mid;
-        }
-        const uint32_t dst = d0 + among + lo;
-        posi_o[dst] = rec[2 * r];
-        velr_o[dst] = rec[2 * r + 1];
+        const uint32_t bound = key + (arrivals_first ? 0u : 1u);   // residents in front of me: key < mine (low side) / <= mine (high side)
+        const uint32_t dst = d0 + among + first_not(0u, nl, [&](uint32_t i) { return keyS[l0 + i] < bound; });
+        get_record(rec, r, posi_o[dst], velr_o[dst]);
         key_o[dst] = key;
     }
 }
@@ -550,29 +493,11 @@ __global__ __launch_bounds__(64) void k_recut_scatter(const float4* __restrict__
         r0 += (uint32_t)__popcll(m0); r1 += (uint32_t)__popcll(m1); r2 += (uint32_t)__popcll(m2);
     }
 }
-// one chunk of both leaving lists -> 8-float records ; arrived records -> their final slots ; the kept run -> its final place
-__global__ __launch_bounds__(256) void k_recut_pack(const float4* __restrict__ p, const float4* __restrict__ v, uint32_t first_lo,
-                                                    uint32_t n_lo, uint32_t first_hi, uint32_t n_hi, float4* __restrict__ rec_lo,
-                                                    float4* __restrict__ rec_hi) {
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t < n_lo) { rec_lo[2 * t] = p[first_lo + t]; rec_lo[2 * t + 1] = v[first_lo + t]; }
-    else if (t - n_lo < n_hi) { const uint32_t i = t - n_lo; rec_hi[2 * i] = p[first_hi + i]; rec_hi[2 * i + 1] = v[first_hi + i]; }
-}
-__global__ __launch_bounds__(256) void k_recut_unpack(const float4* __restrict__ rec_lo, uint32_t n_lo, uint32_t slot_lo,
-                                                      const float4* __restrict__ rec_hi, uint32_t n_hi, uint32_t slot_hi,
-                                                      float4* __restrict__ p, float4* __restrict__ v) {
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t < n_lo) { p[slot_lo + t] = rec_lo[2 * t]; v[slot_lo + t] = rec_lo[2 * t + 1]; }
-    else if (t - n_lo < n_hi) { const uint32_t i = t - n_lo; p[slot_hi + i] = rec_hi[2 * i]; v[slot_hi + i] = rec_hi[2 * i + 1]; }
-}
+// the kept run -> its final place (the two leaving lists and what arrives: launch_pack_records / launch_unpack_records, chunk by chunk)
 __global__ __launch_bounds__(256) void k_recut_copy(const float4* __restrict__ ps, const float4* __restrict__ vs, uint32_t src,
                                                     float4* __restrict__ pd, float4* __restrict__ vd, uint32_t dst, uint32_t count) {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     if (t < count) { pd[dst + t] = ps[src + t]; vd[dst + t] = vs[src + t]; }
-}
-__global__ void k_recut_counts_out(float4* __restrict__ out_lo, float4* __restrict__ out_hi, uint32_t down, uint32_t up) {
-    if (threadIdx.x == 0) out_lo[0] = make_float4(__uint_as_float(down), 0.f, 0.f, 0.f);
-    if (threadIdx.x == 1) out_hi[0] = make_float4(__uint_as_float(up), 0.f, 0.f, 0.f);
 }
 
 // ---- loop transport (sph_loop_transport_create): ONE slab whose two neighbours are its own periodic images ------------
@@ -582,8 +507,9 @@ __global__ __launch_bounds__(256) void k_loop_copy(const float4* __restrict__ up
                                                    const float4* __restrict__ down_src, float4* __restrict__ hi_dst, uint32_t n_down,
                                                    uint32_t first_record4, float shift, int shift_z) {
     for (uint32_t t = blockIdx.x * 256u + threadIdx.x; t < n_up + n_down; t += gridDim.x * 256u) {
-        const bool up = t < n_up;                            // sent upwards: arrives from below, one slab height lower
-        const uint32_t i = up ? t : t - n_up;
+        const SideSplit s = side_split(t, n_up, n_down);
+        const bool up = !s.hi;                               // sent upwards: arrives from below, one slab height lower
+        const uint32_t i = s.i;
         float4 v = up ? up_src[i] : down_src[i];
         if (shift_z && i >= first_record4 && ((i - first_record4) & 1u) == 0u) v.z += up ? -shift : shift;
         (up ? lo_dst : hi_dst)[i] = v;
@@ -1442,19 +1368,16 @@ int step_settle(sph_slab* s, Step& st) {
     for (int side = 0; side < 2; side++) {
         const uint32_t cnt = side == 0 ? in_lo : in_hi;
         if (!cnt) continue;
-        if (side == 0 && front_slots) {
-            hipLaunchKernelGGL(k_slab_unpack, dim3(ceil_div(cnt, 256u)), dim3(256), 0, c->stream, s->mig_recv[0] + 2, cnt,
-                               c->posi + c->own_off - cnt, c->velr + c->own_off - cnt, (uint32_t*)nullptr, c->grid, G,
-                               s->h_lb_dev + HL_ERR);
-            continue;
-        }
-        const uint32_t at = c->own_off + c->n + appended;
-        hipLaunchKernelGGL(k_slab_unpack, dim3(ceil_div(cnt, 256u)), dim3(256), 0, c->stream, s->mig_recv[side] + 2, cnt,
-                           c->posi + at, c->velr + at, merge ? c->k0 + c->n + appended : (uint32_t*)nullptr, c->grid, G,
-                           s->h_lb_dev + HL_ERR);
-        appended += cnt;
+        // any owned layer is fine for the pass over all particles, but a particle that is not inside this slab at all cannot be
+        // represented: flagged (SLAB_ERR_ARRIVAL_OUTSIDE), the step reports SPH_E_STATE
+        const bool in_front = side == 0 && front_slots;
+        const uint32_t at = in_front ? c->own_off - cnt : c->own_off + c->n + appended;
+        uint32_t* const key = merge ? c->k0 + c->n + appended : nullptr;          // (front_slots: no merge)
+        rc = launch_unpack_records(c->stream, RecSide{s->mig_recv[side] + 2, c->posi + at, c->velr + at, key, cnt}, RecSide{}, c->grid, G,
+                                   s->h_lb_dev + HL_ERR + SLAB_ERR_ARRIVAL_OUTSIDE);
+        if (rc) return rc;
+        if (!in_front) appended += cnt;
     }
-    SPH_HIP(hipGetLastError());
     if (merge) {
         rc = launch_merge_arrivals(c, appended, in_lo); if (rc) return rc;   // the first in_lo came up from below
     } else {
@@ -1476,9 +1399,8 @@ int step_settle(sph_slab* s, Step& st) {
             fprintf(stderr, "[slab %d] step %llu: far arrivals %u/%u of %u/%u; leavers %u/%u (far %u/%u); bounds %u %u %u %u of %u; "
                     "peer boundary %u/%u\n", s->rank, (unsigned long long)s->steps, st.far_in_lo, st.far_in_hi, in_lo, in_hi, m_lo, m_hi,
                     st.far_lo, st.far_hi, st.lb0, st.lb1, st.lb2, st.lb3, st.n0, st.peer_own_lo, st.peer_own_hi);
-        hipLaunchKernelGGL(k_slab_bounds, dim3(1), dim3(64), 0, c->stream, c->keyS + c->own_off, c->n, st.layer, c->grid.zl, G,
-                           s->d_lb, s->h_lb_dev);
-        SPH_HIP(hipGetLastError());
+        rc = launch_lower_bounds(c->stream, c->keyS + c->own_off, c->n, layer_bound_targets(c), s->d_lb, s->h_lb_dev + HL_LB);
+        if (rc) return rc;
         SPH_HIP(hipStreamSynchronize(c->stream));
         s->host_waits++;
         rc = slab_check_device_flags(s); if (rc) return rc;
@@ -1539,10 +1461,12 @@ int step_ghosts(sph_slab* s, Step& st) {
     }
     // ---- halo A: boundary layers -> neighbours' ghost layers -----------------------------------------------------------
     hipStream_t pack_stream = early_halo ? s->comm : c->stream;
-    if (!p1 && h_lo + h_hi)
-        hipLaunchKernelGGL(k_slab_pack2, dim3(ceil_div(h_lo + h_hi, 256u)), dim3(256), 0, pack_stream, c->posi, c->velr, c->own_off, h_lo,
-                           c->own_off + n - h_hi, h_hi, s->halo_send[0], s->halo_send[1]);
-    SPH_HIP(hipGetLastError());
+    if (!p1) {                                                  // both boundary layers -> their halo messages, one launch
+        const uint32_t first_hi = c->own_off + n - h_hi;
+        rc = launch_pack_records(pack_stream, RecSide{s->halo_send[0], c->posi + c->own_off, c->velr + c->own_off, nullptr, h_lo},
+                                 RecSide{s->halo_send[1], c->posi + first_hi, c->velr + first_hi, nullptr, h_hi});
+        if (rc) return rc;
+    }
     if (!early_halo) {
         rc = after_main(s); if (rc) return rc;                  // the comm stream may start once the slices are packed
         // the interior density runs while the halo travels: queued BEFORE the transfers are handed to the transport.
@@ -1651,11 +1575,9 @@ int step_forces(sph_slab* s, Step& st) {
     if (!st.p1) {
         rc = slab_exchange(s, s->pg.group[sph_slab::G_HALO_B]); if (rc) return rc;
         s->pg.posted[sph_slab::G_HALO_B] = true;
-        if (g_lo + g_hi)
-            hipLaunchKernelGGL(k_slab_unpack_dp2, dim3(ceil_div(g_lo + g_hi, 256u)), dim3(256), 0, s->comm, s->dens_recv[0],
-                               c->dp + c->own_off - g_lo, c->cw + c->own_off - g_lo, g_lo, s->dens_recv[1], c->dp + c->own_off + n,
-                               c->cw + c->own_off + n, g_hi, c->phys);
-        SPH_HIP(hipGetLastError());
+        rc = launch_unpack_dp(s->comm, s->dens_recv[0], c->dp + c->own_off - g_lo, c->cw + c->own_off - g_lo, g_lo, s->dens_recv[1],
+                              c->dp + c->own_off + n, c->cw + c->own_off + n, g_hi, c->phys);
+        if (rc) return rc;
     }   // (the one-message step: the inner ghost layers' densities came out of this rank's own density launches above)
     // the boundary layers' force pass: on the comm stream, behind the ghosts' (rho, p) -- beside the interior launch
     // (it reads what that one reads and writes other slots of the ping-pong arrays), not behind it
@@ -1721,13 +1643,13 @@ int slab_fail(sph_slab* s, int rc) {
             // this step's wait and stop; nothing else is owed (no header of this rank promised anything)
             g.posted[sph_slab::G_FIRST] = true;
             after_main(s);      // (a bounds kernel of this step may be queued on the main stream: it writes the same header words)
-            hipLaunchKernelGGL(k_slab_abort_headers, dim3(1), dim3(64), 0, s->comm, s->mig_send[0], s->mig_send[1]);
+            launch_headers(s->comm, s->mig_send[0], s->mig_send[1], bare_header(0u, 1u), bare_header(0u, 1u));
             e = slab_exchange(s, g.group[sph_slab::G_FIRST]);
         } else if (g.headers) {
             for (int i = sph_slab::G_REST; i <= sph_slab::G_HALO_B && !e; i++)
                 if (!g.posted[i]) e = slab_exchange(s, g.group[i]);
             if (!e) {                                           // the next step's header: "abort"
-                hipLaunchKernelGGL(k_slab_abort_headers, dim3(1), dim3(64), 0, s->comm, s->mig_send[0], s->mig_send[1]);
+                launch_headers(s->comm, s->mig_send[0], s->mig_send[1], bare_header(0u, 1u), bare_header(0u, 1u));
                 e = slab_exchange(s, g.group[sph_slab::G_NEXT]);
             }
         }
@@ -2238,8 +2160,7 @@ static int slab_recut_body(sph_slab* s, uint32_t new_lo, uint32_t new_hi) {
     hipLaunchKernelGGL(k_recut_scatter, dim3(nblk), dim3(64), 0, c->stream, c->posi + off, c->velr + off, n, c->grid, new_lo, new_hi,
                        s->recut_blk, c->posi2, c->velr2, keep0, down0, up0);
     // the counts: one record each way (the first record of the migrant buffers)
-    hipLaunchKernelGGL(k_recut_counts_out, dim3(1), dim3(64), 0, c->stream, s->mig_send[0], s->mig_send[1], down, up);
-    SPH_HIP(hipGetLastError());
+    rc = launch_headers(c->stream, s->mig_send[0], s->mig_send[1], bare_header(down, 0u), bare_header(up, 0u)); if (rc) return rc;
     rc = after_main(s); if (rc) return rc;
     const uint32_t none[2] = {0, 0};
     rc = slab_exchange(s, msg_first(s, SPH_TAG_RECUT_COUNTS, none, none));
@@ -2268,18 +2189,20 @@ static int slab_recut_body(sph_slab* s, uint32_t new_lo, uint32_t new_hi) {
     for (uint32_t j = 0; j < rounds; j++) {
         auto part = [&](uint32_t total) { return total > j * chunk ? min(chunk, total - j * chunk) : 0u; };
         const uint32_t s_lo = part(down), s_hi = part(up), r_lo = part(in_lo), r_hi = part(in_hi);
-        if (s_lo + s_hi)
-            hipLaunchKernelGGL(k_recut_pack, dim3(ceil_div(s_lo + s_hi, 256u)), dim3(256), 0, c->stream, c->posi2, c->velr2, down0 + j * chunk,
-                               s_lo, up0 + j * chunk, s_hi, s->halo_send[0], s->halo_send[1]);
-        SPH_HIP(hipGetLastError());
+        const uint32_t d_at = down0 + j * chunk, u_at = up0 + j * chunk;
+        rc = launch_pack_records(c->stream, RecSide{s->halo_send[0], c->posi2 + d_at, c->velr2 + d_at, nullptr, s_lo},
+                                 RecSide{s->halo_send[1], c->posi2 + u_at, c->velr2 + u_at, nullptr, s_hi});
+        if (rc) return rc;
         rc = after_main(s); if (rc) return rc;
         const uint32_t sent[2] = {s_lo, s_hi}, taken[2] = {r_lo, r_hi};
         rc = slab_exchange(s, msg_halo(s, SPH_TAG_RECUT, sent, taken));
         if (rc) return rc;
-        if (r_lo + r_hi && !over)
-            hipLaunchKernelGGL(k_recut_unpack, dim3(ceil_div(r_lo + r_hi, 256u)), dim3(256), 0, s->comm, s->halo_recv[0], r_lo,
-                               base + j * chunk, s->halo_recv[1], r_hi, base + in_lo + keep + j * chunk, c->posi, c->velr);
-        SPH_HIP(hipGetLastError());
+        if (!over) {                                      // no keys: the next step hashes and sorts
+            const uint32_t lo_at = base + j * chunk, hi_at = base + in_lo + keep + j * chunk;
+            rc = launch_unpack_records(s->comm, RecSide{s->halo_recv[0], c->posi + lo_at, c->velr + lo_at, nullptr, r_lo},
+                                       RecSide{s->halo_recv[1], c->posi + hi_at, c->velr + hi_at, nullptr, r_hi}, c->grid, 0u, nullptr);
+            if (rc) return rc;
+        }
         rc = after_comm(s); if (rc) return rc;            // the send buffers are free again, the arrivals are in
     }
     rc = slab_wait_stream(s, s->comm, "re-cut (particles)"); if (rc) return rc;
@@ -2332,7 +2255,7 @@ int sph_slab_recut_stats(const sph_slab* s, uint64_t out[2]) {
     return SPH_OK;
 }
 
-// test hook: raise one of the sticky device-side error words by hand (what k_slab_insert / k_slab_unpack do when an
+// test hook: raise one of the sticky device-side error words by hand (what k_slab_insert / k_unpack_records do when an
 // arrival is where it cannot be), so that the failure path of a step that has not sent anything yet can be exercised
 int sph_slab_test_raise_flag(sph_slab* s, int flag) {
     SPH_REQUIRE(s && flag >= 0 && flag < 2, SPH_E_INVALID, "bad argument");

@@ -521,20 +521,14 @@ __device__ __forceinline__ bool mover_slot_less(uint32_t mover_slot, uint32_t sl
     return mover_slot < slot || mover_slot - f.lo < f.cnt;         // (unsigned: slots below f.lo wrap to huge values)
 }
 
-// first r in [0, m) with (sk[r], sv[r]) >= (key, slot), the arrays in LDS
-__device__ __forceinline__ uint32_t small_lower_bound(const uint32_t* sk, const uint32_t* sv, uint32_t m, uint32_t key,
-                                                      uint32_t slot, Front f) {
-    uint32_t lo = 0, hi = m;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        const uint32_t k = sk[mid];
-        if (k < key || (k == key && mover_slot_less(sv[mid], slot, f))) lo = mid + 1; else hi = mid;
-    }
-    return lo;
+// first r in [lo, hi) with (mk[r], mi[r]) >= (key, slot): the sorted movers, in global memory or in the one-block sort's LDS
+__device__ __forceinline__ uint32_t mm_lower_bound(const uint32_t* __restrict__ mk, const uint32_t* __restrict__ mi, uint32_t lo, uint32_t hi,
+                                                   uint32_t key, uint32_t slot, Front f) {
+    return first_not(lo, hi, [&](uint32_t r) {
+        const uint32_t k = mk[r];
+        return k < key || (k == key && mover_slot_less(mi[r], slot, f));
+    });
 }
-
-__device__ __forceinline__ uint32_t mm_lower_bound(const uint32_t* __restrict__ mk, const uint32_t* __restrict__ mi,
-                                                   uint32_t lo, uint32_t hi, uint32_t key, uint32_t slot, Front f);
 
 // `alone`: no other sort kernel is launched beside this one (radix_sort_bits, when the host's last known count says the
 // movers fit): then a count beyond OS_SMALL_MAX -- the first step of a burst, one step ahead of the host's knowledge --
@@ -726,7 +720,7 @@ __global__ __launch_bounds__(SMALL_THREADS) void k_os_small(uint32_t* ak, uint32
             const uint32_t slot = t * OS_TILE;
             const uint32_t a = t == ntiles ? 0xFFFFFFFFu : A[slot];
             tileA[t] = a;
-            tileL[t] = t == ntiles ? m : small_lower_bound(s_key, s_val, m, a, slot, front);
+            tileL[t] = t == ntiles ? m : mm_lower_bound(s_key, s_val, 0u, m, a, slot, front);
         }
     }
 }
@@ -1033,18 +1027,6 @@ __global__ __launch_bounds__(256) void k_mm_compact(const uint64_t* __restrict__
     }
 }
 
-// first r in [lo, hi) with (mk[r], mi[r]) >= (key, slot)
-__device__ __forceinline__ uint32_t mm_lower_bound(const uint32_t* __restrict__ mk, const uint32_t* __restrict__ mi,
-                                                   uint32_t lo, uint32_t hi, uint32_t key, uint32_t slot, Front f) {
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        const uint32_t k = mk[mid];
-        const bool less = k < key || (k == key && mover_slot_less(mi[mid], slot, f));
-        if (less) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // Coarse ranks: tileL[t] = #movers with (key, slot) < (A[t * 4096], t * 4096), tileL[ntiles] = m.  The per-wave
 // searches of k_mm_scatter then run inside [tileL[t], tileL[t+1]] -- a handful of movers instead of all of them
 // (16 dependent loads per search at 40 K movers made the placement latency-bound: 180 us at C3).
@@ -1062,6 +1044,9 @@ __global__ __launch_bounds__(256) void k_mm_tile_rank(const uint32_t* __restrict
     const uint32_t slot = t * MM_RANK_TILE;
     const uint32_t a = t == ntiles ? 0xFFFFFFFFu : A[slot];
     tileA[t] = a;                      // first key of every tile: the coarse level of k_mm_place_movers' searches
+    // (26 SGPRs where the hand-written loop had 24: hipcc turns the predicate's result into a pair of selects on lo and hi, and
+    // keeps their mask in two more scalars, where it had branched around `lo = mid + 1`; two instructions shorter.  The other
+    // callers of mm_lower_bound came out register for register as before -- profiles/search_unify_resources.txt)
     tileL[t] = t == ntiles ? m : mm_lower_bound(mk, mi, 0u, m, a, slot, front);
 }
 
@@ -1127,17 +1112,12 @@ __device__ __forceinline__ void mm_place_body(uint32_t bid, uint32_t nblocks, co
             s = ce.x - slot_base; e = ce.y - slot_base;
         } else {
             // coarse: last tile whose first key is < key (s lies in it or at the start of the next one)
-            uint32_t lo = 0, hi = ntiles;               // first tile t with tileA[t] >= key
-            while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (tileA[mid] < key) lo = mid + 1; else hi = mid; }
-            uint32_t a = lo ? (lo - 1u) * MM_RANK_TILE : 0u, b = min(lo * MM_RANK_TILE, n);
-            while (a < b) { const uint32_t mid = a + ((b - a) >> 1); if (A[mid] < key) a = mid + 1; else b = mid; }
-            s = a;                                      // first slot with A >= key
+            const uint32_t lo = first_not(0u, ntiles, [&](uint32_t t) { return tileA[t] < key; });   // first tile t with tileA[t] >= key
+            s = first_not(lo ? (lo - 1u) * MM_RANK_TILE : 0u, min(lo * MM_RANK_TILE, n), [&](uint32_t i) { return A[i] < key; });   // first slot with A >= key
             uint32_t step = 1u, p = s;                  // gallop to the first slot with A > key
             while (p < n && A[p] == key) { p = min(p + step, n); step <<= 1; }
-            uint32_t q = p > s ? max(s, p - (step >> 1)) : s;   // A[q .. ) still may equal key; A[p] != key or p == n
-            a = q; b = p;
-            while (a < b) { const uint32_t mid = a + ((b - a) >> 1); if (A[mid] <= key) a = mid + 1; else b = mid; }
-            e = a;
+            const uint32_t q = p > s ? max(s, p - (step >> 1)) : s;   // A[q .. ) still may equal key; A[p] != key or p == n
+            e = first_not(q, p, [&](uint32_t i) { return A[i] <= key; });
         }
         // non-movers of cell `key` below `slot` end here (a front mover -- an arrival from the slab below -- precedes them all)
         const uint32_t j = slot - front.lo < front.cnt ? s : min(max(slot, s), e);

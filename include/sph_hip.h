@@ -50,7 +50,7 @@
  *                  sph_set_sort_mode sph_set_direct_hull sph_set_pair_small_launch sph_set_block_order sph_slab_set_early_force
  *   [test hook]    exist for tests and measurement harnesses only: sph_test_trust_mover_hint sph_slab_test_raise_flag
  *                  sph_rccl_transport_selftest sph_loop_transport_create/_destroy sph_memory_stats sph_test_fail_alloc
- *                  sph_test_scan sph_test_guard sph_test_guard_check
+ *                  sph_test_scan sph_test_lower_bounds sph_test_guard sph_test_guard_check
  */
 #ifndef SPH_HIP_H
 #define SPH_HIP_H
@@ -1058,6 +1058,11 @@ int sph_slab_set_protocol(sph_slab* s, int groups);
  * out[i] = in[0] + ... + in[i - 1] and *total = the sum of all n, in unsigned arithmetic of `bits` (32 or 64) bits, wrap-around
  * included.  in, out (n values) and total (one) are host memory; n = 0 writes only *total = 0.  Waits for the result. */
 /* [test hook] */ int sph_test_scan(sph_ctx* c, int bits, uint32_t n, const void* in, void* out, void* total);
+/* TEST HOOK: the library's binary search (layer bounds, the merges of arrivals and ghosts, the sorts' ranks and the voxeliser's work
+ * list all run it) through the lower-bounds kernel of the slab messages, on keys of the caller's: out[k] = the first i in [0, n]
+ * with i == n or keys[i] >= targets[k], for k < m.  keys (n values in ascending order; equal keys allowed), targets and out
+ * (m <= 32 values each) are host memory.  Waits for the result. */
+/* [test hook] */ int sph_test_lower_bounds(sph_ctx* c, const uint32_t* keys, uint32_t n, const uint32_t* targets, uint32_t m, uint32_t* out);
 /* TEST HOOK: guarded allocations.  While band_bytes (a multiple of 4096; any other value is refused and changes nothing) is not 0,
  * every device, pinned and mapped allocation the library makes has a band of that many bytes in front of the caller's range and
  * another behind it, filled with a pattern of 32-bit words: nonzero, below 512 (a subnormal as fp32) and varying with the position.

@@ -11,7 +11,7 @@ rows=list(csv.DictReader(open("gpurun_out/prof_arr/a_kernel_stats.csv")))
 tot=sum(float(r["TotalDurationNs"]) for r in rows)
 print("  kernel-busy total %.1f ms" % (tot/1e6))
 for r in rows:
-    if any(k in r["Name"] for k in ("k_mm_", "k_slab_", "k_cells", "k_os_", "copyBuffer")): print("   ", r["Name"][:44], r["Calls"], "avg %.1f us" % (float(r["AverageNs"])/1e3), "total %.2f ms" % (float(r["TotalDurationNs"])/1e6))
+    if any(k in r["Name"] for k in ("k_mm_", "k_slab_", "k_pack_records", "k_unpack_", "k_lower_bounds", "k_headers", "k_cells", "k_os_", "copyBuffer")): print("   ", r["Name"][:44], r["Calls"], "avg %.1f us" % (float(r["AverageNs"])/1e3), "total %.2f ms" % (float(r["TotalDurationNs"])/1e6))
 PY
 done
 rm -rf gpurun_out/prof_arr
