@@ -45,12 +45,18 @@ REC = capi.HALO_RECORD_FLOATS
 # ------------------------------------------------------------------------------------------------
 # partitioning
 # ------------------------------------------------------------------------------------------------
-def cell_layer_of(z, box_z, gz):
+def cell_layer_of(z, box_z, gz, z_range=None):
     """Global z cell layer with the device's arithmetic (csrc/sph_device.hpp cell_coord): subtract
-    boxMin, divide by the box dimension, multiply by the grid size, floor, clamp -- all in fp32."""
+    boxMin, divide by the box dimension, multiply by the grid size, floor, clamp -- all in fp32.
+    z_range: None (a box of height box_z centred on the origin, sph_default_params) or the (box_min[2], box_max[2]) of an
+    sph_params whose box lies elsewhere."""
     z = np.asarray(z, dtype=np.float32)
-    bmin = np.float32(-np.float32(box_z) / np.float32(2.0))
-    bdim = np.float32(np.float32(box_z) / np.float32(2.0)) - bmin
+    if z_range is None:
+        bmin = np.float32(-np.float32(box_z) / np.float32(2.0))
+        bdim = np.float32(np.float32(box_z) / np.float32(2.0)) - bmin
+    else:
+        bmin = np.float32(z_range[0])
+        bdim = np.float32(z_range[1]) - bmin
     q = ((z - bmin) / bdim) * np.float32(gz)
     return np.clip(np.floor(q).astype(np.int64), 0, int(gz) - 1)
 
@@ -296,8 +302,9 @@ class SlabSimulation:
         rank: positions are global, so every rank pushes the particles it owns out of every sphere (ghosts arrive already
         pushed) and advances the centres once per step.  A sphere placed over fluid moves particles by up to its radius in
         one step, and in a slab run such a particle must still land inside its neighbour's slab (include/sph_hip.h).
-        params: None (the reference's constants for box and grid, sph_default_params), or a capi.Params of the same box and
-        grid with other physics parameters, the same on every rank."""
+        params: None (the reference's constants for box and grid, sph_default_params), or a capi.Params of the same box
+        dimensions and grid with other physics parameters, the same on every rank; its box need not be centred on the origin
+        (the cuts are taken over the layers of ITS box_min[2] .. box_max[2])."""
         self.comm = comm
         self.rank, self.world = comm.rank, comm.world
         try:                       # torch before libsph_hip.so (capi.load): one HIP runtime per process
@@ -307,6 +314,8 @@ class SlabSimulation:
         self.box = tuple(float(b) for b in box)
         self.grid = tuple(int(g) for g in grid)
         self.params = capi.default_params(self.box, self.grid) if params is None else params
+        # where the layers lie: the params' own box (it need not be centred on the origin)
+        self.z_range = None if params is None else (float(params.box_min[2]), float(params.box_max[2]))
         # which protocol THIS class's Python step speaks (NativeSlabSimulation's step is the library's: its own `protocol`)
         self.python_protocol = int(python_protocol)
         if self.python_protocol == 1:
@@ -322,7 +331,7 @@ class SlabSimulation:
         if particles is not None:
             pos_all, vel_all = particles
             self.total = int(pos_all.shape[0])
-            layers = cell_layer_of(pos_all[:, 2], self.box[2], gz)
+            layers = cell_layer_of(pos_all[:, 2], self.box[2], gz, self.z_range)
             hist = np.bincount(layers, minlength=gz)
             self.cuts = choose_cuts(hist, self.world, self.min_layers)
             z_lo, z_hi = self.cuts[self.rank], self.cuts[self.rank + 1]
@@ -340,7 +349,7 @@ class SlabSimulation:
             for iz in range(iz0, iz1):
                 p, _ = ic.dam_break_lattice((nx, ny, nz), self.box, jitter, start=iz * nx * ny, count=nx * ny,
                                             jitter_dims=jd)
-                hist += np.bincount(cell_layer_of(p[:, 2], self.box[2], gz), minlength=gz)
+                hist += np.bincount(cell_layer_of(p[:, 2], self.box[2], gz, self.z_range), minlength=gz)
             hist = comm.allreduce_sum(hist).astype(np.int64)
             self.cuts = choose_cuts(hist, self.world, self.min_layers)
             z_lo, z_hi = self.cuts[self.rank], self.cuts[self.rank + 1]
@@ -348,8 +357,8 @@ class SlabSimulation:
             spacing, radius = float(ic.SPACING), float(ic.PARTICLE_RADIUS)
             amp = 0.5 * float(jd[2]) * 0.01 * radius if jitter else 0.0
             zc = -self.box[2] / 2 + radius + spacing * np.arange(nz)
-            lo_l = cell_layer_of(zc - amp - 1e-4, self.box[2], gz)
-            hi_l = cell_layer_of(zc + amp + 1e-4, self.box[2], gz)
+            lo_l = cell_layer_of(zc - amp - 1e-4, self.box[2], gz, self.z_range)
+            hi_l = cell_layer_of(zc + amp + 1e-4, self.box[2], gz, self.z_range)
             cand = np.nonzero((hi_l >= z_lo) & (lo_l < z_hi))[0]
             # Whole lattice layers, none of them straddling a cut (every BASELINE config: the lattice planes sit a quarter
             # of a cell from the faces, the jitter is 0.08 of a cell): the slab's particles are ONE run of creation
@@ -363,7 +372,7 @@ class SlabSimulation:
             for iz in cand:
                 start = int(iz) * nx * ny
                 p, _ = ic.dam_break_lattice((nx, ny, nz), self.box, jitter, start=start, count=nx * ny, jitter_dims=jd)
-                lay = cell_layer_of(p[:, 2], self.box[2], gz)
+                lay = cell_layer_of(p[:, 2], self.box[2], gz, self.z_range)
                 keep = (lay >= z_lo) & (lay < z_hi)
                 chunks_p.append(p[keep])
                 chunks_i.append((start + np.nonzero(keep)[0]).astype(np.uint32))
@@ -562,7 +571,7 @@ class SlabSimulation:
             local = np.asarray(e.layer_histogram(), dtype=np.int64)
         else:
             pos, _, _ = e.download_owned()
-            layers = cell_layer_of(pos[:, 2], self.box[2], gz) if pos.shape[0] else np.zeros(0, np.int64)
+            layers = cell_layer_of(pos[:, 2], self.box[2], gz, self.z_range) if pos.shape[0] else np.zeros(0, np.int64)
             local = np.bincount(layers, minlength=gz).astype(np.int64)
         return self.comm.allreduce_sum(local).astype(np.int64)
 
@@ -586,7 +595,7 @@ class SlabSimulation:
         if cuts is None:
             return False
         pos, vel, idx = e.download_owned()
-        layers = cell_layer_of(pos[:, 2], self.box[2], gz) if pos.shape[0] else np.zeros(0, np.int64)
+        layers = cell_layer_of(pos[:, 2], self.box[2], gz, self.z_range) if pos.shape[0] else np.zeros(0, np.int64)
         dest = np.searchsorted(np.asarray(cuts[1:-1]), layers, side="right")    # rank that owns each layer now
         rec = np.zeros((pos.shape[0], REC), np.float32)
         rec[:, 0:3] = pos; rec[:, 3] = idx.view(np.float32); rec[:, 4:7] = vel

@@ -177,7 +177,11 @@ uint32_t sph_capacity(const sph_ctx* c);
  * of the wave in units of h (x as a coarse + a fine half, one reference per group of lanes that lie within 6 h in
  * y and z and 1000 h in x: right at any extent of the wave while a cell is at most 12 h wide), with NORMALISED kernel sums (the reference's densities ~2e6 do not
  * fit fp16); row sums are added up in fp32 and scaled once.  The force and collision passes stay fp32 (decided on
- * a device measurement).  Looser tolerance: DESIGN.md section 4. */
+ * a device measurement).  Looser tolerance: DESIGN.md section 4.
+ * A mixed density depends on which 64 slots share a wave (the reference point is the wave's).  A slab context's waves are
+ * not the whole-domain context's, so in mixed precision an N-slab run (sph_slab_step) equals the one-context run to the mixed
+ * tolerance, NOT bit for bit, under either message protocol (sph_slab_set_protocol); where the packed fp16 arithmetic is exact
+ * the two agree to fp32 rounding (tests/test_gpu_slabs_mixed.py holds both). */
 enum { SPH_PRECISION_F32 = 0, SPH_PRECISION_MIXED_F16 = 1 };
 int sph_set_precision(sph_ctx* c, int precision);
 int sph_get_precision(const sph_ctx* c);
@@ -1037,6 +1041,11 @@ int sph_slab_timing_get(sph_slab* s, double out[SPH_SLAB_T_WORDS]);
  * ghost layers (sph_create_slab_layers) and slabs of >= 4 cell layers; a particle that crosses more than TWO layers in a step is
  * SPH_E_STATE under it.  COLLECTIVE in effect: every rank of the chain must run the same protocol.  Price: ~2x the halo bytes and
  * the density of one more layer per side; gain: two message latencies off the step's critical path.
+ * Accepted on a SPH_PRECISION_MIXED_F16 context too.  There a ghost's recomputed density is computed in the RECEIVER's waves,
+ * not the owner's: it is the owner's value wherever the packed fp16 arithmetic is exact and within the mixed tolerance of it
+ * otherwise, so the two ends of a pair may use densities of one particle that differ by that much.  In
+ * mixed precision an N-slab run equals the one-context run to the mixed tolerance, not bit for bit, under EITHER protocol
+ * (sph_set_precision; tests/test_gpu_slabs_mixed.py).
  * sph_slab_protocol: out = {protocol, one-message steps so far, of which needed the second message}. */
 int sph_slab_set_protocol(sph_slab* s, int groups);
 /* [introspect] */ int sph_slab_protocol(const sph_slab* s, uint64_t out[3]);

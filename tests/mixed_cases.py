@@ -2,7 +2,8 @@
 documents about its walks -- TEST INFRASTRUCTURE, imports without a GPU.
 
 tests/test_mixed_cases_cpu.py shows on the CPU that the bars the GPU tests use are reachable and that the cases reach the
-walks they are meant for; tests/test_gpu_mixed_walks.py runs them on the device.
+walks they are meant for; tests/test_gpu_mixed_walks.py runs them on the device, tests/test_gpu_slabs_mixed.py the moving
+tower (d_tower) inside the z-slab step.
 
 DYADIC cases -- why the packed fp16 arithmetic is EXACT on them, and the bar is therefore the fp32 one (1e-5):
 h = 0.125, box_min = (-2, -2, -2), and every particle sits on a site box_min + (k + 0.5) h/2 without jitter.  Hence
@@ -111,6 +112,31 @@ def _droplet_sites():
 @lru_cache(maxsize=None)
 def d_droplets():
     return _case("D-droplets", _sites(_droplet_sites()), _dyadic_params((32, 32, 32)))
+
+
+TOWER_SHIFTS = 12                      # d_tower(0) .. d_tower(12): the block stays 2 sites and more below the top wall
+TOWER_VEL = (0.0, 0.0, 64.0)           # every particle's velocity; with TOWER_DT one step moves every particle one site up
+TOWER_DT = 2.0 ** -10
+
+
+@lru_cache(maxsize=None)
+def d_tower(shift=0):
+    """A dyadic case that MOVES and stays dyadic: 16 x 16 x 72 sites thinned to ~60 % (11,167 particles, the same ones for
+    every shift) in a box 48 cell layers of edge h tall, `shift` sites above its start.  No gravity, and a rest density above
+    every density of the case, so every pressure is 0.  With the velocity TOWER_VEL on every particle a step of TOWER_DT is a
+    rigid translation by exactly one site (h/2 in z): pressure terms are 0 times finite values, viscous terms are 0 (no
+    relative velocity), no collision has r.v < 0, a = 0, and x += 2^-10 * 64 is exact in fp32 on multiples of 2^-5.  So
+    the state after k steps from d_tower(0) is d_tower(k), bit for bit, and the block crosses a cell layer every second step.
+    The box is 48 h tall, not 36: (p - ref) / h stays below 64 all the same."""
+    p = params(DY_MIN, (2, 2, 4), (32, 32, 48), DY_H)
+    p.gravity_y = F(0)
+    p.rest_density = F(2 ** 19)
+    assert 0 <= shift <= TOWER_SHIFTS
+    return _case(f"D-tower+{shift}", _sites(_thinned_block((24, 24, 8 + shift), (16, 16, 72), 0.6, 111)), p, shift=shift)
+
+
+def tower_velocity(n):
+    return np.tile(np.asarray(TOWER_VEL, F), (n, 1))
 
 
 DYADIC = {"D-block": d_block, "D-wide-4h": lambda: d_wide(4), "D-wide-12h": lambda: d_wide(12), "D-droplets": d_droplets}

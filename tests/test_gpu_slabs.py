@@ -291,6 +291,38 @@ def test_slab_entry_points_directly():
         assert c.n == len(mine) - want[3] and c.slab_counts()[0] == want[0]
 
 
+@pytest.mark.parametrize("local_layers", [30, 31, 60, 61, 64])
+def test_layer_histogram_past_one_chunk_of_targets(local_layers):
+    """sph_layer_histogram finds the layers' ends 30 targets at a time and carries the last end of a chunk into the next: 30
+    local layers are one full chunk, 31 one layer more, 60 two full chunks, 61 and 64 a third.  A whole-domain context, slab
+    contexts over the whole grid with one and two ghost layers per side (their lowest ghost layer is global layer -1 or -2,
+    their highest gz or gz + 1: neither has an entry in the histogram) and a slab in the middle of a taller grid whose ghost
+    layers hold leavers; particles in every layer but a random fifth of them, which stay empty.  The integers of np.bincount
+    over the float32 cell layers."""
+    L = local_layers
+    kinds = {"whole": (L, None, 1), "slab, 1 ghost layer": (L - 2, (0, L - 2), 1), "slab, 2 ghost layers": (L - 4, (0, L - 4), 2),
+             "middle slab": (L + 6, (4, 4 + L - 2), 1)}
+    for k, (what, (gz, zs, ghost_layers)) in enumerate(kinds.items()):
+        box, grid = (1.0, 1.0, gz / 8.0), (8, 8, gz)
+        rng = np.random.default_rng(1000 * L + k)
+        pos = ((rng.random((3000, 3)) - 0.5) * np.array(box) * 0.999).astype(np.float32)
+        layers = slab.cell_layer_of(pos[:, 2], box[2], gz)
+        # a slab context is given the particles of its would-be ghost layers too (leavers: counted in their global layer)
+        lo, hi = (max(zs[0] - 1, 0), min(zs[1], gz - 1)) if zs else (0, gz - 1)
+        empty = lo + rng.permutation(hi - lo + 1)[:(hi - lo + 1) // 5]
+        keep = ~np.isin(layers, empty) & (layers >= lo) & (layers <= hi)
+        pos, layers = pos[keep], layers[keep]
+        want = np.bincount(layers, minlength=gz).astype(np.uint32)
+        assert np.count_nonzero(want[lo:hi + 1] == 0) == empty.size >= 5 and want.sum() == pos.shape[0], what
+        with capi.Context(pos.shape[0] + 64, params=capi.default_params(box, grid), slab=zs, ghost_capacity=1024 if zs else 0,
+                          ghost_layers=ghost_layers) as c:
+            c.upload(pos, np.zeros_like(pos))
+            c.hash(); c.sort()
+            got = c.layer_histogram()
+        assert got.dtype == np.uint32 and got.shape == (gz,)
+        assert np.array_equal(got, want), (what, L, np.nonzero(got != want)[0][:8], got[got != want][:8], want[got != want][:8])
+
+
 @pytest.mark.parametrize("transport,protocol", [("local", 3), ("host", 3), ("local", 1)])
 def test_rebalance_on_gpu_engines(transport, protocol):
     """slab.SlabSimulation.rebalance() with the product engine: the fluid drifts out of its slabs, the

@@ -63,6 +63,24 @@ def test_cell_layer_matches_the_oracle_hash():
     o.close()
 
 
+def test_cell_layer_of_a_box_off_the_origin():
+    """A params whose box is not centred on the origin (the tower of tests/mixed_cases.py: z from -2 to 4, 48 layers): the
+    set-up bins by that box, as the device and the float64 model's float32 cell coordinates do; a centred box given as a
+    range gives the layers it gives without one."""
+    import mixed_cases as mc
+    import sph_model
+    for shift in (0, 1, mc.TOWER_SHIFTS):
+        case = mc.d_tower(shift)
+        p = case.params
+        want = sph_model.Model(p).cells(case.pos)[:, 2]
+        got = slab.cell_layer_of(case.pos[:, 2], 6.0, 48, (float(p.box_min[2]), float(p.box_max[2])))
+        assert np.array_equal(got, want)
+        assert not np.array_equal(slab.cell_layer_of(case.pos[:, 2], 6.0, 48), want)
+    pos, _, box, grid = make_case("up")
+    assert np.array_equal(slab.cell_layer_of(pos[:, 2], box[2], grid[2], (-box[2] / 2, box[2] / 2)),
+                          slab.cell_layer_of(pos[:, 2], box[2], grid[2]))
+
+
 @pytest.mark.parametrize("case,world", [("up", 3), ("down", 2), ("shear", 4)])
 def test_slabs_in_process_match_single_domain(case, world):
     steps = 24
