@@ -47,6 +47,13 @@ __device__ __forceinline__ uint32_t ordered_block(uint32_t b, uint32_t nb, const
     return base + j;
 }
 
+// ---- the lane's element of an array that starts at a wave-uniform address: `base` stays in SGPRs and `lane_bytes` (the lane id
+//      times the element size, formed once per kernel) is the load's 32-bit VGPR offset -- no 64-bit address arithmetic per load.
+template <class T>
+__device__ __forceinline__ T lane_elem(const T* base, uint32_t lane_bytes) {
+    return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + lane_bytes);
+}
+
 // ---- wave64 reductions over DPP (no LDS): row reductions by quad_perm / mirrors, then
 //      row_bcast15 / row_bcast31 carry the partial results to lane 63 (gfx9 DPP controls).
 template <int CTRL, int ROW_MASK = 0xF>

@@ -53,6 +53,7 @@ constexpr int PIECE = 128;          // staged candidates per piece (2 coalesced 
 typedef float v2f __attribute__((ext_vector_type(2)));
 typedef const volatile __attribute__((address_space(3))) v2f* lds_v2f_ptr;
 typedef const volatile __attribute__((address_space(3))) float* lds_f32_ptr;
+typedef const volatile __attribute__((address_space(3))) char* lds_byte_ptr;
 
 // ---- cell table -----------------------------------------------------------------------------------
 // {start, end} per occupied cell; empty cells stay {0, 0}.  Only the cells touched by the previous
@@ -348,28 +349,39 @@ __device__ __forceinline__ void wave_hulls(const Rows& R, Hulls& H) {
 }
 
 // Walk the 9 rows: stage every piece [a, b) of a row's hull through registers into the wave's LDS
-// slice (`load(a)` issues the global loads, `store()` writes them to LDS) and call `pieces(r, a, b)`
-// for the per-lane work.  The first piece of the NEXT row is requested before the current piece
-// is processed, so its global-memory latency hides behind the pair arithmetic.
-//
+// slice (`load(a)` issues the global loads, `store()` writes them to LDS) and call `work(r, a, b)`
+// for the per-lane work.  The NEXT piece -- of this row, or the first one of the next non-empty row -- is requested
+// as soon as the current one is in LDS and before it is processed, so its global-memory latency hides behind the
+// pair arithmetic.  There is ONE `load` in front of the rows and ONE per row, behind `store()`, where the staging
+// registers are dead: with loads at three places of a row (its first piece unless prefetched, every further piece,
+// the next row's first) hipcc kept two sets of staging registers and copied one into the other and back at every row:
+// 28 v_mov_b32 per row in k_force, 12 in k_density (profiles/pair_row_bookkeeping_ab.txt).
 template <class Load, class Store, class Work>
 __device__ __forceinline__ void traverse(const Hulls& H, Load&& load, Store&& store, Work&& work) {
-    bool ready = false;
+    auto first_behind = [&](int r, uint32_t& a) {          // start of the first non-empty row behind row r, if there is one
+        bool any = false;
+#pragma unroll
+        for (int q = 8; q > r; q--) {
+            uint32_t end = H.B[q];                           // (an empty row's hull is [0, 0): wave_hulls)
+            asm volatile("" : "+s"(end));                   // a fresh scalar compare at every use: kept alive, the flags of nine rows are 18 SGPRs
+            if (end != 0u) { a = H.A[q]; any = true; }
+        }
+        return any;
+    };
+    uint32_t a_next = 0u;
+    if (!first_behind(-1, a_next)) return;
+    load(a_next);
 #pragma unroll
     for (int r = 0; r < 9; r++) {
         if (H.A[r] >= H.B[r]) continue;          // wave-uniform
-        if (!ready) load(H.A[r]);
-        ready = false;
         for (uint32_t a = H.A[r]; a < H.B[r]; a += PIECE) {
-            const uint32_t b = min(a + PIECE, H.B[r]);
-            if (a != H.A[r]) load(a);
             store();
-            if (b >= H.B[r] && r + 1 < 9 && H.A[r + 1] < H.B[r + 1]) {
-                load(H.A[r + 1]);
-                ready = true;
-            }
+            bool more = true;
+            a_next = a + PIECE;
+            if (a_next >= H.B[r]) more = first_behind(r, a_next);
+            if (more) load(a_next);
             wave_lds_sync();
-            work(r, a, b);
+            work(r, a, min(a + PIECE, H.B[r]));
             wave_lds_sync();
         }
     }
@@ -447,6 +459,24 @@ __device__ __forceinline__ bool wave_targets(const Targets& T, uint32_t wave, ui
     return first < hi;
 }
 
+#ifdef SPH_PAIR_STATS
+__device__ unsigned long long g_pair_stats[12];  // debug build only (-DSPH_PAIR_STATS): waves, pieces, walk length, chunks, collision rounds,
+                                                 // waves with a hull > 256 / 512 / 2048 slots, [8] sum over waves of the busiest LANE's collision
+                                                 // candidates (what a per-particle queue would have to work off), [9] sum over all lanes of them,
+                                                 // [10] / [11] candidates walked under the per-lane range test in k_force / k_density
+__device__ int g_pair_stats_on;
+#define PAIR_STAT(k, v) do { if (lane == 0 && g_pair_stats_on) atomicAdd(&g_pair_stats[k], (unsigned long long)(v)); } while (0)
+extern "C" void sph_debug_pair_stats(unsigned long long* out, int on) {     // read + clear the counters, then count or not
+    (void)hipDeviceSynchronize();
+    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pair_stats), sizeof(g_pair_stats));
+    unsigned long long z[12] = {};
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_pair_stats), z, sizeof(z));
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_pair_stats_on), &on, sizeof(on));
+}
+#else
+#define PAIR_STAT(k, v) do { } while (0)
+#endif
+
 // ---- density + pressure (kernelComputeDensities, particleSystem.cu:132-187) ---------------------------
 // rho_i = sum_{j in 27 cells, r2 < h2} m * POLY6 * (h2 - r2)^3   (self included)   (.cu:28-37)
 // p_i   = max(0, k * (rho_i - rho0))                                              (.cu:15-17)
@@ -495,6 +525,7 @@ __global__ __launch_bounds__(THREADS, SPH_DENS_OCC) void k_density(const float4*
     Hulls H;
     wave_hulls(R, H);
     float4 q0, q1;
+    const uint32_t lane16 = lane << 4;
     float acc = 0.f;
     const float h2_v = in_vgpr(ph.h2);
     // one candidate; the staged walk and the direct walk share it, so a row gives the same bits either way
@@ -530,8 +561,9 @@ __global__ __launch_bounds__(THREADS, SPH_DENS_OCC) void k_density(const float4*
     traverse(
         H,
         [&](uint32_t a) {   // the arrays are padded by 2*PIECE entries: no bounds predicate needed
-            q0 = posi[a + lane];
-            q1 = posi[a + WAVE + lane];
+            const float4* const pa = posi + a;                   // wave-uniform: the lane's part of the address is formed once
+            q0 = lane_elem(pa, lane16);
+            q1 = lane_elem(pa + WAVE, lane16);
         },
         [&]() {
             s_xy[slice + lane] = make_float2(q0.x, q0.y);
@@ -552,7 +584,8 @@ __global__ __launch_bounds__(THREADS, SPH_DENS_OCC) void k_density(const float4*
             const uint32_t tmin = wave_min_u32_uniform_first(len) & ~(uint32_t)(UNROLL - 1);
             // z pairs: candidates (rel, rel + 1), (rel + 2, rel + 3), ... -- from s_z when rel is even, else from the copy
             // shifted by one, where candidate rel sits at the even index rel - 1
-            lds_v2f_ptr zp = (lds_v2f_ptr)((rel & 1u) ? (const float*)s_zo : (const float*)s_z) + ((slice + rel) >> 1);
+            // (slice is even: rel's parity is the entry's.  An odd rel reads from s_zo + (slice + rel - 1): one index, two bases)
+            lds_v2f_ptr zp = (lds_v2f_ptr)(((rel & 1u) ? (const float*)s_zo - 1 : (const float*)s_z) + idx);
             auto group = [&](uint32_t t, bool check) {
 #pragma unroll
                 for (int u = 0; u < UNROLL; u += 2) {
@@ -566,9 +599,13 @@ __global__ __launch_bounds__(THREADS, SPH_DENS_OCC) void k_density(const float4*
             };
             uint32_t t = 0;
             for (; t < tmin; t += UNROLL) group(t, false);
+#ifdef SPH_PAIR_STATS
+            const uint32_t stat_t0 = t;
+#endif
             // until every lane is through its range.  (A final HALF group for a remainder <= 2 was tried: 3 LDS reads fewer per
             // wave, but 22 VALU and 21 SALU more -- every row pays the second test; profiles/pair_clamp_drain_ab.txt.)
             for (; __ballot(t < len) != 0ull; t += UNROLL) group(t, true);
+            PAIR_STAT(11, t - stat_t0);
         });
     finish();
 }
@@ -993,22 +1030,6 @@ __device__ __forceinline__ void integrate_one(const Phys& ph, float dt, float4& 
 //   dv += m (1 + e) (r.v / d^2) r, count++ ; finally dv = -dv / (m (1 + count)).
 // The reference runs three separate traversals plus an integrate pass; FORCE, COLL and INTEG select
 // what this instantiation does so that the phase API can still run them one at a time.
-#ifdef SPH_PAIR_STATS
-__device__ unsigned long long g_pair_stats[12];  // debug build only (-DSPH_PAIR_STATS): waves, pieces, walk length, chunks, collision rounds,
-                                                 // waves with a hull > 256 / 512 / 2048 slots, [8] sum over waves of the busiest LANE's collision
-                                                 // candidates (what a per-particle queue would have to work off), [9] sum over all lanes of them
-__device__ int g_pair_stats_on;
-#define PAIR_STAT(k, v) do { if (lane == 0 && g_pair_stats_on) atomicAdd(&g_pair_stats[k], (unsigned long long)(v)); } while (0)
-extern "C" void sph_debug_pair_stats(unsigned long long* out, int on) {     // read + clear the counters, then count or not
-    (void)hipDeviceSynchronize();
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pair_stats), sizeof(g_pair_stats));
-    unsigned long long z[12] = {};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_pair_stats), z, sizeof(z));
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_pair_stats_on), &on, sizeof(on));
-}
-#else
-#define PAIR_STAT(k, v) do { } while (0)
-#endif
 // Sph: empty, or Spheres for the collider instantiation of the fused pass (one more argument: the sphere table, by value), or
 // SpheresTracked for a tracked context's (the table by pointer and the impulse outputs)
 // CLAMP: the r < h cut as the fma's clamp modifier (cut_below_zero); the host launches it only while h <= 1
@@ -1028,6 +1049,7 @@ __global__ __launch_bounds__(THREADS, SPH_FORCE_OCC) void k_force(
     // the same 2.56 ms -- at 8 particles per cell every 16-byte-aligned stride is a two-way bank conflict.  Not kept:
     // profiles/r05_force_b128_experiment.txt.)
     constexpr int E2 = 5;
+    constexpr uint32_t EB = E2 * sizeof(float2);          // bytes per candidate
     constexpr int ENT = lds_ent(THREADS);
     __shared__ float2 s_e[ENT * 5];
     // a range read from device memory: the grid is an upper bound, whole blocks beyond the range leave before the zero-fill
@@ -1203,6 +1225,8 @@ __global__ __launch_bounds__(THREADS, SPH_FORCE_OCC) void k_force(
     traverse(
         H,
         [&](uint32_t a) {
+            // (plain indexing: with the wave-uniform base of k_density's loads this kernel has 70 VALU fewer per wave and 1.5 % MORE
+            // busy cycles, profiles/pair_row_bookkeeping_ab.txt)
             q0 = posi[a + lane]; q1 = posi[a + WAVE + lane];
             w0 = velr[a + lane]; w1 = velr[a + WAVE + lane];
             if (FORCE) { e0 = cw[a + lane]; e1 = cw[a + WAVE + lane]; }
@@ -1226,7 +1250,9 @@ __global__ __launch_bounds__(THREADS, SPH_FORCE_OCC) void k_force(
             const uint32_t len = l1 > l0 ? l1 - l0 : 0u;
             uint32_t T, tmin_raw;                       // a known trip count lets hipcc interleave two candidates
             wave_min_max_u32(len, tmin_raw, T);
-            uint32_t idx = slice + (len ? l0 - a : 0u);
+            // the walk's position in s_e in BYTES (EB per candidate): the induction variable IS the LDS offset, so no chunk and
+            // no round of the drain multiplies an index by the 40-byte stride (a quarter-rate v_mul_lo_u32)
+            uint32_t idx = __umul24(slice + (len ? l0 - a : 0u), EB);
             // Candidates are walked in chunks of 32.  The pressure/viscosity arithmetic runs for every
             // candidate; the collision test only records "d <= 2R" in a per-lane bit mask (2 VALU per
             // candidate) and the few close pairs (~4 of ~216 per particle) are worked off after the chunk.
@@ -1235,7 +1261,7 @@ __global__ __launch_bounds__(THREADS, SPH_FORCE_OCC) void k_force(
             uint32_t near = 0u;
             PAIR_STAT(1, 1); PAIR_STAT(2, T);
             auto pair = [&](int u, bool valid) {
-                const lds_v2f_ptr e = (lds_v2f_ptr)s_e + (idx + u) * 5;
+                const lds_v2f_ptr e = (lds_v2f_ptr)((lds_byte_ptr)s_e + (idx + u * EB));
                 const v2f qa = e[0], qb = e[1];
                 v2f qc = {0.f, 0.f}, qd = {0.f, 0.f};
                 if (FORCE) { qc = e[2]; qd = e[3]; }
@@ -1253,13 +1279,14 @@ __global__ __launch_bounds__(THREADS, SPH_FORCE_OCC) void k_force(
                 for (; t < tsafe; t += SPH_FORCE_UNROLL) {
 #pragma unroll
                     for (int u = 0; u < SPH_FORCE_UNROLL; u++) pair(u, true);
-                    idx += SPH_FORCE_UNROLL;
+                    idx += SPH_FORCE_UNROLL * EB;
                     done += SPH_FORCE_UNROLL;
                 }
+                PAIR_STAT(10, t < tend ? (tend - t + SPH_FORCE_UNROLL - 1u) & ~(uint32_t)(SPH_FORCE_UNROLL - 1) : 0u);
                 for (; t < tend; t += SPH_FORCE_UNROLL) {
 #pragma unroll
                     for (int u = 0; u < SPH_FORCE_UNROLL; u++) pair(u, t + u < len);
-                    idx += SPH_FORCE_UNROLL;
+                    idx += SPH_FORCE_UNROLL * EB;
                     done += SPH_FORCE_UNROLL;
                 }
 #ifdef SPH_PAIR_STATS
@@ -1280,8 +1307,7 @@ __global__ __launch_bounds__(THREADS, SPH_FORCE_OCC) void k_force(
                     while (near != 0u) {
                         const uint32_t hb = 31u - (uint32_t)__clz((int)near);
                         near &= ~(1u << hb);
-                        const uint32_t ci = idx0 + (done - 1u - hb);
-                        const float2* e = &s_e[(ci << 2) + ci];          // ci * 5 without v_mul_lo_u32
+                        const float2* e = (const float2*)((const char*)s_e + (idx0 + __umul24(done - 1u - hb, EB)));      // (a full-rate 24-bit multiply)
                         const float2 qa = e[0], qb = e[1], qc = e[2];
                         collide_math(qa.x, qa.y, qb.x, qb.y, qc.x, qc.y);
                     }
