@@ -504,10 +504,35 @@ int launch_unpack_dp(hipStream_t st, const float2* src_lo, float2* dp_lo, float2
 constexpr uint32_t LB_MAX = 32;
 struct LbTargets { uint32_t v[LB_MAX]; uint32_t m; };
 int launch_lower_bounds(hipStream_t st, const uint32_t* keys, uint32_t n, const LbTargets& tg, uint32_t* out, volatile uint32_t* out_host);
-// the ends of a slab's boundary layers in its sorted keys, G ghost layers per side: first ghost | first owned layer | ... | last | ghost
+// The bounds a slab step looks up in its sorted owned keys (k_slab_bounds_pack, sph_slab.hip): the first slot whose key lies in
+// local layer bound_layer(b, G, zl) or above.  G ghost layers per side: the owned layers are the local layers [G, zl - G);
+// "layer k" counts from the first owned layer = 1 on the low side, "layer zl-k" mirrors it on the high side.
+enum Bound {
+    B_OWN_BEGIN, B_FIRST_END,       // the first four in ascending order: the start of the owned layers (what lies in front leaves
+    B_LAST_BEGIN, B_OWN_END,        // downwards), the end of the first one, the start of the last one, their end (the rest leaves upwards)
+    B_DEEP_LO, B_DEEP_HI,           // the deep interior, layers [4, zl-4): at least three layers from either cut
+    B_NEAR_LO, B_NEAR_HI,           // the start of layer 3 / of layer zl-3: the layers next to the deep interior
+    B_EARLY_LO, B_EARLY_HI,         // layers [6, zl-6): their force pass reads densities of the deep launch only
+    B_LAYER5,                       // the start of layer 5, to check exactly that
+    B_COUNT
+};
+__host__ __device__ inline uint32_t bound_layer(uint32_t b, uint32_t G, uint32_t zl) {
+    // thin slabs: a range that does not exist is empty (its end clamped to its start), every target a layer of the grid
+    // (a constant table indexed HERE becomes a chain of selects in the kernel; one returned by value went to LDS, 44 bytes a thread)
+    const uint32_t d0 = min(G + 3u, zl - 1u), d1 = zl >= 2u * G + 6u ? zl - G - 3u : d0;
+    const uint32_t e0 = min(G + 2u, zl - 1u), e1 = zl >= 2u * G + 4u ? zl - G - 2u : e0;
+    const uint32_t f0 = min(G + 5u, zl - 1u), f1 = zl >= 2u * G + 11u ? zl - G - 5u : f0;
+    const uint32_t d_end = max(d1, d0), e_end = max(e1, e0), f_end = max(f1, f0), layer5 = min(G + 4u, zl - 1u);
+    const uint32_t z[B_COUNT] = {G, G + 1u, zl - G - 1u, zl - G,    // B_OWN_BEGIN, B_FIRST_END, B_LAST_BEGIN, B_OWN_END
+                                 d0, d_end, e0, e_end,              // B_DEEP_LO, B_DEEP_HI, B_NEAR_LO, B_NEAR_HI
+                                 f0, f_end, layer5};                // B_EARLY_LO, B_EARLY_HI, B_LAYER5
+    return z[b];
+}
+// the ends of a slab's boundary layers in its sorted keys, in ascending order: first ghost | first owned layer | ... | last | ghost
 inline LbTargets layer_bound_targets(const sph_ctx* c) {
     const uint32_t layer = c->grid.g[0] * c->grid.g[1], G = c->ghost_layers, zl = c->grid.zl;
-    return LbTargets{{G * layer, (G + 1u) * layer, (zl - G - 1u) * layer, (zl - G) * layer}, 4u};
+    return LbTargets{{bound_layer(B_OWN_BEGIN, G, zl) * layer, bound_layer(B_FIRST_END, G, zl) * layer,
+                      bound_layer(B_LAST_BEGIN, G, zl) * layer, bound_layer(B_OWN_END, G, zl) * layer}, 4u};
 }
 // record 0 of both send buffers (a message's header)
 int launch_headers(hipStream_t st, float4* out_lo, float4* out_hi, float4 lo, float4 hi);

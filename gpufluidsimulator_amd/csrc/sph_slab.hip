@@ -7,9 +7,9 @@
 //   -----------                                   -----------
 //   hash + sort owned particles
 //   k_slab_bounds_pack: layer bounds, leavers
-//     + header {#leavers, #boundary, #far}     -> exchange MIGRANTS (header + 255 inline records: 8 KB)
+//     + header (SlabHeader)                    -> exchange MIGRANTS (header + 255 inline records: 8 KB)
 //   density of the DEEP interior (layers >= 4        k_slab_post_headers: own bounds + the neighbours' headers
-//     from either cut; its slot range is read        into mapped host memory, then a sequence word
+//     from either cut; its slot range is read        into mapped host memory (HostWords), then a sequence word
 //     from DEVICE memory: the host does not
 //     know the bounds yet)
 //   [early stream, behind the deep density by event: force+collision+integrate of the INNERMOST layers (>= 6 from either
@@ -69,37 +69,65 @@
 
 namespace sph {
 
-// words of the pinned, mapped host block the step's one wait reads (sph_slab::h_lb)
-enum {
-    HL_LB = 0,        // [0..3] own layer bounds: first slot (relative to the owned range) with a key >= layer, 2*layer,
-                      //        (zl-2)*layer, (zl-1)*layer
-    HL_DEEP = 4,      // [4..5] the deep interior [first key >= 4*layer, first key >= (zl-4)*layer), ABSOLUTE slots
-    HL_FAR = 6,       // [6..7] my leavers (down, up) that are NOT in the neighbour's adjacent layer (crossed > 1 layer)
-    HL_HDR_LO = 8,    // [8..11]  header received from the lower neighbour {#arrivals, #its boundary layer, #far, abort}
-    HL_HDR_HI = 12,   // [12..15] ... from the upper neighbour
-    HL_SEQ = 16,      // written last: the step number
-    HL_ERR = 17,      // [17..18] sticky error words set by device-side checks (plain stores of 1): SLAB_ERR_*
-    HL_NEAR = 20,     // [20..21] first slot of local layer 3 / of local layer zl-3 (ABSOLUTE): the layers next to the deep interior
-    HL_EARLY = 22,    // [22..23] the slots whose force pass may run in front of the wait: local layers [6, zl-6) (ABSOLUTE; empty: equal)
-    HL_RECUT = 24,    // [24..25] sph_slab_recut: particles that go down / up ; [26..27] what the neighbours send (from below, from above)
-    HL_HDR2_LO = 32,  // [32..35] second header word group from the lower neighbour {#its second layer, #very far leavers, 0, 0}
-    HL_HDR2_HI = 36,  // [36..39] ... from the upper neighbour
-    HL_VFAR = 40,     // [40..41] my leavers (down, up) that are not even in the neighbour's SECOND layer (crossed > 2 layers)
-    HL_WORDS = 48
+enum Side { LO = 0, HI = 1 };      // towards rank - 1 / rank + 1: the index of every per-side pair below
+
+// ---- a first message (MIGRANTS, ONE, the re-cut's counts): record 0 is the header, the particle records follow ----------------
+constexpr size_t REC = 2 * sizeof(float4);      // a particle record: position, velocity
+// The header, in wire order.  k_slab_bounds_pack writes all of it; an abort header or a re-cut count header (bare_header, written
+// through launch_headers) is its first four words only: words 4-7 of those are whatever the buffer held, and nobody reads them.
+struct alignas(16) SlabHeader {
+    uint32_t leavers;       // records that follow as this step's leavers (the re-cut: particles that change owner)
+    uint32_t boundary;      // what stays in the sender's boundary layer on that side
+    uint32_t far;           // leavers that are NOT in the receiver's adjacent layer (crossed > 1 layer)
+    uint32_t abort;         // the sender failed: nothing more comes from it
+    uint32_t second;        // what stays in the sender's SECOND layer on that side
+    uint32_t very_far;      // leavers of EITHER side that are not even in a neighbour's second layer (crossed > 2 layers)
+    uint32_t zero[2];
+};
+static_assert(sizeof(SlabHeader) == REC, "a header is one record");
+constexpr uint32_t REC4 = REC / sizeof(float4), HDR4 = sizeof(SlabHeader) / sizeof(float4);      // float4s per record, per header
+__host__ __device__ inline SlabHeader* header_of(float4* buf) { return reinterpret_cast<SlabHeader*>(buf); }
+__host__ __device__ inline float4* records_of(float4* buf) { return buf + HDR4; }       // the records behind the header
+
+// the pinned, mapped host block the step's one wait reads (sph_slab::host), filled by k_slab_post_headers
+struct HostWords {
+    uint32_t bounds[4];     // own layer bounds B_OWN_BEGIN .. B_OWN_END, slots relative to the owned range
+    uint32_t deep[2];       // the deep interior [first key in layer 4, first key in layer zl-4) on a 64-slot chunk, ABSOLUTE slots
+    uint32_t far[2];        // my leavers (down, up) that are NOT in the neighbour's adjacent layer (crossed > 1 layer)
+    SlabHeader hdr[2];      // the headers received from the lower / upper neighbour
+    uint32_t seq;           // written last: the step number
+    uint32_t err[2];        // sticky error words set by device-side checks (plain stores of 1): SLAB_ERR_*
+    uint32_t near[2];       // first slot of local layer 3 / of local layer zl-3 (ABSOLUTE): the layers next to the deep interior
+    uint32_t early[2];      // the slots whose force pass may run in front of the wait: local layers [6, zl-6) (ABSOLUTE; empty: equal)
+    uint32_t recut_out[2];  // sph_slab_recut: particles that go down / up
+    uint32_t recut_in[2];   // ... and what the neighbours send (from below, from above)
+    uint32_t vfar;          // my leavers of either side that are not even in the neighbour's SECOND layer (crossed > 2 layers)
 };
 enum { SLAB_ERR_INSERT_LAYER = 0, SLAB_ERR_ARRIVAL_OUTSIDE = 1 };
-// device words (sph_slab::d_lb): [0..3] bounds, [4..5] deep range (absolute), [6..7] far counts, [8..10] the
-// fused kernel's block counters {far down, far up, blocks done}
-enum { DL_DEEP = 4, DL_FAR = 6, DL_CTR = 8, DL_NEAR = 12, DL_PING = 14, DL_EARLY = 16, DL_VFAR = 18, DL_CTR2 = 20, DL_WORDS = 24 };
+// its device counterpart (sph_slab::dev), written by k_slab_bounds_pack; every pair on an 8-byte boundary
+struct DevWords {
+    uint32_t bounds[4], deep[2], far[2], near[2], early[2];     // as in HostWords; deep and early: the ranges the launches in
+                                                                 // front of the wait read (launch_density / force_dev_range)
+    uint32_t far_ctr[2], vfar_ctr, blocks_done;                  // the bounds kernel's tickets: far / very far leavers so far, blocks done
+    uint32_t vfar;
+    uint32_t ping;                                               // sph_slab_ping: words that did not match
+};
 
 constexpr uint32_t MIG_INLINE = 255;   // leavers per side that ride in the first (fixed-size, 8 KB) migrant message
 
-// ONE kernel after the sort: every block finds the six layer bounds of the sorted owned keys (six threads, binary
-// searches over L2-resident lines: cheaper than a kernel boundary), then the blocks pack the leavers -- they sit at
-// the two ends of the sorted owned range, [0, lb0) go down, [lb3, n) go up -- and count the FAR ones: a leaver whose
-// true cell layer is not the neighbour's adjacent layer (it crossed more than one layer in a step; its key is clamped
-// into my ghost layer, so only its position can tell).  The block that finishes last writes record 0 of both
-// messages, the header {#leavers, #particles that stay in my boundary layer on that side, #far leavers, 0}, and the
+// particles of the SECOND owned layer next to either cut, from the bounds (slots relative to the owned range): what a header
+// says of the sender (k_slab_bounds_pack) and what the sender itself adds to the size of its next one-message step (step_headers)
+__host__ __device__ inline void second_layer_counts(uint32_t first_end, uint32_t last_begin, uint32_t near_lo, uint32_t near_hi,
+                                                    uint32_t n2[2]) {
+    n2[LO] = max(near_lo, first_end) - first_end;
+    n2[HI] = last_begin - min(near_hi, last_begin);
+}
+
+// ONE kernel after the sort: every block finds the layer bounds of the sorted owned keys (a wave per bound, searches
+// over L2-resident lines: cheaper than a kernel boundary), then the blocks pack the leavers -- they sit at
+// the two ends of the sorted owned range, [0, B_OWN_BEGIN) go down, [B_OWN_END, n) go up -- and count the FAR ones: a leaver
+// whose true cell layer is not the neighbour's adjacent layer (it crossed more than one layer in a step; its key is clamped
+// into my ghost layer, so only its position can tell).  The block that finishes last writes both messages' SlabHeader and the
 // device words the deep-interior density launch reads its slot range from.
 // first slot in [0, n) with keys[slot] >= v, by ONE WAVE: 64 probes per round at equal spacing, 4 rounds for 16.7 M keys
 // (a lane-per-target binary search is 24 DEPENDENT loads, ~0.8 us each from a cold L2: this kernel sits between the
@@ -128,7 +156,7 @@ __device__ __forceinline__ uint32_t wave_lower_bound(const uint32_t* __restrict_
 __global__ __launch_bounds__(256) void k_slab_bounds_pack(const uint32_t* __restrict__ keys, const float4* __restrict__ posi,
                                                           const float4* __restrict__ velr, uint32_t n, uint32_t own_off,
                                                           uint32_t layer, uint32_t cap, GridDesc g, uint32_t early_cap,
-                                                          uint32_t* __restrict__ dl, float4* __restrict__ out_lo,
+                                                          DevWords* __restrict__ dl, float4* __restrict__ out_lo,
                                                           float4* __restrict__ out_hi, uint32_t pack_blocks,
                                                           const uint32_t* __restrict__ keys_abs, uint2* __restrict__ cells,
                                                           volatile uint32_t* __restrict__ ends_host, uint32_t G, uint32_t two_layers,
@@ -137,7 +165,7 @@ __global__ __launch_bounds__(256) void k_slab_bounds_pack(const uint32_t* __rest
         cells_build_thread(keys_abs, own_off, own_off + n, cells, ends_host, 0u, (blockIdx.x - pack_blocks) * 256u + threadIdx.x);
         return;
     }
-    __shared__ uint32_t s_lb[12];
+    __shared__ uint32_t s_lb[(B_COUNT + 3u) & ~3u];          // (whole 16-byte rows)
     __shared__ uint32_t s_last;
     const uint32_t zl = g.zl;
     {
@@ -145,39 +173,32 @@ __global__ __launch_bounds__(256) void k_slab_bounds_pack(const uint32_t* __rest
         // slabs of fewer than 7 owned layers).  Two would do for the density itself (arrivals land in the boundary
         // layer, the ghosts beyond it); the third lets the boundary layers' force launch -- which, rounded to whole
         // 64-slot chunks, reaches into the second layer and so reads densities of the third -- run on the comm stream
-        // without waiting for the deep launch (the host checks that it really stays inside: targets 6 and 7)
-        // (G = ghost layers per side: the owned layers are the local layers [G, zl - G); "layer k" in these comments counts from
-        // the first owned layer = 1, as with one ghost layer)
-        const uint32_t d0 = min(G + 3u, zl - 1u), d1 = zl >= 2u * G + 6u ? zl - G - 3u : d0;
-        const uint32_t e0 = min(G + 2u, zl - 1u), e1 = zl >= 2u * G + 4u ? zl - G - 2u : e0;
-        // [8..10]: the EARLY force range, local layers [6, zl-6) -- particles whose 27 cells lie in layers 5 .. zl-6, all of
+        // without waiting for the deep launch (the host checks that it really stays inside: B_NEAR_LO and B_NEAR_HI)
+        // B_EARLY_*: the EARLY force range, local layers [6, zl-6) -- particles whose 27 cells lie in layers 5 .. zl-6, all of
         // whose densities the deep launch (layers >= 4, from a chunk boundary inside layer 4) has written: their force pass
-        // needs nothing that comes over a link or moves before it.  [10] = first slot of layer 5, to check exactly that.
-        const uint32_t f0 = min(G + 5u, zl - 1u), f1 = zl >= 2u * G + 11u ? zl - G - 5u : f0;
-        const uint32_t targets[11] = {G * layer, (G + 1u) * layer, (zl - G - 1u) * layer, (zl - G) * layer, d0 * layer, max(d1, d0) * layer,
-                                      e0 * layer, max(e1, e0) * layer, f0 * layer, max(f1, f0) * layer, min(G + 4u, zl - 1u) * layer};
+        // needs nothing that comes over a link or moves before it.  B_LAYER5 = first slot of layer 5, to check exactly that.
         const uint32_t wave = threadIdx.x >> 6;
-        for (uint32_t t = wave; t < 11u; t += 4u) {                         // wave w: targets w, w + 4, w + 8
-            const uint32_t r = wave_lower_bound(keys, n, targets[t]);
+        for (uint32_t t = wave; t < B_COUNT; t += 4u) {                     // wave w: bounds w, w + 4, w + 8
+            const uint32_t r = wave_lower_bound(keys, n, bound_layer(t, G, zl) * layer);
             if ((threadIdx.x & 63u) == 0u) s_lb[t] = r;
         }
     }
     __syncthreads();
-    const uint32_t lb0 = s_lb[0], lb3 = s_lb[3];
+    const uint32_t lb0 = s_lb[B_OWN_BEGIN], lb3 = s_lb[B_OWN_END];
     const uint32_t m_lo = lb0, m_hi = n - lb3;
     uint32_t far_l = 0, far_h = 0;                     // per thread (a thread packs several leavers when there are many)
     uint32_t vfar = 0;                                 // leavers of either side beyond the neighbour's SECOND layer
     for (uint32_t k = blockIdx.x * 256u + threadIdx.x; k < cap && (k < m_lo || k < m_hi); k += pack_blocks * 256u) {
         if (k < m_lo) {
             const float4 p = posi[k];
-            put_record(out_lo + 2, k, p, velr[k]);
+            put_record(records_of(out_lo), k, p, velr[k]);
             const int lz = (int)cell_coord(p.z, g.box_min[2], g.box_dims[2], g.gf[2], g.g[2]);
             far_l += lz != g.z_off + (int)G - 1 ? 1u : 0u;    // not global layer z_lo - 1
             vfar += lz < g.z_off + (int)G - 2 ? 1u : 0u;
         }
         if (k < m_hi) {
             const float4 p = posi[lb3 + k];
-            put_record(out_hi + 2, k, p, velr[lb3 + k]);
+            put_record(records_of(out_hi), k, p, velr[lb3 + k]);
             const int lz = (int)cell_coord(p.z, g.box_min[2], g.box_dims[2], g.gf[2], g.g[2]);
             far_h += lz != g.z_off + (int)zl - (int)G ? 1u : 0u;   // not global layer z_hi
             vfar += lz > g.z_off + (int)zl - (int)G + 1 ? 1u : 0u;
@@ -188,10 +209,10 @@ __global__ __launch_bounds__(256) void k_slab_bounds_pack(const uint32_t* __rest
         // order -- [first layer | second layer] towards the lower neighbour, [second-last | last] towards the upper one: for the
         // receiver both are two of ITS ghost layers in ascending key order.  Slices that have been final since the sort: the
         // receiver merges its own leavers in (k_slab_unpack_ghosts_merge), so nothing waits for this rank's arrivals.
-        const uint32_t r_lo0 = lb0, r_lo1 = max(s_lb[6], lb0), r_hi0 = min(s_lb[7], lb3), r_hi1 = lb3;
+        const uint32_t r_lo0 = lb0, r_lo1 = max(s_lb[B_NEAR_LO], lb0), r_hi0 = min(s_lb[B_NEAR_HI], lb3), r_hi1 = lb3;
         const uint32_t n_rl = min(r_lo1 - r_lo0, cap2), n_rh = min(r_hi1 - r_hi0, cap2);
-        float4* const dl_ = out_lo + 2u * (1u + min(m_lo, cap));
-        float4* const dh_ = out_hi + 2u * (1u + min(m_hi, cap));
+        float4* const dl_ = records_of(out_lo) + REC4 * min(m_lo, cap);               // behind the leavers
+        float4* const dh_ = records_of(out_hi) + REC4 * min(m_hi, cap);
         for (uint32_t k = blockIdx.x * 256u + threadIdx.x; k < n_rl + n_rh; k += pack_blocks * 256u) {
             if (k < n_rl) put_record(dl_, k, posi[r_lo0 + k], velr[r_lo0 + k]);
             else { const uint32_t j = k - n_rl; put_record(dh_, j, posi[r_hi0 + j], velr[r_hi0 + j]); }
@@ -201,35 +222,37 @@ __global__ __launch_bounds__(256) void k_slab_bounds_pack(const uint32_t* __rest
     // returned value is awaited, so an add has been performed before its wave passes the barrier below) -- no fence
     uint32_t seen = 0;
     if (__ballot(far_l | far_h) != 0ull) {            // rare: somebody crossed more than one layer
-        if (far_l) seen += atomicAdd(&dl[DL_CTR + 0], far_l);
-        if (far_h) seen += atomicAdd(&dl[DL_CTR + 1], far_h);
-        if (vfar) seen += atomicAdd(&dl[DL_CTR2], vfar);
+        if (far_l) seen += atomicAdd(&dl->far_ctr[LO], far_l);
+        if (far_h) seen += atomicAdd(&dl->far_ctr[HI], far_h);
+        if (vfar) seen += atomicAdd(&dl->vfar_ctr, vfar);
     }
     asm volatile("" :: "v"(seen));                                        // keep the returns (and their waits)
     __syncthreads();
-    if (threadIdx.x == 0) s_last = atomicAdd(&dl[DL_CTR + 2], 1u) == pack_blocks - 1u ? 1u : 0u;
+    if (threadIdx.x == 0) s_last = atomicAdd(&dl->blocks_done, 1u) == pack_blocks - 1u ? 1u : 0u;
     __syncthreads();
     if (!s_last || threadIdx.x != 0) return;
-    const uint32_t far_lo = atomicExch(&dl[DL_CTR + 0], 0u), far_hi = atomicExch(&dl[DL_CTR + 1], 0u);
-    const uint32_t vfar_all = atomicExch(&dl[DL_CTR2], 0u);                            // (either side: any of them fails the one-message step)
-    atomicExch(&dl[DL_CTR + 2], 0u);                                                   // re-armed for the next step
-    // header, 8 words: {#leavers, #my boundary layer on that side, #far leavers, abort} {#my SECOND layer on that side, #very far, 0, 0}
-    const uint32_t n2_lo = max(s_lb[6], s_lb[1]) - s_lb[1], n2_hi = s_lb[2] - min(s_lb[7], s_lb[2]);
-    out_lo[0] = make_float4(__uint_as_float(m_lo), __uint_as_float(s_lb[1] - lb0), __uint_as_float(far_lo), 0.f);
-    out_lo[1] = make_float4(__uint_as_float(n2_lo), __uint_as_float(vfar_all), 0.f, 0.f);
-    out_hi[0] = make_float4(__uint_as_float(m_hi), __uint_as_float(lb3 - s_lb[2]), __uint_as_float(far_hi), 0.f);
-    out_hi[1] = make_float4(__uint_as_float(n2_hi), __uint_as_float(vfar_all), 0.f, 0.f);
-    dl[DL_VFAR] = vfar_all; dl[DL_VFAR + 1] = vfar_all;
-    for (int t = 0; t < 4; t++) dl[t] = s_lb[t];
+    const uint32_t far_lo = atomicExch(&dl->far_ctr[LO], 0u), far_hi = atomicExch(&dl->far_ctr[HI], 0u);
+    const uint32_t vfar_all = atomicExch(&dl->vfar_ctr, 0u);                           // (either side: any of them fails the one-message step)
+    atomicExch(&dl->blocks_done, 0u);                                                  // re-armed for the next step
+    uint32_t n2[2];
+    second_layer_counts(s_lb[B_FIRST_END], s_lb[B_LAST_BEGIN], s_lb[B_NEAR_LO], s_lb[B_NEAR_HI], n2);
+    SlabHeader h[2] = {};
+    h[LO].leavers = m_lo; h[LO].boundary = s_lb[B_FIRST_END] - lb0; h[LO].far = far_lo; h[LO].second = n2[LO];
+    h[HI].leavers = m_hi; h[HI].boundary = lb3 - s_lb[B_LAST_BEGIN]; h[HI].far = far_hi; h[HI].second = n2[HI];
+    h[LO].very_far = h[HI].very_far = vfar_all;
+    *header_of(out_lo) = h[LO];
+    *header_of(out_hi) = h[HI];
+    dl->vfar = vfar_all;
+    for (int t = 0; t < 4; t++) dl->bounds[t] = s_lb[t];
     // the deep range starts on a 64-slot chunk of what will be the owned range once the lower leavers are gone (the usual
     // step: no arrivals): the launch over "everything that is not deep" cuts its hole on whole waves from there
     // (targets_with_hole rounds the hole's start UP), so the two launches -- on two streams -- cover disjoint slots
     // instead of both writing the up to 63 slots in front of the first whole chunk (the same values: benign, but unordered)
-    const uint32_t deep0 = lb0 + ((s_lb[4] - lb0 + 63u) & ~63u);
-    dl[DL_DEEP] = own_off + deep0;
-    dl[DL_DEEP + 1] = own_off + max(s_lb[5], deep0);
-    dl[DL_FAR] = far_lo; dl[DL_FAR + 1] = far_hi;
-    dl[DL_NEAR] = own_off + s_lb[6]; dl[DL_NEAR + 1] = own_off + max(s_lb[7], s_lb[6]);
+    const uint32_t deep0 = lb0 + ((s_lb[B_DEEP_LO] - lb0 + 63u) & ~63u), deep1 = max(s_lb[B_DEEP_HI], deep0);
+    dl->deep[0] = own_off + deep0;
+    dl->deep[1] = own_off + deep1;
+    dl->far[LO] = far_lo; dl->far[HI] = far_hi;
+    dl->near[LO] = own_off + s_lb[B_NEAR_LO]; dl->near[HI] = own_off + max(s_lb[B_NEAR_HI], s_lb[B_NEAR_LO]);
     {   // empty unless every slot of layer 5 (and so of every layer up to zl-6) lies inside the deep range
         // and no longer than early_cap slots: the launch is there to fill the links' latency, not to run beside the interior
         // launch for its whole length (two big k_force grids side by side evict each other's L2 working sets)
@@ -237,9 +260,10 @@ __global__ __launch_bounds__(256) void k_slab_bounds_pack(const uint32_t* __rest
         // 64, and the launch over "everything that is not deep" then re-rounds the hole's start -- it recomputes up to 63
         // slots at the head of the deep range on ANOTHER stream.  Same bits in fp32, but in mixed precision a density depends on
         // which particles share a wave: no slot the early launch reads -- layer 5 onwards -- may lie in that head.)
-        const bool ok = zl >= 2u * G + 11u && s_lb[10] >= deep0 + 64u && s_lb[9] <= max(s_lb[5], deep0) && s_lb[9] > s_lb[8];
-        dl[DL_EARLY] = own_off + s_lb[8];
-        dl[DL_EARLY + 1] = own_off + (ok ? min(s_lb[9], s_lb[8] + early_cap) : s_lb[8]);
+        const uint32_t e0 = s_lb[B_EARLY_LO], e1 = s_lb[B_EARLY_HI];
+        const bool ok = zl >= 2u * G + 11u && s_lb[B_LAYER5] >= deep0 + 64u && e1 <= deep1 && e1 > e0;
+        dl->early[0] = own_off + e0;
+        dl->early[1] = own_off + (ok ? min(e1, e0 + early_cap) : e0);
     }
 }
 
@@ -263,38 +287,46 @@ __global__ __launch_bounds__(256) void k_slab_early_finish(const uint32_t* __res
     }
 }
 
-// word 0 and word 3 of a header that says nothing else (launch_headers): a count (the re-cut's first message), or "abort" -- a
-// rank that failed tells its neighbours in the header of its NEXT migrant message
+// the first four words (what launch_headers writes) of a header that says nothing else: a count (the re-cut's first message), or
+// "abort" -- a rank that failed tells its neighbours in the header of its NEXT migrant message
 static float4 bare_header(uint32_t count, uint32_t abort) {
-    float4 h = make_float4(0.f, 0.f, 0.f, 0.f);
-    memcpy(&h.x, &count, 4);
-    memcpy(&h.w, &abort, 4);
-    return h;
+    SlabHeader h = {};
+    h.leavers = count; h.abort = abort;
+    float4 first;
+    memcpy(&first, &h, sizeof first);
+    return first;
 }
 
 // comm stream, right behind the migrant exchange: everything the host's one wait needs, in one mapped block, the
-// sequence word last (a system-scope fence in between: the host polls that word and then reads the rest)
-__global__ void k_slab_post_headers(const uint32_t* __restrict__ dl, const float4* __restrict__ hdr_lo,
-                                    const float4* __restrict__ hdr_hi, volatile uint32_t* __restrict__ host, uint32_t seq) {
+// sequence word last (a system-scope fence in between: the host polls that word and then reads the rest).  The err words
+// are not written here: they are sticky across steps.
+__global__ void k_slab_post_headers(const DevWords* __restrict__ dl, const SlabHeader* __restrict__ hdr_lo,
+                                    const SlabHeader* __restrict__ hdr_hi, volatile HostWords* __restrict__ host, uint32_t seq) {
+    // the named words of a header, in wire order
+    constexpr uint32_t SlabHeader::*word[6] = {&SlabHeader::leavers, &SlabHeader::boundary, &SlabHeader::far,
+                                                &SlabHeader::abort,   &SlabHeader::second,   &SlabHeader::very_far};
     const uint32_t t = threadIdx.x;                       // one wave: a lane per word, all stores in flight together
-    if (t < 8u) host[t] = dl[t];
-    else if (t == 16u || t == 17u) host[HL_NEAR + (t - 16u)] = dl[DL_NEAR + (t - 16u)];
-    else if (t == 18u || t == 19u) host[HL_EARLY + (t - 18u)] = dl[DL_EARLY + (t - 18u)];
-    else if (t == 20u || t == 21u) host[HL_VFAR + (t - 20u)] = dl[DL_VFAR + (t - 20u)];
-    else if (t >= 32u && t < 40u) {                           // words 4..7 of the neighbours' headers
-        const float4* h = t < 36u ? hdr_lo : hdr_hi;
-        const uint32_t* hw = reinterpret_cast<const uint32_t*>(h);
-        host[t] = h ? hw[4u + ((t - 32u) & 3u)] : 0u;         // {#its second layer, #very far leavers, 0, 0}
+    const uint32_t* src = nullptr;                        // (a lane picks its two addresses: then ONE load and ONE store)
+    volatile uint32_t* dst = nullptr;
+    auto words = [&](uint32_t first, uint32_t count, const uint32_t* from, volatile uint32_t* to) {
+        if (t - first < count) { src = from + (t - first); dst = to + (t - first); }
+    };
+    words(0u, 4u, dl->bounds, host->bounds);
+    words(4u, 2u, dl->deep, host->deep);
+    words(6u, 2u, dl->far, host->far);
+    words(8u, 2u, dl->near, host->near);
+    words(10u, 2u, dl->early, host->early);
+    words(12u, 1u, &dl->vfar, &host->vfar);
+    if (t - 16u < 12u) {                                  // the neighbours' headers (no neighbour: zeros)
+        const uint32_t side = (t - 16u) / 6u, w = (t - 16u) % 6u;
+        const SlabHeader* in = side == LO ? hdr_lo : hdr_hi;
+        src = in ? &(in->*word[w]) : nullptr;
+        dst = &(host->hdr[side].*word[w]);
     }
-    else if (t < 16u) {
-        const float4* h = t < 12u ? hdr_lo : hdr_hi;
-        const uint32_t w = (t - 8u) & 3u;
-        const uint32_t* hw = reinterpret_cast<const uint32_t*>(h);
-        host[t] = h ? hw[w] : 0u;                             // {#arrivals, #its boundary layer, #far, abort}
-    }
+    if (dst) *dst = src ? *src : 0u;
     __threadfence_system();
     __builtin_amdgcn_wave_barrier();
-    if (t == 0u) host[HL_SEQ] = seq;
+    if (t == 0u) host->seq = seq;
 }
 
 // (density, pressure) of both boundary layers -> messages, one launch (the way back, with the neighbour terms: launch_unpack_dp)
@@ -771,7 +803,7 @@ int loop_exchange(void* self, int tag, const void* send_lo, size_t send_lo_bytes
     const uint32_t n_up = (uint32_t)(send_hi_bytes / 16), n_down = (uint32_t)(send_lo_bytes / 16);
     if (n_up + n_down) {
         hipLaunchKernelGGL(k_loop_copy, dim3(min(ceil_div(n_up + n_down, 256u), 2048u)), dim3(256), 0, st, (const float4*)send_hi,
-                           (float4*)recv_lo, n_up, (const float4*)send_lo, (float4*)recv_hi, n_down, (tag == SPH_TAG_MIGRANTS || tag == SPH_TAG_ONE) ? 2u : 0u,
+                           (float4*)recv_lo, n_up, (const float4*)send_lo, (float4*)recv_hi, n_down, (tag == SPH_TAG_MIGRANTS || tag == SPH_TAG_ONE) ? HDR4 : 0u,
                            E->shift, recs ? 1 : 0);
         SPH_HIP(hipGetLastError());
     }
@@ -793,7 +825,7 @@ struct sph_slab {
     sph_ctx* c = nullptr;
     sph::Buffers mem;                    // every device and pinned buffer below (slab_free)
     int rank = 0, world = 1;
-    bool has_lo = false, has_hi = false;
+    bool has[2] = {false, false};        // a neighbour on that side (Side: LO = rank - 1, HI = rank + 1)
     sph_transport tr{};
     bool host_staged = false;            // the transport wants host buffers (tests); else device pointers on the comm stream
     hipStream_t comm = nullptr;
@@ -810,10 +842,10 @@ struct sph_slab {
     hipStream_t early = nullptr;         // the early force launch's own stream (behind the deep density by event): its tail then runs
     hipEvent_t ev_early_go = nullptr, ev_early_done = nullptr;   // beside the interior launch instead of in front of it
     uint32_t gcap = 0, mcap = 0;         // halo / migrant capacity per side, in records
-    uint32_t* d_lb = nullptr;            // DL_* words: layer bounds, deep-interior range, far counts, block counters (device)
-    volatile uint32_t* h_lb = nullptr;   // HL_* words (pinned, mapped): what the step's one wait reads
-    uint32_t* h_lb_dev = nullptr;        // its device view
-    uint32_t seq = 0;                    // step number the device echoes into h_lb[HL_SEQ]
+    DevWords* dev = nullptr;             // layer bounds, deep-interior range, far counts, block counters (device)
+    volatile HostWords* host = nullptr;  // pinned, mapped: what the step's one wait reads
+    HostWords* host_dev = nullptr;       // its device view
+    uint32_t seq = 0;                    // step number the device echoes into host->seq
     double wait_timeout_s = 120.0;       // bound of the poll (sph_slab_set_wait_timeout; SPH_SLAB_TIMEOUT_S)
     int device = 0;                      // copied from the context: destroy does not touch it
     float4* mig_send[2] = {nullptr, nullptr};   // (1 + mcap) records of 2 float4
@@ -899,8 +931,8 @@ hipEvent_t slab_timing_event(sph_slab* s) {
 // ones get pinned host copies (the comm stream is drained first: a test transport, not the product path).
 int slab_exchange_raw(sph_slab* s, int tag, const void* send_lo, size_t send_lo_bytes, void* recv_lo, size_t recv_lo_bytes,
                       const void* send_hi, size_t send_hi_bytes, void* recv_hi, size_t recv_hi_bytes) {
-    if (!s->has_lo || s->pg.peer_dead[0]) send_lo_bytes = recv_lo_bytes = 0;
-    if (!s->has_hi || s->pg.peer_dead[1]) send_hi_bytes = recv_hi_bytes = 0;
+    if (!s->has[LO] || s->pg.peer_dead[LO]) send_lo_bytes = recv_lo_bytes = 0;
+    if (!s->has[HI] || s->pg.peer_dead[HI]) send_hi_bytes = recv_hi_bytes = 0;
     s->exchanges++;
     if (!s->host_staged) {
         int rc = s->tr.exchange(s->tr.self, tag, send_lo, send_lo_bytes, recv_lo, recv_lo_bytes, send_hi, send_hi_bytes, recv_hi,
@@ -939,8 +971,7 @@ int slab_exchange(sph_slab* s, const Msg& m) {
     return rc;
 }
 
-// ---- the message groups.  A particle record is a position and a velocity; record 0 of a migrant buffer is the header.
-constexpr size_t REC = 2 * sizeof(float4);
+// ---- the message groups.  A particle record is a position and a velocity (REC bytes); record 0 of a migrant buffer is its SlabHeader.
 
 // records of a one-message group per side, from what the same link carried in the previous step: a margin of 1/16 + 1024
 // records, whole 64-record chunks (slab.py mirrors it: SlabSimulation.one_message_rows)
@@ -1021,8 +1052,8 @@ struct OnComm {
 int slab_wait_headers(sph_slab* s) {
     const auto t0 = std::chrono::steady_clock::now();
     uint32_t spins = 0;
-    if (s->h_lb[HL_SEQ] == s->seq) s->waits_ready++;          // the device got here first: this step is paced by the host
-    while (s->h_lb[HL_SEQ] != s->seq) {
+    if (s->host->seq == s->seq) s->waits_ready++;             // the device got here first: this step is paced by the host
+    while (s->host->seq != s->seq) {
         __builtin_ia32_pause();
         if ((++spins & 0x3FFFu) == 0u) {
             const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -1043,10 +1074,10 @@ int slab_wait_headers(sph_slab* s) {
 }
 
 int slab_check_device_flags(sph_slab* s) {
-    SPH_REQUIRE(s->h_lb[HL_ERR + SLAB_ERR_INSERT_LAYER] == 0u, SPH_E_STATE,
+    SPH_REQUIRE(s->host->err[SLAB_ERR_INSERT_LAYER] == 0u, SPH_E_STATE,
                 "rank %d: an arriving particle was not in the boundary layer next to the cut it crossed (the sorted order of "
                 "that layer is invalid)", s->rank);
-    SPH_REQUIRE(s->h_lb[HL_ERR + SLAB_ERR_ARRIVAL_OUTSIDE] == 0u, SPH_E_STATE,
+    SPH_REQUIRE(s->host->err[SLAB_ERR_ARRIVAL_OUTSIDE] == 0u, SPH_E_STATE,
                 "rank %d: an arriving particle lies outside this slab altogether (it crossed a whole slab in one step)", s->rank);
     return SPH_OK;
 }
@@ -1064,7 +1095,7 @@ int slab_timing_collect(sph_slab* s) {
     return SPH_OK;
 }
 
-// The step's state from phase to phase (slab_step_body).  Counts per side: _lo towards rank - 1, _hi towards rank + 1.
+// The step's state from phase to phase (slab_step_body).  Per-side counts are indexed by Side.
 struct Step {
     float dt = 0.f;
     std::chrono::steady_clock::time_point t_begin, t_waited;
@@ -1075,15 +1106,17 @@ struct Step {
     bool early_launched = false, early_pending = false;   // the early force launch: queued / the main stream has not joined it yet
     uint32_t early_done_v = 0, early_grid_slots = 0;      // (the sequence number of that join: hop_mark) ; its grid
     // ---- from the headers (step_headers)
-    uint32_t lb0 = 0, lb1 = 0, lb2 = 0, lb3 = 0, deep_lo = 0, deep_hi = 0, near_lo = 0, near_hi = 0, early_lo = 0, early_hi = 0;
-    uint32_t m_lo = 0, m_hi = 0, far_lo = 0, far_hi = 0;          // my leavers, and the far ones among them
-    uint32_t in_lo = 0, in_hi = 0, far_in_lo = 0, far_in_hi = 0;  // the arrivals, and the far ones among them
-    uint32_t own_lo = 0, own_hi = 0;                              // my boundary layers (the arrivals included: step_settle)
-    uint32_t peer_own_lo = 0, peer_own_hi = 0, n2p_lo = 0, n2p_hi = 0;   // the neighbours' boundary and second layers
-    uint32_t tot_s[2] = {0, 0}, tot_r[2] = {0, 0};                // records either end of a link packed: the next ONE step's sizes
+    uint32_t lb[4] = {0, 0, 0, 0};                   // B_OWN_BEGIN .. B_OWN_END
+    uint32_t deep[2] = {0, 0}, early[2] = {0, 0};    // slot ranges [begin, end): the deep density's, the early force launch's
+    uint32_t near[2] = {0, 0};                       // first slot of layer 3 / of layer zl-3
+    uint32_t m[2] = {0, 0}, far[2] = {0, 0};         // my leavers, and the far ones among them
+    uint32_t in[2] = {0, 0}, far_in[2] = {0, 0};     // the arrivals, and the far ones among them
+    uint32_t own[2] = {0, 0};                        // my boundary layers (the arrivals included: step_settle)
+    uint32_t peer_own[2] = {0, 0}, n2p[2] = {0, 0};  // the neighbours' boundary and second layers
+    uint32_t tot_s[2] = {0, 0}, tot_r[2] = {0, 0};   // records either end of a link packed: the next ONE step's sizes
     bool early_halo = false;                         // no arrivals: the halo work goes to the comm stream at once
     // ---- the ghosts and the slot ranges of the passes (step_ghosts)
-    uint32_t n = 0, g_lo = 0, g_hi = 0, h_lo = 0, h_hi = 0, a = 0, b = 0;
+    uint32_t n = 0, g[2] = {0, 0}, h[2] = {0, 0}, a = 0, b = 0;
     bool need_deep_event = false;
     uint32_t deep_v = 0;
 };
@@ -1105,9 +1138,8 @@ int step_pre_wait(sph_slab* s, Step& st) {
     // first step of a burst).  The first step after a create / re-cut has no such counts and runs the three-group protocol.
     st.p1 = s->protocol == 1 && s->one_ready && s->world > 1;
     for (int k = 0; k < 2; k++) {
-        const bool has = k == 0 ? s->has_lo : s->has_hi;
-        st.S_s[k] = st.p1 && has ? one_cap(s->one_prev_s[k]) : 0u;
-        st.S_r[k] = st.p1 && has ? one_cap(s->one_prev_r[k]) : 0u;
+        st.S_s[k] = st.p1 && s->has[k] ? one_cap(s->one_prev_s[k]) : 0u;
+        st.S_r[k] = st.p1 && s->has[k] ? one_cap(s->one_prev_r[k]) : 0u;
     }
     s->pg.group[sph_slab::G_FIRST] = msg_migrants(s);
     if (st.p1) {
@@ -1132,7 +1164,7 @@ int step_pre_wait(sph_slab* s, Step& st) {
     // grid-stride loops; behind them the blocks that build the cell table of the owned slots when the sort left it pending (not on a skipped sort)
     const uint32_t pack_blocks = st.p1 ? 128u : min(ceil_div(s->mcap, 256u), 16u), build_blocks = owned_build_pending ? cells_build_blocks(st.n0) : 0u;
     hipLaunchKernelGGL(k_slab_bounds_pack, dim3(pack_blocks + build_blocks), dim3(256), 0, c->stream, c->keyS + st.off0, c->posi + st.off0,
-                       c->velr + st.off0, st.n0, st.off0, st.layer, s->mcap, c->grid, s->early_cap, s->d_lb, s->mig_send[0], s->mig_send[1],
+                       c->velr + st.off0, st.n0, st.off0, st.layer, s->mcap, c->grid, s->early_cap, s->dev, s->mig_send[LO], s->mig_send[HI],
                        pack_blocks, c->keyS, c->table.cells, c->mm_count_host_dev + HW_FIRST_KEY, c->ghost_layers, st.p1 ? 1u : 0u, s->gcap);
     SPH_HIP(hipGetLastError());
     rc = after_main(s); if (rc) return rc;
@@ -1143,7 +1175,7 @@ int step_pre_wait(sph_slab* s, Step& st) {
     st.deep_valid = c->grid.zl >= 2u * st.G + 7u;
     if (st.deep_valid) {
         PhaseTimer t(c, SPH_PH_DENS);
-        rc = launch_density_dev_range(c, s->d_lb + DL_DEEP, st.n0);
+        rc = launch_density_dev_range(c, &s->dev->deep[0], st.n0);
         if (rc) return rc;
     }
     // ---- and behind it, on the early stream, the fused force pass of the innermost layers (local layers [6, zl-6): every
@@ -1166,7 +1198,7 @@ int step_pre_wait(sph_slab* s, Step& st) {
         rc = hop_wait(s, HOP_MAIN_EARLY, s->early, s->ev_early_go, go); if (rc) return rc;
         hipStream_t saved = c->stream;
         c->stream = s->early;
-        { PhaseTimer t(c, SPH_PH_FORCE); rc = launch_force_dev_range(c, s->d_lb + DL_EARLY, st.early_grid_slots, st.dt); }
+        { PhaseTimer t(c, SPH_PH_FORCE); rc = launch_force_dev_range(c, &s->dev->early[0], st.early_grid_slots, st.dt); }
         c->stream = saved;
         if (rc) return rc;
         rc = hop_mark(s, HOP_EARLY_MAIN, s->early, s->ev_early_done, &st.early_done_v); if (rc) return rc;
@@ -1176,8 +1208,8 @@ int step_pre_wait(sph_slab* s, Step& st) {
     }
     s->pg.posted[sph_slab::G_FIRST] = true;                    // (also when the call fails: the transport is dead then)
     rc = slab_exchange(s, s->pg.group[sph_slab::G_FIRST]); if (rc) return rc;
-    hipLaunchKernelGGL(k_slab_post_headers, dim3(1), dim3(64), 0, s->comm, s->d_lb, s->has_lo ? s->mig_recv[0] : (float4*)nullptr,
-                       s->has_hi ? s->mig_recv[1] : (float4*)nullptr, s->h_lb_dev, s->seq);
+    hipLaunchKernelGGL(k_slab_post_headers, dim3(1), dim3(64), 0, s->comm, s->dev, s->has[LO] ? header_of(s->mig_recv[LO]) : nullptr,
+                       s->has[HI] ? header_of(s->mig_recv[HI]) : nullptr, s->host_dev, s->seq);
     SPH_HIP(hipGetLastError());
     return SPH_OK;
 }
@@ -1190,22 +1222,18 @@ void record_owed(sph_slab* s, const Step& st) {
     sph_slab::Progress& g = s->pg;
     auto umin = [](uint32_t x, uint32_t y) { return x < y ? x : y; };
     const uint32_t inl0 = umin(MIG_INLINE, s->mcap);
-    const uint32_t mm[2] = {umin(st.m_lo, s->mcap), umin(st.m_hi, s->mcap)}, ii[2] = {umin(st.in_lo, s->mcap), umin(st.in_hi, s->mcap)};
-    const uint32_t own[2] = {st.own_lo, st.own_hi}, peer[2] = {st.peer_own_lo, st.peer_own_hi},
-                   fo[2] = {umin(st.far_lo, st.m_lo), umin(st.far_hi, st.m_hi)}, fi[2] = {umin(st.far_in_lo, st.in_lo), umin(st.far_in_hi, st.in_hi)},
-                   mraw[2] = {st.m_lo, st.m_hi}, iraw[2] = {st.in_lo, st.in_hi};
-    const bool any_rest = st.m_lo > inl0 || st.m_hi > inl0 || st.in_lo > inl0 || st.in_hi > inl0;
+    const bool any_rest = st.m[LO] > inl0 || st.m[HI] > inl0 || st.in[LO] > inl0 || st.in[HI] > inl0;
     uint32_t rest_s[2], rest_r[2], h[2] = {0, 0}, gh[2] = {0, 0}, next_s[2], next_r[2];
     for (int k = 0; k < 2; k++) {
-        const bool has = k == 0 ? s->has_lo : s->has_hi;
         if (st.p1) {                  // all that can still be owed is the part of the one message that did not fit its fixed size
             rest_s[k] = st.tot_s[k] > st.S_s[k] ? umin(st.tot_s[k], s->msg_cap) - st.S_s[k] : 0u;
             rest_r[k] = st.tot_r[k] > st.S_r[k] ? umin(st.tot_r[k], s->msg_cap) - st.S_r[k] : 0u;
         } else {
-            rest_s[k] = any_rest && mm[k] > inl0 ? mm[k] - inl0 : 0u;
-            rest_r[k] = any_rest && ii[k] > inl0 ? ii[k] - inl0 : 0u;
-            h[k] = has ? umin(own[k] + iraw[k] - fi[k], s->gcap) : 0u;
-            gh[k] = has ? umin(peer[k] + mraw[k] - fo[k], s->gcap) : 0u;
+            const uint32_t mm = umin(st.m[k], s->mcap), ii = umin(st.in[k], s->mcap);
+            rest_s[k] = any_rest && mm > inl0 ? mm - inl0 : 0u;
+            rest_r[k] = any_rest && ii > inl0 ? ii - inl0 : 0u;
+            h[k] = s->has[k] ? umin(st.own[k] + st.in[k] - umin(st.far_in[k], st.in[k]), s->gcap) : 0u;
+            gh[k] = s->has[k] ? umin(st.peer_own[k] + st.m[k] - umin(st.far[k], st.m[k]), s->gcap) : 0u;
         }
         next_s[k] = one_cap(st.tot_s[k]); next_r[k] = one_cap(st.tot_r[k]);
     }
@@ -1217,8 +1245,8 @@ void record_owed(sph_slab* s, const Step& st) {
     // (the neighbours, for whom this step goes through, take their next step under the slab's protocol: a one-message step is
     // sized from THIS step's headers, which both ends have)
     if (s->protocol == 1 && next_s[0] <= s->msg_cap && next_s[1] <= s->msg_cap && next_r[0] <= s->msg_cap && next_r[1] <= s->msg_cap) {
-        const uint32_t ns[2] = {s->has_lo ? next_s[0] : 0u, s->has_hi ? next_s[1] : 0u};
-        const uint32_t nr[2] = {s->has_lo ? next_r[0] : 0u, s->has_hi ? next_r[1] : 0u};
+        const uint32_t ns[2] = {s->has[LO] ? next_s[LO] : 0u, s->has[HI] ? next_s[HI] : 0u};
+        const uint32_t nr[2] = {s->has[LO] ? next_r[LO] : 0u, s->has[HI] ? next_r[HI] : 0u};
         g.group[sph_slab::G_NEXT] = msg_first(s, SPH_TAG_ONE, ns, nr);
     } else {
         g.group[sph_slab::G_NEXT] = msg_migrants(s);
@@ -1233,43 +1261,44 @@ int step_headers(sph_slab* s, Step& st) {
     rc = slab_wait_headers(s); if (rc) return rc;
     st.t_waited = std::chrono::steady_clock::now();
     s->pg.headers = true;
-    st.lb0 = s->h_lb[HL_LB]; st.lb1 = s->h_lb[HL_LB + 1]; st.lb2 = s->h_lb[HL_LB + 2]; st.lb3 = s->h_lb[HL_LB + 3];
-    st.deep_lo = s->h_lb[HL_DEEP]; st.deep_hi = s->h_lb[HL_DEEP + 1];
-    st.near_lo = s->h_lb[HL_NEAR]; st.near_hi = s->h_lb[HL_NEAR + 1];                  // first slot of layer 3 / of layer zl-3
-    st.early_lo = s->h_lb[HL_EARLY];                                                    // what the early force launch covered:
-    st.early_hi = min(s->h_lb[HL_EARLY + 1], st.early_lo + st.early_grid_slots);        // its range, as far as its grid reached
-    s->early_span = s->h_lb[HL_EARLY + 1] - st.early_lo;
+    const volatile HostWords& hw = *s->host;
+    for (int k = 0; k < 4; k++) st.lb[k] = hw.bounds[k];
+    for (int k = 0; k < 2; k++) { st.deep[k] = hw.deep[k]; st.near[k] = hw.near[k]; }
+    st.early[0] = hw.early[0];                                                  // what the early force launch covered:
+    st.early[1] = min(hw.early[1], st.early[0] + st.early_grid_slots);          // its range, as far as its grid reached
+    s->early_span = hw.early[1] - st.early[0];
     s->early_span_known = true;
-    st.far_lo = s->has_lo ? s->h_lb[HL_FAR] : 0u; st.far_hi = s->has_hi ? s->h_lb[HL_FAR + 1] : 0u;
-    st.m_lo = st.lb0; st.m_hi = st.n0 - st.lb3;
-    st.own_lo = st.lb1 - st.lb0; st.own_hi = st.lb3 - st.lb2;
-    st.in_lo = s->has_lo ? s->h_lb[HL_HDR_LO] : 0u; st.peer_own_lo = s->has_lo ? s->h_lb[HL_HDR_LO + 1] : 0u;
-    st.in_hi = s->has_hi ? s->h_lb[HL_HDR_HI] : 0u; st.peer_own_hi = s->has_hi ? s->h_lb[HL_HDR_HI + 1] : 0u;
-    st.far_in_lo = s->has_lo ? s->h_lb[HL_HDR_LO + 2] : 0u; st.far_in_hi = s->has_hi ? s->h_lb[HL_HDR_HI + 2] : 0u;
+    st.m[LO] = st.lb[B_OWN_BEGIN]; st.m[HI] = st.n0 - st.lb[B_OWN_END];
+    st.own[LO] = st.lb[B_FIRST_END] - st.lb[B_OWN_BEGIN]; st.own[HI] = st.lb[B_OWN_END] - st.lb[B_LAST_BEGIN];
     // the SECOND layers next to the cuts (the one-message step's ghosts-of-ghosts; every header carries the counts, so that the
-    // step after a three-group step can size its message): mine from the bounds, the neighbours' from their headers
-    // (the same expressions as the kernel's header words: k_slab_bounds_pack)
-    const uint32_t n2_lo = s->has_lo ? max(st.near_lo - st.off0, st.lb1) - st.lb1 : 0u;
-    const uint32_t n2_hi = s->has_hi ? st.lb2 - min(st.near_hi - st.off0, st.lb2) : 0u;
-    st.n2p_lo = s->has_lo ? s->h_lb[HL_HDR2_LO] : 0u; st.n2p_hi = s->has_hi ? s->h_lb[HL_HDR2_HI] : 0u;
-    const uint32_t vfar_mine = s->h_lb[HL_VFAR], vfar_peer = (s->has_lo ? s->h_lb[HL_HDR2_LO + 1] : 0u) + (s->has_hi ? s->h_lb[HL_HDR2_HI + 1] : 0u);
-    // records either end of a link packed this step: what the NEXT one-message step is sized from
-    st.tot_s[0] = s->has_lo ? st.m_lo + st.own_lo + n2_lo : 0u; st.tot_s[1] = s->has_hi ? st.m_hi + st.own_hi + n2_hi : 0u;
-    st.tot_r[0] = s->has_lo ? st.in_lo + st.peer_own_lo + st.n2p_lo : 0u; st.tot_r[1] = s->has_hi ? st.in_hi + st.peer_own_hi + st.n2p_hi : 0u;
+    // step after a three-group step can size its message): mine from the bounds, as my header said them; the neighbours' from theirs
+    uint32_t n2[2];
+    second_layer_counts(st.lb[B_FIRST_END], st.lb[B_LAST_BEGIN], st.near[LO] - st.off0, st.near[HI] - st.off0, n2);
+    const uint32_t vfar_mine = hw.vfar;
+    uint32_t vfar_peer = 0;
     bool* dead = s->pg.peer_dead;                   // that neighbour's header said "abort"
-    dead[0] = s->has_lo && s->h_lb[HL_HDR_LO + 3] != 0u;
-    dead[1] = s->has_hi && s->h_lb[HL_HDR_HI + 3] != 0u;
+    for (int k = 0; k < 2; k++) {
+        if (!s->has[k]) continue;                   // no neighbour: nothing sent, nothing received, nobody to die
+        const volatile SlabHeader& h = hw.hdr[k];
+        st.far[k] = hw.far[k];
+        st.in[k] = h.leavers; st.peer_own[k] = h.boundary; st.far_in[k] = h.far; st.n2p[k] = h.second;
+        vfar_peer += h.very_far;
+        dead[k] = h.abort != 0u;
+        // records either end of a link packed this step: what the NEXT one-message step is sized from
+        st.tot_s[k] = st.m[k] + st.own[k] + n2[k];
+        st.tot_r[k] = st.in[k] + st.peer_own[k] + st.n2p[k];
+    }
     record_owed(s, st);
     SPH_REQUIRE(!dead[0] && !dead[1], SPH_E_PEER, "rank %d: its %s neighbour reported a failure and stopped (step %llu)",
                 s->rank, dead[0] ? (dead[1] ? "lower and upper" : "lower") : "upper", (unsigned long long)s->steps);
-    const uint32_t m_lo = st.m_lo, m_hi = st.m_hi, in_lo = st.in_lo, in_hi = st.in_hi;
-    SPH_REQUIRE(s->has_lo || m_lo == 0, SPH_E_STATE, "rank %d: %u particles below the lowest slab", s->rank, m_lo);
-    SPH_REQUIRE(s->has_hi || m_hi == 0, SPH_E_STATE, "rank %d: %u particles above the highest slab", s->rank, m_hi);
+    const uint32_t m_lo = st.m[LO], m_hi = st.m[HI], in_lo = st.in[LO], in_hi = st.in[HI];
+    SPH_REQUIRE(s->has[LO] || m_lo == 0, SPH_E_STATE, "rank %d: %u particles below the lowest slab", s->rank, m_lo);
+    SPH_REQUIRE(s->has[HI] || m_hi == 0, SPH_E_STATE, "rank %d: %u particles above the highest slab", s->rank, m_hi);
     // both ends of a link see the same numbers (mine in my header, the neighbour's in its header): they fail together
     SPH_REQUIRE(m_lo <= s->mcap && m_hi <= s->mcap && in_lo <= s->mcap && in_hi <= s->mcap, SPH_E_CAPACITY,
                 "rank %d: a burst of %u/%u leaving, %u/%u arriving particles exceeds the migrant capacity %u", s->rank, m_lo, m_hi,
                 in_lo, in_hi, s->mcap);
-    SPH_REQUIRE(st.far_in_lo <= in_lo && st.far_in_hi <= in_hi && st.far_lo <= m_lo && st.far_hi <= m_hi, SPH_E_STATE,
+    SPH_REQUIRE(st.far_in[LO] <= in_lo && st.far_in[HI] <= in_hi && st.far[LO] <= m_lo && st.far[HI] <= m_hi, SPH_E_STATE,
                 "rank %d: inconsistent migrant headers", s->rank);
     // capacity for what arrives, checked BEFORE anything is dropped or merged: on this error the owned range is still the
     // sorted range of this step
@@ -1281,9 +1310,9 @@ int step_headers(sph_slab* s, Step& st) {
                     "ghost layers (the three-group protocol takes such particles as long as they land in an interior layer)", s->rank,
                     vfar_mine, vfar_peer);
         SPH_REQUIRE(st.tot_s[0] <= s->msg_cap && st.tot_s[1] <= s->msg_cap && st.tot_r[0] <= s->msg_cap && st.tot_r[1] <= s->msg_cap &&
-                        st.peer_own_lo + st.n2p_lo <= s->gcap && st.peer_own_hi + st.n2p_hi <= s->gcap, SPH_E_CAPACITY,
+                        st.peer_own[LO] + st.n2p[LO] <= s->gcap && st.peer_own[HI] + st.n2p[HI] <= s->gcap, SPH_E_CAPACITY,
                     "rank %d: two layers of %u+%u / %u+%u residents (+ %u / %u leavers) exceed the message buffers (%u records) or the ghost "
-                    "capacity %u", s->rank, st.peer_own_lo, st.n2p_lo, st.peer_own_hi, st.n2p_hi, in_lo, in_hi, s->msg_cap, s->gcap);
+                    "capacity %u", s->rank, st.peer_own[LO], st.n2p[LO], st.peer_own[HI], st.n2p[HI], in_lo, in_hi, s->msg_cap, s->gcap);
     }
     // ---- what did not fit the first group, exact size (both ends know both counts): more leavers than ride in MIGRANTS, or
     //      in the one-message step more records than its size fixed in advance (a burst: many more leavers than the step before)
@@ -1300,7 +1329,7 @@ int step_headers(sph_slab* s, Step& st) {
 int step_settle(sph_slab* s, Step& st) {
     sph_ctx* c = s->c;
     int rc;
-    const uint32_t G = st.G, m_lo = st.m_lo, m_hi = st.m_hi, in_lo = st.in_lo, in_hi = st.in_hi;
+    const uint32_t G = st.G, m_lo = st.m[LO], m_hi = st.m[HI], in_lo = st.in[LO], in_hi = st.in[HI];
     // A step without arrivals (the usual one) hands the rest of the halo work to the COMM stream at once: the main
     // stream is busy with the deep density, and pack -> HALO A -> ghost unpack need nothing from it (the slices they
     // read have been final since the sort).  The ghosts are then in place when the deep density ends, and everything
@@ -1325,31 +1354,30 @@ int step_settle(sph_slab* s, Step& st) {
                 "rank %d: %u + %u arriving particles exceed the capacity %u", s->rank, c->n, in_lo + in_hi, c->cap);
     rc = after_comm(s); if (rc) return rc;                      // the received records are in mig_recv
     const bool merge = c->sort_merge && c->order_valid && table_covers(c, c->own_off, c->own_off + c->n);
-    const bool in_place = merge && st.far_in_lo == 0 && st.far_in_hi == 0 && in_lo <= SLAB_INSERT_MAX &&
-                          in_hi <= SLAB_INSERT_MAX && in_lo <= c->own_off && st.own_lo + st.own_hi <= c->n;
+    const bool in_place = merge && st.far_in[LO] == 0 && st.far_in[HI] == 0 && in_lo <= SLAB_INSERT_MAX &&
+                          in_hi <= SLAB_INSERT_MAX && in_lo <= c->own_off && st.own[LO] + st.own[HI] <= c->n;
     if (in_place) {
         // only the two boundary layers are touched (see k_slab_insert): their cells leave the table, the merged
         // layers come back from the scratch arrays, their cells are built again
         for (int side = 0; side < 2; side++) {
-            const uint32_t k = side == 0 ? in_lo : in_hi;
+            const uint32_t k = st.in[side];
             if (!k) continue;
-            const uint32_t nl = side == 0 ? st.own_lo : st.own_hi;
-            const uint32_t l0 = side == 0 ? c->own_off : c->own_off + c->n - st.own_hi;
-            const uint32_t d0 = side == 0 ? l0 - k : l0;
+            const uint32_t nl = st.own[side];
+            const uint32_t l0 = side == LO ? c->own_off : c->own_off + c->n - nl;
+            const uint32_t d0 = side == LO ? l0 - k : l0;
             rc = launch_cells_clear_range(c, l0, l0 + nl); if (rc) return rc;
             hipLaunchKernelGGL(k_slab_insert, dim3(ceil_div(nl + k, 256u)), dim3(256), 0, c->stream, c->posi, c->velr, c->keyS, l0,
-                               nl, s->mig_recv[side] + 2, k, c->grid, c->posi2, c->velr2, c->keyS2, d0,
-                               side == 0 ? G : c->grid.zl - G - 1u, side == 0, s->h_lb_dev + HL_ERR);
+                               nl, records_of(s->mig_recv[side]), k, c->grid, c->posi2, c->velr2, c->keyS2, d0,
+                               side == LO ? G : c->grid.zl - G - 1u, side == LO, s->host_dev->err);
             hipLaunchKernelGGL(k_slab_copy_back, dim3(ceil_div(nl + k, 256u)), dim3(256), 0, c->stream, c->posi2, c->velr2, c->keyS2,
                                c->posi, c->velr, c->keyS, d0, nl + k);
             SPH_HIP(hipGetLastError());
-            if (side == 0) c->own_off = d0;
+            if (side == LO) c->own_off = d0;
             c->n += k;
             table_set(c, c->own_off, c->own_off + c->n);
             rc = launch_cells_build_range(c, d0, d0 + nl + k); if (rc) return rc;
         }
-        st.own_lo += in_lo;
-        st.own_hi += in_hi;
+        for (int side = 0; side < 2; side++) st.own[side] += st.in[side];
         s->inserts++;
         s->resorts++;
         return SPH_OK;
@@ -1366,15 +1394,15 @@ int step_settle(sph_slab* s, Step& st) {
     uint32_t appended = 0;
     const bool front_slots = !merge && in_lo <= c->own_off;
     for (int side = 0; side < 2; side++) {
-        const uint32_t cnt = side == 0 ? in_lo : in_hi;
+        const uint32_t cnt = st.in[side];
         if (!cnt) continue;
         // any owned layer is fine for the pass over all particles, but a particle that is not inside this slab at all cannot be
         // represented: flagged (SLAB_ERR_ARRIVAL_OUTSIDE), the step reports SPH_E_STATE
-        const bool in_front = side == 0 && front_slots;
+        const bool in_front = side == LO && front_slots;
         const uint32_t at = in_front ? c->own_off - cnt : c->own_off + c->n + appended;
         uint32_t* const key = merge ? c->k0 + c->n + appended : nullptr;          // (front_slots: no merge)
-        rc = launch_unpack_records(c->stream, RecSide{s->mig_recv[side] + 2, c->posi + at, c->velr + at, key, cnt}, RecSide{}, c->grid, G,
-                                   s->h_lb_dev + HL_ERR + SLAB_ERR_ARRIVAL_OUTSIDE);
+        rc = launch_unpack_records(c->stream, RecSide{records_of(s->mig_recv[side]), c->posi + at, c->velr + at, key, cnt}, RecSide{}, c->grid, G,
+                                   &s->host_dev->err[SLAB_ERR_ARRIVAL_OUTSIDE]);
         if (rc) return rc;
         if (!in_front) appended += cnt;
     }
@@ -1387,28 +1415,28 @@ int step_settle(sph_slab* s, Step& st) {
         rc = step_hash(c); if (rc) return rc;
         rc = step_sort(c); if (rc) return rc;
     }
-    st.own_lo += in_lo - st.far_in_lo;          // the far ones went past the boundary layer
-    st.own_hi += in_hi - st.far_in_hi;
+    for (int side = 0; side < 2; side++) st.own[side] += st.in[side] - st.far_in[side];      // the far ones went past the boundary layer
     s->resorts++;
-    if (st.far_in_lo || st.far_in_hi) {
+    if (st.far_in[LO] || st.far_in[HI]) {
         // rare (a particle crossed more than one cell layer in a step): count the layers again.  The neighbours
         // size their ghost messages from the headers, so what the count must confirm is that every far arrival
         // stayed clear of the OTHER boundary layer and of the ghost layers.
         s->far_steps++;
         if (getenv("SPH_SLAB_DEBUG"))
             fprintf(stderr, "[slab %d] step %llu: far arrivals %u/%u of %u/%u; leavers %u/%u (far %u/%u); bounds %u %u %u %u of %u; "
-                    "peer boundary %u/%u\n", s->rank, (unsigned long long)s->steps, st.far_in_lo, st.far_in_hi, in_lo, in_hi, m_lo, m_hi,
-                    st.far_lo, st.far_hi, st.lb0, st.lb1, st.lb2, st.lb3, st.n0, st.peer_own_lo, st.peer_own_hi);
-        rc = launch_lower_bounds(c->stream, c->keyS + c->own_off, c->n, layer_bound_targets(c), s->d_lb, s->h_lb_dev + HL_LB);
+                    "peer boundary %u/%u\n", s->rank, (unsigned long long)s->steps, st.far_in[LO], st.far_in[HI], in_lo, in_hi, m_lo, m_hi,
+                    st.far[LO], st.far[HI], st.lb[0], st.lb[1], st.lb[2], st.lb[3], st.n0, st.peer_own[LO], st.peer_own[HI]);
+        rc = launch_lower_bounds(c->stream, c->keyS + c->own_off, c->n, layer_bound_targets(c), s->dev->bounds, s->host_dev->bounds);
         if (rc) return rc;
         SPH_HIP(hipStreamSynchronize(c->stream));
         s->host_waits++;
         rc = slab_check_device_flags(s); if (rc) return rc;
-        const uint32_t r0 = s->h_lb[0], r1 = s->h_lb[1], r2 = s->h_lb[2], r3 = s->h_lb[3];
-        SPH_REQUIRE(r0 == 0u && r3 == c->n && r1 - r0 == st.own_lo && r3 - r2 == st.own_hi, SPH_E_STATE,
+        const volatile uint32_t* r = s->host->bounds;
+        const uint32_t first = r[B_FIRST_END] - r[B_OWN_BEGIN], last = r[B_OWN_END] - r[B_LAST_BEGIN];
+        SPH_REQUIRE(r[B_OWN_BEGIN] == 0u && r[B_OWN_END] == c->n && first == st.own[LO] && last == st.own[HI], SPH_E_STATE,
                     "rank %d: a particle that crossed several cell layers in one step landed in a boundary or ghost "
                     "layer (boundary layers %u/%u, expected %u/%u): the time step is too large for this slab width",
-                    s->rank, r1 - r0, r3 - r2, st.own_lo, st.own_hi);
+                    s->rank, first, last, st.own[LO], st.own[HI]);
     }
     return SPH_OK;
 }
@@ -1418,14 +1446,20 @@ int step_ghosts(sph_slab* s, Step& st) {
     sph_ctx* c = s->c;
     int rc;
     const bool p1 = st.p1, early_halo = st.early_halo;
-    const uint32_t n = st.n = c->n, m_lo = st.m_lo, m_hi = st.m_hi;
+    const uint32_t n = st.n = c->n;
     // ghosts = what stayed in the neighbour's boundary layer + what I just sent INTO that layer; the one-message step keeps
     // the neighbour's second layer as well (g1: the inner ghost layer, whose densities this rank computes itself)
-    const uint32_t g1_lo = s->has_lo ? st.peer_own_lo + m_lo - st.far_lo : 0u, g1_hi = s->has_hi ? st.peer_own_hi + m_hi - st.far_hi : 0u;
-    const uint32_t g_lo = st.g_lo = p1 && s->has_lo ? st.peer_own_lo + st.n2p_lo + m_lo : g1_lo;
-    const uint32_t g_hi = st.g_hi = p1 && s->has_hi ? st.peer_own_hi + st.n2p_hi + m_hi : g1_hi;
-    const uint32_t h_lo = st.h_lo = s->has_lo ? st.own_lo : 0u, h_hi = st.h_hi = s->has_hi ? st.own_hi : 0u;
-    SPH_REQUIRE(st.own_lo <= n && st.own_hi <= n, SPH_E_STATE, "rank %d: inconsistent boundary counts", s->rank);
+    // (nr: the residents the neighbour packed behind its leavers in the one message.  A side without a neighbour sent and
+    // received nothing -- step_headers checked it -- so every count of it but its own boundary layer is 0 as it stands.)
+    uint32_t g1[2], nr[2];
+    for (int k = 0; k < 2; k++) {
+        g1[k] = st.peer_own[k] + st.m[k] - st.far[k];
+        nr[k] = st.peer_own[k] + st.n2p[k];
+        st.g[k] = p1 ? nr[k] + st.m[k] : g1[k];
+        st.h[k] = s->has[k] ? st.own[k] : 0u;
+    }
+    const uint32_t g_lo = st.g[LO], g_hi = st.g[HI], h_lo = st.h[LO], h_hi = st.h[HI];
+    SPH_REQUIRE(st.own[LO] <= n && st.own[HI] <= n, SPH_E_STATE, "rank %d: inconsistent boundary counts", s->rank);
     // (past this check the three-group step's h / g equal the HALO A / HALO B sizes record_owed clamped to gcap)
     SPH_REQUIRE(h_lo <= s->gcap && h_hi <= s->gcap && g_lo <= s->gcap && g_hi <= s->gcap && g_lo <= c->own_off &&
                     c->own_off + n + g_hi <= c->tot, SPH_E_CAPACITY,
@@ -1444,7 +1478,7 @@ int step_ghosts(sph_slab* s, Step& st) {
     // (An unconditional record costs the device ~6 us of idle per step; a MISSING one cost 18 NaN particles in one of
     // three 2-rank rehearsals of round 3: the high-priority comm stream overtook a deep launch that queued behind
     // another rank's kernels.)
-    st.need_deep_event = early_halo && !(a <= st.near_lo && b >= st.near_hi);
+    st.need_deep_event = early_halo && !(a <= st.near[LO] && b >= st.near[HI]);
     if (st.need_deep_event) { rc = hop_mark(s, HOP_DEEP, c->stream, s->ev_deep, &st.deep_v); if (rc) return rc; }
     // the slots the non-deep density launches cover: the owned range -- and, in the one-message step, the inner ghost layers
     // on either side (what HALO B carries in the three-group step), rounded down to a whole 64-slot chunk in front so that the
@@ -1455,9 +1489,9 @@ int step_ghosts(sph_slab* s, Step& st) {
     // step +4 ... +9 us at every link setting (profiles/r06b_periodic_slab_protocols_ghost_density_split.txt).
     uint32_t dens_lo = c->own_off, dens_hi = c->own_off + n;
     if (p1) {
-        const uint32_t back = (g1_lo + 63u) & ~63u;
-        dens_lo = c->own_off - (back <= g_lo ? back : g1_lo);
-        dens_hi = c->own_off + n + g1_hi;
+        const uint32_t back = (g1[LO] + 63u) & ~63u;
+        dens_lo = c->own_off - (back <= g_lo ? back : g1[LO]);
+        dens_hi = c->own_off + n + g1[HI];
     }
     // ---- halo A: boundary layers -> neighbours' ghost layers -----------------------------------------------------------
     hipStream_t pack_stream = early_halo ? s->comm : c->stream;
@@ -1472,7 +1506,7 @@ int step_ghosts(sph_slab* s, Step& st) {
         // the interior density runs while the halo travels: queued BEFORE the transfers are handed to the transport.
         // What the deep launch already did is left out.
         PhaseTimer t(c, SPH_PH_DENS);
-        rc = st.deep_valid ? launch_density_hole(c, a, b, st.deep_lo, st.deep_hi) : launch_density_range(c, a, b);
+        rc = st.deep_valid ? launch_density_hole(c, a, b, st.deep[0], st.deep[1]) : launch_density_range(c, a, b);
         if (rc) return rc;
     }
     if (!p1) {
@@ -1487,15 +1521,14 @@ int step_ghosts(sph_slab* s, Step& st) {
         // The one-message step: the neighbours' two layers came with their headers and leavers (behind those, in the same
         // buffer); no message here.  A side this rank sent nobody to is unpacked as it is; else its own leavers -- still in the
         // send buffer -- are merged in where the neighbour will put them (k_slab_unpack_ghosts_merge), then the cells.
-        const float4* res_lo = s->mig_recv[0] + 2 * (1 + (size_t)st.in_lo);
-        const float4* res_hi = s->mig_recv[1] + 2 * (1 + (size_t)st.in_hi);
-        const uint32_t nr_lo = s->has_lo ? st.peer_own_lo + st.n2p_lo : 0u, nr_hi = s->has_hi ? st.peer_own_hi + st.n2p_hi : 0u;
-        if (m_lo + m_hi == 0u) {
+        const float4* res_lo = records_of(s->mig_recv[LO]) + REC4 * (size_t)st.in[LO];       // behind the arrivals
+        const float4* res_hi = records_of(s->mig_recv[HI]) + REC4 * (size_t)st.in[HI];
+        if (st.m[LO] + st.m[HI] == 0u) {
             hipLaunchKernelGGL(k_slab_unpack_ghosts, dim3(ceil_div(g_lo + g_hi, 256u)), dim3(256), 0, s->comm, res_lo, g_lo, c->own_off - g_lo,
                                res_hi, g_hi, c->own_off + n, c->posi, c->velr, c->keyS, c->table.cells, c->grid);
         } else {
-            hipLaunchKernelGGL(k_slab_unpack_ghosts_merge, dim3(ceil_div(g_lo + g_hi, 256u)), dim3(256), 0, s->comm, res_lo, nr_lo,
-                               s->mig_send[0] + 2, s->has_lo ? m_lo : 0u, c->own_off - g_lo, res_hi, nr_hi, s->mig_send[1] + 2, s->has_hi ? m_hi : 0u,
+            hipLaunchKernelGGL(k_slab_unpack_ghosts_merge, dim3(ceil_div(g_lo + g_hi, 256u)), dim3(256), 0, s->comm, res_lo, nr[LO],
+                               records_of(s->mig_send[LO]), st.m[LO], c->own_off - g_lo, res_hi, nr[HI], records_of(s->mig_send[HI]), st.m[HI],
                                c->own_off + n, c->posi, c->velr, c->keyS, c->grid);
             OnComm on(s);
             rc = launch_cells_build_2ranges(c, c->own_off - g_lo, c->own_off, c->own_off + n, c->own_off + n + g_hi);
@@ -1516,7 +1549,7 @@ int step_ghosts(sph_slab* s, Step& st) {
         OnComm on(s);
         {
             PhaseTimer t(c, SPH_PH_DENS);
-            rc = launch_density_hole(c, dens_lo, dens_hi, st.deep_lo, st.deep_hi);
+            rc = launch_density_hole(c, dens_lo, dens_hi, st.deep[0], st.deep[1]);
             if (rc) return rc;
         }
         if (!p1 && h_lo + h_hi)
@@ -1546,7 +1579,7 @@ int step_ghosts(sph_slab* s, Step& st) {
 int step_forces(sph_slab* s, Step& st) {
     sph_ctx* c = s->c;
     int rc;
-    const uint32_t n = st.n, g_lo = st.g_lo, g_hi = st.g_hi, a = st.a, b = st.b;
+    const uint32_t n = st.n, g_lo = st.g[LO], g_hi = st.g[HI], a = st.a, b = st.b;
     // the interior forces run while halo B travels
     const bool mark = force_begin(c, true);
     {
@@ -1554,9 +1587,9 @@ int step_forces(sph_slab* s, Step& st) {
         // what the early launch did is left out in whole 64-slot chunks of the FINAL owned range (the up to 63 slots at
         // either end of its range are simply computed again: same inputs, same bits)
         uint32_t h0 = 0, h1 = 0;
-        if (st.early_launched && st.deep_valid && st.early_hi > st.early_lo && st.early_lo >= c->own_off) {
-            h0 = c->own_off + ((st.early_lo - c->own_off + 63u) & ~63u);
-            h1 = c->own_off + ((st.early_hi - c->own_off) & ~63u);
+        if (st.early_launched && st.deep_valid && st.early[1] > st.early[0] && st.early[0] >= c->own_off) {
+            h0 = c->own_off + ((st.early[0] - c->own_off + 63u) & ~63u);
+            h1 = c->own_off + ((st.early[1] - c->own_off) & ~63u);
         }
         if (h1 > h0 && h0 >= a && h1 <= b) {
             rc = launch_force_hole(c, a, b, h0, h1, true, true, true, st.dt, mark);                  // interior: queued before the transfer
@@ -1849,7 +1882,7 @@ int sph_slab_create(sph_slab** out, sph_ctx* ctx, int rank, int world, const sph
     sph_slab* s = new (std::nothrow) sph_slab();
     SPH_REQUIRE(s, SPH_E_NOMEM, "out of host memory");
     s->c = ctx; s->rank = rank; s->world = world;
-    s->has_lo = rank > 0; s->has_hi = rank + 1 < world;
+    s->has[LO] = rank > 0; s->has[HI] = rank + 1 < world;
     s->device = ctx->device;
     if (const char* e = getenv("SPH_SLAB_TIMEOUT_S")) { const double v = atof(e); if (v > 0.0) s->wait_timeout_s = v; }
     if (const char* e = getenv("SPH_SLAB_EARLY_SPAN")) { const long v = atol(e); if (v > 0) s->early_cap = (uint32_t)v; }
@@ -1871,11 +1904,11 @@ int sph_slab_create(sph_slab** out, sph_ctx* ctx, int rank, int world, const sph
               hipEventCreateWithFlags(&s->ev_early_done, hipEventDisableTiming) == hipSuccess;
     if (!ok) { set_error("sph_slab_create: creating the streams and events failed"); slab_free(s); return SPH_E_NOMEM; }
     Buffers& m = s->mem;
-    int rc = m.alloc(&s->d_lb, DL_WORDS, true);
-    if (!rc) rc = m.alloc_host(&s->h_lb, HL_WORDS, (volatile uint32_t**)&s->h_lb_dev);
+    int rc = m.alloc(&s->dev, 1, true);
+    if (!rc) rc = m.alloc_host(&s->host, 1, (volatile HostWords**)&s->host_dev);
     // (a context with two ghost layers may run the one-message step: leavers AND two layers of residents in one buffer)
     s->msg_cap = ctx->ghost_layers >= 2u ? s->mcap + s->gcap + 64u : s->mcap;
-    const size_t mig_bytes = (size_t)(1 + s->msg_cap) * 2 * sizeof(float4), halo_bytes = (size_t)(s->gcap + 1) * 2 * sizeof(float4);
+    const size_t mig_bytes = (1 + (size_t)s->msg_cap) * REC, halo_bytes = ((size_t)s->gcap + 1) * REC;
     for (int k = 0; k < 2 && !rc; k++) {      // (the migrant buffers start as zeros: a header nobody wrote yet reads "nothing")
         rc = m.alloc(&s->mig_send[k], mig_bytes / sizeof(float4), true);
         if (!rc) rc = m.alloc(&s->mig_recv[k], mig_bytes / sizeof(float4), true);
@@ -1905,7 +1938,7 @@ int sph_slab_create(sph_slab** out, sph_ctx* ctx, int rank, int world, const sph
         if (!s->hops_by_value) m.release(&s->hop_mem);      // (the probe rejected it: events)
     }
     if (rc) { slab_free(s); return rc; }                    // (the owner's message names what failed)
-    for (int k = 0; k < HL_WORDS; k++) s->h_lb[k] = 0u;
+    memset((void*)s->host, 0, sizeof(HostWords));
     ctx->host_paced = true;            // sph_slab_step waits for the device once per step
     *out = s;
     return SPH_OK;
@@ -2057,7 +2090,7 @@ int sph_slab_ping(sph_slab* s, size_t bytes, uint32_t reps, double out[3]) {
     out[0] = out[1] = out[2] = 0.0;
     if (s->world < 2) return SPH_OK;
     const uint32_t words = (uint32_t)(bytes / 4), grid = min(ceil_div(words, 256u), 1024u);
-    uint32_t* bad = s->d_lb + DL_PING;
+    uint32_t* bad = &s->dev->ping;
     SPH_HIP(hipMemsetAsync(bad, 0, sizeof(uint32_t), s->comm));
     const uint64_t exchanges0 = s->exchanges;
     const bool timed0 = s->time_groups;
@@ -2067,12 +2100,12 @@ int sph_slab_ping(sph_slab* s, size_t bytes, uint32_t reps, double out[3]) {
     s->t_group[4] = sph_slab::Acc();
     for (uint32_t rep = 0; rep <= reps && !rc; rep++) {
         s->time_groups = rep > 0;                             // round 0 is the connection set-up
-        hipLaunchKernelGGL(k_slab_ping_fill, dim3(grid), dim3(256), 0, s->comm, s->has_lo ? (uint32_t*)s->halo_send[0] : nullptr,
-                           s->has_hi ? (uint32_t*)s->halo_send[1] : nullptr, words, (uint32_t)s->rank, rep);
+        hipLaunchKernelGGL(k_slab_ping_fill, dim3(grid), dim3(256), 0, s->comm, s->has[LO] ? (uint32_t*)s->halo_send[LO] : nullptr,
+                           s->has[HI] ? (uint32_t*)s->halo_send[HI] : nullptr, words, (uint32_t)s->rank, rep);
         rc = slab_exchange(s, ping);
         if (rc) break;
-        hipLaunchKernelGGL(k_slab_ping_check, dim3(grid), dim3(256), 0, s->comm, s->has_lo ? (const uint32_t*)s->halo_recv[0] : nullptr,
-                           s->has_hi ? (const uint32_t*)s->halo_recv[1] : nullptr, words, (uint32_t)s->rank, rep, bad);
+        hipLaunchKernelGGL(k_slab_ping_check, dim3(grid), dim3(256), 0, s->comm, s->has[LO] ? (const uint32_t*)s->halo_recv[LO] : nullptr,
+                           s->has[HI] ? (const uint32_t*)s->halo_recv[HI] : nullptr, words, (uint32_t)s->rank, rep, bad);
         if (hipGetLastError() != hipSuccess) { set_error("ping: kernel launch failed"); rc = SPH_E_DEVICE; }
     }
     s->time_groups = timed0;
@@ -2145,14 +2178,14 @@ static int slab_recut_body(sph_slab* s, uint32_t new_lo, uint32_t new_hi) {
     mm_drop_marks(c);
     const uint32_t n = c->n, off = c->own_off, nblk = ceil_div(max(n, 1u), RECUT_BLOCK);
     if (!s->recut_blk) { rc = s->mem.alloc(&s->recut_blk, (size_t)2 * (ceil_div(c->cap, RECUT_BLOCK) + 1), false); if (rc) return rc; }
-    s->h_lb[HL_RECUT] = s->h_lb[HL_RECUT + 1] = 0u;
+    s->host->recut_out[LO] = s->host->recut_out[HI] = 0u;
     hipLaunchKernelGGL(k_recut_count, dim3(nblk), dim3(256), 0, c->stream, c->posi + off, n, c->grid, new_lo, new_hi, s->recut_blk);
-    hipLaunchKernelGGL(k_recut_scan, dim3(1), dim3(1024), 0, c->stream, s->recut_blk, nblk, s->h_lb_dev + HL_RECUT);
+    hipLaunchKernelGGL(k_recut_scan, dim3(1), dim3(1024), 0, c->stream, s->recut_blk, nblk, s->host_dev->recut_out);
     SPH_HIP(hipGetLastError());
     SPH_HIP(hipStreamSynchronize(c->stream));
-    const uint32_t down = s->h_lb[HL_RECUT], up = s->h_lb[HL_RECUT + 1];
+    const uint32_t down = s->host->recut_out[LO], up = s->host->recut_out[HI];
     SPH_REQUIRE(down + up <= n, SPH_E_STATE, "rank %d: re-cut counts %u + %u exceed the %u owned particles", s->rank, down, up, n);
-    SPH_REQUIRE((s->has_lo || down == 0u) && (s->has_hi || up == 0u), SPH_E_INVALID,
+    SPH_REQUIRE((s->has[LO] || down == 0u) && (s->has[HI] || up == 0u), SPH_E_INVALID,
                 "rank %d: the new layers [%u, %u) leave %u / %u particles without an owner", s->rank, new_lo, new_hi, down, up);
     const uint32_t keep = n - down - up;
     // [stays | goes down | goes up] in the ping-pong arrays, from the canonical offset
@@ -2165,12 +2198,11 @@ static int slab_recut_body(sph_slab* s, uint32_t new_lo, uint32_t new_hi) {
     const uint32_t none[2] = {0, 0};
     rc = slab_exchange(s, msg_first(s, SPH_TAG_RECUT_COUNTS, none, none));
     if (rc) return rc;
-    uint32_t in_lo = 0, in_hi = 0;
-    if (s->has_lo) SPH_HIP(hipMemcpyAsync((void*)&s->h_lb[HL_RECUT + 2], s->mig_recv[0], sizeof(uint32_t), hipMemcpyDeviceToHost, s->comm));
-    if (s->has_hi) SPH_HIP(hipMemcpyAsync((void*)&s->h_lb[HL_RECUT + 3], s->mig_recv[1], sizeof(uint32_t), hipMemcpyDeviceToHost, s->comm));
+    for (int k = 0; k < 2; k++)
+        if (s->has[k])
+            SPH_HIP(hipMemcpyAsync((void*)&s->host->recut_in[k], &header_of(s->mig_recv[k])->leavers, sizeof(uint32_t), hipMemcpyDeviceToHost, s->comm));
     rc = slab_wait_stream(s, s->comm, "re-cut (counts)"); if (rc) return rc;
-    if (s->has_lo) in_lo = s->h_lb[HL_RECUT + 2];
-    if (s->has_hi) in_hi = s->h_lb[HL_RECUT + 3];
+    const uint32_t in_lo = s->has[LO] ? s->host->recut_in[LO] : 0u, in_hi = s->has[HI] ? s->host->recut_in[HI] : 0u;
     const uint64_t n_new = (uint64_t)keep + in_lo + in_hi;
     // A rank that cannot hold what is coming does NOT simply return: its neighbours have sized the particle rounds from the
     // counts and are about to post them -- they would sit in their bounded waits and abort their transports.  It takes part
@@ -2225,7 +2257,7 @@ int sph_slab_recut(sph_slab* s, uint32_t new_z_lo, uint32_t new_z_hi) {
     SPH_REQUIRE(s->world == 1 || new_z_hi - new_z_lo >= 2, SPH_E_INVALID, "a slab needs at least two cell layers");
     SPH_REQUIRE(s->world == 1 || s->protocol != 1 || new_z_hi - new_z_lo >= 4, SPH_E_INVALID,
                 "the one-message step needs slabs of at least four cell layers (asked for [%u, %u))", new_z_lo, new_z_hi);
-    SPH_REQUIRE((s->has_lo || new_z_lo == 0u) && (s->has_hi || new_z_hi == s->c->params.grid[2]), SPH_E_INVALID,
+    SPH_REQUIRE((s->has[LO] || new_z_lo == 0u) && (s->has[HI] || new_z_hi == s->c->params.grid[2]), SPH_E_INVALID,
                 "rank %d of %d: the outer slabs reach to the ends of the grid", s->rank, s->world);
     // a particle moves ONE rank per call: a new range that does not even touch the old one would hand particles to a
     // neighbour that does not own their layer either (the full single-hop rule -- new cut r within [old cut r-1, old cut
@@ -2259,7 +2291,7 @@ int sph_slab_recut_stats(const sph_slab* s, uint64_t out[2]) {
 // arrival is where it cannot be), so that the failure path of a step that has not sent anything yet can be exercised
 int sph_slab_test_raise_flag(sph_slab* s, int flag) {
     SPH_REQUIRE(s && flag >= 0 && flag < 2, SPH_E_INVALID, "bad argument");
-    s->h_lb[HL_ERR + flag] = 1u;
+    s->host->err[flag] = 1u;
     return SPH_OK;
 }
 

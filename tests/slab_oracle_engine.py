@@ -212,6 +212,21 @@ def make_case(name):
     return pos, vel, box, grid
 
 
+def far_case(direction="up", speed=2.8e5):
+    """make_case's block at rest under the cuts [0, 4, 8, 64] of three slabs, except 20 particles that cross more than one
+    cell layer per step (2.8e5: 0.14 = 2.24 layers).  "up": of the two lattice layers under the first cut (cell layer 3, the
+    top layer of slab 0, at 3.25 and 3.75 cells), flying up into slab 1.  "down": of the two lattice layers above the second
+    cut (cell layer 8, the bottom layer of slab 2, at 8.25 and 8.75 cells), flying down into slab 1.  What the oracle makes
+    of either at each speed the GPU tests use: tests/test_slab_cpu.py::test_far_case_premises."""
+    pos, vel, box, grid = make_case("up")
+    vel[:] = 0.0
+    iz = np.arange(pos.shape[0]) // (12 * 12)
+    near, next_ = {"up": (7, 6), "down": (16, 17)}[direction]
+    fast = np.concatenate([np.nonzero(iz == near)[0][::15][:10], np.nonzero(iz == next_)[0][::15][:10]])
+    vel[fast, 2] = speed if direction == "up" else -speed
+    return pos, vel, box, grid, fast
+
+
 def gloo_worker(rank, world, port, case, steps, out_dir, protocol=3):
     """Entry of one CPU rank (torch.multiprocessing.spawn): TorchDistComm over gloo."""
     import torch.distributed as dist

@@ -215,7 +215,7 @@ def _slab_create_failures(fluid):
 
         failed = _fail_each(lambda: L.sph_slab_create(C.byref(h), c.h, 0, 1, tr, 0), after)     # the last attempt went through
         n_slab = capi.memory_stats()[2] - held[2]
-        # d_lb, h_lb, 2 x 6 message buffers, and hop_mem where the write / wait-value probe accepts it (released where it does not)
+        # dev, host, 2 x 6 message buffers, and hop_mem where the write / wait-value probe accepts it (released where it does not)
         assert n_slab >= 14 and failed in (n_slab, n_slab + 1), (failed, n_slab)
         capi._check(L.sph_slab_step(h, DT, 2))                   # the slab the context got in the end works
         capi._check(L.sph_slab_sync(h))

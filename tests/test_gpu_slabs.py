@@ -14,7 +14,7 @@ import pytest
 
 from gpufluidsimulator_amd import capi, ic, slab
 from conftest import bits
-from slab_oracle_engine import make_case
+from slab_oracle_engine import far_case as _far_case, make_case
 
 pytestmark = pytest.mark.gpu
 DT = 5e-7
@@ -347,25 +347,15 @@ def test_rebalance_on_gpu_engines(transport, protocol):
     _same_bits(st, ref)
 
 
-def _far_case():
-    """make_case's block at rest, except 20 particles of the two lattice layers under the first cut (cell layer 3,
-    the top layer of slab 0 of 3): they fly up at 2.8e5 -- 0.14 = 2.24 cell layers per step."""
-    pos, vel, box, grid = make_case("up")
-    vel[:] = 0.0
-    idx = np.arange(pos.shape[0])
-    iz = idx // (12 * 12)
-    fast = np.concatenate([np.nonzero(iz == 7)[0][::15][:10], np.nonzero(iz == 6)[0][::15][:10]])
-    vel[fast, 2] = 2.8e5
-    return pos, vel, box, grid, fast
-
-
-def test_particle_crossing_two_layers_in_one_step():
+@pytest.mark.parametrize("direction", ["up", "down"])
+def test_particle_crossing_two_layers_in_one_step(direction):
     """The slab twin of test_gpu_edge_cases.py::test_faster_than_one_cell_per_step.  A leaver that crossed MORE than
     one cell layer does not land in the neighbour's boundary layer: its sender counts it as `far` in the migrant
     header, the receiver then takes the step's arrivals in through the pass over all particles (any key is fine
     there) instead of merging them into the boundary layer in place, counts its layers again (one more wait on that
-    step only), and both sides size their ghost messages accordingly.  Result: the whole-domain physics."""
-    pos, vel, box, grid, fast = _far_case()
+    step only), and both sides size their ghost messages accordingly.  Result: the whole-domain physics.  "down": the same
+    from the bottom layer of slab 2 into slab 1 -- the sender's far count towards rank - 1, the receiver's from rank + 1."""
+    pos, vel, box, grid, fast = _far_case(direction)
     steps, world = 4, 3
     res = _run_slabs(world, box, grid, steps, particles=(pos, vel))
     assert res[0][2] == [0, 4, 8, 64]
@@ -379,23 +369,25 @@ def test_particle_crossing_two_layers_in_one_step():
     _same_bits(st, ref)
 
 
-def test_one_message_step_with_particles_crossing_two_layers_and_refusing_three():
+@pytest.mark.parametrize("direction", ["up", "down"])
+def test_one_message_step_with_particles_crossing_two_layers_and_refusing_three(direction):
     """The one-message step keeps TWO ghost layers, so a particle that crosses into the neighbour's second layer in one step is
     still inside the copy this rank holds of that layer: the sender merges it into its ghost copy where the neighbour will put
     it, the receiver takes it through the pass over all particles as ever -- whole-domain bits.  One that flies FURTHER is in
     nobody's copy: SPH_E_STATE on the ranks that see it, SPH_E_PEER on the others (the three-group protocol takes such a
-    particle as long as it lands in an interior layer: test_particle_crossing_two_layers_in_one_step)."""
-    pos, vel, box, grid, fast = _far_case()
-    vel[fast, 2] = 2.0e5               # 0.1 = 1.6 cell layers per step: from 3.25 / 3.75 cells (the top layer of slab 0) to 4.85 / 5.35,
-    steps, world = 4, 3                # i.e. into the FIRST and the SECOND layer of slab 1
+    particle as long as it lands in an interior layer: test_particle_crossing_two_layers_in_one_step).  "down": the mirror
+    image, from 8.25 / 8.75 cells (the bottom layer of slab 2) into the last and the second-last layer of slab 1."""
+    # 0.1 = 1.6 cell layers per step: from 3.25 / 3.75 cells (the top layer of slab 0) to 4.85 / 5.35, i.e. into the FIRST and
+    # the SECOND layer of slab 1
+    pos, vel, box, grid, fast = _far_case(direction, 2.0e5)
+    steps, world = 4, 3
     res = _run_slabs(world, box, grid, steps, particles=(pos, vel), protocol=1)
     assert res[0][2] == [0, 4, 8, 64]
     assert sum(r[1]["far_steps"] for r in res) >= 1 and all(r[1]["one_message_steps"] == steps - 1 for r in res), [r[1] for r in res]
     ref = _whole_domain(pos, vel, box, grid, steps)
     assert np.abs(ref["pos"][fast, 2] - pos[fast, 2]).min() > 0.0625
     _same_bits(res[0][0], ref)
-    pos, vel, box, grid, fast = _far_case()
-    vel[fast, 2] = 3.4e5               # 2.72 layers per step: from 3.75 to 6.47 cells, the THIRD layer of slab 1
+    pos, vel, box, grid, fast = _far_case(direction, 3.4e5)      # 2.72 layers per step: from 3.75 to 6.47 cells, the THIRD layer of slab 1
     errors = _run_slabs(world, box, grid, steps, particles=(pos, vel), protocol=1, expect_error=True)
     assert errors and any("more than TWO cell layers" in str(e) for e in errors), errors
 

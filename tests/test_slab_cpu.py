@@ -13,7 +13,7 @@ import pytest
 
 from gpufluidsimulator_amd import slab
 from oracle import oracle
-from slab_oracle_engine import OracleEngine, OracleEngine2, gloo_worker, make_case
+from slab_oracle_engine import OracleEngine, OracleEngine2, far_case, gloo_worker, make_case
 
 DT = 5e-7
 
@@ -108,6 +108,32 @@ def test_slabs_in_process_match_single_domain(case, world):
     assert total_migrants > 0, "the case is meant to push particles across slab boundaries"
     for other in results[1:]:
         assert np.array_equal(other[0]["pos"], st["pos"])
+
+
+# far_case on the whole-domain oracle: the cell layers of the 20 fast particles after step 1, and a lower bound of their
+# displacement after four steps (the one the GPU test of that speed asserts; the fastest is bound by the middle speed's)
+FAR_PREMISES = {("up", 2.8e5): ({4, 5}, 0.14), ("down", 2.8e5): ({6, 7}, 0.14),
+                ("up", 2.0e5): ({4, 5}, 0.0625), ("down", 2.0e5): ({6, 7}, 0.0625),
+                ("up", 3.4e5): ({5, 6}, 0.14), ("down", 3.4e5): ({5, 6}, 0.14)}
+
+
+@pytest.mark.parametrize("direction,speed", sorted(FAR_PREMISES))
+def test_far_case_premises(direction, speed):
+    """What tests/test_gpu_slabs.py's far cases rest on, under the cuts [0, 4, 8, 64] (slab 1 = cell layers 4 .. 7).  At 2.8e5 and
+    2.0e5 the fast particles land in the first and the second layer of slab 1 from their side -- 4 and 5 going up, 7 and 6 going
+    down -- so some crossed more than one layer ("far") and none more than two; at 3.4e5 some reach the THIRD layer from their
+    side (6 going up, 5 going down), which the one-message step refuses."""
+    pos, vel, box, grid, fast = far_case(direction, speed)
+    want_layers, min_dz = FAR_PREMISES[direction, speed]
+    o = oracle.Oracle(pos, vel, box, grid, oracle.CELL_LINEAR)
+    o.step(DT, 1)
+    layers = set(slab.cell_layer_of(o.state()["pos"][fast, 2], box[2], grid[2]).tolist())
+    o.step(DT, 3)
+    dz = np.abs(o.state()["pos"][fast, 2] - pos[fast, 2])
+    o.close()
+    print(direction, speed, "layers after step 1", sorted(layers), "smallest |dz| after 4 steps", dz.min(), "=", dz.min() * grid[2] / box[2], "cells")
+    assert layers == want_layers
+    assert dz.min() > min_dz
 
 
 @pytest.mark.parametrize("protocol", [3, 1])
