@@ -1,54 +1,17 @@
-// sph_headless.cpp -- headless driver with the reference's command line
-// (SPH/particles.cpp:676-706: -n= -box= -i= -benchmark -device= -file=) and its runBenchmark()
-// output line (:176-192), on top of include/particleSystem.h.  No GLUT / OpenGL.
-//   sph_headless -benchmark -n=262144 -box=8 -i=100 [-device=0] [-grid=128] [-ic=grid|random] [-steps=1] [-dump=8]
-//                [-log=benchmark.txt [-logstyle=oscar|frames]] [-file=<snapshot>] [-collider=x,y,z,r[,ux,uy,uz]] [-collidermass=M[,ax,ay,az]]
-//                [-obstacle=<shape> ... [-obstaclecell=s] [-obstaclevel=ux,uy,uz]]
-//                [-obstaclemesh=FILE.obj [-obstacleband=N] [-obstacleinvert] [-obstaclecell=s] [-obstaclevel=ux,uy,uz]]
-// -obstacle: solid shapes the fluid collides with (ParticleSystem::setObstacles, sph_obstacle_build); see parse_obstacle below
-// -collider: the reference's collider sphere (centre, radius, and a velocity: default at rest), made to push the fluid
-// (ParticleSystem::enableCollider; one sphere, as the reference's UI has).
-//   -emit=x,y,z,r,vx,vy,vz,every   a faucet: before every `every`-th update (0, every, 2 every, ...) a lattice ball of radius r
-//                      spacings (the points of addSphere, spacing 2R) is appended at (x, y, z) with velocity (vx, vy, vz)
-//                      (ParticleSystem::emitSphere) -- unless a particle is still inside the ball's sphere (countParticles), or
-//                      the capacity (-capacity=M, default twice -n) would be exceeded
-//   -drain=x0,y0,z0,x1,y1,z1[,every]   a kill volume: before every `every`-th update (default: each) the particles in the box
-//                      [x0, x1) x [y0, y1) x [z0, z1) are removed (ParticleSystem::removeParticles); with -emit, the emission
-//                      comes first.  With either flag -out writes one row per creation index below the capacity (zeros where
-//                      there is no particle).  One device only.
-//   -add=k,count       before update k, `count` particles at rest at the points of sph_ic_random_box(seed 2024) are appended
-//                      (ParticleSystem::addParticles); needs room (-capacity=M)
-//   -frames=DIR [-frameevery=K] [-framesize=WxH] [-camera=ex,ey,ez,tx,ty,tz[,fovy]] [-color=index|speed:lo:hi|density:lo:hi]
-//                      pictures: after the updates 0, K, 2K, ... (K = 1 by default) the particles are rendered on the device
-//                      (ParticleSystem::renderFrame) and written to DIR/frame_NNNNNN.ppm, NNNNNN the 0-based number of the update
-//                      the picture follows.  Defaults: 640x480, the reference's view (eye 0,0,3, the origin, 60 degrees), the
-//                      reference's colouring by creation index.  One device only.
-//   -surface[=r,K[,tau]] [-tint=r,g,b] [-absorb=r,g,b]   with -frames: the pictures show the fluid as a surface
-//                      (ParticleSystem::setRenderSurface, sph_render_surface): sphere depth smoothed K times over a radius of r
-//                      pixels (r 0..16, K 0..8; default 5,2) with the depth falloff tau (world units; default 0: four particle
-//                      radii), normals from it, a water-like shading with the base colour -tint (default 0.25,0.55,0.95) and
-//                      the absorption -absorb per unit of thickness (default 6,2,0.5; 0,0,0: no thickness pass)
-//   -mesh=DIR [-meshevery=K] [-meshcell=s] [-meshradius=r] [-iso=v]   geometry: after the updates 0, K, 2K, ... (K = 1 by default)
-//                      the fluid's surface is extracted on the device as a triangle mesh (ParticleSystem::writeMeshOBJ,
-//                      sph_mesh_extract) and written to DIR/mesh_NNNNN.obj (Wavefront OBJ: v, vn, f), NNNNN the 0-based number of
-//                      the update the mesh follows.  -meshcell the lattice spacing (default: the particle radius), -meshradius
-//                      the particles' reach (default: three spacings, at most eight), -iso the level (default 0.5).  Independent
-//                      of -frames; both may be given.  One device only.  At the end one line tells the mesh of the final state
-//                      (ParticleSystem::extractMesh): vertices, triangles and an FNV-1a hash of positions, normals, triangles.
-// Several GPUs (no counterpart in the reference, which is a single-device program): -gpus=N cuts the dam into N
-// z-slabs and steps them with sph_slab_step through the C ABI --
-//   -gpus=N            N child PROCESSES, forked before anything touches a GPU, rank r on device r (+ -device=), messages
-//                      over RCCL (sph_rccl_transport_create; rank 0 hands the id to the others through pipes);
-//   -gpus=N -onegpu    N THREADS of this process on one device over the device-to-device transport (a one-GPU box).
-//   -protocol=1        the one-message slab step (sph_slab_set_protocol: two ghost layers, ghost densities recomputed locally).
-// The reference's line is printed with NumDevsUsed = N.
+// sph_headless.cpp -- headless driver with the reference's command line (SPH/particles.cpp:676-706: -n= -box= -i= -benchmark
+// -device= -file=) and its runBenchmark() output line (:176-192), on top of include/particleSystem.h; -gpus=N (no counterpart
+// in the reference, a single-device program) steps z-slabs through the C ABI.  No GLUT / OpenGL.
+// What each option means is stated once, by `sph_headless -help`; its form, by the parser's error message.
+// Structure: parse_options() fills one Options struct -- the only code that sees argv, and none of it needs a device.  main()
+// dispatches: -help, the slab run (slab_job, run_slabs) or the one-device run (run_one_device: set_up, before_update,
+// after_update, report).
 #include "../../include/particleSystem.h"
 
 #include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -66,29 +29,129 @@
 #include <sys/wait.h>
 #include <unistd.h>
 
-static bool flag(int argc, char** argv, const char* name) {   // checkCmdLineFlag, helper_string.h:111
-    for (int i = 1; i < argc; i++) {
-        const char* a = argv[i];
+namespace {
+
+const float kTimestep = 0.0000005f;        // particles.cpp:88
+
+// ---- everything the command line can say ------------------------------------------------------------------------------
+struct Options {
+    struct {
+        uint n = 262144;                   // NUM_PARTICLES, particleSystem.h:15
+        float box = 2.0f;                  // BOX_SIZE
+        int iterations = 100, substeps = 1, dump = 0, device = 0;      // (findCudaDevice: -device=N, else the first, helper_cuda.h:845)
+        uint grid = 0;                     // 0: the reference's formula nextPow2(box / (0.66666 h))
+        ParticleSystem::ParticleConfig ic = ParticleSystem::CONFIG_GRID;   // initParticleSystem resets to CONFIG_GRID
+        const char* load = nullptr;        // -load=, or -file=
+        bool help = false, warmup = true;
+        uint capacity = 0;                 // -capacity=M; default -n, with -emit / -add twice -n: they need room to grow
+        const char *out = nullptr, *save = nullptr, *log = nullptr;
+        double logfreq = 2000.0;           // BENCHMARK_FREQ
+        ParticleSystem::BenchmarkLogStyle logstyle = ParticleSystem::LOG_FRAMES;
+    } run;
+    struct {
+        bool on = false, has_mass = false, has_accel = false;      // -collider; -collidermass; its ax,ay,az
+        float center[3] = {0.f, 0.f, 0.f}, radius = 0.f, velocity[3] = {0.f, 0.f, 0.f}, mass = 0.f, accel[3] = {0.f, 0.f, 0.f};
+    } collider;
+    struct {                               // -obstacle= shapes or an -obstaclemesh=; the cell and the velocity serve either
+        std::vector<sph_shape> shapes;
+        const char* mesh = nullptr;
+        bool invert = false, has_velocity = false;
+        uint band = 0;                     // 0, as the cell: the library's default
+        float cell = 0.f, velocity[3] = {0.f, 0.f, 0.f};
+    } obstacle;
+    struct { bool on = false; float center[3] = {0.f, 0.f, 0.f}, velocity[3] = {0.f, 0.f, 0.f}; int radius = 0, every = 0; } emit;
+    struct { bool on = false; float lo[3] = {0.f, 0.f, 0.f}, hi[3] = {0.f, 0.f, 0.f}; int every = 1; } drain;
+    struct { bool on = false; int at = -1, count = 0; } add;
+    struct { bool given = false; int at = -1, radius = 10; } sphere;
+    struct {
+        const char* dir = nullptr;
+        int every = 1, color_mode = SPH_COLOR_INDEX, width = 640, height = 480;
+        float eye[3] = {0.f, 0.f, 3.f}, target[3] = {0.f, 0.f, 0.f}, fovy = 60.f, color_lo = 0.f, color_hi = 1.f;
+    } frames;
+    struct { bool on = false; sph_surface_style style; } surface;
+    struct { const char* dir = nullptr; int every = 1; sph_mesh_params params; } mesh;
+    struct { int gpus = 1, protocol = 3; bool on = false, onegpu = false; uint32_t lattice[3] = {0, 0, 0}; uint64_t particles = 0; } slabs;
+    bool grows() const { return emit.on || drain.on || add.on; }      // -out then has one row per creation index below the capacity
+};
+
+// ---- the parser: the only code that sees argv ---------------------------------------------------------------------------
+struct Args {
+    int argc; char** argv;
+    static const char* match(const char* a, const char* name) {      // what follows `name` in a, any number of dashes skipped
         while (*a == '-') a++;
-        size_t l = strlen(name);
-        if (!strncmp(a, name, l) && (a[l] == 0 || a[l] == '=')) return true;
+        const size_t l = strlen(name);
+        return strncmp(a, name, l) ? nullptr : a + l;
     }
+    bool flag(const char* name) const {                               // checkCmdLineFlag, helper_string.h:111
+        for (int i = 1; i < argc; i++) if (const char* t = match(argv[i], name)) if (*t == 0 || *t == '=') return true;
+        return false;
+    }
+    const char* value(const char* name) const {                       // of the first -name=...
+        for (int i = 1; i < argc; i++) if (const char* t = match(argv[i], name)) if (*t == '=') return t + 1;
+        return nullptr;
+    }
+};
+
+__attribute__((format(printf, 1, 2))) bool fail(const char* fmt, ...) {      // the error line; false, for `return fail(...)`
+    va_list ap; va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap);
     return false;
 }
 
-static const char* value(int argc, char** argv, const char* name) {
-    for (int i = 1; i < argc; i++) {
-        const char* a = argv[i];
-        while (*a == '-') a++;
-        size_t l = strlen(name);
-        if (!strncmp(a, name, l) && a[l] == '=') return a + l + 1;
-    }
-    return nullptr;
+bool parse_every(const Args& a, const char* name, int& every) {      // -name=K, a whole number >= 1
+    const char* v = a.value(name);
+    if (char extra = 0; v && (sscanf(v, "%d%c", &every, &extra) != 1 || every < 1)) return fail("-%s=%s: expected a whole number >= 1\n", name, v);
+    return true;
 }
 
-// ---- -obstacle=sphere:cx,cy,cz,r | box:cx,cy,cz,hx,hy,hz[,r] | capsule:ax,ay,az,bx,by,bz,r | plane:px,py,pz,nx,ny,nz -------------
-// (repeatable; a leading `!` inverts the shape).  The library checks the values; this only checks the form.
-static bool parse_obstacle(const char* arg, sph_shape* out) {
+bool parse_run(const Args& a, Options& o) {
+    auto& r = o.run;
+    if (const char* v = a.value("n")) r.n = (uint)strtoul(v, nullptr, 10);
+    if (const char* v = a.value("box")) r.box = (float)atof(v);
+    if (const char* v = a.value("i")) r.iterations = atoi(v);
+    if (const char* v = a.value("steps")) r.substeps = atoi(v);
+    if (const char* v = a.value("dump")) r.dump = atoi(v);
+    if (const char* v = a.value("device")) r.device = atoi(v);
+    if (const char* v = a.value("grid")) r.grid = (uint)strtoul(v, nullptr, 10);
+    if (const char* v = a.value("logfreq")) r.logfreq = atof(v);
+    r.warmup = !a.flag("nowarmup");
+    r.out = a.value("out"); r.save = a.value("save"); r.log = a.value("log");
+    if (const char* v = a.value("ic")) {
+        if (!strcmp(v, "random")) r.ic = ParticleSystem::CONFIG_RANDOM;
+        else if (strcmp(v, "grid")) return fail("-ic=%s: expected grid or random\n", v);
+    }
+    // -file=<path>: the reference runs ONE update and would compare with a reference file (particles.cpp:690-692, 194-217;
+    // the comparison itself is commented out upstream).  Here the file is a state snapshot (-save): it is loaded like -load.
+    const char* file = a.value("file");
+    r.load = a.value("load");
+    if (file && !r.load) r.load = file;
+    if (file && !a.value("i")) r.iterations = 1;                      // numIterations = 1, particles.cpp:692
+    // -benchmark selects the headless path upstream (without it a GLUT window opens); this build has no other path
+    if (!a.flag("benchmark") && !file) fprintf(stderr, "note: no OpenGL in this build -- running headless, as with -benchmark\n");
+    r.help = a.flag("help");
+    return true;
+}
+
+bool parse_collider(const Args& a, Options& o) {
+    auto& c = o.collider;
+    const char* v = a.value("collider"); if (!v) return true;
+    const int k = sscanf(v, "%f,%f,%f,%f,%f,%f,%f", &c.center[0], &c.center[1], &c.center[2], &c.radius, &c.velocity[0], &c.velocity[1], &c.velocity[2]);
+    if ((k != 4 && k != 7) || !(c.radius > 0.f)) return fail("-collider=%s: expected x,y,z,r or x,y,z,r,ux,uy,uz with r > 0\n", v);
+    return c.on = true;
+}
+
+bool parse_collider_mass(const Args& a, Options& o) {      // (after the obstacles: the order of the checks is kept)
+    auto& c = o.collider;
+    const char* v = a.value("collidermass"); if (!v) return true;
+    const int k = sscanf(v, "%f,%f,%f,%f", &c.mass, &c.accel[0], &c.accel[1], &c.accel[2]);
+    const bool finite = std::isfinite(c.mass) && std::isfinite(c.accel[0]) && std::isfinite(c.accel[1]) && std::isfinite(c.accel[2]);
+    if (!c.on || (k != 1 && k != 4) || !(c.mass >= 0.f) || !finite)
+        return fail("-collidermass=%s: expected M or M,ax,ay,az with M >= 0, next to a -collider\n", v);
+    c.has_accel = k == 4;
+    return c.has_mass = true;
+}
+
+// one -obstacle= (a leading `!` inverts the shape).  The library checks the values; this only checks the form.
+bool parse_shape(const char* arg, sph_shape* out) {
     sph_shape s{};
     if (*arg == '!') { s.invert = 1; arg++; }
     float v[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -107,9 +170,249 @@ static bool parse_obstacle(const char* arg, sph_shape* out) {
     return true;
 }
 
-// ---- -gpus=N: z-slabs through the C ABI ---------------------------------------------------------------------------
-namespace {
+bool parse_obstacles(const Args& a, Options& o) {
+    auto& ob = o.obstacle;
+    for (int i = 1; i < a.argc; i++) {
+        const char* t = Args::match(a.argv[i], "obstacle=");
+        sph_shape sh;
+        if (t && !parse_shape(t, &sh))
+            return fail("-obstacle=%s: expected [!]sphere:cx,cy,cz,r | [!]box:cx,cy,cz,hx,hy,hz[,r] | [!]capsule:ax,ay,az,bx,by,bz,r | [!]plane:px,py,pz,nx,ny,nz\n", t);
+        if (t) ob.shapes.push_back(sh);
+    }
+    const char* cell = a.value("obstaclecell"); if (cell) ob.cell = (float)atof(cell);
+    if (const char* v = a.value("obstaclevel")) {
+        if (sscanf(v, "%f,%f,%f", &ob.velocity[0], &ob.velocity[1], &ob.velocity[2]) != 3) return fail("-obstaclevel=%s: expected ux,uy,uz\n", v);
+        ob.has_velocity = true;
+    }
+    ob.mesh = a.value("obstaclemesh");
+    if (const char* v = a.value("obstacleband")) {
+        char* end = nullptr;
+        const long b = strtol(v, &end, 10);
+        if (end == v || *end || b < 1 || b > SPH_OBSTACLE_MESH_MAX_BAND) return fail("-obstacleband=%s: expected 1..%d\n", v, SPH_OBSTACLE_MESH_MAX_BAND);
+        ob.band = (uint)b;
+    }
+    ob.invert = a.flag("obstacleinvert");
+    if (ob.mesh && !ob.shapes.empty()) return fail("-obstaclemesh and -obstacle exclude each other: a context holds one grid (no union of a mesh with shapes)\n");
+    if (ob.mesh && !*ob.mesh) return fail("-obstaclemesh=: expected a Wavefront OBJ file\n");
+    if (!ob.mesh && (ob.band || ob.invert)) return fail("-obstacleband / -obstacleinvert go with an -obstaclemesh\n");
+    if (ob.shapes.empty() && !ob.mesh && (ob.has_velocity || cell)) return fail("-obstaclecell / -obstaclevel go with an -obstacle\n");
+    return true;
+}
 
+bool parse_emit_drain(const Args& a, Options& o) {
+    if (const char* v = a.value("emit")) {
+        auto& e = o.emit;
+        float rr = 0.f;
+        const int k = sscanf(v, "%f,%f,%f,%f,%f,%f,%f,%d", &e.center[0], &e.center[1], &e.center[2], &rr, &e.velocity[0], &e.velocity[1], &e.velocity[2], &e.every);
+        e.radius = (int)rr;
+        if (k != 8 || e.radius < 0 || (float)e.radius != rr || e.every < 1)
+            return fail("-emit=%s: expected x,y,z,r,vx,vy,vz,every with r a whole number of lattice spacings >= 0 and every >= 1\n", v);
+        e.on = true;
+    }
+    if (const char* v = a.value("drain")) {
+        auto& d = o.drain;
+        const int k = sscanf(v, "%f,%f,%f,%f,%f,%f,%d", &d.lo[0], &d.lo[1], &d.lo[2], &d.hi[0], &d.hi[1], &d.hi[2], &d.every);
+        if ((k != 6 && k != 7) || d.every < 1) return fail("-drain=%s: expected x0,y0,z0,x1,y1,z1 or x0,y0,z0,x1,y1,z1,every with every >= 1\n", v);
+        d.on = true;
+    }
+    return true;
+}
+
+bool parse_frames(const Args& a, Options& o) {
+    auto& f = o.frames;
+    char extra = 0;
+    f.dir = a.value("frames");
+    if (a.flag("frames") && (!f.dir || !*f.dir)) return fail("-frames: expected -frames=<directory>\n");
+    if (!parse_every(a, "frameevery", f.every)) return false;
+    if (const char* v = a.value("framesize")) {
+        int fw = 0, fh = 0;
+        if (sscanf(v, "%dx%d%c", &fw, &fh, &extra) != 2 || fw < 1 || fw > SPH_RENDER_MAX_SIZE || fh < 1 || fh > SPH_RENDER_MAX_SIZE)
+            return fail("-framesize=%s: expected <W>x<H> with 1..%d each\n", v, SPH_RENDER_MAX_SIZE);
+        f.width = fw; f.height = fh;
+    }
+    if (const char* v = a.value("camera")) {
+        float c[7] = {f.eye[0], f.eye[1], f.eye[2], f.target[0], f.target[1], f.target[2], f.fovy};
+        const int k = sscanf(v, "%f,%f,%f,%f,%f,%f,%f%c", &c[0], &c[1], &c[2], &c[3], &c[4], &c[5], &c[6], &extra);
+        bool ok = (k == 6 || k == 7) && c[6] > 0.f && c[6] < 180.f;
+        for (int q = 0; q < 7; q++) ok = ok && std::isfinite(c[q]);
+        ok = ok && !(c[0] == c[3] && c[2] == c[5]);      // up is +y: the view direction must not be vertical (nor null)
+        if (!ok) return fail("-camera=%s: expected ex,ey,ez,tx,ty,tz or ex,ey,ez,tx,ty,tz,fovy with 0 < fovy < 180 and a view direction that is not vertical\n", v);
+        for (int q = 0; q < 3; q++) { f.eye[q] = c[q]; f.target[q] = c[3 + q]; }
+        f.fovy = c[6];
+    }
+    if (const char* v = a.value("color")) {
+        bool ok = true;
+        if (!strcmp(v, "index")) f.color_mode = SPH_COLOR_INDEX;
+        else if (!strncmp(v, "speed:", 6) || !strncmp(v, "density:", 8)) {
+            f.color_mode = v[0] == 's' ? SPH_COLOR_SPEED : SPH_COLOR_DENSITY;
+            ok = sscanf(strchr(v, ':') + 1, "%f:%f%c", &f.color_lo, &f.color_hi, &extra) == 2 && std::isfinite(f.color_lo) && std::isfinite(f.color_hi) &&
+                 f.color_lo != f.color_hi;
+        } else ok = false;
+        if (!ok) return fail("-color=%s: expected index, speed:<lo>:<hi> or density:<lo>:<hi> with lo != hi\n", v);
+    }
+    auto& s = o.surface;      // -surface -tint -absorb: options of -frames
+    s.on = a.flag("surface");
+    sph_surface_defaults(&s.style);
+    if (!s.on && !a.value("tint") && !a.value("absorb")) return true;
+    if (!o.frames.dir || !s.on)
+        return fail("-surface / -tint / -absorb: expected -frames=<directory> -surface[=<r>,<K>[,<tau>]] [-tint=<r>,<g>,<b>] [-absorb=<r>,<g>,<b>]\n");
+    if (const char* v = a.value("surface")) {
+        int sr = 0, sk = 0;
+        float tau = 0.f;
+        const int k = sscanf(v, "%d,%d,%f%c", &sr, &sk, &tau, &extra);
+        if ((k != 2 && k != 3) || sr < 0 || sr > SPH_SURFACE_MAX_RADIUS_PX || sk < 0 || sk > SPH_SURFACE_MAX_ITERATIONS || !std::isfinite(tau) || tau < 0.f)
+            return fail("-surface=%s: expected <r>,<K> or <r>,<K>,<tau> with r 0..%d, K 0..%d and tau >= 0\n", v, SPH_SURFACE_MAX_RADIUS_PX, SPH_SURFACE_MAX_ITERATIONS);
+        s.style.smooth_radius_px = (uint32_t)sr;
+        s.style.smooth_iterations = (uint32_t)sk;
+        s.style.depth_falloff = tau;
+    }
+    const char* names[2] = {"tint", "absorb"};
+    float* fields[2] = {s.style.tint, s.style.absorb};
+    for (int n = 0; n < 2; n++)
+        if (const char* v = a.value(names[n])) {
+            float c3[3] = {0.f, 0.f, 0.f};
+            bool ok = sscanf(v, "%f,%f,%f%c", &c3[0], &c3[1], &c3[2], &extra) == 3;
+            for (int q = 0; q < 3; q++) ok = ok && std::isfinite(c3[q]) && c3[q] >= 0.f;
+            if (!ok) return fail("-%s=%s: expected <r>,<g>,<b>, each finite and >= 0\n", names[n], v);
+            for (int q = 0; q < 3; q++) fields[n][q] = c3[q];
+        }
+    return true;
+}
+
+bool parse_mesh(const Args& a, Options& o) {
+    auto& m = o.mesh;
+    char extra = 0;
+    m.dir = a.value("mesh");
+    sph_mesh_defaults(&m.params);
+    if (a.flag("mesh") && (!m.dir || !*m.dir)) return fail("-mesh: expected -mesh=<directory>\n");
+    if (!parse_every(a, "meshevery", m.every)) return false;
+    const char* names[3] = {"meshcell", "meshradius", "iso"};
+    float* fields[3] = {&m.params.spacing, &m.params.radius, &m.params.iso};
+    bool any = a.value("meshevery") != nullptr;
+    for (int n = 0; n < 3; n++)
+        if (const char* v = a.value(names[n])) {
+            float x = 0.f;
+            if (sscanf(v, "%f%c", &x, &extra) != 1 || !std::isfinite(x) || !(x > 0.f))
+                return fail("-%s=%s: expected a number > 0 (an option of -mesh=<directory>)\n", names[n], v);
+            *fields[n] = x;
+            any = true;
+        }
+    if (!m.dir && any) return fail("-meshevery / -meshcell / -meshradius / -iso: expected -mesh=<directory> next to them\n");
+    return true;
+}
+
+// what joins the fluid at one update, -add and -sphere, and the room for all who join (after -emit: the default depends on it)
+bool parse_add_sphere(const Args& a, Options& o) {
+    auto& r = o.run;
+    if (const char* v = a.value("add")) {
+        if (sscanf(v, "%d,%d", &o.add.at, &o.add.count) != 2 || o.add.at < 0 || o.add.count < 1) return fail("-add=%s: expected <update>,<count>\n", v);
+        o.add.on = true;
+    }
+    if (const char* v = a.value("sphere")) {
+        o.sphere.given = true; o.sphere.at = atoi(v);
+        if (const char* c = strchr(v, ',')) o.sphere.radius = atoi(c + 1);
+    }
+    r.capacity = r.n;
+    if (o.emit.on || o.add.on) r.capacity = r.n < 0x7FFFFFFFu / 2u ? 2u * r.n : r.n;
+    if (const char* v = a.value("capacity")) r.capacity = (uint)strtoul(v, nullptr, 10);
+    return true;
+}
+
+// -gpus and its options, and what a slab run cannot take
+bool parse_slabs(const Args& a, Options& o) {
+    auto& s = o.slabs;
+    if (const char* v = a.value("gpus")) s.gpus = atoi(v);
+    s.on = s.gpus > 1 || (s.gpus == 1 && a.flag("slab"));     // (-gpus=1 -slab: the same machinery with one rank -- fork, RCCL communicator of one)
+    if (!s.on) return true;
+    const struct { bool given; const char* what; const char* reason; } one_device_only[] = {      // the first row that was given reports
+        {o.grows(), "-emit / -drain / -add are", "sph_emit and sph_remove work on a whole-domain context (the slab step sizes its messages from "
+                                                 "the previous step's counts); run them on one device"},
+        {o.surface.on, "-surface is", "sph_render_surface works on a whole-domain context (the ranks would have to composite their images); run it on one device"},
+        {o.mesh.dir != nullptr, "-mesh is", "sph_mesh_extract works on a whole-domain context (the ranks would have to share a lattice seam); run it on one device"},
+        {o.frames.dir != nullptr, "-frames is", "sph_render works on a whole-domain context (the ranks would have to composite their images); run it on one device"},
+        {o.collider.on, "-collider is", "run it on one device, or set the sphere on every rank through the library "
+                                        "(gpufluidsimulator_amd.slab.NativeSlabSimulation(colliders=...))"},
+        {!o.obstacle.shapes.empty(), "-obstacle is", "sph_obstacle_build works on a whole-domain context (the slab step makes several force launches per step); "
+                                                     "run it on one device"},
+        {o.obstacle.mesh != nullptr, "-obstaclemesh is", "sph_obstacle_build_obj works on a whole-domain context; run it on one device"},
+    };
+    for (const auto& rule : one_device_only)
+        if (rule.given) return fail("%s not supported with -gpus=%d%s: %s\n", rule.what, s.gpus, s.gpus == 1 ? " -slab" : "", rule.reason);
+    if (o.run.ic != ParticleSystem::CONFIG_GRID || o.run.load || o.sphere.given || o.run.save || o.run.log || o.run.dump)
+        return fail("-gpus=%d runs the dam-break lattice (-ic=grid) and takes -n -box -grid -i -steps -lattice -out -device -onegpu -nowarmup\n", s.gpus);
+    uint32_t cube = (uint32_t)std::floor(std::cbrt((double)o.run.n));
+    while ((uint64_t)cube * cube * cube < o.run.n) cube++;                      // the lattice of reset(CONFIG_GRID), the first -n points of it
+    s.lattice[0] = s.lattice[1] = s.lattice[2] = cube; s.particles = o.run.n;
+    if (const char* v = a.value("lattice")) {
+        if (sscanf(v, "%u,%u,%u", &s.lattice[0], &s.lattice[1], &s.lattice[2]) != 3) return fail("-lattice=nx,ny,nz\n");
+        s.particles = (uint64_t)s.lattice[0] * s.lattice[1] * s.lattice[2];
+    }
+    if (const char* v = a.value("protocol")) s.protocol = atoi(v);
+    if (s.protocol != 1 && s.protocol != 3) return fail("-protocol=%d: 3 (three message groups per step) or 1 (one)\n", s.protocol);
+    s.onegpu = a.flag("onegpu");
+    return true;
+}
+
+// The groups in the order of their checks: a command line with two mistakes reports the first of them.  -help is looked at
+// right after -ic (parse_run) and ends the parsing.
+bool parse_options(int argc, char** argv, Options& o) {
+    const Args a{argc, argv};
+    if (!parse_run(a, o)) return false;
+    if (o.run.help) return true;
+    if (!(parse_collider(a, o) && parse_obstacles(a, o) && parse_collider_mass(a, o) && parse_emit_drain(a, o) && parse_frames(a, o) &&
+          parse_mesh(a, o) && parse_add_sphere(a, o) && parse_slabs(a, o)))
+        return false;
+    // -logstyle=oscar: the line form of the reference's committed logs (benchmarks/oscar/); default: what its source writes (particleSystem.cpp:703-714)
+    const char* st = o.run.log ? a.value("logstyle") : nullptr;
+    if (st && strcmp(st, "oscar") && strcmp(st, "frames")) return fail("-logstyle=%s: expected oscar or frames\n", st);
+    if (st && !strcmp(st, "oscar")) o.run.logstyle = ParticleSystem::LOG_OSCAR;
+    return true;
+}
+
+void print_help() {
+    printf("usage: sph_headless [-benchmark] [-n=<particles>] [-box=<edge>] [-i=<iterations>] [-device=<id>] [-grid=<cells per axis>] [-ic=grid|random] [-steps=<per "
+           "update>] [-gpus=<N> [-onegpu] [-slab] [-lattice=nx,ny,nz] [-protocol=1|3]] [-dump=<count>] [-log=<file> [-logfreq=<ms>] [-logstyle=oscar|frames]] "
+           "[-sphere=<update>[,<radius>]] [-collider=<x>,<y>,<z>,<radius>[,<ux>,<uy>,<uz>]] [-collidermass=<M>[,<ax>,<ay>,<az>]] [-obstacle=<shape> ... "
+           "[-obstaclecell=<s>] [-obstaclevel=<ux>,<uy>,<uz>]] [-obstaclemesh=<file.obj> [-obstacleband=<N>] [-obstacleinvert] [-obstaclecell=<s>] "
+           "[-obstaclevel=<ux>,<uy>,<uz>]] [-emit=<x>,<y>,<z>,<r>,<vx>,<vy>,<vz>,<every>] [-drain=<x0>,<y0>,<z0>,<x1>,<y1>,<z1>[,<every>]] [-add=<update>,<count>] "
+           "[-capacity=<particles>] [-out=<file>] [-save=<file>] [-load=<file>] [-file=<file>] [-frames=<dir> [-frameevery=<K>] [-framesize=<W>x<H>] "
+           "[-camera=<ex>,<ey>,<ez>,<tx>,<ty>,<tz>[,<fovy>]] [-color=index|speed:<lo>:<hi>|density:<lo>:<hi>] [-surface[=<r>,<K>[,<tau>]] [-tint=<r>,<g>,<b>] "
+           "[-absorb=<r>,<g>,<b>]]] [-mesh=<dir> [-meshevery=<K>] [-meshcell=<s>] [-meshradius=<r>] [-iso=<v>]]\n"
+           "  -collider: a solid sphere the fluid flows around, moving at (ux, uy, uz) (default: at rest); one device only\n"
+           "  -collidermass: the -collider sphere is a free body of mass M > 0 that the fluid pushes, under the acceleration (ax, ay, az) (default: (0, gravity_y, 0) of "
+           "the run), or with M = 0 a kinematic obstacle whose load is wanted; prints its centre, velocity and last impulse at the end; one device only\n"
+           "  -obstacle: a solid the fluid collides with, [!]sphere:cx,cy,cz,r | [!]box:cx,cy,cz,hx,hy,hz[,r] | [!]capsule:ax,ay,az,bx,by,bz,r | "
+           "[!]plane:px,py,pz,nx,ny,nz (solid behind the normal); repeatable, the union is rasterised on the device as one grid of signed distances over the box, `!` "
+           "inverts a shape; -obstaclecell the grid spacing (default: the particle diameter), -obstaclevel a uniform velocity of the whole grid; one device only\n"
+           "  -obstaclemesh: a closed triangle mesh (Wavefront OBJ: v and f lines) as the solid, voxelised on the device into signed distances -obstacleband nodes wide "
+           "(1..16, default 3); -obstacleinvert: the fluid is inside the mesh; honours -obstaclecell and -obstaclevel; prints triangles used and skipped, lost crossings "
+           "and odd columns (a closed mesh: 0 and 0); not together with -obstacle; one device only\n"
+           "  -emit: every <every> updates append a lattice ball of radius <r> spacings at (x, y, z) moving at (vx, vy, vz), if its place is clear\n"
+           "  -drain: every <every> updates (default 1) remove the particles inside the box [x0,x1) x [y0,y1) x [z0,z1); one device only\n"
+           "  -frames: render the particles on the device after the updates 0, K, 2K, ... (-frameevery=K, default 1) and write <dir>/frame_NNNNNN.ppm (binary PPM), "
+           "NNNNNN = the 0-based number of the update the picture follows; -framesize default 640x480 (1..4096 each), -camera default 0,0,3,0,0,0,60 (eye, target, "
+           "vertical field of view in degrees: the reference's view), -color default index (the reference's colouring), or speed / density mapped from [lo, hi]; one "
+           "device only\n"
+           "  -surface: with -frames, draw the fluid as a surface instead of sphere sprites: the spheres' depth smoothed <K> times (0..8, default 2) over a radius of <r> "
+           "pixels (0..16, default 5) with the depth falloff <tau> (world units, default 0 = four particle radii), normals from the smoothed depth and a water-like "
+           "shading; -tint the base colour (default 0.25,0.55,0.95), -absorb the absorption per unit of thickness and channel (default 6,2,0.5; 0,0,0 = no thickness "
+           "pass); one device only\n"
+           "  -mesh: extract the fluid's surface on the device as a closed triangle mesh after the updates 0, K, 2K, ... (-meshevery=K, default 1) and write "
+           "<dir>/mesh_NNNNN.obj (Wavefront OBJ), NNNNN = the 0-based number of the update the mesh follows; -meshcell the lattice spacing (default: the particle "
+           "radius), -meshradius each particle's reach (default three spacings, at most eight), -iso the level of the surface (default 0.5); independent of -frames; one "
+           "device only\n");
+}
+
+// the reference's line (particles.cpp:191-192), then the same as JSON; `more` goes on inside the JSON object
+void print_result(unsigned long long particles, int iterations, int substeps, double secs, unsigned devices, const char* more) {
+    const double avg = secs / (iterations > 0 ? iterations : 1);
+    printf("particles, Throughput = %.4f KParticles/s, Time = %.5f s, Size = %llu particles, NumDevsUsed = %u, Workgroup = %u\n",
+           (1.0e-3 * (double)particles) / avg, avg, particles, devices, 0);
+    printf("{\"particle_steps_per_s\": %.1f, \"particles\": %llu, \"iterations\": %d, \"steps_per_update\": %d, \"seconds\": %.6f%s}\n",
+           (double)particles * iterations * substeps / secs, particles, iterations, substeps, secs, more);
+}
+
+// ---- -gpus=N: z-slabs through the C ABI ---------------------------------------------------------------------------
 struct SlabJob {
     uint32_t lattice[3];
     uint64_t particles;              // the first `particles` lattice points (creation index = x + nx (y + ny z))
@@ -124,21 +427,26 @@ struct SlabJob {
 
 struct Plan { std::vector<uint32_t> cuts; std::vector<uint64_t> hist; uint64_t per_layer = 0; };
 
+// the cell layer of lattice plane iz of reset(CONFIG_GRID) -- a particle radius from the wall, a diameter apart -- moved by dz
+uint32_t plane_layer(const SlabJob& j, uint32_t iz, double dz = 0.0) {
+    const double radius = 1.0 / 64.0, z = -j.box / 2.0 + radius + 2.0 * radius * iz + dz;
+    const long c = (long)std::floor((z + j.box / 2.0) / j.box * j.grid);
+    return (uint32_t)std::min<long>(std::max<long>(c, 0), (long)j.grid - 1);
+}
+
 // Count-balanced cuts of whole cell layers, every slab at least two layers (gpufluidsimulator_amd/slab.py: choose_cuts).
 // The lattice planes must not straddle a cell face (every BASELINE config: planes sit a quarter of a cell from the faces,
 // the jitter is 0.08 of a cell), so that a slab is one run of creation indices generated on its own device.
 bool plan_slabs(const SlabJob& j, int world, Plan& pl, std::string& err) {
     const uint32_t nx = j.lattice[0], ny = j.lattice[1], nz = j.lattice[2], gz = j.grid;
-    const double radius = 1.0 / 64.0, spacing = 2.0 * radius, amp = 0.5 * j.box * 0.01 * radius + 1e-4;
+    const double amp = 0.5 * j.box * 0.01 * (1.0 / 64.0) + 1e-4;      // the jitter of a plane's particles
     pl.hist.assign(gz, 0);
-    auto layer = [&](double z) { long c = (long)std::floor((z + j.box / 2.0) / j.box * gz); return (uint32_t)std::min<long>(std::max<long>(c, 0), gz - 1); };
     for (uint32_t iz = 0; iz < nz; iz++) {
         const uint64_t first = (uint64_t)iz * nx * ny;
         if (first >= j.particles) break;
         const uint64_t cnt = std::min<uint64_t>((uint64_t)nx * ny, j.particles - first);
-        const double zc = -j.box / 2.0 + radius + spacing * iz;
-        if (layer(zc - amp) != layer(zc + amp)) { err = "a lattice plane straddles a cell face: use `python bench.py --gpus N`"; return false; }
-        pl.hist[layer(zc)] += cnt;
+        if (plane_layer(j, iz, -amp) != plane_layer(j, iz, amp)) { err = "a lattice plane straddles a cell face: use `python bench.py --gpus N`"; return false; }
+        pl.hist[plane_layer(j, iz)] += cnt;
     }
     const uint32_t min_layers = j.protocol == 1 ? 4u : 2u;      // (the one-message step: four layers per slab, slab.py choose_cuts)
     if ((uint64_t)world * min_layers > gz) { err = "more slabs than groups of " + std::to_string(min_layers) + " cell layers"; return false; }
@@ -191,15 +499,12 @@ void rank_main(const SlabJob& j, const Plan& pl, int rank, int world, int device
     uint64_t n_own = 0, first = 0;
     {   // my lattice planes: one run of creation indices
         const uint32_t nx = j.lattice[0], ny = j.lattice[1];
-        const double radius = 1.0 / 64.0, spacing = 2.0 * radius;
         bool any = false;
         for (uint32_t iz = 0; iz < j.lattice[2]; iz++) {
             const uint64_t f = (uint64_t)iz * nx * ny;
             if (f >= j.particles) break;
-            const double zc = -j.box / 2.0 + radius + spacing * iz;
-            long c = (long)std::floor((zc + j.box / 2.0) / j.box * j.grid);
-            c = std::min<long>(std::max<long>(c, 0), (long)j.grid - 1);
-            if ((uint32_t)c < z_lo || (uint32_t)c >= z_hi) continue;
+            const uint32_t c = plane_layer(j, iz);
+            if (c < z_lo || c >= z_hi) continue;
             if (!any) { first = f; any = true; }
             n_own += std::min<uint64_t>((uint64_t)nx * ny, j.particles - f);
         }
@@ -404,486 +709,148 @@ int run_slabs(const SlabJob& j, int world, bool onegpu, int device0) {
     }
     if (bad) return EXIT_FAILURE;
     if (owned != j.particles) { fprintf(stderr, "the slabs hold %llu of %llu particles\n", (unsigned long long)owned, (unsigned long long)j.particles); return EXIT_FAILURE; }
-    const double avg = secs / (j.iterations > 0 ? j.iterations : 1);
-    printf("particles, Throughput = %.4f KParticles/s, Time = %.5f s, Size = %llu particles, NumDevsUsed = %u, Workgroup = %u\n",
-           (1.0e-3 * (double)j.particles) / avg, avg, (unsigned long long)j.particles, (unsigned)world, 0);
-    printf("{\"particle_steps_per_s\": %.1f, \"particles\": %llu, \"iterations\": %d, \"steps_per_update\": %d, \"seconds\": %.6f, "
-           "\"gpus\": %d, \"ranks_as\": \"%s\", \"ping_us\": [%.1f, %.1f, %.1f]}\n",
-           (double)j.particles * j.iterations * j.substeps / secs, (unsigned long long)j.particles, j.iterations, j.substeps, secs, world,
-           onegpu ? "threads" : "processes", res[0].ping_us[0], res[0].ping_us[1], res[0].ping_us[2]);
+    char more[256];
+    snprintf(more, sizeof more, ", \"gpus\": %d, \"ranks_as\": \"%s\", \"ping_us\": [%.1f, %.1f, %.1f]", world, onegpu ? "threads" : "processes",
+             res[0].ping_us[0], res[0].ping_us[1], res[0].ping_us[2]);
+    print_result(j.particles, j.iterations, j.substeps, secs, (unsigned)world, more);
     return 0;
 }
 
-}  // namespace
+SlabJob slab_job(const Options& o) {
+    SlabJob j{};
+    for (int a = 0; a < 3; a++) j.lattice[a] = o.slabs.lattice[a];
+    j.box = o.run.box;
+    j.grid = o.run.grid ? o.run.grid : sph_grid_dim_for_edge(o.run.box, 0.1f);
+    j.iterations = o.run.iterations; j.substeps = o.run.substeps; j.warmup = o.run.warmup; j.dt = kTimestep;
+    j.particles = o.slabs.particles; j.out = o.run.out; j.protocol = o.slabs.protocol;
+    return j;
+}
 
-int main(int argc, char** argv) {
-    uint numParticles = 262144;            // NUM_PARTICLES, particleSystem.h:15
-    float box = 2.0f;                      // BOX_SIZE
-    int iterations = 100, substeps = 1, dump = 0;
-    const float timestep = 0.0000005f;     // particles.cpp:88
-    if (const char* v = value(argc, argv, "n")) numParticles = (uint)strtoul(v, nullptr, 10);
-    if (const char* v = value(argc, argv, "box")) box = (float)atof(v);
-    if (const char* v = value(argc, argv, "i")) iterations = atoi(v);
-    if (const char* v = value(argc, argv, "steps")) substeps = atoi(v);
-    if (const char* v = value(argc, argv, "dump")) dump = atoi(v);
-    int device = 0;                        // findCudaDevice: -device=N, else the first device (helper_cuda.h:845)
-    if (const char* v = value(argc, argv, "device")) device = atoi(v);
-    uint gridDim = 0;                      // 0: the reference's formula nextPow2(box / (0.66666 h))
-    if (const char* v = value(argc, argv, "grid")) gridDim = (uint)strtoul(v, nullptr, 10);
-    ParticleSystem::ParticleConfig ic = ParticleSystem::CONFIG_GRID;   // initParticleSystem resets to CONFIG_GRID
-    if (const char* v = value(argc, argv, "ic")) {
-        if (!strcmp(v, "random")) ic = ParticleSystem::CONFIG_RANDOM;
-        else if (strcmp(v, "grid")) { fprintf(stderr, "-ic=%s: expected grid or random\n", v); return EXIT_FAILURE; }
+// ---- one device: the reference's run on a ParticleSystem ---------------------------------------------------------------
+struct Run {
+    ParticleSystem* ps = nullptr;
+    uint particles = 0;                    // -n, or what the snapshot holds
+    uint ball_points = 0, start = 0, emitted = 0;      // of the faucet's ball; particles at the first update; appended since
+    bool full_noted = false;
+};
+
+// the ParticleSystem as the options ask for it: collider, obstacles, log, frames, mesh
+bool set_up(const Options& o, Run& run) {
+    const auto& r = o.run;
+    int is950 = 0;      // cudaInit (particleSystem.cu:432-435) -> findCudaDevice -> cudaSetDevice, then initParticleSystem
+    if (sph_device_count(&is950) <= 0 || !is950) return fail("No gfx950 (MI355X) device found, exiting\n");
+    if (sph_select_device(r.device) < 0) return fail("-device=%d: %s\n", r.device, sph_last_error());
+    ParticleSystem* ps = run.ps = new ParticleSystem(r.n, make_float3(r.box, r.box, r.box), ParticleSystem::HIP_PARALLEL, uint3{r.grid, r.grid, r.grid}, r.capacity);
+    ps->reset(r.ic);                                      // initParticleSystem, particles.cpp:119-132
+    run.particles = r.n;
+    if (r.load) {
+        ps->loadState(r.load);
+        run.particles = (uint)ps->getNumParticles();      // the snapshot decides how many particles there are
     }
-    // -file=<path>: the reference runs ONE update and would compare with a reference file (particles.cpp:690-692, 194-217;
-    // the comparison itself is commented out upstream).  Here the file is a state snapshot (-save): it is loaded like -load.
-    const char* file = value(argc, argv, "file");
-    const char* load = value(argc, argv, "load");
-    if (file && !load) load = file;
-    if (file && !value(argc, argv, "i")) iterations = 1;                    // numIterations = 1, particles.cpp:692
-    // -benchmark selects the headless path upstream (without it a GLUT window opens); this build has no other path
-    const bool benchmark = flag(argc, argv, "benchmark");
-    if (!benchmark && !file) fprintf(stderr, "note: no OpenGL in this build -- running headless, as with -benchmark\n");
-    if (flag(argc, argv, "help")) {
-        printf("usage: sph_headless [-benchmark] [-n=<particles>] [-box=<edge>] [-i=<iterations>] [-device=<id>] [-grid=<cells per axis>] "
-               "[-ic=grid|random] [-steps=<per update>] [-gpus=<N> [-onegpu] [-slab] [-lattice=nx,ny,nz] [-protocol=1|3]] "
-               "[-dump=<count>] [-log=<file> [-logfreq=<ms>] [-logstyle=oscar|frames]] [-sphere=<update>[,<radius>]] "
-               "[-collider=<x>,<y>,<z>,<radius>[,<ux>,<uy>,<uz>]] [-collidermass=<M>[,<ax>,<ay>,<az>]] "
-               "[-obstacle=<shape> ... [-obstaclecell=<s>] [-obstaclevel=<ux>,<uy>,<uz>]] "
-               "[-obstaclemesh=<file.obj> [-obstacleband=<N>] [-obstacleinvert] [-obstaclecell=<s>] [-obstaclevel=<ux>,<uy>,<uz>]] [-emit=<x>,<y>,<z>,<r>,<vx>,<vy>,<vz>,<every>] "
-               "[-drain=<x0>,<y0>,<z0>,<x1>,<y1>,<z1>[,<every>]] [-add=<update>,<count>] [-capacity=<particles>] [-out=<file>] [-save=<file>] [-load=<file>] [-file=<file>] "
-               "[-frames=<dir> [-frameevery=<K>] [-framesize=<W>x<H>] [-camera=<ex>,<ey>,<ez>,<tx>,<ty>,<tz>[,<fovy>]] [-color=index|speed:<lo>:<hi>|density:<lo>:<hi>] "
-               "[-surface[=<r>,<K>[,<tau>]] [-tint=<r>,<g>,<b>] [-absorb=<r>,<g>,<b>]]] "
-               "[-mesh=<dir> [-meshevery=<K>] [-meshcell=<s>] [-meshradius=<r>] [-iso=<v>]]\n"
-               "  -collider: a solid sphere the fluid flows around, moving at (ux, uy, uz) (default: at rest); one device only\n"
-               "  -collidermass: the -collider sphere is a free body of mass M > 0 that the fluid pushes, under the acceleration (ax, ay, az) "
-               "(default: (0, gravity_y, 0) of the run), or with M = 0 a kinematic obstacle whose load is wanted; prints its centre, velocity "
-               "and last impulse at the end; one device only\n"
-               "  -obstacle: a solid the fluid collides with, [!]sphere:cx,cy,cz,r | [!]box:cx,cy,cz,hx,hy,hz[,r] | [!]capsule:ax,ay,az,bx,by,bz,r "
-               "| [!]plane:px,py,pz,nx,ny,nz (solid behind the normal); repeatable, the union is rasterised on the device as one grid of signed "
-               "distances over the box, `!` inverts a shape; -obstaclecell the grid spacing (default: the particle diameter), -obstaclevel a "
-               "uniform velocity of the whole grid; one device only\n"
-               "  -obstaclemesh: a closed triangle mesh (Wavefront OBJ: v and f lines) as the solid, voxelised on the device into signed "
-               "distances -obstacleband nodes wide (1..16, default 3); -obstacleinvert: the fluid is inside the mesh; honours -obstaclecell "
-               "and -obstaclevel; prints triangles used and skipped, lost crossings and odd columns (a closed mesh: 0 and 0); not together "
-               "with -obstacle; one device only\n"
-               "  -emit: every <every> updates append a lattice ball of radius <r> spacings at (x, y, z) moving at (vx, vy, vz), if its place is clear\n"
-               "  -drain: every <every> updates (default 1) remove the particles inside the box [x0,x1) x [y0,y1) x [z0,z1); one device only\n"
-               "  -frames: render the particles on the device after the updates 0, K, 2K, ... (-frameevery=K, default 1) and write "
-               "<dir>/frame_NNNNNN.ppm (binary PPM), NNNNNN = the 0-based number of the update the picture follows; -framesize default 640x480 "
-               "(1..4096 each), -camera default 0,0,3,0,0,0,60 (eye, target, vertical field of view in degrees: the reference's view), "
-               "-color default index (the reference's colouring), or speed / density mapped from [lo, hi]; one device only\n"
-               "  -surface: with -frames, draw the fluid as a surface instead of sphere sprites: the spheres' depth smoothed <K> times (0..8, "
-               "default 2) over a radius of <r> pixels (0..16, default 5) with the depth falloff <tau> (world units, default 0 = four particle "
-               "radii), normals from the smoothed depth and a water-like shading; -tint the base colour (default 0.25,0.55,0.95), -absorb the "
-               "absorption per unit of thickness and channel (default 6,2,0.5; 0,0,0 = no thickness pass); one device only\n"
-               "  -mesh: extract the fluid's surface on the device as a closed triangle mesh after the updates 0, K, 2K, ... (-meshevery=K, "
-               "default 1) and write <dir>/mesh_NNNNN.obj (Wavefront OBJ), NNNNN = the 0-based number of the update the mesh follows; "
-               "-meshcell the lattice spacing (default: the particle radius), -meshradius each particle's reach (default three spacings, "
-               "at most eight), -iso the level of the surface (default 0.5); independent of -frames; one device only\n");
-        return 0;
-    }
-    const int gpus = value(argc, argv, "gpus") ? atoi(value(argc, argv, "gpus")) : 1;
-    // -collider=x,y,z,r[,ux,uy,uz]
-    float col[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const char* colliderArg = value(argc, argv, "collider");
-    if (colliderArg) {
-        const int k = sscanf(colliderArg, "%f,%f,%f,%f,%f,%f,%f", &col[0], &col[1], &col[2], &col[3], &col[4], &col[5], &col[6]);
-        if ((k != 4 && k != 7) || !(col[3] > 0.f)) {
-            fprintf(stderr, "-collider=%s: expected x,y,z,r or x,y,z,r,ux,uy,uz with r > 0\n", colliderArg);
-            return EXIT_FAILURE;
-        }
-    }
-    // -obstacle=<shape> (repeatable), -obstaclecell=s, -obstaclevel=ux,uy,uz
-    std::vector<sph_shape> obstacles;
-    for (int i = 1; i < argc; i++) {
-        const char* a = argv[i];
-        while (*a == '-') a++;
-        if (strncmp(a, "obstacle=", 9)) continue;
-        sph_shape sh;
-        if (!parse_obstacle(a + 9, &sh)) {
-            fprintf(stderr, "-obstacle=%s: expected [!]sphere:cx,cy,cz,r | [!]box:cx,cy,cz,hx,hy,hz[,r] | [!]capsule:ax,ay,az,bx,by,bz,r | "
-                            "[!]plane:px,py,pz,nx,ny,nz\n", a + 9);
-            return EXIT_FAILURE;
-        }
-        obstacles.push_back(sh);
-    }
-    float obstacleCell = 0.f, obstacleVel[3] = {0.f, 0.f, 0.f};
-    if (const char* v = value(argc, argv, "obstaclecell")) obstacleCell = (float)atof(v);
-    const char* obstacleVelArg = value(argc, argv, "obstaclevel");
-    if (obstacleVelArg && sscanf(obstacleVelArg, "%f,%f,%f", &obstacleVel[0], &obstacleVel[1], &obstacleVel[2]) != 3) {
-        fprintf(stderr, "-obstaclevel=%s: expected ux,uy,uz\n", obstacleVelArg);
-        return EXIT_FAILURE;
-    }
-    // -obstaclemesh=FILE.obj, -obstacleband=N, -obstacleinvert
-    const char* obstacleMesh = value(argc, argv, "obstaclemesh");
-    uint obstacleBand = 0;
-    if (const char* v = value(argc, argv, "obstacleband")) {
-        char* end = nullptr;
-        const long b = strtol(v, &end, 10);
-        if (end == v || *end || b < 1 || b > SPH_OBSTACLE_MESH_MAX_BAND) {
-            fprintf(stderr, "-obstacleband=%s: expected 1..%d\n", v, SPH_OBSTACLE_MESH_MAX_BAND);
-            return EXIT_FAILURE;
-        }
-        obstacleBand = (uint)b;
-    }
-    const bool obstacleInvert = flag(argc, argv, "obstacleinvert");
-    if (obstacleMesh && !obstacles.empty()) {
-        fprintf(stderr, "-obstaclemesh and -obstacle exclude each other: a context holds one grid (no union of a mesh with shapes)\n");
-        return EXIT_FAILURE;
-    }
-    if (obstacleMesh && !*obstacleMesh) {
-        fprintf(stderr, "-obstaclemesh=: expected a Wavefront OBJ file\n");
-        return EXIT_FAILURE;
-    }
-    if (!obstacleMesh && (obstacleBand || obstacleInvert)) {
-        fprintf(stderr, "-obstacleband / -obstacleinvert go with an -obstaclemesh\n");
-        return EXIT_FAILURE;
-    }
-    if (obstacles.empty() && !obstacleMesh && (obstacleVelArg || value(argc, argv, "obstaclecell"))) {
-        fprintf(stderr, "-obstaclecell / -obstaclevel go with an -obstacle\n");
-        return EXIT_FAILURE;
-    }
-    // -collidermass=M[,ax,ay,az]
-    float cm[4] = {0.f, 0.f, 0.f, 0.f};
-    int cmFields = 0;
-    const char* colliderMassArg = value(argc, argv, "collidermass");
-    if (colliderMassArg) {
-        cmFields = sscanf(colliderMassArg, "%f,%f,%f,%f", &cm[0], &cm[1], &cm[2], &cm[3]);
-        if (!colliderArg || (cmFields != 1 && cmFields != 4) || !(cm[0] >= 0.f) || !std::isfinite(cm[0]) || !std::isfinite(cm[1]) ||
-            !std::isfinite(cm[2]) || !std::isfinite(cm[3])) {
-            fprintf(stderr, "-collidermass=%s: expected M or M,ax,ay,az with M >= 0, next to a -collider\n", colliderMassArg);
-            return EXIT_FAILURE;
-        }
-    }
-    // -emit=x,y,z,r,vx,vy,vz,every  and  -drain=x0,y0,z0,x1,y1,z1[,every]
-    float em[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, dr[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    int emitR = 0, emitEvery = 0, drainEvery = 1;
-    const char* emitArg = value(argc, argv, "emit");
-    const char* drainArg = value(argc, argv, "drain");
-    if (emitArg) {
-        float rr = 0.f;
-        const int k = sscanf(emitArg, "%f,%f,%f,%f,%f,%f,%f,%d", &em[0], &em[1], &em[2], &rr, &em[4], &em[5], &em[6], &emitEvery);
-        emitR = (int)rr;
-        if (k != 8 || emitR < 0 || (float)emitR != rr || emitEvery < 1) {
-            fprintf(stderr, "-emit=%s: expected x,y,z,r,vx,vy,vz,every with r a whole number of lattice spacings >= 0 and every >= 1\n", emitArg);
-            return EXIT_FAILURE;
-        }
-    }
-    if (drainArg) {
-        const int k = sscanf(drainArg, "%f,%f,%f,%f,%f,%f,%d", &dr[0], &dr[1], &dr[2], &dr[3], &dr[4], &dr[5], &drainEvery);
-        if ((k != 6 && k != 7) || drainEvery < 1) {
-            fprintf(stderr, "-drain=%s: expected x0,y0,z0,x1,y1,z1 or x0,y0,z0,x1,y1,z1,every with every >= 1\n", drainArg);
-            return EXIT_FAILURE;
-        }
-    }
-    // -frames=DIR [-frameevery=K] [-framesize=WxH] [-camera=ex,ey,ez,tx,ty,tz[,fovy]] [-color=index|speed:lo:hi|density:lo:hi]
-    const char* framesDir = value(argc, argv, "frames");
-    int frameEvery = 1, colorMode = SPH_COLOR_INDEX;
-    unsigned frameW = 640, frameH = 480;
-    float camv[7] = {0.f, 0.f, 3.f, 0.f, 0.f, 0.f, 60.f}, colorLo = 0.f, colorHi = 1.f;
-    char extra = 0;
-    if (flag(argc, argv, "frames") && (!framesDir || !*framesDir)) { fprintf(stderr, "-frames: expected -frames=<directory>\n"); return EXIT_FAILURE; }
-    if (const char* v = value(argc, argv, "frameevery")) {
-        if (sscanf(v, "%d%c", &frameEvery, &extra) != 1 || frameEvery < 1) { fprintf(stderr, "-frameevery=%s: expected a whole number >= 1\n", v); return EXIT_FAILURE; }
-    }
-    if (const char* v = value(argc, argv, "framesize")) {
-        int fw = 0, fh = 0;
-        if (sscanf(v, "%dx%d%c", &fw, &fh, &extra) != 2 || fw < 1 || fw > SPH_RENDER_MAX_SIZE || fh < 1 || fh > SPH_RENDER_MAX_SIZE) {
-            fprintf(stderr, "-framesize=%s: expected <W>x<H> with 1..%d each\n", v, SPH_RENDER_MAX_SIZE);
-            return EXIT_FAILURE;
-        }
-        frameW = (unsigned)fw; frameH = (unsigned)fh;
-    }
-    if (const char* v = value(argc, argv, "camera")) {
-        const int k = sscanf(v, "%f,%f,%f,%f,%f,%f,%f%c", &camv[0], &camv[1], &camv[2], &camv[3], &camv[4], &camv[5], &camv[6], &extra);
-        bool ok = (k == 6 || k == 7) && camv[6] > 0.f && camv[6] < 180.f;
-        for (int a = 0; a < 7; a++) ok = ok && std::isfinite(camv[a]);
-        ok = ok && !(camv[0] == camv[3] && camv[2] == camv[5]);      // up is +y: the view direction must not be vertical (nor null)
-        if (!ok) {
-            fprintf(stderr, "-camera=%s: expected ex,ey,ez,tx,ty,tz or ex,ey,ez,tx,ty,tz,fovy with 0 < fovy < 180 and a view direction that is not vertical\n", v);
-            return EXIT_FAILURE;
-        }
-    }
-    if (const char* v = value(argc, argv, "color")) {
-        bool ok = true;
-        if (!strcmp(v, "index")) colorMode = SPH_COLOR_INDEX;
-        else if (!strncmp(v, "speed:", 6) || !strncmp(v, "density:", 8)) {
-            colorMode = v[0] == 's' ? SPH_COLOR_SPEED : SPH_COLOR_DENSITY;
-            ok = sscanf(strchr(v, ':') + 1, "%f:%f%c", &colorLo, &colorHi, &extra) == 2 && std::isfinite(colorLo) && std::isfinite(colorHi) && colorLo != colorHi;
-        } else ok = false;
-        if (!ok) { fprintf(stderr, "-color=%s: expected index, speed:<lo>:<hi> or density:<lo>:<hi> with lo != hi\n", v); return EXIT_FAILURE; }
-    }
-    // -surface[=r,K[,tau]] [-tint=r,g,b] [-absorb=r,g,b]
-    const bool surfaceOn = flag(argc, argv, "surface");
-    sph_surface_style surfaceStyle;
-    sph_surface_defaults(&surfaceStyle);
-    if (surfaceOn || value(argc, argv, "tint") || value(argc, argv, "absorb")) {
-        if (!framesDir || !surfaceOn) {
-            fprintf(stderr, "-surface / -tint / -absorb: expected -frames=<directory> -surface[=<r>,<K>[,<tau>]] [-tint=<r>,<g>,<b>] [-absorb=<r>,<g>,<b>]\n");
-            return EXIT_FAILURE;
-        }
-        if (const char* v = value(argc, argv, "surface")) {
-            int sr = 0, sk = 0;
-            float tau = 0.f;
-            const int k = sscanf(v, "%d,%d,%f%c", &sr, &sk, &tau, &extra);
-            if ((k != 2 && k != 3) || sr < 0 || sr > SPH_SURFACE_MAX_RADIUS_PX || sk < 0 || sk > SPH_SURFACE_MAX_ITERATIONS || !std::isfinite(tau) || tau < 0.f) {
-                fprintf(stderr, "-surface=%s: expected <r>,<K> or <r>,<K>,<tau> with r 0..%d, K 0..%d and tau >= 0\n", v, SPH_SURFACE_MAX_RADIUS_PX,
-                        SPH_SURFACE_MAX_ITERATIONS);
-                return EXIT_FAILURE;
-            }
-            surfaceStyle.smooth_radius_px = (uint32_t)sr;
-            surfaceStyle.smooth_iterations = (uint32_t)sk;
-            surfaceStyle.depth_falloff = tau;
-        }
-        const char* names[2] = {"tint", "absorb"};
-        float* fields[2] = {surfaceStyle.tint, surfaceStyle.absorb};
-        for (int a = 0; a < 2; a++)
-            if (const char* v = value(argc, argv, names[a])) {
-                float c3[3] = {0.f, 0.f, 0.f};
-                bool ok = sscanf(v, "%f,%f,%f%c", &c3[0], &c3[1], &c3[2], &extra) == 3;
-                for (int q = 0; q < 3; q++) ok = ok && std::isfinite(c3[q]) && c3[q] >= 0.f;
-                if (!ok) { fprintf(stderr, "-%s=%s: expected <r>,<g>,<b>, each finite and >= 0\n", names[a], v); return EXIT_FAILURE; }
-                for (int q = 0; q < 3; q++) fields[a][q] = c3[q];
-            }
-    }
-    // -mesh=DIR [-meshevery=K] [-meshcell=s] [-meshradius=r] [-iso=v]
-    const char* meshDir = value(argc, argv, "mesh");
-    int meshEvery = 1;
-    sph_mesh_params meshParams;
-    sph_mesh_defaults(&meshParams);
-    if (flag(argc, argv, "mesh") && (!meshDir || !*meshDir)) { fprintf(stderr, "-mesh: expected -mesh=<directory>\n"); return EXIT_FAILURE; }
-    if (const char* v = value(argc, argv, "meshevery")) {
-        if (sscanf(v, "%d%c", &meshEvery, &extra) != 1 || meshEvery < 1) { fprintf(stderr, "-meshevery=%s: expected a whole number >= 1\n", v); return EXIT_FAILURE; }
-    }
-    {
-        const char* names[3] = {"meshcell", "meshradius", "iso"};
-        float* fields[3] = {&meshParams.spacing, &meshParams.radius, &meshParams.iso};
-        for (int a = 0; a < 3; a++)
-            if (const char* v = value(argc, argv, names[a])) {
-                float x = 0.f;
-                if (sscanf(v, "%f%c", &x, &extra) != 1 || !std::isfinite(x) || !(x > 0.f)) { fprintf(stderr, "-%s=%s: expected a number > 0 (an option of -mesh=<directory>)\n", names[a], v); return EXIT_FAILURE; }
-                *fields[a] = x;
-            }
-        if (!meshDir && (value(argc, argv, "meshevery") || value(argc, argv, "meshcell") || value(argc, argv, "meshradius") || value(argc, argv, "iso"))) {
-            fprintf(stderr, "-meshevery / -meshcell / -meshradius / -iso: expected -mesh=<directory> next to them\n");
-            return EXIT_FAILURE;
-        }
-    }
-    int addAt = -1, addCount = 0;
-    const char* addArg = value(argc, argv, "add");
-    if (addArg && (sscanf(addArg, "%d,%d", &addAt, &addCount) != 2 || addAt < 0 || addCount < 1)) {
-        fprintf(stderr, "-add=%s: expected <update>,<count>\n", addArg);
-        return EXIT_FAILURE;
-    }
-    if (gpus > 1 || (gpus == 1 && flag(argc, argv, "slab"))) {     // (-gpus=1 -slab: the same machinery with one rank -- fork, RCCL communicator of one)
-        if (emitArg || drainArg || addArg) {
-            fprintf(stderr, "-emit / -drain / -add are not supported with -gpus=%d%s: sph_emit and sph_remove work on a whole-domain context "
-                            "(the slab step sizes its messages from the previous step's counts); run them on one device\n",
-                    gpus, gpus == 1 ? " -slab" : "");
-            return EXIT_FAILURE;
-        }
-        if (surfaceOn) {
-            fprintf(stderr, "-surface is not supported with -gpus=%d%s: sph_render_surface works on a whole-domain context (the ranks would "
-                            "have to composite their images); run it on one device\n", gpus, gpus == 1 ? " -slab" : "");
-            return EXIT_FAILURE;
-        }
-        if (meshDir) {
-            fprintf(stderr, "-mesh is not supported with -gpus=%d%s: sph_mesh_extract works on a whole-domain context (the ranks would have to "
-                            "share a lattice seam); run it on one device\n", gpus, gpus == 1 ? " -slab" : "");
-            return EXIT_FAILURE;
-        }
-        if (framesDir) {
-            fprintf(stderr, "-frames is not supported with -gpus=%d%s: sph_render works on a whole-domain context (the ranks would have to "
-                            "composite their images); run it on one device\n", gpus, gpus == 1 ? " -slab" : "");
-            return EXIT_FAILURE;
-        }
-        if (colliderArg) {
-            fprintf(stderr, "-collider is not supported with -gpus=%d%s: run it on one device, or set the sphere on every rank "
-                            "through the library (gpufluidsimulator_amd.slab.NativeSlabSimulation(colliders=...))\n",
-                    gpus, gpus == 1 ? " -slab" : "");
-            return EXIT_FAILURE;
-        }
-        if (!obstacles.empty()) {
-            fprintf(stderr, "-obstacle is not supported with -gpus=%d%s: sph_obstacle_build works on a whole-domain context (the slab step "
-                            "makes several force launches per step); run it on one device\n", gpus, gpus == 1 ? " -slab" : "");
-            return EXIT_FAILURE;
-        }
-        if (obstacleMesh) {
-            fprintf(stderr, "-obstaclemesh is not supported with -gpus=%d%s: sph_obstacle_build_obj works on a whole-domain context; run it "
-                            "on one device\n", gpus, gpus == 1 ? " -slab" : "");
-            return EXIT_FAILURE;
-        }
-        if (ic != ParticleSystem::CONFIG_GRID || load || value(argc, argv, "sphere") || value(argc, argv, "save") || value(argc, argv, "log") || dump) {
-            fprintf(stderr, "-gpus=%d runs the dam-break lattice (-ic=grid) and takes -n -box -grid -i -steps -lattice -out -device -onegpu -nowarmup\n", gpus);
-            return EXIT_FAILURE;
-        }
-        SlabJob j{};
-        uint32_t s = (uint32_t)std::floor(std::cbrt((double)numParticles));
-        while ((uint64_t)s * s * s < numParticles) s++;                     // the lattice of reset(CONFIG_GRID)
-        j.lattice[0] = j.lattice[1] = j.lattice[2] = s;
-        j.particles = numParticles;
-        if (const char* v = value(argc, argv, "lattice")) {
-            if (sscanf(v, "%u,%u,%u", &j.lattice[0], &j.lattice[1], &j.lattice[2]) != 3) { fprintf(stderr, "-lattice=nx,ny,nz\n"); return EXIT_FAILURE; }
-            j.particles = (uint64_t)j.lattice[0] * j.lattice[1] * j.lattice[2];
-        }
-        j.box = box;
-        j.grid = gridDim ? gridDim : sph_grid_dim_for_edge(box, 0.1f);
-        j.iterations = iterations; j.substeps = substeps; j.warmup = !flag(argc, argv, "nowarmup"); j.dt = timestep;
-        j.out = value(argc, argv, "out");
-        j.protocol = value(argc, argv, "protocol") ? atoi(value(argc, argv, "protocol")) : 3;
-        if (j.protocol != 1 && j.protocol != 3) { fprintf(stderr, "-protocol=%d: 3 (three message groups per step) or 1 (one)\n", j.protocol); return EXIT_FAILURE; }
-        return run_slabs(j, gpus, flag(argc, argv, "onegpu"), device);
-    }
-    int is950 = 0;
-    if (sph_device_count(&is950) <= 0 || !is950) {
-        fprintf(stderr, "No gfx950 (MI355X) device found, exiting\n");   // cudaInit, particleSystem.cu:432-435
-        return EXIT_FAILURE;
-    }
-    if (sph_select_device(device) < 0) {                  // cudaInit -> findCudaDevice -> cudaSetDevice
-        fprintf(stderr, "-device=%d: %s\n", device, sph_last_error());
-        return EXIT_FAILURE;
-    }
-    uint capacity = numParticles;          // -emit needs room to grow: -capacity=M, default twice -n
-    if (emitArg || addArg) capacity = numParticles < 0x7FFFFFFFu / 2u ? 2u * numParticles : numParticles;
-    if (const char* v = value(argc, argv, "capacity")) capacity = (uint)strtoul(v, nullptr, 10);
-    ParticleSystem* psystem = new ParticleSystem(numParticles, make_float3(box, box, box), ParticleSystem::HIP_PARALLEL,
-                                                 uint3{gridDim, gridDim, gridDim}, capacity);
-    psystem->reset(ic);                                   // initParticleSystem, particles.cpp:119-132
-    if (const char* v = load) {
-        psystem->loadState(v);
-        numParticles = (uint)psystem->getNumParticles();  // the snapshot decides how many particles there are
-    }
-    psystem->setIterations(substeps);
-    if (colliderArg) {
-        psystem->setColliderPos(make_float3(col[0], col[1], col[2]));
-        psystem->setColliderRadius(col[3]);
-        psystem->setColliderVelocity(make_float3(col[4], col[5], col[6]));
-        psystem->enableCollider(true);
-        if (colliderMassArg) {
-            sph_params rp;
-            sph_get_params(psystem->context(), &rp);
+    ps->setIterations(r.substeps);
+    if (const auto& c = o.collider; c.on) {
+        ps->setColliderPos(make_float3(c.center[0], c.center[1], c.center[2]));
+        ps->setColliderRadius(c.radius);
+        ps->setColliderVelocity(make_float3(c.velocity[0], c.velocity[1], c.velocity[2]));
+        ps->enableCollider(true);
+        if (c.has_mass) {
+            sph_params rp; sph_get_params(ps->context(), &rp);
             const float grav[3] = {0.f, rp.gravity_y, 0.f};
-            psystem->setColliderMass(cm[0], cmFields == 4 ? cm + 1 : grav);
-            if (cm[0] == 0.f) psystem->senseColliderImpulse(true);       // a kinematic obstacle: the impulse is all that is asked for
+            ps->setColliderMass(c.mass, c.has_accel ? c.accel : grav);
+            if (c.mass == 0.f) ps->senseColliderImpulse(true);       // a kinematic obstacle: the impulse is all that is asked for
         }
     }
-    if (!obstacles.empty()) {
-        psystem->setObstacles(obstacles.data(), (uint)obstacles.size(), obstacleCell);
-        if (obstacleVelArg) psystem->setObstacleMotion(nullptr, obstacleVel);
-    }
-    if (obstacleMesh) {
-        psystem->setObstacleMeshOBJ(obstacleMesh, obstacleCell, obstacleBand, obstacleInvert);
-        if (obstacleVelArg) psystem->setObstacleMotion(nullptr, obstacleVel);
+    const auto& ob = o.obstacle;
+    if (!ob.shapes.empty()) ps->setObstacles(ob.shapes.data(), (uint)ob.shapes.size(), ob.cell);
+    if (ob.mesh) ps->setObstacleMeshOBJ(ob.mesh, ob.cell, ob.band, ob.invert);
+    if (ob.has_velocity) ps->setObstacleMotion(nullptr, ob.velocity);
+    if (ob.mesh) {
         uint64_t ms[4];
-        psystem->getObstacleMeshStats(ms);
+        ps->getObstacleMeshStats(ms);
         printf("obstacle mesh: %llu triangles used, %llu skipped, %llu lost crossings, %llu odd columns\n", (unsigned long long)ms[0],
                (unsigned long long)ms[1], (unsigned long long)ms[2], (unsigned long long)ms[3]);
     }
-    if (const char* v = value(argc, argv, "log")) {
-        const char* fq = value(argc, argv, "logfreq");
-        // -logstyle=oscar: the line form of the reference's committed logs (benchmarks/oscar/, what its benchmark.py reads);
-        // default: what its current source writes (particleSystem.cpp:703-714)
-        const char* st = value(argc, argv, "logstyle");
-        if (st && strcmp(st, "oscar") && strcmp(st, "frames")) { fprintf(stderr, "-logstyle=%s: expected oscar or frames\n", st); return EXIT_FAILURE; }
-        psystem->setBenchmarkLog(v, fq ? atof(fq) : 2000.0, st && !strcmp(st, "oscar") ? ParticleSystem::LOG_OSCAR : ParticleSystem::LOG_FRAMES);
+    if (r.log) ps->setBenchmarkLog(r.log, r.logfreq, r.logstyle);
+    if (const auto& f = o.frames; f.dir) {
+        if (mkdir(f.dir, 0755) != 0 && errno != EEXIST) return fail("-frames=%s: cannot create the directory\n", f.dir);
+        ps->setCamera(f.width, f.height, f.eye, f.target, f.fovy);
+        ps->setRenderColor(f.color_mode, f.color_lo, f.color_hi);
+        ps->setRenderSurface(o.surface.on, &o.surface.style);
     }
-    if (framesDir) {
-        if (mkdir(framesDir, 0755) != 0 && errno != EEXIST) { fprintf(stderr, "-frames=%s: cannot create the directory\n", framesDir); return EXIT_FAILURE; }
-        psystem->setCamera(frameW, frameH, camv, camv + 3, camv[6]);
-        psystem->setRenderColor(colorMode, colorLo, colorHi);
-        psystem->setRenderSurface(surfaceOn, &surfaceStyle);
+    if (const auto& m = o.mesh; m.dir) {
+        uint32_t md[3]; float mo[3];
+        if (sph_mesh_lattice(ps->context(), &m.params, md, mo) < 0) return fail("-mesh: %s\n", sph_last_error());
+        if (mkdir(m.dir, 0755) != 0 && errno != EEXIST) return fail("-mesh=%s: cannot create the directory\n", m.dir);
+        ps->setMeshParams(&m.params);
     }
-    if (meshDir) {
-        uint32_t md[3];
-        float mo[3];
-        if (sph_mesh_lattice(psystem->context(), &meshParams, md, mo) < 0) { fprintf(stderr, "-mesh: %s\n", sph_last_error()); return EXIT_FAILURE; }
-        if (mkdir(meshDir, 0755) != 0 && errno != EEXIST) { fprintf(stderr, "-mesh=%s: cannot create the directory\n", meshDir); return EXIT_FAILURE; }
-        psystem->setMeshParams(&meshParams);
-    }
-    uint3 g = psystem->getGridSize();
-    printf("Run %u particles simulation for %d iterations... (grid %ux%ux%u, box %g)\n\n", numParticles, iterations, g.x, g.y, g.z, box);
-    if (!flag(argc, argv, "nowarmup")) psystem->update(timestep, 0);   // warm-up step, not timed
-    sph_sync(psystem->context());
-    auto t0 = std::chrono::steady_clock::now();
-    // -sphere=<k>[,<r>]: before update k, drop a ball of (2r+1)^3 lattice points (radius r spacings) at the top of
-    // the box the way the GUI's key '4' does (addSphere, particles.cpp:306-318; centred here instead of frand())
-    int sphereAt = -1, ballr = 10;
-    if (const char* v = value(argc, argv, "sphere")) {
-        sphereAt = atoi(v);
-        if (const char* c = strchr(v, ',')) ballr = atoi(c + 1);
-    }
-    // the faucet's ball: as many lattice points as addSphere's loops accept; its place is the sphere around them
-    uint ballPoints = 0, emittedTotal = 0;
-    const uint startParticles = (uint)psystem->getNumParticles();
-    bool fullNoted = false;
-    if (emitArg) {
-        const float sp = psystem->getParticleRadius() * 2.0f;
-        for (int z = -emitR; z <= emitR; z++)
-            for (int y = -emitR; y <= emitR; y++)
-                for (int x = -emitR; x <= emitR; x++) {
+    const float sp = ps->getParticleRadius() * 2.0f;      // the faucet's ball: as many lattice points as addSphere's loops accept
+    if (const int er = o.emit.radius; o.emit.on)
+        for (int z = -er; z <= er; z++)
+            for (int y = -er; y <= er; y++)
+                for (int x = -er; x <= er; x++) {
                     const float dx = x * sp, dy = y * sp, dz = z * sp;
-                    if (sqrtf(dx * dx + dy * dy + dz * dz) <= psystem->getParticleRadius() * 2.0f * emitR) ballPoints++;
+                    if (sqrtf(dx * dx + dy * dy + dz * dz) <= ps->getParticleRadius() * 2.0f * er) run.ball_points++;
                 }
+    return true;
+}
+
+// before update i: the faucet, the kill volume, -add's particles, -sphere's ball
+void before_update(const Options& o, Run& run, int i) {
+    ParticleSystem* ps = run.ps;
+    const float pr = ps->getParticleRadius();
+    if (const auto& e = o.emit; e.on && i % e.every == 0) {       // unless a particle is still in the ball's place, or the capacity is used up
+        sph_region nozzle = {SPH_REGION_SPHERE, {e.center[0], e.center[1], e.center[2]}, {0.f, 0.f, 0.f}, pr + (pr * 2.0f) * e.radius};
+        const bool room = (uint64_t)ps->getNumParticles() + run.ball_points <= (uint64_t)ps->getCapacity() &&
+                          (uint64_t)run.start + run.emitted + run.ball_points <= (uint64_t)ps->getCapacity();
+        if (!room && !run.full_noted) { fprintf(stderr, "note: -emit stops at update %d: the capacity %d is used up (-capacity=)\n", i, ps->getCapacity()); run.full_noted = true; }
+        if (room && ps->countParticles(&nozzle, 1) == 0) run.emitted += (uint)ps->emitSphere(e.center, e.velocity, e.radius, pr * 2.0f);
     }
-    for (int i = 0; i < iterations; ++i) {
-        if (emitArg && i % emitEvery == 0) {
-            const float pr = psystem->getParticleRadius();
-            sph_region nozzle = {SPH_REGION_SPHERE, {em[0], em[1], em[2]}, {0.f, 0.f, 0.f}, pr + (pr * 2.0f) * emitR};
-            const bool room = (uint64_t)psystem->getNumParticles() + ballPoints <= (uint64_t)psystem->getCapacity() &&
-                              (uint64_t)startParticles + emittedTotal + ballPoints <= (uint64_t)psystem->getCapacity();
-            if (!room && !fullNoted) { fprintf(stderr, "note: -emit stops at update %d: the capacity %d is used up (-capacity=)\n", i, psystem->getCapacity()); fullNoted = true; }
-            if (room && psystem->countParticles(&nozzle, 1) == 0) emittedTotal += (uint)psystem->emitSphere(em, em + 4, emitR, pr * 2.0f);
-        }
-        if (drainArg && i % drainEvery == 0) {
-            sph_region kill = {SPH_REGION_BOX, {dr[0], dr[1], dr[2]}, {dr[3], dr[4], dr[5]}, 0.f};
-            psystem->removeParticles(&kill, 1);
-        }
-        if (i == addAt) {
-            std::vector<float> xyz((size_t)addCount * 3), xyzw((size_t)addCount * 4, 1.0f);
-            const float dims[3] = {box, box, box};
-            sph_ic_random_box((uint64_t)addCount, dims, 0.f, 2024u, 1.0f, xyz.data(), nullptr);
-            for (int k = 0; k < addCount; k++) for (int a = 0; a < 3; a++) xyzw[4 * (size_t)k + a] = xyz[3 * (size_t)k + a];
-            emittedTotal += (uint)addCount;
-            psystem->addParticles(xyzw.data(), nullptr, addCount);
-        }
-        if (i == sphereAt) {
-            const float pr = psystem->getParticleRadius(), tr = pr + (pr * 2.0f) * ballr;
-            float pos[4] = {0.0f, psystem->getBoxMax().y - tr, 0.0f, 0.0f}, vel[4] = {0.f, 0.f, 0.f, 0.f};
-            psystem->addSphere(0, pos, vel, ballr, pr * 2.0f);
-        }
-        psystem->update(timestep, (float)i);
-        if (framesDir && i % frameEvery == 0) {
-            const std::string path = std::string(framesDir) + "/frame_" + std::to_string(1000000 + i % 1000000).substr(1) + ".ppm";
-            psystem->renderFrame();
-            psystem->writeFrame(path.c_str());
-        }
-        if (meshDir && i % meshEvery == 0) {
-            const std::string path = std::string(meshDir) + "/mesh_" + std::to_string(100000 + i % 100000).substr(1) + ".obj";
-            psystem->writeMeshOBJ(path.c_str());
-        }
+    if (const auto& d = o.drain; d.on && i % d.every == 0) {
+        sph_region kill = {SPH_REGION_BOX, {d.lo[0], d.lo[1], d.lo[2]}, {d.hi[0], d.hi[1], d.hi[2]}, 0.f};
+        ps->removeParticles(&kill, 1);
     }
-    sph_sync(psystem->context());
-    auto t1 = std::chrono::steady_clock::now();
-    const double secs = std::chrono::duration<double>(t1 - t0).count();
-    const double avg = secs / (iterations > 0 ? iterations : 1);
-    // the reference's line, particles.cpp:191-192
-    if (emitArg || drainArg || addArg) printf("emitted %u particles, %d left of %u + %u\n", emittedTotal, psystem->getNumParticles(), startParticles, emittedTotal);
-    printf("particles, Throughput = %.4f KParticles/s, Time = %.5f s, Size = %u particles, NumDevsUsed = %u, Workgroup = %u\n",
-           (1.0e-3 * numParticles) / avg, avg, numParticles, 1, 0);
-    printf("{\"particle_steps_per_s\": %.1f, \"particles\": %u, \"iterations\": %d, \"steps_per_update\": %d, \"seconds\": %.6f}\n",
-           (double)numParticles * iterations * substeps / secs, numParticles, iterations, substeps, secs);
-    if (colliderMassArg) {       // floats with 9, doubles with 17 digits: they read back exactly
-        double J[3];
-        psystem->getColliderImpulse(J);
-        const float3 cc = psystem->getColliderPos(), cu = psystem->getColliderVelocity();
+    if (i == o.add.at) {                 // at rest, at the points of sph_ic_random_box(seed 2024)
+        const int count = o.add.count;
+        std::vector<float> xyz((size_t)count * 3), xyzw((size_t)count * 4, 1.0f);
+        const float dims[3] = {o.run.box, o.run.box, o.run.box};
+        sph_ic_random_box((uint64_t)count, dims, 0.f, 2024u, 1.0f, xyz.data(), nullptr);
+        for (int k = 0; k < count; k++) for (int a = 0; a < 3; a++) xyzw[4 * (size_t)k + a] = xyz[3 * (size_t)k + a];
+        run.emitted += (uint)count;
+        ps->addParticles(xyzw.data(), nullptr, count);
+    }
+    if (i == o.sphere.at) {              // the ball the GUI's key '4' drops (addSphere, particles.cpp:306-318), centred at the top instead of frand()
+        const float tr = pr + (pr * 2.0f) * o.sphere.radius;
+        float pos[4] = {0.0f, ps->getBoxMax().y - tr, 0.0f, 0.0f}, vel[4] = {0.f, 0.f, 0.f, 0.f};
+        ps->addSphere(0, pos, vel, o.sphere.radius, pr * 2.0f);
+    }
+}
+
+// after update i: its picture and its mesh, named by the 0-based number of the update
+void after_update(const Options& o, Run& run, int i) {
+    if (o.frames.dir && i % o.frames.every == 0) {
+        const std::string path = std::string(o.frames.dir) + "/frame_" + std::to_string(1000000 + i % 1000000).substr(1) + ".ppm";
+        run.ps->renderFrame();
+        run.ps->writeFrame(path.c_str());
+    }
+    if (o.mesh.dir && i % o.mesh.every == 0) {
+        const std::string path = std::string(o.mesh.dir) + "/mesh_" + std::to_string(100000 + i % 100000).substr(1) + ".obj";
+        run.ps->writeMeshOBJ(path.c_str());
+    }
+}
+
+bool report(const Options& o, Run& run, double secs) {
+    ParticleSystem* ps = run.ps;
+    if (o.grows()) printf("emitted %u particles, %d left of %u + %u\n", run.emitted, ps->getNumParticles(), run.start, run.emitted);
+    print_result(run.particles, o.run.iterations, o.run.substeps, secs, 1, "");
+    if (o.collider.has_mass) {       // floats with 9, doubles with 17 digits: they read back exactly
+        double J[3]; ps->getColliderImpulse(J);
+        const float3 cc = ps->getColliderPos(), cu = ps->getColliderVelocity();
         printf("collider: centre %.9g %.9g %.9g velocity %.9g %.9g %.9g impulse %.17g %.17g %.17g\n", cc.x, cc.y, cc.z, cu.x, cu.y, cu.z,
                J[0], J[1], J[2]);
     }
-    if (meshDir) {       // the mesh of the final state through ParticleSystem::extractMesh: its size and an FNV-1a hash of its bytes
-        std::vector<float> mp, mn;
-        std::vector<uint32_t> mt;
-        psystem->extractMesh(mp, mn, mt);
+    if (o.mesh.dir) {       // the mesh of the final state through ParticleSystem::extractMesh: its size and an FNV-1a hash of its bytes
+        std::vector<float> mp, mn; std::vector<uint32_t> mt;
+        ps->extractMesh(mp, mn, mt);
         unsigned long long hsh = 1469598103934665603ull;
         auto mix = [&hsh](const void* data, size_t bytes) {
             const unsigned char* b = (const unsigned char*)data;
@@ -892,16 +859,47 @@ int main(int argc, char** argv) {
         mix(mp.data(), mp.size() * 4); mix(mn.data(), mn.size() * 4); mix(mt.data(), mt.size() * 4);
         printf("mesh: %zu vertices, %zu triangles, fnv1a64 %016llx\n", mp.size() / 3, mt.size() / 3, hsh);
     }
-    if (dump > 0) psystem->dumpParticles(0, (uint)dump);
-    if (const char* v = value(argc, argv, "out")) {      // xyzw per creation index, then vxyz0, raw fp32
-        FILE* f = fopen(v, "wb");
-        if (!f) { fprintf(stderr, "cannot open %s\n", v); return EXIT_FAILURE; }
-        const size_t rows = (emitArg || drainArg || addArg) ? (size_t)psystem->getCapacity() : (size_t)numParticles;     // by creation index
-        fwrite(psystem->getArray(ParticleSystem::POSITION), sizeof(float) * 4, rows, f);
-        fwrite(psystem->getArray(ParticleSystem::VELOCITY), sizeof(float) * 4, rows, f);
+    if (o.run.dump > 0) ps->dumpParticles(0, (uint)o.run.dump);
+    if (o.run.out) {      // xyzw per creation index, then vxyz0, raw fp32
+        FILE* f = fopen(o.run.out, "wb");
+        if (!f) return fail("cannot open %s\n", o.run.out);
+        const size_t rows = o.grows() ? (size_t)ps->getCapacity() : (size_t)run.particles;
+        fwrite(ps->getArray(ParticleSystem::POSITION), sizeof(float) * 4, rows, f);
+        fwrite(ps->getArray(ParticleSystem::VELOCITY), sizeof(float) * 4, rows, f);
         fclose(f);
     }
-    if (const char* v = value(argc, argv, "save")) psystem->saveState(v);
-    delete psystem;
+    if (o.run.save) ps->saveState(o.run.save);
+    return true;
+}
+
+int run_one_device(const Options& o) {
+    Run run;
+    if (!set_up(o, run)) return EXIT_FAILURE;
+    ParticleSystem* ps = run.ps;
+    const uint3 g = ps->getGridSize();
+    printf("Run %u particles simulation for %d iterations... (grid %ux%ux%u, box %g)\n\n", run.particles, o.run.iterations, g.x, g.y, g.z, o.run.box);
+    if (o.run.warmup) ps->update(kTimestep, 0);           // warm-up step, not timed
+    sph_sync(ps->context());
+    const auto t0 = std::chrono::steady_clock::now();
+    run.start = (uint)ps->getNumParticles();
+    for (int i = 0; i < o.run.iterations; ++i) {
+        before_update(o, run, i);
+        ps->update(kTimestep, (float)i);
+        after_update(o, run, i);
+    }
+    sph_sync(ps->context());
+    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (!report(o, run, secs)) return EXIT_FAILURE;
+    delete ps;
     return 0;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    Options o;
+    if (!parse_options(argc, argv, o)) return EXIT_FAILURE;
+    if (o.run.help) { print_help(); return 0; }
+    if (o.slabs.on) return run_slabs(slab_job(o), o.slabs.gpus, o.slabs.onegpu, o.run.device);
+    return run_one_device(o);
 }
