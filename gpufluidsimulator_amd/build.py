@@ -57,6 +57,11 @@ def build(force: bool = False, verbose: bool = False) -> str:
     if os.path.exists(main_src) and (force or _stale(exe, [main_src, LIB] + headers)):
         run([HIPCC, "-O2", "-std=c++17", "-x", "c++", main_src, "-x", "none", "-o", exe, "-L" + HERE, "-lsph_hip",
              "-Wl,-rpath,$ORIGIN"])
+    # the host class's posed obstacle and load sensor, for the tests (the driver above has no option for them yet)
+    exe, main_src = os.path.join(HERE, "sph_pose_probe"), os.path.join(CSRC, "sph_pose_probe.cpp")
+    if os.path.exists(main_src) and (force or _stale(exe, [main_src, LIB] + headers)):
+        run([HIPCC, "-O2", "-std=c++17", "-x", "c++", main_src, "-x", "none", "-o", exe, "-L" + HERE, "-lsph_hip",
+             "-Wl,-rpath,$ORIGIN"])
     return LIB
 
 

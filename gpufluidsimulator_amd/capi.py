@@ -118,6 +118,11 @@ class ObstacleGrid(C.Structure):
     _fields_ = [("dims", C.c_uint32 * 3), ("origin", C.c_float * 3), ("spacing", C.c_float)]
 
 
+class ObstaclePose(C.Structure):
+    """`sph_obstacle_pose` of include/sph_hip.h: a pivot of the body frame, the quaternion (w, x, y, z) body -> world, omega in world axes."""
+    _fields_ = [("pivot", C.c_float * 3), ("quat", C.c_float * 4), ("omega", C.c_float * 3)]
+
+
 OBSTACLE_MESH_MAX_BAND = 16        # SPH_OBSTACLE_MESH_MAX_BAND
 OBSTACLE_MESH_DEFAULT_BAND = 3     # SPH_OBSTACLE_MESH_DEFAULT_BAND
 
@@ -219,6 +224,11 @@ SIGNATURES = {
     "sph_obstacle_get": (C.c_int, [_P, C.POINTER(ObstacleGrid), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "sph_obstacle_read": (C.c_int, [_P, _P]),
     "sph_obstacle_sample": (C.c_int, [_P, _U32, _P, _P, _P, _P]),
+    "sph_obstacle_set_pose": (C.c_int, [_P, C.POINTER(ObstaclePose)]),
+    "sph_obstacle_get_pose": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_float),
+                                        C.POINTER(C.c_float)]),
+    "sph_obstacle_set_sensor": (C.c_int, [_P, C.c_int]),
+    "sph_obstacle_get_load": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_uint64)]),
     "sph_obstacle_build_mesh": (C.c_int, [_P, C.POINTER(ObstacleMeshParams), C.POINTER(C.c_float), C.POINTER(C.c_float), _U32, _P,
                                           _U32, _P]),
     "sph_obstacle_build_mesh_dev": (C.c_int, [_P, C.POINTER(ObstacleMeshParams), C.POINTER(C.c_float), C.POINTER(C.c_float), _U32,
@@ -686,6 +696,38 @@ class Context:
         phi, nrm, inside = np.empty(n, np.float32), np.empty((n, 3), np.float32), np.empty(n, np.uint8)
         _check(self.L.sph_obstacle_sample(self.h, n, pts.ctypes.data, phi.ctypes.data, nrm.ctypes.data, inside.ctypes.data))
         return phi, nrm, inside.astype(bool)
+
+    def set_obstacle_pose(self, pivot=None, quat=None, omega=(0.0, 0.0, 0.0)):
+        """The rigid pose of the obstacle: `pivot` a point of the grid's own (body) frame, `quat` = (w, x, y, z) body -> world
+        about it (normalised by the library), `omega` the angular velocity in world axes; the pose advances once per step.
+        set_obstacle_pose(None) drops the pose: translation only."""
+        if pivot is None:
+            _check(self.L.sph_obstacle_set_pose(self.h, None))
+            return
+        p = ObstaclePose(_f3(pivot), (C.c_float * 4)(*[float(v) for v in quat]), _f3(omega))
+        _check(self.L.sph_obstacle_set_pose(self.h, C.byref(p)))
+
+    def obstacle_pose(self):
+        """None without a pose, else {"pivot" (3,) float32, "quat" (4,) float64 (unit, advanced), "omega" (3,) float32,
+        "rot" (3, 3) float32 body -> world as the next launch takes it}."""
+        posed, piv, q, om, rot = C.c_int(), (C.c_float * 3)(), (C.c_double * 4)(), (C.c_float * 3)(), (C.c_float * 9)()
+        _check(self.L.sph_obstacle_get_pose(self.h, C.byref(posed), piv, q, om, rot))
+        if not posed.value:
+            return None
+        return {"pivot": np.array(list(piv), np.float32), "quat": np.array(list(q), np.float64),
+                "omega": np.array(list(om), np.float32), "rot": np.array(list(rot), np.float32).reshape(3, 3)}
+
+    def set_obstacle_sensor(self, on=True):
+        """Switch the load sensor: while on, every integrate also sums what the obstacle took from the fluid (obstacle_load)."""
+        _check(self.L.sph_obstacle_set_sensor(self.h, int(bool(on))))
+
+    def obstacle_load(self):
+        """{"J" (3,), "L" (3,) float64, "about" (3,) float32, "steps"}: the momentum and the angular momentum about `about` the
+        obstacle took in the LAST integrate (divide by dt for force and torque).  Synchronises."""
+        J, L, about, steps = (C.c_double * 3)(), (C.c_double * 3)(), (C.c_float * 3)(), C.c_uint64()
+        _check(self.L.sph_obstacle_get_load(self.h, J, L, about, C.byref(steps)))
+        return {"J": np.array(list(J), np.float64), "L": np.array(list(L), np.float64),
+                "about": np.array(list(about), np.float32), "steps": int(steps.value)}
 
     # -- obstacles from a triangle mesh (include/sph_hip.h: sph_obstacle_build_mesh and the calls next to it) -----------------------
     def build_obstacle_mesh(self, vertices, triangles, spacing=0.0, band=0, invert=False, bounds=None):

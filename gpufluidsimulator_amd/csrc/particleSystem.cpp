@@ -520,6 +520,19 @@ void ParticleSystem::setObstacleMeshOBJ(const char* path, float spacing, uint ba
 
 void ParticleSystem::getObstacleMeshStats(uint64_t out[4]) { SPH_CHECK(sph_obstacle_mesh_stats(m_ctx, out)); }
 
+void ParticleSystem::setObstaclePose(const float pivot[3], const float quat[4], const float* omega) {
+    sph_obstacle_pose p = {};
+    for (int k = 0; k < 3; k++) { p.pivot[k] = pivot[k]; p.omega[k] = omega ? omega[k] : 0.f; }
+    for (int k = 0; k < 4; k++) p.quat[k] = quat[k];
+    SPH_CHECK(sph_obstacle_set_pose(m_ctx, &p));
+}
+
+void ParticleSystem::clearObstaclePose() { SPH_CHECK(sph_obstacle_set_pose(m_ctx, nullptr)); }
+
+void ParticleSystem::senseObstacleLoad(bool on) { SPH_CHECK(sph_obstacle_set_sensor(m_ctx, on ? 1 : 0)); }
+
+void ParticleSystem::getObstacleLoad(double J[3], double L[3]) { SPH_CHECK(sph_obstacle_get_load(m_ctx, J, L, nullptr, nullptr)); }
+
 void ParticleSystem::saveState(const std::string& path) { SPH_CHECK(sph_snapshot_save(m_ctx, path.c_str())); }
 
 void ParticleSystem::loadState(const std::string& path) {

@@ -283,6 +283,18 @@ struct sph_ctx {
     float* ob_phi = nullptr;
     float* ob_brick = nullptr;
     float ob_off[3] = {0.f, 0.f, 0.f}, ob_vel[3] = {0.f, 0.f, 0.f};
+    // the rigid pose (sph_obstacle_set_pose): while `ob_posed`, the grid's coordinates are a body frame turned by the unit
+    // quaternion ob_quat (w, x, y, z; double) about ob_pivot, and ob_omega is the angular velocity in world axes.  It belongs to
+    // the context like the motion and advances where the offset does (advance_obstacle).
+    bool ob_posed = false;
+    float ob_pivot[3] = {0.f, 0.f, 0.f}, ob_omega[3] = {0.f, 0.f, 0.f};
+    double ob_quat[4] = {1.0, 0.0, 0.0, 0.0};
+    // the load sensor (sph_obstacle_set_sensor): while `ob_sense`, every push leaves one row of six float64 sums and one mask
+    // word per wave, and k_obstacle_load adds them once per integrate.  Allocated when the sensor is first switched on.
+    bool ob_sense = false;
+    double* ob_rows = nullptr;          // ceil(cap / 64) rows of 6: J, L
+    uint32_t* ob_wmask = nullptr;       // ceil(cap / 64) words, padded to whole quads plus one
+    double* ob_load = nullptr;          // J[3], L[3], the integrate count (uint64), about[3] (fp32) and a pad word: 72 bytes
     // an obstacle voxelised from a triangle mesh (sph_obstacle_mesh.hip) keeps the scratch of its build -- the work list with the
     // four counters in front, and the parity marks of the columns -- until the next installation, sph_obstacle_clear or
     // sph_destroy; both null for every other obstacle, and sph_obstacle_mesh_stats reads the counters
@@ -477,7 +489,7 @@ int launch_integrate(sph_ctx* c, float dt);
 // posi2 / velr2 and the next keys k0, and, with `mark`, the movers' marks, which the pass keeps right; else posi / velr alone
 inline bool have_obstacle(const sph_ctx* c) { return c->ob_phi != nullptr; }
 int launch_obstacle_push(sph_ctx* c, bool fused, bool mark);
-void advance_obstacle(sph_ctx* c, float dt);
+int advance_obstacle(sph_ctx* c, float dt);   // once per integrate, behind the push: queues the load's sum while sensing, then offset and pose move on
 // the installation helpers of sph_obstacle.hip, for the mesh voxeliser (sph_obstacle_mesh.hip): the context check, the lattice
 // of a build (checks only), the clamp distance D, the exchange of the context's grid (on failure: no obstacle) and the bricks
 int obstacle_ctx(const sph_ctx* c, const char* who);

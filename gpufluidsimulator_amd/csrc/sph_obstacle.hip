@@ -7,7 +7,9 @@
 //   k_obstacle_clamp   one node per lane: the clamp of an uploaded field                                    (sph_obstacle_set_grid)
 //   k_obstacle_bricks  one brick of OBSTACLE_BRICK^3 cells per lane: the minimum over its (OBSTACLE_BRICK + 1)^3 nodes
 //   k_obstacle_sample  one caller point per lane: the sample rule                                           (sph_obstacle_sample)
-//   k_obstacle_push    one owned slot per lane, behind every integrate of a context with an obstacle: the push
+//   k_obstacle_push    one owned slot per lane, behind every integrate of a context with an obstacle: the push; <POSED> for a
+//                      solid that turns (sph_obstacle_set_pose), <SENSE> leaves the waves' sums of what the solid took
+//   k_obstacle_load    one block behind a sensing push: the waves' sums in a fixed order                    (sph_obstacle_get_load)
 //
 // The push is a pass of its own and not a fourth pack of k_force / k_integrate (sph_pairs.hip): the fused kernel sits at the edge
 // of its occupancy, and an eight-node gather in its epilogue would cost it.  Reading the integrate's STORED output is also what
@@ -37,6 +39,17 @@ struct ObstacleArgs {
     float off[3], u[3];
 };
 
+// The rigid pose and the sensor's buffers as the push and the sample take them: by value, and as the LAST kernel argument rather
+// than as fields of ObstacleArgs, so that the arguments of the plain instantiation keep their offsets and its code its text.
+struct ObstaclePose {
+    float rot[9];          // body -> world, row-major
+    float pivot[3];        // a point of the body frame
+    float P[3];            // the same point in the world: pivot + off (an unposed context: off)
+    float omega[3];        // world axes
+    double* rows;          // the sensor: six sums per wave
+    uint32_t* mask;        // ... and whether the wave wrote them
+};
+
 // the shapes of one build: a kernel argument by value, like Spheres (the half-spaces' normals already normalised)
 struct Shapes {
     sph_shape s[SPH_MAX_SHAPES];
@@ -59,6 +72,50 @@ __device__ __forceinline__ bool ob_locate(const ObstacleArgs& A, float x, float 
     i[0] = (uint32_t)i0; i[1] = (uint32_t)i1; i[2] = (uint32_t)i2;
     f[0] = g0 - (float)i0; f[1] = g1 - (float)i1; f[2] = g2 - (float)i2;
     return true;
+}
+
+// the same on a posed context: d = x - P, the body-frame point R^T d + pivot, its cell.  d stays with the caller (omega x d,
+// the torque's arm)
+__device__ __forceinline__ bool ob_locate_posed(const ObstacleArgs& A, const ObstaclePose& X, float x, float y, float z, uint32_t i[3],
+                                                float f[3], float d[3]) {
+#pragma clang fp contract(off)
+    const float d0 = x - X.P[0], d1 = y - X.P[1], d2 = z - X.P[2];
+    d[0] = d0; d[1] = d1; d[2] = d2;
+    const float q0 = ((X.rot[0] * d0 + X.rot[3] * d1) + X.rot[6] * d2) + X.pivot[0];
+    const float q1 = ((X.rot[1] * d0 + X.rot[4] * d1) + X.rot[7] * d2) + X.pivot[1];
+    const float q2 = ((X.rot[2] * d0 + X.rot[5] * d1) + X.rot[8] * d2) + X.pivot[2];
+    const float g0 = (q0 - A.origin[0]) / A.s;
+    const float g1 = (q1 - A.origin[1]) / A.s;
+    const float g2 = (q2 - A.origin[2]) / A.s;
+    if (!(g0 >= 0.f) || !(g0 < A.nm1[0]) || !(g1 >= 0.f) || !(g1 < A.nm1[1]) || !(g2 >= 0.f) || !(g2 < A.nm1[2])) return false;
+    const int i0 = (int)g0, i1 = (int)g1, i2 = (int)g2;
+    i[0] = (uint32_t)i0; i[1] = (uint32_t)i1; i[2] = (uint32_t)i2;
+    f[0] = g0 - (float)i0; f[1] = g1 - (float)i1; f[2] = g2 - (float)i2;
+    return true;
+}
+
+template <bool POSED>
+__device__ __forceinline__ bool ob_locate_at(const ObstacleArgs& A, const ObstaclePose& X, float x, float y, float z, uint32_t i[3],
+                                             float f[3], float d[3]) {
+    if constexpr (POSED) return ob_locate_posed(A, X, x, y, z, i, f, d);
+    else return ob_locate(A, x, y, z, i, f);
+}
+
+// the body normal of a posed context in world axes (not renormalised)
+__device__ __forceinline__ void ob_world_normal(const ObstaclePose& X, float& nx, float& ny, float& nz) {
+#pragma clang fp contract(off)
+    const float b0 = nx, b1 = ny, b2 = nz;
+    nx = (X.rot[0] * b0 + X.rot[1] * b1) + X.rot[2] * b2;
+    ny = (X.rot[3] * b0 + X.rot[4] * b1) + X.rot[5] * b2;
+    nz = (X.rot[6] * b0 + X.rot[7] * b1) + X.rot[8] * b2;
+}
+
+// lane l's value of a float64, as lane_value of sph_pairs.hip reads a float: two 32-bit readlanes
+__device__ __forceinline__ double lane_value_f64(double v, uint32_t l) {
+    const uint64_t b = __builtin_bit_cast(uint64_t, v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, (int)l);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), (int)l);
+    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
 }
 
 // phi and the unit normal in a cell: the eight-node gather (i[k] <= n[k] - 2, so every node is inside the array)
@@ -96,13 +153,21 @@ __device__ __forceinline__ void ob_sample_cell(const ObstacleArgs& A, const uint
 // Fused (keys_out != null): a particle with `hit` also gets the next step's key, and, where the launch marked the movers, the
 // wave's mask word is put right -- bit = (key != keyS[slot]) for the lanes that hit -- and the tile's count takes the difference
 // of the popcounts with one integer atomic add (force_finish scans the counts afterwards).
+// POSED (sph_obstacle_set_pose): the sample goes through the body frame and the solid's velocity at the particle is
+// u + omega x d; the brick guard is applied to the body-frame cell and holds as it is.  SENSE (sph_obstacle_set_sensor): a lane
+// that takes `wn < 0` also forms t = -(mass * (k * n)) and d x t and adds them, iteration by iteration, to six float64 sums of
+// its own; the wave then adds its kicked lanes' sums in ascending lane order -- two scalar-indexed 32-bit reads per value, as
+// push_out_of_spheres(..., SpheresTracked) reads its floats, no LDS, no atomics -- and lane 0 stores the row.  EVERY wave that
+// owns a slot stores its mask word, 0 where it leaves at the guard's ballot, so k_obstacle_load never reads a row of an earlier
+// launch.  <false, false> is the kernel without either, operation for operation.
+template <bool POSED, bool SENSE>
 __global__ __launch_bounds__(OBSTACLE_THREADS) void k_obstacle_push(float4* __restrict__ posi, float4* __restrict__ velr,
                                                                     float4* __restrict__ pos_by_index,
                                                                     uint32_t* __restrict__ keys_out,
                                                                     const uint32_t* __restrict__ keyS,
                                                                     uint64_t* __restrict__ mm_mask,
                                                                     uint32_t* __restrict__ mm_tile_cnt, uint32_t lo, uint32_t n,
-                                                                    ObstacleArgs A, GridDesc g, Phys ph) {
+                                                                    ObstacleArgs A, GridDesc g, Phys ph, ObstaclePose X) {
 #pragma clang fp contract(off)
     const uint32_t rel = blockIdx.x * OBSTACLE_THREADS + threadIdx.x;
     const bool active = rel < n;
@@ -111,31 +176,73 @@ __global__ __launch_bounds__(OBSTACLE_THREADS) void k_obstacle_push(float4* __re
     const float eps = ph.wall_eps;
     const float guard = eps + 0.25f * A.s;
     uint32_t ci[3];
-    float cf[3];
+    float cf[3], d[3];
     bool may = false;
-    if (active && ob_locate(A, pi.x, pi.y, pi.z, ci, cf)) {
+    if (active && ob_locate_at<POSED>(A, X, pi.x, pi.y, pi.z, ci, cf, d)) {
         const uint32_t b = ((ci[2] >> OBSTACLE_BRICK_SH) * A.nb[1] + (ci[1] >> OBSTACLE_BRICK_SH)) * A.nb[0] + (ci[0] >> OBSTACLE_BRICK_SH);
         may = A.brick[b] < guard;
     }
-    if (__ballot(may) == 0ull) return;                                   // wave-uniform: nearly every wave
+    [[maybe_unused]] const bool row_owner = active && (threadIdx.x & 63u) == 0u;     // (lane 0 of a wave that owns a slot)
+    if (__ballot(may) == 0ull) {                                         // wave-uniform: nearly every wave
+        if constexpr (SENSE) { if (row_owner) X.mask[rel >> 6] = 0u; }
+        return;
+    }
     bool hit = false;
     float4 vi = make_float4(0.f, 0.f, 0.f, 0.f);
+    [[maybe_unused]] double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    [[maybe_unused]] bool kicked = false;
     if (may) {
         vi = velr[slot];
         for (int it = 0; it < SPH_OBSTACLE_PUSH_ITERATIONS; it++) {
-            if (it > 0 && !ob_locate(A, pi.x, pi.y, pi.z, ci, cf)) break;
+            if (it > 0 && !ob_locate_at<POSED>(A, X, pi.x, pi.y, pi.z, ci, cf, d)) break;
             float phi, nx, ny, nz;
             ob_sample_cell(A, ci, cf, phi, nx, ny, nz);
             if (!(phi < eps)) break;
-            const float wn = ((vi.x - A.u[0]) * nx + (vi.y - A.u[1]) * ny) + (vi.z - A.u[2]) * nz;
+            if constexpr (SENSE && !POSED) { d[0] = pi.x - A.off[0]; d[1] = pi.y - A.off[1]; d[2] = pi.z - A.off[2]; }
+            float us0 = A.u[0], us1 = A.u[1], us2 = A.u[2];
+            if constexpr (POSED) {
+                ob_world_normal(X, nx, ny, nz);
+                us0 = A.u[0] + (X.omega[1] * d[2] - X.omega[2] * d[1]);
+                us1 = A.u[1] + (X.omega[2] * d[0] - X.omega[0] * d[2]);
+                us2 = A.u[2] + (X.omega[0] * d[1] - X.omega[1] * d[0]);
+            }
+            const float wn = ((vi.x - us0) * nx + (vi.y - us1) * ny) + (vi.z - us2) * nz;
             if (wn < 0.f) {
                 const float k = (ph.wall_damping - 1.f) * wn;
-                vi.x = vi.x + k * nx; vi.y = vi.y + k * ny; vi.z = vi.z + k * nz;
+                if constexpr (!SENSE) {
+                    vi.x = vi.x + k * nx; vi.y = vi.y + k * ny; vi.z = vi.z + k * nz;
+                } else {
+                    const float kx = k * nx, ky = k * ny, kz = k * nz;
+                    vi.x = vi.x + kx; vi.y = vi.y + ky; vi.z = vi.z + kz;
+                    const float t0 = -(ph.mass * kx), t1 = -(ph.mass * ky), t2 = -(ph.mass * kz);
+                    acc[0] = acc[0] + (double)t0; acc[1] = acc[1] + (double)t1; acc[2] = acc[2] + (double)t2;
+                    acc[3] = acc[3] + ((double)d[1] * (double)t2 - (double)d[2] * (double)t1);
+                    acc[4] = acc[4] + ((double)d[2] * (double)t0 - (double)d[0] * (double)t2);
+                    acc[5] = acc[5] + ((double)d[0] * (double)t1 - (double)d[1] * (double)t0);
+                    kicked = true;
+                }
             }
             const float t = eps - phi;
             pi.x = pi.x + t * nx; pi.y = pi.y + t * ny; pi.z = pi.z + t * nz;
             hit = true;
         }
+    }
+    if constexpr (SENSE) {
+        const uint64_t km = __ballot(kicked);
+        if (km != 0ull) {                                                // wave-uniform
+            double sum[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            for (uint64_t m = km; m != 0ull; m &= m - 1ull) {
+                const uint32_t l = (uint32_t)__builtin_ctzll(m);
+#pragma unroll
+                for (int a = 0; a < 6; a++) sum[a] = sum[a] + lane_value_f64(acc[a], l);
+            }
+            if (row_owner) {
+                double* row = X.rows + (size_t)(rel >> 6) * 6u;
+#pragma unroll
+                for (int a = 0; a < 6; a++) row[a] = sum[a];
+            }
+        }
+        if (row_owner) X.mask[rel >> 6] = km != 0ull ? 1u : 0u;
     }
     bool moved = false;
     if (hit) {
@@ -167,17 +274,72 @@ __global__ __launch_bounds__(OBSTACLE_THREADS) void k_obstacle_push(float4* __re
     }
 }
 
+// ---- the load: the waves' rows added in a fixed order (sph_obstacle_get_load) ----------------------------------------------------
+// One block, once per integrate of a sensing context, behind the push.  The order is k_spheres_step's (sph_pairs.hip): thread t
+// takes the waves [t K, (t + 1) K), K = ceil(waves / 256) rounded up to a multiple of 4, and adds the rows the masks point to
+// in ascending wave order; the threads that found a row are then added in ascending thread order.  It is a twin and not a
+// function shared with k_spheres_step: that kernel selects 3-column pieces of a 24-column row by the bits of its mask word
+// and goes on to the body update from its shared sums, this one takes whole rows of 6, and a shared body would have to carry
+// both as parameters through a kernel whose bits tests/test_gpu_collider_sums.py pins.
+constexpr uint32_t OBSTACLE_LOAD_THREADS = 256;
+struct ObstacleAbout { float P[3]; };
+__global__ __launch_bounds__(OBSTACLE_LOAD_THREADS) void k_obstacle_load(const double* __restrict__ rows, const uint32_t* __restrict__ mask,
+                                                                         uint32_t n_waves, double* out, ObstacleAbout about) {
+#pragma clang fp contract(off)
+    constexpr uint32_t T = OBSTACLE_LOAD_THREADS, NJ = 6;
+    __shared__ double s_acc[T][NJ];
+    __shared__ uint64_t s_found[T / 64];
+    const uint32_t t = threadIdx.x;
+    const uint32_t K = ((n_waves + T - 1u) / T + 3u) & ~3u;
+    const uint32_t w0 = t * K, w1 = min(w0 + K, n_waves);
+    double acc[NJ] = {};
+    bool found = false;
+    for (uint32_t q = w0; q < w1; q += 4u) {
+        const uint4 m4 = *reinterpret_cast<const uint4*>(mask + q);          // (the buffer is padded to whole quads)
+        const uint32_t mm[4] = {m4.x, m4.y, m4.z, m4.w};
+#pragma unroll
+        for (uint32_t e = 0; e < 4u; e++) {
+            if (q + e < w1 && mm[e] != 0u) {
+                found = true;
+                const double* row = rows + (size_t)(q + e) * NJ;
+#pragma unroll
+                for (uint32_t a = 0; a < NJ; a++) acc[a] = acc[a] + row[a];
+            }
+        }
+    }
+    const uint64_t fb = __ballot(found);
+    if ((t & 63u) == 0u) s_found[t >> 6] = fb;
+    if (found) {
+#pragma unroll
+        for (uint32_t a = 0; a < NJ; a++) s_acc[t][a] = acc[a];
+    }
+    __syncthreads();
+    if (t < NJ) {
+        double sum = 0.0;
+        for (uint32_t w = 0; w < T / 64u; w++)
+            for (uint64_t m = s_found[w]; m != 0ull; m &= m - 1ull) sum = sum + s_acc[w * 64u + (uint32_t)__builtin_ctzll(m)][t];
+        out[t] = sum;
+    }
+    if (t == NJ) reinterpret_cast<unsigned long long*>(out)[NJ] += 1ull;     // integrates since the obstacle was installed
+    if (t > NJ && t <= NJ + 3u) reinterpret_cast<float*>(out + NJ + 1u)[t - NJ - 1u] = about.P[t - NJ - 1u];
+}
+
 // ---- the sample rule for caller points ----------------------------------------------------------------------------------------
+// POSED: x is a world point, the normal comes back in world axes, by the push's arithmetic
+template <bool POSED>
 __global__ __launch_bounds__(OBSTACLE_THREADS) void k_obstacle_sample(const float* __restrict__ pos, uint32_t n, ObstacleArgs A,
                                                                       float* __restrict__ phi_out, float* __restrict__ nrm_out,
-                                                                      uint8_t* __restrict__ in_out) {
+                                                                      uint8_t* __restrict__ in_out, ObstaclePose X) {
     const uint32_t t = blockIdx.x * OBSTACLE_THREADS + threadIdx.x;
     if (t >= n) return;
     uint32_t ci[3];
-    float cf[3];
+    float cf[3], d[3];
     float phi = INFINITY, nx = 0.f, ny = 0.f, nz = 0.f;
-    const bool in = ob_locate(A, pos[3u * t], pos[3u * t + 1u], pos[3u * t + 2u], ci, cf);
-    if (in) ob_sample_cell(A, ci, cf, phi, nx, ny, nz);
+    const bool in = ob_locate_at<POSED>(A, X, pos[3u * t], pos[3u * t + 1u], pos[3u * t + 2u], ci, cf, d);
+    if (in) {
+        ob_sample_cell(A, ci, cf, phi, nx, ny, nz);
+        if constexpr (POSED) ob_world_normal(X, nx, ny, nz);
+    }
     phi_out[t] = phi;
     nrm_out[3u * t] = nx; nrm_out[3u * t + 1u] = ny; nrm_out[3u * t + 2u] = nz;
     in_out[t] = in ? 1 : 0;
@@ -265,19 +427,97 @@ float ob_clamp_distance(const sph_obstacle_grid& G) {
     return G.spacing * (float)(G.dims[0] + G.dims[1] + G.dims[2]);
 }
 
+// rot of the header from the unit quaternion: float64, each entry rounded once
+void ob_rot_of(const double q[4], float rot[9]) {
+#pragma clang fp contract(off)
+    const double w = q[0], x = q[1], y = q[2], z = q[3];
+    rot[0] = (float)(1.0 - 2.0 * (y * y + z * z)); rot[1] = (float)(2.0 * (x * y - w * z)); rot[2] = (float)(2.0 * (x * z + w * y));
+    rot[3] = (float)(2.0 * (x * y + w * z)); rot[4] = (float)(1.0 - 2.0 * (x * x + z * z)); rot[5] = (float)(2.0 * (y * z - w * x));
+    rot[6] = (float)(2.0 * (x * z - w * y)); rot[7] = (float)(2.0 * (y * z + w * x)); rot[8] = (float)(1.0 - 2.0 * (x * x + y * y));
+}
+
+// q / |q| with the header's sum; false: the squared norm is 0 or not finite
+static bool ob_quat_unit(const double in[4], double out[4]) {
+#pragma clang fp contract(off)
+    const double n2 = ((in[0] * in[0] + in[1] * in[1]) + in[2] * in[2]) + in[3] * in[3];
+    if (!(n2 > 0.0) || !std::isfinite(n2)) return false;
+    const double len = std::sqrt(n2);
+    for (int k = 0; k < 4; k++) out[k] = in[k] / len;
+    return true;
+}
+
+static ObstaclePose obstacle_pose(const sph_ctx* c) {
+#pragma clang fp contract(off)
+    ObstaclePose X{};
+    if (c->ob_posed) ob_rot_of(c->ob_quat, X.rot);
+    for (int k = 0; k < 3; k++) {
+        X.pivot[k] = c->ob_posed ? c->ob_pivot[k] : 0.f;
+        X.P[k] = c->ob_posed ? c->ob_pivot[k] + c->ob_off[k] : c->ob_off[k];
+        X.omega[k] = c->ob_posed ? c->ob_omega[k] : 0.f;
+    }
+    X.rows = c->ob_rows;
+    X.mask = c->ob_wmask;
+    return X;
+}
+
 int launch_obstacle_push(sph_ctx* c, bool fused, bool mark) {
     if (c->n == 0) return SPH_OK;
-    hipLaunchKernelGGL(k_obstacle_push, dim3(ceil_div(c->n, OBSTACLE_THREADS)), dim3(OBSTACLE_THREADS), 0, c->stream,
-                       fused ? c->posi2 : c->posi, fused ? c->velr2 : c->velr, c->pos_out, fused ? c->k0 : nullptr, c->keyS,
-                       fused && mark ? c->mm_mask : nullptr, c->mm_tile_cnt, c->own_off, c->n, obstacle_args(c), c->grid, c->phys);
+#define SPH_LAUNCH_PUSH(P, S)                                                                                                    \
+    hipLaunchKernelGGL((k_obstacle_push<P, S>), dim3(ceil_div(c->n, OBSTACLE_THREADS)), dim3(OBSTACLE_THREADS), 0, c->stream,      \
+                       fused ? c->posi2 : c->posi, fused ? c->velr2 : c->velr, c->pos_out, fused ? c->k0 : nullptr, c->keyS,       \
+                       fused && mark ? c->mm_mask : nullptr, c->mm_tile_cnt, c->own_off, c->n, obstacle_args(c), c->grid, c->phys, \
+                       obstacle_pose(c))
+    const bool sense = c->ob_sense && c->ob_load;
+    if (c->ob_posed) { if (sense) SPH_LAUNCH_PUSH(true, true); else SPH_LAUNCH_PUSH(true, false); }
+    else { if (sense) SPH_LAUNCH_PUSH(false, true); else SPH_LAUNCH_PUSH(false, false); }
+#undef SPH_LAUNCH_PUSH
     SPH_HIP(hipGetLastError());
     return SPH_OK;
 }
 
-void advance_obstacle(sph_ctx* c, float dt) {
+// Once per integrate, behind the push (sph_pairs.hip: advance_colliders).  A sensing context queues the load's sum first -- with
+// the P the push just used, and also without particles (no push ran: zeros) --, then offset and pose move on by dt.
+int advance_obstacle(sph_ctx* c, float dt) {
 #pragma clang fp contract(off)
-    if (!have_obstacle(c)) return;
+    if (!have_obstacle(c)) return SPH_OK;
+    if (c->ob_sense && c->ob_load) {
+        const ObstaclePose X = obstacle_pose(c);
+        hipLaunchKernelGGL(k_obstacle_load, dim3(1), dim3(OBSTACLE_LOAD_THREADS), 0, c->stream, c->ob_rows, c->ob_wmask,
+                           ceil_div(c->n, (uint32_t)WAVE), c->ob_load, ObstacleAbout{{X.P[0], X.P[1], X.P[2]}});
+        SPH_HIP(hipGetLastError());
+    }
     for (int k = 0; k < 3; k++) c->ob_off[k] = c->ob_off[k] + dt * c->ob_vel[k];
+    if (c->ob_posed) {                                  // the Cayley step of the header, float64
+        const double w = c->ob_quat[0], x = c->ob_quat[1], y = c->ob_quat[2], z = c->ob_quat[3];
+        const double h = 0.5 * (double)dt;
+        const double a0 = h * (double)c->ob_omega[0], a1 = h * (double)c->ob_omega[1], a2 = h * (double)c->ob_omega[2];
+        const double q[4] = {((w - a0 * x) - a1 * y) - a2 * z, ((x + a0 * w) + a1 * z) - a2 * y, ((y + a1 * w) + a2 * x) - a0 * z,
+                             ((z + a2 * w) + a0 * y) - a1 * x};
+        ob_quat_unit(q, c->ob_quat);                    // (|q'|^2 = 1 + |a|^2 >= 1; if it is not finite the pose stays)
+    }
+    return SPH_OK;
+}
+
+static void pose_reset(sph_ctx* c) {
+    c->ob_posed = false;
+    for (int k = 0; k < 3; k++) c->ob_pivot[k] = c->ob_omega[k] = 0.f;
+    c->ob_quat[0] = 1.0; c->ob_quat[1] = c->ob_quat[2] = c->ob_quat[3] = 0.0;
+}
+
+// The sensor's buffers, by capacity (the first sph_obstacle_set_sensor(on)): one row of six sums and one mask word per wave of
+// the owned slots, the masks padded as tracked_buffers_alloc (sph_pairs.hip) pads the spheres' -- k_obstacle_load reads them in
+// quads --, and the 72 bytes of the result.  Rows and masks are not cleared: every wave a sum reads was stored by the push in
+// front of it.  All three or none: ob_load doubles as "the buffers are there".
+constexpr size_t OBSTACLE_LOAD_WORDS = 9;        // J[3], L[3], the count, about[3] (fp32) + a pad word: 72 bytes
+constexpr size_t OBSTACLE_MASK_QUAD = 4;
+static int sensor_buffers_alloc(sph_ctx* c) {
+    Buffers& m = c->mem;
+    const size_t waves = ceil_div(c->cap, (uint32_t)WAVE);
+    int rc = m.alloc(&c->ob_rows, waves * 6, false);
+    if (!rc) rc = m.alloc(&c->ob_wmask, ((waves + OBSTACLE_MASK_QUAD - 1) & ~(OBSTACLE_MASK_QUAD - 1)) + OBSTACLE_MASK_QUAD, false);
+    if (!rc) rc = m.alloc(&c->ob_load, OBSTACLE_LOAD_WORDS, true);
+    if (rc) { m.release(&c->ob_load); m.release(&c->ob_wmask); m.release(&c->ob_rows); }
+    return rc;
 }
 
 void release_obstacle(sph_ctx* c) {
@@ -454,6 +694,66 @@ int sph_obstacle_clear(sph_ctx* c) {
         release_obstacle(c);
     }
     for (int k = 0; k < 3; k++) c->ob_off[k] = c->ob_vel[k] = 0.f;
+    pose_reset(c);
+    if (c->ob_load) {                                      // (the sensor's switch stays; its sums and the integrate count start again)
+        SPH_HIP(hipSetDevice(c->device));
+        SPH_HIP(hipMemsetAsync(c->ob_load, 0, OBSTACLE_LOAD_WORDS * sizeof(double), c->stream));
+    }
+    return SPH_OK;
+}
+
+int sph_obstacle_set_pose(sph_ctx* c, const sph_obstacle_pose* pose) {
+    if (int e = obstacle_ctx(c, "sph_obstacle_set_pose")) return e;
+    if (!pose) { pose_reset(c); return SPH_OK; }
+    const sph_obstacle_pose p = *pose;
+    for (int k = 0; k < 3; k++)
+        SPH_REQUIRE(std::isfinite(p.pivot[k]) && std::isfinite(p.omega[k]), SPH_E_INVALID, "obstacle pose: pivot or omega is not finite");
+    for (int k = 0; k < 4; k++) SPH_REQUIRE(std::isfinite(p.quat[k]), SPH_E_INVALID, "obstacle pose: the quaternion is not finite");
+    const double q[4] = {(double)p.quat[0], (double)p.quat[1], (double)p.quat[2], (double)p.quat[3]};
+    double unit[4];
+    SPH_REQUIRE(ob_quat_unit(q, unit), SPH_E_INVALID, "obstacle pose: the quaternion's squared norm is 0 or not finite");
+    c->ob_posed = true;
+    for (int k = 0; k < 3; k++) { c->ob_pivot[k] = p.pivot[k]; c->ob_omega[k] = p.omega[k]; }
+    for (int k = 0; k < 4; k++) c->ob_quat[k] = unit[k];
+    return SPH_OK;
+}
+
+int sph_obstacle_get_pose(const sph_ctx* c, int* posed, float pivot[3], double quat[4], float omega[3], float rot[9]) {
+    SPH_REQUIRE(c, SPH_E_INVALID, "null context");
+    if (posed) *posed = c->ob_posed ? 1 : 0;
+    for (int k = 0; k < 3; k++) {
+        if (pivot) pivot[k] = c->ob_pivot[k];
+        if (omega) omega[k] = c->ob_omega[k];
+    }
+    if (quat) for (int k = 0; k < 4; k++) quat[k] = c->ob_quat[k];
+    if (rot) ob_rot_of(c->ob_quat, rot);
+    return SPH_OK;
+}
+
+int sph_obstacle_set_sensor(sph_ctx* c, int on) {
+    if (int e = obstacle_ctx(c, "sph_obstacle_set_sensor")) return e;
+    if (on && !c->ob_load) {
+        SPH_HIP(hipSetDevice(c->device));
+        if (int rc = sensor_buffers_alloc(c)) return rc;
+    }
+    c->ob_sense = on != 0;
+    return SPH_OK;
+}
+
+int sph_obstacle_get_load(sph_ctx* c, double J[3], double L[3], float about[3], uint64_t* steps) {
+    if (int e = obstacle_ctx(c, "sph_obstacle_get_load")) return e;
+    double host[OBSTACLE_LOAD_WORDS] = {};
+    if (c->ob_load) {
+        SPH_HIP(hipSetDevice(c->device));
+        SPH_HIP(hipMemcpyAsync(host, c->ob_load, sizeof(host), hipMemcpyDeviceToHost, c->stream));
+        SPH_HIP(hipStreamSynchronize(c->stream));
+    }
+    for (int k = 0; k < 3; k++) {
+        if (J) J[k] = host[k];
+        if (L) L[k] = host[3 + k];
+    }
+    if (steps) std::memcpy(steps, &host[6], sizeof(uint64_t));
+    if (about) std::memcpy(about, &host[7], 3 * sizeof(float));
     return SPH_OK;
 }
 
@@ -505,8 +805,12 @@ int sph_obstacle_sample(sph_ctx* c, uint32_t n, const float* pos_xyz, float* phi
     if (!rc) {
         hip(hipMemcpyAsync(d_pos, pos_xyz, (size_t)n * 12, hipMemcpyHostToDevice, c->stream), "copy of the points");
         if (!rc) {
-            hipLaunchKernelGGL(k_obstacle_sample, dim3(ceil_div(n, OBSTACLE_THREADS)), dim3(OBSTACLE_THREADS), 0, c->stream, d_pos, n,
-                               obstacle_args(c), d_phi, d_nrm, d_in);
+            if (c->ob_posed)
+                hipLaunchKernelGGL(k_obstacle_sample<true>, dim3(ceil_div(n, OBSTACLE_THREADS)), dim3(OBSTACLE_THREADS), 0, c->stream,
+                                   d_pos, n, obstacle_args(c), d_phi, d_nrm, d_in, obstacle_pose(c));
+            else
+                hipLaunchKernelGGL(k_obstacle_sample<false>, dim3(ceil_div(n, OBSTACLE_THREADS)), dim3(OBSTACLE_THREADS), 0, c->stream,
+                                   d_pos, n, obstacle_args(c), d_phi, d_nrm, d_in, obstacle_pose(c));
             hip(hipGetLastError(), "k_obstacle_sample");
         }
         if (!rc && phi) hip(hipMemcpyAsync(phi, d_phi, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream), "copy of phi");

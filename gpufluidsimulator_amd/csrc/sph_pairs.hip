@@ -1504,7 +1504,7 @@ static SpheresTracked tracked_pack(const sph_ctx* c) { return SpheresTracked{c->
 // context queues k_spheres_step instead: the impulses of the launch just queued, the bodies and the centres, on the device.
 static int advance_colliders(sph_ctx* c, float dt) {
 #pragma clang fp contract(off)
-    advance_obstacle(c, dt);                      // (the obstacle's offset: once per step as well)
+    if (int rc = advance_obstacle(c, dt)) return rc;      // (the obstacle's offset and pose: once per step as well)
     if (c->tracked) {
         hipLaunchKernelGGL(k_spheres_step, dim3(1), dim3(SPHERES_STEP_THREADS), 0, c->stream, c->trk_table, c->trk_partial,
                            c->trk_mask, ceil_div(c->n, 64u), c->trk_J, c->bodies, dt, c->phys);

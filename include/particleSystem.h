@@ -174,6 +174,14 @@ public:
                             const float* hi = nullptr);
     // used, skipped, lost crossings, odd columns of the mesh-built obstacle: a closed mesh gives out[2] = out[3] = 0
     void getObstacleMeshStats(uint64_t out[4]);
+    // The obstacle as a rigid body that turns (sph_obstacle_set_pose): pivot a point of the grid's own frame, quat = (w, x, y, z)
+    // body -> world about it, omega the angular velocity in world axes (nullptr: 0); the pose advances once per step.
+    void setObstaclePose(const float pivot[3], const float quat[4], const float* omega = nullptr);
+    void clearObstaclePose();
+    // The load sensor (sph_obstacle_set_sensor / _get_load): J and L are the momentum and the angular momentum about the
+    // pivot's place in the world that the obstacle took from the fluid in the last update; divide by the time step.
+    void senseObstacleLoad(bool on);
+    void getObstacleLoad(double J[3], double L[3]);
 
     // ---- additive (absent upstream; named by BASELINE.json's north star) ------------------------
     // 4 floats per particle, by creation index (the original NVIDIA sample's layout), getCapacity() rows; the pointer

@@ -32,7 +32,7 @@
  *                  sph_set_colliders sph_get_colliders sph_set_collider_bodies sph_get_collider_impulses | sph_emit sph_remove sph_count_in_regions |
  *                  sph_obstacle_lattice sph_obstacle_build sph_obstacle_set_grid sph_obstacle_clear sph_obstacle_set_motion
  *                  sph_obstacle_get sph_obstacle_read sph_obstacle_sample sph_obstacle_build_mesh sph_obstacle_build_mesh_dev
- *                  sph_obstacle_build_obj |
+ *                  sph_obstacle_build_obj sph_obstacle_set_pose sph_obstacle_get_pose sph_obstacle_set_sensor sph_obstacle_get_load |
  *                  sph_camera_look_at sph_render sph_render_read sph_render_image_dev sph_surface_defaults sph_render_surface
  *                  sph_render_surface_read | sph_mesh_defaults sph_mesh_lattice sph_mesh_extract sph_mesh_read sph_mesh_dev
  *                  sph_mesh_save_obj |
@@ -313,7 +313,7 @@ int sph_get_collider_impulses(sph_ctx* c, uint32_t* n, double* J, uint64_t* step
 /* ---- solid obstacles of any shape: a signed-distance grid the fluid collides with (no counterpart in the reference) --------------
  * A whole-domain context holds at most one OBSTACLE: a regular grid of signed distances phi (phi < 0 inside the solid), sampled
  * trilinearly, built on the device from analytic shapes (sph_obstacle_build) or uploaded by the caller (sph_obstacle_set_grid:
- * the door for voxelised meshes).  It is static or translates uniformly.  After EVERY integrate -- the fused one of sph_step and
+ * the door for voxelised meshes).  It is static, translates uniformly, or turns about a pivot (THE POSE below).  After EVERY integrate -- the fused one of sph_step and
  * sph_force_collide_integrate, and sph_integrate -- a pass of its own pushes the owned particles out of the solid; a context
  * without an obstacle launches and allocates exactly what a library without this section does.
  *
@@ -413,6 +413,67 @@ int sph_obstacle_read(sph_ctx* c, float* phi);
 /* SAMPLE on the device for n caller points (xyz triples) with the current offset: "how far is this point from the solid".
  * Outside the grid: phi = +inf, normal (0, 0, 0), inside_grid 0.  Any output may be NULL.  Synchronises. */
 int sph_obstacle_sample(sph_ctx* c, uint32_t n, const float* pos_xyz, float* phi, float* normal_xyz, uint8_t* inside_grid);
+
+/* ---- obstacles that turn, and the load the fluid puts on them ---------------------------------------------------------------------
+ * THE POSE (sph_obstacle_set_pose; NULL = no pose: translation only, the rule above bit for bit).  The grid's own coordinates
+ * are the BODY frame.  pivot is a point of the body frame, quat = (w, x, y, z) rotates body to world about it, omega is the
+ * angular velocity in world axes, radians per unit of time.  off and u of sph_obstacle_set_motion keep their meaning, and the
+ * pivot's place in the world is P[k] = pivot[k] + off[k], fp32, computed once per launch on the host.  The pose belongs to the
+ * context like the motion: installing another grid keeps it, sph_obstacle_clear resets it to no pose, and it advances only while
+ * a grid is installed.
+ * Host state, float64, no contraction, only + - * / sqrt (tests/obstacle_pose_model.py repeats it exactly; no sin or cos):
+ *     on set:          q = (double)quat / sqrt(((w*w + x*x) + y*y) + z*z)
+ *     after each step, where the offset advances, with a[k] = (0.5 * (double)dt) * (double)omega[k]:
+ *         w' = ((w - a0*x) - a1*y) - a2*z      x' = ((x + a0*w) + a1*z) - a2*y
+ *         y' = ((y + a1*w) + a2*x) - a0*z      z' = ((z + a2*w) + a0*y) - a1*x
+ *         q  = q' / sqrt(((w'*w' + x'*x') + y'*y') + z'*z')
+ * This is the Cayley step: the angle per step is 2 atan(|omega| dt / 2), not |omega| dt -- at omega dt = 2e-3 it falls short by
+ * a relative 3.3e-7.  A caller who wants an exact angle sets the pose itself every step.
+ *     rot (row-major, body -> world; each entry computed in float64 as written, then rounded once to fp32):
+ *         R00 = 1 - 2*(y*y + z*z)    R01 = 2*(x*y - w*z)        R02 = 2*(x*z + w*y)
+ *         R10 = 2*(x*y + w*z)        R11 = 1 - 2*(x*x + z*z)    R12 = 2*(y*z - w*x)
+ *         R20 = 2*(x*z - w*y)        R21 = 2*(y*z + w*x)        R22 = 1 - 2*(x*x + y*y)
+ * Device rule of a posed context (fp32, each operation rounded, no fusion, sums left to right, as THE RULE).  SAMPLE at x:
+ *     d[k] = x[k] - P[k]
+ *     q[k] = ((R[0][k]*d[0] + R[1][k]*d[1]) + R[2][k]*d[2]) + pivot[k]
+ *     g[k] = (q[k] - origin[k]) / s
+ * then the inside test, the gather, phi and the normal nb of SAMPLE above (the body normal); the world normal, NOT renormalised:
+ *     n[k] = (R[k][0]*nb[0] + R[k][1]*nb[1]) + R[k][2]*nb[2]
+ * PUSH: the solid's velocity at the particle is us = u + omega x d,
+ *     us[0] = u[0] + (omega[1]*d[2] - omega[2]*d[1])   us[1] = u[1] + (omega[2]*d[0] - omega[0]*d[2])
+ *     us[2] = u[2] + (omega[0]*d[1] - omega[1]*d[0])
+ *     wn = ((v.x - us[0])*n.x + (v.y - us[1])*n.y) + (v.z - us[2])*n.z
+ * and everything after that is PUSH above: the kick, t = eps - phi, x = x + t*n, up to SPH_OBSTACLE_PUSH_ITERATIONS times (d is
+ * recomputed from the moved x in every iteration), the wall rule.  sph_obstacle_sample on a posed context samples at world points
+ * and returns the world normal by the same arithmetic.  A posed context with the identity quaternion uses the posed arithmetic;
+ * its bits need not equal an unposed context's.
+ *
+ * THE LOAD (sph_obstacle_set_sensor, sph_obstacle_get_load).  While the sensor is on, in every obstacle push a particle whose
+ * iteration takes the branch `wn < 0` adds k*n to its velocity as before -- no particle bit changes -- and also forms
+ *     t[a] = -(mass * (k * n[a]))                                   fp32 products, each rounded, as the spheres' term
+ *     tau[0] = (double)d[1]*(double)t[2] - (double)d[2]*(double)t[1]   and cyclic (exact products, one rounding)
+ * with the fp32 d of that iteration; on an unposed context pivot = (0, 0, 0), so d = x - off and P = off.  J is the sum of t and
+ * L the sum of tau over the owned particles, float64 from 0.0 in a fixed order: a lane adds its iterations in order; a wave adds
+ * its kicked lanes in ascending order; the waves are added as the tracked spheres' are (256 runs of K = ceil(waves / 256) rounded
+ * up to a multiple of 4 waves, ascending within a run, then the runs that hold a row in ascending order).  No floating-point
+ * atomic is involved.  J is the momentum and L the angular momentum about `about` (the P of that push) the solid took in the
+ * LAST integrate: J / dt is the force, L / dt the torque.  The position projection and the wall pass are not part of it.  `steps`
+ * counts the integrates with a grid installed while the sensor was on; a step without particles counts and reads zeros.
+ * A caller who reads the load and sets the pose each step drives a wheel by the fluid.
+ * The sensor without an obstacle is legal and reads zeros; sph_obstacle_clear keeps the switch and zeroes the load and `steps`.
+ * Device buffers (48 + 4 bytes per 64 particles of CAPACITY, and 72 bytes) are allocated when the sensor is first switched on
+ * and freed by sph_destroy.  A context that calls none of the four launches and allocates exactly what it did before.
+ *   SPH_E_STATE    a slab context (all four but sph_obstacle_get_pose).
+ *   SPH_E_INVALID  a pivot, quaternion or omega that is not finite; a quaternion whose squared norm in double is 0 or not finite.
+ * In every refused case nothing has changed and nothing was allocated.  The calls are legal at any stage and write none of the
+ * context's step flags.  Out of scope: free rigid bodies with an inertia tensor, slab contexts, snapshots carrying the pose. */
+typedef struct sph_obstacle_pose { float pivot[3]; float quat[4]; float omega[3]; } sph_obstacle_pose;
+int sph_obstacle_set_pose(sph_ctx* c, const sph_obstacle_pose* pose);
+/* The ADVANCED pose: *posed 0 = none (then pivot, omega 0 and the identity); rot as the next launch takes it.  Any pointer may be NULL. */
+int sph_obstacle_get_pose(const sph_ctx* c, int* posed, float pivot[3], double quat[4], float omega[3], float rot[9]);
+int sph_obstacle_set_sensor(sph_ctx* c, int on);
+/* J, L, about and steps of the last integrate; any pointer may be NULL.  Synchronises. */
+int sph_obstacle_get_load(sph_ctx* c, double J[3], double L[3], float about[3], uint64_t* steps);
 
 /* ---- obstacles from a triangle mesh: the mesh voxelised on the device into the grid above ----------------------------------------
  * sph_obstacle_build_mesh turns a closed triangle mesh -- host arrays, device arrays (sph_mesh_dev's pointers feed it with no host
