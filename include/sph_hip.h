@@ -461,6 +461,8 @@ int sph_obstacle_sample(sph_ctx* c, uint32_t n, const float* pos_xyz, float* phi
  * counts the integrates with a grid installed while the sensor was on; a step without particles counts and reads zeros.
  * A caller who reads the load and sets the pose each step drives a wheel by the fluid.
  * The sensor without an obstacle is legal and reads zeros; sph_obstacle_clear keeps the switch and zeroes the load and `steps`.
+ * While the switch is off nothing is summed: J, L, `about` and `steps` stay what the last sensing integrate left, and switching
+ * the sensor on again or installing another grid over the installed one keeps them too (`steps` goes on counting from there).
  * Device buffers (48 + 4 bytes per 64 particles of CAPACITY, and 72 bytes) are allocated when the sensor is first switched on
  * and freed by sph_destroy.  A context that calls none of the four launches and allocates exactly what it did before.
  *   SPH_E_STATE    a slab context (all four but sph_obstacle_get_pose).
@@ -469,7 +471,10 @@ int sph_obstacle_sample(sph_ctx* c, uint32_t n, const float* pos_xyz, float* phi
  * context's step flags.  Out of scope: free rigid bodies with an inertia tensor, slab contexts, snapshots carrying the pose. */
 typedef struct sph_obstacle_pose { float pivot[3]; float quat[4]; float omega[3]; } sph_obstacle_pose;
 int sph_obstacle_set_pose(sph_ctx* c, const sph_obstacle_pose* pose);
-/* The ADVANCED pose: *posed 0 = none (then pivot, omega 0 and the identity); rot as the next launch takes it.  Any pointer may be NULL. */
+/* The ADVANCED pose: *posed 0 = none (then pivot, omega 0 and the identity); rot as the next launch takes it.  Any pointer may be NULL.
+ * get -> set is NOT the identity: quat is the float64 state, sph_obstacle_pose.quat is float32 and sph_obstacle_set_pose normalises
+ * again, so an advanced pose cannot be handed to another context bit for bit (a pose that was set and has not advanced can: by
+ * the arguments of its set). */
 int sph_obstacle_get_pose(const sph_ctx* c, int* posed, float pivot[3], double quat[4], float omega[3], float rot[9]);
 int sph_obstacle_set_sensor(sph_ctx* c, int on);
 /* J, L, about and steps of the last integrate; any pointer may be NULL.  Synchronises. */

@@ -15,14 +15,26 @@ Three things live here, all of them plain data or plain Python:
            sph_upload in slot order, with the same parameters, colliders, bodies and settings, and that then makes the calls
            the context under test has made since.  The two have different histories (merge sort against full sort, deferred
            table clear against none, fresh keys against a hash) and the same inputs call for call, so they agree bit for bit.
+           The twin is also handed the load sensor's switch and the obstacle's pose -- by the arguments of its last
+           sph_obstacle_set_pose.  A pose that has ADVANCED since has no exact way into a fresh context (sph_obstacle_get_pose
+           shows the float64 quaternion, sph_obstacle_set_pose takes a float32 one and normalises again;
+           tests/test_context_walk_cpu.py pins that), so at such a boundary the walker RE-SEATS the context under test first: one
+           extra "kept" call on it, set_obstacle_pose(pivot, float32(shown quaternion), omega), which the numpy record follows by
+           obstacle_pose_model.quat_set and the twin repeats; the trace says so.  Long uninterrupted advances of a pose are
+           tests/test_gpu_obstacle_pose.py's (fifty steps in lockstep).
 
   PREFIXES, CALLS, continuation(), fuzz_ops()   the states, the calls that cross them and the long histories, as data: the
            GPU tests run them, the CPU test walks them through a Mirror alone and proves the coverage.
 
 An op is a tuple (name, args...); call_id() names it.  Nothing here peeks into the struct."""
+import hashlib
+
 import numpy as np
 
+import mesh_obstacle_cases
+import mesh_obstacle_model as mom
 import obstacle_model as om
+import obstacle_pose_model as pm
 import region_model
 
 LOADED, HASHED, SORTED, CELLS = 0, 1, 2, 3
@@ -42,7 +54,9 @@ TABLE = {
     "sph_set_collider_bodies": _NONE, "sph_set_colliders": _NONE,
     "sph_sort": ("set SORTED", "set", "cleared", "kept"),
     "force_finish": _NONE,
-    "sph_obstacle_build": _NONE,         # ... and _set_grid, _clear, _set_motion, _sample: one row of the document
+    "sph_obstacle_build": _NONE,         # ... and its twelve siblings, one row of the document: _set_grid, _clear, _set_motion, _sample,
+                                         # _set_pose, _get_pose, _set_sensor, _get_load, _build_mesh, _build_mesh_dev, _mesh_stats
+                                         # (walked) and _build_obj (SKIPPED_CALLS)
     "sph_mesh_extract": _NONE,           # the views: sph_render, sph_render_surface, sph_mesh_extract, one row as well
 }
 # rows of the document that a whole-domain context under the native API cannot execute (named by an identifier of their
@@ -53,6 +67,11 @@ SKIPPED_ROWS = {
     "set_slab_range": "sph_slab_recut only",
     "cudaMapZIndex": "the compat seam's own entry point",
     "launch_merge_arrivals": "sph_slab_step only",
+}
+
+# entry points of a walked row that the walk leaves out, by name and with the reason
+SKIPPED_CALLS = {
+    "sph_obstacle_build_obj": "a host parser in front of sph_obstacle_build_mesh: tests/test_gpu_obstacle_mesh_host.py has it",
 }
 
 PHASES = ("hash", "sort", "build_cells", "density", "force", "collide", "integrate", "fci")
@@ -75,11 +94,27 @@ BODY = (np.array([2.0e4], np.float32), np.array([[0.0, -9.81 * 11000, 0.0]], np.
 OBSTACLE_SPACING = 1.0 / 16.0
 OBSTACLES = {"both": [om.halfspace((-0.9, -0.93, 0.0), (-0.5, 1.0, 0.0)), om.box((-0.55, -0.6, -0.5), (0.1, 0.4, 0.1))]}
 MOTION = {"on": (np.array([0.013, -0.007, 0.004], np.float32), np.array([300.0, 0.0, -200.0], np.float32)),
-          "off": (np.zeros(3, np.float32), np.zeros(3, np.float32))}
+          "off": (np.zeros(3, np.float32), np.zeros(3, np.float32)),
+          # into the fluid ("on" carries the ramp away from it): the solid kicks particles that are at rest, which a load needs
+          "in": (np.array([0.013, -0.007, 0.004], np.float32), np.array([-200.0, 300.0, 100.0], np.float32)),
+          # where the mould of ("obstacle_build_mesh_dev",) stands: the fluid's own shape, inverted, a fifth of the box aside
+          "mould": (np.array([0.2, 0.12, -0.16], np.float32), np.zeros(3, np.float32))}
 CALLER_GRID = {"dims": (23, 21, 19), "origin": np.array([-1.13, -1.11, -1.07], np.float32), "spacing": np.float32(0.1)}
-OBSTACLE_OPS = ("obstacle_build", "obstacle_set_grid", "obstacle_motion", "obstacle_clear", "obstacle_sample")
+OBSTACLE_OPS = ("obstacle_build", "obstacle_set_grid", "obstacle_motion", "obstacle_clear", "obstacle_sample",
+                "obstacle_pose", "obstacle_get_pose", "obstacle_sensor", "obstacle_load",
+                "obstacle_build_mesh", "obstacle_mesh_stats", "obstacle_build_mesh_dev")
 VIEWS = ("render", "render_surface", "extract_mesh")
 MESH = dict(spacing=1.0 / 16.0, radius=1.0 / 8.0)
+# the mesh of ("extract_mesh", "coarse"), which feeds ("obstacle_build_mesh_dev",): a quarter of MESH's triangles (numpy voxelises them)
+MESH_COARSE = dict(spacing=1.0 / 8.0, radius=3.0 / 16.0)
+# ("obstacle_pose", tag): (pivot, quat (w, x, y, z), omega).  The pivot sits inside the ramp of OBSTACLES["both"], in the corner
+# where every particle set of this module has particles: a grid turned about it keeps them inside its lattice.  The quaternion
+# is skew and not normalised (about 14 degrees); "still" is the same pose with omega = 0.
+POSE_PIVOT = (-0.95, -0.99, -0.9)
+POSE_QUAT = (0.9, 0.03, -0.09, 0.06)
+POSES = {"turning": (POSE_PIVOT, POSE_QUAT, (3.0, -40.0, 11.0)), "still": (POSE_PIVOT, POSE_QUAT, (0.0, 0.0, 0.0))}
+# ("obstacle_build_mesh", name): small closed meshes, voxelised on the OBSTACLE_SPACING lattice of the box
+WALK_MESHES = {"ico": lambda: mesh_obstacle_cases.icosphere(2, 0.35, (-0.6, -0.8, -0.6), rotation_seed=5)}
 
 
 def caller_field(seed):
@@ -87,6 +122,46 @@ def caller_field(seed):
     x, y, z = (a.astype(np.float64) for a in om.node_positions(CALLER_GRID))
     d = np.sqrt((x[None, None, :] + 0.6) ** 2 + (y[None, :, None] + 0.8) ** 2 + (z[:, None, None] + 0.6) ** 2) - 0.35
     return (d + np.random.default_rng(seed).normal(0.0, 0.02, d.shape)).astype(np.float32)
+
+
+# ---- numpy models whose result is shared: a build of a mesh on a lattice, the mesh of a particle set --------------------------------
+_SHARED = {}
+
+
+def _digest(*arrays):
+    h = hashlib.sha1()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
+def _grid_key(grid):
+    return tuple(int(v) for v in grid["dims"]), _digest(np.asarray(grid["origin"], np.float32)), float(grid["spacing"])
+
+
+def mesh_field(vertices, triangles, grid, invert=False):
+    """(phi, (used, skipped, lost crossings, odd columns)) of mesh_obstacle_model.build, computed once per mesh and lattice"""
+    key = ("field", _digest(vertices, triangles), _grid_key(grid), bool(invert))
+    if key not in _SHARED:
+        phi, stats = mom.build(grid, vertices, triangles, 0, invert)
+        phi.setflags(write=False)
+        _SHARED[key] = (phi, tuple(int(v) for v in stats))
+    return _SHARED[key]
+
+
+def walk_mesh(name):
+    if ("mesh", name) not in _SHARED:
+        _SHARED["mesh", name] = WALK_MESHES[name]()
+    return _SHARED["mesh", name]
+
+
+def fluid_mesh(pos, box_min, box_max, radius, params):
+    """mesh_model.mesh_of, computed once per particle set (by the bits of the positions), box and parameters"""
+    import mesh_model
+    key = ("fluid", _digest(pos), tuple(box_min), tuple(box_max), float(radius), tuple(sorted(params.items())))
+    if key not in _SHARED:
+        _SHARED[key] = mesh_model.mesh_of(pos, box_min, box_max, radius, **params)
+    return _SHARED[key]
 
 
 def sample_points():
@@ -117,7 +192,8 @@ def call_id(op):
     if name == "emit": return "emit:explicit" if op[3] else "emit:auto"
     if name == "remove": return "remove:nothing" if op[1] == "none" else "remove:something"
     if name in ("set_params", "set_colliders", "set_collider_bodies", "set_precision", "set_sort_mode", "obstacle_build",
-                "obstacle_motion"): return f"{name}:{op[1]}"
+                "obstacle_motion", "obstacle_pose", "obstacle_sensor", "obstacle_build_mesh"): return f"{name}:{op[1]}"
+    if name == "extract_mesh" and len(op) > 1: return f"{name}:{op[1]}"
     return name
 
 
@@ -139,6 +215,13 @@ class Mirror:
         self.n_colliders, self.tracked = 0, False
         self.obstacle, self.motion = None, None     # the installed grid (None, or a tag that names the field) and the last motion set
         self.ob_steps = 0                # integrates that advanced the obstacle's offset (those with a grid installed)
+        # the pose and the load sensor, by the header's words: the pose belongs to the context like the motion (another grid keeps
+        # it, a clear resets it); the sensor is legal without an obstacle; sph_obstacle_clear keeps the switch and zeroes the load
+        # and `steps`; `steps` counts the integrates that ran with both a grid and the sensor; while the switch is off nothing is
+        # summed, and switching it on again or installing a grid over another keeps the load and `steps` as they are
+        self.pose, self.sense, self.load_steps = None, False, 0
+        self.posed_sense_steps = 0       # ... of which the context was also posed (what the histories are chosen by)
+        self.have_mesh = False           # sph_mesh_extract has run: sph_mesh_dev has pointers for sph_obstacle_build_mesh_dev
         self.sorts = []                  # what apply() predicted for the sorts of the last op: (merge: True/False/None, both forms: True/False/None)
         self.reached, self.calls = set(), set()     # coverage: (row, column, observable), (stage, call id)
 
@@ -196,11 +279,17 @@ class Mirror:
             self.sorts.append((merge, None if merge is None else (merge and self.sort_calls <= self.both_until)))
         self._row("sph_sort")
 
-    def _fused(self):
-        self._row("force_finish")
+    def _integrated(self):
         self.have_force = self.have_coll = False
         self.integrated = True
-        self.ob_steps += self.obstacle is not None
+        if self.obstacle is not None:
+            self.ob_steps += 1
+            self.load_steps += self.sense
+            self.posed_sense_steps += self.sense and self.pose is not None
+
+    def _fused(self):
+        self._row("force_finish")
+        self._integrated()
 
     def _phase(self, name):
         if name == "hash": self._hash()
@@ -209,9 +298,7 @@ class Mirror:
         elif name == "density": self.have_dens = True
         elif name == "force": self.have_force = True
         elif name == "collide": self.have_coll = True
-        elif name == "integrate":
-            self.have_force = self.have_coll = False; self.integrated = True
-            self.ob_steps += self.obstacle is not None
+        elif name == "integrate": self._integrated()
         elif name == "fci": self._fused()
 
     # -- every entry point -------------------------------------------------------------------------------------------------------
@@ -263,11 +350,24 @@ class Mirror:
         elif name == "obstacle_build": self.obstacle = ("build", op[1]); self._row("sph_obstacle_build")
         elif name == "obstacle_set_grid": self.obstacle = ("grid", int(op[1])); self._row("sph_obstacle_build")
         elif name == "obstacle_motion": self.motion = op[1]; self._row("sph_obstacle_build")
-        elif name == "obstacle_clear": self.obstacle = self.motion = None; self._row("sph_obstacle_build")     # (the motion goes with it)
+        elif name == "obstacle_clear":             # (the motion and the pose go with it; the sensor's switch stays, its count starts again)
+            self.obstacle = self.motion = self.pose = None; self.load_steps = 0; self._row("sph_obstacle_build")
         elif name == "obstacle_sample":
             if self.obstacle is None: return E_STATE
             self._row("sph_obstacle_build")
-        elif name in VIEWS: self._row("sph_mesh_extract")
+        elif name == "obstacle_pose": self.pose = None if op[1] == "none" else op[1]; self._row("sph_obstacle_build")
+        elif name == "obstacle_sensor": self.sense = bool(op[1]); self._row("sph_obstacle_build")
+        elif name in ("obstacle_get_pose", "obstacle_load"): self._row("sph_obstacle_build")
+        elif name == "obstacle_build_mesh": self.obstacle = ("mesh", op[1]); self._row("sph_obstacle_build")
+        elif name == "obstacle_mesh_stats":        # SPH_E_STATE unless the installed obstacle came from a mesh
+            if self.obstacle is None or self.obstacle[0] not in ("mesh", "mesh_dev"): return E_STATE
+            self._row("sph_obstacle_build")
+        elif name == "obstacle_build_mesh_dev":    # fed by sph_mesh_dev, which returns SPH_E_STATE while no mesh was extracted
+            if not self.have_mesh: return E_STATE
+            self.obstacle = ("mesh_dev",); self._row("sph_obstacle_build")
+        elif name in VIEWS:
+            self.have_mesh |= name == "extract_mesh"
+            self._row("sph_mesh_extract")
         elif name not in ("count_in", "download", "sync"):
             raise KeyError(name)
         return 0
@@ -325,7 +425,16 @@ PREFIXES = {     # name -> dict(before: ops in front of the boundary, after: ops
     # ... and with two tiles of the movers' marks (16384 slots each) under the obstacle's pass
     "hashed_20k_obstacle": dict(before=[("obstacle_build", "both"), ("upload", 20000, "flow")] + _STEPPED, after=[("hash",)],
                                 capacity=24576, calls="few"),
+    # a moving, turning, sensing obstacle from the start: every call of CALLS meets a context whose pose has already advanced
+    # (the boundary re-seats it, see Walker.rebase) and whose sensor buffers exist
+    "stepped_posed": dict(before=[("obstacle_build", "both"), ("obstacle_motion", "in"), ("obstacle_pose", "turning"),
+                                  ("obstacle_sensor", 1), _UP] + _STEPPED, after=[]),
+    # ... and 313 waves (more than one partial run in front of k_obstacle_load) with two mover tiles under the posed push
+    "hashed_20k_posed": dict(before=[("obstacle_build", "both"), ("obstacle_pose", "turning"), ("obstacle_sensor", 1),
+                                     ("upload", 20000, "flow")] + _STEPPED, after=[("hash",)], capacity=24576, calls="few"),
 }
+# the prefixes that also run HEAVY (below); all of them are at CELLS, so HEAVY brings the other three stages along
+HEAVY_PREFIXES = ("stepped", "cells", "stepped_obstacle", "stepped_posed")
 CONTINUATIONS = ("phases", "fci", "step")
 
 # name -> (class, ops, anchor): anchor True = the step that follows also runs against the float64 model; "bare" = the first
@@ -333,6 +442,8 @@ CONTINUATIONS = ("phases", "fci", "step")
 # the obstacle.  (A prefix that installs an obstacle runs every call it has with the bare twin, and none against the float64
 # model, which knows no obstacle.)
 _OB = ("obstacle_build", "both")
+_TURN, _SENSE, _MESH = ("obstacle_pose", "turning"), ("obstacle_sensor", 1), ("obstacle_build_mesh", "ico")
+_OWN = [("extract_mesh", "coarse"), ("obstacle_build_mesh_dev",), ("obstacle_motion", "mould")]
 CALLS = {
     "upload_smaller": ("edit", [("upload", 3000, "flow")], False),
     "load_snapshot": ("edit", [("load_snapshot",)], False),
@@ -386,14 +497,51 @@ CALLS = {
     "obstacle_set_by_index": ("edit", [_OB, ("set_by_index", "both", 35)], "bare"),
     "obstacle_load_snapshot": ("edit", [_OB, ("load_snapshot",)], "bare"),
     "obstacle_box_moved": ("keep", [_OB, ("set_params", "shift")], "bare"),        # the walls are the new box's; the solid stays
+    # the pose, the load sensor and the mesh doors
+    "pose_on": ("keep", [_OB, _TURN], "bare"),
+    "pose_off": ("keep", [_OB, _TURN, ("obstacle_pose", "none")], "bare"),
+    "pose_still_moving": ("keep", [_OB, ("obstacle_motion", "on"), ("obstacle_pose", "still")], "bare"),
+    "pose_alone": ("keep", [_TURN], False),                                        # no grid: nothing pushes, the quaternion stays
+    "pose_on_caller_grid": ("keep", [("obstacle_set_grid", 52), _TURN], "bare"),
+    "pose_on_mesh": ("keep", [_MESH, _TURN], "bare"),
+    "sensor_on": ("keep", [_OB, _SENSE], "bare"),
+    "sensor_posed": ("keep", [_OB, _TURN, _SENSE], "bare"),
+    "sensor_alone": ("keep", [_SENSE, ("obstacle_load",)], False),                 # no grid: legal, reads zeros
+    "sensor_off_again": ("keep", [_OB, _SENSE, ("obstacle_sensor", 0)], "bare"),
+    "load_read": ("keep", [("obstacle_load",)], False),
+    "pose_read": ("keep", [("obstacle_get_pose",)], False),
+    "mesh_on": ("keep", [_MESH], "bare"),
+    "mesh_stats": ("keep", [_MESH, ("obstacle_mesh_stats",)], "bare"),
+    "mesh_stats_none": ("keep", [("obstacle_mesh_stats",)], False),                # refused: no obstacle, or not one from a mesh
+    "mesh_from_own_none": ("keep", [("obstacle_build_mesh_dev",)], False),         # refused: no mesh was extracted
+    "mesh_replaced": ("keep", [_OB, _MESH], "bare"),
+    "posed_remove": ("edit", [_OB, _TURN, _SENSE, ("remove", 0)], "bare"),
+    "posed_emit": ("edit", [_OB, _TURN, _SENSE, ("emit", 120, 47, False)], "bare"),
+    "posed_set_by_index": ("edit", [_OB, _TURN, _SENSE, ("set_by_index", "both", 36)], "bare"),
+    "posed_load_snapshot": ("edit", [_OB, _TURN, _SENSE, ("load_snapshot",)], "bare"),
+    "posed_box_moved": ("keep", [_OB, _TURN, _SENSE, ("set_params", "shift")], "bare"),
+    # the device door: the context's own last mesh, inverted (a mould of the fluid's shape) and set aside so that it touches some
+    # particles and not all.  numpy voxelises a few thousand triangles in seconds, so these calls run under HEAVY_PREFIXES only and
+    # reach LOADED, HASHED and SORTED by an edit of velocities (the positions, and so the shared model, stay) or by phase calls
+    "mesh_from_own": ("keep", _OWN, "bare"),
+    "mesh_from_own_loaded": ("edit", [("set_by_index", "vel", 37)] + _OWN, "bare"),
+    "mesh_from_own_hashed": ("keep", [("hash",)] + _OWN, "bare"),
+    "mesh_from_own_sorted": ("keep", [("hash",), ("sort",)] + _OWN, "bare"),
+    # ... and a mesh that is an edit old: the device buffers the view left behind, voxelised around other particles (the twin, born
+    # behind the edit, has no such mesh and is handed the grid through sph_obstacle_set_grid)
+    "mesh_from_own_stale": ("edit", [_OWN[0], ("emit", 120, 48, False)] + _OWN[1:], "bare"),
 }
+HEAVY = ("mesh_from_own", "mesh_from_own_loaded", "mesh_from_own_hashed", "mesh_from_own_sorted", "mesh_from_own_stale")
 FEW = ("upload_smaller", "reset_lattice", "set_by_index_both", "emit_auto", "remove_something", "remove_nothing", "remove_emit",
        "emit_remove", "params_box_moved", "precision_mixed", "sort_mode_0", "hash_again", "refused_phase",
-       "obstacle_on", "obstacle_off", "obstacle_moving", "obstacle_remove", "obstacle_emit")
+       "obstacle_on", "obstacle_off", "obstacle_moving", "obstacle_remove", "obstacle_emit",
+       "sensor_posed", "posed_remove", "posed_emit", "mesh_on")
 
 
 def calls_for(prefix):
-    return list(CALLS) if PREFIXES[prefix].get("calls", "all") == "all" else list(FEW)
+    if PREFIXES[prefix].get("calls", "all") != "all":
+        return list(FEW)
+    return [c for c in CALLS if c not in HEAVY or prefix in HEAVY_PREFIXES]
 
 
 def usable(m, ops):
@@ -408,12 +556,17 @@ FUZZ_SEEDS = (101, 102, 103, 104, 106, 107, 108, 109)       # each holds at leas
 # change of motion, a view and a refused call (tests/test_context_walk_cpu.py); their steps are single ones, so that the bare
 # twin anchors every completed step that has an obstacle
 FUZZ_SEEDS_OBSTACLE = (201, 202, 203, 204, 206, 211)
+# histories that draw the pose, the sensor and the mesh doors as well (extended="pose"); what each of them holds is said in
+# tests/test_context_walk_cpu.py.  The device door is drawn only where it is refused: its numpy model costs seconds per particle set.
+FUZZ_SEEDS_POSE = (319, 370, 371, 400, 401, 420)
 FUZZ_CAPACITY = 16384
 
 
 def fuzz_ops(seed, n_ops=40, extended=False):
     """The operation list of one seed: an upload and n_ops calls, each legal or deliberately illegal by the mirror.  extended: a
-    quarter of the calls are the obstacle's or a view (drawn first, so the lists of the plain seeds are what they always were)."""
+    quarter of the calls are the obstacle's or a view (drawn first, so the lists of the plain seeds are what they always were);
+    extended="pose": three in ten are the pose's, the sensor's or a mesh door's (drawn before those, so the lists of the obstacle
+    seeds are what they were as well)."""
     rng = np.random.default_rng(seed)
     m = Mirror(FUZZ_CAPACITY)
     ops = []
@@ -429,6 +582,20 @@ def fuzz_ops(seed, n_ops=40, extended=False):
     push(("upload", 6000, "flow"))
     head = len(ops)
     while len(ops) < head + n_ops:
+        if extended == "pose" and rng.random() < 0.3:
+            k = int(rng.integers(12))
+            if k in (0, 1): push(("obstacle_pose", "turning"))
+            elif k == 2: push(("obstacle_pose", "still"))
+            elif k == 3: push(("obstacle_pose", "none"))
+            elif k in (4, 5): push(("obstacle_sensor", 1))
+            elif k == 6: push(("obstacle_sensor", 0))
+            elif k == 7: push(("obstacle_load",))
+            elif k == 8: push(("obstacle_get_pose",))
+            elif k == 9: push(("obstacle_build_mesh", "ico"))
+            elif k == 10: push(("obstacle_mesh_stats",))      # refused unless the grid came from a mesh
+            elif not m.have_mesh: push(("obstacle_build_mesh_dev",))     # refused: no mesh was extracted
+            else: push(("obstacle_get_pose",))
+            continue
         if extended and rng.random() < 0.25:
             k = int(rng.integers(12))
             s = int(rng.integers(1 << 20))
@@ -506,6 +673,13 @@ def _bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
 
 
+def _bits64(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+_NO_POSE = {"pivot": np.zeros(3, np.float32), "q": np.array([1.0, 0.0, 0.0, 0.0]), "omega": np.zeros(3, np.float32)}
+
+
 def _rc(fn, *a, **kw):
     """(return code, result) of a capi.Context method"""
     from gpufluidsimulator_amd import capi
@@ -573,6 +747,15 @@ class Walker:
         self.b = self.bm = None
         self.b_fresh = False
         self.anchored = self.anchor_touched = 0
+        # the pose as numpy knows it (never read from the library): kept by pm.quat_set (through pm.pose), pm.quat_step (through
+        # pm.advance) alone; pose_args is what the last set_obstacle_pose was given, pose_moved whether an integrate advanced it since
+        self.pose, self.pose_args, self.pose_moved = None, None, False
+        # the load as numpy knows it: `about` of the last sensing integrate, and J, L where that integrate was anchored (None: it
+        # was not, and only the twin can say)
+        self.load = {"J": np.zeros(3), "L": np.zeros(3), "about": np.zeros(3, np.float32)}
+        self.own_mesh = None             # (vertices, triangles) of the last extract_mesh, by the model
+        self.anchor_sensed = self.anchor_kicked = 0
+        self.anchor_last = None          # (touched, n) of the last anchored integrate
 
     def close(self):
         for c in (self.c, self.t, self.b):
@@ -645,7 +828,7 @@ class Walker:
             rc, _ = _rc(c.render_surface, self.cam)
             return (rc, None) if rc else _rc(lambda: c.read_image() + c.read_surface())
         if name == "extract_mesh":
-            mp = self.capi.mesh_defaults(**MESH)
+            mp = self.capi.mesh_defaults(**(MESH_COARSE if len(op) > 1 else MESH))
             rc, counts = _rc(c.extract_mesh, mp)
             return (rc, None) if rc else _rc(lambda: (c.mesh_lattice(mp), counts, c.mesh_field()) + c.read_mesh())
         if name == "obstacle_build":
@@ -656,6 +839,13 @@ class Walker:
         if name == "obstacle_motion": return _rc(c.set_obstacle_motion, offset=MOTION[op[1]][0], velocity=MOTION[op[1]][1])
         if name == "obstacle_clear": return _rc(c.clear_obstacle)
         if name == "obstacle_sample": return _rc(c.sample_obstacle, sample_points())
+        if name == "obstacle_pose": return _rc(c.set_obstacle_pose, None) if op[1] == "none" else _rc(c.set_obstacle_pose, *POSES[op[1]])
+        if name == "obstacle_get_pose": return _rc(self.pose_state, c)
+        if name == "obstacle_sensor": return _rc(c.set_obstacle_sensor, bool(op[1]))
+        if name == "obstacle_load": return _rc(c.obstacle_load)
+        if name == "obstacle_build_mesh": return _rc(c.build_obstacle_mesh, *walk_mesh(op[1]), spacing=OBSTACLE_SPACING)
+        if name == "obstacle_mesh_stats": return _rc(c.obstacle_mesh_stats)
+        if name == "obstacle_build_mesh_dev": return _rc(c.build_obstacle_from_mesh, spacing=OBSTACLE_SPACING, invert=True)
         if name == "download": return _rc(c.download)
         if name == "download_forces": return _rc(c.download_forces)
         if name == "set_precision": return _rc(c.set_precision, bool(op[1]))
@@ -680,7 +870,7 @@ class Walker:
             assert (sel > 0) == (op[1] != "none"), ("the region of this walk selects", sel)
         if name in ("sort", "step", "step_phased"):
             before = (c.sort_stats(), c.sort_forms())
-        ob_steps, off_before = m.ob_steps, self.off
+        ob_steps, off_before, pose_before = m.ob_steps, self.off, self.pose
         want_rc = m.apply(op, sel)
         rc, out = self._perform(c, op)
         assert rc == want_rc, f"{op}: returned {rc}, the table says {want_rc}"
@@ -703,7 +893,12 @@ class Walker:
             self._obstacle_call(op, out)
         elif name in VIEWS:
             self._check_view(op, out)
-        self.off = om.advance(self.off, self.u, self.dt, m.ob_steps - ob_steps)
+        for _ in range(m.ob_steps - ob_steps):     # once per integrate with a grid installed: the load's point, then offset and pose
+            if m.sense:
+                self.load = {"J": None, "L": None, "about": pm.world_pivot(self.pose, self.off)}
+            if self.pose is not None:
+                self.pose, self.pose_moved = pm.advance(self.pose, self.off, self.u, self.dt)[0], True
+            self.off = om.advance(self.off, self.u, self.dt, 1)
         if before is not None and m.sorts and all(s[0] is not None for s in m.sorts):
             stats, forms = c.sort_stats(), c.sort_forms()
             assert stats["sorts"] - before[0]["sorts"] == len(m.sorts), f"{op}: sorts"
@@ -720,11 +915,19 @@ class Walker:
         if edited:
             if self.twinning:
                 self.rebase()
+        elif self.t is not None and name == "obstacle_build_mesh_dev" and not self.tm.have_mesh:
+            # the mesh was extracted in front of the twin's boundary: the twin gets the grid through another door, as in _fresh
+            _, origin, spacing, _, _, phi = self.obstacle_state(c)
+            self.t.set_obstacle_grid(phi, origin, spacing)
+            self.tm.apply(("obstacle_set_grid", 0))
+            c.sync(); self.t.sync()
         elif self.t is not None and self.tm.apply(op) == 0:
             rc2, _ = self._perform(self.t, op)
             assert rc2 == 0, f"{op}: the twin returned {rc2}"
             c.sync(); self.t.sync()               # lockstep: a sort may look at a count the device has produced
-            self._bare_follows(op, m.ob_steps - ob_steps, off_before)
+            self._bare_follows(op, m.ob_steps - ob_steps, off_before, pose_before)
+        if m.ob_steps > ob_steps and m.sense:     # every integrate of a sensing context: steps, about and, where anchored, J and L
+            self._check_load(c.obstacle_load(), f"behind {self.trace[-3:]}")
         return 0
 
     # -- the obstacle, by numpy -------------------------------------------------------------------------------------------------
@@ -745,8 +948,27 @@ class Walker:
             self.off, self.u = MOTION[op[1]]
         elif name == "obstacle_clear":
             self.ob, self.off, self.u = None, np.zeros(3, np.float32), np.zeros(3, np.float32)
+            self.pose = self.pose_args = None
+            self.load = {"J": np.zeros(3), "L": np.zeros(3), "about": np.zeros(3, np.float32)}
+        elif name == "obstacle_pose":
+            if op[1] == "none":
+                self.pose = self.pose_args = None
+            else:
+                self._seat(*POSES[op[1]])
+        elif name == "obstacle_get_pose":
+            self._check_pose(out, f"{op}")
+        elif name == "obstacle_load":
+            self._check_load(out, f"{op}")
+        elif name in ("obstacle_build_mesh", "obstacle_build_mesh_dev"):      # the lattice of sph_obstacle_build, of the box as it is now
+            p = self._params()
+            grid = om.lattice(OBSTACLE_SPACING, tuple(p.box_min), tuple(p.box_max), p.particle_radius)
+            mesh, invert = (walk_mesh(op[1]), False) if name == "obstacle_build_mesh" else (self.own_mesh, True)
+            phi, stats = mesh_field(mesh[0], mesh[1], grid, invert)
+            self.ob = {"grid": grid, "phi": phi, "stats": stats}
+        elif name == "obstacle_mesh_stats":
+            assert out == self.ob["stats"] and out[0] > 100 and not any(out[1:]), f"{op}: {out}, the model {self.ob['stats']}"
         elif name == "obstacle_sample":
-            want = om.sample(self.ob["grid"], self.ob["phi"], self.off, sample_points())
+            want = pm.sample(self.ob["grid"], self.ob["phi"], self.off, self.pose, sample_points())     # (unposed: obstacle_model.sample)
             assert 100 < want[2].sum() < 500
             assert np.array_equal(out[2], want[2]), f"{op}: inside the grid"
             assert np.array_equal(_bits(out[0]), _bits(want[0])) and np.array_equal(_bits(out[1]), _bits(want[1])), f"{op}: phi, normal"
@@ -762,9 +984,48 @@ class Walker:
         return (tuple(int(v) for v in g.dims), np.array(list(g.origin), np.float32), np.float32(g.spacing),
                 np.array(list(off), np.float32), np.array(list(vel), np.float32), None if ob is None else ob["phi"])
 
+    def pose_state(self, c):
+        """(posed, pivot, quat float64, omega, rot) as sph_obstacle_get_pose shows them, posed or not"""
+        import ctypes as C
+        posed, piv, q, w, rot = C.c_int(), (C.c_float * 3)(), (C.c_double * 4)(), (C.c_float * 3)(), (C.c_float * 9)()
+        self.capi._check(c.L.sph_obstacle_get_pose(c.h, C.byref(posed), piv, q, w, rot))
+        return (int(posed.value), np.array(list(piv), np.float32), np.array(list(q), np.float64), np.array(list(w), np.float32),
+                np.array(list(rot), np.float32).reshape(3, 3))
+
+    def _seat(self, pivot, quat, omega):
+        """the record of a pose just set: pm.quat_set of the caller's float32 quaternion"""
+        self.pose, self.pose_args, self.pose_moved = pm.pose(pivot, quat, omega), (pivot, quat, omega), False
+
+    def _check_pose(self, got, tag):
+        """sph_obstacle_get_pose against the record: without a pose the context reads the identity and zeros"""
+        posed, piv, q, w, rot = got
+        assert posed == (self.pose is not None) == (self.m.pose is not None), f"posed {posed} {tag}"
+        ps = self.pose if self.pose is not None else _NO_POSE
+        assert np.array_equal(_bits(piv), _bits(ps["pivot"])) and np.array_equal(_bits(w), _bits(ps["omega"])), f"pivot, omega {tag}"
+        assert np.array_equal(_bits64(q), _bits64(ps["q"])), f"quaternion {q}, by numpy {ps['q']} {tag}"
+        assert np.array_equal(_bits(rot), _bits(pm.rot_of(ps["q"]))), f"rot {tag}"
+
+    def _check_load(self, got, tag):
+        """sph_obstacle_get_load against the record and the mirror's count"""
+        assert got["steps"] == self.m.load_steps, f"load steps {got['steps']}, the header's words say {self.m.load_steps} {tag}"
+        assert np.array_equal(_bits(got["about"]), _bits(self.load["about"])), f"load about {got['about']}, by numpy {self.load['about']} {tag}"
+        for k in ("J", "L"):
+            if self.load[k] is not None:
+                assert np.array_equal(_bits64(got[k]), _bits64(self.load[k])), f"load {k} {got[k]}, by numpy {self.load[k]} {tag}"
+
     def _check_obstacle(self, tag):
         """what the library shows of the obstacle against numpy's record, and the twin's against the context's"""
         m = self.m
+        pose, load = self.pose_state(self.c), self.c.obstacle_load()
+        self._check_pose(pose, tag)
+        self._check_load(load, tag)
+        for x, y in zip(pose, self.pose_state(self.t)):       # the twin was handed the pose (Walker.rebase) and advances it alike
+            assert np.array_equal(np.atleast_1d(x).view(np.uint8), np.atleast_1d(y).view(np.uint8)), f"the twin's pose {tag}"
+        if self.tm.load_steps > 0:       # both have summed since the boundary (the twin is younger: not `steps`)
+            twin = self.t.obstacle_load()
+            assert np.array_equal(_bits64(load["J"]), _bits64(twin["J"])) and np.array_equal(_bits64(load["L"]), _bits64(twin["L"])), \
+                f"the twin's load {tag}"
+            assert np.array_equal(_bits(load["about"]), _bits(twin["about"])), f"the twin's load about {tag}"
         got = self.obstacle_state(self.c)
         assert (m.obstacle is None) == (self.ob is None) == (got[5] is None), f"obstacle installed {tag}"
         assert np.array_equal(_bits(got[3]), _bits(self.off)), f"obstacle offset {got[3]}, by numpy {self.off} {tag}"
@@ -781,7 +1042,7 @@ class Walker:
 
     # -- the views, by numpy ------------------------------------------------------------------------------------------------------
     def _check_view(self, op, out):
-        import mesh_model, render_model, surface_model
+        import render_model, surface_model
         c, p = self.c, self._params()
         pos, vel, idx = c.download_owned()
         R = p.particle_radius
@@ -796,7 +1057,8 @@ class Walker:
             for got, want, what in zip(out, (w.rgba, w.id, w.depth, w.raw, w.thick, w.normal), ("rgba", "id", "depth", "raw", "thick", "normal")):
                 assert got.shape == want.shape and np.array_equal(got.view(np.uint8), np.ascontiguousarray(want).view(np.uint8)), f"{op}: {what}"
         else:
-            counts, origin, _, mpos, mnrm, mtri = mesh_model.mesh_of(pos, tuple(p.box_min), tuple(p.box_max), R, **MESH)
+            counts, origin, _, mpos, mnrm, mtri = fluid_mesh(pos, tuple(p.box_min), tuple(p.box_max), R, MESH_COARSE if len(op) > 1 else MESH)
+            self.own_mesh = (mpos, mtri)     # what ("obstacle_build_mesh_dev",) voxelises: the library's, by the assertions below
             (dims, got_origin), (nv, nt), got_counts, gpos, gnrm, gtri = out
             assert dims == counts.shape[::-1] and np.array_equal(_bits(got_origin), _bits(origin)), f"{op}: lattice"
             assert nt == len(mtri) > 100 and nv == len(mpos), f"{op}: {nv} vertices, {nt} triangles; the model {len(mpos)}, {len(mtri)}"
@@ -805,7 +1067,7 @@ class Walker:
             assert np.array_equal(gtri, mtri), f"{op}: triangles"
 
     # -- the bare twin --------------------------------------------------------------------------------------------------------
-    def _bare_follows(self, op, integrates, off_before):
+    def _bare_follows(self, op, integrates, off_before, pose_before):
         """the bare twin makes the call too, unless it is the obstacle's; behind the first integrate since its boundary the context
         must hold the model's push of the bare twin's output"""
         if self.b is None or op[0] in OBSTACLE_OPS:
@@ -815,22 +1077,40 @@ class Walker:
             self.b.sync()
         if op[0] in ("integrate", "fci", "step", "step_phased"):
             if self.b_fresh and integrates == 1:
-                self._check_against_model(off_before)
+                self._check_against_model(off_before, pose_before)
             self.b_fresh = False
 
-    def _check_against_model(self, off_before):
-        c, p, live = self.c, self._params(), self.live
+    def _check_against_model(self, off_before, pose_before):
+        """the integrate just made is the model's push of the bare twin's output, particle by particle IN SLOT ORDER (the load's
+        sums depend on it; the two were uploaded alike and have sorted the same positions): obstacle_model.push, or
+        obstacle_pose_model.push wherever the record is posed or sensing -- then also the load's J and L in the header's order"""
+        c, p, live, m = self.c, self._params(), self.live, self.m
         tag = f"behind {self.trace[-3:]}"
-        got, bare = c.download(), self.b.download()
-        want_p, want_v, touched = om.push(bare["pos"][live], bare["vel"][live], self.ob["grid"], self.ob["phi"], off_before, self.u,
-                                          tuple(p.box_min), tuple(p.box_max), p.wall_eps, p.wall_damping)
-        assert np.array_equal(_bits(got["pos"][live]), _bits(want_p)), \
-            f"positions against obstacle_model.push of the bare twin's: {int((_bits(got['pos'][live]) != _bits(want_p)).any(axis=1).sum())} of {touched.sum()} touched differ {tag}"
-        assert np.array_equal(_bits(got["vel"][live]), _bits(want_v)), f"velocities against obstacle_model.push of the bare twin's {tag}"
+        (pa, va, ia), (pb, vb, ib) = c.download_owned(), self.b.download_owned()
+        assert np.array_equal(ia, ib), f"slot order against the bare twin's {tag}"
+        solid = (self.ob["grid"], self.ob["phi"], off_before, self.u)
+        walls = (tuple(p.box_min), tuple(p.box_max), p.wall_eps, p.wall_damping)
+        st = None
+        if pose_before is not None or m.sense:
+            st = {}
+            want_p, want_v, touched = pm.push(pb, vb, *solid, pose_before, *walls, p.mass, stats=st)
+        else:
+            want_p, want_v, touched = om.push(pb, vb, *solid, *walls)
+        model = "obstacle_model.push" if st is None else "obstacle_pose_model.push"
+        assert np.array_equal(_bits(pa), _bits(want_p)), \
+            f"positions against {model} of the bare twin's: {int((_bits(pa) != _bits(want_p)).any(axis=1).sum())} of {touched.sum()} touched differ {tag}"
+        assert np.array_equal(_bits(va), _bits(want_v)), f"velocities against {model} of the bare twin's {tag}"
+        got, bare = c.download(want=("density", "pressure")), self.b.download(want=("density", "pressure"))
         for k in ("density", "pressure"):
             assert np.array_equal(_bits(got[k][live]), _bits(bare[k][live])), f"{k} against the bare twin's {tag}"
+        if m.sense:                  # (`about` and `steps` are the record's and the mirror's already: Walker.do)
+            self.load["J"], self.load["L"] = pm.load_in_order(st["lane"], st["kicked"], pb.shape[0])
+            self._check_load(c.obstacle_load(), tag)
+            self.anchor_sensed += 1
+            self.anchor_kicked += int(st["kicked"].sum())
         self.anchored += 1
         self.anchor_touched += int(touched.sum())
+        self.anchor_last = (int(touched.sum()), pb.shape[0])
 
     def probe_refusals(self):
         """every phase call the table says is illegal now returns SPH_E_STATE (and changes nothing: the twin never makes it)"""
@@ -863,7 +1143,14 @@ class Walker:
             if phi is not None:
                 t.set_obstacle_grid(phi, origin, spacing)
             t.set_obstacle_motion(offset=off, velocity=vel3)
-            tm.obstacle, tm.motion = m.obstacle, m.motion
+            tm.obstacle, tm.motion = (None if phi is None else ("grid", "handed")), m.motion
+            # the sensor's switch, and the pose by the arguments of its last set (rebase has re-seated a pose that had advanced)
+            if m.sense:
+                t.set_obstacle_sensor(True)
+            if self.pose is not None:
+                assert not self.pose_moved
+                t.set_obstacle_pose(*self.pose_args)
+            tm.sense, tm.pose = m.sense, m.pose
         t.upload(pos, vel, idx)
         tm.n, tm.next_index = m.n, m.next_index
         tm._row("sph_upload")
@@ -877,6 +1164,17 @@ class Walker:
             if old is not None:
                 old.close()
         self.t = self.b = None
+        if self.pose is not None and self.pose_moved:
+            # sph_obstacle_get_pose shows float64 and sph_obstacle_set_pose takes float32 and normalises again: an advanced
+            # pose has no exact way into a fresh context.  So the context under test is RE-SEATED first -- one more "kept"
+            # call on it -- with what the twin can be given too, and the record follows by pm.quat_set
+            shown = self.pose_state(c)
+            self._check_pose(shown, "in front of the re-seat")
+            pivot, _, omega = self.pose_args
+            quat = tuple(float(v) for v in shown[2].astype(np.float32))
+            c.set_obstacle_pose(pivot, quat, omega)
+            self._seat(pivot, quat, omega)
+            self.trace.append(("re-seat the pose", quat))
         pos, vel, idx = c.download_owned()
         p = self._params()
         assert c.L.sph_get_precision(c.h) == m.precision

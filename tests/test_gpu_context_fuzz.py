@@ -6,7 +6,12 @@ must be what sph_download_owned, sph_download and sph_download_positions4 report
 
 Six more seeds also draw the obstacle calls and the views.  There every view is compared with its numpy model, the obstacle the
 library shows with numpy's record of it, and every completed step that has an obstacle is obstacle_model.push applied to the
-output of a bare twin (a context without the obstacle, rebuilt at the same boundaries)."""
+output of a bare twin (a context without the obstacle, rebuilt at the same boundaries).
+
+Six more again (context_walk.FUZZ_SEEDS_POSE) also draw the pose, the load sensor and the mesh doors: every completed step behind a
+posed or sensing obstacle is obstacle_pose_model.push of the bare twin's output with the load's J and L in the header's order, and
+the pose and the load are held to the numpy record after every call.  Every completed step is a boundary, so an advanced pose is
+re-seated there (context_walk.Walker.rebase); long uninterrupted advances are tests/test_gpu_obstacle_pose.py's."""
 import pytest
 
 import context_walk as cw
@@ -39,6 +44,9 @@ def _history(seed, snapshot, extended):
             raise AssertionError(f"seed {seed}, call {len(done)} of {ops}: {e}") from e
         if extended:         # every integrate with an obstacle installed was the first behind a boundary, and was held to the model
             assert w.anchored == w.m.ob_steps >= 2 and w.anchor_touched > 0, (w.anchored, w.m.ob_steps, w.anchor_touched)
+        if extended == "pose":
+            assert w.anchored >= 3 and w.anchor_sensed >= w.m.posed_sense_steps >= 2 and w.anchor_kicked > 0, \
+                (w.anchored, w.anchor_sensed, w.m.posed_sense_steps, w.anchor_kicked)
 
 
 @pytest.mark.parametrize("seed", cw.FUZZ_SEEDS)
@@ -49,3 +57,8 @@ def test_history(seed, snapshot):
 @pytest.mark.parametrize("seed", cw.FUZZ_SEEDS_OBSTACLE)
 def test_history_with_obstacles_and_views(seed, snapshot):
     _history(seed, snapshot, True)
+
+
+@pytest.mark.parametrize("seed", cw.FUZZ_SEEDS_POSE)
+def test_history_with_pose_sensor_and_mesh(seed, snapshot):
+    _history(seed, snapshot, "pose")

@@ -12,7 +12,16 @@ The obstacle calls, the surface and the mesh are calls of the matrix like any ot
 the start.  What the library shows of the obstacle is held to a numpy record of it after every call (field, lattice, the offset
 advanced once per integrate); every view is compared with its numpy model; and wherever an obstacle is installed when the step
 is finished, the first integrate is obstacle_model.push applied to the output of a BARE twin -- a context without the obstacle
-that made the same calls -- for every particle, under all three continuations."""
+that made the same calls -- for every particle, under all three continuations.
+
+So are the pose, the load sensor and the mesh doors (sph_obstacle_set_pose, _get_pose, _set_sensor, _get_load, _build_mesh,
+_build_mesh_dev, _mesh_stats): set, switched, read and built at every stage, alone and together, on a caller's grid and on a
+mesh-built one, in front of every edit, and on two prefixes that are posed and sensing from the start.  The pose and the load
+the library shows are held to a numpy record after every call (the quaternion as uint64 bits, `steps` by the header's words);
+behind a posed or sensing obstacle the first integrate is obstacle_pose_model.push of the bare twin's output in slot order, with
+J and L summed in the header's order, and at least one particle kicked.  The twin is handed the sensor's switch and the pose;
+a pose that has advanced is re-seated on the context under test first (context_walk.Walker.rebase says why).  The device door
+voxelises the context's own last mesh; its numpy model takes seconds, so its calls -- one of them with a mesh that is an edit old -- run under context_walk.HEAVY_PREFIXES."""
 import pytest
 
 import context_walk as cw
@@ -52,6 +61,11 @@ def run_case(prefix, call, cont, snapshot):
                 w.compare("the continuation")
         if pushes:
             assert w.anchored == 1 and w.anchor_touched > 0, (w.anchored, w.anchor_touched)
+            assert w.anchor_sensed == int(w.m.sense), (w.anchor_sensed, w.m.sense)
+            if w.m.sense:                                  # a load of zero would prove nothing
+                assert w.anchor_kicked > 0, "no particle was kicked under the sensor"
+            if w.m.obstacle == ("mesh_dev",) and w.m.pose is None:     # the mould of the fluid's own mesh: some particles, not all
+                assert 20 <= w.anchor_last[0] < w.anchor_last[1], w.anchor_last
             w.do(("hash",))                                # the keys the pass left (fused) or a hash computes: numpy's, of the slots' positions
             w.compare("the hash behind the push")
         elif w.bare:
