@@ -57,11 +57,12 @@ def build(force: bool = False, verbose: bool = False) -> str:
     if os.path.exists(main_src) and (force or _stale(exe, [main_src, LIB] + headers)):
         run([HIPCC, "-O2", "-std=c++17", "-x", "c++", main_src, "-x", "none", "-o", exe, "-L" + HERE, "-lsph_hip",
              "-Wl,-rpath,$ORIGIN"])
-    # the host class's posed obstacle and load sensor, for the tests (the driver above has no option for them yet)
-    exe, main_src = os.path.join(HERE, "sph_pose_probe"), os.path.join(CSRC, "sph_pose_probe.cpp")
-    if os.path.exists(main_src) and (force or _stale(exe, [main_src, LIB] + headers)):
-        run([HIPCC, "-O2", "-std=c++17", "-x", "c++", main_src, "-x", "none", "-o", exe, "-L" + HERE, "-lsph_hip",
-             "-Wl,-rpath,$ORIGIN"])
+    # test programs for the host class: the posed obstacle and load sensor, and the obstacle slots
+    for name in ("sph_pose_probe", "sph_set_probe"):
+        exe, main_src = os.path.join(HERE, name), os.path.join(CSRC, name + ".cpp")
+        if os.path.exists(main_src) and (force or _stale(exe, [main_src, LIB] + headers)):
+            run([HIPCC, "-O2", "-std=c++17", "-x", "c++", main_src, "-x", "none", "-o", exe, "-L" + HERE, "-lsph_hip",
+                 "-Wl,-rpath,$ORIGIN"])
     return LIB
 
 

@@ -6,6 +6,7 @@ no CPU fallback -- a missing library or a missing gfx950 device raises.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 
 import numpy as np
@@ -235,6 +236,10 @@ SIGNATURES = {
                                               _P, _U32, _P]),
     "sph_obstacle_build_obj": (C.c_int, [_P, C.POINTER(ObstacleMeshParams), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_char_p]),
     "sph_obstacle_mesh_stats": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "sph_obstacle_select": (C.c_int, [_P, _U32]),
+    "sph_obstacle_selected": (_U32, [_P]),
+    "sph_obstacle_installed": (_U32, [_P, C.POINTER(_U32)]),
+    "sph_obstacle_clear_all": (C.c_int, [_P]),
     "sph_mesh_defaults": (None, [C.POINTER(MeshParams)]),
     "sph_mesh_lattice": (C.c_int, [_P, C.POINTER(MeshParams), C.POINTER(_U32), C.POINTER(C.c_float)]),
     "sph_mesh_extract": (C.c_int, [_P, C.POINTER(MeshParams), C.POINTER(_U32), C.POINTER(_U32)]),
@@ -466,6 +471,24 @@ def _f32(a, cols):
     return a.reshape(-1, cols)
 
 
+MAX_OBSTACLES = 4        # SPH_MAX_OBSTACLES
+
+
+def _slotted(method):
+    """An obstacle method with the optional keyword slot=k: select k, call, restore the selection."""
+    @functools.wraps(method)
+    def call(self, *args, slot=None, **kw):
+        if slot is None:
+            return method(self, *args, **kw)
+        before = self.selected_obstacle()
+        self.select_obstacle(slot)
+        try:
+            return method(self, *args, **kw)
+        finally:
+            self.select_obstacle(before)
+    return call
+
+
 class Context:
     """One `sph_ctx`: the device state of a particle system (or of one z-slab of it)."""
 
@@ -634,6 +657,25 @@ class Context:
                 "velocities": np.array([list(r.velocity) for r in rows], np.float32).reshape(-1, 3)}
 
     # -- obstacles (whole-domain contexts; include/sph_hip.h: sph_obstacle_build and the calls next to it) -------------------------
+    # Every method below marked @_slotted takes an optional slot=k: it selects slot k, calls and restores the selection; without
+    # it the call addresses the current selection (slot 0 unless select_obstacle chose another).
+    def select_obstacle(self, slot):
+        """Every obstacle call from now on addresses `slot` (0..MAX_OBSTACLES - 1)."""
+        _check(self.L.sph_obstacle_select(self.h, int(slot)))
+
+    def selected_obstacle(self) -> int:
+        return int(self.L.sph_obstacle_selected(self.h))
+
+    def installed_obstacles(self):
+        """(count, mask): the slots that hold a grid; bit k of mask = slot k."""
+        mask = _U32()
+        n = self.L.sph_obstacle_installed(self.h, C.byref(mask))
+        return int(n), int(mask.value)
+
+    def clear_obstacles_all(self):
+        """clear_obstacle on every slot, and the selection back to 0."""
+        _check(self.L.sph_obstacle_clear_all(self.h))
+
     @staticmethod
     def _bounds(bounds):
         if bounds is None:
@@ -641,6 +683,7 @@ class Context:
         lo, hi = bounds
         return _f3(lo), _f3(hi)
 
+    @_slotted
     def obstacle_lattice(self, spacing=0.0, bounds=None) -> ObstacleGrid:
         """The lattice build_obstacle would use: a host helper.  bounds = (lo, hi) or None (the box)."""
         g = ObstacleGrid()
@@ -648,6 +691,7 @@ class Context:
         _check(self.L.sph_obstacle_lattice(self.h, float(spacing), lo, hi, C.byref(g)))
         return g
 
+    @_slotted
     def build_obstacle(self, shapes, spacing=0.0, bounds=None):
         """Rasterise the union of `shapes` (Shape.sphere / box / capsule / halfspace) on the device and install it as the
         context's obstacle: every later integrate pushes the particles out of it.  spacing 0 = the particle diameter."""
@@ -656,6 +700,7 @@ class Context:
         lo, hi = self._bounds(bounds)
         _check(self.L.sph_obstacle_build(self.h, float(spacing), lo, hi, len(shapes), arr))
 
+    @_slotted
     def set_obstacle_grid(self, phi, origin, spacing):
         """Install the caller's signed distances: phi of shape (n_z, n_y, n_x) (x fastest), float32; negative inside the solid."""
         phi = np.ascontiguousarray(phi, dtype=np.float32)
@@ -664,14 +709,17 @@ class Context:
         g = ObstacleGrid((_U32 * 3)(phi.shape[2], phi.shape[1], phi.shape[0]), _f3(origin), float(spacing))
         _check(self.L.sph_obstacle_set_grid(self.h, C.byref(g), phi.ctypes.data))
 
+    @_slotted
     def clear_obstacle(self):
         _check(self.L.sph_obstacle_clear(self.h))
 
+    @_slotted
     def set_obstacle_motion(self, offset=None, velocity=None):
         """Offset and / or velocity of the grid (None = keep): the offset advances by dt * velocity once per step."""
         _check(self.L.sph_obstacle_set_motion(self.h, None if offset is None else _f3(offset),
                                               None if velocity is None else _f3(velocity)))
 
+    @_slotted
     def obstacle(self, read=False):
         """None without an obstacle, else {"dims": (n_x, n_y, n_z), "origin", "spacing", "offset", "velocity"} with the advanced
         offset; read=True adds "phi", the installed (clamped) field of shape (n_z, n_y, n_x) (synchronises)."""
@@ -688,6 +736,7 @@ class Context:
             out["phi"] = phi
         return out
 
+    @_slotted
     def sample_obstacle(self, points):
         """(phi (n,), normal (n, 3), inside_grid (n,) bool) of the obstacle at `points`, by the rule the particles see: phi =
         +inf and normal 0 outside the grid.  Synchronises."""
@@ -697,6 +746,7 @@ class Context:
         _check(self.L.sph_obstacle_sample(self.h, n, pts.ctypes.data, phi.ctypes.data, nrm.ctypes.data, inside.ctypes.data))
         return phi, nrm, inside.astype(bool)
 
+    @_slotted
     def set_obstacle_pose(self, pivot=None, quat=None, omega=(0.0, 0.0, 0.0)):
         """The rigid pose of the obstacle: `pivot` a point of the grid's own (body) frame, `quat` = (w, x, y, z) body -> world
         about it (normalised by the library), `omega` the angular velocity in world axes; the pose advances once per step.
@@ -707,6 +757,7 @@ class Context:
         p = ObstaclePose(_f3(pivot), (C.c_float * 4)(*[float(v) for v in quat]), _f3(omega))
         _check(self.L.sph_obstacle_set_pose(self.h, C.byref(p)))
 
+    @_slotted
     def obstacle_pose(self):
         """None without a pose, else {"pivot" (3,) float32, "quat" (4,) float64 (unit, advanced), "omega" (3,) float32,
         "rot" (3, 3) float32 body -> world as the next launch takes it}."""
@@ -717,10 +768,12 @@ class Context:
         return {"pivot": np.array(list(piv), np.float32), "quat": np.array(list(q), np.float64),
                 "omega": np.array(list(om), np.float32), "rot": np.array(list(rot), np.float32).reshape(3, 3)}
 
+    @_slotted
     def set_obstacle_sensor(self, on=True):
         """Switch the load sensor: while on, every integrate also sums what the obstacle took from the fluid (obstacle_load)."""
         _check(self.L.sph_obstacle_set_sensor(self.h, int(bool(on))))
 
+    @_slotted
     def obstacle_load(self):
         """{"J" (3,), "L" (3,) float64, "about" (3,) float32, "steps"}: the momentum and the angular momentum about `about` the
         obstacle took in the LAST integrate (divide by dt for force and torque).  Synchronises."""
@@ -730,6 +783,7 @@ class Context:
                 "about": np.array(list(about), np.float32), "steps": int(steps.value)}
 
     # -- obstacles from a triangle mesh (include/sph_hip.h: sph_obstacle_build_mesh and the calls next to it) -----------------------
+    @_slotted
     def build_obstacle_mesh(self, vertices, triangles, spacing=0.0, band=0, invert=False, bounds=None):
         """Voxelise the closed triangle mesh (vertices (nv, 3) float32, triangles (nt, 3) uint32) on the device into a truncated
         signed distance, `band` nodes wide (0 = 3), and install it as the context's obstacle.  Synchronises."""
@@ -738,6 +792,7 @@ class Context:
         lo, hi = self._bounds(bounds)
         _check(self.L.sph_obstacle_build_mesh(self.h, C.byref(p), lo, hi, v.shape[0], v.ctypes.data, t.shape[0], t.ctypes.data))
 
+    @_slotted
     def build_obstacle_from_mesh(self, spacing=0.0, band=0, invert=False, bounds=None):
         """The same from the context's own last extract_mesh, through its device pointers: no host trip, no host wait."""
         pos, _, tri, nv, nt = self.mesh_dev()
@@ -745,12 +800,14 @@ class Context:
         lo, hi = self._bounds(bounds)
         _check(self.L.sph_obstacle_build_mesh_dev(self.h, C.byref(p), lo, hi, nv, pos, nt, tri))
 
+    @_slotted
     def build_obstacle_obj(self, path, spacing=0.0, band=0, invert=False, bounds=None):
         """The same from a Wavefront OBJ file (`v` and `f` lines; polygons are fanned).  Synchronises."""
         p = ObstacleMeshParams(float(spacing), int(band), int(bool(invert)))
         lo, hi = self._bounds(bounds)
         _check(self.L.sph_obstacle_build_obj(self.h, C.byref(p), lo, hi, os.fsencode(path)))
 
+    @_slotted
     def obstacle_mesh_stats(self):
         """(triangles used, triangles skipped, lost crossings, odd columns) of the mesh-built obstacle: a closed mesh has no odd
         column and no lost crossing.  Synchronises."""

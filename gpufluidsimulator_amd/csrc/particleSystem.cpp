@@ -533,6 +533,12 @@ void ParticleSystem::senseObstacleLoad(bool on) { SPH_CHECK(sph_obstacle_set_sen
 
 void ParticleSystem::getObstacleLoad(double J[3], double L[3]) { SPH_CHECK(sph_obstacle_get_load(m_ctx, J, L, nullptr, nullptr)); }
 
+void ParticleSystem::selectObstacle(uint slot) { SPH_CHECK(sph_obstacle_select(m_ctx, slot)); }
+
+uint ParticleSystem::selectedObstacle() { return sph_obstacle_selected(m_ctx); }
+
+void ParticleSystem::clearAllObstacles() { SPH_CHECK(sph_obstacle_clear_all(m_ctx)); }
+
 void ParticleSystem::saveState(const std::string& path) { SPH_CHECK(sph_snapshot_save(m_ctx, path.c_str())); }
 
 void ParticleSystem::loadState(const std::string& path) {

@@ -213,6 +213,35 @@ enum HostWord : uint32_t {
     HW_WORDS = 8
 };
 
+// One obstacle slot of a whole-domain context (sph_obstacle.hip): the clamped signed distances, 4 bytes per node, and the minimum
+// of every brick of OBSTACLE_BRICK^3 cells; grid.dims = 0, 0, 0 and null pointers while there is none.  Allocated by the call
+// that installs a grid, freed by sph_obstacle_clear; never by a caller who sets no obstacle.  The offset advances on the host
+// once per step, next to the spheres' centres (sph_pairs.hip: advance_colliders).
+struct Obstacle {
+    sph_obstacle_grid grid{};
+    float* phi = nullptr;
+    float* brick = nullptr;
+    float off[3] = {0.f, 0.f, 0.f}, vel[3] = {0.f, 0.f, 0.f};
+    // the rigid pose (sph_obstacle_set_pose): while `posed`, the grid's coordinates are a body frame turned by the unit
+    // quaternion quat (w, x, y, z; double) about pivot, and omega is the angular velocity in world axes.  It belongs to the
+    // slot like the motion and advances where the offset does (advance_obstacle).
+    bool posed = false;
+    float pivot[3] = {0.f, 0.f, 0.f}, omega[3] = {0.f, 0.f, 0.f};
+    double quat[4] = {1.0, 0.0, 0.0, 0.0};
+    // the load sensor (sph_obstacle_set_sensor): while `sense`, every push leaves one row of six float64 sums and one mask
+    // word per wave, and k_obstacle_load adds them once per integrate.  Allocated when the slot's sensor is first switched on.
+    bool sense = false;
+    double* rows = nullptr;             // ceil(cap / 64) rows of 6: J, L
+    uint32_t* wmask = nullptr;          // ceil(cap / 64) words, padded to whole quads plus one
+    double* load = nullptr;             // J[3], L[3], the integrate count (uint64), about[3] (fp32) and a pad word: 72 bytes
+    // an obstacle voxelised from a triangle mesh (sph_obstacle_mesh.hip) keeps the scratch of its build -- the work list with the
+    // four counters in front, and the parity marks of the columns -- until the next installation, sph_obstacle_clear or
+    // sph_destroy; both null for every other obstacle, and sph_obstacle_mesh_stats reads the counters
+    uint64_t* mesh_work = nullptr;
+    uint32_t* mesh_marks = nullptr;
+    bool installed() const { return phi != nullptr; }
+};
+
 }  // namespace sph
 
 // The opaque context of include/sph_hip.h.
@@ -275,31 +304,10 @@ struct sph_ctx {
     uint32_t* trk_mask = nullptr;       // ceil(cap / 64) words, padded to a multiple of 4
     double* trk_J = nullptr;            // SPH_MAX_COLLIDERS x 3 doubles of the last integrate, then the step count (uint64)
 
-    // the obstacle (sph_obstacle.hip): the clamped signed distances, 4 bytes per node, and the minimum of every brick of
-    // OBSTACLE_BRICK^3 cells; ob_grid.dims = 0, 0, 0 and null pointers while there is none.  Allocated by the call that
-    // installs a grid, freed by sph_obstacle_clear; never by a caller who sets no obstacle.  The offset advances on the host
-    // once per step, next to the spheres' centres (sph_pairs.hip: advance_colliders).
-    sph_obstacle_grid ob_grid{};
-    float* ob_phi = nullptr;
-    float* ob_brick = nullptr;
-    float ob_off[3] = {0.f, 0.f, 0.f}, ob_vel[3] = {0.f, 0.f, 0.f};
-    // the rigid pose (sph_obstacle_set_pose): while `ob_posed`, the grid's coordinates are a body frame turned by the unit
-    // quaternion ob_quat (w, x, y, z; double) about ob_pivot, and ob_omega is the angular velocity in world axes.  It belongs to
-    // the context like the motion and advances where the offset does (advance_obstacle).
-    bool ob_posed = false;
-    float ob_pivot[3] = {0.f, 0.f, 0.f}, ob_omega[3] = {0.f, 0.f, 0.f};
-    double ob_quat[4] = {1.0, 0.0, 0.0, 0.0};
-    // the load sensor (sph_obstacle_set_sensor): while `ob_sense`, every push leaves one row of six float64 sums and one mask
-    // word per wave, and k_obstacle_load adds them once per integrate.  Allocated when the sensor is first switched on.
-    bool ob_sense = false;
-    double* ob_rows = nullptr;          // ceil(cap / 64) rows of 6: J, L
-    uint32_t* ob_wmask = nullptr;       // ceil(cap / 64) words, padded to whole quads plus one
-    double* ob_load = nullptr;          // J[3], L[3], the integrate count (uint64), about[3] (fp32) and a pad word: 72 bytes
-    // an obstacle voxelised from a triangle mesh (sph_obstacle_mesh.hip) keeps the scratch of its build -- the work list with the
-    // four counters in front, and the parity marks of the columns -- until the next installation, sph_obstacle_clear or
-    // sph_destroy; both null for every other obstacle, and sph_obstacle_mesh_stats reads the counters
-    uint64_t* ob_mesh_work = nullptr;
-    uint32_t* ob_mesh_marks = nullptr;
+    // the obstacles (sph_obstacle.hip): SPH_MAX_OBSTACLES slots, each what `struct Obstacle` (above) holds, and the slot the
+    // sph_obstacle_* calls address (sph_obstacle_select).  The installed slots act in ascending order behind every integrate.
+    sph::Obstacle ob[SPH_MAX_OBSTACLES];
+    uint32_t ob_sel = 0;
 
     // the image of the last sph_render (sph_render.hip): per pixel a 64-bit key (depth bits << 32 | slot) and the resolved
     // RGBA8, creation index and depth.  Allocated at the first render, again when the image size changes; never by a caller
@@ -487,7 +495,12 @@ int step_cells(sph_ctx* c);
 int launch_integrate(sph_ctx* c, float dt);
 // the obstacle (sph_obstacle.hip): push the owned particles an integrate just wrote out of the solid.  `fused`: the launch wrote
 // posi2 / velr2 and the next keys k0, and, with `mark`, the movers' marks, which the pass keeps right; else posi / velr alone
-inline bool have_obstacle(const sph_ctx* c) { return c->ob_phi != nullptr; }
+inline bool have_obstacle(const sph_ctx* c) {        // any slot installed
+    for (const Obstacle& o : c->ob) if (o.installed()) return true;
+    return false;
+}
+inline Obstacle& selected_obstacle(sph_ctx* c) { return c->ob[c->ob_sel]; }
+inline const Obstacle& selected_obstacle(const sph_ctx* c) { return c->ob[c->ob_sel]; }
 int launch_obstacle_push(sph_ctx* c, bool fused, bool mark);
 int advance_obstacle(sph_ctx* c, float dt);   // once per integrate, behind the push: queues the load's sum while sensing, then offset and pose move on
 // the installation helpers of sph_obstacle.hip, for the mesh voxeliser (sph_obstacle_mesh.hip): the context check, the lattice

@@ -59,6 +59,15 @@ struct Options {
         uint band = 0;                     // 0, as the cell: the library's default
         float cell = 0.f, velocity[3] = {0.f, 0.f, 0.f};
     } obstacle;
+    struct Solid {                         // -solid=<k>:... and its options: slot k of the context (the -obstacle family is slot 0)
+        bool given = false, invert = false, has_velocity = false, has_spin = false, has_cell = false;
+        std::vector<sph_shape> shapes;
+        std::string mesh;                  // the OBJ file of -solid=<k>:[!]mesh:FILE.obj, else empty
+        uint band = 0;
+        float cell = 0.f, velocity[3] = {0.f, 0.f, 0.f}, pivot[3] = {0.f, 0.f, 0.f}, omega[3] = {0.f, 0.f, 0.f};
+    } solid[SPH_MAX_OBSTACLES];
+    bool solidhelp = false;
+    bool solids() const { for (const Solid& s : solid) if (s.given) return true; return false; }
     struct { bool on = false; float center[3] = {0.f, 0.f, 0.f}, velocity[3] = {0.f, 0.f, 0.f}; int radius = 0, every = 0; } emit;
     struct { bool on = false; float lo[3] = {0.f, 0.f, 0.f}, hi[3] = {0.f, 0.f, 0.f}; int every = 1; } drain;
     struct { bool on = false; int at = -1, count = 0; } add;
@@ -199,6 +208,76 @@ bool parse_obstacles(const Args& a, Options& o) {
     return true;
 }
 
+// -solid=<k>:... and -solidcell / -solidband / -solidvel / -solidspin=<k>:..., all repeatable: the slots 0..3 of the context, each
+// with the grammar of the -obstacle family behind the `<k>:`.  Only the form is checked here.
+const char* solid_slot(const char* t, int* k) {                    // "<k>:rest" -> rest, or null
+    if (t[0] < '0' || t[0] >= '0' + SPH_MAX_OBSTACLES || t[1] != ':') return nullptr;
+    *k = t[0] - '0';
+    return t + 2;
+}
+
+bool parse_solids(const Args& a, Options& o) {
+    o.solidhelp = a.flag("solidhelp");
+    const char* const slot_form = "expected <k>:..., k = 0..3\n";
+    for (int i = 1; i < a.argc; i++) {
+        int k = 0;
+        if (const char* t = Args::match(a.argv[i], "solid=")) {
+            const char* rest = solid_slot(t, &k);
+            if (!rest) return fail("-solid=%s: %s", t, slot_form);
+            auto& s = o.solid[k];
+            const bool inv = *rest == '!';
+            if (!strncmp(rest + (inv ? 1 : 0), "mesh:", 5)) {
+                const char* file = rest + (inv ? 1 : 0) + 5;
+                if (!*file) return fail("-solid=%s: expected <k>:[!]mesh:FILE.obj\n", t);
+                if (!s.mesh.empty()) return fail("-solid=%s: slot %d already has a mesh\n", t, k);
+                s.mesh = file; s.invert = inv;
+            } else {
+                sph_shape sh;
+                if (!parse_shape(rest, &sh))
+                    return fail("-solid=%s: expected <k>:<shape> with the shapes of -obstacle, or <k>:[!]mesh:FILE.obj\n", t);
+                s.shapes.push_back(sh);
+            }
+            s.given = true;
+        } else if (const char* t = Args::match(a.argv[i], "solidcell=")) {
+            const char* rest = solid_slot(t, &k);
+            char tail = 0;
+            if (!rest || sscanf(rest, "%f%c", &o.solid[k].cell, &tail) != 1) return fail("-solidcell=%s: expected <k>:<s>, k = 0..3\n", t);
+            o.solid[k].has_cell = true;
+        } else if (const char* t = Args::match(a.argv[i], "solidband=")) {
+            const char* rest = solid_slot(t, &k);
+            char* end = nullptr;
+            const long b = rest ? strtol(rest, &end, 10) : 0;
+            if (!rest || end == rest || *end || b < 1 || b > SPH_OBSTACLE_MESH_MAX_BAND)
+                return fail("-solidband=%s: expected <k>:<N>, k = 0..3, N = 1..%d\n", t, SPH_OBSTACLE_MESH_MAX_BAND);
+            o.solid[k].band = (uint)b;
+        } else if (const char* t = Args::match(a.argv[i], "solidvel=")) {
+            const char* rest = solid_slot(t, &k);
+            char tail = 0;
+            float* u = rest ? o.solid[k].velocity : nullptr;
+            if (!rest || sscanf(rest, "%f,%f,%f%c", &u[0], &u[1], &u[2], &tail) != 3) return fail("-solidvel=%s: expected <k>:ux,uy,uz, k = 0..3\n", t);
+            o.solid[k].has_velocity = true;
+        } else if (const char* t = Args::match(a.argv[i], "solidspin=")) {
+            const char* rest = solid_slot(t, &k);
+            char tail = 0;
+            float* p = rest ? o.solid[k].pivot : nullptr; float* w = rest ? o.solid[k].omega : nullptr;
+            if (!rest || sscanf(rest, "%f,%f,%f,%f,%f,%f%c", &p[0], &p[1], &p[2], &w[0], &w[1], &w[2], &tail) != 6)
+                return fail("-solidspin=%s: expected <k>:px,py,pz,wx,wy,wz, k = 0..3\n", t);
+            o.solid[k].has_spin = true;
+        }
+    }
+    for (int k = 0; k < SPH_MAX_OBSTACLES; k++) {
+        const auto& s = o.solid[k];
+        if (!s.given && (s.has_cell || s.band || s.has_velocity || s.has_spin))
+            return fail("-solidcell / -solidband / -solidvel / -solidspin=%d:... go with a -solid=%d:...\n", k, k);
+        if (!s.mesh.empty() && !s.shapes.empty())
+            return fail("-solid=%d: a mesh and shapes exclude each other: a slot holds one grid (no union of a mesh with shapes)\n", k);
+        if (s.mesh.empty() && s.band) return fail("-solidband=%d:... goes with a -solid=%d:mesh:FILE.obj\n", k, k);
+    }
+    if (o.solid[0].given && (!o.obstacle.shapes.empty() || o.obstacle.mesh))
+        return fail("-solid=0:... and -obstacle / -obstaclemesh both address slot 0: give the solid through one of them\n");
+    return true;
+}
+
 bool parse_emit_drain(const Args& a, Options& o) {
     if (const char* v = a.value("emit")) {
         auto& e = o.emit;
@@ -335,6 +414,8 @@ bool parse_slabs(const Args& a, Options& o) {
         {!o.obstacle.shapes.empty(), "-obstacle is", "sph_obstacle_build works on a whole-domain context (the slab step makes several force launches per step); "
                                                      "run it on one device"},
         {o.obstacle.mesh != nullptr, "-obstaclemesh is", "sph_obstacle_build_obj works on a whole-domain context; run it on one device"},
+        {o.solids(), "-solid is", "sph_obstacle_select works on a whole-domain context (the slab step makes several force launches per step); "
+                                  "run it on one device"},
     };
     for (const auto& rule : one_device_only)
         if (rule.given) return fail("%s not supported with -gpus=%d%s: %s\n", rule.what, s.gpus, s.gpus == 1 ? " -slab" : "", rule.reason);
@@ -359,7 +440,7 @@ bool parse_options(int argc, char** argv, Options& o) {
     const Args a{argc, argv};
     if (!parse_run(a, o)) return false;
     if (o.run.help) return true;
-    if (!(parse_collider(a, o) && parse_obstacles(a, o) && parse_collider_mass(a, o) && parse_emit_drain(a, o) && parse_frames(a, o) &&
+    if (!(parse_collider(a, o) && parse_obstacles(a, o) && parse_solids(a, o) && parse_collider_mass(a, o) && parse_emit_drain(a, o) && parse_frames(a, o) &&
           parse_mesh(a, o) && parse_add_sphere(a, o) && parse_slabs(a, o)))
         return false;
     // -logstyle=oscar: the line form of the reference's committed logs (benchmarks/oscar/); default: what its source writes (particleSystem.cpp:703-714)
@@ -401,6 +482,19 @@ void print_help() {
            "<dir>/mesh_NNNNN.obj (Wavefront OBJ), NNNNN = the 0-based number of the update the mesh follows; -meshcell the lattice spacing (default: the particle "
            "radius), -meshradius each particle's reach (default three spacings, at most eight), -iso the level of the surface (default 0.5); independent of -frames; one "
            "device only\n");
+}
+
+// -solidhelp: the options of the obstacle slots (the text of -help is that of the releases before them)
+void print_solid_help() {
+    printf("usage: sph_headless ... [-solid=<k>:<shape> ...] [-solid=<k>:[!]mesh:<file.obj>] [-solidcell=<k>:<s>] [-solidband=<k>:<N>] "
+           "[-solidvel=<k>:<ux>,<uy>,<uz>] [-solidspin=<k>:<px>,<py>,<pz>,<wx>,<wy>,<wz>]\n"
+           "  A context holds %d obstacle slots, k = 0..%d; after every update the installed slots push the fluid in ascending order of k, in one pass.\n"
+           "  -solid: a solid in slot k, with the shapes of -obstacle (several with one k form a union) or a closed triangle mesh ([!]mesh:, `!`: the fluid is inside "
+           "it); repeatable\n"
+           "  -solidcell / -solidband / -solidvel: the grid spacing, the mesh's band and the uniform velocity of slot k, as -obstaclecell / -obstacleband / -obstaclevel\n"
+           "  -solidspin: slot k turns about the pivot (px, py, pz) with the angular velocity (wx, wy, wz), from the identity pose, and its load sensor is on\n"
+           "  The -obstacle family addresses slot 0: a slot 0 given through both is refused.  At the end every installed slot prints its offset, its quaternion and the "
+           "momentum J and angular momentum L it took in the last update.  One device only.\n", SPH_MAX_OBSTACLES, SPH_MAX_OBSTACLES - 1);
 }
 
 // the reference's line (particles.cpp:191-192), then the same as JSON; `more` goes on inside the JSON object
@@ -770,6 +864,26 @@ bool set_up(const Options& o, Run& run) {
         printf("obstacle mesh: %llu triangles used, %llu skipped, %llu lost crossings, %llu odd columns\n", (unsigned long long)ms[0],
                (unsigned long long)ms[1], (unsigned long long)ms[2], (unsigned long long)ms[3]);
     }
+    for (uint k = 0; k < (uint)SPH_MAX_OBSTACLES; k++) {       // the slots of -solid=<k>:..., each as the -obstacle family sets slot 0
+        const auto& s = o.solid[k];
+        if (!s.given) continue;
+        ps->selectObstacle(k);
+        if (!s.shapes.empty()) ps->setObstacles(s.shapes.data(), (uint)s.shapes.size(), s.cell);
+        else ps->setObstacleMeshOBJ(s.mesh.c_str(), s.cell, s.band, s.invert);
+        if (s.has_velocity) ps->setObstacleMotion(nullptr, s.velocity);
+        if (s.has_spin) {
+            const float identity[4] = {1.f, 0.f, 0.f, 0.f};
+            ps->setObstaclePose(s.pivot, identity, s.omega);
+            ps->senseObstacleLoad(true);
+        }
+        if (!s.mesh.empty()) {
+            uint64_t ms[4];
+            ps->getObstacleMeshStats(ms);
+            printf("solid %u mesh: %llu triangles used, %llu skipped, %llu lost crossings, %llu odd columns\n", k, (unsigned long long)ms[0],
+                   (unsigned long long)ms[1], (unsigned long long)ms[2], (unsigned long long)ms[3]);
+        }
+    }
+    ps->selectObstacle(0);
     if (r.log) ps->setBenchmarkLog(r.log, r.logfreq, r.logstyle);
     if (const auto& f = o.frames; f.dir) {
         if (mkdir(f.dir, 0755) != 0 && errno != EEXIST) return fail("-frames=%s: cannot create the directory\n", f.dir);
@@ -848,6 +962,21 @@ bool report(const Options& o, Run& run, double secs) {
         printf("collider: centre %.9g %.9g %.9g velocity %.9g %.9g %.9g impulse %.17g %.17g %.17g\n", cc.x, cc.y, cc.z, cu.x, cu.y, cu.z,
                J[0], J[1], J[2]);
     }
+    if (o.solids()) {       // every installed slot: floats with 9, doubles with 17 digits
+        uint32_t mask = 0;
+        sph_obstacle_installed(ps->context(), &mask);
+        for (uint k = 0; k < (uint)SPH_MAX_OBSTACLES; k++) {
+            if (!(mask >> k & 1u)) continue;
+            ps->selectObstacle(k);
+            float off[3]; double q[4], J[3], L[3];
+            sph_obstacle_get(ps->context(), nullptr, off, nullptr);
+            sph_obstacle_get_pose(ps->context(), nullptr, nullptr, q, nullptr, nullptr);
+            ps->getObstacleLoad(J, L);
+            printf("solid %u: offset %.9g %.9g %.9g quaternion %.17g %.17g %.17g %.17g J %.17g %.17g %.17g L %.17g %.17g %.17g\n", k, off[0], off[1],
+                   off[2], q[0], q[1], q[2], q[3], J[0], J[1], J[2], L[0], L[1], L[2]);
+        }
+        ps->selectObstacle(0);
+    }
     if (o.mesh.dir) {       // the mesh of the final state through ParticleSystem::extractMesh: its size and an FNV-1a hash of its bytes
         std::vector<float> mp, mn; std::vector<uint32_t> mt;
         ps->extractMesh(mp, mn, mt);
@@ -900,6 +1029,7 @@ int main(int argc, char** argv) {
     Options o;
     if (!parse_options(argc, argv, o)) return EXIT_FAILURE;
     if (o.run.help) { print_help(); return 0; }
+    if (o.solidhelp) { print_solid_help(); return 0; }
     if (o.slabs.on) return run_slabs(slab_job(o), o.slabs.gpus, o.slabs.onegpu, o.run.device);
     return run_one_device(o);
 }

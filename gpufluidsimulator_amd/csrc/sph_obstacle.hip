@@ -1,6 +1,6 @@
-// sph_obstacle.hip -- solid obstacles of any shape: one grid of signed distances per whole-domain context, which the fluid
-// collides with (sph_obstacle_lattice, _build, _set_grid, _clear, _set_motion, _get, _read, _sample of include/sph_hip.h, which
-// states the rule).  The reference has no counterpart.  A grid voxelised from a triangle mesh (sph_obstacle_mesh.hip) is installed
+// sph_obstacle.hip -- solid obstacles of any shape: grids of signed distances, one per obstacle slot of a whole-domain context,
+// which the fluid collides with (sph_obstacle_lattice, _build, _set_grid, _clear, _set_motion, _get, _read, _sample, _select of
+// include/sph_hip.h, which states the rule).  The reference has no counterpart.  A grid voxelised from a triangle mesh (sph_obstacle_mesh.hip) is installed
 // through install_begin / install_finish below and is then this file's like any other.
 //
 //   k_obstacle_raster  one node per lane: the union of the analytic shapes, clamped                         (sph_obstacle_build)
@@ -9,7 +9,8 @@
 //   k_obstacle_sample  one caller point per lane: the sample rule                                           (sph_obstacle_sample)
 //   k_obstacle_push    one owned slot per lane, behind every integrate of a context with an obstacle: the push; <POSED> for a
 //                      solid that turns (sph_obstacle_set_pose), <SENSE> leaves the waves' sums of what the solid took
-//   k_obstacle_load    one block behind a sensing push: the waves' sums in a fixed order                    (sph_obstacle_get_load)
+//   k_obstacle_push_set  the same for every installed set of slots but {slot 0}: the slots in ascending order, in one launch
+//   k_obstacle_load    one block per sensing slot behind a sensing push: the waves' sums in a fixed order                    (sph_obstacle_get_load)
 //
 // The push is a pass of its own and not a fourth pack of k_force / k_integrate (sph_pairs.hip): the fused kernel sits at the edge
 // of its occupancy, and an eight-node gather in its epilogue would cost it.  Reading the integrate's STORED output is also what
@@ -274,6 +275,202 @@ __global__ __launch_bounds__(OBSTACLE_THREADS) void k_obstacle_push(float4* __re
     }
 }
 
+// ---- the push of a set of slots ---------------------------------------------------------------------------------------------------
+// Every installed set but {slot 0}: ONE launch, the installed slots in ascending order on each owned particle, slot j on what
+// slot j - 1 left (include/sph_hip.h: SEVERAL OBSTACLES).  The slots travel by value in one kernel argument and are only ever
+// indexed by the constant of an unrolled loop, so they stay in scalar registers and never reach scratch.
+//   * a lane reads its position once and one brick word per installed slot; one ballot over "any slot may touch" lets a wave that
+//     is near nothing leave after 16 + 4 K bytes per lane, a 0 mask word stored for each sensing slot;
+//   * otherwise the lane loads its velocity once and goes through the slots; a slot no lane can touch is skipped wave-uniformly;
+//   * a lane that an earlier slot moved takes the later slot's guard from where it is NOW (its first look-up is stale);
+//   * posed or not is a wave-uniform branch per slot, each side the arithmetic of k_obstacle_push<POSED> (the identity pose is
+//     not the unposed rule); the wall rule runs behind the iterations of every slot that hit, as in a pass of its own;
+//   * a sensing slot's six lane sums are reduced in ascending lane order and stored right behind its iterations;
+//   * position, velocity, by-index row, key and the marks' fix-up (with the union of the hits) are stored once, at the end.
+constexpr uint32_t OB_SLOT_INSTALLED = 1u, OB_SLOT_POSED = 2u, OB_SLOT_SENSE = 4u;
+struct ObstacleSlot {
+    ObstacleArgs A;
+    ObstaclePose X;
+    uint32_t flags;
+};
+struct ObstacleSet { ObstacleSlot s[SPH_MAX_OBSTACLES]; };
+static_assert(sizeof(ObstacleSet) <= 1024, "the slots are one kernel argument");
+
+// the guard of one slot at (x, y, z): inside the grid and the brick's minimum under eps + 0.25 s
+template <bool POSED>
+__device__ __forceinline__ bool ob_slot_may(const ObstacleSlot& S, float guard, float x, float y, float z) {
+    uint32_t ci[3];
+    float cf[3], d[3];
+    if (!ob_locate_at<POSED>(S.A, S.X, x, y, z, ci, cf, d)) return false;
+    const uint32_t b = ((ci[2] >> OBSTACLE_BRICK_SH) * S.A.nb[1] + (ci[1] >> OBSTACLE_BRICK_SH)) * S.A.nb[0] + (ci[0] >> OBSTACLE_BRICK_SH);
+    return S.A.brick[b] < guard;
+}
+
+// the iterations of one slot on the lanes with `may`, as k_obstacle_push<POSED, .> writes them (its first iteration reuses the
+// guard's cell; locating again at the same position gives the same cell).  true: the slot hit the lane
+template <bool POSED, bool SENSE>
+__device__ __forceinline__ bool ob_slot_iterate(const ObstacleSlot& S, const Phys& ph, bool may, bool sense, float4& pi, float4& vi,
+                                                double acc[6], bool& kicked) {
+#pragma clang fp contract(off)
+    const ObstacleArgs& A = S.A;
+    const ObstaclePose& X = S.X;
+    const float eps = ph.wall_eps;
+    bool hit = false;
+    if (may) {
+        for (int it = 0; it < SPH_OBSTACLE_PUSH_ITERATIONS; it++) {
+            uint32_t ci[3];
+            float cf[3], d[3];
+            if (!ob_locate_at<POSED>(A, X, pi.x, pi.y, pi.z, ci, cf, d)) break;
+            float phi, nx, ny, nz;
+            ob_sample_cell(A, ci, cf, phi, nx, ny, nz);
+            if (!(phi < eps)) break;
+            if constexpr (SENSE && !POSED) { d[0] = pi.x - A.off[0]; d[1] = pi.y - A.off[1]; d[2] = pi.z - A.off[2]; }
+            float us0 = A.u[0], us1 = A.u[1], us2 = A.u[2];
+            if constexpr (POSED) {
+                ob_world_normal(X, nx, ny, nz);
+                us0 = A.u[0] + (X.omega[1] * d[2] - X.omega[2] * d[1]);
+                us1 = A.u[1] + (X.omega[2] * d[0] - X.omega[0] * d[2]);
+                us2 = A.u[2] + (X.omega[0] * d[1] - X.omega[1] * d[0]);
+            }
+            const float wn = ((vi.x - us0) * nx + (vi.y - us1) * ny) + (vi.z - us2) * nz;
+            if (wn < 0.f) {
+                const float k = (ph.wall_damping - 1.f) * wn;
+                const float kx = k * nx, ky = k * ny, kz = k * nz;
+                vi.x = vi.x + kx; vi.y = vi.y + ky; vi.z = vi.z + kz;
+                if constexpr (SENSE) {
+                    if (sense) {                                         // wave-uniform
+                        const float t0 = -(ph.mass * kx), t1 = -(ph.mass * ky), t2 = -(ph.mass * kz);
+                        acc[0] = acc[0] + (double)t0; acc[1] = acc[1] + (double)t1; acc[2] = acc[2] + (double)t2;
+                        acc[3] = acc[3] + ((double)d[1] * (double)t2 - (double)d[2] * (double)t1);
+                        acc[4] = acc[4] + ((double)d[2] * (double)t0 - (double)d[0] * (double)t2);
+                        acc[5] = acc[5] + ((double)d[0] * (double)t1 - (double)d[1] * (double)t0);
+                        kicked = true;
+                    }
+                }
+            }
+            const float t = eps - phi;
+            pi.x = pi.x + t * nx; pi.y = pi.y + t * ny; pi.z = pi.z + t * nz;
+            hit = true;
+        }
+    }
+    return hit;
+}
+
+template <bool SENSE>
+__global__ __launch_bounds__(OBSTACLE_THREADS) void k_obstacle_push_set(float4* __restrict__ posi, float4* __restrict__ velr,
+                                                                        float4* __restrict__ pos_by_index,
+                                                                        uint32_t* __restrict__ keys_out,
+                                                                        const uint32_t* __restrict__ keyS,
+                                                                        uint64_t* __restrict__ mm_mask,
+                                                                        uint32_t* __restrict__ mm_tile_cnt, uint32_t lo, uint32_t n,
+                                                                        GridDesc g, Phys ph, ObstacleSet set) {
+#pragma clang fp contract(off)
+    const uint32_t rel = blockIdx.x * OBSTACLE_THREADS + threadIdx.x;
+    const bool active = rel < n;
+    const uint32_t slot = lo + (active ? rel : n - 1u);
+    float4 pi = posi[slot];
+    const float eps = ph.wall_eps;
+    bool may[SPH_MAX_OBSTACLES];
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < SPH_MAX_OBSTACLES; k++) {
+        const ObstacleSlot& S = set.s[k];
+        may[k] = false;
+        if (S.flags & OB_SLOT_INSTALLED) {                               // kernel-uniform
+            const float guard = eps + 0.25f * S.A.s;
+            if (active)
+                may[k] = (S.flags & OB_SLOT_POSED) ? ob_slot_may<true>(S, guard, pi.x, pi.y, pi.z)
+                                                   : ob_slot_may<false>(S, guard, pi.x, pi.y, pi.z);
+        }
+        any = any || may[k];
+    }
+    [[maybe_unused]] const bool row_owner = active && (threadIdx.x & 63u) == 0u;     // (lane 0 of a wave that owns a slot)
+    if (__ballot(any) == 0ull) {                                         // wave-uniform: nearly every wave
+        if constexpr (SENSE) {
+            if (row_owner) {
+#pragma unroll
+                for (int k = 0; k < SPH_MAX_OBSTACLES; k++)
+                    if ((set.s[k].flags & (OB_SLOT_INSTALLED | OB_SLOT_SENSE)) == (OB_SLOT_INSTALLED | OB_SLOT_SENSE))
+                        set.s[k].X.mask[rel >> 6] = 0u;
+            }
+        }
+        return;
+    }
+    float4 vi = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (any) vi = velr[slot];
+    bool hit = false;                                                    // the union over the slots: the lane has moved
+#pragma unroll
+    for (int k = 0; k < SPH_MAX_OBSTACLES; k++) {
+        const ObstacleSlot& S = set.s[k];
+        if (!(S.flags & OB_SLOT_INSTALLED)) continue;                    // kernel-uniform
+        const bool posed = (S.flags & OB_SLOT_POSED) != 0u;
+        [[maybe_unused]] const bool sense = (S.flags & OB_SLOT_SENSE) != 0u;
+        bool m = may[k];
+        if (hit) {                                                       // moved by an earlier slot: the guard from where it is now
+            const float guard = eps + 0.25f * S.A.s;
+            m = posed ? ob_slot_may<true>(S, guard, pi.x, pi.y, pi.z) : ob_slot_may<false>(S, guard, pi.x, pi.y, pi.z);
+        }
+        if (__ballot(m) == 0ull) {                                       // wave-uniform: no lane can touch this slot
+            if constexpr (SENSE) { if (sense && row_owner) S.X.mask[rel >> 6] = 0u; }
+            continue;
+        }
+        [[maybe_unused]] double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        [[maybe_unused]] bool kicked = false;
+        const bool h = posed ? ob_slot_iterate<true, SENSE>(S, ph, m, sense, pi, vi, acc, kicked)
+                             : ob_slot_iterate<false, SENSE>(S, ph, m, sense, pi, vi, acc, kicked);
+        if constexpr (SENSE) {
+            if (sense) {                                                 // kernel-uniform
+                const uint64_t km = __ballot(kicked);
+                if (km != 0ull) {                                        // wave-uniform
+                    double sum[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+                    for (uint64_t q = km; q != 0ull; q &= q - 1ull) {
+                        const uint32_t l = (uint32_t)__builtin_ctzll(q);
+#pragma unroll
+                        for (int a = 0; a < 6; a++) sum[a] = sum[a] + lane_value_f64(acc[a], l);
+                    }
+                    if (row_owner) {
+                        double* row = S.X.rows + (size_t)(rel >> 6) * 6u;
+#pragma unroll
+                        for (int a = 0; a < 6; a++) row[a] = sum[a];
+                    }
+                }
+                if (row_owner) S.X.mask[rel >> 6] = km != 0ull ? 1u : 0u;
+            }
+        }
+        if (h) {
+            wall(pi.x, vi.x, ph.box_min[0], ph.box_max[0], eps, ph.wall_damping);
+            wall(pi.y, vi.y, ph.box_min[1], ph.box_max[1], eps, ph.wall_damping);
+            wall(pi.z, vi.z, ph.box_min[2], ph.box_max[2], eps, ph.wall_damping);
+            hit = true;
+        }
+    }
+    bool moved = false;
+    if (hit) {
+        posi[slot] = pi;
+        velr[slot] = vi;
+        pos_by_index[__float_as_uint(pi.w)] = make_float4(pi.x, pi.y, pi.z, 1.0f);
+        if (keys_out) {
+            const uint32_t key = cell_key(g, pi.x, pi.y, pi.z);
+            keys_out[rel] = key;
+            moved = key != keyS[slot];
+        }
+    }
+    if (mm_mask) {
+        const uint64_t hm = __ballot(hit);
+        if (hm != 0ull) {                                                // wave-uniform
+            const uint64_t mv = __ballot(moved);                         // (a subset of hm)
+            if ((threadIdx.x & 63u) == 0u) {                             // (lane 0 of a wave that got here owns a slot)
+                const uint32_t chunk = rel >> 6;
+                const uint64_t old = mm_mask[chunk], now = (old & ~hm) | mv;
+                if (now != old) {
+                    mm_mask[chunk] = now;
+                    atomicAdd(&mm_tile_cnt[chunk / MM_TILE_CHUNKS], (uint32_t)__popcll(now) - (uint32_t)__popcll(old));
+                }
+            }
+        }
+    }
+}
+
 // ---- the load: the waves' rows added in a fixed order (sph_obstacle_get_load) ----------------------------------------------------
 // One block, once per integrate of a sensing context, behind the push.  The order is k_spheres_step's (sph_pairs.hip): thread t
 // takes the waves [t K, (t + 1) K), K = ceil(waves / 256) rounded up to a multiple of 4, and adds the rows the masks point to
@@ -406,18 +603,18 @@ __global__ __launch_bounds__(OBSTACLE_THREADS) void k_obstacle_bricks(ObstacleAr
 
 static uint32_t ob_bricks_axis(uint32_t n) { return ceil_div(n - 1u, OBSTACLE_BRICK); }
 
-static ObstacleArgs obstacle_args(const sph_ctx* c) {
+static ObstacleArgs obstacle_args(const Obstacle& o) {
     ObstacleArgs A{};
-    A.phi = c->ob_phi;
-    A.brick = c->ob_brick;
-    A.s = c->ob_grid.spacing;
+    A.phi = o.phi;
+    A.brick = o.brick;
+    A.s = o.grid.spacing;
     for (int k = 0; k < 3; k++) {
-        A.origin[k] = c->ob_grid.origin[k];
-        A.n[k] = c->ob_grid.dims[k];
+        A.origin[k] = o.grid.origin[k];
+        A.n[k] = o.grid.dims[k];
         A.nm1[k] = (float)(A.n[k] - 1u);
         A.nb[k] = ob_bricks_axis(A.n[k]);
-        A.off[k] = c->ob_off[k];
-        A.u[k] = c->ob_vel[k];
+        A.off[k] = o.off[k];
+        A.u[k] = o.vel[k];
     }
     return A;
 }
@@ -446,62 +643,99 @@ static bool ob_quat_unit(const double in[4], double out[4]) {
     return true;
 }
 
-static ObstaclePose obstacle_pose(const sph_ctx* c) {
+static ObstaclePose obstacle_pose(const Obstacle& o) {
 #pragma clang fp contract(off)
     ObstaclePose X{};
-    if (c->ob_posed) ob_rot_of(c->ob_quat, X.rot);
+    if (o.posed) ob_rot_of(o.quat, X.rot);
     for (int k = 0; k < 3; k++) {
-        X.pivot[k] = c->ob_posed ? c->ob_pivot[k] : 0.f;
-        X.P[k] = c->ob_posed ? c->ob_pivot[k] + c->ob_off[k] : c->ob_off[k];
-        X.omega[k] = c->ob_posed ? c->ob_omega[k] : 0.f;
+        X.pivot[k] = o.posed ? o.pivot[k] : 0.f;
+        X.P[k] = o.posed ? o.pivot[k] + o.off[k] : o.off[k];
+        X.omega[k] = o.posed ? o.omega[k] : 0.f;
     }
-    X.rows = c->ob_rows;
-    X.mask = c->ob_wmask;
+    X.rows = o.rows;
+    X.mask = o.wmask;
     return X;
 }
 
+static ObstacleSet obstacle_set(const sph_ctx* c) {
+    ObstacleSet S{};
+    for (uint32_t k = 0; k < (uint32_t)SPH_MAX_OBSTACLES; k++) {
+        const Obstacle& o = c->ob[k];
+        if (!o.installed()) continue;
+        S.s[k].A = obstacle_args(o);
+        S.s[k].X = obstacle_pose(o);
+        S.s[k].flags = OB_SLOT_INSTALLED | (o.posed ? OB_SLOT_POSED : 0u) | (o.sense && o.load ? OB_SLOT_SENSE : 0u);
+    }
+    return S;
+}
+
+// The installed set {slot 0} is the library of one obstacle: k_obstacle_push with its arguments.  Every other set: one launch of
+// k_obstacle_push_set.
 int launch_obstacle_push(sph_ctx* c, bool fused, bool mark) {
     if (c->n == 0) return SPH_OK;
+    bool others = false, any_sense = false;
+    for (uint32_t k = 0; k < (uint32_t)SPH_MAX_OBSTACLES; k++) {
+        const Obstacle& o = c->ob[k];
+        if (!o.installed()) continue;
+        others = others || k != 0u;
+        any_sense = any_sense || (o.sense && o.load);
+    }
+#define SPH_PUSH_ARGS                                                                                                            \
+    fused ? c->posi2 : c->posi, fused ? c->velr2 : c->velr, c->pos_out, fused ? c->k0 : nullptr, c->keyS,                          \
+        fused && mark ? c->mm_mask : nullptr, c->mm_tile_cnt, c->own_off, c->n
+    if (others) {
+        const ObstacleSet S = obstacle_set(c);
+        if (any_sense)
+            hipLaunchKernelGGL(k_obstacle_push_set<true>, dim3(ceil_div(c->n, OBSTACLE_THREADS)), dim3(OBSTACLE_THREADS), 0, c->stream,
+                               SPH_PUSH_ARGS, c->grid, c->phys, S);
+        else
+            hipLaunchKernelGGL(k_obstacle_push_set<false>, dim3(ceil_div(c->n, OBSTACLE_THREADS)), dim3(OBSTACLE_THREADS), 0, c->stream,
+                               SPH_PUSH_ARGS, c->grid, c->phys, S);
+        SPH_HIP(hipGetLastError());
+        return SPH_OK;
+    }
+    const Obstacle& o = c->ob[0];
 #define SPH_LAUNCH_PUSH(P, S)                                                                                                    \
     hipLaunchKernelGGL((k_obstacle_push<P, S>), dim3(ceil_div(c->n, OBSTACLE_THREADS)), dim3(OBSTACLE_THREADS), 0, c->stream,      \
-                       fused ? c->posi2 : c->posi, fused ? c->velr2 : c->velr, c->pos_out, fused ? c->k0 : nullptr, c->keyS,       \
-                       fused && mark ? c->mm_mask : nullptr, c->mm_tile_cnt, c->own_off, c->n, obstacle_args(c), c->grid, c->phys, \
-                       obstacle_pose(c))
-    const bool sense = c->ob_sense && c->ob_load;
-    if (c->ob_posed) { if (sense) SPH_LAUNCH_PUSH(true, true); else SPH_LAUNCH_PUSH(true, false); }
-    else { if (sense) SPH_LAUNCH_PUSH(false, true); else SPH_LAUNCH_PUSH(false, false); }
+                       SPH_PUSH_ARGS, obstacle_args(o), c->grid, c->phys, obstacle_pose(o))
+    if (o.posed) { if (any_sense) SPH_LAUNCH_PUSH(true, true); else SPH_LAUNCH_PUSH(true, false); }
+    else { if (any_sense) SPH_LAUNCH_PUSH(false, true); else SPH_LAUNCH_PUSH(false, false); }
 #undef SPH_LAUNCH_PUSH
+#undef SPH_PUSH_ARGS
     SPH_HIP(hipGetLastError());
     return SPH_OK;
 }
 
-// Once per integrate, behind the push (sph_pairs.hip: advance_colliders).  A sensing context queues the load's sum first -- with
-// the P the push just used, and also without particles (no push ran: zeros) --, then offset and pose move on by dt.
+// Once per integrate, behind the push (sph_pairs.hip: advance_colliders), slot by slot.  A sensing slot queues its load's sum
+// first -- with the P the push just used, and also without particles (no push ran: zeros) --, then its offset and pose move on
+// by dt.
 int advance_obstacle(sph_ctx* c, float dt) {
 #pragma clang fp contract(off)
-    if (!have_obstacle(c)) return SPH_OK;
-    if (c->ob_sense && c->ob_load) {
-        const ObstaclePose X = obstacle_pose(c);
-        hipLaunchKernelGGL(k_obstacle_load, dim3(1), dim3(OBSTACLE_LOAD_THREADS), 0, c->stream, c->ob_rows, c->ob_wmask,
-                           ceil_div(c->n, (uint32_t)WAVE), c->ob_load, ObstacleAbout{{X.P[0], X.P[1], X.P[2]}});
-        SPH_HIP(hipGetLastError());
-    }
-    for (int k = 0; k < 3; k++) c->ob_off[k] = c->ob_off[k] + dt * c->ob_vel[k];
-    if (c->ob_posed) {                                  // the Cayley step of the header, float64
-        const double w = c->ob_quat[0], x = c->ob_quat[1], y = c->ob_quat[2], z = c->ob_quat[3];
-        const double h = 0.5 * (double)dt;
-        const double a0 = h * (double)c->ob_omega[0], a1 = h * (double)c->ob_omega[1], a2 = h * (double)c->ob_omega[2];
-        const double q[4] = {((w - a0 * x) - a1 * y) - a2 * z, ((x + a0 * w) + a1 * z) - a2 * y, ((y + a1 * w) + a2 * x) - a0 * z,
-                             ((z + a2 * w) + a0 * y) - a1 * x};
-        ob_quat_unit(q, c->ob_quat);                    // (|q'|^2 = 1 + |a|^2 >= 1; if it is not finite the pose stays)
+    for (Obstacle& o : c->ob) {
+        if (!o.installed()) continue;
+        if (o.sense && o.load) {
+            const ObstaclePose X = obstacle_pose(o);
+            hipLaunchKernelGGL(k_obstacle_load, dim3(1), dim3(OBSTACLE_LOAD_THREADS), 0, c->stream, o.rows, o.wmask,
+                               ceil_div(c->n, (uint32_t)WAVE), o.load, ObstacleAbout{{X.P[0], X.P[1], X.P[2]}});
+            SPH_HIP(hipGetLastError());
+        }
+        for (int k = 0; k < 3; k++) o.off[k] = o.off[k] + dt * o.vel[k];
+        if (o.posed) {                                  // the Cayley step of the header, float64
+            const double w = o.quat[0], x = o.quat[1], y = o.quat[2], z = o.quat[3];
+            const double h = 0.5 * (double)dt;
+            const double a0 = h * (double)o.omega[0], a1 = h * (double)o.omega[1], a2 = h * (double)o.omega[2];
+            const double q[4] = {((w - a0 * x) - a1 * y) - a2 * z, ((x + a0 * w) + a1 * z) - a2 * y, ((y + a1 * w) + a2 * x) - a0 * z,
+                                 ((z + a2 * w) + a0 * y) - a1 * x};
+            ob_quat_unit(q, o.quat);                    // (|q'|^2 = 1 + |a|^2 >= 1; if it is not finite the pose stays)
+        }
     }
     return SPH_OK;
 }
 
-static void pose_reset(sph_ctx* c) {
-    c->ob_posed = false;
-    for (int k = 0; k < 3; k++) c->ob_pivot[k] = c->ob_omega[k] = 0.f;
-    c->ob_quat[0] = 1.0; c->ob_quat[1] = c->ob_quat[2] = c->ob_quat[3] = 0.0;
+static void pose_reset(Obstacle& o) {
+    o.posed = false;
+    for (int k = 0; k < 3; k++) o.pivot[k] = o.omega[k] = 0.f;
+    o.quat[0] = 1.0; o.quat[1] = o.quat[2] = o.quat[3] = 0.0;
 }
 
 // The sensor's buffers, by capacity (the first sph_obstacle_set_sensor(on)): one row of six sums and one mask word per wave of
@@ -510,22 +744,23 @@ static void pose_reset(sph_ctx* c) {
 // front of it.  All three or none: ob_load doubles as "the buffers are there".
 constexpr size_t OBSTACLE_LOAD_WORDS = 9;        // J[3], L[3], the count, about[3] (fp32) + a pad word: 72 bytes
 constexpr size_t OBSTACLE_MASK_QUAD = 4;
-static int sensor_buffers_alloc(sph_ctx* c) {
+static int sensor_buffers_alloc(sph_ctx* c, Obstacle& o) {
     Buffers& m = c->mem;
     const size_t waves = ceil_div(c->cap, (uint32_t)WAVE);
-    int rc = m.alloc(&c->ob_rows, waves * 6, false);
-    if (!rc) rc = m.alloc(&c->ob_wmask, ((waves + OBSTACLE_MASK_QUAD - 1) & ~(OBSTACLE_MASK_QUAD - 1)) + OBSTACLE_MASK_QUAD, false);
-    if (!rc) rc = m.alloc(&c->ob_load, OBSTACLE_LOAD_WORDS, true);
-    if (rc) { m.release(&c->ob_load); m.release(&c->ob_wmask); m.release(&c->ob_rows); }
+    int rc = m.alloc(&o.rows, waves * 6, false);
+    if (!rc) rc = m.alloc(&o.wmask, ((waves + OBSTACLE_MASK_QUAD - 1) & ~(OBSTACLE_MASK_QUAD - 1)) + OBSTACLE_MASK_QUAD, false);
+    if (!rc) rc = m.alloc(&o.load, OBSTACLE_LOAD_WORDS, true);
+    if (rc) { m.release(&o.load); m.release(&o.wmask); m.release(&o.rows); }
     return rc;
 }
 
 void release_obstacle(sph_ctx* c) {
-    c->mem.release(&c->ob_mesh_marks);
-    c->mem.release(&c->ob_mesh_work);
-    c->mem.release(&c->ob_brick);
-    c->mem.release(&c->ob_phi);
-    c->ob_grid = sph_obstacle_grid{};
+    Obstacle& o = selected_obstacle(c);
+    c->mem.release(&o.mesh_marks);
+    c->mem.release(&o.mesh_work);
+    c->mem.release(&o.brick);
+    c->mem.release(&o.phi);
+    o.grid = sph_obstacle_grid{};
 }
 
 static int check_grid(const sph_obstacle_grid& G) {
@@ -615,23 +850,25 @@ int obstacle_ctx(const sph_ctx* c, const char* who) {
 // On failure there is no obstacle.
 int install_begin(sph_ctx* c, const sph_obstacle_grid& G) {
     SPH_HIP(hipSetDevice(c->device));
-    if (have_obstacle(c)) {
+    Obstacle& o = selected_obstacle(c);
+    if (o.installed()) {
         SPH_HIP(hipStreamSynchronize(c->stream));          // (a push of the old grid may still be running)
         release_obstacle(c);
     }
     const size_t nodes = (size_t)G.dims[0] * G.dims[1] * G.dims[2];
     const size_t bricks = (size_t)ob_bricks_axis(G.dims[0]) * ob_bricks_axis(G.dims[1]) * ob_bricks_axis(G.dims[2]);
-    int rc = c->mem.alloc(&c->ob_phi, nodes, false);
-    if (!rc) rc = c->mem.alloc(&c->ob_brick, bricks, false);
+    int rc = c->mem.alloc(&o.phi, nodes, false);
+    if (!rc) rc = c->mem.alloc(&o.brick, bricks, false);
     if (rc) { release_obstacle(c); return rc; }
-    c->ob_grid = G;
+    o.grid = G;
     return SPH_OK;
 }
 
 int install_finish(sph_ctx* c) {
-    const ObstacleArgs A = obstacle_args(c);
+    const Obstacle& o = selected_obstacle(c);
+    const ObstacleArgs A = obstacle_args(o);
     const uint32_t bricks = A.nb[0] * A.nb[1] * A.nb[2];
-    hipLaunchKernelGGL(k_obstacle_bricks, dim3(ceil_div(bricks, OBSTACLE_THREADS)), dim3(OBSTACLE_THREADS), 0, c->stream, A, c->ob_brick,
+    hipLaunchKernelGGL(k_obstacle_bricks, dim3(ceil_div(bricks, OBSTACLE_THREADS)), dim3(OBSTACLE_THREADS), 0, c->stream, A, o.brick,
                        bricks);
     SPH_HIP(hipGetLastError());
     return SPH_OK;
@@ -656,8 +893,9 @@ int sph_obstacle_build(sph_ctx* c, float spacing, const float lo[3], const float
     if (int e = check_shapes(n, shapes, &sh)) return e;
     if (int e = install_begin(c, G)) return e;
     const uint32_t nodes = G.dims[0] * G.dims[1] * G.dims[2];
-    hipLaunchKernelGGL(k_obstacle_raster, dim3(ceil_div(nodes, OBSTACLE_THREADS)), dim3(OBSTACLE_THREADS), 0, c->stream, c->ob_phi, nodes,
-                       obstacle_args(c), sh, ob_clamp_distance(G));
+    const Obstacle& o = selected_obstacle(c);
+    hipLaunchKernelGGL(k_obstacle_raster, dim3(ceil_div(nodes, OBSTACLE_THREADS)), dim3(OBSTACLE_THREADS), 0, c->stream, o.phi, nodes,
+                       obstacle_args(o), sh, ob_clamp_distance(G));
     SPH_HIP(hipGetLastError());
     return install_finish(c);
 }
@@ -671,10 +909,11 @@ int sph_obstacle_set_grid(sph_ctx* c, const sph_obstacle_grid* grid, const float
     for (size_t i = 0; i < nodes; i++)
         SPH_REQUIRE(std::isfinite(phi[i]), SPH_E_INVALID, "obstacle grid: phi[%zu] is not finite", i);
     if (int e = install_begin(c, G)) return e;
-    hipError_t he = hipMemcpyAsync(c->ob_phi, phi, nodes * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    Obstacle& o = selected_obstacle(c);
+    hipError_t he = hipMemcpyAsync(o.phi, phi, nodes * sizeof(float), hipMemcpyHostToDevice, c->stream);
     if (he == hipSuccess) {
         hipLaunchKernelGGL(k_obstacle_clamp, dim3(ceil_div((uint32_t)nodes, OBSTACLE_THREADS)), dim3(OBSTACLE_THREADS), 0, c->stream,
-                           c->ob_phi, (uint32_t)nodes, ob_clamp_distance(G));
+                           o.phi, (uint32_t)nodes, ob_clamp_distance(G));
         he = hipGetLastError();
     }
     int rc = he == hipSuccess ? install_finish(c) : hip_fail(he, "obstacle upload", __FILE__, __LINE__);
@@ -688,23 +927,25 @@ int sph_obstacle_set_grid(sph_ctx* c, const sph_obstacle_grid* grid, const float
 
 int sph_obstacle_clear(sph_ctx* c) {
     if (int e = obstacle_ctx(c, "sph_obstacle_clear")) return e;
-    if (have_obstacle(c)) {
+    Obstacle& o = selected_obstacle(c);
+    if (o.installed()) {                                   // (only then: the other slots' pushes do not read this one)
         SPH_HIP(hipSetDevice(c->device));
         SPH_HIP(hipStreamSynchronize(c->stream));
         release_obstacle(c);
     }
-    for (int k = 0; k < 3; k++) c->ob_off[k] = c->ob_vel[k] = 0.f;
-    pose_reset(c);
-    if (c->ob_load) {                                      // (the sensor's switch stays; its sums and the integrate count start again)
+    for (int k = 0; k < 3; k++) o.off[k] = o.vel[k] = 0.f;
+    pose_reset(o);
+    if (o.load) {                                          // (the sensor's switch stays; its sums and the integrate count start again)
         SPH_HIP(hipSetDevice(c->device));
-        SPH_HIP(hipMemsetAsync(c->ob_load, 0, OBSTACLE_LOAD_WORDS * sizeof(double), c->stream));
+        SPH_HIP(hipMemsetAsync(o.load, 0, OBSTACLE_LOAD_WORDS * sizeof(double), c->stream));
     }
     return SPH_OK;
 }
 
 int sph_obstacle_set_pose(sph_ctx* c, const sph_obstacle_pose* pose) {
     if (int e = obstacle_ctx(c, "sph_obstacle_set_pose")) return e;
-    if (!pose) { pose_reset(c); return SPH_OK; }
+    Obstacle& o = selected_obstacle(c);
+    if (!pose) { pose_reset(o); return SPH_OK; }
     const sph_obstacle_pose p = *pose;
     for (int k = 0; k < 3; k++)
         SPH_REQUIRE(std::isfinite(p.pivot[k]) && std::isfinite(p.omega[k]), SPH_E_INVALID, "obstacle pose: pivot or omega is not finite");
@@ -712,40 +953,43 @@ int sph_obstacle_set_pose(sph_ctx* c, const sph_obstacle_pose* pose) {
     const double q[4] = {(double)p.quat[0], (double)p.quat[1], (double)p.quat[2], (double)p.quat[3]};
     double unit[4];
     SPH_REQUIRE(ob_quat_unit(q, unit), SPH_E_INVALID, "obstacle pose: the quaternion's squared norm is 0 or not finite");
-    c->ob_posed = true;
-    for (int k = 0; k < 3; k++) { c->ob_pivot[k] = p.pivot[k]; c->ob_omega[k] = p.omega[k]; }
-    for (int k = 0; k < 4; k++) c->ob_quat[k] = unit[k];
+    o.posed = true;
+    for (int k = 0; k < 3; k++) { o.pivot[k] = p.pivot[k]; o.omega[k] = p.omega[k]; }
+    for (int k = 0; k < 4; k++) o.quat[k] = unit[k];
     return SPH_OK;
 }
 
 int sph_obstacle_get_pose(const sph_ctx* c, int* posed, float pivot[3], double quat[4], float omega[3], float rot[9]) {
     SPH_REQUIRE(c, SPH_E_INVALID, "null context");
-    if (posed) *posed = c->ob_posed ? 1 : 0;
+    const Obstacle& o = selected_obstacle(c);
+    if (posed) *posed = o.posed ? 1 : 0;
     for (int k = 0; k < 3; k++) {
-        if (pivot) pivot[k] = c->ob_pivot[k];
-        if (omega) omega[k] = c->ob_omega[k];
+        if (pivot) pivot[k] = o.pivot[k];
+        if (omega) omega[k] = o.omega[k];
     }
-    if (quat) for (int k = 0; k < 4; k++) quat[k] = c->ob_quat[k];
-    if (rot) ob_rot_of(c->ob_quat, rot);
+    if (quat) for (int k = 0; k < 4; k++) quat[k] = o.quat[k];
+    if (rot) ob_rot_of(o.quat, rot);
     return SPH_OK;
 }
 
 int sph_obstacle_set_sensor(sph_ctx* c, int on) {
     if (int e = obstacle_ctx(c, "sph_obstacle_set_sensor")) return e;
-    if (on && !c->ob_load) {
+    Obstacle& o = selected_obstacle(c);
+    if (on && !o.load) {
         SPH_HIP(hipSetDevice(c->device));
-        if (int rc = sensor_buffers_alloc(c)) return rc;
+        if (int rc = sensor_buffers_alloc(c, o)) return rc;
     }
-    c->ob_sense = on != 0;
+    o.sense = on != 0;
     return SPH_OK;
 }
 
 int sph_obstacle_get_load(sph_ctx* c, double J[3], double L[3], float about[3], uint64_t* steps) {
     if (int e = obstacle_ctx(c, "sph_obstacle_get_load")) return e;
+    const Obstacle& o = selected_obstacle(c);
     double host[OBSTACLE_LOAD_WORDS] = {};
-    if (c->ob_load) {
+    if (o.load) {
         SPH_HIP(hipSetDevice(c->device));
-        SPH_HIP(hipMemcpyAsync(host, c->ob_load, sizeof(host), hipMemcpyDeviceToHost, c->stream));
+        SPH_HIP(hipMemcpyAsync(host, o.load, sizeof(host), hipMemcpyDeviceToHost, c->stream));
         SPH_HIP(hipStreamSynchronize(c->stream));
     }
     for (int k = 0; k < 3; k++) {
@@ -759,39 +1003,43 @@ int sph_obstacle_get_load(sph_ctx* c, double J[3], double L[3], float about[3], 
 
 int sph_obstacle_set_motion(sph_ctx* c, const float offset[3], const float velocity[3]) {
     if (int e = obstacle_ctx(c, "sph_obstacle_set_motion")) return e;
+    Obstacle& o = selected_obstacle(c);
     for (int k = 0; k < 3; k++)
         SPH_REQUIRE((!offset || std::isfinite(offset[k])) && (!velocity || std::isfinite(velocity[k])), SPH_E_INVALID,
                     "obstacle motion: offset or velocity is not finite");
     for (int k = 0; k < 3; k++) {
-        if (offset) c->ob_off[k] = offset[k];
-        if (velocity) c->ob_vel[k] = velocity[k];
+        if (offset) o.off[k] = offset[k];
+        if (velocity) o.vel[k] = velocity[k];
     }
     return SPH_OK;
 }
 
 int sph_obstacle_get(const sph_ctx* c, sph_obstacle_grid* grid, float offset[3], float velocity[3]) {
     SPH_REQUIRE(c, SPH_E_INVALID, "null context");
-    if (grid) *grid = c->ob_grid;
+    const Obstacle& o = selected_obstacle(c);
+    if (grid) *grid = o.grid;
     for (int k = 0; k < 3; k++) {
-        if (offset) offset[k] = c->ob_off[k];
-        if (velocity) velocity[k] = c->ob_vel[k];
+        if (offset) offset[k] = o.off[k];
+        if (velocity) velocity[k] = o.vel[k];
     }
     return SPH_OK;
 }
 
 int sph_obstacle_read(sph_ctx* c, float* phi) {
     SPH_REQUIRE(c && phi, SPH_E_INVALID, "null argument");
-    SPH_REQUIRE(have_obstacle(c), SPH_E_STATE, "sph_obstacle_read: no obstacle is installed");
+    const Obstacle& o = selected_obstacle(c);
+    SPH_REQUIRE(o.installed(), SPH_E_STATE, "sph_obstacle_read: no obstacle is installed");
     SPH_HIP(hipSetDevice(c->device));
-    const size_t nodes = (size_t)c->ob_grid.dims[0] * c->ob_grid.dims[1] * c->ob_grid.dims[2];
-    SPH_HIP(hipMemcpyAsync(phi, c->ob_phi, nodes * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    const size_t nodes = (size_t)o.grid.dims[0] * o.grid.dims[1] * o.grid.dims[2];
+    SPH_HIP(hipMemcpyAsync(phi, o.phi, nodes * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     SPH_HIP(hipStreamSynchronize(c->stream));
     return SPH_OK;
 }
 
 int sph_obstacle_sample(sph_ctx* c, uint32_t n, const float* pos_xyz, float* phi, float* normal_xyz, uint8_t* inside_grid) {
     SPH_REQUIRE(c, SPH_E_INVALID, "null context");
-    SPH_REQUIRE(have_obstacle(c), SPH_E_STATE, "sph_obstacle_sample: no obstacle is installed");
+    const Obstacle& o = selected_obstacle(c);
+    SPH_REQUIRE(o.installed(), SPH_E_STATE, "sph_obstacle_sample: no obstacle is installed");
     SPH_REQUIRE(n == 0 || pos_xyz, SPH_E_INVALID, "null positions");
     if (n == 0) return SPH_OK;
     SPH_HIP(hipSetDevice(c->device));
@@ -805,12 +1053,12 @@ int sph_obstacle_sample(sph_ctx* c, uint32_t n, const float* pos_xyz, float* phi
     if (!rc) {
         hip(hipMemcpyAsync(d_pos, pos_xyz, (size_t)n * 12, hipMemcpyHostToDevice, c->stream), "copy of the points");
         if (!rc) {
-            if (c->ob_posed)
+            if (o.posed)
                 hipLaunchKernelGGL(k_obstacle_sample<true>, dim3(ceil_div(n, OBSTACLE_THREADS)), dim3(OBSTACLE_THREADS), 0, c->stream,
-                                   d_pos, n, obstacle_args(c), d_phi, d_nrm, d_in, obstacle_pose(c));
+                                   d_pos, n, obstacle_args(o), d_phi, d_nrm, d_in, obstacle_pose(o));
             else
                 hipLaunchKernelGGL(k_obstacle_sample<false>, dim3(ceil_div(n, OBSTACLE_THREADS)), dim3(OBSTACLE_THREADS), 0, c->stream,
-                                   d_pos, n, obstacle_args(c), d_phi, d_nrm, d_in, obstacle_pose(c));
+                                   d_pos, n, obstacle_args(o), d_phi, d_nrm, d_in, obstacle_pose(o));
             hip(hipGetLastError(), "k_obstacle_sample");
         }
         if (!rc && phi) hip(hipMemcpyAsync(phi, d_phi, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream), "copy of phi");
@@ -820,6 +1068,36 @@ int sph_obstacle_sample(sph_ctx* c, uint32_t n, const float* pos_xyz, float* phi
         hip(e, "hipStreamSynchronize");
     }
     tmp.free_all();
+    return rc;
+}
+
+int sph_obstacle_select(sph_ctx* c, uint32_t slot) {
+    if (int e = obstacle_ctx(c, "sph_obstacle_select")) return e;
+    SPH_REQUIRE(slot < (uint32_t)SPH_MAX_OBSTACLES, SPH_E_INVALID, "obstacle slot %u: 0..%d", slot, SPH_MAX_OBSTACLES - 1);
+    c->ob_sel = slot;
+    return SPH_OK;
+}
+
+uint32_t sph_obstacle_selected(const sph_ctx* c) { return c ? c->ob_sel : 0u; }
+
+uint32_t sph_obstacle_installed(const sph_ctx* c, uint32_t* mask) {
+    uint32_t count = 0, m = 0;
+    if (c)
+        for (uint32_t k = 0; k < (uint32_t)SPH_MAX_OBSTACLES; k++)
+            if (c->ob[k].installed()) { count++; m |= 1u << k; }
+    if (mask) *mask = m;
+    return count;
+}
+
+int sph_obstacle_clear_all(sph_ctx* c) {
+    if (int e = obstacle_ctx(c, "sph_obstacle_clear_all")) return e;
+    int rc = SPH_OK;
+    for (uint32_t k = 0; k < (uint32_t)SPH_MAX_OBSTACLES; k++) {
+        c->ob_sel = k;
+        const int e = sph_obstacle_clear(c);
+        if (e && !rc) rc = e;
+    }
+    c->ob_sel = 0;
     return rc;
 }
 

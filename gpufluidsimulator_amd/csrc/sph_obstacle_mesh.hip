@@ -354,6 +354,7 @@ static int obmesh_build_dev(sph_ctx* c, const sph_obstacle_grid& G, uint32_t ban
                             uint32_t nt, const uint32_t* tri_dev) {
 #pragma clang fp contract(off)
     if (int e = install_begin(c, G)) return e;
+    Obstacle& o = selected_obstacle(c);
     ObMeshLattice L{};
     L.s = G.spacing;
     for (int k = 0; k < 3; k++) { L.origin[k] = G.origin[k]; L.n[k] = G.dims[k]; L.nm1[k] = (float)(G.dims[k] - 1u); }
@@ -361,26 +362,26 @@ static int obmesh_build_dev(sph_ctx* c, const sph_obstacle_grid& G, uint32_t ban
     L.words = ceil_div(G.dims[0] + 1u, 32u);
     const uint32_t nodes = G.dims[0] * G.dims[1] * G.dims[2];
     const size_t mark_words = (size_t)G.dims[1] * G.dims[2] * L.words;
-    int rc = c->mem.alloc(&c->ob_mesh_work, obmesh_work_words(nt), false);
-    if (!rc) rc = c->mem.alloc(&c->ob_mesh_marks, mark_words, false);
+    int rc = c->mem.alloc(&o.mesh_work, obmesh_work_words(nt), false);
+    if (!rc) rc = c->mem.alloc(&o.mesh_marks, mark_words, false);
     if (rc) { release_obstacle(c); return rc; }
-    const ObMeshWork w = obmesh_work(c->ob_mesh_work, nt);
+    const ObMeshWork w = obmesh_work(o.mesh_work, nt);
     const uint32_t nb = ceil_div(nt, OBMESH_THREADS);
     // no more workgroups than there can be tiles: a triangle's box has at most this many
     const uint64_t most = (uint64_t)nt * ceil_div(G.dims[0], WAVE) * ceil_div(G.dims[1] * G.dims[2], OBMESH_TILE_ROWS);
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(OBMESH_MAX_BLOCKS, (most + OBMESH_WAVES - 1u) / OBMESH_WAVES);
-    hipError_t he = hipMemsetD32Async((hipDeviceptr_t)c->ob_phi, 0x7F800000, nodes, c->stream);      // the bits of +inf
-    if (he == hipSuccess) he = hipMemsetAsync(c->ob_mesh_marks, 0, mark_words * sizeof(uint32_t), c->stream);
-    if (he == hipSuccess) he = hipMemsetAsync(c->ob_mesh_work, 0, OBMESH_HEAD * sizeof(uint64_t), c->stream);
+    hipError_t he = hipMemsetD32Async((hipDeviceptr_t)o.phi, 0x7F800000, nodes, c->stream);      // the bits of +inf
+    if (he == hipSuccess) he = hipMemsetAsync(o.mesh_marks, 0, mark_words * sizeof(uint32_t), c->stream);
+    if (he == hipSuccess) he = hipMemsetAsync(o.mesh_work, 0, OBMESH_HEAD * sizeof(uint64_t), c->stream);
     if (he == hipSuccess) {
         hipLaunchKernelGGL(k_obmesh_count, dim3(nb), dim3(OBMESH_THREADS), 0, c->stream, pos_dev, tri_dev, nv, nt, L, w);
         hipLaunchKernelGGL(k_obmesh_scan, dim3(1), dim3(OBMESH_SCAN2), 0, c->stream, w, nb);
         hipLaunchKernelGGL(k_obmesh_distance, dim3(blocks), dim3(OBMESH_THREADS), 0, c->stream, pos_dev, tri_dev, nv, nt, L, w,
-                           (uint32_t*)c->ob_phi);
+                           (uint32_t*)o.phi);
         hipLaunchKernelGGL(k_obmesh_cross, dim3(blocks), dim3(OBMESH_THREADS), 0, c->stream, pos_dev, tri_dev, nv, nt, L, w,
-                           c->ob_mesh_marks);
-        hipLaunchKernelGGL(k_obmesh_finish, dim3(ceil_div(nodes, OBMESH_THREADS)), dim3(OBMESH_THREADS), 0, c->stream, c->ob_phi, nodes, L,
-                           c->ob_mesh_marks, w.cnt, invert, ob_clamp_distance(G));
+                           o.mesh_marks);
+        hipLaunchKernelGGL(k_obmesh_finish, dim3(ceil_div(nodes, OBMESH_THREADS)), dim3(OBMESH_THREADS), 0, c->stream, o.phi, nodes, L,
+                           o.mesh_marks, w.cnt, invert, ob_clamp_distance(G));
         he = hipGetLastError();
     }
     rc = he == hipSuccess ? install_finish(c) : hip_fail(he, "mesh voxeliser", __FILE__, __LINE__);
@@ -499,10 +500,11 @@ int sph_obstacle_build_obj(sph_ctx* c, const sph_obstacle_mesh_params* p, const 
 
 int sph_obstacle_mesh_stats(sph_ctx* c, uint64_t out[4]) {
     SPH_REQUIRE(c && out, SPH_E_INVALID, "null argument");
-    SPH_REQUIRE(have_obstacle(c) && c->ob_mesh_work, SPH_E_STATE, "sph_obstacle_mesh_stats: the obstacle was not built from a mesh");
+    const Obstacle& o = selected_obstacle(c);
+    SPH_REQUIRE(o.installed() && o.mesh_work, SPH_E_STATE, "sph_obstacle_mesh_stats: the obstacle was not built from a mesh");
     SPH_HIP(hipSetDevice(c->device));
     uint32_t h[4] = {0, 0, 0, 0};
-    SPH_HIP(hipMemcpyAsync(h, c->ob_mesh_work + 2, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    SPH_HIP(hipMemcpyAsync(h, o.mesh_work + 2, sizeof h, hipMemcpyDeviceToHost, c->stream));
     SPH_HIP(hipStreamSynchronize(c->stream));
     for (int k = 0; k < 4; k++) out[k] = h[k];
     return SPH_OK;

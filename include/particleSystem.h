@@ -182,6 +182,11 @@ public:
     // pivot's place in the world that the obstacle took from the fluid in the last update; divide by the time step.
     void senseObstacleLoad(bool on);
     void getObstacleLoad(double J[3], double L[3]);
+    // Several obstacles (sph_obstacle_select): the context holds SPH_MAX_OBSTACLES slots, and every obstacle member above
+    // addresses the selected one (0 by default; clearObstacles() clears the selected slot).  They act in ascending slot order.
+    void selectObstacle(uint slot);
+    uint selectedObstacle();
+    void clearAllObstacles();
 
     // ---- additive (absent upstream; named by BASELINE.json's north star) ------------------------
     // 4 floats per particle, by creation index (the original NVIDIA sample's layout), getCapacity() rows; the pointer

@@ -32,7 +32,8 @@
  *                  sph_set_colliders sph_get_colliders sph_set_collider_bodies sph_get_collider_impulses | sph_emit sph_remove sph_count_in_regions |
  *                  sph_obstacle_lattice sph_obstacle_build sph_obstacle_set_grid sph_obstacle_clear sph_obstacle_set_motion
  *                  sph_obstacle_get sph_obstacle_read sph_obstacle_sample sph_obstacle_build_mesh sph_obstacle_build_mesh_dev
- *                  sph_obstacle_build_obj sph_obstacle_set_pose sph_obstacle_get_pose sph_obstacle_set_sensor sph_obstacle_get_load |
+ *                  sph_obstacle_build_obj sph_obstacle_set_pose sph_obstacle_get_pose sph_obstacle_set_sensor sph_obstacle_get_load
+ *                  sph_obstacle_select sph_obstacle_selected sph_obstacle_installed sph_obstacle_clear_all |
  *                  sph_camera_look_at sph_render sph_render_read sph_render_image_dev sph_surface_defaults sph_render_surface
  *                  sph_render_surface_read | sph_mesh_defaults sph_mesh_lattice sph_mesh_extract sph_mesh_read sph_mesh_dev
  *                  sph_mesh_save_obj |
@@ -311,7 +312,8 @@ int sph_set_collider_bodies(sph_ctx* c, uint32_t n, const sph_collider_body* bod
 int sph_get_collider_impulses(sph_ctx* c, uint32_t* n, double* J, uint64_t* steps);
 
 /* ---- solid obstacles of any shape: a signed-distance grid the fluid collides with (no counterpart in the reference) --------------
- * A whole-domain context holds at most one OBSTACLE: a regular grid of signed distances phi (phi < 0 inside the solid), sampled
+ * A whole-domain context holds SPH_MAX_OBSTACLES obstacle slots (SEVERAL OBSTACLES below; a caller who never selects a slot
+ * works with slot 0 alone, and everything up to that section describes one slot).  An OBSTACLE is a regular grid of signed distances phi (phi < 0 inside the solid), sampled
  * trilinearly, built on the device from analytic shapes (sph_obstacle_build) or uploaded by the caller (sph_obstacle_set_grid:
  * the door for voxelised meshes).  It is static, translates uniformly, or turns about a pivot (THE POSE below).  After EVERY integrate -- the fused one of sph_step and
  * sph_force_collide_integrate, and sph_integrate -- a pass of its own pushes the owned particles out of the solid; a context
@@ -479,6 +481,37 @@ int sph_obstacle_get_pose(const sph_ctx* c, int* posed, float pivot[3], double q
 int sph_obstacle_set_sensor(sph_ctx* c, int on);
 /* J, L, about and steps of the last integrate; any pointer may be NULL.  Synchronises. */
 int sph_obstacle_get_load(sph_ctx* c, double J[3], double L[3], float about[3], uint64_t* steps);
+
+/* ---- several obstacles per context: a vessel and a wheel, one push pass ------------------------------------------------------------
+ * A whole-domain context holds SPH_MAX_OBSTACLES obstacle SLOTS.  Each slot is what "the obstacle" is in the sections around
+ * this one: its grid and brick minima, offset and velocity, pose, sensor switch, sensor buffers and load, and the scratch and
+ * stats of a mesh build.  sph_obstacle_select chooses the slot that EVERY sph_obstacle_* call addresses from then on (build,
+ * set_grid, the three mesh builds, clear, set_motion, get, read, sample, set_pose, get_pose, set_sensor, get_load, mesh_stats,
+ * lattice); the default is slot 0, so a caller who never selects sees a library of one obstacle call for call.
+ * THE RULE.  After every integrate the INSTALLED slots act on each owned particle in ASCENDING SLOT ORDER: slot j applies PUSH --
+ * posed or not, as that slot is -- to what slot j - 1 left, with its own off, u, P, rot, omega, its own guard eps + 0.25 s_j and
+ * its own "wall rule once more if hit".  Each rule is unchanged to the bit: the pass equals tests/obstacle_model.py /
+ * tests/obstacle_pose_model.py applied one after the other (tests/obstacle_set_model.py).  A particle no slot hit is not written;
+ * one that some slot hit gets its final position and velocity, its by-index row and, in the fused step, the next key and mover
+ * mark, all from the final position.  Where solids overlap the order decides, as for the spheres.  THE LOAD is per slot: the
+ * terms of that slot's iterations with that slot's d, summed in the order given above; `about` and `steps` are per slot too.
+ * Offsets and poses advance per slot where one slot's advance today, and only while that slot holds a grid.
+ * ONE PASS.  While slot 0 is the only installed slot the library launches the kernels of one obstacle with their arguments.
+ * Every other set is one launch that reads each position once and walks the installed slots in order (sph_obstacle.hip:
+ * k_obstacle_push_set), followed by one load sum per sensing slot.
+ * Installing into or clearing a slot waits for the stream only if THAT slot holds a grid, and leaves the other slots alone.  A
+ * slot's sensor buffers are allocated when that slot's sensor is first switched on; sph_destroy frees them.  None of the four
+ * calls below writes a step flag: they are legal at any stage of a step.
+ *   SPH_E_INVALID  sph_obstacle_select with slot >= SPH_MAX_OBSTACLES;   SPH_E_STATE  a slab context (select, clear_all).
+ * In both cases nothing has changed and nothing was allocated. */
+#define SPH_MAX_OBSTACLES 4
+int sph_obstacle_select(sph_ctx* c, uint32_t slot);
+/* The selected slot (0 for a NULL or a slab context). */
+uint32_t sph_obstacle_selected(const sph_ctx* c);
+/* The number of slots that hold a grid; *mask (may be NULL): bit k = slot k. */
+uint32_t sph_obstacle_installed(const sph_ctx* c, uint32_t* mask);
+/* sph_obstacle_clear on every slot, and the selection back to 0. */
+int sph_obstacle_clear_all(sph_ctx* c);
 
 /* ---- obstacles from a triangle mesh: the mesh voxelised on the device into the grid above ----------------------------------------
  * sph_obstacle_build_mesh turns a closed triangle mesh -- host arrays, device arrays (sph_mesh_dev's pointers feed it with no host
