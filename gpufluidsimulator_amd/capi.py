@@ -157,6 +157,19 @@ class SurfaceStyle(C.Structure):
                 ("specular", C.c_float)]
 
 
+class SolidLook(C.Structure):
+    """`sph_solid_look` of include/sph_hip.h: how one obstacle slot is drawn."""
+    _fields_ = [("draw", C.c_int32), ("open", C.c_int32), ("color", C.c_float * 3)]
+
+
+class SolidStyle(C.Structure):
+    """`sph_solid_style` of include/sph_hip.h (sph_render_set_solids); solid_defaults() fills one."""
+    _fields_ = [("slot", SolidLook * 4), ("light", C.c_float * 3), ("ambient", C.c_float)]     # 4: SPH_MAX_OBSTACLES
+
+
+RENDER_ID_SOLID = 0xFFFFFFF0  # SPH_RENDER_ID_SOLID: the id plane of a pixel won by slot k reads RENDER_ID_SOLID + k
+SOLID_MAX_STEPS = 512         # SPH_SOLID_MAX_STEPS
+SOLID_BISECTIONS = 6          # SPH_SOLID_BISECTIONS
 SURFACE_MAX_RADIUS_PX = 16   # SPH_SURFACE_MAX_RADIUS_PX
 SURFACE_MAX_ITERATIONS = 8   # SPH_SURFACE_MAX_ITERATIONS
 MESH_MAX_REACH = 8           # SPH_MESH_MAX_REACH
@@ -217,6 +230,9 @@ SIGNATURES = {
     "sph_surface_defaults": (None, [C.POINTER(SurfaceStyle)]),
     "sph_render_surface": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(RenderStyle), C.POINTER(SurfaceStyle)]),
     "sph_render_surface_read": (C.c_int, [_P, _P, _P, _P]),
+    "sph_solid_defaults": (None, [C.POINTER(SolidStyle)]),
+    "sph_render_set_solids": (C.c_int, [_P, C.POINTER(SolidStyle)]),
+    "sph_render_get_solids": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(SolidStyle)]),
     "sph_obstacle_lattice": (C.c_int, [_P, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(ObstacleGrid)]),
     "sph_obstacle_build": (C.c_int, [_P, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), _U32, C.POINTER(Shape)]),
     "sph_obstacle_set_grid": (C.c_int, [_P, C.POINTER(ObstacleGrid), _P]),
@@ -431,6 +447,27 @@ def surface_defaults(**fields) -> SurfaceStyle:
         elif k not in ("smooth_radius_px", "smooth_iterations", "depth_falloff", "flat_color", "specular"):
             raise TypeError(f"sph_surface_style has no field {k!r}")
         setattr(s, k, v)
+    return s
+
+
+def solid_defaults(looks=None, **fields) -> SolidStyle:
+    """`sph_solid_defaults` (a host helper: no GPU needed), with any field replaced: light, ambient; looks: {slot: dict of
+    draw, open, color} for the slots that differ."""
+    s = SolidStyle()
+    load().sph_solid_defaults(C.byref(s))
+    for k, v in fields.items():
+        if k == "light":
+            v = (C.c_float * 3)(*[float(x) for x in v])
+        elif k != "ambient":
+            raise TypeError(f"sph_solid_style has no field {k!r}")
+        setattr(s, k, v)
+    for q, look in (looks or {}).items():
+        for k, v in look.items():
+            if k == "color":
+                v = (C.c_float * 3)(*[float(x) for x in v])
+            elif k not in ("draw", "open"):
+                raise TypeError(f"sph_solid_look has no field {k!r}")
+            setattr(s.slot[int(q)], k, v)
     return s
 
 
@@ -877,6 +914,17 @@ class Context:
         sf = surface_defaults() if surface is None else surface
         st = self._render_style(**style)
         _check(self.L.sph_render_surface(self.h, C.byref(camera), C.byref(st), C.byref(sf)))
+
+    def set_render_solids(self, style: "SolidStyle | None"):
+        """While a style is set, render() and render_surface() also draw every installed obstacle slot whose look has draw != 0
+        (`sph_render_set_solids`); None switches the solids off, the default.  Launches and allocates nothing."""
+        _check(self.L.sph_render_set_solids(self.h, None if style is None else C.byref(style)))
+
+    def render_solids(self):
+        """The SolidStyle that is set, as it was given; None while the solids are off."""
+        on, s = C.c_int(0), SolidStyle()
+        _check(self.L.sph_render_get_solids(self.h, C.byref(on), C.byref(s)))
+        return s if on.value else None
 
     def read_surface(self):
         """(raw_depth[h, w] float32, thickness_q[h, w] uint32, normals[h, w, 3] float32) of the last surface render;

@@ -445,6 +445,13 @@ void ParticleSystem::setRenderSurface(bool on, const sph_surface_style* s) {
     else sph_surface_defaults(&m_surfaceStyle);
 }
 
+void ParticleSystem::setRenderSolids(bool on, const sph_solid_style* s) {      // (the context keeps the style)
+    sph_solid_style style;
+    if (s) style = *s;
+    else sph_solid_defaults(&style);
+    SPH_CHECK(sph_render_set_solids(m_ctx, on ? &style : nullptr));
+}
+
 void ParticleSystem::renderFrame() {
     if (m_surfaceOn) SPH_CHECK(sph_render_surface(m_ctx, &m_camera, &m_renderStyle, &m_surfaceStyle));
     else SPH_CHECK(sph_render(m_ctx, &m_camera, &m_renderStyle));

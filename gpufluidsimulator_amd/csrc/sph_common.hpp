@@ -329,6 +329,14 @@ struct sph_ctx {
     float* rd_sf_normal = nullptr;
     bool rd_surface = false;                    // the last render was a surface render (sph_render_surface_read)
     bool rd_sf_thick_on = false;                // ... and its thickness pass ran
+    // the solids in the picture (sph_render_set_solids): the style as the caller gave it, and the planes the march leaves for
+    // the surface's shading -- the nearest hit's depth (+inf: none), slot and eye-space normal (4 + 4 + 12 bytes per pixel).
+    // Allocated at the first surface render with solids on, freed with the image; never while the style is off.
+    bool rd_solids = false;
+    sph_solid_style rd_solid_style{};
+    float* rd_so_depth = nullptr;
+    uint32_t* rd_so_slot = nullptr;
+    float* rd_so_normal = nullptr;
 
     // the mesh of the last sph_mesh_extract (sph_mesh.hip): the lattice's counts and vertex bases (4 + 4 bytes per node), the
     // scans' block sums with the two totals and the case table in front (mesh_aux), and the vertices, normals and triangles.
@@ -503,6 +511,48 @@ inline Obstacle& selected_obstacle(sph_ctx* c) { return c->ob[c->ob_sel]; }
 inline const Obstacle& selected_obstacle(const sph_ctx* c) { return c->ob[c->ob_sel]; }
 int launch_obstacle_push(sph_ctx* c, bool fused, bool mark);
 int advance_obstacle(sph_ctx* c, float dt);   // once per integrate, behind the push: queues the load's sum while sensing, then offset and pose move on
+// the solids as a picture (k_solid_march, sph_obstacle.hip; THE RULE of sph_render_set_solids): the camera and the looks as the
+// kernels take them, by value
+struct SolidCam {
+    uint32_t width, height;
+    float rot[9], trans[3];
+    float focal, near_z, far_z;
+    float half_w, half_h;
+};
+struct SolidLooks {
+    int32_t open[SPH_MAX_OBSTACLES];
+    float color[SPH_MAX_OBSTACLES][3];
+    float L[3];              // the light, normalised
+    float ambient;
+};
+// SHADE of the rule: the colour c of slot `slot` under the eye-space normal ne (the slot picked by selects: a by-value table
+// indexed by a lane's value would go to scratch)
+__device__ __forceinline__ void solid_color(const SolidLooks& K, uint32_t slot, const float ne[3], float c[3]) {
+#pragma clang fp contract(off)
+    const float ndl = fmaxf(0.0f, (ne[0] * K.L[0] + ne[1] * K.L[1]) + ne[2] * K.L[2]);
+    const float g = K.ambient + (1.0f - K.ambient) * ndl;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        float col = K.color[0][k];
+#pragma unroll
+        for (uint32_t q = 1; q < (uint32_t)SPH_MAX_OBSTACLES; q++)
+            if (slot == q) col = K.color[q][k];
+        c[k] = fminf(fmaxf(col * g, 0.0f), 1.0f);
+    }
+}
+__device__ __forceinline__ uint32_t solid_rgba(const float c[3]) {
+#pragma clang fp contract(off)
+    uint32_t out = 0xFF000000u;
+#pragma unroll
+    for (int k = 0; k < 3; k++) out |= (uint32_t)(c[k] * 255.0f + 0.5f) << (8 * k);
+    return out;
+}
+// whether the style is set and some installed slot has draw != 0: else a render is the one without solids, launch for launch
+bool solids_drawn(const sph_ctx* c);
+// One march of every drawn slot over the image.  so_depth null: composed straight into sph_render's resolved planes (depth
+// holds the fluid's d, +inf on background); else the nearest hit of every pixel goes to the three planes for k_surface_shade
+int launch_solid_march(sph_ctx* c, const SolidCam& cam, const SolidLooks& looks, uint32_t* rgba, uint32_t* id, float* depth,
+                       float* so_depth, uint32_t* so_slot, float* so_normal);
 // the installation helpers of sph_obstacle.hip, for the mesh voxeliser (sph_obstacle_mesh.hip): the context check, the lattice
 // of a build (checks only), the clamp distance D, the exchange of the context's grid (on failure: no obstacle) and the bricks
 int obstacle_ctx(const sph_ctx* c, const char* who);

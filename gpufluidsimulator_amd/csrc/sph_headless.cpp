@@ -78,6 +78,7 @@ struct Options {
         float eye[3] = {0.f, 0.f, 3.f}, target[3] = {0.f, 0.f, 0.f}, fovy = 60.f, color_lo = 0.f, color_hi = 1.f;
     } frames;
     struct { bool on = false; sph_surface_style style; } surface;
+    struct { bool on = false; sph_solid_style style; } drawsolids;      // -drawsolids and -solidlook=<k>:...
     struct { const char* dir = nullptr; int every = 1; sph_mesh_params params; } mesh;
     struct { int gpus = 1, protocol = 3; bool on = false, onegpu = false; uint32_t lattice[3] = {0, 0, 0}; uint64_t particles = 0; } slabs;
     bool grows() const { return emit.on || drain.on || add.on; }      // -out then has one row per creation index below the capacity
@@ -329,6 +330,25 @@ bool parse_frames(const Args& a, Options& o) {
         } else ok = false;
         if (!ok) return fail("-color=%s: expected index, speed:<lo>:<hi> or density:<lo>:<hi> with lo != hi\n", v);
     }
+    auto& d = o.drawsolids;   // -drawsolids -solidlook (repeatable): options of -frames
+    d.on = a.flag("drawsolids");
+    sph_solid_defaults(&d.style);
+    bool looks = false;
+    for (int i = 1; i < a.argc; i++)
+        if (const char* t = Args::match(a.argv[i], "solidlook=")) {
+            int k = 0, open = 0;
+            float c3[3] = {0.f, 0.f, 0.f};
+            const char* rest = solid_slot(t, &k);
+            const int got = rest ? sscanf(rest, "%f,%f,%f,%d%c", &c3[0], &c3[1], &c3[2], &open, &extra) : 0;
+            bool ok = (got == 3 || got == 4) && (open == 0 || open == 1);
+            for (int q = 0; q < 3; q++) ok = ok && c3[q] >= 0.f && c3[q] <= 1.f;      // (false for a NaN)
+            if (!ok) return fail("-solidlook=%s: expected <k>:<r>,<g>,<b>[,<open>], k = 0..3, each colour in [0, 1], open 0 or 1\n", t);
+            for (int q = 0; q < 3; q++) d.style.slot[k].color[q] = c3[q];
+            d.style.slot[k].open = open;
+            looks = true;
+        }
+    if ((d.on || looks) && (!o.frames.dir || !d.on))
+        return fail("-drawsolids / -solidlook: expected -frames=<directory> -drawsolids [-solidlook=<k>:<r>,<g>,<b>[,<open>]]\n");
     auto& s = o.surface;      // -surface -tint -absorb: options of -frames
     s.on = a.flag("surface");
     sph_surface_defaults(&s.style);
@@ -407,6 +427,7 @@ bool parse_slabs(const Args& a, Options& o) {
         {o.grows(), "-emit / -drain / -add are", "sph_emit and sph_remove work on a whole-domain context (the slab step sizes its messages from "
                                                  "the previous step's counts); run them on one device"},
         {o.surface.on, "-surface is", "sph_render_surface works on a whole-domain context (the ranks would have to composite their images); run it on one device"},
+        {o.drawsolids.on, "-drawsolids is", "sph_render_set_solids works on a whole-domain context (a slab context does not render); run it on one device"},
         {o.mesh.dir != nullptr, "-mesh is", "sph_mesh_extract works on a whole-domain context (the ranks would have to share a lattice seam); run it on one device"},
         {o.frames.dir != nullptr, "-frames is", "sph_render works on a whole-domain context (the ranks would have to composite their images); run it on one device"},
         {o.collider.on, "-collider is", "run it on one device, or set the sphere on every rank through the library "
@@ -487,12 +508,16 @@ void print_help() {
 // -solidhelp: the options of the obstacle slots (the text of -help is that of the releases before them)
 void print_solid_help() {
     printf("usage: sph_headless ... [-solid=<k>:<shape> ...] [-solid=<k>:[!]mesh:<file.obj>] [-solidcell=<k>:<s>] [-solidband=<k>:<N>] "
-           "[-solidvel=<k>:<ux>,<uy>,<uz>] [-solidspin=<k>:<px>,<py>,<pz>,<wx>,<wy>,<wz>]\n"
+           "[-solidvel=<k>:<ux>,<uy>,<uz>] [-solidspin=<k>:<px>,<py>,<pz>,<wx>,<wy>,<wz>] [-frames=<dir> -drawsolids "
+           "[-solidlook=<k>:<r>,<g>,<b>[,<open>]]]\n"
            "  A context holds %d obstacle slots, k = 0..%d; after every update the installed slots push the fluid in ascending order of k, in one pass.\n"
            "  -solid: a solid in slot k, with the shapes of -obstacle (several with one k form a union) or a closed triangle mesh ([!]mesh:, `!`: the fluid is inside "
            "it); repeatable\n"
            "  -solidcell / -solidband / -solidvel: the grid spacing, the mesh's band and the uniform velocity of slot k, as -obstaclecell / -obstacleband / -obstaclevel\n"
            "  -solidspin: slot k turns about the pivot (px, py, pz) with the angular velocity (wx, wy, wz), from the identity pose, and its load sensor is on\n"
+           "  -drawsolids: with -frames, the installed slots are drawn into the pictures, sprites or -surface: their distance grids ray-marched on the device, "
+           "in front of or behind the fluid by depth; -solidlook the colour of slot k (default 0.72,0.72,0.75) and, with open = 1, the stretch of solid a ray "
+           "starts in left out, so that one looks into a vessel; repeatable\n"
            "  The -obstacle family addresses slot 0: a slot 0 given through both is refused.  At the end every installed slot prints its offset, its quaternion and the "
            "momentum J and angular momentum L it took in the last update.  One device only.\n", SPH_MAX_OBSTACLES, SPH_MAX_OBSTACLES - 1);
 }
@@ -890,6 +915,7 @@ bool set_up(const Options& o, Run& run) {
         ps->setCamera(f.width, f.height, f.eye, f.target, f.fovy);
         ps->setRenderColor(f.color_mode, f.color_lo, f.color_hi);
         ps->setRenderSurface(o.surface.on, &o.surface.style);
+        ps->setRenderSolids(o.drawsolids.on, &o.drawsolids.style);
     }
     if (const auto& m = o.mesh; m.dir) {
         uint32_t md[3]; float mo[3];

@@ -7,6 +7,7 @@
 //   k_obstacle_clamp   one node per lane: the clamp of an uploaded field                                    (sph_obstacle_set_grid)
 //   k_obstacle_bricks  one brick of OBSTACLE_BRICK^3 cells per lane: the minimum over its (OBSTACLE_BRICK + 1)^3 nodes
 //   k_obstacle_sample  one caller point per lane: the sample rule                                           (sph_obstacle_sample)
+//   k_solid_march      one pixel per lane: the drawn slots ray-marched into a picture by that rule           (sph_render_set_solids)
 //   k_obstacle_push    one owned slot per lane, behind every integrate of a context with an obstacle: the push; <POSED> for a
 //                      solid that turns (sph_obstacle_set_pose), <SENSE> leaves the waves' sums of what the solid took
 //   k_obstacle_push_set  the same for every installed set of slots but {slot 0}: the slots in ascending order, in one launch
@@ -542,6 +543,143 @@ __global__ __launch_bounds__(OBSTACLE_THREADS) void k_obstacle_sample(const floa
     in_out[t] = in ? 1 : 0;
 }
 
+// ---- the solids as a picture (sph_render_set_solids; THE RULE of include/sph_hip.h) -----------------------------------------------
+// One pixel per lane; a wave is an 8 x 8 tile of pixels and a block of SOLID_THREADS lanes a 16 x 16 one, so that the rays of a
+// wave walk the same bricks and their eight-node gathers share cache lines.  The slots travel by value like the push's; posed or
+// not is a wave-uniform branch per slot.  The loop bound is each lane's own: neighbouring rays need similar step counts, and a
+// lane that has left only waits for its tile.  No LDS, no atomics.  Every sample is ob_locate_at + ob_sample_cell: the bits of
+// sph_obstacle_sample.  The brick minima are NOT used: the length of a step depends on phi itself, so no sample whose value
+// decides the next one can be skipped with the outcome known.
+constexpr uint32_t SOLID_THREADS = 256, SOLID_TILE = 16;
+
+// CLIP, MARCH and REFINE of one slot along the ray O + z D.  zstop: a hit at or behind it cannot win (the fluid's depth, an
+// earlier slot's hit), so the march leaves at the first free sample there -- every later crossing has z_s >= za >= zstop.
+// true: a crossing; zs and the WORLD normal n are then set
+template <bool POSED>
+__device__ __forceinline__ bool solid_march_slot(const ObstacleSlot& S, bool open, const float O[3], const float D[3], float le,
+                                                 float near_z, float far_z, float zstop, float& zs, float n[3]) {
+#pragma clang fp contract(off)
+    const ObstacleArgs& A = S.A;
+    const ObstaclePose& X = S.X;
+    float Ob[3], Db[3];
+    if constexpr (POSED) {
+        const float d0 = O[0] - X.P[0], d1 = O[1] - X.P[1], d2 = O[2] - X.P[2];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            Ob[k] = ((X.rot[k] * d0 + X.rot[3 + k] * d1) + X.rot[6 + k] * d2) + X.pivot[k];
+            Db[k] = (X.rot[k] * D[0] + X.rot[3 + k] * D[1]) + X.rot[6 + k] * D[2];
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; k++) { Ob[k] = O[k] - A.off[k]; Db[k] = D[k]; }
+    }
+    float t0 = near_z, t1 = far_z;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const float lo = A.origin[k], hi = A.origin[k] + A.nm1[k] * A.s;
+        const float inv = 1.0f / Db[k];
+        const float ta = (lo - Ob[k]) * inv, tb = (hi - Ob[k]) * inv;
+        t0 = fmaxf(t0, fminf(ta, tb));
+        t1 = fminf(t1, fmaxf(ta, tb));
+    }
+    if (!(t0 <= t1)) return false;
+    const float qs = 0.25f * A.s;
+    float z = t0, za = t0, zb = t0;
+    float b0 = 0.f, b1 = 0.f, b2 = 0.f;             // the body normal of the sample that last set zb
+    bool open_run = open, cross = false;
+    uint32_t ci[3];
+    float cf[3], d[3], phi, nx, ny, nz;
+    for (int it = 0; it < SPH_SOLID_MAX_STEPS; it++) {
+        if (!(z <= t1)) break;
+        float a = qs;
+        if (ob_locate_at<POSED>(A, X, O[0] + z * D[0], O[1] + z * D[1], O[2] + z * D[2], ci, cf, d)) {
+            ob_sample_cell(A, ci, cf, phi, nx, ny, nz);
+            if (phi < 0.f) {
+                if (!open_run) { zb = z; b0 = nx; b1 = ny; b2 = nz; cross = true; break; }
+                a = fmaxf(0.5f * (-phi), qs);
+            } else {
+                open_run = false;
+                a = fmaxf(0.5f * phi, qs);
+            }
+        }
+        za = z;
+        if (za >= zstop) break;
+        z = z + a / le;
+    }
+    if (!cross) return false;
+    for (int it = 0; it < SPH_SOLID_BISECTIONS; it++) {
+        const float zm = 0.5f * (za + zb);
+        bool solid = false;
+        if (ob_locate_at<POSED>(A, X, O[0] + zm * D[0], O[1] + zm * D[1], O[2] + zm * D[2], ci, cf, d)) {
+            ob_sample_cell(A, ci, cf, phi, nx, ny, nz);
+            solid = phi < 0.f;
+        }
+        if (solid) { zb = zm; b0 = nx; b1 = ny; b2 = nz; }
+        else za = zm;
+    }
+    if constexpr (POSED) ob_world_normal(X, b0, b1, b2);
+    zs = zb;
+    n[0] = b0; n[1] = b1; n[2] = b2;
+    return true;
+}
+
+// DIRECT (sph_render): depth holds the fluid's d (+inf on background); a pixel whose nearest hit lies strictly in front of it
+// takes the solid's RGBA, id and depth, every other pixel is left alone.  Else (sph_render_surface): the nearest hit of every
+// pixel -- depth (+inf: none), slot, eye-space normal -- goes to the so_ planes, and k_surface_shade composes.
+// `set` holds the DRAWN slots only (flags 0 elsewhere).
+template <bool DIRECT>
+__global__ __launch_bounds__(SOLID_THREADS) void k_solid_march(SolidCam C, SolidLooks K, ObstacleSet set, uint32_t* __restrict__ rgba,
+                                                               uint32_t* __restrict__ id, float* __restrict__ depth,
+                                                               float* __restrict__ so_depth, uint32_t* __restrict__ so_slot,
+                                                               float* __restrict__ so_normal) {
+#pragma clang fp contract(off)
+    const uint32_t wave = threadIdx.x >> 6, l = threadIdx.x & 63u;
+    const uint32_t i = blockIdx.x * SOLID_TILE + (wave & 1u) * 8u + (l & 7u);
+    const uint32_t j = blockIdx.y * SOLID_TILE + (wave >> 1) * 8u + (l >> 3);
+    if (i >= C.width || j >= C.height) return;
+    const size_t pix = (size_t)j * C.width + i;
+    const float ex = (((float)i + 0.5f) - C.half_w) / C.focal;
+    const float ey = (C.half_h - ((float)j + 0.5f)) / C.focal;
+    const float le = sqrtf((ex * ex + ey * ey) + 1.0f);
+    float O[3], D[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        O[k] = -((C.rot[k] * C.trans[0] + C.rot[3 + k] * C.trans[1]) + C.rot[6 + k] * C.trans[2]);
+        D[k] = (C.rot[k] * ex + C.rot[3 + k] * ey) + C.rot[6 + k];
+    }
+    float best = DIRECT ? depth[pix] : INFINITY;       // what a hit has to beat, strictly: the lowest slot wins among equals
+    uint32_t slot = 0;
+    bool hit = false;
+    float n[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (uint32_t s = 0; s < (uint32_t)SPH_MAX_OBSTACLES; s++) {
+        const ObstacleSlot& S = set.s[s];
+        if (!(S.flags & OB_SLOT_INSTALLED)) continue;                               // wave-uniform, as the next
+        float zs, ns[3];
+        const bool got = (S.flags & OB_SLOT_POSED)
+            ? solid_march_slot<true>(S, K.open[s] != 0, O, D, le, C.near_z, C.far_z, best, zs, ns)
+            : solid_march_slot<false>(S, K.open[s] != 0, O, D, le, C.near_z, C.far_z, best, zs, ns);
+        if (got && zs < best) { best = zs; slot = s; hit = true; n[0] = ns[0]; n[1] = ns[1]; n[2] = ns[2]; }
+    }
+    float ne[3] = {0.f, 0.f, 0.f};
+    if (hit) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) ne[k] = (C.rot[3 * k] * n[0] + C.rot[3 * k + 1] * n[1]) + C.rot[3 * k + 2] * n[2];
+    }
+    if constexpr (DIRECT) {
+        if (!hit) return;
+        float c[3];
+        solid_color(K, slot, ne, c);
+        rgba[pix] = solid_rgba(c);
+        id[pix] = SPH_RENDER_ID_SOLID + slot;
+        depth[pix] = best;
+    } else {
+        so_depth[pix] = hit ? best : INFINITY;
+        so_slot[pix] = slot;
+        so_normal[3 * pix] = ne[0]; so_normal[3 * pix + 1] = ne[1]; so_normal[3 * pix + 2] = ne[2];
+    }
+}
+
 // ---- installation ---------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float ob_shape_phi(const sph_shape& S, float px, float py, float pz) {
 #pragma clang fp contract(off)
@@ -667,6 +805,29 @@ static ObstacleSet obstacle_set(const sph_ctx* c) {
         S.s[k].flags = OB_SLOT_INSTALLED | (o.posed ? OB_SLOT_POSED : 0u) | (o.sense && o.load ? OB_SLOT_SENSE : 0u);
     }
     return S;
+}
+
+bool solids_drawn(const sph_ctx* c) {
+    if (!c->rd_solids) return false;
+    for (uint32_t k = 0; k < (uint32_t)SPH_MAX_OBSTACLES; k++)
+        if (c->ob[k].installed() && c->rd_solid_style.slot[k].draw != 0) return true;
+    return false;
+}
+
+int launch_solid_march(sph_ctx* c, const SolidCam& cam, const SolidLooks& looks, uint32_t* rgba, uint32_t* id, float* depth,
+                       float* so_depth, uint32_t* so_slot, float* so_normal) {
+    ObstacleSet S = obstacle_set(c);                 // the offset and the pose the next push would see
+    for (uint32_t k = 0; k < (uint32_t)SPH_MAX_OBSTACLES; k++)
+        if (c->rd_solid_style.slot[k].draw == 0) S.s[k].flags = 0u;
+    const dim3 grid(ceil_div(cam.width, SOLID_TILE), ceil_div(cam.height, SOLID_TILE));
+    if (so_depth)
+        hipLaunchKernelGGL(k_solid_march<false>, grid, dim3(SOLID_THREADS), 0, c->stream, cam, looks, S, rgba, id, depth, so_depth,
+                           so_slot, so_normal);
+    else
+        hipLaunchKernelGGL(k_solid_march<true>, grid, dim3(SOLID_THREADS), 0, c->stream, cam, looks, S, rgba, id, depth, so_depth,
+                           so_slot, so_normal);
+    SPH_HIP(hipGetLastError());
+    return SPH_OK;
 }
 
 // The installed set {slot 0} is the library of one obstacle: k_obstacle_push with its arguments.  Every other set: one launch of

@@ -31,6 +31,11 @@
 //   k_surface_shade   one pixel per lane: normals from Z_K and its four neighbours, the front particle's colour, the thickness,
 //                     the shading; RGBA8 + creation index + normals
 // tests/surface_model.py is its arithmetic in numpy; every plane is compared bit for bit.
+//
+// The solids (sph_render_set_solids): while a style is set and a drawn slot is installed, k_solid_march (sph_obstacle.hip, next
+// to the sample rule it repeats) runs behind k_render_resolve and stores straight into the resolved planes; in a surface render
+// it runs in front of k_surface_shade<true>, which composes, and k_solid_depth puts the winners' depth into Z_K afterwards.
+// tests/solid_render_model.py is the arithmetic in numpy.
 #include "sph_common.hpp"
 
 #include <cmath>
@@ -343,16 +348,38 @@ __device__ __forceinline__ float dot3(const float a[3], const float b[3]) {
     return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2];
 }
 
+// SOLID (a solid style is set, sph_render_set_solids): the so_ planes hold every pixel's nearest solid hit (k_solid_march).  A
+// pixel whose hit lies in front of the fluid, or that has no fluid, takes the solid's colour, id and normal (its depth follows
+// in k_solid_depth: the neighbours' normals read Z here); a fluid pixel with a hit behind it shades over the solid's colour
+// instead of the background's.  <false> is the kernel without solids, operation for operation.
+template <bool SOLID>
 __global__ __launch_bounds__(RENDER_THREADS) void k_surface_shade(const uint64_t* __restrict__ keys, const float* __restrict__ Z,
                                                                   const uint32_t* __restrict__ thick, const float4* __restrict__ posi,
                                                                   const float4* __restrict__ velr, const float2* __restrict__ dp,
                                                                   uint32_t n, RenderArgs A, SurfaceArgs F, uint32_t* __restrict__ rgba,
-                                                                  uint32_t* __restrict__ id, float* __restrict__ normal) {
+                                                                  uint32_t* __restrict__ id, float* __restrict__ normal, SolidLooks K,
+                                                                  const float* __restrict__ so_depth, const uint32_t* __restrict__ so_slot,
+                                                                  const float* __restrict__ so_normal) {
 #pragma clang fp contract(off)
     const uint32_t pix = blockIdx.x * RENDER_THREADS + threadIdx.x;
     if (pix >= A.width * A.height) return;
     const uint64_t key = keys[pix];
     const uint32_t slot = (uint32_t)key;
+    float behind[3] = {F.bg[0], F.bg[1], F.bg[2]};      // what shows through the fluid
+    if constexpr (SOLID) {
+        const float zs = so_depth[pix];
+        if (sf_finite(zs)) {
+            const uint32_t ss = so_slot[pix];
+            const float ne[3] = {so_normal[3 * (size_t)pix], so_normal[3 * (size_t)pix + 1], so_normal[3 * (size_t)pix + 2]};
+            solid_color(K, ss, ne, behind);
+            if (key == RENDER_EMPTY || slot >= n || zs < Z[pix]) {
+                rgba[pix] = solid_rgba(behind);
+                id[pix] = SPH_RENDER_ID_SOLID + ss;
+                normal[3 * (size_t)pix] = ne[0]; normal[3 * (size_t)pix + 1] = ne[1]; normal[3 * (size_t)pix + 2] = ne[2];
+                return;
+            }
+        }
+    }
     if (key == RENDER_EMPTY || slot >= n) {      // (slot >= n cannot happen: the splat only writes slots below n)
         rgba[pix] = A.background;
         id[pix] = 0xFFFFFFFFu;
@@ -418,7 +445,7 @@ __global__ __launch_bounds__(RENDER_THREADS) void k_surface_shade(const uint64_t
     for (int k = 0; k < 3; k++) {
         const float base = F.flat ? F.tint[k] : F.tint[k] * c[k];
         const float tr = F.thick ? 1.0f / (1.0f + F.absorb[k] * T) : 0.0f;
-        const float body = (base * lit) * (1.0f - tr) + F.bg[k] * tr;
+        const float body = (base * lit) * (1.0f - tr) + (SOLID ? behind[k] : F.bg[k]) * tr;
         const float o = (body * (1.0f - fres) + fres) + F.specular * spec;
         out |= (uint32_t)(fminf(fmaxf(o, 0.0f), 1.0f) * 255.0f + 0.5f) << (8 * k);
     }
@@ -428,9 +455,21 @@ __global__ __launch_bounds__(RENDER_THREADS) void k_surface_shade(const uint64_t
     for (int k = 0; k < 3; k++) normal[3 * (size_t)pix + k] = nv[k];
 }
 
+// behind k_surface_shade<true>: the depth plane of the pixels the solid won (the shade's own test)
+__global__ __launch_bounds__(RENDER_THREADS) void k_solid_depth(const uint64_t* __restrict__ keys, uint32_t n, uint32_t npix,
+                                                                const float* __restrict__ so_depth, float* __restrict__ Z) {
+    const uint32_t pix = blockIdx.x * RENDER_THREADS + threadIdx.x;
+    if (pix >= npix) return;
+    const float zs = so_depth[pix];
+    if (!sf_finite(zs)) return;
+    const uint64_t key = keys[pix];
+    if (key == RENDER_EMPTY || (uint32_t)key >= n || zs < Z[pix]) Z[pix] = zs;
+}
+
 // the image and its surface planes leave the context's owner before the context does: another image size, a failed allocation
 static void release_image(sph_ctx* c) {
     Buffers& m = c->mem;
+    m.release(&c->rd_so_normal); m.release(&c->rd_so_slot); m.release(&c->rd_so_depth);
     m.release(&c->rd_sf_normal); m.release(&c->rd_sf_thick); m.release(&c->rd_sf_pong); m.release(&c->rd_sf_raw);
     m.release(&c->rd_depth); m.release(&c->rd_id); m.release(&c->rd_rgba); m.release(&c->rd_keys);
     c->rd_alloc_w = c->rd_alloc_h = 0;
@@ -556,6 +595,36 @@ static RenderArgs render_args(const sph_ctx* c, const sph_camera* cam, const sph
     return A;
 }
 
+// the camera and the context's solid style as k_solid_march takes them
+static SolidCam solid_cam(const RenderArgs& A) {
+    SolidCam C;
+    memset(&C, 0, sizeof(C));
+    C.width = A.width;
+    C.height = A.height;
+    for (int k = 0; k < 9; k++) C.rot[k] = A.rot[k];
+    for (int k = 0; k < 3; k++) C.trans[k] = A.trans[k];
+    C.focal = A.focal;
+    C.near_z = A.near_z;
+    C.far_z = A.far_z;
+    C.half_w = A.half_w;
+    C.half_h = A.half_h;
+    return C;
+}
+
+static SolidLooks solid_looks(const sph_ctx* c) {
+    const sph_solid_style& s = c->rd_solid_style;
+    SolidLooks K;
+    memset(&K, 0, sizeof(K));
+    const double ll = std::sqrt((double)s.light[0] * s.light[0] + (double)s.light[1] * s.light[1] + (double)s.light[2] * s.light[2]);
+    for (int q = 0; q < SPH_MAX_OBSTACLES; q++) {
+        K.open[q] = s.slot[q].open;
+        for (int k = 0; k < 3; k++) K.color[q][k] = s.slot[q].color[k];
+    }
+    for (int k = 0; k < 3; k++) K.L[k] = (float)((double)s.light[k] / ll);
+    K.ambient = s.ambient;
+    return K;
+}
+
 int sph_render(sph_ctx* c, const sph_camera* cam, const sph_render_style* style) {
     if (int e = check_render(c, cam, style, "sph_render")) return e;
     SPH_HIP(hipSetDevice(c->device));
@@ -580,6 +649,9 @@ int sph_render(sph_ctx* c, const sph_camera* cam, const sph_render_style* style)
     hipLaunchKernelGGL(k_render_resolve, dim3(pix_blocks), dim3(RENDER_THREADS), 0, c->stream, c->rd_keys, c->posi + c->own_off,
                        c->velr + c->own_off, c->dp + c->own_off, c->n, A, c->rd_rgba, c->rd_id, c->rd_depth);
     SPH_HIP(hipGetLastError());
+    if (solids_drawn(c))
+        if (int e = launch_solid_march(c, solid_cam(A), solid_looks(c), c->rd_rgba, c->rd_id, c->rd_depth, nullptr, nullptr, nullptr))
+            return e;
     c->rd_w = w;
     c->rd_h = h;
     c->rd_valid = true;
@@ -631,6 +703,17 @@ int sph_render_surface(sph_ctx* c, const sph_camera* cam, const sph_render_style
             return rc;
         }
     }
+    const bool solids = solids_drawn(c);
+    if (solids && !c->rd_so_depth) {                      // the first surface render with solids of an image of this size
+        int rc = c->mem.alloc(&c->rd_so_depth, npix, false);
+        if (!rc) rc = c->mem.alloc(&c->rd_so_slot, npix, false);
+        if (!rc) rc = c->mem.alloc(&c->rd_so_normal, (size_t)npix * 3, false);
+        if (rc) {
+            SPH_HIP(hipStreamSynchronize(c->stream));
+            release_image(c);
+            return rc;
+        }
+    }
     const RenderArgs A = render_args(c, cam, style);
     SurfaceArgs F;
     memset(&F, 0, sizeof(F));
@@ -676,14 +759,69 @@ int sph_render_surface(sph_ctx* c, const sph_camera* cam, const sph_render_style
         hipLaunchKernelGGL(k_surface_filter, dim3(ceil_div(w, SF_TX), ceil_div(h, SF_TY)), dim3(SF_TX, SF_TY), 0, c->stream, src, dst, w, h, F);
         src = dst;
     }
-    hipLaunchKernelGGL(k_surface_shade, dim3(pix_blocks), dim3(RENDER_THREADS), 0, c->stream, c->rd_keys, c->rd_depth, c->rd_sf_thick,
-                       c->posi + c->own_off, c->velr + c->own_off, c->dp + c->own_off, c->n, A, F, c->rd_rgba, c->rd_id, c->rd_sf_normal);
+    if (solids) {
+        const SolidLooks K = solid_looks(c);
+        if (int e = launch_solid_march(c, solid_cam(A), K, nullptr, nullptr, nullptr, c->rd_so_depth, c->rd_so_slot, c->rd_so_normal))
+            return e;
+        hipLaunchKernelGGL(k_surface_shade<true>, dim3(pix_blocks), dim3(RENDER_THREADS), 0, c->stream, c->rd_keys, c->rd_depth,
+                           c->rd_sf_thick, c->posi + c->own_off, c->velr + c->own_off, c->dp + c->own_off, c->n, A, F, c->rd_rgba,
+                           c->rd_id, c->rd_sf_normal, K, c->rd_so_depth, c->rd_so_slot, c->rd_so_normal);
+        hipLaunchKernelGGL(k_solid_depth, dim3(pix_blocks), dim3(RENDER_THREADS), 0, c->stream, c->rd_keys, c->n, npix, c->rd_so_depth,
+                           c->rd_depth);
+    } else {
+        hipLaunchKernelGGL(k_surface_shade<false>, dim3(pix_blocks), dim3(RENDER_THREADS), 0, c->stream, c->rd_keys, c->rd_depth,
+                           c->rd_sf_thick, c->posi + c->own_off, c->velr + c->own_off, c->dp + c->own_off, c->n, A, F, c->rd_rgba,
+                           c->rd_id, c->rd_sf_normal, SolidLooks{}, (const float*)nullptr, (const uint32_t*)nullptr,
+                           (const float*)nullptr);
+    }
     SPH_HIP(hipGetLastError());
     c->rd_w = w;
     c->rd_h = h;
     c->rd_valid = true;
     c->rd_surface = true;
     c->rd_sf_thick_on = F.thick != 0;
+    return SPH_OK;
+}
+
+void sph_solid_defaults(sph_solid_style* s) {
+    if (!s) return;
+    memset(s, 0, sizeof *s);
+    for (int q = 0; q < SPH_MAX_OBSTACLES; q++) {
+        s->slot[q].draw = 1;
+        s->slot[q].open = 0;
+        s->slot[q].color[0] = 0.72f; s->slot[q].color[1] = 0.72f; s->slot[q].color[2] = 0.75f;
+    }
+    s->light[0] = 1.0f; s->light[1] = 1.0f; s->light[2] = -1.0f;
+    s->ambient = 0.25f;
+}
+
+int sph_render_set_solids(sph_ctx* c, const sph_solid_style* s) {
+    SPH_REQUIRE(c, SPH_E_INVALID, "null context");
+    SPH_REQUIRE(!c->slab, SPH_E_STATE, "sph_render_set_solids is not supported on a slab context (it does not render)");
+    if (!s) {
+        c->rd_solids = false;
+        return SPH_OK;
+    }
+    for (int q = 0; q < SPH_MAX_OBSTACLES; q++)
+        for (int k = 0; k < 3; k++)
+            SPH_REQUIRE(std::isfinite(s->slot[q].color[k]) && s->slot[q].color[k] >= 0.f && s->slot[q].color[k] <= 1.f, SPH_E_INVALID,
+                        "solid style: slot %d colour channel %d: finite and in [0, 1]", q, k);
+    SPH_REQUIRE(std::isfinite(s->ambient) && s->ambient >= 0.f && s->ambient <= 1.f, SPH_E_INVALID, "solid style: ambient %g: finite "
+                "and in [0, 1]", (double)s->ambient);
+    const double ll = std::sqrt((double)s->light[0] * s->light[0] + (double)s->light[1] * s->light[1] +
+                                (double)s->light[2] * s->light[2]);
+    SPH_REQUIRE(finite3(s->light, 3) && ll > 0.0, SPH_E_INVALID, "solid style: light: a finite vector that is not zero");
+    SPH_REQUIRE(c->cap < SPH_RENDER_ID_SOLID, SPH_E_CAPACITY, "sph_render_set_solids: capacity %u: the id plane keeps the ids from "
+                "0x%X for the solids", c->cap, SPH_RENDER_ID_SOLID);
+    c->rd_solid_style = *s;
+    c->rd_solids = true;
+    return SPH_OK;
+}
+
+int sph_render_get_solids(const sph_ctx* c, int* on, sph_solid_style* out) {
+    SPH_REQUIRE(c, SPH_E_INVALID, "null context");
+    if (on) *on = c->rd_solids ? 1 : 0;
+    if (out && c->rd_solids) *out = c->rd_solid_style;
     return SPH_OK;
 }
 

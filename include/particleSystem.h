@@ -140,6 +140,9 @@ public:
     // on: renderFrame draws the fluid as a surface (sph_render_surface: smoothed depth, normals, thickness, a water-like
     // shading) in the style *s (nullptr: sph_surface_defaults); off (the default): the sphere sprites of sph_render.
     void setRenderSurface(bool on, const sph_surface_style* s = nullptr);
+    // on: renderFrame also draws the installed obstacle slots (sph_render_set_solids: their distance grids ray-marched into
+    // either picture) in the style *s (nullptr: sph_solid_defaults); off (the default): the fluid alone.
+    void setRenderSolids(bool on, const sph_solid_style* s = nullptr);
     // Queue one render of the particles as they are (asynchronous, no copy of the state); getFrameDevice: its RGBA8 image on
     // the device.  writeFrame: the last rendered image as a binary PPM (P6, RGB, no alpha), rows top to bottom.
     void renderFrame();

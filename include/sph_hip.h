@@ -35,7 +35,7 @@
  *                  sph_obstacle_build_obj sph_obstacle_set_pose sph_obstacle_get_pose sph_obstacle_set_sensor sph_obstacle_get_load
  *                  sph_obstacle_select sph_obstacle_selected sph_obstacle_installed sph_obstacle_clear_all |
  *                  sph_camera_look_at sph_render sph_render_read sph_render_image_dev sph_surface_defaults sph_render_surface
- *                  sph_render_surface_read | sph_mesh_defaults sph_mesh_lattice sph_mesh_extract sph_mesh_read sph_mesh_dev
+ *                  sph_render_surface_read sph_solid_defaults sph_render_set_solids sph_render_get_solids | sph_mesh_defaults sph_mesh_lattice sph_mesh_extract sph_mesh_read sph_mesh_dev
  *                  sph_mesh_save_obj |
  *                  sph_hash sph_sort sph_build_cells sph_density sph_force sph_collide sph_integrate sph_step sph_step_phased
  *                  sph_force_collide_integrate | sph_timing_enable sph_timing_get sph_timing_reset | the z-slab phase calls
@@ -778,6 +778,78 @@ int sph_render_surface(sph_ctx* c, const sph_camera* camera, const sph_render_st
  * when the thickness pass was off), normal_xyz 3 floats per pixel.  Any pointer may be NULL.  Synchronises.  SPH_E_STATE unless
  * the last render was a surface render. */
 int sph_render_surface_read(sph_ctx* c, float* raw_depth, uint32_t* thickness_q, float* normal_xyz);
+
+/* ---- pictures: the SOLIDS -- the obstacle slots' distance grids ray-marched into both renderers -----------------------------------
+ * Opt-in: while a solid style is set, sph_render and sph_render_surface also draw every obstacle slot that is installed and has
+ * draw != 0, with the offset and pose the next push would see.  A context that never sets a style launches, allocates and
+ * computes what it did without this section, obstacles installed or not.
+ *
+ * THE RULE (fp32, every operation rounded, no multiply-add fusion, sums left to right, IEEE division and square root; fminf and
+ * fmaxf return the other operand when one is NaN; tests/solid_render_model.py is the same arithmetic in numpy and gives every
+ * plane bit for bit).
+ * RAY of pixel (i, j); half_w = 0.5f*width, half_h = 0.5f*height, focal = focal_px, rot and trans the camera's:
+ *     ex = (((float)i + 0.5f) - half_w) / focal ;  ey = (half_h - ((float)j + 0.5f)) / focal ;  le = sqrtf((ex*ex + ey*ey) + 1.0f)
+ *     O[k] = -((rot[k]*trans[0] + rot[3+k]*trans[1]) + rot[6+k]*trans[2])
+ *     D[k] = (rot[k]*ex + rot[3+k]*ey) + rot[6+k]
+ *     X(z)[k] = O[k] + z*D[k]                             (z is the eye-space depth: comparable with the fluid's d and Z_K)
+ * CLIP, per slot, in its body frame.  Unposed: Ob = O - off, Db = D.  Posed (R = rot of sph_obstacle_set_pose, P = pivot + off),
+ * with dO = O - P:
+ *     Ob[k] = ((R[0][k]*dO[0] + R[1][k]*dO[1]) + R[2][k]*dO[2]) + pivot[k] ;  Db[k] = (R[0][k]*D[0] + R[1][k]*D[1]) + R[2][k]*D[2]
+ * With lo_k = origin_k, hi_k = origin_k + (float)(n_k - 1)*s, for k = 0, 1, 2 in turn, from t0 = near_z, t1 = far_z:
+ *     inv = 1.0f / Db[k] ;  ta = (lo_k - Ob[k])*inv ;  tb = (hi_k - Ob[k])*inv ;  t0 = fmaxf(t0, fminf(ta, tb)) ;  t1 = fminf(t1, fmaxf(ta, tb))
+ * !(t0 <= t1) is a miss.  (A zero Db[k] gives infinities, or a NaN that the min and max drop.)
+ * MARCH.  z = za = t0, open_run = (look.open != 0).  Up to SPH_SOLID_MAX_STEPS times:
+ *     if !(z <= t1): miss.  Take the slot's SAMPLE at X(z) -- the rule of sph_obstacle_sample, posed or not.
+ *     outside the grid:            a = 0.25f*s ;  za = z
+ *     inside, phi < 0, open_run:   a = fmaxf(0.5f*(-phi), 0.25f*s) ;  za = z
+ *     inside, phi < 0, otherwise:  zb = z, a crossing: the loop ends
+ *     inside, !(phi < 0):          open_run = false ;  a = fmaxf(0.5f*phi, 0.25f*s) ;  za = z
+ *     z = z + a / le
+ * A ray that uses up the steps misses.  (0.5: an interpolated field's gradient reaches about 1.4, see the PUSH; the floor of a
+ * quarter spacing: geometry is resolved to the spacing.  open: the stretch of solid in which the ray starts is invisible -- one
+ * looks into an inverted sphere, a bowl, and sees its far inside wall.)
+ * REFINE.  SPH_SOLID_BISECTIONS times:  zm = 0.5f*(za + zb) ;  sample at X(zm) ;  inside the grid and phi < 0: zb = zm, else za = zm.
+ * The hit is z_s = zb; its world normal n is that of the sample that last set zb (a posed slot's: rot * body normal, not
+ * renormalised, as in the push).
+ * SHADE.  L the style's light, normalised on the host in double and rounded once (eye space, as the surface's):
+ *     ne[k] = (rot[3k]*n[0] + rot[3k+1]*n[1]) + rot[3k+2]*n[2] ;  ndl = fmaxf(0, (ne[0]*L[0] + ne[1]*L[1]) + ne[2]*L[2])
+ *     g = ambient + (1.0f - ambient)*ndl ;  c_k = fminf(fmaxf(color_k*g, 0), 1) ;  channel8 = (uint8)(c_k*255.0f + 0.5f) ;  alpha = 255
+ * SEVERAL SLOTS.  The smallest z_s wins, among equal z_s the lowest slot.
+ * sph_render.  A pixel goes to the solid iff it has a hit and either no sprite covers it or z_s < d of the winning sprite
+ * (strict).  It then holds the solid's RGBA, id SPH_RENDER_ID_SOLID + slot and depth z_s; every other pixel is bit for bit what
+ * it is with the style off.  (The march of a pixel stops at the first free sample at or behind the fluid's d: no later crossing
+ * could win.)
+ * sph_render_surface.  A pixel goes to the solid iff it has a hit and either it is background or z_s < Z_K.  It then holds RGBA,
+ * id and depth as above, and its normal is ne.  Where the fluid wins and the ray has a hit behind it, the shading's bg_k is the
+ * solid's c_k: water in a vessel lets the vessel show through by its thickness.  Z_0, the thickness and the smoothing are
+ * untouched, and a fluid pixel's normal comes from Z_K as before.
+ * How: one pixel per lane, a wave an 8 x 8 tile of pixels, behind the splat on the context's stream; the composition is a plain
+ * store, no atomic, no host wait. */
+#define SPH_RENDER_ID_SOLID  0xFFFFFFF0u   /* id plane: a pixel won by slot k reads SPH_RENDER_ID_SOLID + k */
+#define SPH_SOLID_MAX_STEPS  512
+#define SPH_SOLID_BISECTIONS 6
+typedef struct sph_solid_look {
+    int32_t draw;                  /* 0: the slot is not drawn */
+    int32_t open;                  /* != 0: the stretch of solid in which a ray starts is invisible */
+    float   color[3];              /* each in [0, 1] */
+} sph_solid_look;
+typedef struct sph_solid_style {
+    sph_solid_look slot[SPH_MAX_OBSTACLES];
+    float light[3];                /* eye space; any non-zero finite vector */
+    float ambient;                 /* in [0, 1] */
+} sph_solid_style;
+/* draw 1, open 0, colour (0.72, 0.72, 0.75) for every slot, light (1, 1, -1), ambient 0.25 */
+void sph_solid_defaults(sph_solid_style* s);
+/* The style belongs to the context; NULL switches the solids off (the default).  Legal at any stage; writes no step flag,
+ * launches nothing and allocates nothing.  The extra device planes (the solid's depth, slot and eye-space normal: 4 + 4 + 12 bytes
+ * per pixel) are allocated at the first surface render with solids on and freed with the image; sph_render needs none.
+ *   SPH_E_STATE     a slab context;
+ *   SPH_E_INVALID   a colour, light or ambient that is not finite, a colour component or ambient outside [0, 1], a zero light;
+ *   SPH_E_CAPACITY  sph_capacity >= SPH_RENDER_ID_SOLID (the id plane could not tell a solid from a particle).
+ * In every refused case nothing has changed. */
+int sph_render_set_solids(sph_ctx* c, const sph_solid_style* style);
+/* *on = whether a style is set; *out = that style as it was given (untouched while off).  Either pointer may be NULL. */
+int sph_render_get_solids(const sph_ctx* c, int* on, sph_solid_style* out);
 
 /* ---- geometry: the fluid's surface as a triangle mesh, extracted on the device (no counterpart in the reference, which only draws
  *      into a GL window) ---------------------------------------------------------------------------------------------------------
