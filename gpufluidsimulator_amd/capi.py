@@ -326,6 +326,9 @@ SIGNATURES = {
     "sph_slab_timing_reset": (C.c_int, [_P]),
     "sph_slab_timing_get": (C.c_int, [_P, C.POINTER(C.c_double)]),
     "sph_slab_test_raise_flag": (C.c_int, [_P, C.c_int]),
+    "sph_slab_test_set_hop_seq": (C.c_int, [_P, _U32]),
+    "sph_slab_test_hop_state": (C.c_int, [_P, C.POINTER(_U32)]),
+    "sph_slab_one_clamped": (C.c_uint64, [C.c_void_p]),
     "sph_slab_in_place_merges": (C.c_uint64, [C.c_void_p]),
     "sph_slab_exchanges": (C.c_uint64, [C.c_void_p]),
     "sph_slab_failed": (C.c_int, [C.c_void_p]),

@@ -869,6 +869,7 @@ struct sph_slab {
     uint32_t one_prev_r[2] = {0, 0};     // ... and what each neighbour packed towards me
     uint32_t msg_cap = 0;                // records a migrant / one-message buffer holds behind its header
     uint64_t one_steps = 0, one_rest_msgs = 0;
+    uint64_t one_clamped = 0;            // one-message steps with a size the rule put beyond the buffers and one_size cut down to them
     bool early_force = true;             // the force pass of the innermost layers runs in front of the step's wait, on a stream of its own
                                          // (sph_slab_set_early_force: ~3 us per step when the links are fast, -30 at 40 us per group)
     uint32_t early_cap = 1u << 20;       // slots of that launch at most (~150 us of k_force): what a link's latency needs, no more
@@ -976,6 +977,9 @@ int slab_exchange(sph_slab* s, const Msg& m) {
 // records of a one-message group per side, from what the same link carried in the previous step: a margin of 1/16 + 1024
 // records, whole 64-record chunks (slab.py mirrors it: SlabSimulation.one_message_rows)
 uint32_t one_cap(uint32_t prev) { return (prev + prev / 16u + 1024u + 63u) & ~63u; }
+// ... and never more than the buffers hold.  Both ends of a link form this number from counts both saw, so it is the same on
+// both only if msg_cap is: every rank of a chain is created with the same ghost and migrant capacity (sph_slab_set_protocol).
+uint32_t one_size(const sph_slab* s, uint32_t prev) { return min(one_cap(prev), s->msg_cap); }
 
 // a first group: the header and S_s / S_r records behind it per side (ONE: one_cap records; the re-cut's counts: none)
 Msg msg_first(const sph_slab* s, int tag, const uint32_t S_s[2], const uint32_t S_r[2]) {
@@ -1027,6 +1031,18 @@ int hop_wait(sph_slab* s, int edge, hipStream_t to, hipEvent_t ev, uint32_t valu
     }
     SPH_HIP(hipStreamWaitEvent(to, ev, 0));
     return SPH_OK;
+}
+// A sequence number is 32 bits and the wait is "word >= number": past the wrap the stale large word would satisfy every wait at
+// once, silently.  So a slab whose busiest edge has used half the range goes over to events FOR GOOD -- checked only on entry to a
+// step, a re-cut or a ping, where no mark of this slab is still waiting for its wait to be queued; the value waits already
+// queued have their writes queued in front of them (above), so nothing is drained and hop_mem is left as it is.  The other half
+// of the range is the room one call has: a re-cut marks twice per round and has no small bound on its rounds.  (~2^31 marks: a
+// week or more of stepping at 3-4 marks per 0.5 ms step; the events were created with the slab.)
+constexpr uint32_t HOP_SEQ_LIMIT = 0x7FFFFFF0u;
+void hop_retire_if_worn(sph_slab* s) {
+    if (!s->hops_by_value) return;
+    for (uint32_t seq : s->hop_seq)
+        if (seq >= HOP_SEQ_LIMIT) { s->hops_by_value = false; return; }
 }
 int after_main(sph_slab* s) {
     uint32_t v;
@@ -1101,6 +1117,7 @@ struct Step {
     std::chrono::steady_clock::time_point t_begin, t_waited;
     bool p1 = false;                                 // the one-message step (see step_pre_wait)
     uint32_t S_s[2] = {0, 0}, S_r[2] = {0, 0};       // ... its records behind the header per side (send, receive)
+    bool clamped = false;                            // ... one of the four was cut down to the buffers (one_size)
     uint32_t layer = 0, n0 = 0, off0 = 0, G = 0;     // cells per layer; the owned range right after the sort; ghost layers per side
     bool deep_valid = false;                         // the deep interior's density launched before the wait still holds
     bool early_launched = false, early_pending = false;   // the early force launch: queued / the main stream has not joined it yet
@@ -1137,18 +1154,14 @@ int step_pre_wait(sph_slab* s, Step& st) {
     // both ends saw in the PREVIOUS step's headers (what does not fit follows in an exact second message after the wait: the
     // first step of a burst).  The first step after a create / re-cut has no such counts and runs the three-group protocol.
     st.p1 = s->protocol == 1 && s->one_ready && s->world > 1;
+    // The rule's margin never refuses a step: a size beyond the buffers is CLAMPED to them (one_size) -- the previous counts fitted
+    // (step_headers checked them), and counts that outgrow the buffers this step fail there, on both ends of the link together.
     for (int k = 0; k < 2; k++) {
-        st.S_s[k] = st.p1 && s->has[k] ? one_cap(s->one_prev_s[k]) : 0u;
-        st.S_r[k] = st.p1 && s->has[k] ? one_cap(s->one_prev_r[k]) : 0u;
+        st.S_s[k] = st.p1 && s->has[k] ? one_size(s, s->one_prev_s[k]) : 0u;
+        st.S_r[k] = st.p1 && s->has[k] ? one_size(s, s->one_prev_r[k]) : 0u;
+        st.clamped = st.clamped || (st.p1 && s->has[k] && (one_cap(s->one_prev_s[k]) > s->msg_cap || one_cap(s->one_prev_r[k]) > s->msg_cap));
     }
-    s->pg.group[sph_slab::G_FIRST] = msg_migrants(s);
-    if (st.p1) {
-        // (checked before FIRST becomes the ONE group: a rank that fails here sends its abort header at the MIGRANTS size)
-        SPH_REQUIRE(st.S_s[0] <= s->msg_cap && st.S_s[1] <= s->msg_cap && st.S_r[0] <= s->msg_cap && st.S_r[1] <= s->msg_cap,
-                    SPH_E_CAPACITY, "rank %d: the one-message step would carry %u/%u (send) %u/%u (receive) records; the buffers hold %u",
-                    s->rank, st.S_s[0], st.S_s[1], st.S_r[0], st.S_r[1], s->msg_cap);
-        s->pg.group[sph_slab::G_FIRST] = msg_first(s, SPH_TAG_ONE, st.S_s, st.S_r);
-    }
+    s->pg.group[sph_slab::G_FIRST] = st.p1 ? msg_first(s, SPH_TAG_ONE, st.S_s, st.S_r) : msg_migrants(s);
     rc = slab_check_device_flags(s); if (rc) return rc;
     // ---- hash + sort the owned particles (leavers end up at the two ends of the owned range) -----------------------
     rc = step_hash(c, true);                      // the old ghosts' cells are cleared by the sort's first kernel, not by one of their own
@@ -1235,7 +1248,7 @@ void record_owed(sph_slab* s, const Step& st) {
             h[k] = s->has[k] ? umin(st.own[k] + st.in[k] - umin(st.far_in[k], st.in[k]), s->gcap) : 0u;
             gh[k] = s->has[k] ? umin(st.peer_own[k] + st.m[k] - umin(st.far[k], st.m[k]), s->gcap) : 0u;
         }
-        next_s[k] = one_cap(st.tot_s[k]); next_r[k] = one_cap(st.tot_r[k]);
+        next_s[k] = one_size(s, st.tot_s[k]); next_r[k] = one_size(s, st.tot_r[k]);    // (as step_pre_wait will size it)
     }
     g.group[sph_slab::G_REST] = msg_rest(g.group[sph_slab::G_FIRST], rest_s, rest_r);
     g.posted[sph_slab::G_REST] = (rest_s[0] | rest_s[1] | rest_r[0] | rest_r[1]) == 0u;      // (nothing owed)
@@ -1243,8 +1256,9 @@ void record_owed(sph_slab* s, const Step& st) {
     g.group[sph_slab::G_HALO_B] = msg_dens(s, h, gh);
     g.posted[sph_slab::G_HALO_A] = g.posted[sph_slab::G_HALO_B] = st.p1;    // (no such messages in this protocol)
     // (the neighbours, for whom this step goes through, take their next step under the slab's protocol: a one-message step is
-    // sized from THIS step's headers, which both ends have)
-    if (s->protocol == 1 && next_s[0] <= s->msg_cap && next_s[1] <= s->msg_cap && next_r[0] <= s->msg_cap && next_r[1] <= s->msg_cap) {
+    // sized from THIS step's headers, which both ends have -- each link from its own counts, so a link whose counts are fine
+    // gets the group its far end will post whatever the other link's counts are)
+    if (s->protocol == 1) {
         const uint32_t ns[2] = {s->has[LO] ? next_s[LO] : 0u, s->has[HI] ? next_s[HI] : 0u};
         const uint32_t nr[2] = {s->has[LO] ? next_r[LO] : 0u, s->has[HI] ? next_r[HI] : 0u};
         g.group[sph_slab::G_NEXT] = msg_first(s, SPH_TAG_ONE, ns, nr);
@@ -1321,7 +1335,7 @@ int step_headers(sph_slab* s, Step& st) {
         s->pg.posted[sph_slab::G_REST] = true;
         if (st.p1) s->one_rest_msgs++; else s->rest_msgs++;
     }
-    if (st.p1) s->one_steps++;
+    if (st.p1) { s->one_steps++; if (st.clamped) s->one_clamped++; }
     return SPH_OK;
 }
 
@@ -1694,6 +1708,7 @@ int slab_fail(sph_slab* s, int rc) {
 
 int slab_step_once(sph_slab* s, float dt) {
     if (s->failed) { set_error("%s", s->fail_msg); return s->failed; }
+    hop_retire_if_worn(s);
     const int rc = slab_step_body(s, dt);
     return rc ? slab_fail(s, rc) : SPH_OK;
 }
@@ -2089,6 +2104,7 @@ int sph_slab_ping(sph_slab* s, size_t bytes, uint32_t reps, double out[3]) {
     SPH_HIP(hipSetDevice(s->c->device));
     out[0] = out[1] = out[2] = 0.0;
     if (s->world < 2) return SPH_OK;
+    hop_retire_if_worn(s);       // (a ping takes no hop today; the rule is "every call that queues work looks first")
     const uint32_t words = (uint32_t)(bytes / 4), grid = min(ceil_div(words, 256u), 1024u);
     uint32_t* bad = &s->dev->ping;
     SPH_HIP(hipMemsetAsync(bad, 0, sizeof(uint32_t), s->comm));
@@ -2168,9 +2184,10 @@ static int slab_wait_stream(sph_slab* s, hipStream_t st, const char* what) {
 // the order in which the whole-domain sorted array lists the new owner's particles -- and the context is re-keyed for
 // its new layers; the next step starts with a full (stable) radix sort, as after an upload.  COLLECTIVE over the
 // chain; every particle may move ONE rank per call: the caller keeps new cut r within [old cut r-1, old cut r+1].
-static int slab_recut_body(sph_slab* s, uint32_t new_lo, uint32_t new_hi) {
+static int slab_recut_body(sph_slab* s, uint32_t new_lo, uint32_t new_hi, bool* overflow) {
     sph_ctx* c = s->c;
     int rc;
+    *overflow = false;
     SPH_HIP(hipStreamSynchronize(s->comm));
     rc = step_hash(c); if (rc) return rc;
     rc = step_sort(c); if (rc) return rc;                 // (a slab's sort also builds the table of its owned slots)
@@ -2206,9 +2223,10 @@ static int slab_recut_body(sph_slab* s, uint32_t new_lo, uint32_t new_hi) {
     const uint64_t n_new = (uint64_t)keep + in_lo + in_hi;
     // A rank that cannot hold what is coming does NOT simply return: its neighbours have sized the particle rounds from the
     // counts and are about to post them -- they would sit in their bounded waits and abort their transports.  It takes part
-    // in every round (its leaving runs go out, what arrives is received and dropped), THEN reports the error and is failed;
-    // its neighbours complete their re-cut and hear of the failure in the header of its next migrant message, as after a
-    // failed step (slab_fail).
+    // in every round (its leaving runs go out, what arrives is received and dropped), THEN reports the error and is failed
+    // (`*overflow`: all rounds done, the transport alive): sph_slab_recut takes that error through slab_fail, which posts the
+    // abort header as the first group of the step its neighbours take next -- MIGRANTS, the re-cut cleared their one_ready --
+    // so they complete their re-cut and return SPH_E_PEER from that step, as after a failed step.
     const bool over = n_new > c->cap;
     // what stays goes to its final place in the (now free) primary arrays: behind what comes from below
     const uint32_t base = c->gcap;
@@ -2239,6 +2257,7 @@ static int slab_recut_body(sph_slab* s, uint32_t new_lo, uint32_t new_hi) {
     }
     rc = slab_wait_stream(s, s->comm, "re-cut (particles)"); if (rc) return rc;
     SPH_HIP(hipStreamSynchronize(c->stream));
+    *overflow = over;
     SPH_REQUIRE(!over, SPH_E_CAPACITY, "rank %d: the layers [%u, %u) hold %llu particles, the capacity is %u (the neighbours' re-cut "
                 "went through; this rank's particles are lost: the slab is failed)", s->rank, new_lo, new_hi, (unsigned long long)n_new, c->cap);
     c->own_off = base;
@@ -2270,9 +2289,20 @@ int sph_slab_recut(sph_slab* s, uint32_t new_z_lo, uint32_t new_z_hi) {
     const bool timed0 = s->time_groups;
     s->time_groups = false;
     s->pg = sph_slab::Progress();
-    const int rc = slab_recut_body(s, new_z_lo, new_z_hi);
+    hop_retire_if_worn(s);
+    bool overflow = false;
+    const int rc = slab_recut_body(s, new_z_lo, new_z_hi, &overflow);
     s->time_groups = timed0;
     s->exchanges = exchanges0;                            // (the step counters count the steps' messages)
+    if (rc && overflow && !s->transport_dead) {
+        // The new layers do not fit, every round is done and the links are alive: the neighbours' re-cut went through and their
+        // next call is a step.  Fail as a step that has not posted its first group fails (slab_fail's first branch; `pg` is
+        // fresh): the abort header travels as that step's first group, which is MIGRANTS on both ends -- a re-cut clears
+        // one_ready, so the step after it runs the three-group protocol whatever the slab's protocol is.
+        s->one_ready = false;
+        s->pg.group[sph_slab::G_FIRST] = msg_migrants(s);
+        return slab_fail(s, rc);
+    }
     if (rc) {                                             // a half-done re-cut cannot be resumed: the slab is failed
         s->failed = rc;
         snprintf(s->fail_msg, sizeof s->fail_msg, "%s", sph_last_error());
@@ -2292,6 +2322,32 @@ int sph_slab_recut_stats(const sph_slab* s, uint64_t out[2]) {
 int sph_slab_test_raise_flag(sph_slab* s, int flag) {
     SPH_REQUIRE(s && flag >= 0 && flag < 2, SPH_E_INVALID, "bad argument");
     s->host->err[flag] = 1u;
+    return SPH_OK;
+}
+
+// test hooks: the write / wait-value edges at a sequence number of the caller's choice (tests put it just under HOP_SEQ_LIMIT; the
+// wrap itself would take days to reach).  Every stream of the slab is drained first -- the comm stream under the bounded wait -- so
+// no wait is queued while its word changes; then all five counters AND all five words get `value`: the next mark on an edge
+// writes value + 1 and its wait finds `value` there, as after any other mark.  SPH_E_STATE on a slab that orders by events.
+int sph_slab_test_set_hop_seq(sph_slab* s, uint32_t value) {
+    SPH_REQUIRE(s, SPH_E_INVALID, "null slab");
+    SPH_REQUIRE(!s->failed, s->failed, "%s", s->fail_msg);
+    SPH_REQUIRE(s->hops_by_value && s->hop_mem, SPH_E_STATE, "this slab orders its streams by events: there is no sequence number to set");
+    SPH_HIP(hipSetDevice(s->c->device));
+    int rc = slab_wait_stream(s, s->comm, "setting the hop sequence numbers"); if (rc) return rc;
+    if (s->early) SPH_HIP(hipStreamSynchronize(s->early));
+    SPH_HIP(hipStreamSynchronize(s->c->stream));
+    uint32_t words[5 * 16] = {};
+    for (int e = 0; e < 5; e++) words[16 * e] = value;
+    SPH_HIP(hipMemcpy(s->hop_mem, words, sizeof words, hipMemcpyHostToDevice));
+    for (uint32_t& seq : s->hop_seq) seq = value;
+    return SPH_OK;
+}
+
+int sph_slab_test_hop_state(const sph_slab* s, uint32_t out[6]) {
+    SPH_REQUIRE(s && out, SPH_E_INVALID, "null argument");
+    out[0] = s->hops_by_value ? 1u : 0u;
+    for (int e = 0; e < 5; e++) out[1 + e] = s->hop_seq[e];
     return SPH_OK;
 }
 
@@ -2317,6 +2373,8 @@ int sph_slab_counters(const sph_slab* s, uint64_t out[8]) {
 }
 
 uint64_t sph_slab_exchanges(const sph_slab* s) { return s ? s->exchanges : 0; }
+
+uint64_t sph_slab_one_clamped(const sph_slab* s) { return s ? s->one_clamped : 0; }
 
 int sph_slab_failed(const sph_slab* s) {
     return s ? s->failed : SPH_E_INVALID;

@@ -755,9 +755,16 @@ class NativeSlabSimulation(SlabSimulation):
                  protocol=None, **kw):
         """protocol: 3 = MIGRANTS / HALO A / HALO B (three dependent message groups per step); 1 = the one-message step
         (sph_slab_set_protocol: two ghost layers, ghost densities recomputed locally; slabs of >= 4 cell layers).  The same on
-        every rank."""
+        every rank: checked here, before anything is built (two small all-reduces), because ranks that speak different protocols
+        post messages of different tags and sizes and would only find out in the first step's time-outs.  migrant_capacity and
+        the capacities behind **kw must be the same on every rank too (include/sph_hip.h: sph_slab_set_protocol)."""
         if protocol is None:               # (SPH_SLAB_PROTOCOL=1: the default of callers that do not say -- a test switch)
             protocol = int(os.environ.get("SPH_SLAB_PROTOCOL", "3"))
+        if comm.world > 1:                 # (a rank's environment may differ from its neighbours')
+            most, least = int(comm.allreduce_max(int(protocol))), -int(comm.allreduce_max(-int(protocol)))
+            if most != least:
+                raise ValueError(f"the ranks do not agree on the slab protocol: {least} on some, {most} on others (rank {comm.rank} "
+                                 f"was given {int(protocol)}; callers that do not say take it from SPH_SLAB_PROTOCOL)")
         if protocol not in (1, 3):
             raise ValueError("protocol is 1 (one message per step) or 3")
         self.protocol = int(protocol)
@@ -917,6 +924,7 @@ class NativeSlabSimulation(SlabSimulation):
         pr = (C.c_uint64 * 3)()
         capi._check(capi.load().sph_slab_protocol(self._slab, pr))
         self.stats["protocol"], self.stats["one_message_steps"], self.stats["one_message_rests"] = int(pr[0]), int(pr[1]), int(pr[2])
+        self.stats["one_message_clamped"] = int(capi.load().sph_slab_one_clamped(self._slab))     # sizes cut down to the buffers
 
     def sync(self):
         capi._check(capi.load().sph_slab_sync(self._slab))

@@ -46,10 +46,11 @@
  *   [introspect]   read-only views for parity tests, profiles and bench lines; may grow or change with the implementation:
  *                  sph_get_keys sph_get_order sph_get_cell_range sph_get_cells sph_cell_key sph_download_forces sph_sort_stats
  *                  sph_mesh_field_dims sph_mesh_field_read sph_obstacle_mesh_stats sph_sort_forms sph_last_sort_skipped sph_slab_stats sph_slab_counters sph_slab_in_place_merges
- *                  sph_slab_exchanges sph_slab_recut_stats sph_slab_early_force_stats sph_slab_protocol sph_rccl_transport_info
+ *                  sph_slab_exchanges sph_slab_one_clamped sph_slab_recut_stats sph_slab_early_force_stats sph_slab_protocol sph_rccl_transport_info
  *   [tuning]       switches whose defaults are the product's settings; in fp32 results do not depend on them (A/B runs):
  *                  sph_set_sort_mode sph_set_direct_hull sph_set_pair_small_launch sph_set_block_order sph_slab_set_early_force
  *   [test hook]    exist for tests and measurement harnesses only: sph_test_trust_mover_hint sph_slab_test_raise_flag
+ *                  sph_slab_test_set_hop_seq sph_slab_test_hop_state
  *                  sph_rccl_transport_selftest sph_loop_transport_create/_destroy sph_memory_stats sph_test_fail_alloc
  *                  sph_test_scan sph_test_lower_bounds sph_test_guard sph_test_guard_check
  */
@@ -1125,7 +1126,10 @@ typedef struct sph_slab sph_slab;
  * step needs four (sph_slab_set_protocol, which refuses a thinner slab with SPH_E_STATE and leaves the slab as it was).
  * The step orders its streams by sequence numbers (hipStreamWriteValue32 / hipStreamWaitValue32 on a word of device memory) where the
  * device serves that pair -- tried once here, with both streams drained -- and by events otherwise; SPH_SLAB_HOPS=event in the
- * environment forces events (A/B runs, kernel traces: the runtime's wait is a spinning one-workgroup kernel). */
+ * environment forces events (A/B runs, kernel traces: the runtime's wait is a spinning one-workgroup kernel).  The numbers are
+ * 32 bits and the wait is "word >= number", so they must never wrap: a slab one of whose edges has reached 0x7FFFFFF0 -- half the
+ * range, a week or more of stepping -- SWITCHES TO EVENTS for the rest of its life (it is not re-armed), on entry to its next
+ * sph_slab_step, sph_slab_recut or sph_slab_ping; results do not depend on which of the two orders the streams. */
 int sph_slab_create(sph_slab** out, sph_ctx* ctx, int rank, int world, const sph_transport* transport,
                     uint32_t migrant_capacity);
 void sph_slab_destroy(sph_slab* s);
@@ -1150,6 +1154,9 @@ int sph_slab_set_wait_timeout(sph_slab* s, double seconds);
 /* transport calls so far: 3 in a usual step (migrants, halo A, halo B), 4 when a side has more leavers than ride in the
  * fixed-size migrant message */
 /* [introspect] */ uint64_t sph_slab_exchanges(const sph_slab* s);
+/* one-message steps (sph_slab_set_protocol) whose size rule asked for more records than the message buffers hold on some link and
+ * were sent at the buffers' size instead: a count beside the "second message" counts, 0 under the three-group protocol */
+/* [introspect] */ uint64_t sph_slab_one_clamped(const sph_slab* s);
 /* Re-cut (re-balancing): this slab takes over the cell layers [new_z_lo, new_z_hi) of the global grid.  Entirely on the
  * device, the context and the slab object are kept: the owned particles are split by their layer into "to rank - 1" |
  * "stay" | "to rank + 1" (stable), the leaving runs travel point to point through the slab's transport in chunks of the
@@ -1158,8 +1165,10 @@ int sph_slab_set_wait_timeout(sph_slab* s, double seconds);
  * starts with a full stable sort, as after an upload.  COLLECTIVE: every rank of the chain calls it (a rank whose layers do
  * not change passes its old range), with cuts that agree across ranks; a particle moves at most ONE rank per call, i.e.
  * new cut r lies within [old cut r-1, old cut r+1] (gpufluidsimulator_amd/slab.py: single_hop_cuts steps a larger move).
- * SPH_E_CAPACITY if the new layers hold more particles than the context's capacity (nothing is lost: the slab is failed,
- * download and destroy).  Replaces nothing in the reference (single GPU); SURVEY.md section 8e "re-cut every K steps". */
+ * SPH_E_CAPACITY if the new layers hold more particles than the context's capacity: that rank still takes part in every round of
+ * the re-cut, so its neighbours' calls return SPH_OK, and it is failed the way a step fails -- the "abort" header goes out as the
+ * first message of the step the neighbours take next, which returns SPH_E_PEER to them (and one step later to theirs); destroy
+ * only.  Replaces nothing in the reference (single GPU); SURVEY.md section 8e "re-cut every K steps". */
 int sph_slab_recut(sph_slab* s, uint32_t new_z_lo, uint32_t new_z_hi);
 /* {re-cuts so far, particles that changed owner in them} */
 /* [introspect] */ int sph_slab_recut_stats(const sph_slab* s, uint64_t out[2]);
@@ -1207,7 +1216,12 @@ int sph_slab_timing_get(sph_slab* s, double out[SPH_SLAB_T_WORDS]);
  * locally (one message)"): the receiver merges its own leavers into the copy (the order the neighbour will give them), computes
  * the densities of the inner ghost layer itself -- same candidates, same order, same bits in fp32 -- and the force pass needs no
  * message.  The message's size is fixed in advance by a rule on the counts both ends saw in the previous step's headers (margin
- * 1/16 + 1024 records); what does not fit follows in an exact second message (out[2] counts those); the first step after
+ * 1/16 + 1024 records, and never more than the message buffers hold: a size the rule puts beyond them is cut down to them,
+ * sph_slab_one_clamped counts those steps); what does not fit follows in an exact second message (out[2] counts those); a step
+ * whose counts themselves outgrow the buffers is SPH_E_CAPACITY on both ends of that link.  Both ends form the size from the same
+ * counts AND their own buffers, so EVERY RANK OF A CHAIN MUST BE CREATED WITH THE SAME ghost capacity (sph_create_slab_layers) AND
+ * migrant_capacity (sph_slab_create); the library does not exchange them, and ranks that differ disagree on a message size as
+ * soon as a size is cut down (the local transport reports that, RCCL does not).  The first step after
  * sph_slab_create / sph_slab_recut / this call runs the three-group protocol to learn the counts.  Needs a context with two
  * ghost layers (sph_create_slab_layers) and slabs of >= 4 cell layers; a particle that crosses more than TWO layers in a step is
  * SPH_E_STATE under it.  COLLECTIVE in effect: every rank of the chain must run the same protocol.  Price: ~2x the halo bytes and
@@ -1228,6 +1242,13 @@ int sph_slab_set_protocol(sph_slab* s, int groups);
 /* TEST HOOK: raise sticky device-side error word `flag` (0: an arrival outside its boundary layer, 1: an arrival outside
  * the slab) as the insert / unpack kernels would; the next sph_slab_step then fails before it has sent anything. */
 /* [test hook] */ int sph_slab_test_raise_flag(sph_slab* s, int flag);
+/* TEST HOOKS: the sequence numbers of the write / wait-value edges (sph_slab_create).  _set_hop_seq drains every stream of the slab
+ * (the comm stream under the wait time-out), then sets all five counters and all five words of device memory to `value`, so that
+ * a test reaches the switch to events without a week of steps; SPH_E_STATE on a slab that orders its streams by events.  Call it
+ * between steps, never from another thread while a call on this slab runs.  _hop_state: out = {1 while the slab orders by value,
+ * 0 by events; the five counters}. */
+/* [test hook] */ int sph_slab_test_set_hop_seq(sph_slab* s, uint32_t value);
+/* [test hook] */ int sph_slab_test_hop_state(const sph_slab* s, uint32_t out[6]);
 /* TEST HOOK: what this process's library holds right now: out = {live device bytes, live pinned bytes, live buffers}.  Counted
  * where the library allocates and frees (hipMemGetInfo on a shared card sees everybody's processes): an exact leak check. */
 /* [test hook] */ void sph_memory_stats(uint64_t out[3]);

@@ -227,6 +227,60 @@ def far_case(direction="up", speed=2.8e5):
     return pos, vel, box, grid, fast
 
 
+def one_cap(prev):
+    """csrc/sph_slab.hip one_cap: the one-message step's size rule on the previous step's count."""
+    return (int(prev) + int(prev) // 16 + 1024 + 63) & ~63
+
+
+def slab_buffers(per_layer, ghost_factor, migrant_capacity):
+    """(gcap, mcap, msg_cap) in records, as slab.SlabSimulation sizes the ghost capacity from the fullest cell layer and
+    sph_slab_create the migrant capacity and the message buffers of a context with two ghost layers."""
+    gcap = int(ghost_factor * per_layer) + 1024
+    mcap = min(int(migrant_capacity) if migrant_capacity else gcap // 2 + 1024, gcap)
+    return gcap, mcap, mcap + gcap + 64
+
+
+# The one-message step at the edge of its buffers (tests/test_slab_cpu.py::test_clamp_case_premises counts what these give,
+# tests/test_gpu_slab_limits.py runs them): make_case("tall_up") in three slabs of 8 cell layers of 288 particles, a ghost capacity
+# of 1024 and a migrant capacity of 512 -> message buffers of 1600 records.  A link carries 576 records on a usual step (two
+# layers), 720 and 432 in its two directions on the steps in which a lattice plane of 144 crosses the cut: the size rule asks for
+# 1664, 1792 and 1536.
+CLAMP_CASE = dict(case="tall_up", world=3, steps=28, ghost_factor=0.0, migrant_capacity=512)
+
+
+def clamp_case_counts():
+    """CLAMP_CASE stepped by CPU ranks under the one-message protocol (the oracle engine with two ghost layers): per rank and
+    step {"tot_s", "tot_r": records either end of each link packed, "m": my leavers per side}, and the fullest cell layer."""
+    import threading
+    cc = CLAMP_CASE
+    pos, vel, box, grid = make_case(cc["case"])
+    hub = slab.LocalComm.Hub(cc["world"])
+    rows, errors, per_layer = [[] for _ in range(cc["world"])], [], [0]
+
+    class Counting(OracleEngine2):
+        def slab_counts(self):
+            self.last_counts = super().slab_counts()
+            return self.last_counts
+
+    def rank_main(r):
+        try:
+            sim = slab.SlabSimulation(slab.LocalComm(hub, r), Counting, box, grid, particles=(pos, vel), python_protocol=1)
+            per_layer[0] = sim.per_layer
+            for _ in range(cc["steps"]):
+                sim.step(5e-7)
+                m_lo, _, _, m_hi = sim.engine.last_counts           # (a step counts before anything leaves or arrives)
+                rows[r].append(dict(tot_s=list(sim._one_prev[0]), tot_r=list(sim._one_prev[1]), m=[m_lo, m_hi]))
+        except BaseException as e:     # noqa: BLE001
+            errors.append(e)
+            hub.bar.abort()
+
+    threads = [threading.Thread(target=rank_main, args=(r,)) for r in range(cc["world"])]
+    for t in threads: t.start()
+    for t in threads: t.join(timeout=600)
+    assert not errors, errors
+    return rows, per_layer[0]
+
+
 def gloo_worker(rank, world, port, case, steps, out_dir, protocol=3):
     """Entry of one CPU rank (torch.multiprocessing.spawn): TorchDistComm over gloo."""
     import torch.distributed as dist

@@ -41,6 +41,29 @@ def test_published_cuda_log_gives_the_figures_of_baseline_md():
     assert "total" not in p and "fps" not in p
 
 
+def test_fps_mean_as_written_and_as_the_reference_parser_takes_it():
+    """The one field whose mean differs from the reference's parser: that one averages the digits in front of the decimal point
+    (float(group 13) of 'FPS:(\\d+)\\.(\\d+)fps'), the tool the rate as written.  Both are reported; the expected values are
+    computed here from the lines of the committed log, in the line order, with the same float additions."""
+    path = os.path.join(LOGS, "n131072_CUDA.txt")
+    with open(path) as f:
+        tails = [line.strip().rsplit("FPS:", 1)[1] for line in f.readlines()[2:] if "FPS:" in line]
+    assert len(tails) == 23 and all(t.endswith("fps") and t.count(".") == 1 for t in tails), tails
+    written = [t[:-3] for t in tails]
+    full = sum(float(w) for w in written) / len(written)
+    integer = sum(float(w.split(".")[0]) for w in written) / len(written)
+    assert any(w.split(".")[1].strip("0") for w in written), "the log has fractional rates: the two means differ"
+    s = bls.summarise(path)
+    assert s["mean_ns"]["fps"] == full and s["mean_ns"]["fps_integer_part"] == integer
+    assert 0.0 < full - integer < 1.0
+    assert "fps_integer_part" not in s["percent_of_total"]
+    # a rate without a decimal point (the reference's sequential logs; its own pattern finds no line there): both means are that rate
+    q = bls.summarise(os.path.join(LOGS, "n131072_sequential.txt"))
+    assert q["mean_ns"]["fps"] == q["mean_ns"]["fps_integer_part"] == 0.0
+    txt = subprocess.run([sys.executable, TOOL, path], capture_output=True, text=True, check=True).stdout
+    assert f"{full:.2f}" in txt and f"{integer:.2f}" in txt
+
+
 def test_published_omp_and_small_cuda_logs():
     s = bls.summarise(os.path.join(LOGS, "n131072_OMP.txt"))
     ms = {k: v / 1e6 for k, v in s["mean_ns"].items()}

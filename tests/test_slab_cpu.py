@@ -136,6 +136,45 @@ def test_far_case_premises(direction, speed):
     assert dz.min() > min_dz
 
 
+def test_clamp_case_premises():
+    """What tests/test_gpu_slab_limits.py's run at the edge of the message buffers rests on (slab_oracle_engine.CLAMP_CASE), counted
+    with CPU ranks.  The one-message step sizes a link's message by one_cap on what the link carried the step before; sized like
+    that and REFUSED when it exceeds the buffers (what the library did before it cut the size down to them), these are the steps
+    that would have failed although what they carry fits: at least three must, some with a size that is cut down beside one that
+    is not (the two directions of a link differ on the step after a lattice plane crossed), and no step may carry more than the
+    message buffers, the migrant capacity or the ghost capacity hold -- the run is one that fits."""
+    from slab_oracle_engine import CLAMP_CASE, clamp_case_counts, one_cap, slab_buffers
+    rows, per_layer = clamp_case_counts()
+    gcap, mcap, msg_cap = slab_buffers(per_layer, CLAMP_CASE["ghost_factor"], CLAMP_CASE["migrant_capacity"])
+    assert (per_layer, gcap, mcap, msg_cap) == (288, 1024, 512, 1600)
+    world, steps = CLAMP_CASE["world"], CLAMP_CASE["steps"]
+    refused, mixed, fullest, most_ghosts, most_leavers = 0, 0, 0, 0, 0
+    for k in range(steps):
+        over = []
+        for r in range(world):
+            now = rows[r][k]
+            for side, peer in ((0, r - 1), (1, r + 1)):
+                if not 0 <= peer < world:
+                    assert now["tot_s"][side] == now["tot_r"][side] == now["m"][side] == 0
+                    continue
+                theirs = rows[peer][k]
+                assert now["tot_r"][side] == theirs["tot_s"][1 - side], "both ends of a link hold the same counts"
+                arrivals = theirs["m"][1 - side]
+                ghosts = now["tot_r"][side] - arrivals + now["m"][side]         # the neighbour's two layers + what I sent into them
+                fullest, most_ghosts = max(fullest, now["tot_s"][side]), max(most_ghosts, ghosts)
+                most_leavers = max(most_leavers, now["m"][side])
+                if k >= 1:                                                      # (the first step learns the counts: three groups)
+                    before = rows[r][k - 1]
+                    over += [one_cap(before["tot_s"][side]) > msg_cap, one_cap(before["tot_r"][side]) > msg_cap]
+        refused += any(over)
+        mixed += any(over) and not all(over)
+    print("steps the old check would have refused:", refused, "of", steps - 1, "; with both kinds of size:", mixed, "; fullest message",
+          fullest, "of", msg_cap, "; most ghosts on a side", most_ghosts, "of", gcap, "; most leavers", most_leavers, "of", mcap)
+    assert refused >= 3 and mixed >= 1
+    assert fullest <= msg_cap and most_ghosts <= gcap and most_leavers <= mcap
+    assert most_leavers > 0 and fullest > 2 * per_layer, "a lattice plane crosses a cut within the run"
+
+
 @pytest.mark.parametrize("protocol", [3, 1])
 def test_slabs_over_gloo_world_size_2(protocol):
     """Two real processes over torch.distributed's gloo backend -- under the three-group protocol and under the one-message
@@ -196,6 +235,29 @@ def test_one_message_rule_and_cuts():
     assert all(b - a >= 4 for a, b in zip(cuts, cuts[1:])) and cuts[-1] == 64
     with pytest.raises(ValueError):
         slab.choose_cuts(np.ones(15), 4, 4)
+
+
+def test_ranks_that_disagree_on_the_protocol_are_refused_before_anything_is_built():
+    """NativeSlabSimulation takes its default protocol from SPH_SLAB_PROTOCOL, and a rank's environment may differ from its
+    neighbour's: two ranks over the local comm, given 3 and 1, both get a ValueError that names both values -- from the
+    constructor's first lines, before an engine (and so a device) is asked for."""
+    pos, vel, box, grid = make_case("up")
+    hub = slab.LocalComm.Hub(2)
+    errors = [None, None]
+
+    def rank_main(r):
+        try:
+            slab.NativeSlabSimulation(slab.LocalComm(hub, r), box, grid, transport="local", particles=(pos, vel), protocol=(3, 1)[r])
+        except BaseException as e:     # noqa: BLE001
+            errors[r] = e
+
+    threads = [threading.Thread(target=rank_main, args=(r,)) for r in range(2)]
+    for t in threads: t.start()
+    for t in threads: t.join(timeout=60)
+    assert not any(t.is_alive() for t in threads)
+    for r, e in enumerate(errors):
+        assert isinstance(e, ValueError), errors
+        assert "1 on some, 3 on others" in str(e) and f"rank {r} was given {(3, 1)[r]}" in str(e), errors
 
 
 def test_rebalance_moves_the_cuts_and_keeps_the_physics():
