@@ -124,6 +124,27 @@ class ObstaclePose(C.Structure):
     _fields_ = [("pivot", C.c_float * 3), ("quat", C.c_float * 4), ("omega", C.c_float * 3)]
 
 
+BODY_FREE_X, BODY_FREE_Y, BODY_FREE_Z, BODY_SPIN, BODY_HINGE = 1, 2, 4, 8, 16     # SPH_BODY_*
+BODY_FREE_XYZ = BODY_FREE_X | BODY_FREE_Y | BODY_FREE_Z
+
+
+class ObstacleBody(C.Structure):
+    """`sph_obstacle_body` of include/sph_hip.h (80 bytes): which motions of an obstacle slot the fluid drives, and with what."""
+    _fields_ = [("dof", C.c_uint32), ("mass", C.c_float), ("inertia", C.c_float * 3), ("axis", C.c_float * 3),
+                ("accel", C.c_float * 3), ("torque", C.c_float * 3), ("lo", C.c_float * 3), ("hi", C.c_float * 3)]
+
+    @classmethod
+    def make(cls, dof=0, mass=0.0, inertia=(0.0, 0.0, 0.0), axis=(0.0, 0.0, 0.0), accel=(0.0, 0.0, 0.0), torque=(0.0, 0.0, 0.0),
+             lo=(0.0, 0.0, 0.0), hi=(0.0, 0.0, 0.0)):
+        return cls(int(dof), float(mass), _f3(inertia), _f3(axis), _f3(accel), _f3(torque), _f3(lo), _f3(hi))
+
+    def as_dict(self):
+        out = {"dof": int(self.dof), "mass": np.float32(self.mass)}
+        for f in ("inertia", "axis", "accel", "torque", "lo", "hi"):
+            out[f] = np.array(list(getattr(self, f)), np.float32)
+        return out
+
+
 OBSTACLE_MESH_MAX_BAND = 16        # SPH_OBSTACLE_MESH_MAX_BAND
 OBSTACLE_MESH_DEFAULT_BAND = 3     # SPH_OBSTACLE_MESH_DEFAULT_BAND
 
@@ -246,7 +267,9 @@ SIGNATURES = {
                                         C.POINTER(C.c_float)]),
     "sph_obstacle_set_sensor": (C.c_int, [_P, C.c_int]),
     "sph_obstacle_get_load": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_uint64)]),
-    "sph_obstacle_build_mesh": (C.c_int, [_P, C.POINTER(ObstacleMeshParams), C.POINTER(C.c_float), C.POINTER(C.c_float), _U32, _P,
+    "sph_obstacle_set_body": (C.c_int, [_P, C.POINTER(ObstacleBody)]),
+    "sph_obstacle_get_body": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(ObstacleBody)]),
+    "sph_obstacle_build_mesh": (C.c_int,[_P, C.POINTER(ObstacleMeshParams), C.POINTER(C.c_float), C.POINTER(C.c_float), _U32, _P,
                                           _U32, _P]),
     "sph_obstacle_build_mesh_dev": (C.c_int, [_P, C.POINTER(ObstacleMeshParams), C.POINTER(C.c_float), C.POINTER(C.c_float), _U32,
                                               _P, _U32, _P]),
@@ -821,6 +844,25 @@ class Context:
         _check(self.L.sph_obstacle_get_load(self.h, J, L, about, C.byref(steps)))
         return {"J": np.array(list(J), np.float64), "L": np.array(list(L), np.float64),
                 "about": np.array(list(about), np.float32), "steps": int(steps.value)}
+
+    @_slotted
+    def set_obstacle_body(self, body: "ObstacleBody | None" = None, **fields):
+        """Give the slot a body (include/sph_hip.h: THE BODY): from then on the fluid drives the motions in `dof`, on the device,
+        inside step(dt, n).  `body` is an ObstacleBody, or its fields as keywords (ObstacleBody.make); set_obstacle_body(None)
+        with no keyword drops the body (synchronises) and the slot goes on kinematic from where it is.  The slot needs a pose."""
+        if body is None and not fields:
+            _check(self.L.sph_obstacle_set_body(self.h, None))
+            return
+        b = body if body is not None else ObstacleBody.make(**fields)
+        _check(self.L.sph_obstacle_set_body(self.h, C.byref(b)))
+
+    @_slotted
+    def obstacle_body(self):
+        """None without a body, else the parameters as they were set: {"dof", "mass", "inertia", "axis", "accel", "torque",
+        "lo", "hi"}.  The state is what obstacle() and obstacle_pose() return."""
+        has, b = C.c_int(), ObstacleBody()
+        _check(self.L.sph_obstacle_get_body(self.h, C.byref(has), C.byref(b)))
+        return b.as_dict() if has.value else None
 
     # -- obstacles from a triangle mesh (include/sph_hip.h: sph_obstacle_build_mesh and the calls next to it) -----------------------
     @_slotted

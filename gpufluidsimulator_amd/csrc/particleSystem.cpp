@@ -540,6 +540,15 @@ void ParticleSystem::senseObstacleLoad(bool on) { SPH_CHECK(sph_obstacle_set_sen
 
 void ParticleSystem::getObstacleLoad(double J[3], double L[3]) { SPH_CHECK(sph_obstacle_get_load(m_ctx, J, L, nullptr, nullptr)); }
 
+void ParticleSystem::setObstacleBody(const sph_obstacle_body& body) { SPH_CHECK(sph_obstacle_set_body(m_ctx, &body)); }
+
+void ParticleSystem::clearObstacleBody() { SPH_CHECK(sph_obstacle_set_body(m_ctx, nullptr)); }
+
+void ParticleSystem::getObstacleState(float offset[3], float velocity[3], double quat[4], float omega[3]) {
+    SPH_CHECK(sph_obstacle_get(m_ctx, nullptr, offset, velocity));
+    SPH_CHECK(sph_obstacle_get_pose(m_ctx, nullptr, nullptr, quat, omega, nullptr));
+}
+
 void ParticleSystem::selectObstacle(uint slot) { SPH_CHECK(sph_obstacle_select(m_ctx, slot)); }
 
 uint ParticleSystem::selectedObstacle() { return sph_obstacle_selected(m_ctx); }

@@ -217,6 +217,15 @@ enum HostWord : uint32_t {
 // of every brick of OBSTACLE_BRICK^3 cells; grid.dims = 0, 0, 0 and null pointers while there is none.  Allocated by the call
 // that installs a grid, freed by sph_obstacle_clear; never by a caller who sets no obstacle.  The offset advances on the host
 // once per step, next to the spheres' centres (sph_pairs.hip: advance_colliders).
+// The state of a BODY slot (sph_obstacle_set_body), which lives on the device while the body is set: the push, the sample and
+// the solids' march read it at kernel entry, k_obstacle_body moves it on once per integrate.  rot and P are what the next launch
+// uses: rot from quat, each entry rounded once, and P = pivot + off.
+struct ObstacleBodyBlock {
+    double quat[4];
+    float off[3], u[3], pivot[3], omega[3];
+    float rot[9], P[3];
+};
+
 struct Obstacle {
     sph_obstacle_grid grid{};
     float* phi = nullptr;
@@ -234,6 +243,13 @@ struct Obstacle {
     double* rows = nullptr;             // ceil(cap / 64) rows of 6: J, L
     uint32_t* wmask = nullptr;          // ceil(cap / 64) words, padded to whole quads plus one
     double* load = nullptr;             // J[3], L[3], the integrate count (uint64), about[3] (fp32) and a pad word: 72 bytes
+    // the body (sph_obstacle_set_body): while `body`, off, vel, pivot, omega and quat above are STALE -- the block on the device
+    // holds them, as trk_table holds the spheres of a tracked context -- and the slot is posed and sensing.  The block is
+    // allocated at the slot's first set_body and freed by sph_destroy.
+    bool body = false;
+    sph_obstacle_body bd{};             // as the caller gave it
+    double axis[3] = {0.0, 0.0, 0.0};   // HINGE: bd.axis normalised in double
+    ObstacleBodyBlock* blk = nullptr;
     // an obstacle voxelised from a triangle mesh (sph_obstacle_mesh.hip) keeps the scratch of its build -- the work list with the
     // four counters in front, and the parity marks of the columns -- until the next installation, sph_obstacle_clear or
     // sph_destroy; both null for every other obstacle, and sph_obstacle_mesh_stats reads the counters

@@ -65,6 +65,8 @@ struct Options {
         std::string mesh;                  // the OBJ file of -solid=<k>:[!]mesh:FILE.obj, else empty
         uint band = 0;
         float cell = 0.f, velocity[3] = {0.f, 0.f, 0.f}, pivot[3] = {0.f, 0.f, 0.f}, omega[3] = {0.f, 0.f, 0.f};
+        bool has_body = false;             // -solidbody=<k>:hinge,... | float,...: the fluid drives the slot (sph_obstacle_set_body)
+        sph_obstacle_body body = {};
     } solid[SPH_MAX_OBSTACLES];
     bool solidhelp = false;
     bool solids() const { for (const Solid& s : solid) if (s.given) return true; return false; }
@@ -264,10 +266,46 @@ bool parse_solids(const Args& a, Options& o) {
             if (!rest || sscanf(rest, "%f,%f,%f,%f,%f,%f%c", &p[0], &p[1], &p[2], &w[0], &w[1], &w[2], &tail) != 6)
                 return fail("-solidspin=%s: expected <k>:px,py,pz,wx,wy,wz, k = 0..3\n", t);
             o.solid[k].has_spin = true;
+        } else if (const char* t = Args::match(a.argv[i], "solidbody=")) {
+            const char* rest = solid_slot(t, &k);
+            const char* body_form = "-solidbody=%s: expected <k>:hinge,ax,ay,az,I[,tau] or <k>:float,mass,Ix,Iy,Iz[,gy], k = 0..3\n";
+            if (!rest) return fail(body_form, t);
+            if (o.solid[k].has_body) return fail("-solidbody=%s: slot %d already has a body\n", t, k);
+            sph_obstacle_body b = {};
+            float v[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+            char tail = 0;
+            if (const char* h = strncmp(rest, "hinge,", 6) ? nullptr : rest + 6) {
+                if (sscanf(h, "%f,%f,%f,%f,%f%c", &v[0], &v[1], &v[2], &v[3], &v[4], &tail) != 5) {
+                    v[4] = 0.f;
+                    if (sscanf(h, "%f,%f,%f,%f%c", &v[0], &v[1], &v[2], &v[3], &tail) != 4) return fail(body_form, t);
+                }
+                const double len = std::sqrt((double)v[0] * v[0] + (double)v[1] * v[1] + (double)v[2] * v[2]);
+                if (!(len > 0.0) || !(v[3] > 0.f)) return fail("-solidbody=%s: the axis must not be zero and I must be positive\n", t);
+                b.dof = SPH_BODY_HINGE;
+                b.inertia[0] = v[3];
+                for (int c = 0; c < 3; c++) { b.axis[c] = v[c]; b.torque[c] = (float)((double)v[4] * ((double)v[c] / len)); }
+            } else if (const char* f = strncmp(rest, "float,", 6) ? nullptr : rest + 6) {
+                if (sscanf(f, "%f,%f,%f,%f,%f%c", &v[0], &v[1], &v[2], &v[3], &v[4], &tail) != 5) {
+                    v[4] = 0.f;
+                    if (sscanf(f, "%f,%f,%f,%f%c", &v[0], &v[1], &v[2], &v[3], &tail) != 4) return fail(body_form, t);
+                }
+                if (!(v[0] > 0.f) || !(v[1] > 0.f) || !(v[2] > 0.f) || !(v[3] > 0.f))
+                    return fail("-solidbody=%s: the mass and the three moments must be positive\n", t);
+                b.dof = SPH_BODY_FREE_X | SPH_BODY_FREE_Y | SPH_BODY_FREE_Z | SPH_BODY_SPIN;
+                b.mass = v[0];
+                for (int c = 0; c < 3; c++) { b.inertia[c] = v[1 + c]; b.lo[c] = -1e30f; b.hi[c] = 1e30f; }
+                b.accel[1] = v[4];
+            } else {
+                return fail(body_form, t);
+            }
+            o.solid[k].has_body = true;
+            o.solid[k].body = b;
         }
     }
     for (int k = 0; k < SPH_MAX_OBSTACLES; k++) {
         const auto& s = o.solid[k];
+        if (s.has_body && !(s.given && s.has_spin))
+            return fail("-solidbody=%d:... goes with a -solid=%d:... and a -solidspin=%d:... (the pivot and the first angular velocity)\n", k, k, k);
         if (!s.given && (s.has_cell || s.band || s.has_velocity || s.has_spin))
             return fail("-solidcell / -solidband / -solidvel / -solidspin=%d:... go with a -solid=%d:...\n", k, k);
         if (!s.mesh.empty() && !s.shapes.empty())
@@ -508,13 +546,18 @@ void print_help() {
 // -solidhelp: the options of the obstacle slots (the text of -help is that of the releases before them)
 void print_solid_help() {
     printf("usage: sph_headless ... [-solid=<k>:<shape> ...] [-solid=<k>:[!]mesh:<file.obj>] [-solidcell=<k>:<s>] [-solidband=<k>:<N>] "
-           "[-solidvel=<k>:<ux>,<uy>,<uz>] [-solidspin=<k>:<px>,<py>,<pz>,<wx>,<wy>,<wz>] [-frames=<dir> -drawsolids "
+           "[-solidvel=<k>:<ux>,<uy>,<uz>] [-solidspin=<k>:<px>,<py>,<pz>,<wx>,<wy>,<wz>] "
+           "[-solidbody=<k>:hinge,<ax>,<ay>,<az>,<I>[,<tau>] | <k>:float,<mass>,<Ix>,<Iy>,<Iz>[,<gy>]] [-frames=<dir> -drawsolids "
            "[-solidlook=<k>:<r>,<g>,<b>[,<open>]]]\n"
            "  A context holds %d obstacle slots, k = 0..%d; after every update the installed slots push the fluid in ascending order of k, in one pass.\n"
            "  -solid: a solid in slot k, with the shapes of -obstacle (several with one k form a union) or a closed triangle mesh ([!]mesh:, `!`: the fluid is inside "
            "it); repeatable\n"
            "  -solidcell / -solidband / -solidvel: the grid spacing, the mesh's band and the uniform velocity of slot k, as -obstaclecell / -obstacleband / -obstaclevel\n"
            "  -solidspin: slot k turns about the pivot (px, py, pz) with the angular velocity (wx, wy, wz), from the identity pose, and its load sensor is on\n"
+           "  -solidbody: the FLUID drives slot k from then on, on the device (goes with -solidspin, which gives the pivot and the first angular velocity): "
+           "hinge, a wheel or a flap about the fixed axis (ax, ay, az) through the pivot with the moment I and a constant torque tau about it (default 0); "
+           "float, a free body of that mass with the principal moments (Ix, Iy, Iz) about the pivot, its centre of mass, under the acceleration gy (default 0), "
+           "its offset unbounded.  At the end a body slot also prints its offset, velocity and angular velocity\n"
            "  -drawsolids: with -frames, the installed slots are drawn into the pictures, sprites or -surface: their distance grids ray-marched on the device, "
            "in front of or behind the fluid by depth; -solidlook the colour of slot k (default 0.72,0.72,0.75) and, with open = 1, the stretch of solid a ray "
            "starts in left out, so that one looks into a vessel; repeatable\n"
@@ -901,6 +944,7 @@ bool set_up(const Options& o, Run& run) {
             ps->setObstaclePose(s.pivot, identity, s.omega);
             ps->senseObstacleLoad(true);
         }
+        if (s.has_body) ps->setObstacleBody(s.body);
         if (!s.mesh.empty()) {
             uint64_t ms[4];
             ps->getObstacleMeshStats(ms);
@@ -1000,6 +1044,12 @@ bool report(const Options& o, Run& run, double secs) {
             ps->getObstacleLoad(J, L);
             printf("solid %u: offset %.9g %.9g %.9g quaternion %.17g %.17g %.17g %.17g J %.17g %.17g %.17g L %.17g %.17g %.17g\n", k, off[0], off[1],
                    off[2], q[0], q[1], q[2], q[3], J[0], J[1], J[2], L[0], L[1], L[2]);
+            if (o.solid[k].has_body) {      // where the fluid took it: the block, fetched
+                float bo[3], bu[3], bw[3]; double bq[4];
+                ps->getObstacleState(bo, bu, bq, bw);
+                printf("solid %u body: offset %.9g %.9g %.9g velocity %.9g %.9g %.9g omega %.9g %.9g %.9g\n", k, bo[0], bo[1], bo[2], bu[0],
+                       bu[1], bu[2], bw[0], bw[1], bw[2]);
+            }
         }
         ps->selectObstacle(0);
     }

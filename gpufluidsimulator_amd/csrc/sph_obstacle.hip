@@ -12,6 +12,9 @@
 //                      solid that turns (sph_obstacle_set_pose), <SENSE> leaves the waves' sums of what the solid took
 //   k_obstacle_push_set  the same for every installed set of slots but {slot 0}: the slots in ascending order, in one launch
 //   k_obstacle_load    one block per sensing slot behind a sensing push: the waves' sums in a fixed order                    (sph_obstacle_get_load)
+//   k_obstacle_body    one thread per BODY slot behind its load sum: J and L move the slot's device block on by dt           (sph_obstacle_set_body)
+//   k_obstacle_body_put  one thread: what set_body, set_motion and set_pose write into that block, by value
+// A BODY slot's push, sample and march are instantiations of the kernels above that read the block at entry (ob_overlay).
 //
 // The push is a pass of its own and not a fourth pack of k_force / k_integrate (sph_pairs.hip): the fused kernel sits at the edge
 // of its occupancy, and an eight-node gather in its epilogue would cost it.  Reading the integrate's STORED output is also what
@@ -21,6 +24,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 namespace sph {
 
@@ -52,6 +56,18 @@ struct ObstaclePose {
     uint32_t* mask;        // ... and whether the wave wrote them
 };
 
+// A BODY slot (sph_obstacle_set_body): the pose travels as for a posed slot, and the block's pointer behind it.  The BODY
+// instantiations take this as their last argument; the others keep ObstaclePose, argument for argument.
+struct ObstaclePoseBody {
+    ObstaclePose X;
+    const ObstacleBodyBlock* blk;
+};
+template <bool BODY> using PoseArg = std::conditional_t<BODY, ObstaclePoseBody, ObstaclePose>;
+__device__ __forceinline__ ObstaclePose& pose_of(ObstaclePose& X) { return X; }
+__device__ __forceinline__ ObstaclePose& pose_of(ObstaclePoseBody& X) { return X.X; }
+__device__ __forceinline__ const ObstacleBodyBlock* block_of(const ObstaclePose&) { return nullptr; }
+__device__ __forceinline__ const ObstacleBodyBlock* block_of(const ObstaclePoseBody& X) { return X.blk; }
+
 // the shapes of one build: a kernel argument by value, like Spheres (the half-spaces' normals already normalised)
 struct Shapes {
     sph_shape s[SPH_MAX_SHAPES];
@@ -61,6 +77,18 @@ struct Shapes {
 __device__ __forceinline__ float ob_lerp(float p, float q, float t) {
 #pragma clang fp contract(off)
     return p + t * (q - p);
+}
+
+// The overlay of a BODY slot, at kernel entry: what the host holds of off, u, rot, P, pivot and omega is stale, the block has
+// them.  The address is the same for every lane, so these are scalar loads; everything behind them is the posed arithmetic.
+__device__ __forceinline__ void ob_overlay(ObstacleArgs& A, ObstaclePose& X, const ObstacleBodyBlock* __restrict__ b) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        A.off[k] = b->off[k]; A.u[k] = b->u[k];
+        X.pivot[k] = b->pivot[k]; X.P[k] = b->P[k]; X.omega[k] = b->omega[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 9; k++) X.rot[k] = b->rot[k];
 }
 
 // the cell of x and the fractions inside it; false: outside the grid (NaN and +-inf too)
@@ -161,16 +189,20 @@ __device__ __forceinline__ void ob_sample_cell(const ObstacleArgs& A, const uint
 // its own; the wave then adds its kicked lanes' sums in ascending lane order -- two scalar-indexed 32-bit reads per value, as
 // push_out_of_spheres(..., SpheresTracked) reads its floats, no LDS, no atomics -- and lane 0 stores the row.  EVERY wave that
 // owns a slot stores its mask word, 0 where it leaves at the guard's ballot, so k_obstacle_load never reads a row of an earlier
-// launch.  <false, false> is the kernel without either, operation for operation.
-template <bool POSED, bool SENSE>
+// launch.  <false, false> is the kernel without either, operation for operation.  BODY (sph_obstacle_set_body; only
+// <true, true, true>): the overlay at entry, then <true, true> operation for operation.
+template <bool POSED, bool SENSE, bool BODY = false>
 __global__ __launch_bounds__(OBSTACLE_THREADS) void k_obstacle_push(float4* __restrict__ posi, float4* __restrict__ velr,
                                                                     float4* __restrict__ pos_by_index,
                                                                     uint32_t* __restrict__ keys_out,
                                                                     const uint32_t* __restrict__ keyS,
                                                                     uint64_t* __restrict__ mm_mask,
                                                                     uint32_t* __restrict__ mm_tile_cnt, uint32_t lo, uint32_t n,
-                                                                    ObstacleArgs A, GridDesc g, Phys ph, ObstaclePose X) {
+                                                                    ObstacleArgs A, GridDesc g, Phys ph, PoseArg<BODY> Xa) {
 #pragma clang fp contract(off)
+    static_assert(!BODY || (POSED && SENSE), "a body slot is posed and sensing");
+    ObstaclePose& X = pose_of(Xa);
+    if constexpr (BODY) ob_overlay(A, X, block_of(Xa));
     const uint32_t rel = blockIdx.x * OBSTACLE_THREADS + threadIdx.x;
     const bool active = rel < n;
     const uint32_t slot = lo + (active ? rel : n - 1u);
@@ -288,14 +320,30 @@ __global__ __launch_bounds__(OBSTACLE_THREADS) void k_obstacle_push(float4* __re
 //     not the unposed rule); the wall rule runs behind the iterations of every slot that hit, as in a pass of its own;
 //   * a sensing slot's six lane sums are reduced in ascending lane order and stored right behind its iterations;
 //   * position, velocity, by-index row, key and the marks' fix-up (with the union of the hits) are stored once, at the end.
-constexpr uint32_t OB_SLOT_INSTALLED = 1u, OB_SLOT_POSED = 2u, OB_SLOT_SENSE = 4u;
+//   * BODY (a set in which some slot has a body; an instantiation of its own, so that every other set runs the code it ran
+//     before): a slot with OB_SLOT_BODY takes the overlay at kernel entry, a kernel-uniform branch per slot, scalar loads.
+constexpr uint32_t OB_SLOT_INSTALLED = 1u, OB_SLOT_POSED = 2u, OB_SLOT_SENSE = 4u, OB_SLOT_BODY = 8u;
 struct ObstacleSlot {
     ObstacleArgs A;
     ObstaclePose X;
     uint32_t flags;
 };
 struct ObstacleSet { ObstacleSlot s[SPH_MAX_OBSTACLES]; };
-static_assert(sizeof(ObstacleSet) <= 1024, "the slots are one kernel argument");
+struct ObstacleSetBody {               // the BODY instantiations' argument: the set, and the blocks of its OB_SLOT_BODY slots
+    ObstacleSet set;
+    const ObstacleBodyBlock* blk[SPH_MAX_OBSTACLES];
+};
+static_assert(sizeof(ObstacleSetBody) <= 1024, "the slots are one kernel argument");
+template <bool BODY> using SetArg = std::conditional_t<BODY, ObstacleSetBody, ObstacleSet>;
+__device__ __forceinline__ ObstacleSet& set_of(ObstacleSet& S) { return S; }
+__device__ __forceinline__ ObstacleSet& set_of(ObstacleSetBody& S) { return S.set; }
+
+__device__ __forceinline__ void ob_set_overlay(ObstacleSet&) {}
+__device__ __forceinline__ void ob_set_overlay(ObstacleSetBody& S) {
+#pragma unroll
+    for (int k = 0; k < SPH_MAX_OBSTACLES; k++)
+        if (S.set.s[k].flags & OB_SLOT_BODY) ob_overlay(S.set.s[k].A, S.set.s[k].X, S.blk[k]);      // kernel-uniform
+}
 
 // the guard of one slot at (x, y, z): inside the grid and the brick's minimum under eps + 0.25 s
 template <bool POSED>
@@ -357,15 +405,18 @@ __device__ __forceinline__ bool ob_slot_iterate(const ObstacleSlot& S, const Phy
     return hit;
 }
 
-template <bool SENSE>
+template <bool SENSE, bool BODY = false>
 __global__ __launch_bounds__(OBSTACLE_THREADS) void k_obstacle_push_set(float4* __restrict__ posi, float4* __restrict__ velr,
                                                                         float4* __restrict__ pos_by_index,
                                                                         uint32_t* __restrict__ keys_out,
                                                                         const uint32_t* __restrict__ keyS,
                                                                         uint64_t* __restrict__ mm_mask,
                                                                         uint32_t* __restrict__ mm_tile_cnt, uint32_t lo, uint32_t n,
-                                                                        GridDesc g, Phys ph, ObstacleSet set) {
+                                                                        GridDesc g, Phys ph, SetArg<BODY> seta) {
 #pragma clang fp contract(off)
+    static_assert(!BODY || SENSE, "a body slot is sensing");
+    ob_set_overlay(seta);                              // (nothing for a set without a body)
+    ObstacleSet& set = set_of(seta);
     const uint32_t rel = blockIdx.x * OBSTACLE_THREADS + threadIdx.x;
     const bool active = rel < n;
     const uint32_t slot = lo + (active ? rel : n - 1u);
@@ -481,8 +532,13 @@ __global__ __launch_bounds__(OBSTACLE_THREADS) void k_obstacle_push_set(float4* 
 // both as parameters through a kernel whose bits tests/test_gpu_collider_sums.py pins.
 constexpr uint32_t OBSTACLE_LOAD_THREADS = 256;
 struct ObstacleAbout { float P[3]; };
+struct ObstacleAboutBody { const ObstacleBodyBlock* blk; };      // BODY: the host's P is stale, the block's is that of the push
+__device__ __forceinline__ float about_of(const ObstacleAbout& a, uint32_t k) { return a.P[k]; }
+__device__ __forceinline__ float about_of(const ObstacleAboutBody& a, uint32_t k) { return a.blk->P[k]; }
+template <bool BODY>
 __global__ __launch_bounds__(OBSTACLE_LOAD_THREADS) void k_obstacle_load(const double* __restrict__ rows, const uint32_t* __restrict__ mask,
-                                                                         uint32_t n_waves, double* out, ObstacleAbout about) {
+                                                                         uint32_t n_waves, double* out,
+                                                                         std::conditional_t<BODY, ObstacleAboutBody, ObstacleAbout> about) {
 #pragma clang fp contract(off)
     constexpr uint32_t T = OBSTACLE_LOAD_THREADS, NJ = 6;
     __shared__ double s_acc[T][NJ];
@@ -519,15 +575,119 @@ __global__ __launch_bounds__(OBSTACLE_LOAD_THREADS) void k_obstacle_load(const d
         out[t] = sum;
     }
     if (t == NJ) reinterpret_cast<unsigned long long*>(out)[NJ] += 1ull;     // integrates since the obstacle was installed
-    if (t > NJ && t <= NJ + 3u) reinterpret_cast<float*>(out + NJ + 1u)[t - NJ - 1u] = about.P[t - NJ - 1u];
+    if (t > NJ && t <= NJ + 3u) reinterpret_cast<float*>(out + NJ + 1u)[t - NJ - 1u] = about_of(about, t - NJ - 1u);
+}
+
+// ---- the body step (sph_obstacle_set_body; THE BODY STEP of include/sph_hip.h) ---------------------------------------------------
+// One thread, once per integrate and body slot, behind that slot's k_obstacle_load, whose J and L it reads: the block moves on
+// by dt.  Float64 with each operation rounded; the division and the square root are the correctly rounded ones, so that
+// tests/obstacle_body_model.py repeats it bit for bit.  It is a kernel of its own and not a tail of k_obstacle_load: that
+// kernel's last sums leave six different threads, and a block-wide wait more would only be the same dependence written
+// differently, in a kernel whose bits tests/test_gpu_obstacle_pose.py pins.
+struct ObstacleBodyArgs {
+    double e[3];           // HINGE: the unit axis
+    uint32_t dof;
+    float mass, inertia[3], accel[3], torque[3], lo[3], hi[3];
+    float damp, dt;
+};
+
+// the nine float64 expressions of rot before their rounding (ob_rot_of below rounds the same expressions)
+__host__ __device__ inline void ob_rot_exact(const double q[4], double R[9]) {
+#pragma clang fp contract(off)
+    const double w = q[0], x = q[1], y = q[2], z = q[3];
+    R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - w * z); R[2] = 2.0 * (x * z + w * y);
+    R[3] = 2.0 * (x * y + w * z); R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - w * x);
+    R[6] = 2.0 * (x * z - w * y); R[7] = 2.0 * (y * z + w * x); R[8] = 1.0 - 2.0 * (x * x + y * y);
+}
+
+__global__ __launch_bounds__(WAVE) void k_obstacle_body(ObstacleBodyBlock* __restrict__ blk, const double* __restrict__ load,
+                                                        ObstacleBodyArgs B) {
+#pragma clang fp contract(off)
+    if (threadIdx.x != 0u) return;
+    ObstacleBodyBlock s = *blk;
+    const float dt = B.dt;
+    const double ddt = (double)dt;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        if (B.dof & (1u << a)) {
+            s.u[a] = (float)(((double)s.u[a] + __ddiv_rn(load[a], (double)B.mass)) + ddt * (double)B.accel[a]);
+            wall(s.off[a], s.u[a], B.lo[a], B.hi[a], 0.f, B.damp);
+        }
+        s.off[a] = s.off[a] + dt * s.u[a];
+    }
+    const double T0 = load[3] + ddt * (double)B.torque[0], T1 = load[4] + ddt * (double)B.torque[1],
+                 T2 = load[5] + ddt * (double)B.torque[2];
+    const double w0 = (double)s.omega[0], w1 = (double)s.omega[1], w2 = (double)s.omega[2];
+    if (B.dof & SPH_BODY_HINGE) {
+        const double e0 = B.e[0], e1 = B.e[1], e2 = B.e[2];
+        const double sc = ((w0 * e0 + w1 * e1) + w2 * e2) + __ddiv_rn((T0 * e0 + T1 * e1) + T2 * e2, (double)B.inertia[0]);
+        s.omega[0] = (float)(sc * e0); s.omega[1] = (float)(sc * e1); s.omega[2] = (float)(sc * e2);
+    } else if (B.dof & SPH_BODY_SPIN) {
+        double R[9];
+        ob_rot_exact(s.quat, R);
+        const double I0 = (double)B.inertia[0], I1 = (double)B.inertia[1], I2 = (double)B.inertia[2];
+        const double b0 = (R[0] * w0 + R[3] * w1) + R[6] * w2, b1 = (R[1] * w0 + R[4] * w1) + R[7] * w2,
+                     b2 = (R[2] * w0 + R[5] * w1) + R[8] * w2;
+        const double t0 = (R[0] * T0 + R[3] * T1) + R[6] * T2, t1 = (R[1] * T0 + R[4] * T1) + R[7] * T2,
+                     t2 = (R[2] * T0 + R[5] * T1) + R[8] * T2;
+        const double h0 = I0 * b0, h1 = I1 * b1, h2 = I2 * b2;
+        const double g0 = b1 * h2 - b2 * h1, g1 = b2 * h0 - b0 * h2, g2 = b0 * h1 - b1 * h0;
+        const double n0 = b0 + __ddiv_rn(t0 - ddt * g0, I0), n1 = b1 + __ddiv_rn(t1 - ddt * g1, I1),
+                     n2 = b2 + __ddiv_rn(t2 - ddt * g2, I2);
+        s.omega[0] = (float)((R[0] * n0 + R[1] * n1) + R[2] * n2);
+        s.omega[1] = (float)((R[3] * n0 + R[4] * n1) + R[5] * n2);
+        s.omega[2] = (float)((R[6] * n0 + R[7] * n1) + R[8] * n2);
+    }
+    {                                                   // the Cayley step of THE POSE, as advance_obstacle writes it
+        const double w = s.quat[0], x = s.quat[1], y = s.quat[2], z = s.quat[3];
+        const double h = 0.5 * ddt;
+        const double a0 = h * (double)s.omega[0], a1 = h * (double)s.omega[1], a2 = h * (double)s.omega[2];
+        const double q[4] = {((w - a0 * x) - a1 * y) - a2 * z, ((x + a0 * w) + a1 * z) - a2 * y, ((y + a1 * w) + a2 * x) - a0 * z,
+                             ((z + a2 * w) + a0 * y) - a1 * x};
+        const double n2 = ((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3];
+        if (n2 > 0.0 && n2 < (double)INFINITY) {        // (otherwise the pose stays, as on the host)
+            const double len = __dsqrt_rn(n2);
+#pragma unroll
+            for (int k = 0; k < 4; k++) s.quat[k] = __ddiv_rn(q[k], len);
+        }
+    }
+    double R[9];
+    ob_rot_exact(s.quat, R);
+#pragma unroll
+    for (int k = 0; k < 9; k++) s.rot[k] = (float)R[k];
+#pragma unroll
+    for (int k = 0; k < 3; k++) s.P[k] = s.pivot[k] + s.off[k];
+    *blk = s;
+}
+
+// What the host writes into the block: the values travel by value (k_spheres_install of sph_pairs.hip is the pattern), so no
+// host buffer has to outlive the call and the host does not wait.  P follows from whatever pivot and off the block then holds.
+constexpr uint32_t OB_PUT_OFF = 1u, OB_PUT_U = 2u, OB_PUT_POSE = 4u;
+__global__ __launch_bounds__(WAVE) void k_obstacle_body_put(ObstacleBodyBlock* __restrict__ blk, ObstacleBodyBlock v, uint32_t what) {
+#pragma clang fp contract(off)
+    if (threadIdx.x != 0u) return;
+    ObstacleBodyBlock s = *blk;
+    for (int k = 0; k < 3; k++) {
+        if (what & OB_PUT_OFF) s.off[k] = v.off[k];
+        if (what & OB_PUT_U) s.u[k] = v.u[k];
+        if (what & OB_PUT_POSE) { s.pivot[k] = v.pivot[k]; s.omega[k] = v.omega[k]; }
+    }
+    if (what & OB_PUT_POSE) {
+        for (int k = 0; k < 4; k++) s.quat[k] = v.quat[k];
+        for (int k = 0; k < 9; k++) s.rot[k] = v.rot[k];
+    }
+    for (int k = 0; k < 3; k++) s.P[k] = s.pivot[k] + s.off[k];
+    *blk = s;
 }
 
 // ---- the sample rule for caller points ----------------------------------------------------------------------------------------
 // POSED: x is a world point, the normal comes back in world axes, by the push's arithmetic
-template <bool POSED>
+template <bool POSED, bool BODY = false>
 __global__ __launch_bounds__(OBSTACLE_THREADS) void k_obstacle_sample(const float* __restrict__ pos, uint32_t n, ObstacleArgs A,
                                                                       float* __restrict__ phi_out, float* __restrict__ nrm_out,
-                                                                      uint8_t* __restrict__ in_out, ObstaclePose X) {
+                                                                      uint8_t* __restrict__ in_out, PoseArg<BODY> Xa) {
+    ObstaclePose& X = pose_of(Xa);
+    if constexpr (BODY) ob_overlay(A, X, block_of(Xa));
     const uint32_t t = blockIdx.x * OBSTACLE_THREADS + threadIdx.x;
     if (t >= n) return;
     uint32_t ci[3];
@@ -627,12 +787,14 @@ __device__ __forceinline__ bool solid_march_slot(const ObstacleSlot& S, bool ope
 // takes the solid's RGBA, id and depth, every other pixel is left alone.  Else (sph_render_surface): the nearest hit of every
 // pixel -- depth (+inf: none), slot, eye-space normal -- goes to the so_ planes, and k_surface_shade composes.
 // `set` holds the DRAWN slots only (flags 0 elsewhere).
-template <bool DIRECT>
-__global__ __launch_bounds__(SOLID_THREADS) void k_solid_march(SolidCam C, SolidLooks K, ObstacleSet set, uint32_t* __restrict__ rgba,
+template <bool DIRECT, bool BODY = false>
+__global__ __launch_bounds__(SOLID_THREADS) void k_solid_march(SolidCam C, SolidLooks K, SetArg<BODY> seta, uint32_t* __restrict__ rgba,
                                                                uint32_t* __restrict__ id, float* __restrict__ depth,
                                                                float* __restrict__ so_depth, uint32_t* __restrict__ so_slot,
                                                                float* __restrict__ so_normal) {
 #pragma clang fp contract(off)
+    ob_set_overlay(seta);                              // a drawn BODY slot is where its block says (sph_obstacle_set_body)
+    ObstacleSet& set = set_of(seta);
     const uint32_t wave = threadIdx.x >> 6, l = threadIdx.x & 63u;
     const uint32_t i = blockIdx.x * SOLID_TILE + (wave & 1u) * 8u + (l & 7u);
     const uint32_t j = blockIdx.y * SOLID_TILE + (wave >> 1) * 8u + (l >> 3);
@@ -802,9 +964,62 @@ static ObstacleSet obstacle_set(const sph_ctx* c) {
         if (!o.installed()) continue;
         S.s[k].A = obstacle_args(o);
         S.s[k].X = obstacle_pose(o);
-        S.s[k].flags = OB_SLOT_INSTALLED | (o.posed ? OB_SLOT_POSED : 0u) | (o.sense && o.load ? OB_SLOT_SENSE : 0u);
+        S.s[k].flags = OB_SLOT_INSTALLED | (o.posed ? OB_SLOT_POSED : 0u) | (o.sense && o.load ? OB_SLOT_SENSE : 0u) |
+                       (o.body ? OB_SLOT_BODY : 0u);
     }
     return S;
+}
+
+// the BODY instantiations' argument of the slots S (flags as the caller left them); false: no slot of S has a body
+static bool obstacle_set_body(const sph_ctx* c, const ObstacleSet& S, ObstacleSetBody* out) {
+    bool any = false;
+    out->set = S;
+    for (uint32_t k = 0; k < (uint32_t)SPH_MAX_OBSTACLES; k++) {
+        const bool b = (S.s[k].flags & OB_SLOT_BODY) != 0u;
+        out->blk[k] = b ? c->ob[k].blk : nullptr;
+        any = any || b;
+    }
+    return any;
+}
+
+// ---- the body's host side: the block is the state, the host's copies are stale while `body` -------------------------------------
+static ObstacleBodyArgs body_args(const sph_ctx* c, const Obstacle& o, float dt) {
+    ObstacleBodyArgs B{};
+    const sph_obstacle_body& b = o.bd;
+    B.dof = b.dof;
+    B.mass = b.mass;
+    for (int k = 0; k < 3; k++) {
+        B.e[k] = o.axis[k];
+        B.inertia[k] = b.inertia[k]; B.accel[k] = b.accel[k]; B.torque[k] = b.torque[k]; B.lo[k] = b.lo[k]; B.hi[k] = b.hi[k];
+    }
+    B.damp = c->phys.wall_damping;
+    B.dt = dt;
+    return B;
+}
+
+// the block a kinematic slot would be: the host's state, rot and P as obstacle_pose makes them for the next launch
+static ObstacleBodyBlock body_block_of(const Obstacle& o) {
+    ObstacleBodyBlock v{};
+    const ObstaclePose X = obstacle_pose(o);
+    for (int k = 0; k < 4; k++) v.quat[k] = o.quat[k];
+    for (int k = 0; k < 3; k++) { v.off[k] = o.off[k]; v.u[k] = o.vel[k]; v.pivot[k] = X.pivot[k]; v.omega[k] = X.omega[k]; v.P[k] = X.P[k]; }
+    for (int k = 0; k < 9; k++) v.rot[k] = X.rot[k];
+    return v;
+}
+
+static int body_put(sph_ctx* c, const Obstacle& o, const ObstacleBodyBlock& v, uint32_t what) {
+    SPH_HIP(hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_obstacle_body_put, dim3(1), dim3(WAVE), 0, c->stream, o.blk, v, what);
+    SPH_HIP(hipGetLastError());
+    return SPH_OK;
+}
+
+// synchronises: the block as the last queued step left it
+static int body_fetch(const sph_ctx* c, const Obstacle& o, ObstacleBodyBlock* out) {
+    SPH_HIP(hipSetDevice(c->device));
+    SPH_HIP(hipMemcpyAsync(out, o.blk, sizeof(*out), hipMemcpyDeviceToHost, c->stream));
+    SPH_HIP(hipStreamSynchronize(c->stream));
+    return SPH_OK;
 }
 
 bool solids_drawn(const sph_ctx* c) {
@@ -820,7 +1035,15 @@ int launch_solid_march(sph_ctx* c, const SolidCam& cam, const SolidLooks& looks,
     for (uint32_t k = 0; k < (uint32_t)SPH_MAX_OBSTACLES; k++)
         if (c->rd_solid_style.slot[k].draw == 0) S.s[k].flags = 0u;
     const dim3 grid(ceil_div(cam.width, SOLID_TILE), ceil_div(cam.height, SOLID_TILE));
-    if (so_depth)
+    ObstacleSetBody SB;
+    if (obstacle_set_body(c, S, &SB)) {              // a drawn slot has a body: the instantiations that read the blocks
+        if (so_depth)
+            hipLaunchKernelGGL((k_solid_march<false, true>), grid, dim3(SOLID_THREADS), 0, c->stream, cam, looks, SB, rgba, id, depth,
+                               so_depth, so_slot, so_normal);
+        else
+            hipLaunchKernelGGL((k_solid_march<true, true>), grid, dim3(SOLID_THREADS), 0, c->stream, cam, looks, SB, rgba, id, depth,
+                               so_depth, so_slot, so_normal);
+    } else if (so_depth)
         hipLaunchKernelGGL(k_solid_march<false>, grid, dim3(SOLID_THREADS), 0, c->stream, cam, looks, S, rgba, id, depth, so_depth,
                            so_slot, so_normal);
     else
@@ -846,7 +1069,11 @@ int launch_obstacle_push(sph_ctx* c, bool fused, bool mark) {
         fused && mark ? c->mm_mask : nullptr, c->mm_tile_cnt, c->own_off, c->n
     if (others) {
         const ObstacleSet S = obstacle_set(c);
-        if (any_sense)
+        ObstacleSetBody SB;
+        if (obstacle_set_body(c, S, &SB))              // (a body slot senses: sph_obstacle_set_body)
+            hipLaunchKernelGGL((k_obstacle_push_set<true, true>), dim3(ceil_div(c->n, OBSTACLE_THREADS)), dim3(OBSTACLE_THREADS), 0,
+                               c->stream, SPH_PUSH_ARGS, c->grid, c->phys, SB);
+        else if (any_sense)
             hipLaunchKernelGGL(k_obstacle_push_set<true>, dim3(ceil_div(c->n, OBSTACLE_THREADS)), dim3(OBSTACLE_THREADS), 0, c->stream,
                                SPH_PUSH_ARGS, c->grid, c->phys, S);
         else
@@ -859,7 +1086,10 @@ int launch_obstacle_push(sph_ctx* c, bool fused, bool mark) {
 #define SPH_LAUNCH_PUSH(P, S)                                                                                                    \
     hipLaunchKernelGGL((k_obstacle_push<P, S>), dim3(ceil_div(c->n, OBSTACLE_THREADS)), dim3(OBSTACLE_THREADS), 0, c->stream,      \
                        SPH_PUSH_ARGS, obstacle_args(o), c->grid, c->phys, obstacle_pose(o))
-    if (o.posed) { if (any_sense) SPH_LAUNCH_PUSH(true, true); else SPH_LAUNCH_PUSH(true, false); }
+    if (o.body)                                         // (posed and sensing, its buffers there: sph_obstacle_set_body)
+        hipLaunchKernelGGL((k_obstacle_push<true, true, true>), dim3(ceil_div(c->n, OBSTACLE_THREADS)), dim3(OBSTACLE_THREADS), 0,
+                           c->stream, SPH_PUSH_ARGS, obstacle_args(o), c->grid, c->phys, ObstaclePoseBody{obstacle_pose(o), o.blk});
+    else if (o.posed) { if (any_sense) SPH_LAUNCH_PUSH(true, true); else SPH_LAUNCH_PUSH(true, false); }
     else { if (any_sense) SPH_LAUNCH_PUSH(false, true); else SPH_LAUNCH_PUSH(false, false); }
 #undef SPH_LAUNCH_PUSH
 #undef SPH_PUSH_ARGS
@@ -874,9 +1104,17 @@ int advance_obstacle(sph_ctx* c, float dt) {
 #pragma clang fp contract(off)
     for (Obstacle& o : c->ob) {
         if (!o.installed()) continue;
+        if (o.body) {                                   // the load about the block's P, then the body step: all on the device
+            hipLaunchKernelGGL(k_obstacle_load<true>, dim3(1), dim3(OBSTACLE_LOAD_THREADS), 0, c->stream, o.rows, o.wmask,
+                               ceil_div(c->n, (uint32_t)WAVE), o.load, ObstacleAboutBody{o.blk});
+            SPH_HIP(hipGetLastError());
+            hipLaunchKernelGGL(k_obstacle_body, dim3(1), dim3(WAVE), 0, c->stream, o.blk, o.load, body_args(c, o, dt));
+            SPH_HIP(hipGetLastError());
+            continue;
+        }
         if (o.sense && o.load) {
             const ObstaclePose X = obstacle_pose(o);
-            hipLaunchKernelGGL(k_obstacle_load, dim3(1), dim3(OBSTACLE_LOAD_THREADS), 0, c->stream, o.rows, o.wmask,
+            hipLaunchKernelGGL(k_obstacle_load<false>, dim3(1), dim3(OBSTACLE_LOAD_THREADS), 0, c->stream, o.rows, o.wmask,
                                ceil_div(c->n, (uint32_t)WAVE), o.load, ObstacleAbout{{X.P[0], X.P[1], X.P[2]}});
             SPH_HIP(hipGetLastError());
         }
@@ -1096,7 +1334,8 @@ int sph_obstacle_clear(sph_ctx* c) {
     }
     for (int k = 0; k < 3; k++) o.off[k] = o.vel[k] = 0.f;
     pose_reset(o);
-    if (o.load) {                                          // (the sensor's switch stays; its sums and the integrate count start again)
+    o.body = false;                                        // (the block stays for the slot's next body, as the sensor's buffers do)
+    if (o.load) {                                       // (the sensor's switch stays; its sums and the integrate count start again)
         SPH_HIP(hipSetDevice(c->device));
         SPH_HIP(hipMemsetAsync(o.load, 0, OBSTACLE_LOAD_WORDS * sizeof(double), c->stream));
     }
@@ -1106,6 +1345,8 @@ int sph_obstacle_clear(sph_ctx* c) {
 int sph_obstacle_set_pose(sph_ctx* c, const sph_obstacle_pose* pose) {
     if (int e = obstacle_ctx(c, "sph_obstacle_set_pose")) return e;
     Obstacle& o = selected_obstacle(c);
+    SPH_REQUIRE(pose || !o.body, SPH_E_STATE, "sph_obstacle_set_pose(NULL): the slot has a body, which needs a pose "
+                "(sph_obstacle_set_body(NULL) first)");
     if (!pose) { pose_reset(o); return SPH_OK; }
     const sph_obstacle_pose p = *pose;
     for (int k = 0; k < 3; k++)
@@ -1114,6 +1355,13 @@ int sph_obstacle_set_pose(sph_ctx* c, const sph_obstacle_pose* pose) {
     const double q[4] = {(double)p.quat[0], (double)p.quat[1], (double)p.quat[2], (double)p.quat[3]};
     double unit[4];
     SPH_REQUIRE(ob_quat_unit(q, unit), SPH_E_INVALID, "obstacle pose: the quaternion's squared norm is 0 or not finite");
+    if (o.body) {                                          // the block is the state: written on the stream, no host wait
+        ObstacleBodyBlock v{};
+        for (int k = 0; k < 3; k++) { v.pivot[k] = p.pivot[k]; v.omega[k] = p.omega[k]; }
+        for (int k = 0; k < 4; k++) v.quat[k] = unit[k];
+        ob_rot_of(unit, v.rot);
+        return body_put(c, o, v, OB_PUT_POSE);
+    }
     o.posed = true;
     for (int k = 0; k < 3; k++) { o.pivot[k] = p.pivot[k]; o.omega[k] = p.omega[k]; }
     for (int k = 0; k < 4; k++) o.quat[k] = unit[k];
@@ -1123,6 +1371,18 @@ int sph_obstacle_set_pose(sph_ctx* c, const sph_obstacle_pose* pose) {
 int sph_obstacle_get_pose(const sph_ctx* c, int* posed, float pivot[3], double quat[4], float omega[3], float rot[9]) {
     SPH_REQUIRE(c, SPH_E_INVALID, "null context");
     const Obstacle& o = selected_obstacle(c);
+    if (o.body) {                                          // the host's copy is stale: synchronises
+        ObstacleBodyBlock b;
+        if (int e = body_fetch(c, o, &b)) return e;
+        if (posed) *posed = 1;
+        for (int k = 0; k < 3; k++) {
+            if (pivot) pivot[k] = b.pivot[k];
+            if (omega) omega[k] = b.omega[k];
+        }
+        if (quat) for (int k = 0; k < 4; k++) quat[k] = b.quat[k];
+        if (rot) for (int k = 0; k < 9; k++) rot[k] = b.rot[k];
+        return SPH_OK;
+    }
     if (posed) *posed = o.posed ? 1 : 0;
     for (int k = 0; k < 3; k++) {
         if (pivot) pivot[k] = o.pivot[k];
@@ -1136,6 +1396,8 @@ int sph_obstacle_get_pose(const sph_ctx* c, int* posed, float pivot[3], double q
 int sph_obstacle_set_sensor(sph_ctx* c, int on) {
     if (int e = obstacle_ctx(c, "sph_obstacle_set_sensor")) return e;
     Obstacle& o = selected_obstacle(c);
+    SPH_REQUIRE(on || !o.body, SPH_E_STATE, "sph_obstacle_set_sensor(0): the slot has a body, which the load drives "
+                "(sph_obstacle_set_body(NULL) first)");
     if (on && !o.load) {
         SPH_HIP(hipSetDevice(c->device));
         if (int rc = sensor_buffers_alloc(c, o)) return rc;
@@ -1162,12 +1424,85 @@ int sph_obstacle_get_load(sph_ctx* c, double J[3], double L[3], float about[3], 
     return SPH_OK;
 }
 
+int sph_obstacle_set_body(sph_ctx* c, const sph_obstacle_body* body) {
+    if (int e = obstacle_ctx(c, "sph_obstacle_set_body")) return e;
+    Obstacle& o = selected_obstacle(c);
+    if (!body) {                                           // the slot goes on kinematic from where it is
+        if (!o.body) return SPH_OK;
+        ObstacleBodyBlock b;
+        if (int e = body_fetch(c, o, &b)) return e;
+        for (int k = 0; k < 3; k++) { o.off[k] = b.off[k]; o.vel[k] = b.u[k]; o.pivot[k] = b.pivot[k]; o.omega[k] = b.omega[k]; }
+        for (int k = 0; k < 4; k++) o.quat[k] = b.quat[k];
+        o.body = false;
+        return SPH_OK;
+    }
+    const sph_obstacle_body b = *body;
+    constexpr uint32_t FREE = SPH_BODY_FREE_X | SPH_BODY_FREE_Y | SPH_BODY_FREE_Z;
+    SPH_REQUIRE((b.dof & ~(FREE | SPH_BODY_SPIN | SPH_BODY_HINGE)) == 0u, SPH_E_INVALID, "obstacle body: dof %u has unknown bits", b.dof);
+    SPH_REQUIRE(!((b.dof & SPH_BODY_SPIN) && (b.dof & SPH_BODY_HINGE)), SPH_E_INVALID, "obstacle body: SPIN and HINGE exclude each other");
+    if (b.dof & FREE)
+        SPH_REQUIRE(std::isfinite(b.mass) && b.mass > 0.f, SPH_E_INVALID, "obstacle body: mass %g is not a positive finite number",
+                    (double)b.mass);
+    for (int k = 0; k < 3; k++) {
+        SPH_REQUIRE(std::isfinite(b.accel[k]) && std::isfinite(b.torque[k]), SPH_E_INVALID, "obstacle body: accel or torque is not finite");
+        if (b.dof & (1u << k))
+            SPH_REQUIRE(std::isfinite(b.lo[k]) && std::isfinite(b.hi[k]) && b.lo[k] <= b.hi[k], SPH_E_INVALID,
+                        "obstacle body: the offset's bounds on axis %d are [%g, %g]", k, (double)b.lo[k], (double)b.hi[k]);
+        if ((b.dof & SPH_BODY_SPIN) || ((b.dof & SPH_BODY_HINGE) && k == 0))
+            SPH_REQUIRE(std::isfinite(b.inertia[k]) && b.inertia[k] > 0.f, SPH_E_INVALID,
+                        "obstacle body: moment %d is %g, not a positive finite number", k, (double)b.inertia[k]);
+    }
+    double axis[3] = {0.0, 0.0, 0.0};
+    if (b.dof & SPH_BODY_HINGE) {
+#pragma clang fp contract(off)
+        const double x = (double)b.axis[0], y = (double)b.axis[1], z = (double)b.axis[2];
+        const double n2 = (x * x + y * y) + z * z;
+        SPH_REQUIRE(std::isfinite(n2) && n2 > 0.0, SPH_E_INVALID, "obstacle body: the hinge's axis is zero or not finite");
+        const double len = std::sqrt(n2);
+        axis[0] = x / len; axis[1] = y / len; axis[2] = z / len;
+    }
+    SPH_REQUIRE(o.posed, SPH_E_STATE, "sph_obstacle_set_body: the slot has no pose (sph_obstacle_set_pose first; the identity "
+                "quaternion will do)");
+    SPH_HIP(hipSetDevice(c->device));
+    const bool had_load = o.load != nullptr;
+    if (!had_load)
+        if (int rc = sensor_buffers_alloc(c, o)) return rc;
+    if (!o.blk) {
+        if (int rc = c->mem.alloc(&o.blk, 1, true)) {
+            if (!had_load) { c->mem.release(&o.load); c->mem.release(&o.wmask); c->mem.release(&o.rows); }
+            return rc;
+        }
+    }
+    if (!o.body) {                                         // the state moves to the device: what a kinematic slot would launch with
+        if (int rc = body_put(c, o, body_block_of(o), OB_PUT_OFF | OB_PUT_U | OB_PUT_POSE)) return rc;
+    }
+    o.bd = b;
+    for (int k = 0; k < 3; k++) o.axis[k] = axis[k];
+    o.sense = true;
+    o.body = true;
+    return SPH_OK;
+}
+
+int sph_obstacle_get_body(const sph_ctx* c, int* has_body, sph_obstacle_body* out) {
+    SPH_REQUIRE(c, SPH_E_INVALID, "null context");
+    const Obstacle& o = selected_obstacle(c);
+    if (has_body) *has_body = o.body ? 1 : 0;
+    if (out) *out = o.body ? o.bd : sph_obstacle_body{};
+    return SPH_OK;
+}
+
 int sph_obstacle_set_motion(sph_ctx* c, const float offset[3], const float velocity[3]) {
     if (int e = obstacle_ctx(c, "sph_obstacle_set_motion")) return e;
     Obstacle& o = selected_obstacle(c);
     for (int k = 0; k < 3; k++)
         SPH_REQUIRE((!offset || std::isfinite(offset[k])) && (!velocity || std::isfinite(velocity[k])), SPH_E_INVALID,
                     "obstacle motion: offset or velocity is not finite");
+    if (o.body) {                                          // the block is the state: written on the stream, no host wait
+        if (!offset && !velocity) return SPH_OK;
+        ObstacleBodyBlock v{};
+        for (int k = 0; k < 3; k++) { v.off[k] = offset ? offset[k] : 0.f; v.u[k] = velocity ? velocity[k] : 0.f; }
+        return body_put(c, o, v, (offset ? OB_PUT_OFF : 0u) | (velocity ? OB_PUT_U : 0u));
+    }
     for (int k = 0; k < 3; k++) {
         if (offset) o.off[k] = offset[k];
         if (velocity) o.vel[k] = velocity[k];
@@ -1179,6 +1514,15 @@ int sph_obstacle_get(const sph_ctx* c, sph_obstacle_grid* grid, float offset[3],
     SPH_REQUIRE(c, SPH_E_INVALID, "null context");
     const Obstacle& o = selected_obstacle(c);
     if (grid) *grid = o.grid;
+    if (o.body && (offset || velocity)) {                  // the host's copy is stale: synchronises
+        ObstacleBodyBlock b;
+        if (int e = body_fetch(c, o, &b)) return e;
+        for (int k = 0; k < 3; k++) {
+            if (offset) offset[k] = b.off[k];
+            if (velocity) velocity[k] = b.u[k];
+        }
+        return SPH_OK;
+    }
     for (int k = 0; k < 3; k++) {
         if (offset) offset[k] = o.off[k];
         if (velocity) velocity[k] = o.vel[k];
@@ -1214,7 +1558,10 @@ int sph_obstacle_sample(sph_ctx* c, uint32_t n, const float* pos_xyz, float* phi
     if (!rc) {
         hip(hipMemcpyAsync(d_pos, pos_xyz, (size_t)n * 12, hipMemcpyHostToDevice, c->stream), "copy of the points");
         if (!rc) {
-            if (o.posed)
+            if (o.body)
+                hipLaunchKernelGGL((k_obstacle_sample<true, true>), dim3(ceil_div(n, OBSTACLE_THREADS)), dim3(OBSTACLE_THREADS), 0,
+                                   c->stream, d_pos, n, obstacle_args(o), d_phi, d_nrm, d_in, ObstaclePoseBody{obstacle_pose(o), o.blk});
+            else if (o.posed)
                 hipLaunchKernelGGL(k_obstacle_sample<true>, dim3(ceil_div(n, OBSTACLE_THREADS)), dim3(OBSTACLE_THREADS), 0, c->stream,
                                    d_pos, n, obstacle_args(o), d_phi, d_nrm, d_in, obstacle_pose(o));
             else

@@ -185,6 +185,13 @@ public:
     // pivot's place in the world that the obstacle took from the fluid in the last update; divide by the time step.
     void senseObstacleLoad(bool on);
     void getObstacleLoad(double J[3], double L[3]);
+    // A free body (sph_obstacle_set_body): from then on the fluid drives the motions in body.dof on the device, inside update(),
+    // with no host wait.  The selected obstacle needs a pose (setObstaclePose; the identity quaternion will do).
+    // getObstacleState reads where a body (or a kinematic obstacle) is now; any pointer may be nullptr.  clearObstacleBody: the
+    // obstacle goes on kinematic from where it is.
+    void setObstacleBody(const sph_obstacle_body& body);
+    void clearObstacleBody();
+    void getObstacleState(float offset[3], float velocity[3], double quat[4], float omega[3]);
     // Several obstacles (sph_obstacle_select): the context holds SPH_MAX_OBSTACLES slots, and every obstacle member above
     // addresses the selected one (0 by default; clearObstacles() clears the selected slot).  They act in ascending slot order.
     void selectObstacle(uint slot);

@@ -33,7 +33,8 @@
  *                  sph_obstacle_lattice sph_obstacle_build sph_obstacle_set_grid sph_obstacle_clear sph_obstacle_set_motion
  *                  sph_obstacle_get sph_obstacle_read sph_obstacle_sample sph_obstacle_build_mesh sph_obstacle_build_mesh_dev
  *                  sph_obstacle_build_obj sph_obstacle_set_pose sph_obstacle_get_pose sph_obstacle_set_sensor sph_obstacle_get_load
- *                  sph_obstacle_select sph_obstacle_selected sph_obstacle_installed sph_obstacle_clear_all |
+ *                  sph_obstacle_select sph_obstacle_selected sph_obstacle_installed sph_obstacle_clear_all
+ *                  sph_obstacle_set_body sph_obstacle_get_body |
  *                  sph_camera_look_at sph_render sph_render_read sph_render_image_dev sph_surface_defaults sph_render_surface
  *                  sph_render_surface_read sph_solid_defaults sph_render_set_solids sph_render_get_solids | sph_mesh_defaults sph_mesh_lattice sph_mesh_extract sph_mesh_read sph_mesh_dev
  *                  sph_mesh_save_obj |
@@ -471,7 +472,7 @@ int sph_obstacle_sample(sph_ctx* c, uint32_t n, const float* pos_xyz, float* phi
  *   SPH_E_STATE    a slab context (all four but sph_obstacle_get_pose).
  *   SPH_E_INVALID  a pivot, quaternion or omega that is not finite; a quaternion whose squared norm in double is 0 or not finite.
  * In every refused case nothing has changed and nothing was allocated.  The calls are legal at any stage and write none of the
- * context's step flags.  Out of scope: free rigid bodies with an inertia tensor, slab contexts, snapshots carrying the pose. */
+ * context's step flags.  Out of scope: slab contexts, snapshots carrying the pose (free rigid bodies: THE BODY below). */
 typedef struct sph_obstacle_pose { float pivot[3]; float quat[4]; float omega[3]; } sph_obstacle_pose;
 int sph_obstacle_set_pose(sph_ctx* c, const sph_obstacle_pose* pose);
 /* The ADVANCED pose: *posed 0 = none (then pivot, omega 0 and the identity); rot as the next launch takes it.  Any pointer may be NULL.
@@ -482,6 +483,64 @@ int sph_obstacle_get_pose(const sph_ctx* c, int* posed, float pivot[3], double q
 int sph_obstacle_set_sensor(sph_ctx* c, int on);
 /* J, L, about and steps of the last integrate; any pointer may be NULL.  Synchronises. */
 int sph_obstacle_get_load(sph_ctx* c, double J[3], double L[3], float about[3], uint64_t* steps);
+
+/* ---- free obstacle bodies: the fluid drives a slot's motion, on the device -----------------------------------------------------------
+ * THE BODY (sph_obstacle_set_body; NULL = no body).  A slot with a body has a mass, moments of inertia and a choice `dof` of the
+ * motions the fluid drives: its offset along the FREE axes, its spin about the pivot (SPIN: a free top; HINGE: about one fixed
+ * world axis through the pivot).  While the body is set the slot's state -- off, u, pivot, omega (fp32), quat (float64) and the
+ * derived rot[9] and P[3] of THE POSE -- lives in a block on the device.  The push, sph_obstacle_sample and the solids' march of
+ * sph_render / sph_render_surface read off, u, rot, P, pivot and omega from it at kernel entry and are otherwise the posed,
+ * sensing arithmetic above, operation for operation; the load's `about` is the block's P.  So a water wheel, a valve flap, a
+ * float or a paddle on a rail runs inside sph_step(dt, n) and in the pictures with no host wait.
+ * THE BODY STEP runs once per integrate of an installed body slot, behind that slot's load sum (also without particles: the load
+ * is then zero).  Float64, no contraction, only + - * / sqrt, every product and sum rounded, sums left to right
+ * (tests/obstacle_body_model.py repeats it exactly).  Its inputs are J and L as just summed, and dt:
+ *     per axis a = 0, 1, 2:
+ *         if FREE_a:  u[a] = (float)(((double)u[a] + J[a] / (double)mass) + (double)dt * (double)accel[a])
+ *                     the wall rule of the particles on (off[a], u[a]) with lo[a], hi[a], eps = 0 and wall_damping      (fp32)
+ *         off[a] = off[a] + dt * u[a]                                                   (fp32, as a kinematic slot)
+ *     T[k] = L[k] + (double)dt * (double)torque[k]
+ *     HINGE (e = axis / |axis| in double, w = (double)omega):
+ *         s = ((w0*e0 + w1*e1) + w2*e2) + ((T0*e0 + T1*e1) + T2*e2) / (double)inertia[0]
+ *         omega[k] = (float)(s * e[k])
+ *     SPIN (Rd = the nine float64 expressions of rot BEFORE their rounding, from the current quat; I = (double)inertia):
+ *         wb[k] = (Rd[0][k]*w0 + Rd[1][k]*w1) + Rd[2][k]*w2              Tb likewise from T
+ *         h[k] = I[k] * wb[k]
+ *         g = wb x h,  g[0] = wb1*h2 - wb2*h1 and cyclic
+ *         wb'[k] = wb[k] + (Tb[k] - (double)dt * g[k]) / I[k]
+ *         omega[k] = (float)((Rd[k][0]*wb'0 + Rd[k][1]*wb'1) + Rd[k][2]*wb'2)
+ *     the Cayley step of THE POSE with the new fp32 omega; rot, each entry rounded once; P = pivot + off.
+ * With dof = 0 this is the kinematic slot's advance moved to the device: particles, load and pose equal a kinematic, posed,
+ * sensing slot bit for bit.  L is taken about the P of that push, so THE CALLER places the pivot at the centre of mass (SPIN)
+ * or on the axis (HINGE); gravity (accel) exerts no torque.  lo and hi bound the slot's OFFSET, not its shape.
+ * A body needs a pose (the identity quaternion will do) and switches the slot's sensor on, allocating its buffers as
+ * sph_obstacle_set_sensor does, and -- at the slot's first body -- the block (128 bytes); sph_destroy frees both.  While a body
+ * is set the host's copies are stale: sph_obstacle_get, _get_pose and _sample on that slot synchronise and read the block;
+ * sph_obstacle_set_motion and _set_pose write it with a one-wave kernel whose values travel by value (no host wait), and take
+ * effect at the next integrate.  sph_obstacle_set_body on a slot that has a body replaces the parameters and keeps the state.
+ * sph_obstacle_set_body(NULL) synchronises, and the slot goes on kinematic from where it is (posed, sensing).
+ * sph_obstacle_clear drops the body as it resets the pose; installing another grid keeps it; it advances only while a grid is
+ * installed; snapshots do not carry it.  Both calls address the selected slot, are legal at any stage and write no step flag.
+ *   SPH_E_STATE    a slab context; sph_obstacle_set_body on a slot without a pose; sph_obstacle_set_sensor(0) or
+ *                  sph_obstacle_set_pose(NULL) on a slot that has a body.
+ *   SPH_E_INVALID  a dof with unknown bits or with SPIN and HINGE; a mass that is not finite and > 0 with a FREE bit; a moment
+ *                  (SPIN: all three, HINGE: inertia[0]) that is not finite and > 0; a HINGE axis that is not finite or is zero;
+ *                  accel or torque not finite; lo or hi of a FREE axis not finite, or lo > hi.
+ * In every refused case nothing has changed and nothing was allocated.  Out of scope: bodies colliding with each other or with
+ * the box by their shape, gravity torque, slab contexts, snapshots. */
+enum { SPH_BODY_FREE_X = 1, SPH_BODY_FREE_Y = 2, SPH_BODY_FREE_Z = 4, SPH_BODY_SPIN = 8, SPH_BODY_HINGE = 16 };
+typedef struct sph_obstacle_body {
+    uint32_t dof;       /* which motions the fluid drives; SPIN and HINGE exclude each other; 0 is legal (kinematic, on the device) */
+    float mass;         /* > 0, finite, if any FREE bit */
+    float inertia[3];   /* SPIN: principal moments about the pivot along the BODY axes, each > 0; HINGE: inertia[0] about the axis */
+    float axis[3];      /* HINGE: a fixed world axis through the pivot, finite and non-zero; normalised on the host in double */
+    float accel[3];     /* world; acts on the FREE axes (gravity) */
+    float torque[3];    /* world; a constant external torque (a brake, a motor); HINGE uses its component along the axis */
+    float lo[3], hi[3]; /* bounds of the slot's OFFSET on the FREE axes, lo <= hi: the wall rule with eps = 0 */
+} sph_obstacle_body;
+int sph_obstacle_set_body(sph_ctx* c, const sph_obstacle_body* body);
+/* *has_body 0 = none (then *out is zeros); the parameters as they were set.  Either pointer may be NULL. */
+int sph_obstacle_get_body(const sph_ctx* c, int* has_body, sph_obstacle_body* out);
 
 /* ---- several obstacles per context: a vessel and a wheel, one push pass ------------------------------------------------------------
  * A whole-domain context holds SPH_MAX_OBSTACLES obstacle SLOTS.  Each slot is what "the obstacle" is in the sections around
